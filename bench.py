@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the tree-expansion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--queries Q] [--config 2|3|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--queries Q] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what takes runs of its own: the
+CPU baseline on query 0 (checked against the device), the batched leg and the plan() wall-time leg (config 2, one GPU).
+`--dump-outputs DIR` writes the trees of the last timed step as DIR/<name>.npy (dump_outputs, below).
 
 A "step" is one pass of the hot path over one batch of queries that is already resident in HBM
 (grid, packed sample streams): re-arm the trees, run the expansion kernel to completion
@@ -45,6 +49,9 @@ CONFIGS = {
     5: dict(name="Dubins-RRT* 2048x2048 n=100000 r_rewire=64 rho=8 64 headings (256 independent queries per GPU, one CU each)", alg=4, grid=2048,
             n=100000, r_rewire=64, r_goal=None, queries=256, rho=8.0, nh=64, grid_seed=3),
 }
+
+DUMP_LIMIT_BYTES = 63_000_000  # --dump-outputs writes at most this much: under 64 MB with room for the .npy headers
+DUMP_SAMPLE_SEED = 2024      # the fixed sample of queries when all of them do not fit
 
 DUBINS_F64_OPS = 955  # f64 VALU instructions of one dub_shortest() in the gfx950 ISA (static count over all six words, hipcc -O3; 2 043 instructions in all, 12 divisions)
 F64_VALU_PEAK_TFLOPS = 78.6  # MI355X vector f64 (MI355X_MICROARCH.md)
@@ -196,6 +203,51 @@ def check_against_oracle(tag, r, ro, st):
         raise SystemExit(f"bench: {tag}: device result {got} differs from the CPU oracle {want}")
 
 
+def dump_row_bytes(headings):
+    """Bytes of one tree row in the dump: pts (2 x f32), parent (f64), vcost (f64), heading (f32, Dubins only)."""
+    return 2 * 4 + 8 + 8 + (4 if headings else 0)
+
+
+def dump_selection(n_queries, rows, headings, limit=DUMP_LIMIT_BYTES):
+    """Global query indices that --dump-outputs writes: all of them when they fit in `limit` bytes, otherwise a fixed seeded
+    sample (sorted) of as many as fit.  The same for every run with the same arguments."""
+    per_query = rows * dump_row_bytes(headings) + 5 * 8  # tree rows + query_index / status / j / vgoal / found
+    k = min(n_queries, limit // per_query)
+    if k < 1:
+        raise SystemExit(f"bench: --dump-outputs: one query's tree ({per_query} bytes) exceeds the {limit}-byte limit")
+    if k == n_queries:
+        return np.arange(n_queries)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_queries, size=k, replace=False))
+
+
+def dump_outputs(out_dir, qids, results, rows, headings):
+    """What the timed path hands its caller, for the queries `qids` (results[i] belongs to qids[i]): per query the tree --
+    pts [rows, 2], parent [rows], vcost [rows] and, for Dubins, heading [rows] (the first j + found rows live, the rest -1) --
+    and the scalars status / j / vgoal / found.  float32 for coordinates and headings, float64 for the rest."""
+    k = len(qids)
+    pts = np.full((k, rows, 2), -1, dtype=np.float32)
+    parent = np.full((k, rows), -1, dtype=np.float64)
+    vcost = np.full((k, rows), -1, dtype=np.float64)
+    heading = np.full((k, rows), -1, dtype=np.float32) if headings else None
+    scal = np.zeros((4, k), dtype=np.float64)
+    for i, r in enumerate(results):
+        live = r.j + (1 if r.found else 0)
+        pts[i, :live] = r.pts[:live]
+        parent[i, :live] = r.parent[:live]
+        vcost[i, :live] = r.vcost[:live]
+        if headings:
+            heading[i, :live] = r.head[:live]
+        scal[:, i] = (r.status, r.j, r.vgoal, r.found)
+    arrays = dict(query_index=np.asarray(qids, dtype=np.float64), status=scal[0], j=scal[1], vgoal=scal[2], found=scal[3],
+                  pts=pts, parent=parent, vcost=vcost)
+    if headings:
+        arrays["heading"] = heading
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -216,7 +268,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batched", action="store_true", help="skip the informational batched leg (configs[3] share of one GPU)")
     ap.add_argument("--rewire-leg", action="store_true", help="add an informational leg: query 0 with the opt-in true rewire (not the reference's behaviour)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the CPU baseline, the batched leg and the plan() wall-time leg "
+                         "(each still subject to its --no-* switch); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the trees of the last step as DIR/<name>.npy (float32 / float64, under 64 MB: "
+                         "a fixed seeded sample of the queries when all do not fit)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # called plainly: be the launcher (nothing GPU-related has been imported or called in this process)
@@ -362,6 +422,17 @@ def main():
     else:
         nodes_total, iters_total, nbad = float(nodes_local), float(iters_local), len(bad)
 
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's trees: this rank's batch, or with a communicator the gathered slabs of every rank (global query
+        # g = rank + world * slot; the slabs carry no headings)
+        headings = dubins and not use_comm
+        qids = dump_selection(Q * world, n + 1, headings)
+        if use_comm:
+            got = [batch.gather_fetch(int(g) % world, int(g) // world) for g in qids]
+        else:
+            got = [batch.get_result(int(g)) for g in qids]
+        dump_outputs(args.dump_outputs, qids, got, n + 1, headings)
+
     if rank == 0:
         kern_avg_ms = kern_ms / args.steps
         team, fallbacks = batch.team()
@@ -410,14 +481,14 @@ def main():
                                                  "dubins_word_evaluations_model": int(ndub), "dubins_word_evaluations_made": int(made),
                                                  "f64_ops_per_evaluation": DUBINS_F64_OPS,
                                                  "note": "f64 instructions per evaluation: static count in the compiled ISA of dub_shortest (all branches), not a counter pass; a lane-level figure -- most lanes of a word pass are idle, the SIMD is busy: see bound_observed"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if dubins:
                 out["cpu_baseline"] = cpu_baseline_dubins(og8, cfg, dub_inputs, results[0])
             else:
                 out["cpu_baseline"] = cpu_baseline(og8, cfg, pairs[0], free, states[0], ub_cache.get(0), results[0])
-        if world == 1 and args.config == 2 and not args.no_batched:
+        if args.full and world == 1 and args.config == 2 and not args.no_batched:
             out["batched"] = batched_leg(ctx, og, og8, free, _ffi, hostprep)
-        if world == 1 and args.config == 2 and not args.no_plan_wall and not args.queries and not args.n and not args.team and not args.serial:
+        if args.full and world == 1 and args.config == 2 and not args.no_plan_wall and not args.queries and not args.n and not args.team and not args.serial:
             out["plan_wall"] = plan_wall_leg(og, cfg, pairs[0])
         if world == 1 and args.rewire_leg and alg >= 1:
             out["rewire_correct"] = rewire_leg(ctx, og8, cfg, pairs[0], free, states[0], _ffi, hostprep)

@@ -562,6 +562,7 @@ def test_bench_as_a_rank_and_as_its_own_launcher():
     ranked = _run_bench({"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29731"}, *args)
     for d in (plain, ranked):
         assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2 and d["unit"] == "nodes/s" and d["scaling"] == "weak"
+        assert not {"cpu_baseline", "batched", "plan_wall"} & set(d), "a run without --full only times the steps"
         r = d["roofline"]
         assert r["frac"] is None or 0 < r["frac"] <= 1
         assert r["kernel"].startswith("rrt_expand_block_kernel<64, 1, true")
@@ -569,6 +570,37 @@ def test_bench_as_a_rank_and_as_its_own_launcher():
     assert plain["config"]["collective"] is None and "ncclAllGather" in ranked["config"]["collective"]
     assert ranked["value"] == pytest.approx(plain["value"], rel=0.06)
     assert plain["host_gap_ms"] < 0.25, plain  # the step is the kernel: what the host adds stays below a quarter millisecond
+
+
+def test_bench_full_legs_and_dumped_outputs(tmp_path):
+    """`--full` adds the CPU baseline and the batched leg (bench.py checks both against the oracle itself); `--dump-outputs`
+    writes the tree of the last timed step, which must be the oracle's tree of the bench's query 0, and the same again on a
+    second run."""
+    from rrtplanner_amd.oggen import random_connected_pairs
+
+    n = 3000
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    d = _run_bench({}, "--steps", "2", "--warmup", "1", "--n", str(n), "--full", "--dump-outputs", str(dirs[0]))
+    assert d["steps"] == 2 and d["cpu_baseline"]["device_result_equals_oracle"] and d["batched"]["value"] > 0
+    assert "plan_wall" not in d  # the plan() leg runs only on the config's own n
+    got = {p.stem: np.load(p) for p in dirs[0].glob("*.npy")}
+    assert set(got) == {"query_index", "status", "j", "vgoal", "found", "pts", "parent", "vcost"}
+    assert got["pts"].dtype == np.float32 and all(got[k].dtype == np.float64 for k in got if k != "pts")
+    assert got["pts"].shape == (1, n + 1, 2) and got["parent"].shape == got["vcost"].shape == (1, n + 1)
+
+    og = perlin_occupancygrid(1024, 1024, thresh=0.33, seed=1)
+    og8 = hostprep.og_nonzero(og)  # bench.py's grid
+    xs, xg = random_connected_pairs(og, np.random.default_rng(7), 1)[0]
+    samples = hostprep.draw_free_samples(np.random.default_rng(0), np.argwhere(og == 0), n)
+    st, ro = oracle.plan(og8, n, 1, xs, xg, samples, r2_rewire=hostprep.radius_threshold(64), logs=False)
+    live = ro.j + (1 if ro.found else 0)
+    assert (got["status"][0], got["j"][0], got["vgoal"][0], got["found"][0]) == (st, ro.j, ro.vgoal, ro.found)
+    assert np.array_equal(got["pts"][0, :live], ro.pts[:live]) and np.array_equal(got["parent"][0, :live], ro.parent[:live])
+    assert np.array_equal(got["vcost"][0, :live], ro.vcost[:live]) and (got["parent"][0, live:] == -1).all()
+
+    _run_bench({}, "--steps", "1", "--warmup", "0", "--n", str(n), "--dump-outputs", str(dirs[1]))
+    for k, a in got.items():
+        assert np.array_equal(np.load(dirs[1] / f"{k}.npy"), a), k
 
 
 def test_two_contexts_share_the_device_without_timeouts():

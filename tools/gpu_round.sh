@@ -33,15 +33,15 @@ gap)
     python3 $R/tools/step_gap.py --steps 20 > $O/step_gap.txt 2>&1; echo "gap rc=$?"; cat $O/step_gap.txt
     python3 $R/tools/step_gap.py --steps 20 --config 4 >> $O/step_gap.txt 2>&1; tail -n 9 $O/step_gap.txt ;;
 bench)
-    python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -n 2 $O/bench_default.err
+    python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -n 2 $O/bench_default.err
     RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29999 python3 $R/bench.py --no-cpu-baseline --no-batched > $O/bench_one_rank_comm.json 2> $O/bench_one_rank_comm.err; echo "bench(comm) rc=$?"
-    python3 $R/bench.py --config 3 --no-batched > $O/bench_config3.json 2> $O/bench_config3.err; echo "bench c3 rc=$?"
+    python3 $R/bench.py --config 3 --full --no-batched > $O/bench_config3.json 2> $O/bench_config3.err; echo "bench c3 rc=$?"
     python3 $R/bench.py --config 4 --no-cpu-baseline > $O/bench_config4.json 2> $O/bench_config4.err; echo "bench c4 rc=$?"
     python3 $R/bench.py --queries 8 --no-cpu-baseline --no-batched > $O/bench_config2_q8.json 2>/dev/null
     python3 $R/bench.py --queries 256 --no-cpu-baseline --no-batched > $O/bench_config2_q256.json 2>/dev/null
     for t in 1 2 4 8 16 32; do python3 $R/bench.py --team $t --no-cpu-baseline --no-batched > $O/bench_config2_team$t.json 2>/dev/null; done
     for t in 1 2 4 8; do python3 $R/bench.py --config 4 --team $t --no-cpu-baseline > $O/bench_config4_team$t.json 2>/dev/null; done
-    python3 $R/bench.py --config 5 --steps 3 --warmup 1 > $O/bench_config5.json 2> $O/bench_config5.err; echo "bench c5 rc=$?"
+    python3 $R/bench.py --config 5 --steps 3 --warmup 1 --full > $O/bench_config5.json 2> $O/bench_config5.err; echo "bench c5 rc=$?"
     python3 $R/bench.py --config 5 --serial --queries 16 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_config5_serial_q16.json 2>/dev/null
     python3 $R/bench.py --config 5 --queries 16 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_config5_q16.json 2>/dev/null
     python3 - <<PY
@@ -57,7 +57,7 @@ for f in sorted(glob.glob("$O/bench_*.json")):
 PY
     ;;
 quick)
-    python3 $R/bench.py --no-cpu-baseline > $O/q_default.json 2>$O/q_default.err; echo "default rc=$?"
+    python3 $R/bench.py --full --no-cpu-baseline > $O/q_default.json 2>$O/q_default.err; echo "default rc=$?"
     python3 $R/bench.py --config 4 --team 1 --no-cpu-baseline > $O/q_c4_team1.json 2>/dev/null
     python3 $R/bench.py --config 3 --no-cpu-baseline --no-batched > $O/q_c3.json 2>/dev/null
     python3 $R/bench.py --team 1 --no-cpu-baseline --no-batched > $O/q_c2_team1.json 2>/dev/null
