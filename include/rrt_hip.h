@@ -60,6 +60,9 @@ extern "C" {
 #define RRT_FLAG_DUBINS 64u /* the batch runs Dubins queries (RRT_ALG_DUBINS / RRT_ALG_DUBINS_STAR) only, one CU per query: 16 samples per
                               round on per-node headings and cell records (rrt_dubins_block.h); with RRT_FLAG_SERIAL the
                               one-sample-per-iteration kernel, kept as a cross-check.  rrt_plan sets it by itself for such a query. */
+#define RRT_FLAG_ONEBODY 128u /* pipelined teams of 8 and more workers, RRTStandard / RRTStar: committer and workers as ONE kernel
+                                (rrt_expand_block_kernel) instead of rrt_block_commit_kernel (8 waves, 256 vector registers) next to
+                                rrt_block_work_kernel on two streams of the context; kept as a cross-check, the results are the same */
 #define RRT_FLAG_NOPIPE1 32768u /* one CU per query, RRTStandard / RRTStar: the 16-samples-per-pass block kernel instead of the barrier-free
                                   pipeline (rrt_pipe.h); kept as a cross-check, the results are the same */
 #define RRT_FLAG_TEAM_MAX(g) ((uint32_t)(g) << 8) /* cap the team size at g CUs per query (g = 2, 4, ... 64; 0 = no cap) */

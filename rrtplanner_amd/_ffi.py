@@ -31,10 +31,11 @@ FLAG_TEAM_FAULT = 8
 FLAG_NOPIPE = 16
 FLAG_REWIRE = 32
 FLAG_DUBINS = 64
+FLAG_ONEBODY = 128
 FLAG_NOPIPE1 = 32768
 
 
-def kernel_flags(logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, dubins=False, pipe1=True):
+def kernel_flags(logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, dubins=False, pipe1=True, onebody=False):
     """flags word of rrt_plan / rrt_batch_create.  team: None = as many CUs per query as fit (up to 64), 1 = one CU,
     2..64 = cap on the team's workers; pipe = False: no pipelined teams (workers + one committing CU); team_fault = the
     fault-injection flag of the tests."""
@@ -42,6 +43,7 @@ def kernel_flags(logs=False, serial=False, team=None, team_fault=False, pipe=Tru
     f |= FLAG_REWIRE if rewire else 0  # the opt-in true rewire (not the reference's behaviour)
     f |= FLAG_DUBINS if dubins else 0
     f |= 0 if pipe1 else FLAG_NOPIPE1  # one CU per query: the block kernel instead of the barrier-free pipeline (a cross-check)
+    f |= FLAG_ONEBODY if onebody else 0  # pipelined teams of 8+: committer and workers as one kernel instead of two (a cross-check)
     if team == 1:
         f |= FLAG_NOTEAM
     elif team is not None:
@@ -323,9 +325,9 @@ class Context:
         self.allreduce([0.0])
 
     # ---- one-shot ----
-    def plan(self, query, n, logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, pipe1=True):
+    def plan(self, query, n, logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, pipe1=True, onebody=False):
         res = ResultArrays(n, logs, headings=query.alg >= ALG_DUBINS)
-        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, pipe1=pipe1)
+        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, pipe1=pipe1, onebody=onebody)
         rc = lib().rrt_plan(self._h, C.byref(query), flags, C.byref(res.c))
         _check(self._h, rc, ok=(RRT_OK, RRT_NEED_UNITBALL, RRT_E_GOAL_UNREACHABLE))
         return rc, res
@@ -433,10 +435,10 @@ class Batch:
     """Q independent queries resident on the device (rrt_batch_*)."""
 
     def __init__(self, ctx: Context, Q: int, n_cap: int, logs: bool = False, serial: bool = False, team=None, team_fault: bool = False,
-                 pipe: bool = True, rewire: bool = False, dubins: bool = False, pipe1: bool = True):
+                 pipe: bool = True, rewire: bool = False, dubins: bool = False, pipe1: bool = True, onebody: bool = False):
         self.ctx, self.Q, self.n_cap, self.logs, self.dubins = ctx, int(Q), int(n_cap), logs, dubins
         self._h = C.c_void_p()
-        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, dubins, pipe1)
+        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, dubins, pipe1, onebody)
         _check(ctx.handle, lib().rrt_batch_create(ctx.handle, self.Q, self.n_cap, flags, C.byref(self._h)))
         if not hasattr(ctx, "_batches"):
             ctx._batches = weakref.WeakSet()

@@ -26,6 +26,10 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #include "rrt_block.h"
 namespace rrtdev {
 #define K(G, BSM, PIPE, INF) template __global__ void rrt_expand_block_kernel<G, BSM, PIPE, INF>(BatchView);
+// a pipelined team as two kernels: the committer (8 waves, 256 vector registers) and the workers
+#define S(G, BSM, INF)                                                        \
+    template __global__ void rrt_block_commit_kernel<G, BSM, INF>(BatchView); \
+    template __global__ void rrt_block_work_kernel<G, BSM, INF>(BatchView);
 #if RRT_TU == 10
 K(64, 1, true, false)
 #elif RRT_TU == 11
@@ -50,9 +54,16 @@ K(16, 4, false, false) K(16, 4, false, true) K(8, 8, false, false) K(8, 8, false
 K(4, 16, false, false) K(4, 16, false, true) K(2, 16, false, false) K(2, 16, false, true)
 #elif RRT_TU == 21
 K(1, 16, false, false) K(1, 16, false, true)
+#elif RRT_TU == 22
+S(64, 1, false)
+#elif RRT_TU == 23
+S(32, 2, false)
+#elif RRT_TU == 24
+S(16, 4, false) S(8, 8, false)
 #else
 #error "RRT_TU: unknown translation unit"
 #endif
 #undef K
+#undef S
 }
 #endif

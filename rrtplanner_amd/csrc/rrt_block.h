@@ -325,8 +325,9 @@ constexpr int ROLE_ALL = 0, ROLE_COMMIT = 1, ROLE_WORK = 2;
 // by then).
 // INF: the batch may hold Informed queries (alg 2); without it everything the ellipse needs is compiled out.
 
-// CW: waves of THIS workgroup (16; round 3 measured a committer of 8 waves as a kernel of its own, compiled for 256 vector registers:
-// no gain, profiles/r03_experiments.md -- the parameter stays, the kernels went).
+// CW: waves of THIS workgroup.  16 everywhere, except for a pipelined team's committer launched as a kernel of its own
+// (rrt_block_commit_kernel, the default for teams of 8 and more): 8 waves, so that it is compiled for 256 instead of 128 vector
+// registers and spills nothing.
 template <int G, int BSM, bool PIPE, bool INF, int ROLE, int CW = NWAVE>
 __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PIPE, INF> &L) {
     static_assert(CW == NWAVE || ROLE == ROLE_COMMIT, "only a committer runs with fewer waves");
@@ -956,6 +957,33 @@ __global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv)
     } else {
         rrt_block_body<G, BSM, PIPE, INF, ROLE_ALL>(bv, L);
     }
+}
+#endif
+
+// The two halves of a pipelined team of 8 and more workers as two kernels, launched on two streams of the context (the default;
+// RRT_FLAG_ONEBODY keeps rrt_expand_block_kernel).  Register allocation is per kernel: the committer, a workgroup of 8 waves, gets
+// 256 vector registers instead of the 128 of a 16-wave workgroup, at which its half of the one-body kernel spills; the workers are
+// compiled without the committer's code.  The committer kernel has one workgroup per team (blockIdx.x = query slot), the workers'
+// kernel team_qpad * G of them, launched with bv.member0 = 1.
+template <int G, int BSM, bool INF>
+__global__ __launch_bounds__(512) void rrt_block_commit_kernel(BatchView bv)
+#ifdef RRT_BLOCK_DECL_ONLY
+    ;
+#else
+{
+    __shared__ BlockLds<G, BSM, true, INF> L;
+    rrt_block_body<G, BSM, true, INF, ROLE_COMMIT, 8>(bv, L);
+}
+#endif
+
+template <int G, int BSM, bool INF>
+__global__ __launch_bounds__(TPB) void rrt_block_work_kernel(BatchView bv)
+#ifdef RRT_BLOCK_DECL_ONLY
+    ;
+#else
+{
+    __shared__ BlockLds<G, BSM, true, INF> L;
+    rrt_block_body<G, BSM, true, INF, ROLE_WORK>(bv, L);
 }
 #endif
 

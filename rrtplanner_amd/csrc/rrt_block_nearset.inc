@@ -133,12 +133,12 @@
                 const double cn = V + sqrt_u24(d2);
                 const bool in = cn < bound && !key_lt(cn, rc.y, lbc, lbi);  // rrt.py:518, strict
                 if (in) {
-                    if (key_lt(cn, rc.y, tt.c1, tt.i1)) {
-                        fx2 = fx1;
-                        fx1 = rc.x;
-                    } else if (key_lt(cn, rc.y, tt.c2, tt.i2)) {
-                        fx2 = rc.x;
-                    }
+                    // (the coordinates follow the pair as selects of values: written as conditional assignments, fx1 / fx2 were
+                    //  stored behind a select of addresses and lived in scratch memory)
+                    const bool b1 = key_lt(cn, rc.y, tt.c1, tt.i1);
+                    const bool b2 = key_lt(cn, rc.y, tt.c2, tt.i2);
+                    fx2 = b1 ? fx1 : (b2 ? rc.x : fx2);
+                    fx1 = b1 ? rc.x : fx1;
                     tt.fold(cn, rc.y);
                 }
                 // (m1, m2) <- the two smallest of {m1, m2, cu}, without branches: written as conditional assignments the pair

@@ -62,6 +62,7 @@ struct PinnedDescs {
 struct rrt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;  // pipelined teams of 8 and more: the committers' kernel runs here, next to the workers' on `stream`
     uint8_t *og = nullptr;      // active grid, device (W,H): og_buf + frame * W * H
     uint8_t *og_buf = nullptr;  // allocation holding 1 uploaded grid or `nframes` generated grids
     size_t og_buf_bytes = 0;
@@ -98,6 +99,7 @@ struct rrt_batch {
     bool last_inf = false;      // the last launch ran the Informed instantiation
     bool last_pipe1 = false;    // the last launch ran the barrier-free one-CU kernel (rrt_pipe.h)
     bool last_wide = false;     // the last launch ran a team variant with more than 16 samples per member
+    bool last_split = false;    // the last launch ran committers and workers as two kernels (rrt_block_commit_kernel + rrt_block_work_kernel)
     int32_t team_fallbacks = 0; // launches repeated with one CU per query after a team hand-off timed out
     int32_t team_qpad = 0;      // Q rounded up to a multiple of 8: block = member * team_qpad + query
     int32_t team_want = TEAM_MAX;  // the caller's cap on the team size
@@ -125,6 +127,7 @@ struct rrt_batch {
     unsigned char *d_slab = nullptr;  // result slab: [vcost f64 | nodes u32 | parent i32], each [Q][node_stride]
     size_t slab_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the split team kernels: stream -> stream2 behind the init kernel, back in front of ev1
     bool timed = false;
     float ms_before = 0.f;      // kernel time of the launch a fallback relaunch replaced (rrt_batch_elapsed_ms adds it)
     bool one_cu_once = false;   // the next launch runs one CU per query whatever b->team says (continuation after a timeout)
@@ -232,6 +235,7 @@ extern "C" int rrt_ctx_destroy(rrt_ctx *ctx) {
     if (ctx->single) rrt_batch_destroy(ctx->single);
     (void)rrt_comm_destroy(ctx);
     if (ctx->og_buf) (void)hipFree(ctx->og_buf);
+    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return RRT_OK;
@@ -475,6 +479,8 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
         if (p) (void)hipFree(p);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
+    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
+    if (b->ev_join) (void)hipEventDestroy(b->ev_join);
     cu_release(b->ctx->device, b->claimed_cus);
     b->claimed_cus = 0;
     if (b->ctx->single == b) b->ctx->single = nullptr;
@@ -842,6 +848,22 @@ static const void *block_kernel_of(int team, bool pipe, bool inf, bool wide = fa
     return reinterpret_cast<const void *>(block_kernel_fn_of(team, pipe, inf, wide));
 }
 
+// A pipelined team of 8 and more workers, RRTStandard / RRTStar: the committer as a kernel of its own (8 waves, compiled for 256
+// vector registers: no spills) and the workers' kernel, launched side by side on two streams (RRT_FLAG_ONEBODY: one kernel).
+// Informed batches keep the one-body kernel.
+static bool split_team(int team, bool pipe, bool inf, bool wide, uint32_t flags) {
+    return pipe && !inf && !wide && team >= 8 && !(flags & RRT_FLAG_ONEBODY);
+}
+
+static void split_kernels_of(int team, block_kernel_fn &commit, block_kernel_fn &work) {
+    switch (team) {
+        case 64: commit = rrt_block_commit_kernel<64, 1, false>, work = rrt_block_work_kernel<64, 1, false>; break;
+        case 32: commit = rrt_block_commit_kernel<32, 2, false>, work = rrt_block_work_kernel<32, 2, false>; break;
+        case 16: commit = rrt_block_commit_kernel<16, 4, false>, work = rrt_block_work_kernel<16, 4, false>; break;
+        default: commit = rrt_block_commit_kernel<8, 8, false>, work = rrt_block_work_kernel<8, 8, false>; break;
+    }
+}
+
 // static LDS of the kernels a batch of this team size may launch: its own variants and the one-CU kernel that continues
 // a batch after a hand-off timed out (rrt_batch_sync)
 static size_t block_kernel_static_lds(int team) {
@@ -948,6 +970,7 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
         b->last_team = team;
         b->last_inf = inf;
         b->last_pipe1 = false;
+        b->last_split = false;
         if (team == 1 && !inf && !continuation && !(b->flags & RRT_FLAG_NOPIPE1)) {
             // one CU per query, RRTStandard / RRTStar: the barrier-free pipeline (rrt_pipe.h; static LDS only)
             b->last_pipe1 = true;
@@ -959,12 +982,38 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
             b->timed = true;
             return RRT_OK;
         }
-        HIPCHK(ctx, raise_dynamic_lds(ctx->device, block_kernel_of(team, pipe, inf, wide), (int)blk_lds_bytes));
+        const bool split = split_team(team, pipe, inf, wide, b->flags);
+        block_kernel_fn kcommit = nullptr, kwork = nullptr;
+        if (split) {
+            split_kernels_of(team, kcommit, kwork);
+            if (!ctx->stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+            if (!b->ev_fork) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+            if (!b->ev_join) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
+            HIPCHK(ctx, raise_dynamic_lds(ctx->device, reinterpret_cast<const void *>(kcommit), (int)blk_lds_bytes));
+            HIPCHK(ctx, raise_dynamic_lds(ctx->device, reinterpret_cast<const void *>(kwork), (int)blk_lds_bytes));
+        } else {
+            HIPCHK(ctx, raise_dynamic_lds(ctx->device, block_kernel_of(team, pipe, inf, wide), (int)blk_lds_bytes));
+        }
         hipLaunchKernelGGL(rrt_init_kernel<0>, ig, dim3(256), 0, ctx->stream, v);
         if (team > 1) HIPCHK(ctx, hipMemsetAsync(b->d_team, 0, (size_t)b->Q * TEAM_BYTES, ctx->stream));  // every polled word, every launch
         HIPCHK(ctx, hipEventRecord(b->ev0, ctx->stream));
-        const dim3 tg(team > 1 ? (unsigned)(v.team_qpad * (team + (pipe ? 1 : 0))) : (unsigned)b->Q);
-        hipLaunchKernelGGL(block_kernel_fn_of(team, pipe, inf, wide), tg, dim3(TPB), blk_lds_bytes, ctx->stream, v);
+        if (split) {
+            // the committers (one workgroup of 8 waves per team) on stream2, forked behind the init kernel and the memset; the workers
+            // (team_qpad * team workgroups, members 1 .. team) on the context's stream, which joins stream2 in front of ev1.  The CU
+            // claim above covers both kernels (TeamShape::cus counts the committer); ev0 / ev1 bracket both.
+            HIPCHK(ctx, hipEventRecord(b->ev_fork, ctx->stream));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, b->ev_fork, 0));
+            hipLaunchKernelGGL(kcommit, dim3((unsigned)v.team_qpad), dim3(512), blk_lds_bytes, ctx->stream2, v);
+            BatchView vw = v;
+            vw.member0 = 1;
+            hipLaunchKernelGGL(kwork, dim3((unsigned)(v.team_qpad * team)), dim3(TPB), blk_lds_bytes, ctx->stream, vw);
+            HIPCHK(ctx, hipEventRecord(b->ev_join, ctx->stream2));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_join, 0));
+            b->last_split = true;
+        } else {
+            const dim3 tg(team > 1 ? (unsigned)(v.team_qpad * (team + (pipe ? 1 : 0))) : (unsigned)b->Q);
+            hipLaunchKernelGGL(block_kernel_fn_of(team, pipe, inf, wide), tg, dim3(TPB), blk_lds_bytes, ctx->stream, v);
+        }
         HIPCHK(ctx, hipEventRecord(b->ev1, ctx->stream));
         HIPCHK(ctx, hipGetLastError());
         b->timed = true;
@@ -1099,6 +1148,9 @@ extern "C" int rrt_batch_kernel_name(rrt_batch *b, char *buf, int32_t len) {
         const int team = b->last_team > 0 ? b->last_team : b->team;
         const int bsm = b->last_wide ? 32 : (team <= 4 ? 16 : 64 / team);
         if (b->last_pipe1) snprintf(tmp, sizeof tmp, "rrt_pipe_kernel");
+        else if (b->last_split)  // (the one-body name first: the two kernels are its halves)
+            snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, true, false> as rrt_block_commit_kernel + rrt_block_work_kernel<%d, %d, false>", team,
+                     bsm, team, bsm);
         else snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, %s, %s>", team, bsm, (team > 1 && b->pipe) ? "true" : "false", b->last_inf ? "true" : "false");
     } else if (b->dub_block) {
         snprintf(tmp, sizeof tmp, "rrt_dubins_block_kernel");
