@@ -21,48 +21,19 @@ template __global__ void rrt_expand_kernel<false, false>(BatchView);
 template __global__ void rrt_expand_kernel<true, false>(BatchView);
 }
 
-#else  // teams of compute units: rrt_expand_block_kernel<G, BSM, PIPE, INF>
+#else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_block.h"
+#include "rrt_block_variants.def"
 namespace rrtdev {
 #define K(G, BSM, PIPE, INF) template __global__ void rrt_expand_block_kernel<G, BSM, PIPE, INF>(BatchView);
 // a pipelined team as two kernels: the committer (8 waves, 256 vector registers) and the workers
 #define S(G, BSM, INF)                                                        \
     template __global__ void rrt_block_commit_kernel<G, BSM, INF>(BatchView); \
     template __global__ void rrt_block_work_kernel<G, BSM, INF>(BatchView);
-#if RRT_TU == 10
-K(64, 1, true, false)
-#elif RRT_TU == 11
-K(64, 1, true, true)
-#elif RRT_TU == 12
-K(32, 2, true, false) K(32, 2, true, true)
-#elif RRT_TU == 13
-K(16, 4, true, false) K(16, 4, true, true)
-#elif RRT_TU == 14
-K(8, 8, true, false) K(8, 8, true, true)
-#elif RRT_TU == 15
-K(4, 16, true, false) K(4, 16, true, true)
-#elif RRT_TU == 16
-K(3, 16, true, false) K(3, 16, true, true)
-#elif RRT_TU == 17
-K(2, 16, true, false) K(2, 16, true, true) K(2, 32, true, false)
-#elif RRT_TU == 18
-K(64, 1, false, false) K(64, 1, false, true) K(32, 2, false, false) K(32, 2, false, true)
-#elif RRT_TU == 19
-K(16, 4, false, false) K(16, 4, false, true) K(8, 8, false, false) K(8, 8, false, true)
-#elif RRT_TU == 20
-K(4, 16, false, false) K(4, 16, false, true) K(2, 16, false, false) K(2, 16, false, true)
-#elif RRT_TU == 21
-K(1, 16, false, false) K(1, 16, false, true)
-#elif RRT_TU == 22
-S(64, 1, false)
-#elif RRT_TU == 23
-S(32, 2, false)
-#elif RRT_TU == 24
-S(16, 4, false) S(8, 8, false)
-#else
-#error "RRT_TU: unknown translation unit"
-#endif
+#define RRT_PASTE_(a, b) a##b
+#define RRT_PASTE(a, b) RRT_PASTE_(a, b)
+RRT_PASTE(RRT_UNIT_, RRT_TU)(K, S)  // (a unit that rrt_block_variants.def does not define is a compile error here)
 #undef K
 #undef S
 }

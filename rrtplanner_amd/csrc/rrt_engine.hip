@@ -22,6 +22,7 @@
 #include "rrt_hip.h"
 #include "rrt_kernels.h"
 #include "rrt_block.h"
+#include "rrt_block_variants.def"
 #include "rrt_kernel_decls.h"
 #include "rrt_prims.h"
 
@@ -83,6 +84,64 @@ struct rrt_ctx {
     double *d_red = nullptr;  // small device scratch of rrt_comm_allreduce_f64
 };
 
+typedef void (*block_kernel_fn)(BatchView);
+
+// A launchable variant of the team kernels: one row per entry of rrt_block_variants.def, the only list of them.  A K entry is one
+// kernel (`one`); an S entry is the pipelined team <G, BSM, true, INF> as two kernels (`commit`, `work`).
+struct BlockVariant {
+    int G, BSM;
+    bool pipe, inf;
+    block_kernel_fn one, commit, work;
+};
+static const BlockVariant g_block_variants[] = {
+#define K(G, BSM, PIPE, INF) {G, BSM, PIPE, INF, rrt_expand_block_kernel<G, BSM, PIPE, INF>, nullptr, nullptr},
+#define S(G, BSM, INF) {G, BSM, true, INF, nullptr, rrt_block_commit_kernel<G, BSM, INF>, rrt_block_work_kernel<G, BSM, INF>},
+#define U(k) RRT_UNIT_##k(K, S)
+    RRT_BLOCK_UNITS(U)
+#undef U
+#undef S
+#undef K
+};
+
+// wide: more than 16 samples per member (rrt_block.h, BSM > 16); split: the two kernels of an S entry.  nullptr: not instantiated.
+static const BlockVariant *find_variant(int team, bool pipe, bool inf, bool wide, bool split) {
+    for (const BlockVariant &r : g_block_variants)
+        if (r.G == team && r.pipe == pipe && r.inf == inf && (r.BSM > 16) == wide && (r.commit != nullptr) == split) return &r;
+    return nullptr;
+}
+
+// static LDS of the kernels a batch of this team size may launch: its own variants, those of any smaller team (a launch may run
+// one when other launches hold compute units) and the one-CU kernel that continues a batch after a hand-off timed out (rrt_batch_sync)
+static size_t block_kernel_static_lds(int team) {
+    hipFuncAttributes a{};
+    size_t worst = 0;
+    for (const BlockVariant &r : g_block_variants)
+        for (block_kernel_fn k : {r.one, r.commit, r.work}) {
+            if (!k || r.G > team) continue;
+            if (hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k)) != hipSuccess) return 16384;
+            worst = a.sharedSizeBytes > worst ? a.sharedSizeBytes : worst;
+        }
+    return (worst + 255) & ~(size_t)255;
+}
+
+// What one launch decided (plan_launch).  The batch keeps the plan of its last launch for the questions asked afterwards
+// (rrt_batch_kernel_name, rrt_batch_team_info, rrt_batch_pipelined, the continuation in rrt_batch_sync).
+struct LaunchPlan {
+    int team = 0;               // workers per query (1 after a hand-off timed out; 0: nothing launched yet)
+    int qpad = 0;               // block = member * qpad + query
+    bool pipe = false;          // the pipelined team kernel: one more workgroup per query, which only commits
+    bool inf = false;           // the Informed instantiation
+    bool wide = false;          // a team variant with more than 16 samples per member
+    bool split = false;         // committers and workers as two kernels (rrt_block_commit_kernel + rrt_block_work_kernel)
+    bool pipe1 = false;         // the barrier-free one-CU kernel (rrt_pipe.h)
+    bool continuation = false;  // of a launch that stopped at a block boundary: one CU per query, and the block kernel takes it from there
+    const BlockVariant *row = nullptr;  // the team variant, or nullptr for a kernel that is none (pipe1, Dubins, one sample per iteration)
+    block_kernel_fn kern = nullptr;     // the kernel of a launch that is one kernel (row->one, or the plain kernel)
+    unsigned grid = 0;          // its workgroups (split: qpad committers, qpad * team workers)
+    int lds_chunks = 1;         // node chunks cached in LDS
+    size_t lds_bytes = 0;       // dynamic LDS per workgroup
+};
+
 struct rrt_batch {
     rrt_ctx *ctx = nullptr;
     int32_t Q = 0, n_cap = 0, node_stride = 0, bitmap_words = 0, lds_chunks = 1, spill_stride = 0;
@@ -94,12 +153,7 @@ struct rrt_batch {
     int32_t blk_lds_chunks16 = 1; // ... and the kernels that also keep their parked-entry lists there
     int32_t team = 1;           // workgroups (CUs) per query of the block kernel that scan and resolve (rrt_block.h, teams)
     bool pipe_team = false;     // the team is pipelined: one more workgroup per query, which only commits
-    bool pipe = false;          // the last launch ran the pipelined team kernel
-    int32_t last_team = 0;      // workers per query of the last launch (1 after a hand-off timed out)
-    bool last_inf = false;      // the last launch ran the Informed instantiation
-    bool last_pipe1 = false;    // the last launch ran the barrier-free one-CU kernel (rrt_pipe.h)
-    bool last_wide = false;     // the last launch ran a team variant with more than 16 samples per member
-    bool last_split = false;    // the last launch ran committers and workers as two kernels (rrt_block_commit_kernel + rrt_block_work_kernel)
+    LaunchPlan last;            // the plan of the last launch
     int32_t team_fallbacks = 0; // launches repeated with one CU per query after a team hand-off timed out
     int32_t team_qpad = 0;      // Q rounded up to a multiple of 8: block = member * team_qpad + query
     int32_t team_want = TEAM_MAX;  // the caller's cap on the team size
@@ -133,9 +187,6 @@ struct rrt_batch {
     bool one_cu_once = false;   // the next launch runs one CU per query whatever b->team says (continuation after a timeout)
     std::vector<uint32_t> stage;  // host staging for packed samples
 };
-
-static const void *block_kernel_of(int team, bool pipe, bool inf);
-static size_t block_kernel_static_lds(int team);
 
 // The limit is a property of the kernel on a device, shared by every batch that launches it: it is only ever raised, to the
 // largest request seen, and hipFuncSetAttribute is called when a launch needs more than the kernel already has -- once per
@@ -500,9 +551,6 @@ struct TeamShape {
     bool pipe = false;
     int cus() const { return team > 1 ? qpad * (team + (pipe ? 1 : 0)) : 0; }  // workgroups that must be resident together
 };
-static TeamShape pick_team(int Q, int want, bool allow_pipe, int cus);
-// The batch got two CUs per query without a committer, by itself (no cap from the caller, pipelines allowed): see rrt_batch_launch.
-static bool two_cus_run_the_pipeline(const rrt_batch *b);
 static TeamShape pick_team(int Q, int want, bool allow_pipe, int cus) {
     TeamShape t;
     t.qpad = (Q + 7) & ~7;
@@ -528,6 +576,11 @@ static TeamShape pick_team(int Q, int want, bool allow_pipe, int cus) {
         t.pipe = true;
     }
     return t;
+}
+
+// The batch got two CUs per query without a committer, by itself (no cap from the caller, pipelines allowed): see plan_launch.
+static bool two_cus_run_the_pipeline(const rrt_batch *b) {
+    return b->use_block && b->team == 2 && !b->pipe_team && b->team_want >= TEAM_MAX && !(b->flags & (RRT_FLAG_NOPIPE | RRT_FLAG_NOPIPE1));
 }
 
 extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t flags, rrt_batch **out) {
@@ -809,45 +862,6 @@ static BatchView make_view(rrt_batch *b) {
     return v;
 }
 
-typedef void (*block_kernel_fn)(BatchView);
-
-// wide: a pipelined team of 2 workers with 32 samples per member (rrt_block.h, BSM > 16).  Measured (profiles/r03_experiments.md):
-// config 4's query on 2 + 1 CUs 8.92 -> 7.87 ms; three workers with 21 samples each gained nothing (6.32 vs 6.25 ms) and are not built.
-template <bool INF>
-static block_kernel_fn block_kernel_fn_inf(int team, bool pipe, bool wide) {
-    if constexpr (!INF) {  // (the launch never takes the wide team for a batch with Informed queries)
-        if (pipe && wide && team == 2) return rrt_expand_block_kernel<2, 32, true, false>;
-    }
-    if (pipe) {
-        switch (team) {
-            case 64: return rrt_expand_block_kernel<64, 1, true, INF>;
-            case 32: return rrt_expand_block_kernel<32, 2, true, INF>;
-            case 16: return rrt_expand_block_kernel<16, 4, true, INF>;
-            case 8: return rrt_expand_block_kernel<8, 8, true, INF>;
-            case 4: return rrt_expand_block_kernel<4, 16, true, INF>;
-            case 3: return rrt_expand_block_kernel<3, 16, true, INF>;
-            default: return rrt_expand_block_kernel<2, 16, true, INF>;
-        }
-    }
-    switch (team) {
-        case 64: return rrt_expand_block_kernel<64, 1, false, INF>;
-        case 32: return rrt_expand_block_kernel<32, 2, false, INF>;
-        case 16: return rrt_expand_block_kernel<16, 4, false, INF>;
-        case 8: return rrt_expand_block_kernel<8, 8, false, INF>;
-        case 4: return rrt_expand_block_kernel<4, 16, false, INF>;
-        case 2: return rrt_expand_block_kernel<2, 16, false, INF>;
-        default: return rrt_expand_block_kernel<1, 16, false, INF>;
-    }
-}
-
-static block_kernel_fn block_kernel_fn_of(int team, bool pipe, bool inf, bool wide = false) {
-    return inf ? block_kernel_fn_inf<true>(team, pipe, wide) : block_kernel_fn_inf<false>(team, pipe, wide);
-}
-
-static const void *block_kernel_of(int team, bool pipe, bool inf, bool wide = false) {
-    return reinterpret_cast<const void *>(block_kernel_fn_of(team, pipe, inf, wide));
-}
-
 // A pipelined team of 8 and more workers, RRTStandard / RRTStar: the committer as a kernel of its own (8 waves, compiled for 256
 // vector registers: no spills) and the workers' kernel, launched side by side on two streams (RRT_FLAG_ONEBODY: one kernel).
 // Informed batches keep the one-body kernel.
@@ -855,40 +869,117 @@ static bool split_team(int team, bool pipe, bool inf, bool wide, uint32_t flags)
     return pipe && !inf && !wide && team >= 8 && !(flags & RRT_FLAG_ONEBODY);
 }
 
-static void split_kernels_of(int team, block_kernel_fn &commit, block_kernel_fn &work) {
-    switch (team) {
-        case 64: commit = rrt_block_commit_kernel<64, 1, false>, work = rrt_block_work_kernel<64, 1, false>; break;
-        case 32: commit = rrt_block_commit_kernel<32, 2, false>, work = rrt_block_work_kernel<32, 2, false>; break;
-        case 16: commit = rrt_block_commit_kernel<16, 4, false>, work = rrt_block_work_kernel<16, 4, false>; break;
-        default: commit = rrt_block_commit_kernel<8, 8, false>, work = rrt_block_work_kernel<8, 8, false>; break;
-    }
-}
-
-// static LDS of the kernels a batch of this team size may launch: its own variants and the one-CU kernel that continues
-// a batch after a hand-off timed out (rrt_batch_sync)
-static size_t block_kernel_static_lds(int team) {
-    hipFuncAttributes a{};
-    size_t worst = 0;
-    for (int g : {1, 2, 3, 4, 8, 16, 32, 64})  // (a launch may run any smaller team when other launches hold compute units)
-        for (bool pipe : {false, true})
-            for (bool inf : {false, true}) {
-                if (g > team || (pipe && g < 2)) continue;
-                if (!pipe && g == 3) continue;  // (three workers exist only as a pipelined team)
-                for (bool wide : {false, true}) {
-                    if (wide && !(pipe && g == 2)) continue;
-                    if (hipFuncGetAttributes(&a, block_kernel_of(g, pipe, inf, wide)) != hipSuccess) return 16384;
-                    worst = a.sharedSizeBytes > worst ? a.sharedSizeBytes : worst;
-                }
-            }
-    return (worst + 255) & ~(size_t)255;
-}
-
 static size_t expand_lds_bytes(int lds_chunks) {
     return (size_t)lds_chunks * CHUNK * sizeof(uint32_t);  // dynamic part: the node cache (lists and slots are static LDS)
 }
 
-static bool two_cus_run_the_pipeline(const rrt_batch *b) {
-    return b->use_block && b->team == 2 && !b->pipe_team && b->team_want >= TEAM_MAX && !(b->flags & (RRT_FLAG_NOPIPE | RRT_FLAG_NOPIPE1));
+// Claims the launch's compute units in the device's registry and returns the shape that was granted.  Every member of every team
+// must be resident at once: a team takes the largest shape that fits next to the launches in flight on this device (other
+// batches, other contexts, other host threads of this process).  One CU per query needs no co-residency, but its workgroups occupy
+// CUs all the same.
+static TeamShape claim_cus(rrt_batch *b, int team) {
+    rrt_ctx *ctx = b->ctx;
+    cu_release(ctx->device, b->claimed_cus);  // (a launch that was never synchronised)
+    b->claimed_cus = 0;
+    TeamShape ts;
+    ts.team = team;
+    ts.qpad = b->team_qpad;
+    ts.pipe = b->pipe_team;
+    if (team > 1) {
+        for (;;) {
+            const int free_cus = cu_claim(ctx->device, ctx->num_cu, ts.cus(), 0);
+            if (free_cus < 0) break;  // granted
+            TeamShape smaller = pick_team(b->Q, b->team_want < ts.team ? b->team_want : ts.team, b->pipe_team, free_cus);
+            if (smaller.team >= ts.team && smaller.pipe == ts.pipe) smaller.team = 1;  // (the registry changed in between: do not loop)
+            ts = smaller;
+            if (ts.team <= 1) break;
+        }
+        if (ts.team != team) b->shrunk += 1;
+        b->claimed_cus = ts.team > 1 ? ts.cus() : 0;
+    }
+    if (ts.team <= 1) {
+        ts.team = 1;
+        b->claimed_cus = b->Q < ctx->num_cu ? b->Q : ctx->num_cu;
+        (void)cu_claim(ctx->device, ctx->num_cu, b->claimed_cus, b->claimed_cus);
+    }
+    return ts;
+}
+
+// Decides what this launch of the batch runs, and claims its compute units on the way (the team follows from what is free).
+static int plan_launch(rrt_batch *b, LaunchPlan &p) {
+    rrt_ctx *ctx = b->ctx;
+    p = LaunchPlan{};
+    p.team = 1;
+    p.qpad = b->team_qpad;
+    p.grid = (unsigned)b->Q;
+    p.lds_chunks = b->lds_chunks;
+    if (!b->use_block) {
+        (void)claim_cus(b, 1);
+        if (b->dub_block) {
+            p.kern = rrt_dubins_block_kernel;
+            return RRT_OK;
+        }
+        p.kern = (b->flags & RRT_FLAG_DUBINS)  ? static_cast<block_kernel_fn>(rrt_expand_kernel<false, true>)
+                 : (b->flags & RRT_FLAG_REWIRE) ? static_cast<block_kernel_fn>(rrt_expand_kernel<true, false>)
+                                                : static_cast<block_kernel_fn>(rrt_expand_kernel<false, false>);
+        p.lds_bytes = expand_lds_bytes(b->lds_chunks);
+        if (b->serial_lds_static == 0) {
+            hipFuncAttributes fa{};
+            HIPCHK(ctx, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(p.kern)));
+            b->serial_lds_static = fa.sharedSizeBytes + 1;
+        }
+        const size_t lds_static = b->serial_lds_static - 1;
+        if ((int)(p.lds_bytes + lds_static) > ctx->max_lds) return fail(ctx, RRT_E_HIP, "LDS request %zu exceeds %d", p.lds_bytes + lds_static, ctx->max_lds);
+        return RRT_OK;
+    }
+    bool inf = false;     // any Informed query in this launch?
+    bool narrow = false;  // any near-set radius below a cell?  (the wide variant has no brute-force scan)
+    for (const QDesc &d : b->h_desc) {
+        if (d.status != ST_RUNNING) continue;
+        if (d.alg == RRT_ALG_INFORMED) inf = true;
+        if (d.alg != RRT_ALG_STANDARD && d.r2_rewire < 257u) narrow = true;
+    }
+    // after a hand-off timed out this one launch continues the batch with one CU per query; the team size the batch was
+    // created with stays and the next launch uses it again
+    p.continuation = b->one_cu_once;
+    b->one_cu_once = false;
+    int team = p.continuation ? 1 : b->team;
+    // 86 - 128 queries: two CUs per query fit, a third (the committer of a pipelined team) does not.  The unpipelined team of
+    // two is slower than the barrier-free pipeline on ONE of them (config 4's query x 128: 12.7 ms against 11.0; config 2's:
+    // 45.6 against 37.4, profiles/r04_experiments.md §11) -- unless the batch holds Informed queries, which that kernel does not run.
+    if (two_cus_run_the_pipeline(b) && !p.continuation && !inf) team = 1;
+    const TeamShape ts = claim_cus(b, team);
+    p.team = ts.team;
+    p.qpad = ts.qpad;
+    p.inf = inf;
+    // a two-deep pipeline of super-blocks (one more workgroup per team, which only commits)
+    p.pipe = ts.team > 1 && ts.pipe;
+#ifdef RRT_STAMPS
+    if (const char *e = getenv("RRT_PIPE")) p.pipe = p.pipe && atoi(e) != 0;  // diagnostic build only
+#endif
+    const bool lists = p.team <= 4;  // one wave per sample: its parked entries stay in LDS
+    p.lds_chunks = lists ? b->blk_lds_chunks16 : b->blk_lds_chunks;
+    if (p.team == 1 && !inf && !p.continuation && !(b->flags & RRT_FLAG_NOPIPE1)) {
+        // one CU per query, RRTStandard / RRTStar: the barrier-free pipeline (rrt_pipe.h; static LDS only)
+        p.pipe1 = true;
+        p.kern = rrt_pipe_kernel;
+        return RRT_OK;
+    }
+    p.lds_bytes = (size_t)MAX_CELLS * sizeof(uint32_t) + (lists ? BLOCK_LIST_LDS_BYTES : 0) + expand_lds_bytes(p.lds_chunks);
+#ifndef RRT_NO_WIDE
+    // a pipelined team of 2 workers: 32 samples per member instead of 16 (the waves that are through take the extra ones; the
+    // hand-overs of a block are shared by 64 samples instead of 32).  Measured (profiles/r03_experiments.md): config 4's query on
+    // 2 + 1 CUs 8.92 -> 7.87 ms; three workers with 21 samples each gained nothing (6.32 vs 6.25 ms) and are not built.
+    p.wide = p.pipe && !inf && p.team == 2 && !narrow;
+#endif
+    p.split = split_team(p.team, p.pipe, inf, p.wide, b->flags);
+    p.row = find_variant(p.team, p.pipe, inf, p.wide, p.split);
+    if (!p.row)
+        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_launch: no team kernel for %d workers per query (pipelined %d, Informed %d, wide %d, as two kernels %d): "
+                    "rrt_block_variants.def lists the variants", p.team, p.pipe, inf, p.wide, p.split);
+    p.kern = p.row->one;
+    if (p.team > 1) p.grid = (unsigned)(p.qpad * (p.team + (p.pipe ? 1 : 0)));
+    return RRT_OK;
 }
 
 extern "C" int rrt_batch_launch(rrt_batch *b) {
@@ -898,155 +989,37 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
     if (b->gridW != ctx->W || b->gridH != ctx->H) return fail(ctx, RRT_E_ARG, "rrt_batch_launch: grid changed shape");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!b->one_cu_once) b->ms_before = 0.f;
+    LaunchPlan &p = b->last;
+    if (const int rc = plan_launch(b, p); rc != RRT_OK) return rc;
     BatchView v = make_view(b);
-    dim3 ig((unsigned)((b->bitmap_words + 255) / 256 > 64 ? 64 : (b->bitmap_words + 255) / 256), (unsigned)b->Q);
-    if (b->use_block) {
-        // after a hand-off timed out this one launch continues the batch with one CU per query; the team size the batch was
-        // created with stays and the next launch uses it again
-        int team = b->one_cu_once ? 1 : b->team;
-        bool pipe_shape = b->pipe_team;
-        const bool continuation = b->one_cu_once;  // (of a launch that stopped at a block boundary: the block kernel takes it from there)
-        if (two_cus_run_the_pipeline(b) && !continuation) {
-            // 86 - 128 queries: two CUs per query fit, a third (the committer of a pipelined team) does not.  The unpipelined team of
-            // two is slower than the barrier-free pipeline on ONE of them (config 4's query x 128: 12.7 ms against 11.0; config 2's:
-            // 45.6 against 37.4, profiles/r04_experiments.md §11) -- unless the batch holds Informed queries, which that kernel does not run.
-            bool any_inf = false;
-            for (const QDesc &d : b->h_desc)
-                if (d.status == ST_RUNNING && d.alg == 2) any_inf = true;
-            if (!any_inf) team = 1;
-        }
-        b->one_cu_once = false;
-        cu_release(ctx->device, b->claimed_cus);  // (a launch that was never synchronised)
-        b->claimed_cus = 0;
-        if (team > 1) {
-            // every member of every team must be resident at once: claim the CUs, or take the largest team that fits next to the
-            // launches in flight on this device (other batches, other contexts, other host threads of this process)
-            TeamShape ts;
-            ts.team = team;
-            ts.qpad = b->team_qpad;
-            ts.pipe = pipe_shape;
-            for (;;) {
-                const int free_cus = cu_claim(ctx->device, ctx->num_cu, ts.cus(), 0);
-                if (free_cus < 0) break;  // granted
-                TeamShape smaller = pick_team(b->Q, b->team_want < ts.team ? b->team_want : ts.team, pipe_shape, free_cus);
-                if (smaller.team >= ts.team && smaller.pipe == ts.pipe) smaller.team = 1;  // (the registry changed in between: do not loop)
-                ts = smaller;
-                if (ts.team <= 1) break;
-            }
-            if (ts.team != team) b->shrunk += 1;
-            team = ts.team;
-            pipe_shape = ts.pipe;
-            v.team_qpad = ts.qpad;
-            b->claimed_cus = team > 1 ? ts.cus() : 0;
-        }
-        if (team <= 1) {  // one CU per query needs no co-residency, but its workgroups occupy CUs all the same
-            team = 1;
-            b->claimed_cus = b->Q < ctx->num_cu ? b->Q : ctx->num_cu;
-            (void)cu_claim(ctx->device, ctx->num_cu, b->claimed_cus, b->claimed_cus);
-        }
-        const bool lists = team <= 4;  // one wave per sample: its parked entries stay in LDS
-        v.lds_chunks = lists ? b->blk_lds_chunks16 : b->blk_lds_chunks;
-        const size_t blk_lds_bytes = (size_t)MAX_CELLS * sizeof(uint32_t) + (lists ? BLOCK_LIST_LDS_BYTES : 0) + (size_t)v.lds_chunks * CHUNK * sizeof(uint32_t);
-        // a two-deep pipeline of super-blocks (one more workgroup per team, which only commits) for teams of 8 and more
-        bool pipe = team > 1 && pipe_shape;
-#ifdef RRT_STAMPS
-        if (const char *e = getenv("RRT_PIPE")) pipe = pipe && atoi(e) != 0;  // diagnostic build only
-#endif
-        b->pipe = pipe;
-        bool inf = false;  // any Informed query in this launch?
-        for (const QDesc &d : b->h_desc)
-            if (d.status == ST_RUNNING && d.alg == 2) inf = true;
-#ifndef RRT_NO_WIDE
-        // a pipelined team of 2 workers: 32 samples per member instead of 16 (the waves that are through take the extra ones; the
-        // hand-overs of a block are shared by 64 samples instead of 32) -- unless a query's near-set radius is below a cell (that
-        // variant has no brute-force scan)
-        bool wide = pipe && !inf && team == 2;
-        for (const QDesc &d : b->h_desc)
-            if (d.status == ST_RUNNING && d.alg != RRT_ALG_STANDARD && d.r2_rewire < 257u) wide = false;
-#else
-        const bool wide = false;
-#endif
-        b->last_wide = wide;
-        b->last_team = team;
-        b->last_inf = inf;
-        b->last_pipe1 = false;
-        b->last_split = false;
-        if (team == 1 && !inf && !continuation && !(b->flags & RRT_FLAG_NOPIPE1)) {
-            // one CU per query, RRTStandard / RRTStar: the barrier-free pipeline (rrt_pipe.h; static LDS only)
-            b->last_pipe1 = true;
-            hipLaunchKernelGGL(rrt_init_kernel<0>, ig, dim3(256), 0, ctx->stream, v);
-            HIPCHK(ctx, hipEventRecord(b->ev0, ctx->stream));
-            hipLaunchKernelGGL(rrt_pipe_kernel, dim3((unsigned)b->Q), dim3(TPB), 0, ctx->stream, v);
-            HIPCHK(ctx, hipEventRecord(b->ev1, ctx->stream));
-            HIPCHK(ctx, hipGetLastError());
-            b->timed = true;
-            return RRT_OK;
-        }
-        const bool split = split_team(team, pipe, inf, wide, b->flags);
-        block_kernel_fn kcommit = nullptr, kwork = nullptr;
-        if (split) {
-            split_kernels_of(team, kcommit, kwork);
-            if (!ctx->stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-            if (!b->ev_fork) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-            if (!b->ev_join) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
-            HIPCHK(ctx, raise_dynamic_lds(ctx->device, reinterpret_cast<const void *>(kcommit), (int)blk_lds_bytes));
-            HIPCHK(ctx, raise_dynamic_lds(ctx->device, reinterpret_cast<const void *>(kwork), (int)blk_lds_bytes));
-        } else {
-            HIPCHK(ctx, raise_dynamic_lds(ctx->device, block_kernel_of(team, pipe, inf, wide), (int)blk_lds_bytes));
-        }
-        hipLaunchKernelGGL(rrt_init_kernel<0>, ig, dim3(256), 0, ctx->stream, v);
-        if (team > 1) HIPCHK(ctx, hipMemsetAsync(b->d_team, 0, (size_t)b->Q * TEAM_BYTES, ctx->stream));  // every polled word, every launch
-        HIPCHK(ctx, hipEventRecord(b->ev0, ctx->stream));
-        if (split) {
-            // the committers (one workgroup of 8 waves per team) on stream2, forked behind the init kernel and the memset; the workers
-            // (team_qpad * team workgroups, members 1 .. team) on the context's stream, which joins stream2 in front of ev1.  The CU
-            // claim above covers both kernels (TeamShape::cus counts the committer); ev0 / ev1 bracket both.
-            HIPCHK(ctx, hipEventRecord(b->ev_fork, ctx->stream));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, b->ev_fork, 0));
-            hipLaunchKernelGGL(kcommit, dim3((unsigned)v.team_qpad), dim3(512), blk_lds_bytes, ctx->stream2, v);
-            BatchView vw = v;
-            vw.member0 = 1;
-            hipLaunchKernelGGL(kwork, dim3((unsigned)(v.team_qpad * team)), dim3(TPB), blk_lds_bytes, ctx->stream, vw);
-            HIPCHK(ctx, hipEventRecord(b->ev_join, ctx->stream2));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_join, 0));
-            b->last_split = true;
-        } else {
-            const dim3 tg(team > 1 ? (unsigned)(v.team_qpad * (team + (pipe ? 1 : 0))) : (unsigned)b->Q);
-            hipLaunchKernelGGL(block_kernel_fn_of(team, pipe, inf, wide), tg, dim3(TPB), blk_lds_bytes, ctx->stream, v);
-        }
-        HIPCHK(ctx, hipEventRecord(b->ev1, ctx->stream));
-        HIPCHK(ctx, hipGetLastError());
-        b->timed = true;
-        return RRT_OK;
+    v.team_qpad = p.qpad;
+    v.lds_chunks = p.lds_chunks;
+    if (p.split) {
+        if (!ctx->stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+        if (!b->ev_fork) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+        if (!b->ev_join) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
     }
-    cu_release(ctx->device, b->claimed_cus);
-    b->claimed_cus = b->Q < ctx->num_cu ? b->Q : ctx->num_cu;  // one workgroup per query: no co-residency needed, the CUs are busy all the same
-    (void)cu_claim(ctx->device, ctx->num_cu, b->claimed_cus, b->claimed_cus);
-    if (b->dub_block) {
-        hipLaunchKernelGGL(rrt_init_kernel<0>, ig, dim3(256), 0, ctx->stream, v);
-        HIPCHK(ctx, hipEventRecord(b->ev0, ctx->stream));
-        hipLaunchKernelGGL(rrt_dubins_block_kernel, dim3((unsigned)b->Q), dim3(TPB), 0, ctx->stream, v);
-        HIPCHK(ctx, hipEventRecord(b->ev1, ctx->stream));
-        HIPCHK(ctx, hipGetLastError());
-        b->timed = true;
-        return RRT_OK;
-    }
-    const size_t lds = expand_lds_bytes(b->lds_chunks);
-    typedef void (*serial_kernel_fn)(BatchView);
-    const serial_kernel_fn kern = (b->flags & RRT_FLAG_DUBINS)  ? static_cast<serial_kernel_fn>(rrt_expand_kernel<false, true>)
-                                  : (b->flags & RRT_FLAG_REWIRE) ? static_cast<serial_kernel_fn>(rrt_expand_kernel<true, false>)
-                                                                 : static_cast<serial_kernel_fn>(rrt_expand_kernel<false, false>);
-    if (b->serial_lds_static == 0) {
-        hipFuncAttributes fa{};
-        HIPCHK(ctx, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)));
-        b->serial_lds_static = fa.sharedSizeBytes + 1;
-    }
-    const size_t lds_static = b->serial_lds_static - 1;
-    if ((int)(lds + lds_static) > ctx->max_lds) return fail(ctx, RRT_E_HIP, "LDS request %zu exceeds %d", lds + lds_static, ctx->max_lds);
-    HIPCHK(ctx, raise_dynamic_lds(ctx->device, reinterpret_cast<const void *>(kern), (int)lds));
+    for (block_kernel_fn k : {p.kern, p.split ? p.row->commit : nullptr, p.split ? p.row->work : nullptr})
+        if (k && p.lds_bytes) HIPCHK(ctx, raise_dynamic_lds(ctx->device, reinterpret_cast<const void *>(k), (int)p.lds_bytes));
+    const dim3 ig((unsigned)((b->bitmap_words + 255) / 256 > 64 ? 64 : (b->bitmap_words + 255) / 256), (unsigned)b->Q);
     hipLaunchKernelGGL(rrt_init_kernel<0>, ig, dim3(256), 0, ctx->stream, v);
+    if (p.team > 1) HIPCHK(ctx, hipMemsetAsync(b->d_team, 0, (size_t)b->Q * TEAM_BYTES, ctx->stream));  // every polled word, every launch
     HIPCHK(ctx, hipEventRecord(b->ev0, ctx->stream));
-    hipLaunchKernelGGL(kern, dim3((unsigned)b->Q), dim3(TPB), lds, ctx->stream, v);
+    if (p.split) {
+        // the committers (one workgroup of 8 waves per team) on stream2, forked behind the init kernel and the memset; the workers
+        // (qpad * team workgroups, members 1 .. team) on the context's stream, which joins stream2 in front of ev1.  The CU
+        // claim covers both kernels (TeamShape::cus counts the committer); ev0 / ev1 bracket both.
+        HIPCHK(ctx, hipEventRecord(b->ev_fork, ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, b->ev_fork, 0));
+        hipLaunchKernelGGL(p.row->commit, dim3((unsigned)p.qpad), dim3(512), p.lds_bytes, ctx->stream2, v);
+        BatchView vw = v;
+        vw.member0 = 1;
+        hipLaunchKernelGGL(p.row->work, dim3((unsigned)(p.qpad * p.team)), dim3(TPB), p.lds_bytes, ctx->stream, vw);
+        HIPCHK(ctx, hipEventRecord(b->ev_join, ctx->stream2));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_join, 0));
+    } else {
+        hipLaunchKernelGGL(p.kern, dim3(p.grid), dim3(TPB), p.lds_bytes, ctx->stream, v);
+    }
     HIPCHK(ctx, hipEventRecord(b->ev1, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     b->timed = true;
@@ -1096,7 +1069,7 @@ extern "C" int rrt_batch_sync(rrt_batch *b) {
     // (Only such launches are continued: the Dubins pipeline's stall exit also says ST_TEAM_FAIL, and there the status stays so that
     // rrt_batch_get_result reports RRT_E_HIP instead of "has not run".)
     bool team_fail = false;
-    const bool can_continue = b->use_block && (b->team > 1 || b->last_pipe1);
+    const bool can_continue = b->use_block && (b->team > 1 || b->last.pipe1);
     for (auto &d : b->h_desc)
         if (d.status == ST_TEAM_FAIL && can_continue) {
             d.status = ST_RUNNING;
@@ -1129,7 +1102,7 @@ extern "C" int rrt_batch_team(rrt_batch *b, int32_t *cus_per_query, int32_t *fal
 extern "C" int rrt_batch_team_info(rrt_batch *b, int32_t out[4]) {
     if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_team_info: NULL");
     out[0] = b->use_block ? b->team : 1;
-    out[1] = b->use_block ? (b->last_team > 0 ? b->last_team : b->team) : 1;
+    out[1] = b->use_block ? (b->last.team > 0 ? b->last.team : b->team) : 1;
     out[2] = b->team_fallbacks;
     out[3] = b->shrunk;
     return RRT_OK;
@@ -1137,7 +1110,7 @@ extern "C" int rrt_batch_team_info(rrt_batch *b, int32_t out[4]) {
 
 extern "C" int rrt_batch_pipelined(rrt_batch *b, int32_t *pipelined) {
     if (!b || !pipelined) return fail(nullptr, RRT_E_ARG, "rrt_batch_pipelined: NULL");
-    *pipelined = (b->use_block && b->team > 1 && b->pipe) ? 1 : 0;
+    *pipelined = (b->use_block && b->team > 1 && b->last.pipe) ? 1 : 0;
     return RRT_OK;
 }
 
@@ -1145,13 +1118,15 @@ extern "C" int rrt_batch_kernel_name(rrt_batch *b, char *buf, int32_t len) {
     if (!b || !buf || len < 1) return fail(nullptr, RRT_E_ARG, "rrt_batch_kernel_name: bad argument");
     char tmp[160];
     if (b->use_block) {
-        const int team = b->last_team > 0 ? b->last_team : b->team;
-        const int bsm = b->last_wide ? 32 : (team <= 4 ? 16 : 64 / team);
-        if (b->last_pipe1) snprintf(tmp, sizeof tmp, "rrt_pipe_kernel");
-        else if (b->last_split)  // (the one-body name first: the two kernels are its halves)
-            snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, true, false> as rrt_block_commit_kernel + rrt_block_work_kernel<%d, %d, false>", team,
-                     bsm, team, bsm);
-        else snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, %s, %s>", team, bsm, (team > 1 && b->pipe) ? "true" : "false", b->last_inf ? "true" : "false");
+        // (a batch not launched yet: the one-body variant of the shape it was created with)
+        const BlockVariant *r = b->last.team > 0 ? b->last.row : find_variant(b->team, b->pipe_team, false, false, false);
+        const char *inf = r && r->inf ? "true" : "false";
+        if (b->last.pipe1) snprintf(tmp, sizeof tmp, "rrt_pipe_kernel");
+        else if (!r) return fail(b->ctx, RRT_E_UNSUPPORTED, "rrt_batch_kernel_name: no team kernel for %d workers per query", b->team);
+        else if (r->commit)  // (the one-body name first: the two kernels are its halves)
+            snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, true, %s> as rrt_block_commit_kernel + rrt_block_work_kernel<%d, %d, %s>", r->G, r->BSM,
+                     inf, r->G, r->BSM, inf);
+        else snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, %s, %s>", r->G, r->BSM, r->pipe ? "true" : "false", inf);
     } else if (b->dub_block) {
         snprintf(tmp, sizeof tmp, "rrt_dubins_block_kernel");
     } else {

@@ -1,20 +1,35 @@
 #!/usr/bin/env python3
 """Table of the kernels' register / scratch / LDS use from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
 
-    python tools/resource_usage.py [ROLE]        (ROLE 1 / 2: only that half of the pipelined kernels, like `make asm-role`)
+    python tools/resource_usage.py [ROLE] [--tus "22 10"]
+    (ROLE 1 / 2: only that half of the pipelined kernels, like `make asm-role`; --tus: these units instead of the Makefile's TUS)
 
-Compiles rrt_engine.hip for gfx950 (device only, no GPU needed) and prints one line per kernel."""
+Compiles the kernel units of kernels_tu.hip for gfx950 (device only, no GPU needed) and prints one line per kernel."""
+import argparse
+import os
 import re
 import subprocess
-import sys
+from concurrent.futures import ThreadPoolExecutor
 
-ROOT = __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__)))
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-       f"-I{ROOT}/include", f"-I{ROOT}/rrtplanner_amd/csrc", "--cuda-device-only", "-S", "-o", "/dev/null", f"{ROOT}/rrtplanner_amd/csrc/rrt_engine.hip",
-       "-Rpass-analysis=kernel-resource-usage"]
-if len(sys.argv) > 1:
-    cmd.insert(1, f"-DRRT_ONLY_ROLE={sys.argv[1]}")
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = f"{ROOT}/rrtplanner_amd/csrc"
+ap = argparse.ArgumentParser()
+ap.add_argument("role", nargs="?", choices=["1", "2"])
+ap.add_argument("--tus", default=re.search(r"^TUS \?= (.*)$", open(f"{CSRC}/Makefile").read(), re.M).group(1))
+args = ap.parse_args()
+
+
+def remarks(tu):
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
+           f"-DRRT_TU={tu}", f"-I{ROOT}/include", f"-I{CSRC}", "--cuda-device-only", "-S", "-o", "/dev/null", f"{CSRC}/kernels_tu.hip",
+           "-Rpass-analysis=kernel-resource-usage"]
+    if args.role:
+        cmd.insert(1, f"-DRRT_ONLY_ROLE={args.role}")
+    return subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+
+
+with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+    out = "\n".join(pool.map(remarks, args.tus.split()))
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"remark: Function Name: (\S+)", line)
