@@ -517,8 +517,10 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
             uint32_t nn_d2 = ld2, nn_idx = lidx;
             wave_min_key_idx(nn_d2, nn_idx);
             int radn = rad0;
-            // nothing in the box, or something that a vertex outside the box could beat: double the box (nearest only)
-            while (jsnap > DB_TINY && (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn) && radn < (W > H ? W : H)) {
+            // nothing in the box, or something that a vertex outside the box could beat: double the box (nearest only), until its
+            // radius covers the map's diagonal -- a box as wide as the map still leaves out the cells farther than its radius
+            const uint32_t diag2 = (uint32_t)((W - 1) * (W - 1) + (H - 1) * (H - 1));
+            while (jsnap > DB_TINY && (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn) && (uint32_t)radn * (uint32_t)radn < diag2) {
                 radn = 2 * radn + 1;
                 ld2 = NONE;
                 lidx = NONE;
@@ -531,6 +533,23 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
                     lvl = nearer ? rc.z : lvl;
                     lvh = nearer ? rc.w : lvh;
                 });
+                nn_d2 = ld2;
+                nn_idx = lidx;
+                wave_min_key_idx(nn_d2, nn_idx);
+            }
+            if (nn_d2 == NONE) {  // no record was dealt at all: every vertex in turn, never a stale lane's record as the nearest
+                ld2 = NONE;
+                lidx = NONE;
+                for (uint32_t k = (uint32_t)lane; k < jsnap; k += 64u) {  // (a lane meets its vertices in index order: strict <)
+                    const uint32_t xy = nodes_g[k], d2 = dist2(xy, xq);
+                    const bool nearer = d2 < ld2;
+                    ld2 = nearer ? d2 : ld2;
+                    lidx = nearer ? k : lidx;
+                    lxy = nearer ? xy : lxy;
+                }
+                const unsigned long long cbits = (unsigned long long)__double_as_longlong(vcost[lidx != NONE ? lidx : 0u]);
+                lvl = (uint32_t)cbits;
+                lvh = (uint32_t)(cbits >> 32);
                 nn_d2 = ld2;
                 nn_idx = lidx;
                 wave_min_key_idx(nn_d2, nn_idx);

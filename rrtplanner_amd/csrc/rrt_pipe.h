@@ -682,9 +682,10 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
             wave_min_key_idx(nn_d2, nn_idx);
             // nothing in the box, or something that a vertex outside the box could beat: the box once more at twice the size, then
             // (a sample far from the tree: a region the tree has not reached, or cannot) every vertex in turn -- 4 bytes and six
-            // instructions per vertex, where ever larger boxes would deal out every record of the map
+            // instructions per vertex, where ever larger boxes would deal out every record of the map.  A box as wide as the map
+            // still leaves out the cells farther than its radius (up to the diagonal): a miss always goes on, whatever the radius.
             int radn = rad0;
-            bool far = jsnap > PP_TINY && (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn) && radn < (W > H ? W : H);
+            bool far = jsnap > PP_TINY && (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn);
             if (far) {
                 radn = 2 * radn + 1;
                 ld2 = NONE;
@@ -701,9 +702,9 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
                 nn_d2 = ld2;
                 nn_idx = lidx;
                 wave_min_key_idx(nn_d2, nn_idx);
-                far = (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn) && radn < (W > H ? W : H);
+                far = nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn;
             }
-            if (far) {
+            if (far || nn_d2 == NONE) {  // (NONE: no record was dealt at all; never a stale lane's record as the nearest)
                 ld2 = NONE;
                 lidx = NONE;
                 for (uint32_t b0 = 0; b0 < jsnap; b0 += 256u) {
