@@ -245,6 +245,24 @@ def make_query(alg, n, xs, xg, samples, r2_rewire=0, goal_d2=0, Cmat=None, headi
     return q, s
 
 
+def _adopt(ctx, child, destroy):
+    """A batch or a device tree holds a pointer to its context and has to be destroyed before it.  The context knows its live
+    children (weakly, to close the Python objects) and their native handles (to destroy them itself when the objects are already
+    beyond reach); a child destroys its handle only while the context still lists it."""
+    if not hasattr(ctx, "_batches"):
+        ctx._batches = weakref.WeakSet()
+        ctx._natives = {}
+    ctx._batches.add(child)
+    ctx._natives[id(child)] = (destroy, child._h.value)
+
+
+def _disown(child, destroy):
+    if child._h:
+        if getattr(child.ctx, "_natives", {}).pop(id(child), None) is not None:
+            getattr(lib(), destroy)(child._h)
+        child._h = C.c_void_p()
+
+
 class Context:
     """One device context: a HIP stream + the device-resident occupancy grid."""
 
@@ -261,6 +279,12 @@ class Context:
     def close(self):
         for b in list(getattr(self, "_batches", ())):  # batches hold a pointer to the context: they go first
             b.close()
+        # ... also those that the garbage collector finalises in the same pass as this context: their weak references are
+        # cleared before any __del__ runs, so the set above no longer names them, and their own __del__ may come after this one
+        natives = getattr(self, "_natives", {})
+        for destroy, h in list(natives.values()):
+            getattr(lib(), destroy)(C.c_void_p(h))
+        natives.clear()
         if self._h:
             lib().rrt_ctx_destroy(self._h)
             self._h = C.c_void_p()
@@ -396,16 +420,12 @@ class DeviceTree:
         self.ctx, self.capacity = ctx, int(capacity)
         self._h = C.c_void_p()
         _check(ctx.handle, lib().rrt_tree_create(ctx.handle, self.capacity, C.byref(self._h)))
-        if not hasattr(ctx, "_batches"):
-            ctx._batches = weakref.WeakSet()
-        ctx._batches.add(self)  # closed before the context, like a batch
+        _adopt(ctx, self, "rrt_tree_destroy")  # closed before the context, like a batch
         self._idx = np.zeros(self.capacity, dtype=np.int32)
         self._los = np.zeros(self.capacity + 1, dtype=np.uint8)
 
     def close(self):
-        if self._h:
-            lib().rrt_tree_destroy(self._h)
-            self._h = C.c_void_p()
+        _disown(self, "rrt_tree_destroy")
 
     def __del__(self):
         try:
@@ -440,15 +460,11 @@ class Batch:
         self._h = C.c_void_p()
         flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, dubins, pipe1, onebody)
         _check(ctx.handle, lib().rrt_batch_create(ctx.handle, self.Q, self.n_cap, flags, C.byref(self._h)))
-        if not hasattr(ctx, "_batches"):
-            ctx._batches = weakref.WeakSet()
-        ctx._batches.add(self)
+        _adopt(ctx, self, "rrt_batch_destroy")
         self._n = [0] * self.Q
 
     def close(self):
-        if self._h:
-            lib().rrt_batch_destroy(self._h)
-            self._h = C.c_void_p()
+        _disown(self, "rrt_batch_destroy")
 
     def __del__(self):
         try:
