@@ -32,8 +32,9 @@ extern "C" {
 #define RRT_E_GOAL_UNREACHABLE (-2) /* rrt.py:317-318 would index og[INT64_MIN,..]: no line of sight, j < n */
 #define RRT_E_HIP (-3)
 #define RRT_E_NOGRID (-4)
-#define RRT_E_UNSUPPORTED (-5)     /* rrt_batch_create / rrt_plan: grid larger than 2048 x 2048 or n > 262143 (the expansion kernels' packed keys; such a
-                                      planner runs host-driven over rrt_tree_query instead, slower, same results); rrt_set_grid: more than 32767 cells per axis */
+#define RRT_E_UNSUPPORTED (-5)     /* rrt_batch_create / rrt_plan: grid larger than 2048 x 2048 (4096 x 4096 with RRT_FLAG_LARGE_GRID) or n > 262143 (the
+                                      expansion kernels' packed keys; such a planner runs host-driven over rrt_tree_query instead, slower, same results);
+                                      RRT_FLAG_LARGE_GRID with a planner or flag it does not take; rrt_set_grid: more than 32767 cells per axis */
 #define RRT_E_COMM (-6)            /* multi-GPU gather: librccl missing, no communicator, RCCL error, unequal slabs */
 
 #define RRT_ALG_STANDARD 0 /* RRTStandard.plan     rrt.py:386 */
@@ -65,6 +66,12 @@ extern "C" {
                                 rrt_block_work_kernel on two streams of the context; kept as a cross-check, the results are the same */
 #define RRT_FLAG_NOPIPE1 32768u /* one CU per query, RRTStandard / RRTStar: the 16-samples-per-pass block kernel instead of the barrier-free
                                   pipeline (rrt_pipe.h); kept as a cross-check, the results are the same */
+#define RRT_FLAG_LARGE_GRID 65536u /* opt-in: grids up to 4096 x 4096 (default: 2048 x 2048).  RRTStandard / RRTStar only, ONE CU per query on
+                                     rrt_pipe_large_kernel (rrt_pipe.h, LARGE: 25-bit squared distances), whatever the size of the grid or of
+                                     the batch; no teams.  RRT_E_UNSUPPORTED together with RRT_ALG_INFORMED, the Dubins planners,
+                                     RRT_FLAG_REWIRE, RRT_FLAG_DUBINS, RRT_FLAG_SERIAL or RRT_FLAG_NOPIPE1.  A query of 4096 x 4096 cells keeps
+                                     268 MB of cell records on the device.  Should the pipeline stall (a bounded wait inside the kernel), the
+                                     query ends with RRT_E_HIP: no other kernel takes such a grid. */
 #define RRT_FLAG_TEAM_MAX(g) ((uint32_t)(g) << 8) /* cap the team size at g CUs per query (g = 2, 4, ... 64; 0 = no cap) */
 
 typedef struct rrt_ctx rrt_ctx;
@@ -125,8 +132,8 @@ int rrt_ctx_create(int32_t device_id, rrt_ctx **out);
 int rrt_ctx_destroy(rrt_ctx *ctx); /* destroy the batches created on a context before the context itself */
 const char *rrt_last_error_string(rrt_ctx *ctx); /* ctx may be NULL */
 /* RRT.__init__ / set_og (rrt.py:64-65, :261-272): og_nonzero is (W,H) C-order, 1 = obstacle.  Up to 32767 cells per axis; the
- * expansion kernels (rrt_batch_*, rrt_plan*) take grids up to 2048 x 2048, larger ones serve rrt_tree_query and
- * rrt_prim_collisionfree only. */
+ * expansion kernels (rrt_batch_*, rrt_plan*) take grids up to 2048 x 2048, with RRT_FLAG_LARGE_GRID up to 4096 x 4096; larger ones
+ * serve rrt_tree_query and rrt_prim_collisionfree only. */
 int rrt_set_grid(rrt_ctx *ctx, const uint8_t *og_nonzero, int32_t W, int32_t H);
 
 /* Device-resident noise grids (counterpart of oggen.perlin_occupancygrid, oggen.py:7-45: fractal gradient noise, min-max
@@ -231,6 +238,14 @@ int rrt_tree_query(rrt_tree *t, int32_t x, int32_t y, int64_t r2, int32_t *neare
 /* RRT.collisionfree (rrt.py:183-229) for m segments ab[k] = {ax,ay,bx,by}; cells = grid cells the
  * reference's walk reads before it returns. */
 int rrt_prim_collisionfree(rrt_ctx *ctx, const int32_t *ab, int32_t m, uint8_t *out_free, int32_t *out_cells);
+/* the same with the walk named: RRT_WALK_AUTO (what rrt_prim_collisionfree picks by the grid's size), RRT_WALK_U24 (grids up to
+ * 2048 x 2048), RRT_WALK_U26 (the large-grid pipeline's, grids up to 4096 x 4096), RRT_WALK_WIDE (64-bit division, any grid).
+ * RRT_E_UNSUPPORTED when the grid is larger than the walk takes. */
+#define RRT_WALK_AUTO 0
+#define RRT_WALK_U24 1
+#define RRT_WALK_U26 2
+#define RRT_WALK_WIDE 3
+int rrt_prim_collisionfree_walk(rrt_ctx *ctx, const int32_t *ab, int32_t m, int32_t walk, uint8_t *out_free, int32_t *out_cells);
 /* near()[0] (rrt.py:150-155,:422) and |within()| (rrt.py:176-181) of m query points against j nodes */
 int rrt_prim_nearest_within(rrt_ctx *ctx, const int32_t *pts, int32_t j, const int32_t *xq, int32_t m,
                             int64_t r2, int32_t *out_nearest, int32_t *out_within_count,
@@ -239,6 +254,8 @@ int rrt_prim_nearest_within(rrt_ctx *ctx, const int32_t *pts, int32_t j, const i
 int rrt_prim_sqrt_u32(rrt_ctx *ctx, uint32_t lo, uint32_t count, double *out);
 /* the block kernel's short sqrt, valid for radicands below 2^24 */
 int rrt_prim_sqrt_u24(rrt_ctx *ctx, uint32_t lo, uint32_t count, double *out);
+/* the large-grid pipeline's, valid for radicands below 2^25 */
+int rrt_prim_sqrt_u25(rrt_ctx *ctx, uint32_t lo, uint32_t count, double *out);
 /* sqrt of arbitrary doubles as the kernels compute it (ellipse minor axis, rrt.py:622) */
 int rrt_prim_sqrt_f64(rrt_ctx *ctx, const double *in, uint32_t count, double *out);
 

@@ -93,4 +93,27 @@ RRT_LINE_FN void rrt_line_cell_wide(const rrt_line_t *l, int32_t k, int32_t *x, 
     }
 }
 
+/* The same cell for numerators below 2^26 (grids up to 4096 x 4096: 2 * 4095 * 4095 + 4095 < 2^25) without a 64-bit division: the
+ * float estimate of rrt_line_cell, under the weaker claim that it holds here.  (float)num, rcp_den and their product each carry a
+ * relative error of at most 2^-24, and the quotient is at most k <= major < 2^13 (minor <= major), so the estimate is off by less
+ * than 2^13 * 3.1 * 2^-24 < 2^-9 from the true quotient: its truncation is floor(num / den) or one off on either side.  m * den
+ * then lies within den of num, below 2^26 + 2^14 in magnitude, so the remainder is exact in 32-bit integers and moves m by at
+ * most one step to the exact floor.  tests/test_large_grid_cpu.py checks it against rrt_line_cell_wide. */
+RRT_LINE_FN void rrt_line_cell_u26(const rrt_line_t *l, int32_t k, int32_t *x, int32_t *y) {
+    int32_t den = 2 * l->major;
+    int32_t num = 2 * l->minor * k + l->major;
+    int32_t m = (int32_t)((float)num * l->rcp_den);
+    int32_t r = num - m * den;
+    m += (r >= den) ? 1 : 0;
+    m -= (r < 0) ? 1 : 0;
+    if (den == 0) m = 0;
+    if (l->xmajor) {
+        *x = l->x0 + l->sx * k;
+        *y = l->y0 + l->sy * m;
+    } else {
+        *x = l->x0 + l->sx * m;
+        *y = l->y0 + l->sy * k;
+    }
+}
+
 #endif /* RRT_LINE_H */

@@ -33,16 +33,21 @@ FLAG_REWIRE = 32
 FLAG_DUBINS = 64
 FLAG_ONEBODY = 128
 FLAG_NOPIPE1 = 32768
+FLAG_LARGE_GRID = 65536
+WALK_AUTO, WALK_U24, WALK_U26, WALK_WIDE = 0, 1, 2, 3  # rrt_prim_collisionfree_walk
 
 
-def kernel_flags(logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, dubins=False, pipe1=True, onebody=False):
+def kernel_flags(logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, dubins=False, pipe1=True, onebody=False,
+                 large_grid=False):
     """flags word of rrt_plan / rrt_batch_create.  team: None = as many CUs per query as fit (up to 64), 1 = one CU,
     2..64 = cap on the team's workers; pipe = False: no pipelined teams (workers + one committing CU); team_fault = the
-    fault-injection flag of the tests."""
+    fault-injection flag of the tests; large_grid = grids up to 4096 x 4096, RRTStandard / RRTStar on one CU per query
+    (rrt_pipe_large_kernel)."""
     f = (FLAG_LOGS if logs else 0) | (FLAG_SERIAL if serial else 0) | (FLAG_TEAM_FAULT if team_fault else 0) | (0 if pipe else FLAG_NOPIPE)
     f |= FLAG_REWIRE if rewire else 0  # the opt-in true rewire (not the reference's behaviour)
     f |= FLAG_DUBINS if dubins else 0
     f |= 0 if pipe1 else FLAG_NOPIPE1  # one CU per query: the block kernel instead of the barrier-free pipeline (a cross-check)
+    f |= FLAG_LARGE_GRID if large_grid else 0
     f |= FLAG_ONEBODY if onebody else 0  # pipelined teams of 8+: committer and workers as one kernel instead of two (a cross-check)
     if team == 1:
         f |= FLAG_NOTEAM
@@ -63,6 +68,7 @@ SYMBOLS = (
     "rrt_plan", "rrt_plan_resume", "rrt_plan_batch",
     "rrt_tree_create", "rrt_tree_destroy", "rrt_tree_reset", "rrt_tree_append", "rrt_tree_query",
     "rrt_prim_collisionfree", "rrt_prim_nearest_within", "rrt_prim_sqrt_u32", "rrt_prim_sqrt_u24", "rrt_prim_sqrt_f64",
+    "rrt_prim_collisionfree_walk", "rrt_prim_sqrt_u25",
 )
 
 
@@ -155,6 +161,8 @@ def lib():
             "rrt_prim_sqrt_u32": ([vp, u32, u32, vp], C.c_int),
             "rrt_prim_sqrt_u24": ([vp, u32, u32, vp], C.c_int),
             "rrt_prim_sqrt_f64": ([vp, vp, u32, vp], C.c_int),
+            "rrt_prim_collisionfree_walk": ([vp, vp, i32, i32, vp, vp], C.c_int),
+            "rrt_prim_sqrt_u25": ([vp, u32, u32, vp], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -349,9 +357,10 @@ class Context:
         self.allreduce([0.0])
 
     # ---- one-shot ----
-    def plan(self, query, n, logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, pipe1=True, onebody=False):
+    def plan(self, query, n, logs=False, serial=False, team=None, team_fault=False, pipe=True, rewire=False, pipe1=True, onebody=False,
+             large_grid=False):
         res = ResultArrays(n, logs, headings=query.alg >= ALG_DUBINS)
-        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, pipe1=pipe1, onebody=onebody)
+        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, pipe1=pipe1, onebody=onebody, large_grid=large_grid)
         rc = lib().rrt_plan(self._h, C.byref(query), flags, C.byref(res.c))
         _check(self._h, rc, ok=(RRT_OK, RRT_NEED_UNITBALL, RRT_E_GOAL_UNREACHABLE))
         return rc, res
@@ -376,12 +385,16 @@ class Context:
         return rc, res
 
     # ---- primitives ----
-    def prim_collisionfree(self, ab):
+    def prim_collisionfree(self, ab, walk=WALK_AUTO):
+        """walk: which closed form of the line walk the device runs (WALK_AUTO: by the grid's size; WALK_U26: the large-grid kernel's)"""
         ab = np.ascontiguousarray(ab, dtype=np.int32).reshape(-1, 4)
         m = ab.shape[0]
         free = np.zeros(m, dtype=np.uint8)
         cells = np.zeros(m, dtype=np.int32)
-        _check(self._h, lib().rrt_prim_collisionfree(self._h, ab.ctypes.data, m, free.ctypes.data, cells.ctypes.data))
+        if walk == WALK_AUTO:
+            _check(self._h, lib().rrt_prim_collisionfree(self._h, ab.ctypes.data, m, free.ctypes.data, cells.ctypes.data))
+        else:
+            _check(self._h, lib().rrt_prim_collisionfree_walk(self._h, ab.ctypes.data, m, int(walk), free.ctypes.data, cells.ctypes.data))
         return free.astype(bool), cells
 
     def prim_nearest_within(self, pts, xq, r2):
@@ -403,6 +416,11 @@ class Context:
     def prim_sqrt_u24(self, lo, count):
         out = np.zeros(count, dtype=np.float64)
         _check(self._h, lib().rrt_prim_sqrt_u24(self._h, int(lo), int(count), out.ctypes.data))
+        return out
+
+    def prim_sqrt_u25(self, lo, count):
+        out = np.zeros(count, dtype=np.float64)
+        _check(self._h, lib().rrt_prim_sqrt_u25(self._h, int(lo), int(count), out.ctypes.data))
         return out
 
     def prim_sqrt_f64(self, x):
@@ -455,10 +473,10 @@ class Batch:
     """Q independent queries resident on the device (rrt_batch_*)."""
 
     def __init__(self, ctx: Context, Q: int, n_cap: int, logs: bool = False, serial: bool = False, team=None, team_fault: bool = False,
-                 pipe: bool = True, rewire: bool = False, dubins: bool = False, pipe1: bool = True, onebody: bool = False):
+                 pipe: bool = True, rewire: bool = False, dubins: bool = False, pipe1: bool = True, onebody: bool = False, large_grid: bool = False):
         self.ctx, self.Q, self.n_cap, self.logs, self.dubins = ctx, int(Q), int(n_cap), logs, dubins
         self._h = C.c_void_p()
-        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, dubins, pipe1, onebody)
+        flags = kernel_flags(logs, serial, team, team_fault, pipe, rewire, dubins, pipe1, onebody, large_grid)
         _check(ctx.handle, lib().rrt_batch_create(ctx.handle, self.Q, self.n_cap, flags, C.byref(self._h)))
         _adopt(ctx, self, "rrt_batch_destroy")
         self._n = [0] * self.Q

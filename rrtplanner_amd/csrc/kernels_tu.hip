@@ -8,6 +8,12 @@
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_pipe.h"
 
+#elif RRT_TU == 4  // the same pipeline for grids up to 4096 x 4096 (RRT_FLAG_LARGE_GRID): rrt_pipe_large_kernel
+#define RRT_BLOCK_DECL_ONLY
+#define RRT_SERIAL_DECL_ONLY
+#define RRT_PIPE_LARGE_TU
+#include "rrt_pipe.h"
+
 #elif RRT_TU == 2  // Dubins planners: the pipeline, and the one-sample-per-iteration kernel kept as its cross-check
 #include "rrt_dubins_block.h"
 namespace rrtdev {

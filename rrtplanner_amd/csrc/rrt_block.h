@@ -192,6 +192,27 @@ __device__ __forceinline__ double sqrt_u24(uint32_t d2) {
     return d2 == 0 ? 0.0 : g;
 }
 
+// The same for an integer below 2^25 (grids up to 4096 x 4096, the large-grid pipeline of rrt_pipe.h).  The coupled step leaves g and h
+// with relative errors of the order of the seed's squared (~2^-50); each correction g += (x - g*g) * h squares the error again, so
+// the first leaves g within an ulp and the later ones can only move it onto the correctly rounded root (x - g*g is exact in the
+// fma, and the root of an integer is never half way between two doubles).  One correction more than sqrt_u24: nothing in the
+// argument depends on x < 2^24, but that bound is all its test covers.  tests/test_large_grid_gpu.py checks every input below 2^25.
+__device__ __forceinline__ double sqrt_u25(uint32_t d2) {
+    const double x = (double)d2;
+    double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+    double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    double d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    return d2 == 0 ? 0.0 : g;
+}
+
 // key = 256*d2 + tag of one node against one sample (both pre-scaled by 16): v_pk_sub_i16 + v_dot2_i32_i16.
 // Inline asm: hipcc pads no hazards around it; both instructions only read SALU-written scalars and plain VGPRs.
 __device__ __forceinline__ uint32_t key16(uint32_t node_s, uint32_t q_s, uint32_t tag) {

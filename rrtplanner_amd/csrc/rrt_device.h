@@ -29,7 +29,8 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double f64_inf() { return __longlong_as_double(RRT_INF_BITS); }
 
 // Nodes and samples are packed int16x2: x in the low half, y in the high half.  Grids are
-// at most 2048 x 2048 on this path, so x,y < 2^11 and d2 < 2^23.
+// at most 2048 x 2048 on this path, so x,y < 2^11 and d2 < 2^23 -- except for the large-grid
+// instantiation of the one-CU pipeline (rrt_pipe.h, LARGE): up to 4096 x 4096, x,y < 2^12, d2 < 2^25.
 __device__ __forceinline__ uint32_t pack_xy(int x, int y) { return ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16); }
 __device__ __forceinline__ int ux(uint32_t p) { return (int)(p & 0xffffu); }
 __device__ __forceinline__ int uy(uint32_t p) { return (int)(p >> 16); }
@@ -175,6 +176,43 @@ __device__ __forceinline__ bool los_wave(const uint8_t *__restrict__ og, int H, 
             if (k <= L) {
                 int x, y;
                 rrt_line_cell(&l, k, &x, &y);
+                v[g] = og[(uint32_t)(x * H + y)];
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            unsigned long long m = __ballot(v[g] != 0);
+            if (m) {
+                cells = k0 + 64 * g + (int)__builtin_ctzll(m) + 1;
+                return false;
+            }
+        }
+    }
+    cells = L + 1;
+    return true;
+}
+
+// The same test on grids up to 4096 x 4096 (the large-grid pipeline, rrt_pipe.h): long segments take the cell of the walk from
+// rrt_line_cell_u26 (numerators below 2^26, no 64-bit division); segments shorter than 64 steps keep short_line, whose proof only
+// needs num <= 8001 and whose base x0 * H + y0 < 2^24 fits an int.
+__device__ __forceinline__ bool los_wave_large(const uint8_t *__restrict__ og, int H, uint32_t a, uint32_t b, int lane, int &cells) {
+    rrt_line_t l = rrt_line_setup(ux(a), uy(a), ux(b), uy(b));
+    const int L = l.major;
+    if (L < 64) {
+        bool occ = false;
+        if (lane <= L) occ = og[short_line_cell(short_line(a, b, H), lane)] != 0;
+        unsigned long long m = __ballot(occ);
+        cells = m ? (int)__builtin_ctzll(m) + 1 : L + 1;
+        return m == 0;
+    }
+    for (int k0 = 0; k0 <= L; k0 += 256) {
+        uint8_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int k = k0 + 64 * g + lane;
+            if (k <= L) {
+                int x, y;
+                rrt_line_cell_u26(&l, k, &x, &y);
                 v[g] = og[(uint32_t)(x * H + y)];
             }
         }

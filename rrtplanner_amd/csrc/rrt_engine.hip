@@ -31,6 +31,7 @@ using namespace rrtdev;
 static thread_local std::string g_last_error;
 
 constexpr int RRT_GRID_FAST = 2048;  // the expansion kernels: coordinates below 2^11, squared distances below 2^24 (packed scan keys, sqrt_u24)
+constexpr int RRT_GRID_LARGE = 4096; // RRT_FLAG_LARGE_GRID (rrt_pipe_large_kernel): coordinates below 2^12, squared distances below 2^25
 constexpr int RRT_GRID_MAX = 32767;  // the host-driven path (rrt_tree_query, rrt_prim_collisionfree): 16-bit packed coordinates whose differences fit int16
 
 // Host copy of a batch's query descriptors in page-locked memory: the per-step copies to and from the device (rrt_batch_rearm,
@@ -134,6 +135,7 @@ struct LaunchPlan {
     bool wide = false;          // a team variant with more than 16 samples per member
     bool split = false;         // committers and workers as two kernels (rrt_block_commit_kernel + rrt_block_work_kernel)
     bool pipe1 = false;         // the barrier-free one-CU kernel (rrt_pipe.h)
+    bool large = false;         // ... in its form for grids up to 4096 x 4096 (RRT_FLAG_LARGE_GRID: the only kernel such a batch runs)
     bool continuation = false;  // of a launch that stopped at a block boundary: one CU per query, and the block kernel takes it from there
     const BlockVariant *row = nullptr;  // the team variant, or nullptr for a kernel that is none (pipe1, Dubins, one sample per iteration)
     block_kernel_fn kern = nullptr;     // the kernel of a launch that is one kernel (row->one, or the plain kernel)
@@ -586,9 +588,25 @@ static bool two_cus_run_the_pipeline(const rrt_batch *b) {
 extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t flags, rrt_batch **out) {
     if (!ctx || !out || Q < 1 || n_cap < 1) return fail(ctx, RRT_E_ARG, "rrt_batch_create: bad argument");
     if (!ctx->og) return fail(ctx, RRT_E_NOGRID, "rrt_batch_create: call rrt_set_grid first");
-    if (ctx->W > RRT_GRID_FAST || ctx->H > RRT_GRID_FAST)
-        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_create: the expansion kernels take grids up to %dx%d (24-bit squared distances); a %dx%d grid runs "
-                    "through the host-driven path (rrt_tree_query)", RRT_GRID_FAST, RRT_GRID_FAST, ctx->W, ctx->H);
+    const bool large = (flags & RRT_FLAG_LARGE_GRID) != 0;
+    if (large) {
+        // one kernel takes such a batch (rrt_pipe_large_kernel, RRTStandard / RRTStar, one CU per query): whatever asks for another is refused
+        const struct { uint32_t bit; const char *what; } other[] = {
+            {RRT_FLAG_REWIRE, "RRT_FLAG_REWIRE (the opt-in rewire runs on the one-sample-per-iteration kernel)"},
+            {RRT_FLAG_DUBINS, "RRT_FLAG_DUBINS (the Dubins planners have kernels of their own)"},
+            {RRT_FLAG_SERIAL, "RRT_FLAG_SERIAL (the one-sample-per-iteration kernel)"},
+            {RRT_FLAG_NOPIPE1, "RRT_FLAG_NOPIPE1 (the block kernel)"}};
+        for (const auto &o : other)
+            if (flags & o.bit)
+                return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_create: RRT_FLAG_LARGE_GRID together with %s: those kernels take grids up to %dx%d", o.what,
+                            RRT_GRID_FAST, RRT_GRID_FAST);
+        if (ctx->W > RRT_GRID_LARGE || ctx->H > RRT_GRID_LARGE)
+            return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_create: RRT_FLAG_LARGE_GRID takes grids up to %dx%d (25-bit squared distances); a %dx%d grid runs "
+                        "through the host-driven path (rrt_tree_query)", RRT_GRID_LARGE, RRT_GRID_LARGE, ctx->W, ctx->H);
+    } else if (ctx->W > RRT_GRID_FAST || ctx->H > RRT_GRID_FAST)
+        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_create: the expansion kernels take grids up to %dx%d (24-bit squared distances; RRT_FLAG_LARGE_GRID: up to "
+                    "%dx%d for RRTStandard / RRTStar); a %dx%d grid runs through the host-driven path (rrt_tree_query)", RRT_GRID_FAST, RRT_GRID_FAST,
+                    RRT_GRID_LARGE, RRT_GRID_LARGE, ctx->W, ctx->H);
     if ((long long)n_cap + 1 > 64LL * CHUNK)
         return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_create: n=%d exceeds %d nodes", n_cap, 64 * CHUNK - 1);
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -610,7 +628,7 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     // the opt-in rewire and the Dubins planners run on the one-sample-per-iteration kernel
     b->use_block = !(flags & (RRT_FLAG_SERIAL | RRT_FLAG_REWIRE | RRT_FLAG_DUBINS));
     b->dub_block = (flags & RRT_FLAG_DUBINS) && !(flags & RRT_FLAG_SERIAL);
-    if (b->use_block && !(flags & RRT_FLAG_NOTEAM)) {
+    if (b->use_block && !(flags & RRT_FLAG_NOTEAM) && !large) {  // (a large-grid batch: one CU per query)
         int want = (int)((flags >> 8) & 0x7fu);
         if (want == 0) want = TEAM_MAX;
 #ifdef RRT_STAMPS
@@ -765,7 +783,12 @@ extern "C" int rrt_batch_set_query(rrt_batch *b, int32_t q, const rrt_query *qu)
     d.xs[1] = qu->xs[1];
     d.xg[0] = qu->xg[0];
     d.xg[1] = qu->xg[1];
-    const int64_t cap = 1 << 24;  // any d2 on a 2048x2048 grid is below this
+    if ((b->flags & RRT_FLAG_LARGE_GRID) && qu->alg != RRT_ALG_STANDARD && qu->alg != RRT_ALG_STAR)
+        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_set_query: alg=%d (RRT_ALG_INFORMED) on a batch created with RRT_FLAG_LARGE_GRID: the large-grid "
+                    "kernel runs RRTStandard and RRTStar only", qu->alg);
+    // any d2 on a 2048x2048 grid is below 2^24, on a 4096x4096 grid below 2^25: the clamp changes no answer; the kernels rely on
+    // r2 <= cap (a dead lane's d2 = 2^32 - 1 is never inside the ball, and the stream radius, doubled and squared, does not wrap)
+    const int64_t cap = (b->flags & RRT_FLAG_LARGE_GRID) ? (1 << 26) : (1 << 24);
     d.r2_rewire = (uint32_t)(qu->r2_rewire < 0 ? 0 : (qu->r2_rewire > cap ? cap : qu->r2_rewire));
     d.goal_d2 = (uint32_t)(qu->goal_d2 < 0 ? 0 : (qu->goal_d2 > cap ? cap : qu->goal_d2));
     for (int k = 0; k < 4; ++k) d.C[k] = qu->C[k];
@@ -962,9 +985,12 @@ static int plan_launch(rrt_batch *b, LaunchPlan &p) {
     if (p.team == 1 && !inf && !p.continuation && !(b->flags & RRT_FLAG_NOPIPE1)) {
         // one CU per query, RRTStandard / RRTStar: the barrier-free pipeline (rrt_pipe.h; static LDS only)
         p.pipe1 = true;
-        p.kern = rrt_pipe_kernel;
+        p.large = (b->flags & RRT_FLAG_LARGE_GRID) != 0;
+        p.kern = p.large ? rrt_pipe_large_kernel : rrt_pipe_kernel;
         return RRT_OK;
     }
+    if (b->flags & RRT_FLAG_LARGE_GRID)  // (never: such a batch holds no Informed query and is not continued)
+        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_launch: only rrt_pipe_large_kernel takes a batch created with RRT_FLAG_LARGE_GRID");
     p.lds_bytes = (size_t)MAX_CELLS * sizeof(uint32_t) + (lists ? BLOCK_LIST_LDS_BYTES : 0) + expand_lds_bytes(p.lds_chunks);
 #ifndef RRT_NO_WIDE
     // a pipelined team of 2 workers: 32 samples per member instead of 16 (the waves that are through take the extra ones; the
@@ -1069,7 +1095,8 @@ extern "C" int rrt_batch_sync(rrt_batch *b) {
     // (Only such launches are continued: the Dubins pipeline's stall exit also says ST_TEAM_FAIL, and there the status stays so that
     // rrt_batch_get_result reports RRT_E_HIP instead of "has not run".)
     bool team_fail = false;
-    const bool can_continue = b->use_block && (b->team > 1 || b->last.pipe1);
+    // (nor a large-grid batch: the block kernel cannot take its grid; rrt_batch_get_result reports RRT_E_HIP)
+    const bool can_continue = b->use_block && (b->team > 1 || b->last.pipe1) && !(b->flags & RRT_FLAG_LARGE_GRID);
     for (auto &d : b->h_desc)
         if (d.status == ST_TEAM_FAIL && can_continue) {
             d.status = ST_RUNNING;
@@ -1121,7 +1148,8 @@ extern "C" int rrt_batch_kernel_name(rrt_batch *b, char *buf, int32_t len) {
         // (a batch not launched yet: the one-body variant of the shape it was created with)
         const BlockVariant *r = b->last.team > 0 ? b->last.row : find_variant(b->team, b->pipe_team, false, false, false);
         const char *inf = r && r->inf ? "true" : "false";
-        if (b->last.pipe1) snprintf(tmp, sizeof tmp, "rrt_pipe_kernel");
+        if (b->flags & RRT_FLAG_LARGE_GRID) snprintf(tmp, sizeof tmp, "rrt_pipe_large_kernel");  // (the only kernel of such a batch, launched or not)
+        else if (b->last.pipe1) snprintf(tmp, sizeof tmp, "rrt_pipe_kernel");
         else if (!r) return fail(b->ctx, RRT_E_UNSUPPORTED, "rrt_batch_kernel_name: no team kernel for %d workers per query", b->team);
         else if (r->commit)  // (the one-body name first: the two kernels are its halves)
             snprintf(tmp, sizeof tmp, "rrt_expand_block_kernel<%d, %d, true, %s> as rrt_block_commit_kernel + rrt_block_work_kernel<%d, %d, %s>", r->G, r->BSM,
@@ -1202,6 +1230,9 @@ extern "C" int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out) {
             HIPCHK(ctx, hipMemcpyAsync(out->j_log, b->d_j_log + o, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (d.status == ST_TEAM_FAIL && (b->flags & RRT_FLAG_LARGE_GRID))
+        return fail(ctx, RRT_E_HIP, "query %d: the large-grid pipeline stalled (a bounded wait inside the kernel expired at sample %d); the tree up to there is "
+                    "consistent, and no other kernel takes a batch created with RRT_FLAG_LARGE_GRID", q, d.i);
     if (d.status == ST_TEAM_FAIL)
         return fail(ctx, RRT_E_HIP, b->dub_block ? "query %d: the Dubins pipeline stalled (a bounded wait inside the kernel expired at sample %d); the tree up to there is consistent"
                                                  : "query %d: the workgroups of its team (%d) were not resident together (a hand-off timed out); "
@@ -1620,9 +1651,14 @@ extern "C" int rrt_tree_query(rrt_tree *t, int32_t x, int32_t y, int64_t r2, int
 
 // ---- primitives ---------------------------------------------------------------------------
 
-extern "C" int rrt_prim_collisionfree(rrt_ctx *ctx, const int32_t *ab, int32_t m, uint8_t *out_free, int32_t *out_cells) {
-    if (!ctx || !ab || m < 0 || !out_free) return fail(ctx, RRT_E_ARG, "rrt_prim_collisionfree: bad argument");
+extern "C" int rrt_prim_collisionfree_walk(rrt_ctx *ctx, const int32_t *ab, int32_t m, int32_t walk, uint8_t *out_free, int32_t *out_cells) {
+    if (!ctx || !ab || m < 0 || !out_free || walk < RRT_WALK_AUTO || walk > RRT_WALK_WIDE) return fail(ctx, RRT_E_ARG, "rrt_prim_collisionfree: bad argument");
     if (!ctx->og) return fail(ctx, RRT_E_NOGRID, "rrt_prim_collisionfree: no grid");
+    const int side = ctx->W > ctx->H ? ctx->W : ctx->H;
+    if (walk == RRT_WALK_AUTO) walk = side > RRT_GRID_FAST ? RRT_WALK_WIDE : RRT_WALK_U24;
+    if ((walk == RRT_WALK_U24 && side > RRT_GRID_FAST) || (walk == RRT_WALK_U26 && side > RRT_GRID_LARGE))
+        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_prim_collisionfree: walk %d takes grids up to %d cells per axis, the grid is %dx%d", walk,
+                    walk == RRT_WALK_U24 ? RRT_GRID_FAST : RRT_GRID_LARGE, ctx->W, ctx->H);
     if (m == 0) return RRT_OK;
     for (int k = 0; k < m; ++k)
         if (ab[4 * k] < 0 || ab[4 * k] >= ctx->W || ab[4 * k + 2] < 0 || ab[4 * k + 2] >= ctx->W || ab[4 * k + 1] < 0 ||
@@ -1637,16 +1673,19 @@ extern "C" int rrt_prim_collisionfree(rrt_ctx *ctx, const int32_t *ab, int32_t m
     HIPCHK(ctx, tmp.alloc(&d_free, (size_t)m));
     HIPCHK(ctx, hipMemcpyAsync(d_ab, ab, (size_t)m * 4 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     const int waves_per_block = 4;
-    if (ctx->W > RRT_GRID_FAST || ctx->H > RRT_GRID_FAST)
-        hipLaunchKernelGGL(prim_los_kernel<true>, dim3((unsigned)((m + waves_per_block - 1) / waves_per_block)), dim3(64 * waves_per_block), 0,
-                           ctx->stream, ctx->og, ctx->H, d_ab, m, d_free, d_cells);
-    else
-        hipLaunchKernelGGL(prim_los_kernel<false>, dim3((unsigned)((m + waves_per_block - 1) / waves_per_block)), dim3(64 * waves_per_block), 0,
-                           ctx->stream, ctx->og, ctx->H, d_ab, m, d_free, d_cells);
+    const dim3 grid((unsigned)((m + waves_per_block - 1) / waves_per_block)), block(64 * waves_per_block);
+    if (walk == RRT_WALK_WIDE) hipLaunchKernelGGL(prim_los_kernel<1>, grid, block, 0, ctx->stream, ctx->og, ctx->H, d_ab, m, d_free, d_cells);
+    else if (walk == RRT_WALK_U26) hipLaunchKernelGGL(prim_los_kernel<2>, grid, block, 0, ctx->stream, ctx->og, ctx->H, d_ab, m, d_free, d_cells);
+    else hipLaunchKernelGGL(prim_los_kernel<0>, grid, block, 0, ctx->stream, ctx->og, ctx->H, d_ab, m, d_free, d_cells);
+    HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out_free, d_free, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
     if (out_cells) HIPCHK(ctx, hipMemcpyAsync(out_cells, d_cells, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RRT_OK;
+}
+
+extern "C" int rrt_prim_collisionfree(rrt_ctx *ctx, const int32_t *ab, int32_t m, uint8_t *out_free, int32_t *out_cells) {
+    return rrt_prim_collisionfree_walk(ctx, ab, m, RRT_WALK_AUTO, out_free, out_cells);
 }
 
 extern "C" int rrt_prim_nearest_within(rrt_ctx *ctx, const int32_t *pts, int32_t j, const int32_t *xq, int32_t m, int64_t r2,
@@ -1714,6 +1753,20 @@ extern "C" int rrt_prim_sqrt_u24(rrt_ctx *ctx, uint32_t lo, uint32_t count, doub
     double *d = nullptr;
     HIPCHK(ctx, tmp.alloc(&d, (size_t)count * sizeof(double)));
     hipLaunchKernelGGL(prim_sqrt_u24_kernel, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, lo, count, d);
+    HIPCHK(ctx, hipMemcpyAsync(out, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RRT_OK;
+}
+
+extern "C" int rrt_prim_sqrt_u25(rrt_ctx *ctx, uint32_t lo, uint32_t count, double *out) {
+    if (!ctx || !out) return fail(ctx, RRT_E_ARG, "rrt_prim_sqrt_u25: NULL");
+    if ((unsigned long long)lo + count > (1ull << 25)) return fail(ctx, RRT_E_ARG, "rrt_prim_sqrt_u25: radicand >= 2^25");
+    if (count == 0) return RRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevTmp tmp;
+    double *d = nullptr;
+    HIPCHK(ctx, tmp.alloc(&d, (size_t)count * sizeof(double)));
+    hipLaunchKernelGGL(prim_sqrt_u25_kernel, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, lo, count, d);
     HIPCHK(ctx, hipMemcpyAsync(out, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RRT_OK;

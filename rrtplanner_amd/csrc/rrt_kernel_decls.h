@@ -7,6 +7,7 @@
 namespace rrtdev {
 
 __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv);
+__global__ __launch_bounds__(TPB) void rrt_pipe_large_kernel(BatchView bv);  // grids up to 4096 x 4096 (unit 4)
 __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv);
 
 }  // namespace rrtdev

@@ -201,7 +201,8 @@ constexpr int G2G_U = 4;      // nodes a wave tests per round
 // The nodes considered are kfirst + m * kstep, m < cnt (all of them: 0, 1, j; a team gives each member a stripe and takes the
 // minimum of the stripes' answers).
 // NT: threads of the calling workgroup (a pipelined team's committer may run as a workgroup of its own with fewer waves).
-template <bool DUB = false, int NT = TPB>
+// LARGE: grids up to 4096 x 4096 (the lines of sight by los_wave_large; the costs are sqrt_u32's, exact for any radicand).
+template <bool DUB = false, int NT = TPB, bool LARGE = false>
 __device__ __forceinline__ void go2goal_phase(const uint8_t *og, int H, const uint32_t *nodes_g, const double *vcost, int kfirst, int kstep,
                                               int cnt, uint32_t xg, uint32_t *order, RRT_LDS uint32_t *lds16k, BSlot *bslots, int t, int lane,
                                               int wave, double &pc, uint32_t &pi, const uint8_t *heading = nullptr, int hg = 0, DubCfg dc = DubCfg{}) {
@@ -311,7 +312,7 @@ __device__ __forceinline__ void go2goal_phase(const uint8_t *og, int H, const ui
                     const dub_path_t pth = dub_between_dev(nodes_g[k], heading[k], xg, hg, dc);
                     free_k = dub_sweep_wave(og, dc, nodes_g[k], heading[k], xg, pth, lane, cc);
                 } else {
-                    free_k = los_wave(og, H, nodes_g[k], xg, lane, cc);
+                    free_k = LARGE ? los_wave_large(og, H, nodes_g[k], xg, lane, cc) : los_wave(og, H, nodes_g[k], xg, lane, cc);
                 }
                 if (free_k) {  // rrt.py:318
                     const double c = cost_of((int)k);

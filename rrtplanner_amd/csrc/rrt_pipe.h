@@ -98,12 +98,53 @@ struct PpLds {
 
 // conservative single-precision lower bound of vcost + sqrt(d2): below the f64 value by more than every rounding on the way, for
 // costs up to ~1e5 cells (the same margins as the block kernel's screens, rrt_block.h)
+// With d2 up to 2^25 (LARGE) the conversion (float)d2 rounds too.  The relative errors on the way are then at most: (float)V 2^-24 of
+// V; (float)d2 2^-24, i.e. 2^-25 of the root, plus the hardware root's one ulp 2^-23; the sum, the product and the difference 2^-24
+// each.  Together below 4 * 2^-24 + 2^-23 + 2^-25 < 3.9e-7 of the value, against a factor of 1 - 1.0e-6 (as a float: 1 - 17 * 2^-24) and
+// 4.0e-3 on top: the bound stays below the f64 cost with the margins as they are.
 __device__ __forceinline__ float pp_lower_bound(double V, uint32_t d2) {
     const float s = ((float)V + __builtin_amdgcn_sqrtf((float)d2)) * (1.0f - 1.0e-6f) - 4.0e-3f;
     return s > 0.0f ? s : 0.0f;
 }
 
-__global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
+// the exact f64 root and the line of sight of the kernel's two forms (LARGE: below)
+template <bool LARGE>
+__device__ __forceinline__ double pp_sqrt(uint32_t d2) {
+    if constexpr (LARGE) return sqrt_u25(d2);
+    else return sqrt_u24(d2);
+}
+template <bool LARGE>
+__device__ __forceinline__ bool pp_los(const uint8_t *__restrict__ og, int H, uint32_t a, uint32_t b, int lane, int &cells) {
+    if constexpr (LARGE) return los_wave_large(og, H, a, b, lane, cells);
+    else return los_wave(og, H, a, b, lane, cells);
+}
+
+// The kernel, in one of two forms by the translation unit that includes this file: rrt_pipe_kernel (LARGE = false), or, with
+// RRT_PIPE_LARGE_TU defined, rrt_pipe_large_kernel (LARGE = true) for grids up to 4096 x 4096 (RRT_FLAG_LARGE_GRID).  The same body as
+// text rather than as a function template behind two kernels: through such a wrapper the compiler schedules the plain kernel
+// differently, and its object code is to stay what it was.
+// LARGE: coordinates below 2^12, squared distances below 2^25, rewire radii squared up to 2^26.  What differs from the plain form:
+//   - prices by sqrt_u25 (rrt_block.h) instead of sqrt_u24;
+//   - long lines of sight by los_wave_large (rrt_line_cell_u26), go2goal's included;
+//   - the stream radius is the true integer root of r2 - 1 up to r2 = 2^26 (no saturation): rad0 <= 8191, after the doubling
+//     radn <= 16383, and rad0 * rad0, radn * radn < 2^28 do not wrap;
+//   - r2 <= 2^26 (rrt_batch_set_query clamps there: any d2 on the grid is below 2^25, so the clamp changes no answer) and a dead
+//     lane's d2 == NONE = 2^32 - 1 is still never below it;
+//   - pp_lower_bound: (float)d2 is rounded above 2^24, a relative error of 2^-25 of the root, which its relative margin covers (see there).
+// Everything else -- dist2 (v_pk_sub_i16 + sdot2: 2 * 4095^2 < 2^31), the records {xy, index, vcost f64}, the masks, the cell streams
+// (at 4096 x 4096 the smallest cell is 64 pixels: 64 x 64 = MAX_CELLS cells, at most 4095 * 4097 + 4096 < 2^25 records) -- carries full
+// 32-bit words already.
+#ifdef RRT_PIPE_LARGE_TU
+#define RRT_PIPE_KERNEL rrt_pipe_large_kernel
+#else
+#define RRT_PIPE_KERNEL rrt_pipe_kernel
+#endif
+__global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
+#ifdef RRT_PIPE_LARGE_TU
+    constexpr bool LARGE = true;
+#else
+    constexpr bool LARGE = false;
+#endif
     __shared__ PpLds L;
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int q = (int)blockIdx.x;
@@ -136,7 +177,8 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
         const uint32_t two = (uint32_t)((2 << cshift) * (2 << cshift));
         const uint32_t rr = (star && r2 > two) ? r2 : two;
         rr0 = rr;
-        rad0 = (rr >= (1u << 23)) ? 4096 : (int)sqrtf((float)(rr - 1));
+        // (LARGE: the float root of rr - 1 < 2^26 is within one of the integer root, which the two loops below then reach)
+        rad0 = (!LARGE && rr >= (1u << 23)) ? 4096 : (int)sqrtf((float)(rr - 1));
         while (rad0 > 0 && (uint32_t)(rad0 * rad0) > rr - 1) --rad0;
         while ((uint32_t)((rad0 + 1) * (rad0 + 1)) <= rr - 1) ++rad0;
     }
@@ -278,7 +320,7 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
             const int src = (int)__builtin_ctzll(m);
             const uint32_t pa = (uint32_t)__builtin_amdgcn_readlane((int)a, src);
             int cc = 0;
-            const bool ok = los_wave(og, H, pa, xq, lane, cc);  // rrt.py:519
+            const bool ok = pp_los<LARGE>(og, H, pa, xq, lane, cc);  // rrt.py:519
             nlos += 1;
             ccells += (uint32_t)cc;
             if (ok) {
@@ -377,7 +419,7 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
             // cost are tested, cheapest first (a younger vertex loses every tie against the snapshot's choice: higher index)
             const bool mine_in = ((inball >> lane) & 1ull) != 0ull;
             const u32x4 e = win[lane];
-            const double wcn = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z)) + sqrt_u24(dist2(e.x, xq));
+            const double wcn = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z)) + pp_sqrt<LARGE>(dist2(e.x, xq));
             const bool cnd = mine_in && wcn < cb;
             if (__ballot(cnd) != 0ull) test_priced(cnd, wcn, e.y, e.x, xq, cb, vb, add_los, add_cells);
         }
@@ -515,7 +557,7 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
                     const int pp = (int)__builtin_ctzll(rc);
                     rc &= rc - 1ull;
                     const u32x4 e = ((LP >> pp) & 1ull) != 0ull ? L.winb[(pp - base) & 63] : win[pp];  // a lower head of this pass / an older sample
-                    const double wcn = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z)) + sqrt_u24(dist2(e.x, xq));
+                    const double wcn = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z)) + pp_sqrt<LARGE>(dist2(e.x, xq));
                     hit = wcn < cb;
                 }
                 hitl |= __ballot(hit);
@@ -666,7 +708,7 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
                 lvl = nearer ? rc.z : lvl;
                 lvh = nearer ? rc.w : lvh;
                 if (!star) return;
-                const bool hit = d2 < r2;  // within(), rrt.py:176-181 (d2 == NONE for a dead lane: never below r2 <= 2^24)
+                const bool hit = d2 < r2;  // within(), rrt.py:176-181 (d2 == NONE for a dead lane: never below r2 <= 2^24, LARGE 2^26)
                 hits += hit ? 1u : 0u;
                 const double V = __longlong_as_double((long long)(((unsigned long long)rc.w << 32) | rc.z));
                 const float lb = hit ? pp_lower_bound(V, d2) : FINF;
@@ -762,12 +804,12 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
             const uint32_t e_xy = (lane == slot) ? nn_xy : m1xy;
             const double e_V = __longlong_as_double((long long)(((unsigned long long)((lane == slot) ? nn_vh : m1vh) << 32) | ((lane == slot) ? nn_vl : m1vl)));
             // ---- one exact price per lane ----
-            const double e_cn = e_idx != NONE ? e_V + sqrt_u24(dist2(e_xy, xq)) : f64_inf();
+            const double e_cn = e_idx != NONE ? e_V + pp_sqrt<LARGE>(dist2(e_xy, xq)) : f64_inf();
             DSTAMP(1);  // one price per lane
             // ---- nearest vertex: cost through it, its line of sight (rrt.py:422-425) ----
             const double c_nn = __shfl(e_cn, slot);
             int cells = 0;
-            const bool nocoll = los_wave(og, H, nn_xy, xq, lane, cells);
+            const bool nocoll = pp_los<LARGE>(og, H, nn_xy, xq, lane, cells);
             const bool dup = ((bm_word >> (cell & 31)) & 1u) != 0u;
             double cb = c_nn;
             uint32_t vb = NONE, nlos = 0, ccells = 0;
@@ -785,7 +827,7 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
                         const double V = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z));
                         const uint32_t fd2 = dist2(e.x, xq);
                         const bool has = e.y != NONE && (double)pp_lower_bound(V, fd2) < cb;  // (the best cost may have fallen since the entry was collected)
-                        const double fcn = has ? V + sqrt_u24(fd2) : f64_inf();
+                        const double fcn = has ? V + pp_sqrt<LARGE>(fd2) : f64_inf();
                         test_priced(has, fcn, e.y, e.x, xq, cb, vb, nlos, ccells);
                         // drop the 64 entries just handled
                         u32x4 mv = {0u, NONE, 0u, 0u};
@@ -877,7 +919,7 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
     } else {
         double pc;
         uint32_t pi;
-        go2goal_phase<false>(og, H, nodes_g, vcost, 0, 1, j, xg, reinterpret_cast<uint32_t *>(spill), (RRT_LDS uint32_t *)L.cellcnt, L.bslots, t, lane, wave, pc, pi);
+        go2goal_phase<false, TPB, LARGE>(og, H, nodes_g, vcost, 0, 1, j, xg, reinterpret_cast<uint32_t *>(spill), (RRT_LDS uint32_t *)L.cellcnt, L.bslots, t, lane, wave, pc, pi);
         if (pi != NONE) {
             found = 1;
             vgoal = j;
@@ -916,5 +958,8 @@ __global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv) {
 }
 
 #undef DSTAMP
+#undef RSTAMP
+
+#undef RRT_PIPE_KERNEL
 
 }  // namespace rrtdev

@@ -7,15 +7,16 @@
 
 namespace rrtdev {
 
-// RRT.collisionfree (rrt.py:183-229): one wavefront per segment.  WIDE: grids beyond 2048 x 2048 (see los_wave).
-template <bool WIDE>
+// RRT.collisionfree (rrt.py:183-229): one wavefront per segment.  WALK: 0 los_wave (grids up to 2048 x 2048), 1 los_wave<true> (64-bit
+// division, any grid), 2 los_wave_large (grids up to 4096 x 4096: what rrt_pipe_large_kernel runs).
+template <int WALK>
 __global__ void prim_los_kernel(const uint8_t *og, int H, const int32_t *ab, int m, uint8_t *out_free, int32_t *out_cells) {
     const int lane = (int)(threadIdx.x & 63);
     const int seg = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     if (seg >= m) return;  // whole wave
     const uint32_t a = pack_xy(ab[4 * seg], ab[4 * seg + 1]), b = pack_xy(ab[4 * seg + 2], ab[4 * seg + 3]);
     int cells = 0;
-    const bool ok = los_wave<WIDE>(og, H, a, b, lane, cells);
+    const bool ok = WALK == 2 ? los_wave_large(og, H, a, b, lane, cells) : los_wave<WALK == 1>(og, H, a, b, lane, cells);
     if (lane == 0) {
         out_free[seg] = (uint8_t)ok;
         out_cells[seg] = cells;
@@ -160,6 +161,12 @@ __global__ void prim_sqrt_kernel(uint32_t lo, uint32_t count, double *out) {
 __global__ void prim_sqrt_u24_kernel(uint32_t lo, uint32_t count, double *out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < count) out[k] = sqrt_u24(lo + k);
+}
+
+// the large-grid pipeline's for radicands below 2^25
+__global__ void prim_sqrt_u25_kernel(uint32_t lo, uint32_t count, double *out) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < count) out[k] = sqrt_u25(lo + k);
 }
 
 // sqrt of arbitrary doubles (the ellipse minor axis, rrt.py:622).

@@ -11,7 +11,8 @@ lines of sight of :424/:506, :519 and :537 (one direction, vertex -> sample, ser
 the provider is an ``_ffi.DeviceTree``; the tests substitute a numpy stand-in to check the loop itself on a machine without a GPU.
 
 The same loop is the GENERAL path for problems the expansion kernels do not take (grids beyond 2048 x 2048, n beyond 262 143:
-packed 24-bit keys) with the reference's DEFAULT cost: there the per-candidate Python calls are replaced by their numpy form
+packed 24-bit keys; RRTStandard and RRTStar with the default cost reach 4096 x 4096 on the large-grid kernel, rrt_pipe_large_kernel,
+and only come here past that) with the reference's DEFAULT cost: there the per-candidate Python calls are replaced by their numpy form
 (`vcosts[v] + sqrt(d2)`, rrt.py:72-78), and the rewire block, which cannot fire with that cost (rrt.py:532-536), is skipped.
 Slower than the kernels by orders of magnitude, same results: the class has no size at which it refuses.
 

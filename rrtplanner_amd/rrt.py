@@ -7,7 +7,9 @@ attributes ``dist`` / ``cost`` (rrt.py:334-369) -- but its body is one call into
 (include/rrt_hip.h) instead of the Python loop.  The numpy ``Generator`` stays the source of
 randomness on the host, so the sample stream is the reference's bit for bit.
 
-A caller-supplied ``costfn`` keeps the loop on the host (``hostloop.py``) with the device answering its per-iteration questions.
+A caller-supplied ``costfn`` keeps the loop on the host (``hostloop.py``) with the device answering its per-iteration questions;
+so does a problem the kernels do not take (grids beyond 2048 x 2048 -- for RRTStandard / RRTStar beyond 4096 x 4096 -- or n beyond
+262 143).  ``planner.last_route`` says which way a ``plan()`` went.
 There is no CPU fallback for ``plan()``: without the HIP library or a GPU it raises.
 Tie policy: nearest node / goal connection pick the lowest index among
 equal distance / cost (== a stable argsort in rrt.py:154 and :317).
@@ -497,6 +499,7 @@ class RRT(object):
         self._grid_dirty = True
         self.device_id = 0
         self.last_stats = None
+        self.last_route = None  # which way the last plan() went: "kernel", "kernel-large" (grids up to 4096 x 4096) or "host" (hostloop.py)
 
     # ------------------------------------------------------------------ graph helpers
     def route2gv(self, T: nx.DiGraph, gv) -> List[int]:
@@ -601,7 +604,7 @@ class RRT(object):
             self._grid_dirty = False
         return self._ctx
 
-    def _run(self, alg: int, xstart, xgoal, r_rewire=None, r_goal=None, logs=False, rewire=False):
+    def _run(self, alg: int, xstart, xgoal, r_rewire=None, r_goal=None, logs=False, rewire=False, large_grid=False):
         """Drive one query through the C ABI.  Returns the ResultArrays (+ ellipse log inputs)."""
         xs = hostprep.as_int_point(xstart, "xstart")
         xg = hostprep.as_int_point(xgoal, "xgoal")
@@ -632,6 +635,8 @@ class RRT(object):
             Cmat=Cm,
         )
         kw = {"rewire": True} if rewire else {}
+        if large_grid:
+            kw["large_grid"] = True
         rc, res = ctx.plan(query, n, logs=logs or alg == _ffi.ALG_INFORMED, **kw)
         if rc == _ffi.RRT_NEED_UNITBALL:
             # The tree reached the goal region at iteration i_switch: from there on the reference
@@ -714,13 +719,29 @@ class RRT(object):
         W, H = np.asarray(self.og).shape
         return W > self.FAST_GRID_MAX or H > self.FAST_GRID_MAX or int(self.n) > self.FAST_N_MAX
 
+    LARGE_GRID_MAX = 4096        # the large-grid form of the one-CU pipeline kernel (RRT_FLAG_LARGE_GRID): 25-bit squared distances
+    LARGE_GRID_KERNEL = False    # does this class run on it?  (RRTStandard and RRTStar do)
+
+    def _on_the_large_grid_kernel(self) -> bool:
+        """A grid whose longer side is 2049 to 4096 cells, planned on the device all the same: RRTStandard / RRTStar with the
+        default cost and the reference's rewire, n within the kernels' range.  One CU runs the query.  It looks at the grid, not at
+        _beyond_the_kernels(): whatever else that method refuses still goes to the host loop."""
+        side = max(np.asarray(self.og).shape)
+        return (self.LARGE_GRID_KERNEL and not self._custom_cost and self.FAST_GRID_MAX < side <= self.LARGE_GRID_MAX
+                and int(self.n) <= self.FAST_N_MAX and not _rewire_mode(getattr(self, "rewire", "reference")))
+
     def _plan(self, alg, xstart, xgoal, **kw):
-        if self._custom_cost or self._beyond_the_kernels():
+        large = self._on_the_large_grid_kernel()
+        if large:
+            kw["large_grid"] = True
+        elif self._custom_cost or self._beyond_the_kernels():
+            self.last_route = "host"
             # the host-driven loop over the device primitives (hostloop.py): a custom cost function, or a problem larger than the
             # expansion kernels take (there with the default cost in numpy form) -- slower, same results, never a refusal
             if kw.get("rewire"):
                 raise ValueError('rewire="correct" runs on the expansion kernels only (default cost, grids up to 2048 x 2048, n up to 262143)')
             return None, self._plan_costfn(alg, xstart, xgoal)
+        self.last_route = "kernel-large" if large else "kernel"
         bar = tqdm(total=self.n) if self.pbar else None
         try:
             res = self._run(alg, xstart, xgoal, **kw)
@@ -753,6 +774,8 @@ class RRT(object):
 class RRTStandard(RRT):
     """Plain RRT: the parent of a new node is its nearest node (reference rrt.py:375-447)."""
 
+    LARGE_GRID_KERNEL = True
+
     def __init__(self, og: np.ndarray, n: int, costfn: callable = None, pbar=True, seed: int = 0):
         super().__init__(og, n, costfn=costfn, pbar=pbar, seed=seed)
 
@@ -774,6 +797,8 @@ class RRTStar(RRT):
     after an insertion every near vertex that gets cheaper through the new node and sees it is re-parented, and the costs
     of its descendants are recomputed.  Trees then differ from the reference's on purpose; everything else (sampling,
     acceptance, choose-parent, go2goal, the returned graph) is unchanged."""
+
+    LARGE_GRID_KERNEL = True
 
     def __init__(self, og: np.ndarray, n: int, r_rewire: float, costfn: callable = None, pbar=True, seed: int = 0, rewire: str = "reference"):
         super().__init__(og, n, costfn=costfn, pbar=pbar, seed=seed)
