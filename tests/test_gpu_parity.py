@@ -401,7 +401,9 @@ def test_two_cus_per_query_without_a_committer_runs_the_pipeline(gpu_ctx, with_i
             assert b.kernel_name().startswith("rrt_expand_block_kernel<2, 16, false")
         for q in range(Q):
             if algs[q] == 2:
-                continue  # (needs the host's unit-ball stream to go on: not this test's subject)
+                # (needs the host's unit-ball stream to go on: not this test's subject.  An Informed result of this kernel through
+                # the hand-over: the rrt_expand_block_kernel<2, 16, false, true> row of tests/test_variant_matrix.py)
+                continue
             res = b.get_result(q)
             st, ro = refs[q]
             live = ro.j + (1 if ro.found else 0)
@@ -957,8 +959,8 @@ def test_every_team_size_gives_the_same_trees_every_time(gpu_ctx):
         samples = hostprep.draw_free_samples(np.random.default_rng(q), free, n)
         qs.append(_ffi.make_query(1, n, xs, xg, samples, r2_rewire=hostprep.radius_threshold(64)))
     ref = None
-    for team, pipe in ((None, True), (None, False), (32, True), (16, True), (16, False), (8, True), (4, True), (4, False), (3, True), (2, True),
-                       (2, False), (1, True)):
+    for team, pipe in ((None, True), (None, False), (32, True), (32, False), (16, True), (16, False), (8, True), (8, False), (4, True), (4, False),
+                       (3, True), (2, True), (2, False), (1, True)):
         b = _ffi.Batch(gpu_ctx, Q, n, team=team, pipe=pipe)
         for q, (qu, keep) in enumerate(qs):
             b.set_query(q, qu)

@@ -132,6 +132,23 @@ def _group1_kernels():
     return KERNELS_NOFAULT + list(_GROUP1)
 
 
+def _hand_over(b, qs, tag):
+    """The queries of a launched batch whose oracle run took the unit-ball hand-over (d["ub"]): each must wait at the oracle's
+    i_switch; every one gets its stream and the batch is launched again.  Returns how many there were."""
+    waiting = 0
+    for q, d in enumerate(qs):
+        if d.get("ub") is None:
+            continue
+        r = b.get_result(q, arrays=False)
+        assert r.c.status == _ffi.RRT_NEED_UNITBALL and r.c.i_switch == d["ro"].i_switch, (tag, q)
+        b.set_unitball(q, d["ub"], r.c.i_switch)
+        waiting += 1
+    if waiting:
+        b.launch()
+        b.sync()
+    return waiting
+
+
 def _run_slab_case(ctx, c, kernel):
     """One query on a batch of its own (the kernel's name is the batch's to tell); an Informed one through the unit-ball hand-over."""
     d = slabs.slab_case(c)
@@ -142,12 +159,7 @@ def _run_slab_case(ctx, c, kernel):
     b.launch()
     b.sync()
     name = b.kernel_name()
-    if d["ub"] is not None:
-        r = b.get_result(0, arrays=False)
-        assert r.c.status == _ffi.RRT_NEED_UNITBALL and r.c.i_switch == d["ro"].i_switch, (c["id"], kernel)
-        b.set_unitball(0, d["ub"], r.c.i_switch)
-        b.launch()
-        b.sync()
+    _hand_over(b, [d], (c["id"], kernel))
     _same_as_oracle(b.get_result(0), d["st"], d["ro"], (c["id"], kernel))
     info = b.team_info()
     b.close()
