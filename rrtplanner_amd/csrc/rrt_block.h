@@ -30,6 +30,7 @@
 #pragma once
 
 #include "rrt_kernels.h"
+#include "rrt_cell_stream.h"
 
 namespace rrtdev {
 

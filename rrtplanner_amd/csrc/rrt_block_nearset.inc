@@ -176,12 +176,7 @@
                 toff = (uint32_t)cell * (uint32_t)ccap;
             }
             uint32_t incl = tcnt;
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);
+            incl = wave_incl_sum_u32(incl);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             const uint32_t pre = incl - tcnt;  // lanes past the last cell hold `total`: never <= a live record number
             int cur_c = 0;  // (SCATTER) the cell the last step ended in
@@ -193,23 +188,9 @@
                     const uint32_t idx = base + 64u * (uint32_t)g2 + (uint32_t)lane;
                     uint32_t lo = 0;  // the largest cell c with pre[c] <= idx (an empty cell shares its prefix with its successor)
                     if constexpr (SCATTER) {
-                        // one wave walks the whole stream step by step: the cells that begin in this step write their number into the
-                        // slot of their first record (64 LDS words per wave), a running maximum over the lanes carries it on; the
-                        // lanes in front of the step's first cell start belong to the cell the last step ended in (rrt_pipe.h)
-                        volatile RRT_LDS uint32_t *slots = (volatile RRT_LDS uint32_t *)L.slots[wave];
-                        slots[lane] = NONE;
-                        const uint32_t rel = pre - (base + 64u * (uint32_t)g2);
-                        __builtin_amdgcn_wave_barrier();
-                        if (tcnt != 0u && rel < 64u) slots[rel] = (uint32_t)lane;
-                        __builtin_amdgcn_wave_barrier();
-                        int cv = (int)slots[lane];  // (NONE = -1)
-                        cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x111, 0xf, 0xf, false));
-                        cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x112, 0xf, 0xf, false));
-                        cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x114, 0xf, 0xf, false));
-                        cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x118, 0xf, 0xf, false));
-                        cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x142, 0xa, 0xf, false));
-                        cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x143, 0xc, 0xf, false));
-                        cv = cv < 0 ? cur_c : cv;
+                        // one wave walks the whole stream step by step: the cells that begin in this step name themselves in the slot
+                        // of their first record (stream_cell_of, rrt_cell_stream.h)
+                        const int cv = stream_cell_of((volatile RRT_LDS uint32_t *)L.slots[wave], pre, tcnt, base + 64u * (uint32_t)g2, lane, cur_c);
                         cur_c = __builtin_amdgcn_readlane(cv, 63);
                         lo = (uint32_t)cv;
                     } else {

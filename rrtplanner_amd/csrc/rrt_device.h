@@ -57,15 +57,29 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 // what lets the compiler fold the step into ONE v_max_i32_dpp -- with -1 ("no cell") it was a move of the constant, a DPP move and the max.
 constexpr int DPP_SMAX_ID = (int)0x80000000;
 
-// Wave-wide unsigned sum, result uniform in every lane (same DPP ladder, additive).
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+// Inclusive prefix sum over the lanes of the wave (same DPP ladder, additive): lane l gets the sum of lanes 0..l.
+__device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    return v;
+}
+
+// Wave-wide unsigned sum, result uniform in every lane.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_sum_u32(v), 63); }
+
+// Running signed maximum over the lanes of the wave: lane l gets the maximum of lanes 0..l.
+__device__ __forceinline__ int wave_incl_max_i32(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, v, 0x111, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, v, 0x112, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, v, 0x114, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, v, 0x118, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, v, 0x142, 0xa, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, v, 0x143, 0xc, 0xf, false));
+    return v;
 }
 
 // Wave-wide minimum of non-negative floats (their bit patterns order like unsigned integers).

@@ -33,6 +33,7 @@
 #pragma once
 
 #include "rrt_kernels.h"
+#include "rrt_cell_stream.h"
 
 #ifndef RRT_DUB_STREAM_DEPTH
 #define RRT_DUB_STREAM_DEPTH 2  // steps of a record stream in flight (measured 1..4: profiles/r03_experiments.md)
@@ -78,13 +79,6 @@ struct DbLds {
     unsigned long long dbg[8];  // diagnostic build: [0] samples resolved again, [1] retirements that priced younger vertices, [2] those vertices
 };
 
-// conservative single-precision lower bound of vcost + chord (see the head comment): below the f64 value by more than every
-// rounding on the way, for costs up to ~1e5 cells
-__device__ __forceinline__ float db_lower_bound(double V, uint32_t d2) {
-    const float s = ((float)V + __builtin_amdgcn_sqrtf((float)d2)) * (1.0f - 1.0e-6f) - 4.0e-3f;
-    return s > 0.0f ? s : 0.0f;
-}
-
 __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
     __shared__ DbLds L;
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -120,18 +114,9 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
     u32x4 *cellrec = reinterpret_cast<u32x4 *>(bv.cellrec) + (size_t)q * (size_t)bv.rec_stride;
     uint32_t *cellcnt_g = bv.cellcnt + (size_t)q * (size_t)MAX_CELLS;
     RRT_LDS uint32_t *cellcnt = (RRT_LDS uint32_t *)L.cellcnt;
-    // radius of the first record stream: the rewire radius, but at least two cells (Dubins-RRT has no near set, and a tiny
-    // radius would leave the nearest-vertex search to the doubling below)
-    int rad0 = 0;
-    uint32_t rr0 = 0;  // its square: the stream deals every vertex nearer than that
-    {
-        const uint32_t two = (uint32_t)((2 << cshift) * (2 << cshift));
-        const uint32_t rr = (star && r2 > two) ? r2 : two;
-        rr0 = rr;
-        rad0 = (rr >= (1u << 23)) ? 4096 : (int)sqrtf((float)(rr - 1));
-        while (rad0 > 0 && (uint32_t)(rad0 * rad0) > rr - 1) --rad0;
-        while ((uint32_t)((rad0 + 1) * (rad0 + 1)) <= rr - 1) ++rad0;
-    }
+    const StreamRadius sr = stream_radius(star, r2, cshift, false);  // the first record stream
+    const int rad0 = sr.rad0;
+    const uint32_t rr0 = sr.rr0;
 
     int i = D->i, j = D->j;
     if (t < 6) L.stat[t] = 0ull;  // statistics: added to by whoever retires (under the lock)
@@ -147,108 +132,15 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
     unsigned long long cyc[6] = {D->cyc[0], D->cyc[1], D->cyc[2], D->cyc[3], D->cyc[4], D->cyc[5]};
     unsigned long long tstamp = __builtin_amdgcn_s_memtime();
 #endif
-
-#ifdef RRT_STAMPS
-#define DSTAMP(k)                                               \
-    do {                                                        \
-        unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        cyc[k] += now_ - tstamp;                                \
-        tstamp = now_;                                          \
-    } while (0)
-#else
-#define DSTAMP(k) \
-    do {          \
-    } while (0)
-#endif
     for (int k = t; k < ncells; k += TPB) cellcnt[k] = cellcnt_g[k];
     __syncthreads();
 
-    const float FINF = __uint_as_float(0x7f800000u);
     auto cell_of = [&](uint32_t X) -> int { return (ux(X) >> cshift) * ncy + (uy(X) >> cshift); };
 
-    // The records of the cells that the box of half-width `rad` around X touches, as ONE packed stream: lane l of a step takes
-    // record 64 * step + l of the concatenation of the cells' arrays (exclusive prefix sum of the fill counts over the lanes),
-    // 64 cells at a time.  f(record, live) once per step.  The stream of rrt_pipe.h (round 4; until then this kernel found a
-    // record's cell by a bisection of eight dependent ds_bpermute per step and dealt the box's corners too):
-    // `keep_d2`: every vertex at a squared distance up to this must be dealt; cells farther away than that are left out.
-    // Records of vertices at or above `jsnap` (inserted after the caller's snapshot) are dealt as dead lanes.
-    volatile RRT_LDS uint32_t *slots = (volatile RRT_LDS uint32_t *)L.slots[wave];  // (lanes talk to each other through it: every access as written)
+    // the record streams of this wave (rrt_cell_stream.h)
+    const CellStreamView csv{cshift, ncy, ccap, W, H, cellcnt, (volatile RRT_LDS uint32_t *)L.slots[wave], cellrec, nodes_g, vcost};
     auto stream_box = [&](uint32_t X, int rad, uint32_t keep_d2, uint32_t jsnap, auto &&f) {
-        // a tree of up to 64 vertices: all of them in one step, from the vertex arrays instead of the cells' (the same answers; a
-        // start pose that nothing can be connected to, and the first samples of every run, would otherwise walk ever larger boxes)
-        const bool tiny = jsnap <= DB_TINY;
-        const int x = ux(X), y = uy(X);
-        const int cx0 = (x - rad < 0 ? 0 : x - rad) >> cshift, cx1 = (x + rad > W - 1 ? W - 1 : x + rad) >> cshift;
-        const int cy0 = (y - rad < 0 ? 0 : y - rad) >> cshift, cy1 = (y + rad > H - 1 ? H - 1 : y + rad) >> cshift;
-        const int ny = cy1 - cy0 + 1, ncr = tiny ? 1 : (cx1 - cx0 + 1) * ny;
-        for (int cbase = 0; cbase < ncr; cbase += 64) {
-            uint32_t tcnt = 0, toff = 0;
-            if (tiny) {
-                tcnt = lane == 0 ? jsnap : 0u;  // (one "cell": the vertex arrays)
-            } else if (cbase + lane < ncr) {
-                const int ci = cbase + lane, ccx = cx0 + ci / ny, ccy = cy0 + ci % ny, cell = ccx * ncy + ccy;
-                // squared distance of the sample to the cell's rectangle
-                const int xl = ccx << cshift, xh = xl + (1 << cshift) - 1, yl = ccy << cshift, yh = yl + (1 << cshift) - 1;
-                const int ddx = x < xl ? xl - x : (x > xh ? x - xh : 0), ddy = y < yl ? yl - y : (y > yh ? y - yh : 0);
-                const uint32_t md2 = (uint32_t)(ddx * ddx + ddy * ddy);
-                tcnt = md2 <= keep_d2 ? cellcnt[cell] : 0u;
-                toff = (uint32_t)cell * (uint32_t)ccap;
-            }
-            uint32_t incl = tcnt;
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);
-            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint32_t pre = incl - tcnt;
-            // Which cell a record belongs to, without a search: every non-empty cell whose first record falls into this step writes
-            // its number into that record's slot (64 words of LDS per wave), the lanes read their slots and a running maximum over
-            // the lanes (DPP) carries the number to the records behind it; the lanes in front of the step's first cell start belong
-            // to the cell the last step ended in.
-            int cur_c = 0;
-            auto fetch = [&](uint32_t base) -> u32x4 {
-                const uint32_t idx = base + (uint32_t)lane;
-                slots[lane] = NONE;
-                const uint32_t rel = pre - base;
-                __builtin_amdgcn_wave_barrier();
-                if (tcnt != 0u && rel < 64u) slots[rel] = (uint32_t)lane;
-                __builtin_amdgcn_wave_barrier();
-                int cv = (int)slots[lane];  // (NONE = -1)
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x111, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x112, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x114, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x118, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x142, 0xa, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x143, 0xc, 0xf, false));
-                cv = cv < 0 ? cur_c : cv;
-                cur_c = __builtin_amdgcn_readlane(cv, 63);
-                const uint32_t cpre = (uint32_t)__builtin_amdgcn_ds_bpermute(cv << 2, (int)pre);
-                const uint32_t coff = (uint32_t)__builtin_amdgcn_ds_bpermute(cv << 2, (int)toff);
-                if (tiny) {
-                    const uint32_t k = idx < total ? idx : 0u;
-                    const unsigned long long cbits = (unsigned long long)__double_as_longlong(vcost[k]);
-                    return u32x4{nodes_g[k], k, (uint32_t)cbits, (uint32_t)(cbits >> 32)};
-                }
-                return cellrec[idx < total ? coff + (idx - cpre) : 0u];  // {xy, index, vcost}
-            };
-            // RRT_DUB_STREAM_DEPTH steps in flight: the records of the next steps are requested before this step's are looked at
-            constexpr int SD = RRT_DUB_STREAM_DEPTH;
-            u32x4 rq[SD];
-#pragma unroll
-            for (int k = 0; k < SD; ++k) rq[k] = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k + 1 < SD; ++k)
-                if ((uint32_t)k * 64u < total) rq[k] = fetch((uint32_t)k * 64u);
-            for (uint32_t base = 0; base < total; base += 64u) {
-                const uint32_t ahead = base + (uint32_t)(SD - 1) * 64u;
-                if (ahead < total) rq[SD - 1] = fetch(ahead);
-                f(rq[0], base + (uint32_t)lane < total && rq[0].y < jsnap);
-#pragma unroll
-                for (int k = 0; k + 1 < SD; ++k) rq[k] = rq[k + 1];
-            }
-        }
+        cell_stream_box<RRT_DUB_STREAM_DEPTH, DB_TINY>(csv, X, rad, keep_d2, jsnap, lane, f);
     };
 
     // a word (uniform after the call): the five values of lane `src`
@@ -489,101 +381,51 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
             const uint32_t cell = (uint32_t)ux(xq) * (uint32_t)H + (uint32_t)uy(xq);
             const uint32_t bm_word = __hip_atomic_load(bitmap + (cell >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (set by an L2 atomic: read it there)
             // ---- pass 1 of the record stream: nearest record of the box, |within|, per lane the entry with the smallest bound ----
-            uint32_t hits = 0;
-            uint32_t ld2 = NONE, lidx = NONE, lxy = 0, lvl = 0, lvh = 0;  // this lane's nearest record
-            float m1f = FINF, m2f = FINF;                                 // smallest / second smallest bound among this lane's hits
-            uint32_t m1idx = NONE, m1xy = 0, m1vl = 0, m1vh = 0;
+            NearestRec nr;  // this lane's nearest record
+            BoundPair bp;   // |within|, smallest / second smallest bound among this lane's hits
             stream_box(xq, rad0, rr0 - 1u, jsnap, [&](const u32x4 rc, bool live) {
-                const uint32_t d2 = live ? dist2(rc.x, xq) : NONE;
-                const bool nearer = d2 < ld2 || (d2 == ld2 && live && rc.y < lidx);
-                ld2 = nearer ? d2 : ld2;
-                lidx = nearer ? rc.y : lidx;
-                lxy = nearer ? rc.x : lxy;
-                lvl = nearer ? rc.z : lvl;
-                lvh = nearer ? rc.w : lvh;
-                if (!star) return;
-                const bool hit = d2 < r2;  // within(), rrt.py:176-181 (d2 == NONE for a dead lane: never below r2 <= 2^24)
-                hits += hit ? 1u : 0u;
-                const double V = __longlong_as_double((long long)(((unsigned long long)rc.w << 32) | rc.z));
-                const float lb = hit ? db_lower_bound(V, d2) : FINF;
-                const bool first = lb < m1f || (lb == m1f && hit && rc.y < m1idx);
-                m2f = first ? m1f : __builtin_fminf(m2f, lb);
-                m1f = first ? lb : m1f;
-                m1idx = first ? rc.y : m1idx;
-                m1xy = first ? rc.x : m1xy;
-                m1vl = first ? rc.z : m1vl;
-                m1vh = first ? rc.w : m1vh;
+                const uint32_t d2 = nr.take(rc, live, xq);
+                if (star) bp.take(rc, d2, r2);
             });
-            uint32_t nn_d2 = ld2, nn_idx = lidx;
-            wave_min_key_idx(nn_d2, nn_idx);
+            uint32_t nn_d2, nn_idx;
+            nr.reduce(nn_d2, nn_idx);
             int radn = rad0;
             // nothing in the box, or something that a vertex outside the box could beat: double the box (nearest only), until its
             // radius covers the map's diagonal -- a box as wide as the map still leaves out the cells farther than its radius
             const uint32_t diag2 = (uint32_t)((W - 1) * (W - 1) + (H - 1) * (H - 1));
             while (jsnap > DB_TINY && (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn) && (uint32_t)radn * (uint32_t)radn < diag2) {
                 radn = 2 * radn + 1;
-                ld2 = NONE;
-                lidx = NONE;
-                stream_box(xq, radn, (uint32_t)radn * (uint32_t)radn, jsnap, [&](const u32x4 rc, bool live) {
-                    const uint32_t d2 = live ? dist2(rc.x, xq) : NONE;
-                    const bool nearer = d2 < ld2 || (d2 == ld2 && live && rc.y < lidx);
-                    ld2 = nearer ? d2 : ld2;
-                    lidx = nearer ? rc.y : lidx;
-                    lxy = nearer ? rc.x : lxy;
-                    lvl = nearer ? rc.z : lvl;
-                    lvh = nearer ? rc.w : lvh;
-                });
-                nn_d2 = ld2;
-                nn_idx = lidx;
-                wave_min_key_idx(nn_d2, nn_idx);
+                nr.restart();
+                stream_box(xq, radn, (uint32_t)radn * (uint32_t)radn, jsnap, [&](const u32x4 rc, bool live) { nr.take(rc, live, xq); });
+                nr.reduce(nn_d2, nn_idx);
             }
             if (nn_d2 == NONE) {  // no record was dealt at all: every vertex in turn, never a stale lane's record as the nearest
-                ld2 = NONE;
-                lidx = NONE;
-                for (uint32_t k = (uint32_t)lane; k < jsnap; k += 64u) {  // (a lane meets its vertices in index order: strict <)
-                    const uint32_t xy = nodes_g[k], d2 = dist2(xy, xq);
-                    const bool nearer = d2 < ld2;
-                    ld2 = nearer ? d2 : ld2;
-                    lidx = nearer ? k : lidx;
-                    lxy = nearer ? xy : lxy;
-                }
-                const unsigned long long cbits = (unsigned long long)__double_as_longlong(vcost[lidx != NONE ? lidx : 0u]);
-                lvl = (uint32_t)cbits;
-                lvh = (uint32_t)(cbits >> 32);
-                nn_d2 = ld2;
-                nn_idx = lidx;
-                wave_min_key_idx(nn_d2, nn_idx);
+                scan_all_vertices(nodes_g, vcost, jsnap, xq, lane, nr);
+                nr.reduce(nn_d2, nn_idx);
             }
-            // the nearest vertex's record, uniform
             uint32_t nn_xy, nn_vl, nn_vh;
-            {
-                const unsigned long long m = __ballot(lidx == nn_idx && ld2 == nn_d2);
-                const int src = (int)__builtin_ctzll(m);
-                nn_xy = (uint32_t)__shfl((int)lxy, src);
-                nn_vl = (uint32_t)__shfl((int)lvl, src);
-                nn_vh = (uint32_t)__shfl((int)lvh, src);
-            }
-            const uint32_t nhits = star ? wave_sum_u32(hits) : 0u;
+            nr.winner(nn_d2, nn_idx, nn_xy, nn_vl, nn_vh);
+            const uint32_t nhits = star ? wave_sum_u32(bp.hits) : 0u;
             DSTAMP(0);  // (diagnostic build, wave 0) the first record stream
             // ---- the lane that prices the nearest vertex: the one whose own entry it is, else one without an entry, else the one
             //      whose entry has the largest bound (that entry is left to pass 2) ----
             int slot;
             {
-                const unsigned long long own = __ballot(m1idx == nn_idx);
-                const unsigned long long none = __ballot(m1idx == NONE);
+                const unsigned long long own = __ballot(bp.m1idx == nn_idx);
+                const unsigned long long none = __ballot(bp.m1idx == NONE);
                 if (own) slot = (int)__builtin_ctzll(own);
                 else if (none) slot = (int)__builtin_ctzll(none);
                 else {
-                    const uint32_t inv = ~__float_as_uint(m1f);  // bounds are non-negative floats: the largest has the smallest complement
+                    const uint32_t inv = ~__float_as_uint(bp.m1f);  // bounds are non-negative floats: the largest has the smallest complement
                     const uint32_t mx = wave_min_u32(inv);
                     slot = (int)__builtin_ctzll(__ballot(inv == mx));
                 }
             }
-            float left = m2f;  // this lane's smallest bound among the entries it saw but does not price in pass 1
-            if (lane == slot && m1idx != nn_idx && m1idx != NONE) left = __builtin_fminf(left, m1f);
-            uint32_t e_idx = (lane == slot) ? nn_idx : m1idx;  // the vertex this lane prices (NONE: none)
-            const uint32_t e_xy = (lane == slot) ? nn_xy : m1xy;
-            const double e_V = __longlong_as_double((long long)(((unsigned long long)((lane == slot) ? nn_vh : m1vh) << 32) | ((lane == slot) ? nn_vl : m1vl)));
+            float left = bp.m2f;  // this lane's smallest bound among the entries it saw but does not price in pass 1
+            if (lane == slot && bp.m1idx != nn_idx && bp.m1idx != NONE) left = __builtin_fminf(left, bp.m1f);
+            uint32_t e_idx = (lane == slot) ? nn_idx : bp.m1idx;  // the vertex this lane prices (NONE: none)
+            const uint32_t e_xy = (lane == slot) ? nn_xy : bp.m1xy;
+            const double e_V = __longlong_as_double((long long)(((unsigned long long)((lane == slot) ? nn_vh : bp.m1vh) << 32) | ((lane == slot) ? nn_vl : bp.m1vl)));
             // ---- one word per lane ----
             int e_h = 0;
             dub_path_t e_p;
@@ -614,12 +456,12 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
                 if (__ballot((double)left < cb) != 0ull) {
                     RRT_LDS u32x4 *buf = (RRT_LDS u32x4 *)L.buf[wave];
                     uint32_t nbuf = 0;
-                    const uint32_t skip = (lane == slot) ? NONE : m1idx;  // this lane's entry of pass 1 (the stream deals the same records to the same lanes)
+                    const uint32_t skip = (lane == slot) ? NONE : bp.m1idx;  // this lane's entry of pass 1 (the stream deals the same records to the same lanes)
                     auto flush = [&]() {
                         u32x4 e = {0u, NONE, 0u, 0u};
                         if ((uint32_t)lane < nbuf) e = buf[lane];
                         const double V = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z));
-                        bool has = e.y != NONE && (double)db_lower_bound(V, dist2(e.x, xq)) < cb;  // (the best cost may have fallen since the entry was collected)
+                        bool has = e.y != NONE && (double)chord_lower_bound(V, dist2(e.x, xq)) < cb;  // (the best cost may have fallen since the entry was collected)
                         int fh = 0;
                         dub_path_t fp;
                         fp.t = fp.p = fp.q = 0.0;
@@ -643,7 +485,7 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
                     stream_box(xq, rad0, rr0 - 1u, jsnap, [&](const u32x4 rc, bool live) {
                         const uint32_t d2 = live ? dist2(rc.x, xq) : NONE;
                         const double V = __longlong_as_double((long long)(((unsigned long long)rc.w << 32) | rc.z));
-                        const bool take = d2 < r2 && rc.y != nn_idx && rc.y != skip && (double)db_lower_bound(V, d2) < cb;
+                        const bool take = d2 < r2 && rc.y != nn_idx && rc.y != skip && (double)chord_lower_bound(V, d2) < cb;
                         const unsigned long long tm = __ballot(take);
                         if (tm == 0ull) return;
                         if (take) buf[nbuf + (uint32_t)__builtin_popcountll(tm & ((1ull << lane) - 1ull))] = rc;
@@ -740,7 +582,5 @@ __global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv) {
 #endif
     }
 }
-
-#undef DSTAMP
 
 }  // namespace rrtdev

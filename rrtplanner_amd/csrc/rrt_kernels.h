@@ -267,13 +267,8 @@ __device__ __forceinline__ void go2goal_phase(const uint8_t *og, int H, const ui
             cb[e] = cursor[PB * t + e];
             own += cb[e];
         }
-        uint32_t incl = own;
-        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false);
-        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false);
-        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false);
-        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false);
-        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);
-        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);
+        uint32_t incl = own;  // (a variable of its own, then the call: as the initialiser of a constant the same sum compiles to the loops below in another order)
+        incl = wave_incl_sum_u32(incl);
         if (lane == 63) bslots[wave].pi = incl;  // wave total
         __syncthreads();
         uint32_t base = 0;

@@ -28,6 +28,7 @@
 #pragma once
 
 #include "rrt_block.h"
+#include "rrt_cell_stream.h"
 
 #ifndef RRT_PIPE_STREAM_DEPTH
 #define RRT_PIPE_STREAM_DEPTH 4  // steps of a record stream in flight (round 3 measured 1..4 and took 3; with round 4's cheaper steps 4 is
@@ -96,17 +97,6 @@ struct PpLds {
                                 // retired on their own << 24, [3] waiting for the head [4] publishing, [6] heads retired in passes, [7] publications
 };
 
-// conservative single-precision lower bound of vcost + sqrt(d2): below the f64 value by more than every rounding on the way, for
-// costs up to ~1e5 cells (the same margins as the block kernel's screens, rrt_block.h)
-// With d2 up to 2^25 (LARGE) the conversion (float)d2 rounds too.  The relative errors on the way are then at most: (float)V 2^-24 of
-// V; (float)d2 2^-24, i.e. 2^-25 of the root, plus the hardware root's one ulp 2^-23; the sum, the product and the difference 2^-24
-// each.  Together below 4 * 2^-24 + 2^-23 + 2^-25 < 3.9e-7 of the value, against a factor of 1 - 1.0e-6 (as a float: 1 - 17 * 2^-24) and
-// 4.0e-3 on top: the bound stays below the f64 cost with the margins as they are.
-__device__ __forceinline__ float pp_lower_bound(double V, uint32_t d2) {
-    const float s = ((float)V + __builtin_amdgcn_sqrtf((float)d2)) * (1.0f - 1.0e-6f) - 4.0e-3f;
-    return s > 0.0f ? s : 0.0f;
-}
-
 // the exact f64 root and the line of sight of the kernel's two forms (LARGE: below)
 template <bool LARGE>
 __device__ __forceinline__ double pp_sqrt(uint32_t d2) {
@@ -130,7 +120,7 @@ __device__ __forceinline__ bool pp_los(const uint8_t *__restrict__ og, int H, ui
 //     radn <= 16383, and rad0 * rad0, radn * radn < 2^28 do not wrap;
 //   - r2 <= 2^26 (rrt_batch_set_query clamps there: any d2 on the grid is below 2^25, so the clamp changes no answer) and a dead
 //     lane's d2 == NONE = 2^32 - 1 is still never below it;
-//   - pp_lower_bound: (float)d2 is rounded above 2^24, a relative error of 2^-25 of the root, which its relative margin covers (see there).
+//   - chord_lower_bound: (float)d2 is rounded above 2^24, a relative error of 2^-25 of the root, which its relative margin covers (see there).
 // Everything else -- dist2 (v_pk_sub_i16 + sdot2: 2 * 4095^2 < 2^31), the records {xy, index, vcost f64}, the masks, the cell streams
 // (at 4096 x 4096 the smallest cell is 64 pixels: 64 x 64 = MAX_CELLS cells, at most 4095 * 4097 + 4096 < 2^25 records) -- carries full
 // 32-bit words already.
@@ -169,19 +159,9 @@ __global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
     u32x4 *cellrec = reinterpret_cast<u32x4 *>(bv.cellrec) + (size_t)q * (size_t)bv.rec_stride;
     uint32_t *cellcnt_g = bv.cellcnt + (size_t)q * (size_t)MAX_CELLS;
     RRT_LDS uint32_t *cellcnt = (RRT_LDS uint32_t *)L.cellcnt;
-    // radius of the first record stream: the rewire radius, but at least two cells (RRTStandard has no near set, and a tiny
-    // radius would leave the nearest-vertex search to the doubling below)
-    int rad0 = 0;
-    uint32_t rr0 = 0;  // its square: the stream deals every vertex nearer than that
-    {
-        const uint32_t two = (uint32_t)((2 << cshift) * (2 << cshift));
-        const uint32_t rr = (star && r2 > two) ? r2 : two;
-        rr0 = rr;
-        // (LARGE: the float root of rr - 1 < 2^26 is within one of the integer root, which the two loops below then reach)
-        rad0 = (!LARGE && rr >= (1u << 23)) ? 4096 : (int)sqrtf((float)(rr - 1));
-        while (rad0 > 0 && (uint32_t)(rad0 * rad0) > rr - 1) --rad0;
-        while ((uint32_t)((rad0 + 1) * (rad0 + 1)) <= rr - 1) ++rad0;
-    }
+    const StreamRadius sr = stream_radius(star, r2, cshift, LARGE);  // the first record stream
+    const int rad0 = sr.rad0;
+    const uint32_t rr0 = sr.rr0;
 
     int i = D->i, j = D->j;
     if (t < 5) L.stat[t] = 0ull;  // statistics: added to by whoever retires (under the lock)
@@ -196,113 +176,19 @@ __global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
 #ifdef RRT_STAMPS
     unsigned long long cyc[6] = {D->cyc[0], D->cyc[1], D->cyc[2], D->cyc[3], D->cyc[4], D->cyc[5]};
     unsigned long long tstamp = __builtin_amdgcn_s_memtime();
-#endif
-
-#ifdef RRT_STAMPS
     unsigned long long sleep_iters = 0, nslept = 0;
     bool slept_now = false;
     unsigned long long res_t0 = 0, hist_n[5] = {0, 0, 0, 0, 0}, hist_c[5] = {0, 0, 0, 0, 0};
-#define DSTAMP(k)                                               \
-    do {                                                        \
-        unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        cyc[k] += now_ - tstamp;                                \
-        tstamp = now_;                                          \
-    } while (0)
-#else
-#define DSTAMP(k) \
-    do {          \
-    } while (0)
 #endif
     for (int k = t; k < ncells; k += TPB) cellcnt[k] = cellcnt_g[k];
     if (lane == 0) L.simd_of[wave] = (__builtin_amdgcn_s_getreg((4 << 0) | (4 << 6) | ((2 - 1) << 11)) & 3u);  // HW_REG_HW_ID bits [5:4]: SIMD_ID
     __syncthreads();
 
-    const float FINF = __uint_as_float(0x7f800000u);
     auto cell_of = [&](uint32_t X) -> int { return (ux(X) >> cshift) * ncy + (uy(X) >> cshift); };
-
-    // The records of the cells that the box of half-width `rad` around X touches, as ONE packed stream: lane l of a step takes
-    // record 64 * step + l of the concatenation of the cells' arrays (exclusive prefix sum of the fill counts over the lanes),
-    // 64 cells at a time.  f(record, live) once per step.
-    // Records of vertices at or above `jsnap` (inserted after the caller's snapshot) are dealt as dead lanes.
-    // `keep_d2`: every vertex at a squared distance up to this must be dealt (cells farther away than that are left out: the corners
-    // of the box, a third of its records where the cells are small against the radius).
-    volatile RRT_LDS uint32_t *slots = (volatile RRT_LDS uint32_t *)L.slots[wave];  // (lanes talk to each other through it: every access as written)
+    // the record streams of this wave (rrt_cell_stream.h)
+    const CellStreamView csv{cshift, ncy, ccap, W, H, cellcnt, (volatile RRT_LDS uint32_t *)L.slots[wave], cellrec, nodes_g, vcost};
     auto stream_box = [&](uint32_t X, int rad, uint32_t keep_d2, uint32_t jsnap, auto &&f) {
-        // a tree of up to 64 vertices: all of them in one step, from the vertex arrays instead of the cells' (the same answers; a
-        // start pose that nothing can be connected to, and the first samples of every run, would otherwise walk ever larger boxes)
-        const bool tiny = jsnap <= PP_TINY;
-        const int x = ux(X), y = uy(X);
-        const int cx0 = (x - rad < 0 ? 0 : x - rad) >> cshift, cx1 = (x + rad > W - 1 ? W - 1 : x + rad) >> cshift;
-        const int cy0 = (y - rad < 0 ? 0 : y - rad) >> cshift, cy1 = (y + rad > H - 1 ? H - 1 : y + rad) >> cshift;
-        const int ny = cy1 - cy0 + 1, ncr = tiny ? 1 : (cx1 - cx0 + 1) * ny;
-        for (int cbase = 0; cbase < ncr; cbase += 64) {
-            uint32_t tcnt = 0, toff = 0;
-            if (tiny) {
-                tcnt = lane == 0 ? jsnap : 0u;  // (one "cell": the vertex arrays)
-            } else if (cbase + lane < ncr) {
-                const int ci = cbase + lane, ccx = cx0 + ci / ny, ccy = cy0 + ci % ny, cell = ccx * ncy + ccy;
-                // squared distance of the sample to the cell's rectangle
-                const int xl = ccx << cshift, xh = xl + (1 << cshift) - 1, yl = ccy << cshift, yh = yl + (1 << cshift) - 1;
-                const int ddx = x < xl ? xl - x : (x > xh ? x - xh : 0), ddy = y < yl ? yl - y : (y > yh ? y - yh : 0);
-                const uint32_t md2 = (uint32_t)(ddx * ddx + ddy * ddy);
-                tcnt = md2 <= keep_d2 ? cellcnt[cell] : 0u;
-                toff = (uint32_t)cell * (uint32_t)ccap;
-            }
-            uint32_t incl = tcnt;
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);
-            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint32_t pre = incl - tcnt;
-            // Which cell a record belongs to, without a search and without a loop over the cells: every non-empty cell whose first
-            // record falls into this step writes its number into that record's slot (64 words of LDS per wave), the lanes read
-            // their slots and a running maximum over the lanes (DPP) carries the number to the records behind it; the lanes in
-            // front of the step's first cell start belong to the cell the last step ended in.
-            int cur_c = 0;
-            auto fetch = [&](uint32_t base) -> u32x4 {
-                const uint32_t idx = base + (uint32_t)lane;
-                slots[lane] = NONE;
-                const uint32_t rel = pre - base;
-                __builtin_amdgcn_wave_barrier();
-                if (tcnt != 0u && rel < 64u) slots[rel] = (uint32_t)lane;
-                __builtin_amdgcn_wave_barrier();
-                int cv = (int)slots[lane];  // (NONE = -1)
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x111, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x112, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x114, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x118, 0xf, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x142, 0xa, 0xf, false));
-                cv = max(cv, __builtin_amdgcn_update_dpp(DPP_SMAX_ID, cv, 0x143, 0xc, 0xf, false));
-                cv = cv < 0 ? cur_c : cv;
-                cur_c = __builtin_amdgcn_readlane(cv, 63);
-                const uint32_t cpre = (uint32_t)__builtin_amdgcn_ds_bpermute(cv << 2, (int)pre);
-                const uint32_t coff = (uint32_t)__builtin_amdgcn_ds_bpermute(cv << 2, (int)toff);
-                if (tiny) {
-                    const uint32_t k = idx < total ? idx : 0u;
-                    const unsigned long long cbits = (unsigned long long)__double_as_longlong(vcost[k]);
-                    return u32x4{nodes_g[k], k, (uint32_t)cbits, (uint32_t)(cbits >> 32)};
-                }
-                return cellrec[idx < total ? coff + (idx - cpre) : 0u];  // {xy, index, vcost}
-            };
-            // RRT_PIPE_STREAM_DEPTH steps in flight: the records of the next steps are requested before this step's are looked at
-            constexpr int SD = RRT_PIPE_STREAM_DEPTH;
-            u32x4 rq[SD];
-#pragma unroll
-            for (int k = 0; k < SD; ++k) rq[k] = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k + 1 < SD; ++k)
-                if ((uint32_t)k * 64u < total) rq[k] = fetch((uint32_t)k * 64u);
-            for (uint32_t base = 0; base < total; base += 64u) {
-                const uint32_t ahead = base + (uint32_t)(SD - 1) * 64u;
-                if (ahead < total) rq[SD - 1] = fetch(ahead);
-                f(rq[0], base + (uint32_t)lane < total && rq[0].y < jsnap);
-#pragma unroll
-                for (int k = 0; k + 1 < SD; ++k) rq[k] = rq[k + 1];
-            }
-        }
+        cell_stream_box<RRT_PIPE_STREAM_DEPTH, PP_TINY>(csv, X, rad, keep_d2, jsnap, lane, f);
     };
 
     // Test the priced entries of this wave (lane: has, cost cn through vertex idx at a) that can still become the parent,
@@ -695,114 +581,53 @@ __global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
             const uint32_t cell = (uint32_t)ux(xq) * (uint32_t)H + (uint32_t)uy(xq);
             const uint32_t bm_word = __hip_atomic_load(bitmap + (cell >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (set by an L2 atomic: read it there)
             // ---- pass 1 of the record stream: nearest record of the box, |within|, per lane the entry with the smallest bound ----
-            uint32_t hits = 0;
-            uint32_t ld2 = NONE, lidx = NONE, lxy = 0, lvl = 0, lvh = 0;  // this lane's nearest record
-            float m1f = FINF, m2f = FINF;                                 // smallest / second smallest bound among this lane's hits
-            uint32_t m1idx = NONE, m1xy = 0, m1vl = 0, m1vh = 0;
+            NearestRec nr;  // this lane's nearest record
+            BoundPair bp;   // |within|, smallest / second smallest bound among this lane's hits
             stream_box(xq, rad0, rr0 - 1u, jsnap, [&](const u32x4 rc, bool live) {
-                const uint32_t d2 = live ? dist2(rc.x, xq) : NONE;
-                const bool nearer = d2 < ld2 || (d2 == ld2 && live && rc.y < lidx);
-                ld2 = nearer ? d2 : ld2;
-                lidx = nearer ? rc.y : lidx;
-                lxy = nearer ? rc.x : lxy;
-                lvl = nearer ? rc.z : lvl;
-                lvh = nearer ? rc.w : lvh;
-                if (!star) return;
-                const bool hit = d2 < r2;  // within(), rrt.py:176-181 (d2 == NONE for a dead lane: never below r2 <= 2^24, LARGE 2^26)
-                hits += hit ? 1u : 0u;
-                const double V = __longlong_as_double((long long)(((unsigned long long)rc.w << 32) | rc.z));
-                const float lb = hit ? pp_lower_bound(V, d2) : FINF;
-                const bool first = lb < m1f || (lb == m1f && hit && rc.y < m1idx);
-                m2f = first ? m1f : __builtin_fminf(m2f, lb);
-                m1f = first ? lb : m1f;
-                m1idx = first ? rc.y : m1idx;
-                m1xy = first ? rc.x : m1xy;
-                m1vl = first ? rc.z : m1vl;
-                m1vh = first ? rc.w : m1vh;
+                const uint32_t d2 = nr.take(rc, live, xq);
+                if (star) bp.take(rc, d2, r2);
             });
-            uint32_t nn_d2 = ld2, nn_idx = lidx;
-            wave_min_key_idx(nn_d2, nn_idx);
+            uint32_t nn_d2, nn_idx;
+            nr.reduce(nn_d2, nn_idx);
             // nothing in the box, or something that a vertex outside the box could beat: the box once more at twice the size, then
-            // (a sample far from the tree: a region the tree has not reached, or cannot) every vertex in turn -- 4 bytes and six
-            // instructions per vertex, where ever larger boxes would deal out every record of the map.  A box as wide as the map
-            // still leaves out the cells farther than its radius (up to the diagonal): a miss always goes on, whatever the radius.
+            // (a sample far from the tree: a region the tree has not reached, or cannot) every vertex in turn.  A box as wide as the
+            // map still leaves out the cells farther than its radius (up to the diagonal): a miss always goes on, whatever the radius.
             int radn = rad0;
             bool far = jsnap > PP_TINY && (nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn);
             if (far) {
                 radn = 2 * radn + 1;
-                ld2 = NONE;
-                lidx = NONE;
-                stream_box(xq, radn, (uint32_t)radn * (uint32_t)radn, jsnap, [&](const u32x4 rc, bool live) {
-                    const uint32_t d2 = live ? dist2(rc.x, xq) : NONE;
-                    const bool nearer = d2 < ld2 || (d2 == ld2 && live && rc.y < lidx);
-                    ld2 = nearer ? d2 : ld2;
-                    lidx = nearer ? rc.y : lidx;
-                    lxy = nearer ? rc.x : lxy;
-                    lvl = nearer ? rc.z : lvl;
-                    lvh = nearer ? rc.w : lvh;
-                });
-                nn_d2 = ld2;
-                nn_idx = lidx;
-                wave_min_key_idx(nn_d2, nn_idx);
+                nr.restart();
+                stream_box(xq, radn, (uint32_t)radn * (uint32_t)radn, jsnap, [&](const u32x4 rc, bool live) { nr.take(rc, live, xq); });
+                nr.reduce(nn_d2, nn_idx);
                 far = nn_d2 == NONE || nn_d2 > (uint32_t)radn * (uint32_t)radn;
             }
             if (far || nn_d2 == NONE) {  // (NONE: no record was dealt at all; never a stale lane's record as the nearest)
-                ld2 = NONE;
-                lidx = NONE;
-                for (uint32_t b0 = 0; b0 < jsnap; b0 += 256u) {
-                    uint32_t xy4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const uint32_t k = b0 + 64u * (uint32_t)u + (uint32_t)lane;
-                        xy4[u] = nodes_g[k < jsnap ? k : 0u];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {  // (a lane meets its vertices in index order: strict < keeps the lowest index)
-                        const uint32_t k = b0 + 64u * (uint32_t)u + (uint32_t)lane;
-                        const uint32_t d2 = k < jsnap ? dist2(xy4[u], xq) : NONE;
-                        const bool nearer = d2 < ld2;
-                        ld2 = nearer ? d2 : ld2;
-                        lidx = nearer ? k : lidx;
-                        lxy = nearer ? xy4[u] : lxy;
-                    }
-                }
-                const unsigned long long cbits = (unsigned long long)__double_as_longlong(vcost[lidx != NONE ? lidx : 0u]);
-                lvl = (uint32_t)cbits;
-                lvh = (uint32_t)(cbits >> 32);
-                nn_d2 = ld2;
-                nn_idx = lidx;
-                wave_min_key_idx(nn_d2, nn_idx);
+                scan_all_vertices(nodes_g, vcost, jsnap, xq, lane, nr);
+                nr.reduce(nn_d2, nn_idx);
             }
-            // the nearest vertex's record, uniform
             uint32_t nn_xy, nn_vl, nn_vh;
-            {
-                const unsigned long long m = __ballot(lidx == nn_idx && ld2 == nn_d2);
-                const int src = (int)__builtin_ctzll(m);
-                nn_xy = (uint32_t)__shfl((int)lxy, src);
-                nn_vl = (uint32_t)__shfl((int)lvl, src);
-                nn_vh = (uint32_t)__shfl((int)lvh, src);
-            }
-            const uint32_t nhits = star ? wave_sum_u32(hits) : 0u;
+            nr.winner(nn_d2, nn_idx, nn_xy, nn_vl, nn_vh);
+            const uint32_t nhits = star ? wave_sum_u32(bp.hits) : 0u;
             DSTAMP(0);  // (diagnostic build, wave 0) the first record stream
             // ---- the lane that prices the nearest vertex: the one whose own entry it is, else one without an entry, else the one
             //      whose entry has the largest bound (that entry is left to pass 2) ----
             int slot;
             {
-                const unsigned long long own = __ballot(m1idx == nn_idx);
-                const unsigned long long none = __ballot(m1idx == NONE);
+                const unsigned long long own = __ballot(bp.m1idx == nn_idx);
+                const unsigned long long none = __ballot(bp.m1idx == NONE);
                 if (own) slot = (int)__builtin_ctzll(own);
                 else if (none) slot = (int)__builtin_ctzll(none);
                 else {
-                    const uint32_t inv = ~__float_as_uint(m1f);  // bounds are non-negative floats: the largest has the smallest complement
+                    const uint32_t inv = ~__float_as_uint(bp.m1f);  // bounds are non-negative floats: the largest has the smallest complement
                     const uint32_t mx = wave_min_u32(inv);
                     slot = (int)__builtin_ctzll(__ballot(inv == mx));
                 }
             }
-            float left = m2f;  // this lane's smallest bound among the entries it saw but does not price in pass 1
-            if (lane == slot && m1idx != nn_idx && m1idx != NONE) left = __builtin_fminf(left, m1f);
-            uint32_t e_idx = (lane == slot) ? nn_idx : m1idx;  // the vertex this lane prices (NONE: none)
-            const uint32_t e_xy = (lane == slot) ? nn_xy : m1xy;
-            const double e_V = __longlong_as_double((long long)(((unsigned long long)((lane == slot) ? nn_vh : m1vh) << 32) | ((lane == slot) ? nn_vl : m1vl)));
+            float left = bp.m2f;  // this lane's smallest bound among the entries it saw but does not price in pass 1
+            if (lane == slot && bp.m1idx != nn_idx && bp.m1idx != NONE) left = __builtin_fminf(left, bp.m1f);
+            uint32_t e_idx = (lane == slot) ? nn_idx : bp.m1idx;  // the vertex this lane prices (NONE: none)
+            const uint32_t e_xy = (lane == slot) ? nn_xy : bp.m1xy;
+            const double e_V = __longlong_as_double((long long)(((unsigned long long)((lane == slot) ? nn_vh : bp.m1vh) << 32) | ((lane == slot) ? nn_vl : bp.m1vl)));
             // ---- one exact price per lane ----
             const double e_cn = e_idx != NONE ? e_V + pp_sqrt<LARGE>(dist2(e_xy, xq)) : f64_inf();
             DSTAMP(1);  // one price per lane
@@ -820,13 +645,13 @@ __global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
                 if (__ballot((double)left < cb) != 0ull) {
                     RRT_LDS u32x4 *buf = (RRT_LDS u32x4 *)L.buf[wave];
                     uint32_t nbuf = 0;
-                    const uint32_t skip = (lane == slot) ? NONE : m1idx;  // this lane's entry of pass 1 (the stream deals the same records to the same lanes)
+                    const uint32_t skip = (lane == slot) ? NONE : bp.m1idx;  // this lane's entry of pass 1 (the stream deals the same records to the same lanes)
                     auto flush = [&]() {
                         u32x4 e = {0u, NONE, 0u, 0u};
                         if ((uint32_t)lane < nbuf) e = buf[lane];
                         const double V = __longlong_as_double((long long)(((unsigned long long)e.w << 32) | e.z));
                         const uint32_t fd2 = dist2(e.x, xq);
-                        const bool has = e.y != NONE && (double)pp_lower_bound(V, fd2) < cb;  // (the best cost may have fallen since the entry was collected)
+                        const bool has = e.y != NONE && (double)chord_lower_bound(V, fd2) < cb;  // (the best cost may have fallen since the entry was collected)
                         const double fcn = has ? V + pp_sqrt<LARGE>(fd2) : f64_inf();
                         test_priced(has, fcn, e.y, e.x, xq, cb, vb, nlos, ccells);
                         // drop the 64 entries just handled
@@ -839,7 +664,7 @@ __global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
                     stream_box(xq, rad0, rr0 - 1u, jsnap, [&](const u32x4 rc, bool live) {
                         const uint32_t d2 = live ? dist2(rc.x, xq) : NONE;
                         const double V = __longlong_as_double((long long)(((unsigned long long)rc.w << 32) | rc.z));
-                        const bool take = d2 < r2 && rc.y != nn_idx && rc.y != skip && (double)pp_lower_bound(V, d2) < cb;
+                        const bool take = d2 < r2 && rc.y != nn_idx && rc.y != skip && (double)chord_lower_bound(V, d2) < cb;
                         const unsigned long long tm = __ballot(take);
                         if (tm == 0ull) return;
                         if (take) buf[nbuf + (uint32_t)__builtin_popcountll(tm & ((1ull << lane) - 1ull))] = rc;
@@ -957,7 +782,6 @@ __global__ __launch_bounds__(TPB) void RRT_PIPE_KERNEL(BatchView bv) {
     }
 }
 
-#undef DSTAMP
 #undef RSTAMP
 
 #undef RRT_PIPE_KERNEL

@@ -110,13 +110,7 @@ __global__ __launch_bounds__(TPB) void tree_query_kernel(const uint8_t *og, int 
         cnt += d2 < r2 ? 1u : 0u;
     }
     wave_min_key_idx(bd, bi);
-    uint32_t incl = cnt;  // inclusive prefix over the wave's lanes
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false);
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false);
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false);
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false);
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);
+    const uint32_t incl = wave_incl_sum_u32(cnt);
     if (lane == 63) wtot[wave] = incl;
     if (lane == 0) wnn[wave] = make_uint2(bd, bi);
     __syncthreads();
