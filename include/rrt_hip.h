@@ -176,6 +176,22 @@ int rrt_batch_pipelined(rrt_batch *b, int32_t *pipelined);
 int rrt_batch_kernel_name(rrt_batch *b, char *buf, int32_t len);
 int rrt_batch_elapsed_ms(rrt_batch *b, float *ms); /* HIP events around the last launch's kernels (incl. a launch that timed out) */
 int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out);
+/* Connect m goals to the tree that query q left on the device, in one launch (rrt_goals_kernel): "plan once, route everywhere".
+ * goals_xy is host (m,2).  Per goal the decision of go2goal (rrt.py:311-319) over the vertices [0, j) of the query -- rrt_result.j:
+ * the tree BEFORE its own goal row; row j of a query whose go2goal succeeded is a copy of xgoal, not a vertex --
+ *   cost[k] = vcost[k] + sqrt(d2(k, goal)) in f64, the vertices tried in stable (cost, index) order, the first one with a free line
+ *   of sight to the goal wins:  vertex[g] = that vertex, cost[g] = its cost[k]
+ * (for the query's own xgoal: parent[vgoal] and vcost[vgoal] of its result).  No vertex connects (every line blocked, or the goal on
+ * an obstacle cell): vertex[g] = -1, cost[g] = +inf.  The reference's fall-backs for that case (vgoal = 0, the IndexError of
+ * rrt.py:317-318) belong to plan() and are NOT reproduced: for unreachable goals this call is outside reference parity.
+ * Synchronous on the context's stream; the batch is left as it was (rrt_batch_get_result, rrt_batch_rearm + rrt_batch_launch give
+ * what they gave before).  m == 0: RRT_OK, nothing is launched.
+ * RRT_E_ARG: NULL; q out of range; m < 0 or m > 2^20; a goal outside the grid; a query that has not finished (none set, not launched
+ * or not synchronised, waiting for its unit-ball stream, failed); a context whose grid changed shape, or was rewritten
+ * (rrt_grid_generation) or switched to another frame, since the query last ran.  RRT_E_UNSUPPORTED: a batch created with
+ * RRT_FLAG_DUBINS.  The first call allocates scratch on the batch (at most 512 slabs of n_cap words and 128 MiB, at least one slab),
+ * freed with the batch. */
+int rrt_batch_connect_goals(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -215,6 +231,8 @@ int rrt_gather_fetch(rrt_batch *b, int32_t rank, int32_t q, rrt_result *out);
 int rrt_plan(rrt_ctx *ctx, const rrt_query *query, uint32_t flags, rrt_result *out);
 int rrt_plan_resume(rrt_ctx *ctx, const double *unitball, int32_t count, rrt_result *out);
 int rrt_plan_batch(rrt_ctx *ctx, int32_t Q, const rrt_query *queries, rrt_result *out);
+/* rrt_batch_connect_goals on the tree of the context's last rrt_plan / rrt_plan_resume (the batch behind them stays resident) */
+int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

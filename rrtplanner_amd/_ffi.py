@@ -69,6 +69,7 @@ SYMBOLS = (
     "rrt_tree_create", "rrt_tree_destroy", "rrt_tree_reset", "rrt_tree_append", "rrt_tree_query",
     "rrt_prim_collisionfree", "rrt_prim_nearest_within", "rrt_prim_sqrt_u32", "rrt_prim_sqrt_u24", "rrt_prim_sqrt_f64",
     "rrt_prim_collisionfree_walk", "rrt_prim_sqrt_u25",
+    "rrt_batch_connect_goals", "rrt_plan_connect_goals",
 )
 
 
@@ -163,6 +164,8 @@ def lib():
             "rrt_prim_sqrt_f64": ([vp, vp, u32, vp], C.c_int),
             "rrt_prim_collisionfree_walk": ([vp, vp, i32, i32, vp, vp], C.c_int),
             "rrt_prim_sqrt_u25": ([vp, u32, u32, vp], C.c_int),
+            "rrt_batch_connect_goals": ([vp, i32, vp, i32, vp, vp], C.c_int),
+            "rrt_plan_connect_goals": ([vp, vp, i32, vp, vp], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -193,6 +196,17 @@ def comm_unique_id() -> bytes:
     buf = (C.c_uint8 * COMM_ID_BYTES)()
     _check(None, lib().rrt_comm_unique_id(C.cast(buf, C.c_void_p)))
     return bytes(buf)
+
+
+def _goal_arrays(goals):
+    """(goals as contiguous int32 (M, 2), vertex int32[M], cost float64[M]) for the connect_goals calls; a single point is M = 1"""
+    g = np.asarray(goals)
+    if g.ndim == 1 and g.shape == (2,):
+        g = g[np.newaxis, :]
+    if g.ndim != 2 or g.shape[1] != 2:
+        raise ValueError(f"goals must have shape (M, 2) or (2,), got {g.shape}")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    return g, np.full(g.shape[0], -1, dtype=np.int32), np.full(g.shape[0], np.inf, dtype=np.float64)
 
 
 class ResultArrays:
@@ -371,6 +385,12 @@ class Context:
         _check(self._h, rc, ok=(RRT_OK, RRT_NEED_UNITBALL, RRT_E_GOAL_UNREACHABLE))
         return rc
 
+    def connect_goals(self, goals):
+        """rrt_plan_connect_goals: Batch.connect_goals on the tree of this context's last plan() / plan_resume()"""
+        g, vertex, cost = _goal_arrays(goals)
+        _check(self._h, lib().rrt_plan_connect_goals(self._h, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
+        return vertex, cost
+
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
         query stops at RRT_NEED_UNITBALL -- use Batch for the staged hand-over).  Returns (rc, [ResultArrays])."""
@@ -546,6 +566,14 @@ class Batch:
         rc = lib().rrt_batch_get_result(self._h, int(q), C.byref(res.c))
         _check(self.ctx.handle, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
         return res
+
+    def connect_goals(self, q, goals):
+        """rrt_batch_connect_goals: connect the goals (M, 2) to the finished tree of query q in one launch.  Returns
+        (vertex int32[M], cost float64[M]): per goal the first vertex of [0, j), in stable (cost, index) order of
+        cost = vcost[k] + dist(k, goal), with a free line of sight to it, and that cost; (-1, inf) where no vertex connects."""
+        g, vertex, cost = _goal_arrays(goals)
+        _check(self.ctx.handle, lib().rrt_batch_connect_goals(self._h, int(q), g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
+        return vertex, cost
 
     def debug_cycles(self, q):
         out = (C.c_uint64 * 38)()

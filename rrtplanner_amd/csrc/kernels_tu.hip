@@ -27,6 +27,10 @@ template __global__ void rrt_expand_kernel<false, false>(BatchView);
 template __global__ void rrt_expand_kernel<true, false>(BatchView);
 }
 
+#elif RRT_TU == 5  // many goals against a finished tree (rrt_goals_kernel, rrt_goals_large_kernel): not a team kernel
+#define RRT_SERIAL_DECL_ONLY
+#include "rrt_goals.h"
+
 #else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_block.h"

@@ -24,6 +24,8 @@
 #include "rrt_block.h"
 #include "rrt_block_variants.def"
 #include "rrt_kernel_decls.h"
+#define RRT_GOALS_DECL_ONLY
+#include "rrt_goals.h"
 #include "rrt_prims.h"
 
 using namespace rrtdev;
@@ -188,6 +190,15 @@ struct rrt_batch {
     float ms_before = 0.f;      // kernel time of the launch a fallback relaunch replaced (rrt_batch_elapsed_ms adds it)
     bool one_cu_once = false;   // the next launch runs one CU per query whatever b->team says (continuation after a timeout)
     std::vector<uint32_t> stage;  // host staging for packed samples
+    // rrt_batch_connect_goals: the grid every query last ran on (recorded at launch), and device memory allocated at the first call
+    std::vector<uint64_t> ran_gen;       // [Q] the context's grid generation
+    std::vector<const uint8_t *> ran_og; // [Q] ... and its active grid
+    uint32_t *d_goal_order = nullptr;    // [goal_slabs][n_cap] go2goal_phase's scratch, one slab per workgroup (never `spill`: a later launch needs it)
+    int32_t goal_slabs = 0;
+    uint32_t *d_goals = nullptr;         // [goal_cap] packed goals
+    int32_t *d_goal_vertex = nullptr;    // [goal_cap]
+    double *d_goal_cost = nullptr;       // [goal_cap]
+    int32_t goal_cap = 0;
 };
 
 // The limit is a property of the kernel on a device, shared by every batch that launches it: it is only ever raised, to the
@@ -527,7 +538,7 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath};
+                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -661,6 +672,8 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
         return fail(ctx, RRT_E_HIP, "hipHostMalloc(%zu): %s", (size_t)Q * sizeof(QDesc), hipGetErrorString(e_));
     }
     for (auto &d : b->h_desc) d.status = ST_IDLE;
+    b->ran_gen.assign((size_t)Q, 0);
+    b->ran_og.assign((size_t)Q, nullptr);
     const size_t q = (size_t)Q;
 #define ALLOC(ptr, bytes)                                   \
     do {                                                    \
@@ -1017,6 +1030,11 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
     if (!b->one_cu_once) b->ms_before = 0.f;
     LaunchPlan &p = b->last;
     if (const int rc = plan_launch(b, p); rc != RRT_OK) return rc;
+    for (int q = 0; q < b->Q; ++q)  // the grid the queries of this launch run on (rrt_batch_connect_goals asks for the same one)
+        if (b->h_desc[(size_t)q].status == ST_RUNNING) {
+            b->ran_gen[(size_t)q] = ctx->grid_gen;
+            b->ran_og[(size_t)q] = ctx->og;
+        }
     BatchView v = make_view(b);
     v.team_qpad = p.qpad;
     v.lds_chunks = p.lds_chunks;
@@ -1238,6 +1256,94 @@ extern "C" int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out) {
                                                  : "query %d: the workgroups of its team (%d) were not resident together (a hand-off timed out); "
                                                    "use RRT_FLAG_NOTEAM when other kernels share the device", q, b->dub_block ? d.i : b->team);
     return d.status < 0 ? d.status : RRT_OK;
+}
+
+// ---- many goals against a finished tree (rrt_goals.h) ----
+static int connect_goals(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    if (!goals_xy || !vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (an edge to a goal is a Dubins word to a goal pose; these kernels price straight lines)", who);
+    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
+    if (m < 0 || m > GOALS_MAX) return fail(ctx, RRT_E_ARG, "%s: m=%d, at most %d goals per call", who, m, GOALS_MAX);
+    const QDesc &d = b->h_desc[(size_t)q];
+    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
+        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
+                    d.status == ST_IDLE      ? "no query set"
+                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
+                    : d.status == ST_NEED_UB ? "it waits for its unit-ball stream"
+                                             : "its launch failed");
+    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid changed shape since the batch was created (%dx%d)", who, b->gridW, b->gridH);
+    if (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now): the tree belongs to the "
+                    "other grid", who, q, (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen);
+    const int W = ctx->W, H = ctx->H;
+    b->stage.resize((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        const int x = goals_xy[2 * k], y = goals_xy[2 * k + 1];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
+    }
+    if (m == 0) return RRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // one slab of n_cap words per workgroup, at most GOALS_MAX_SLABS of them and GOALS_SLAB_BUDGET bytes, never fewer than one
+    int slabs = (int)(GOALS_SLAB_BUDGET / ((size_t)b->n_cap * sizeof(uint32_t)));
+    slabs = slabs > GOALS_MAX_SLABS ? GOALS_MAX_SLABS : (slabs < 1 ? 1 : slabs);
+    slabs = slabs > m ? m : slabs;
+    if (slabs > b->goal_slabs) {
+        if (b->d_goal_order) HIPCHK(ctx, hipFree(b->d_goal_order));
+        b->d_goal_order = nullptr;
+        b->goal_slabs = 0;
+        HIPCHK(ctx, hipMalloc((void **)&b->d_goal_order, (size_t)slabs * (size_t)b->n_cap * sizeof(uint32_t)));
+        b->goal_slabs = slabs;
+    }
+    if (m > b->goal_cap) {
+        // each pointer freed and cleared on its own: a failure half way leaves no pointer that is freed twice or overwritten
+        b->goal_cap = 0;
+        if (b->d_goals) HIPCHK(ctx, hipFree(b->d_goals));
+        b->d_goals = nullptr;
+        if (b->d_goal_vertex) HIPCHK(ctx, hipFree(b->d_goal_vertex));
+        b->d_goal_vertex = nullptr;
+        if (b->d_goal_cost) HIPCHK(ctx, hipFree(b->d_goal_cost));
+        b->d_goal_cost = nullptr;
+        // (a malloc that fails leaves the earlier ones in place with goal_cap == 0: the next call frees them above)
+        HIPCHK(ctx, hipMalloc((void **)&b->d_goals, (size_t)m * sizeof(uint32_t)));
+        HIPCHK(ctx, hipMalloc((void **)&b->d_goal_vertex, (size_t)m * sizeof(int32_t)));
+        HIPCHK(ctx, hipMalloc((void **)&b->d_goal_cost, (size_t)m * sizeof(double)));
+        b->goal_cap = m;
+    }
+    GoalsView gv{};
+    gv.og = ctx->og;
+    gv.H = H;
+    gv.nodes = b->d_nodes + (size_t)q * b->node_stride;
+    gv.vcost = b->d_vcost + (size_t)q * b->node_stride;
+    gv.j = d.j;
+    gv.goals = b->d_goals;
+    gv.m = m;
+    gv.order = b->d_goal_order;
+    gv.slab_words = b->n_cap;
+    gv.vertex = b->d_goal_vertex;
+    gv.cost = b->d_goal_cost;
+    if (gv.j < 0 || gv.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, gv.j, b->n_cap);
+    HIPCHK(ctx, hipMemcpyAsync(b->d_goals, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_goal_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cost, b->d_goal_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (also: the staging buffer is reused)
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_connect_goals(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_goals: NULL");
+    return connect_goals("rrt_batch_connect_goals", b, q, goals_xy, m, vertex, cost);
+}
+
+extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_goals: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_goals: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
+    return connect_goals("rrt_plan_connect_goals", ctx->single, 0, goals_xy, m, vertex, cost);
 }
 
 extern "C" int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]) {

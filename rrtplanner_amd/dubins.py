@@ -179,6 +179,13 @@ class _DubinsBase(RRT):
                 bar.close()
         return out
 
+    def connect_goals(self, goals):
+        raise ValueError("connect_goals: a Dubins planner's goal is a pose and its edge a Dubins word; the many-goal kernel prices straight lines "
+                         "(RRTStandard, RRTStar, RRTStarInformed only)")
+
+    def paths_to(self, T, goals):
+        return self.connect_goals(goals)
+
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""
         legs = []

@@ -500,6 +500,7 @@ class RRT(object):
         self.device_id = 0
         self.last_stats = None
         self.last_route = None  # which way the last plan() went: "kernel", "kernel-large" (grids up to 4096 x 4096) or "host" (hostloop.py)
+        self._tree_resident = None  # connect_goals: "device" while the tree of the last plan() is on the device for this grid and n, "host" after the host route
 
     # ------------------------------------------------------------------ graph helpers
     def route2gv(self, T: nx.DiGraph, gv) -> List[int]:
@@ -572,9 +573,11 @@ class RRT(object):
         self.og = og_new
         self.free = np.argwhere(og_new == 0)
         self._grid_dirty = True
+        self._tree_resident = None
 
     def set_n(self, n: int):
         self.n = n
+        self._tree_resident = None
 
     def set_og_resident(self, grids, k: int = 0):
         """Like set_og(grids.host[k]) for grids generated on this planner's device (oggen.DeviceGrids): frame k
@@ -586,6 +589,7 @@ class RRT(object):
         self.og = grids.host[k]
         self.free = np.argwhere(self.og == 0)
         self._grid_dirty = False
+        self._tree_resident = None
 
     def device_context(self) -> "_ffi.Context":
         """The planner's device context (created on demand, without uploading a grid)."""
@@ -614,6 +618,7 @@ class RRT(object):
                 raise ValueError(f"{name}={p.tolist()} lies outside the {W}x{H} occupancy grid")
         n = int(self.n)
         ctx = self._device()
+        self._tree_resident = None
         bitgen = self.rand_gen.bit_generator
         state0 = bitgen.state
         if getattr(self, "_free_packed_of", None) is not self.free:  # (free is replaced, never edited in place: set_og / set_og_resident)
@@ -651,6 +656,7 @@ class RRT(object):
                 raise np.linalg.LinAlgError("rotation_to_world_frame is not finite (xstart == xgoal?)")
             ub = hostprep.draw_unitball(self.rand_gen, n - i_sw)
             rc = ctx.plan_resume(ub, res)
+        self._tree_resident = "device"  # (also when the plan's own goal is unreachable: the tree is complete)
         if rc == _ffi.RRT_E_GOAL_UNREACHABLE:
             # rrt.py:317-318: the next argsort entry is an unfilled row -> og[INT64_MIN, ...]
             raise IndexError(f"index {INT64_MIN} is out of bounds for axis 0 with size {W}")
@@ -736,11 +742,14 @@ class RRT(object):
             kw["large_grid"] = True
         elif self._custom_cost or self._beyond_the_kernels():
             self.last_route = "host"
+            self._tree_resident = None
             # the host-driven loop over the device primitives (hostloop.py): a custom cost function, or a problem larger than the
             # expansion kernels take (there with the default cost in numpy form) -- slower, same results, never a refusal
             if kw.get("rewire"):
                 raise ValueError('rewire="correct" runs on the expansion kernels only (default cost, grids up to 2048 x 2048, n up to 262143)')
-            return None, self._plan_costfn(alg, xstart, xgoal)
+            out = self._plan_costfn(alg, xstart, xgoal)
+            self._tree_resident = "host"  # (only a plan that returned: after one that raised there is no tree at all)
+            return None, out
         self.last_route = "kernel-large" if large else "kernel"
         bar = tqdm(total=self.n) if self.pbar else None
         try:
@@ -752,6 +761,63 @@ class RRT(object):
             if bar is not None:
                 bar.close()
         return res, out
+
+    # ------------------------------------------------------------------ many goals against the tree of the last plan()
+    def _goal_array(self, goals) -> np.ndarray:
+        g = np.asarray(goals)
+        if g.ndim == 1 and g.shape == (2,):
+            g = g[np.newaxis, :]
+        if g.ndim != 2 or g.shape[1] != 2:
+            raise ValueError(f"goals must be an (M, 2) array of grid cells (or one cell), got shape {g.shape}")
+        if not np.issubdtype(g.dtype, np.integer):
+            gf = np.asarray(g, dtype=np.float64)
+            if not np.all(np.isfinite(gf)) or np.any(gf != np.floor(gf)):
+                raise ValueError("goals must be integer grid cells")
+            g = gf
+        W, H = np.asarray(self.og).shape
+        out = (g[:, 0] < 0) | (g[:, 0] >= W) | (g[:, 1] < 0) | (g[:, 1] >= H)
+        if np.any(out):
+            k = int(np.flatnonzero(out)[0])
+            raise ValueError(f"goal {k} = {g[k].astype(np.int64).tolist()} lies outside the {W}x{H} occupancy grid")
+        return g.astype(np.int64)
+
+    def connect_goals(self, goals) -> Tuple[np.ndarray, np.ndarray]:
+        """Connect many goals to the tree of this planner's last plan(), in one device call (rrt_plan_connect_goals): a tree
+        grown from xstart serves every goal, so routes to more goals need no second plan().
+
+        goals: (M, 2) integer cells (a single cell is M = 1).  Returns (vertex int32[M], cost float64[M]): per goal what go2goal
+        (rrt.py:311-319) decides over the tree vertices [0, j) -- the tree before the goal row of plan()'s own xgoal -- i.e. the
+        first vertex, in stable (cost, index) order of cost = vcosts[k] + dist(k, goal), with a free line of sight to the goal,
+        and that cost.  For plan()'s own xgoal this is the parent and the cost of its goal vertex.  Where no vertex connects
+        (walled off, or the goal on an obstacle cell): vertex -1, cost inf -- the reference's fall-backs for that case (vgoal = 0,
+        the IndexError) are plan()'s and are not reproduced here.
+
+        RuntimeError before any plan() and after set_og / set_og_resident / set_n until the next plan(); ValueError for a goal
+        outside the grid and when the last plan() ran on the host (a custom cost function, or a problem beyond the kernels)."""
+        g = self._goal_array(goals)
+        if self._tree_resident is None:
+            raise RuntimeError("connect_goals: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        if self._tree_resident == "host":
+            raise ValueError("connect_goals: the last plan() ran on the host route (a custom cost function has no device cost; a grid or n beyond "
+                             "the kernels' range is not planned on the device), so its tree is not resident on the device")
+        return self._device().connect_goals(g)
+
+    def paths_to(self, T: nx.DiGraph, goals) -> list:
+        """Routes from xstart to many goals over the tree T of the last plan(): one connect_goals call, then per goal the (k, 2)
+        array of points along the tree to the vertex the goal connects to, followed by the goal itself; None where no vertex
+        connects.  (The parent walks run on the host, like route2gv.)"""
+        vertex, _ = self.connect_goals(goals)
+        g = np.asarray(goals).reshape(-1, 2).astype(np.int64)  # (validated by connect_goals)
+        lazy_pts = T.lazy_points() if isinstance(T, TreeDiGraph) else None
+        out = []
+        for v, goal in zip(vertex.tolist(), g):
+            if v < 0:
+                out.append(None)
+                continue
+            path = self.route2gv(T, v)
+            pts = [lazy_pts[u] for u in path] if lazy_pts is not None else [T.nodes[u]["pt"] for u in path]
+            out.append(np.array(pts + [goal], dtype=np.int64).reshape(-1, 2))
+        return out
 
     def go2goal(self, vcosts, points, xgoal, j, children, parents):
         """Connect the goal to the cheapest tree vertex that sees it (reference rrt.py:284-332), on the host arrays the
