@@ -192,6 +192,33 @@ int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out);
  * RRT_FLAG_DUBINS.  The first call allocates scratch on the batch (at most 512 slabs of n_cap words and 128 MiB, at least one slab),
  * freed with the batch. */
 int rrt_batch_connect_goals(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost);
+/* Finished routes from the start to m goals over the tree that query q left on the device, in one call and without leaving the
+ * device until the answer is read back (rrt_routes.h); optionally shortened by greedy line-of-sight shortcuts.
+ *   vertex[g], cost[g]: exactly what rrt_batch_connect_goals gives (the same kernel decides them).
+ *   vertex[g] == -1: the route of g has 0 rows and length[g] = +inf.
+ *   Otherwise the raw route P is root = vertex 0, ..., vertex[g] along the parent pointers, then the goal: k rows (x, y, id), id the
+ *   tree vertex, -1 for the goal row.
+ *   flags & RRT_ROUTES_SHORTCUT: row 0 is emitted, and from the anchor a = 0, while a < k-1, the next row is the LARGEST b in
+ *   (a, k-1] with b == a+1 or collisionfree(P[a], P[b]) -- the line walked from P[a] to P[b], start side to goal side (the walk of
+ *   rrt.py:202-229 is not symmetric); then a = b.  "Largest visible", not "up to the first blocked one": the visible rows need not
+ *   be contiguous.  b == a+1 is taken without a test (a tree edge, or the goal edge go2goal tested).
+ *   length[g]: the f64 sum, left to right from the root, of sqrt((double)d2) over the legs that were emitted, d2 the exact integer
+ *   squared distance.  Without shortcuts it can differ from cost[g] in the last bits (another order of summation; RRT* prices a
+ *   vertex when it is inserted).
+ *   offsets[0..m]: CSR offsets into the rows of all goals, in goal order; offsets[m] is the row count.
+ * The rows stay on the batch: rrt_batch_routes_rows copies them out.  Refusals, and the batch afterwards, as for
+ * rrt_batch_connect_goals (one validation serves both calls); RRT_E_ARG also for flags other than RRT_ROUTES_SHORTCUT and for goals
+ * whose raw routes have more than 2^28 rows together (pass fewer goals per call).  m == 0: RRT_OK, offsets[0] = 0, nothing is launched.
+ * The parent walks are bounded by j steps: one that is not at vertex 0 by then fails the whole call with RRT_E_HIP, before any row
+ * is written.  The first call allocates scratch on the batch (32 bytes a goal, 20 bytes a raw row), later calls grow it, the batch
+ * frees it.  Synchronous on the context's stream: it waits once for the row count (which sizes the rows) and once for the answer. */
+#define RRT_ROUTES_SHORTCUT 0x1u
+int rrt_batch_routes(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                     int64_t *offsets);
+/* The rows of the last rrt_batch_routes on this batch: xy is host (rows, 2) int32, id host int32[rows], rows == its offsets[m].
+ * RRT_E_ARG: NULL (with rows > 0); no rrt_batch_routes on this batch yet, or its last one failed; rows differs from that call's
+ * total; an rrt_batch_launch or rrt_batch_rearm since (the tree the rows belong to is being replaced). */
+int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -233,6 +260,9 @@ int rrt_plan_resume(rrt_ctx *ctx, const double *unitball, int32_t count, rrt_res
 int rrt_plan_batch(rrt_ctx *ctx, int32_t Q, const rrt_query *queries, rrt_result *out);
 /* rrt_batch_connect_goals on the tree of the context's last rrt_plan / rrt_plan_resume (the batch behind them stays resident) */
 int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost);
+/* rrt_batch_routes / rrt_batch_routes_rows on the tree of the context's last rrt_plan / rrt_plan_resume */
+int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets);
+int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

@@ -34,6 +34,7 @@ FLAG_DUBINS = 64
 FLAG_ONEBODY = 128
 FLAG_NOPIPE1 = 32768
 FLAG_LARGE_GRID = 65536
+RRT_ROUTES_SHORTCUT = 1  # flags of rrt_batch_routes / rrt_plan_routes
 WALK_AUTO, WALK_U24, WALK_U26, WALK_WIDE = 0, 1, 2, 3  # rrt_prim_collisionfree_walk
 
 
@@ -70,6 +71,7 @@ SYMBOLS = (
     "rrt_prim_collisionfree", "rrt_prim_nearest_within", "rrt_prim_sqrt_u32", "rrt_prim_sqrt_u24", "rrt_prim_sqrt_f64",
     "rrt_prim_collisionfree_walk", "rrt_prim_sqrt_u25",
     "rrt_batch_connect_goals", "rrt_plan_connect_goals",
+    "rrt_batch_routes", "rrt_batch_routes_rows", "rrt_plan_routes", "rrt_plan_routes_rows",
 )
 
 
@@ -166,6 +168,10 @@ def lib():
             "rrt_prim_sqrt_u25": ([vp, u32, u32, vp], C.c_int),
             "rrt_batch_connect_goals": ([vp, i32, vp, i32, vp, vp], C.c_int),
             "rrt_plan_connect_goals": ([vp, vp, i32, vp, vp], C.c_int),
+            "rrt_batch_routes": ([vp, i32, vp, i32, u32, vp, vp, vp, vp], C.c_int),
+            "rrt_batch_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
+            "rrt_plan_routes": ([vp, vp, i32, u32, vp, vp, vp, vp], C.c_int),
+            "rrt_plan_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -207,6 +213,21 @@ def _goal_arrays(goals):
         raise ValueError(f"goals must have shape (M, 2) or (2,), got {g.shape}")
     g = np.ascontiguousarray(g, dtype=np.int32)
     return g, np.full(g.shape[0], -1, dtype=np.int32), np.full(g.shape[0], np.inf, dtype=np.float64)
+
+
+def _routes(handle, call, rows_call, goals, shortcut):
+    """the two steps of a routes call: `call` decides and builds the routes on the device and gives the CSR offsets, `rows_call`
+    copies the rows out.  (vertex, cost, length, offsets int64[M + 1], xy int32[(rows, 2)], ids int32[rows])"""
+    g, vertex, cost = _goal_arrays(goals)
+    m = g.shape[0]
+    length = np.full(m, np.inf, dtype=np.float64)
+    offsets = np.zeros(m + 1, dtype=np.int64)
+    _check(handle, call(g.ctypes.data, m, RRT_ROUTES_SHORTCUT if shortcut else 0, vertex.ctypes.data, cost.ctypes.data, length.ctypes.data, offsets.ctypes.data))
+    rows = int(offsets[m])
+    xy = np.empty((rows, 2), dtype=np.int32)
+    ids = np.empty(rows, dtype=np.int32)
+    _check(handle, rows_call(xy.ctypes.data, ids.ctypes.data, rows))
+    return vertex, cost, length, offsets, xy, ids
 
 
 class ResultArrays:
@@ -391,6 +412,11 @@ class Context:
         _check(self._h, lib().rrt_plan_connect_goals(self._h, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
         return vertex, cost
 
+    def routes(self, goals, shortcut=False):
+        """rrt_plan_routes + rrt_plan_routes_rows: Batch.routes on the tree of this context's last plan() / plan_resume()"""
+        L = lib()
+        return _routes(self._h, lambda *a: L.rrt_plan_routes(self._h, *a), lambda *a: L.rrt_plan_routes_rows(self._h, *a), goals, shortcut)
+
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
         query stops at RRT_NEED_UNITBALL -- use Batch for the staged hand-over).  Returns (rc, [ResultArrays])."""
@@ -574,6 +600,22 @@ class Batch:
         g, vertex, cost = _goal_arrays(goals)
         _check(self.ctx.handle, lib().rrt_batch_connect_goals(self._h, int(q), g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
         return vertex, cost
+
+    def routes(self, q, goals, shortcut=False):
+        """rrt_batch_routes + rrt_batch_routes_rows: finished routes from the start to the goals (M, 2) over the tree of query q, built
+        on the device.  Returns (vertex, cost, length float64[M], offsets int64[M + 1], xy int32[(rows, 2)], ids int32[rows]): vertex
+        and cost as connect_goals gives them; the route of goal g is xy[offsets[g]:offsets[g + 1]], the points root .. vertex[g] along
+        the tree and then the goal, ids the tree vertices and -1 for the goal row; no rows and length inf where vertex is -1.
+        shortcut=True: from each emitted row the route jumps to the farthest later row it has a free line of sight to."""
+        L = lib()
+        return _routes(self.ctx.handle, lambda *a: L.rrt_batch_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_routes_rows(self._h, *a), goals, shortcut)
+
+    def routes_rows(self, rows):
+        """rrt_batch_routes_rows alone: (xy, ids) of the last routes() call, which left `rows` rows"""
+        xy = np.empty((int(rows), 2), dtype=np.int32)
+        ids = np.empty(int(rows), dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_routes_rows(self._h, xy.ctypes.data, ids.ctypes.data, int(rows)))
+        return xy, ids
 
     def debug_cycles(self, q):
         out = (C.c_uint64 * 38)()

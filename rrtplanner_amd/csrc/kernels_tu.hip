@@ -31,6 +31,9 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_goals.h"
 
+#elif RRT_TU == 6  // finished routes to many goals, with line-of-sight shortcuts (rrt_route_*_kernel): not a team kernel
+#include "rrt_routes.h"
+
 #else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_block.h"

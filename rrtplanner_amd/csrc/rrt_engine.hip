@@ -26,6 +26,8 @@
 #include "rrt_kernel_decls.h"
 #define RRT_GOALS_DECL_ONLY
 #include "rrt_goals.h"
+#define RRT_ROUTES_DECL_ONLY
+#include "rrt_routes.h"
 #include "rrt_prims.h"
 
 using namespace rrtdev;
@@ -199,6 +201,12 @@ struct rrt_batch {
     int32_t *d_goal_vertex = nullptr;    // [goal_cap]
     double *d_goal_cost = nullptr;       // [goal_cap]
     int32_t goal_cap = 0;
+    // rrt_batch_routes: per-goal arrays and the rows of the routes, allocated at the first call, grown by later ones (rrt_routes.h)
+    unsigned char *d_route_goal = nullptr;  // [length | raw_off | fin_off | cnt | kept | err] for route_goal_cap goals
+    int32_t route_goal_cap = 0;
+    unsigned char *d_route_rows = nullptr;  // [row_xy | row_id | out_xy | out_id] for route_row_cap rows
+    int64_t route_row_cap = 0;
+    int64_t route_rows = -1;                // dense rows the last rrt_batch_routes left for rrt_batch_routes_rows; -1: none (launch, rearm)
 };
 
 // The limit is a property of the kernel on a device, shared by every batch that launches it: it is only ever raised, to the
@@ -538,7 +546,7 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost};
+                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -847,6 +855,7 @@ extern "C" int rrt_batch_set_unitball(rrt_batch *b, int32_t q, const double *uni
 extern "C" int rrt_batch_rearm(rrt_batch *b) {
     if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_rearm: NULL");
     rrt_ctx *ctx = b->ctx;
+    b->route_rows = -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (auto &d : b->h_desc)
         if (d.status != ST_IDLE) arm_desc(d);
@@ -1024,6 +1033,7 @@ static int plan_launch(rrt_batch *b, LaunchPlan &p) {
 extern "C" int rrt_batch_launch(rrt_batch *b) {
     if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_launch: NULL");
     rrt_ctx *ctx = b->ctx;
+    b->route_rows = -1;
     if (!ctx->og) return fail(ctx, RRT_E_NOGRID, "rrt_batch_launch: no grid");
     if (b->gridW != ctx->W || b->gridH != ctx->H) return fail(ctx, RRT_E_ARG, "rrt_batch_launch: grid changed shape");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1259,9 +1269,12 @@ extern "C" int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out) {
 }
 
 // ---- many goals against a finished tree (rrt_goals.h) ----
-static int connect_goals(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+// The part that rrt_batch_connect_goals and rrt_batch_routes share: every refusal, the goals packed and uploaded, the scratch of the
+// first call, and the goals kernel launched on the context's stream.  Nothing is read back and nothing waited for: vertex and cost
+// of the m goals are in b->d_goal_vertex / b->d_goal_cost once the stream gets there.  m == 0: RRT_OK, nothing launched.
+static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, bool null_out) {
     rrt_ctx *ctx = b->ctx;
-    if (!goals_xy || !vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (!goals_xy || null_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     if (b->flags & RRT_FLAG_DUBINS)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (an edge to a goal is a Dubins word to a goal pose; these kernels price straight lines)", who);
     if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
@@ -1329,6 +1342,12 @@ static int connect_goals(const char *who, rrt_batch *b, int32_t q, const int32_t
     HIPCHK(ctx, hipMemcpyAsync(b->d_goals, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
     HIPCHK(ctx, hipGetLastError());
+    return RRT_OK;
+}
+
+static int connect_goals(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost); rc != RRT_OK || m == 0) return rc;
     HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_goal_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(cost, b->d_goal_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (also: the staging buffer is reused)
@@ -1344,6 +1363,128 @@ extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int
     if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_goals: NULL");
     if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_goals: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
     return connect_goals("rrt_plan_connect_goals", ctx->single, 0, goals_xy, m, vertex, cost);
+}
+
+// ---- finished routes to many goals (rrt_routes.h) ----
+static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
+                        double *length, int64_t *offsets) {
+    rrt_ctx *ctx = b->ctx;
+    b->route_rows = -1;  // whatever happens below, the rows of an earlier call are gone
+    if (flags & ~(uint32_t)RRT_ROUTES_SHORTCUT) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_ROUTES_SHORTCUT is defined", who, flags);
+    if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost || !length || !offsets); rc != RRT_OK) return rc;
+    if (m == 0) {
+        offsets[0] = 0;
+        b->route_rows = 0;
+        return RRT_OK;
+    }
+    if (m > b->route_goal_cap) {
+        b->route_goal_cap = 0;
+        if (b->d_route_goal) HIPCHK(ctx, hipFree(b->d_route_goal));
+        b->d_route_goal = nullptr;
+        // [length f64 m | raw_off i64 m+1 | fin_off i64 m+1 | cnt i32 m | kept i32 m | err i32]
+        HIPCHK(ctx, hipMalloc((void **)&b->d_route_goal, (size_t)m * 32 + 2 * sizeof(int64_t) + sizeof(int32_t)));
+        b->route_goal_cap = m;
+    }
+    const bool cut = (flags & RRT_ROUTES_SHORTCUT) != 0;
+    const size_t cap = (size_t)b->route_goal_cap;
+    RoutesView rv{};
+    rv.og = ctx->og;
+    rv.H = ctx->H;
+    rv.nodes = b->d_nodes + (size_t)q * b->node_stride;
+    rv.parent = b->d_parent + (size_t)q * b->node_stride;
+    rv.j = b->h_desc[(size_t)q].j;
+    rv.goals = b->d_goals;
+    rv.vertex = b->d_goal_vertex;
+    rv.m = m;
+    rv.length = reinterpret_cast<double *>(b->d_route_goal);
+    rv.raw_off = reinterpret_cast<int64_t *>(rv.length + cap);
+    rv.fin_off = cut ? rv.raw_off + cap + 1 : rv.raw_off;
+    rv.cnt = reinterpret_cast<int32_t *>(rv.raw_off + 2 * (cap + 1));
+    rv.kept = rv.cnt + cap;
+    rv.err = rv.kept + cap;
+    const unsigned lanes_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB), waves_grid = (unsigned)((m + ROUTE_TPB / 64 - 1) / (ROUTE_TPB / 64));
+    HIPCHK(ctx, hipMemsetAsync(rv.err, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.cnt, rv.raw_off, m);
+    HIPCHK(ctx, hipGetLastError());
+    // the one wait that the sizes force: the rows of all routes together decide how much memory the rows need
+    int64_t raw_rows = 0;
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&raw_rows, rv.raw_off + m, sizeof raw_rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, rv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err)
+        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
+    if (raw_rows < 0 || (uint64_t)raw_rows > ROUTE_ROW_BUDGET)
+        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d goals have %lld rows together, at most %zu per call: pass fewer goals at a time", who, m,
+                    (long long)raw_rows, ROUTE_ROW_BUDGET);
+    if (raw_rows > b->route_row_cap) {
+        b->route_row_cap = 0;
+        if (b->d_route_rows) HIPCHK(ctx, hipFree(b->d_route_rows));
+        b->d_route_rows = nullptr;
+        // [row_xy u32 | row_id i32 | out_xy i32 x 2 | out_id i32], each of raw_rows (shortcuts only ever drop rows)
+        HIPCHK(ctx, hipMalloc((void **)&b->d_route_rows, (size_t)raw_rows * 5 * sizeof(int32_t)));
+        b->route_row_cap = raw_rows;
+    }
+    const size_t rcap = (size_t)b->route_row_cap;
+    rv.row_xy = reinterpret_cast<uint32_t *>(b->d_route_rows);
+    rv.row_id = reinterpret_cast<int32_t *>(rv.row_xy + rcap);
+    rv.out_xy = rv.row_id + rcap;
+    rv.out_id = rv.out_xy + 2 * rcap;
+    hipLaunchKernelGGL(rrt_route_fill_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv, cut ? 0 : 1);
+    if (cut) {
+        const unsigned wgs = (unsigned)(m < ROUTE_CUT_MAX_WG ? m : ROUTE_CUT_MAX_WG);
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_route_cut_large_kernel : rrt_route_cut_kernel, dim3(wgs), dim3(TPB), 0, ctx->stream, rv);
+        hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.kept, rv.fin_off, m);
+    }
+    hipLaunchKernelGGL(rrt_route_pack_kernel, dim3(waves_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_goal_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cost, b->d_goal_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(length, rv.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(offsets, rv.fin_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (offsets[m] < 0 || offsets[m] > raw_rows) return fail(ctx, RRT_E_HIP, "%s: %lld rows kept of %lld", who, (long long)offsets[m], (long long)raw_rows);
+    b->route_rows = offsets[m];
+    return RRT_OK;
+}
+
+static int batch_routes_rows(const char *who, rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
+    rrt_ctx *ctx = b->ctx;
+    if (b->route_rows < 0)
+        return fail(ctx, RRT_E_ARG, "%s: no routes on this batch (no rrt_batch_routes call yet, one that failed, or a launch or rearm since)", who);
+    if (rows != b->route_rows) return fail(ctx, RRT_E_ARG, "%s: rows=%lld, the last rrt_batch_routes call left %lld", who, (long long)rows, (long long)b->route_rows);
+    if (rows == 0) return RRT_OK;
+    if (!xy || !id) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int32_t *out_xy = reinterpret_cast<int32_t *>(b->d_route_rows) + 2 * (size_t)b->route_row_cap;
+    HIPCHK(ctx, hipMemcpyAsync(xy, out_xy, (size_t)rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(id, out_xy + 2 * (size_t)b->route_row_cap, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_routes(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                                int64_t *offsets) {
+    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_routes: NULL");
+    return batch_routes("rrt_batch_routes", b, q, goals_xy, m, flags, vertex, cost, length, offsets);
+}
+
+extern "C" int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
+    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_routes_rows: NULL");
+    return batch_routes_rows("rrt_batch_routes_rows", b, xy, id, rows);
+}
+
+extern "C" int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_routes: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_routes: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
+    return batch_routes("rrt_plan_routes", ctx->single, 0, goals_xy, m, flags, vertex, cost, length, offsets);
+}
+
+extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_routes_rows: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_routes_rows: no routes (no rrt_plan on this context yet, or its batch is gone)");
+    return batch_routes_rows("rrt_plan_routes_rows", ctx->single, xy, id, rows);
 }
 
 extern "C" int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]) {

@@ -186,6 +186,9 @@ class _DubinsBase(RRT):
     def paths_to(self, T, goals):
         return self.connect_goals(goals)
 
+    def routes_to(self, goals, shortcut=False):
+        return self.connect_goals(goals)
+
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""
         legs = []

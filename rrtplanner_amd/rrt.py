@@ -819,6 +819,29 @@ class RRT(object):
             out.append(np.array(pts + [goal], dtype=np.int64).reshape(-1, 2))
         return out
 
+    def routes_to(self, goals, shortcut: bool = False) -> Tuple[list, np.ndarray]:
+        """Finished routes from xstart to many goals over the tree of the last plan(), built on the device in one call
+        (rrt_plan_routes): connect_goals' decision, the parent walks, optionally line-of-sight shortcuts, and the lengths.
+
+        Returns (routes, length): routes[g] is the (k, 2) int64 array of points xstart .. goal -- without shortcuts what paths_to
+        gives -- or None where no vertex connects; length float64[M] is the sum of the legs' lengths from xstart on, inf for None.
+        shortcut=True: starting at xstart, the route goes on to the farthest later point of the raw route that has a free line of
+        sight (collisionfree, walked towards the goal) from where it stands; every leg stays free and the route never gets longer.
+        It takes no T: the tree is the one resident on the device.  RuntimeError / ValueError as connect_goals."""
+        g = self._goal_array(goals)
+        if self._tree_resident is None:
+            raise RuntimeError("routes_to: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        if self._tree_resident == "host":
+            raise ValueError("routes_to: the last plan() ran on the host route (a custom cost function has no device cost; a grid or n beyond "
+                             "the kernels' range is not planned on the device), so its tree is not resident on the device")
+        vertex, _, length, offsets, xy, _ = self._device().routes(g, shortcut=shortcut)
+        if len(vertex) == 0:
+            return [], length
+        routes = np.split(xy.astype(np.int64), offsets[1:-1])  # (views of one array: no per-goal copies)
+        for k in np.flatnonzero(vertex < 0).tolist():
+            routes[k] = None
+        return routes, length
+
     def go2goal(self, vcosts, points, xgoal, j, children, parents):
         """Connect the goal to the cheapest tree vertex that sees it (reference rrt.py:284-332), on the host arrays the
         caller passes -- the helper of the reference's public surface; plan() itself does this step on the device.
