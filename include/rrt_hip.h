@@ -219,6 +219,31 @@ int rrt_batch_routes(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m
  * RRT_E_ARG: NULL (with rows > 0); no rrt_batch_routes on this batch yet, or its last one failed; rows differs from that call's
  * total; an rrt_batch_launch or rrt_batch_rearm since (the tree the rows belong to is being replaced). */
 int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows);
+/* Keep the finished tree of query q when the map changed (rrt_keep.h): the context's CURRENT grid og' -- same shape as the batch's,
+ * set by rrt_set_grid / rrt_noise_grids / rrt_select_frame since the query ran -- is adopted for query q, and the vertices that
+ * still hang on the root through free edges become a view next to the tree:
+ *   edge_ok[0] = the root's cell is free in og';  edge_ok[k] = collisionfree(og', nodes[parent[k]], nodes[k]) for k > 0, the line
+ *   walked from the parent to the child;  alive[k] = edge_ok[k] and alive[parent[k]].
+ * *n_alive = number of alive vertices; alive (host, j bytes, may be NULL) = the flags.  The tree arrays are not modified and no cost
+ * changes: rrt_batch_get_result gives what it gave before.  Afterwards rrt_batch_connect_goals / rrt_batch_routes accept the new
+ * grid for query q, take every line of sight on it and consider only the alive vertices, in stable (cost, original index) order;
+ * the vertex numbers and route ids they return are the original ones.  No alive vertex (the root blocked): every goal answers
+ * -1 / +inf with 0 rows.  Every call starts from the whole tree, it is not cumulative: keeping the tree for the original map again
+ * restores every vertex.  Other queries of the batch stay refused until they are kept themselves.  rrt_batch_rearm,
+ * rrt_batch_launch and rrt_batch_set_query (a new rrt_plan) drop the view.
+ * The walk is not symmetric (rrt.py:202-229).  plan() tested the edges of a reference-mode tree from the parent's side, so on an
+ * unchanged map all of its vertices stay alive; the rewire of RRT_FLAG_REWIRE tests child to parent, so on such a tree an edge may
+ * be cut even on an unchanged map.  Only the parent-to-child direction is tested.
+ * Synchronous on the context's stream.  RRT_E_ARG: NULL; q out of range; a query that has not finished; a context grid of another
+ * shape than the batch's.  RRT_E_UNSUPPORTED: a batch created with RRT_FLAG_DUBINS.  Such a refusal changes nothing.  A call that
+ * fails later (an allocation, a device error) drops a view query q had together with the grid that view was built for: the query
+ * is then refused by the goals and routes calls until it is kept or launched again, never answered from its whole tree on a grid
+ * that cut it.  An rrt_batch_set_query that is refused leaves the query and its view as they were.  The first call allocates
+ * scratch on the batch (10 bytes a vertex of capacity, and 16 for each query that is kept), freed with the batch. */
+int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive);
+/* kernel time in ms of the three stages of the last successful rrt_batch_keep_tree on this batch, from events on the stream:
+ * edge test, pointer jumping, compaction.  RRT_E_ARG when there is none (or its tree had no vertex). */
+int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -263,6 +288,12 @@ int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int
 /* rrt_batch_routes / rrt_batch_routes_rows on the tree of the context's last rrt_plan / rrt_plan_resume */
 int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets);
 int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows);
+/* rrt_batch_keep_tree / rrt_batch_keep_tree_ms on the tree of the context's last rrt_plan / rrt_plan_resume */
+int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive);
+int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]);
+/* *j = vertices of the finished tree of the context's last rrt_plan / rrt_plan_resume: the bytes rrt_plan_keep_tree writes into
+ * `alive`.  RRT_E_ARG: NULL; no finished rrt_plan on this context. */
+int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

@@ -72,6 +72,7 @@ SYMBOLS = (
     "rrt_prim_collisionfree_walk", "rrt_prim_sqrt_u25",
     "rrt_batch_connect_goals", "rrt_plan_connect_goals",
     "rrt_batch_routes", "rrt_batch_routes_rows", "rrt_plan_routes", "rrt_plan_routes_rows",
+    "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
 )
 
 
@@ -172,6 +173,11 @@ def lib():
             "rrt_batch_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
             "rrt_plan_routes": ([vp, vp, i32, u32, vp, vp, vp, vp], C.c_int),
             "rrt_plan_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
+            "rrt_batch_keep_tree": ([vp, i32, C.POINTER(i32), vp], C.c_int),
+            "rrt_batch_keep_tree_ms": ([vp, C.POINTER(C.c_float * 3)], C.c_int),
+            "rrt_plan_keep_tree": ([vp, C.POINTER(i32), vp], C.c_int),
+            "rrt_plan_keep_tree_ms": ([vp, C.POINTER(C.c_float * 3)], C.c_int),
+            "rrt_plan_tree_size": ([vp, C.POINTER(i32)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -228,6 +234,19 @@ def _routes(handle, call, rows_call, goals, shortcut):
     ids = np.empty(rows, dtype=np.int32)
     _check(handle, rows_call(xy.ctypes.data, ids.ctypes.data, rows))
     return vertex, cost, length, offsets, xy, ids
+
+
+def _keep_tree(handle, call, size, j):
+    """a keep_tree call: `call` takes (n_alive, alive) and fills one flag per vertex of the tree.  `size` bounds them and comes from
+    the library: the capacity the batch was created with, or the tree size the library reports for the query.  j() is asked for the
+    vertices of the tree after the call has accepted the query.  bool[j]"""
+    alive = np.zeros(max(int(size), 1), dtype=np.uint8)
+    n_alive = C.c_int32(-1)
+    _check(handle, call(C.byref(n_alive), alive.ctypes.data))
+    alive = alive[:int(j())].astype(bool)
+    if int(alive.sum()) != n_alive.value:
+        raise RRTError(RRT_E_HIP, f"keep_tree: {n_alive.value} vertices alive, {int(alive.sum())} flags set")
+    return alive
 
 
 class ResultArrays:
@@ -416,6 +435,19 @@ class Context:
         """rrt_plan_routes + rrt_plan_routes_rows: Batch.routes on the tree of this context's last plan() / plan_resume()"""
         L = lib()
         return _routes(self._h, lambda *a: L.rrt_plan_routes(self._h, *a), lambda *a: L.rrt_plan_routes_rows(self._h, *a), goals, shortcut)
+
+    def keep_tree(self):
+        """rrt_plan_keep_tree: Batch.keep_tree on the tree of this context's last plan() / plan_resume()"""
+        L = lib()
+        j = C.c_int32(0)
+        _check(self._h, L.rrt_plan_tree_size(self._h, C.byref(j)))
+        return _keep_tree(self._h, lambda *a: L.rrt_plan_keep_tree(self._h, *a), j.value, lambda: j.value)
+
+    def keep_tree_ms(self):
+        """kernel time in ms of the last keep_tree(): (edge test, pointer jumping, compaction)"""
+        ms = (C.c_float * 3)()
+        _check(self._h, lib().rrt_plan_keep_tree_ms(self._h, C.byref(ms)))
+        return tuple(ms)
 
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
@@ -609,6 +641,21 @@ class Batch:
         shortcut=True: from each emitted row the route jumps to the farthest later row it has a free line of sight to."""
         L = lib()
         return _routes(self.ctx.handle, lambda *a: L.rrt_batch_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_routes_rows(self._h, *a), goals, shortcut)
+
+    def keep_tree(self, q):
+        """rrt_batch_keep_tree: keep the finished tree of query q on the context's CURRENT grid (set_grid / select_frame since the
+        query ran; same shape).  Returns alive bool[j]: the vertices whose edges up to the root are all free on it, each edge walked
+        from the parent to the child.  Afterwards connect_goals / routes of query q run on the new grid over the alive vertices only
+        and answer in the original vertex numbers; the tree arrays (get_result) are untouched.  Not cumulative: every call starts
+        from the whole tree.  rearm, launch and set_query drop the view."""
+        L = lib()
+        return _keep_tree(self.ctx.handle, lambda *a: L.rrt_batch_keep_tree(self._h, int(q), *a), self.n_cap, lambda: self.get_result(q, arrays=False).j)
+
+    def keep_tree_ms(self):
+        """kernel time in ms of the last keep_tree(): (edge test, pointer jumping, compaction)"""
+        ms = (C.c_float * 3)()
+        _check(self.ctx.handle, lib().rrt_batch_keep_tree_ms(self._h, C.byref(ms)))
+        return tuple(ms)
 
     def routes_rows(self, rows):
         """rrt_batch_routes_rows alone: (xy, ids) of the last routes() call, which left `rows` rows"""

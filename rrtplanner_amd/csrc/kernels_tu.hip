@@ -34,6 +34,9 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #elif RRT_TU == 6  // finished routes to many goals, with line-of-sight shortcuts (rrt_route_*_kernel): not a team kernel
 #include "rrt_routes.h"
 
+#elif RRT_TU == 7  // keep a finished tree when the map changes: the view of its alive vertices (rrt_keep_*_kernel): not a team kernel
+#include "rrt_keep.h"
+
 #else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_block.h"

@@ -28,6 +28,8 @@
 #include "rrt_goals.h"
 #define RRT_ROUTES_DECL_ONLY
 #include "rrt_routes.h"
+#define RRT_KEEP_DECL_ONLY
+#include "rrt_keep.h"
 #include "rrt_prims.h"
 
 using namespace rrtdev;
@@ -207,7 +209,26 @@ struct rrt_batch {
     unsigned char *d_route_rows = nullptr;  // [row_xy | row_id | out_xy | out_id] for route_row_cap rows
     int64_t route_row_cap = 0;
     int64_t route_rows = -1;                // dense rows the last rrt_batch_routes left for rrt_batch_routes_rows; -1: none (launch, rearm)
+    // rrt_batch_keep_tree: the views of the queries that were kept on a new map (rrt_keep.h), allocated at the first call per query
+    std::vector<unsigned char *> d_keep;    // [Q] nullptr, or [live_vcost f64 | live_nodes u32 | live_id i32], each of n_cap
+    std::vector<int32_t> keep_alive;        // [Q] vertices of the view; -1: no view, the goals and routes calls see the whole tree
+    unsigned char *d_keep_tmp = nullptr;    // [anc i32 x 2 | ok u8 x 2 | count i32 at the end], each array of n_cap (rounded up to 8 bytes)
+    hipEvent_t ev_keep[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_keep_tree
+    bool keep_timed = false;
 };
+
+// no query of the batch has a view any more (a launch, a rearm), or only query q (a new query in its place, a keep_tree that starts
+// over).  The grid a view was built for goes with it: that grid was adopted for the alive vertices only, so without the view the
+// whole tree has no grid it is known to be valid on, and goals_decide refuses the query until it is kept or launched again.  A query
+// without a view keeps its recorded grid: that is the grid its whole tree ran on.
+static void drop_keep_views(rrt_batch *b, int32_t q = -1) {
+    for (size_t k = 0; k < b->keep_alive.size(); ++k)
+        if ((q < 0 || (size_t)q == k) && b->keep_alive[k] >= 0) {
+            b->keep_alive[k] = -1;
+            b->ran_gen[k] = 0;
+            b->ran_og[k] = nullptr;
+        }
+}
 
 // The limit is a property of the kernel on a device, shared by every batch that launches it: it is only ever raised, to the
 // largest request seen, and hipFuncSetAttribute is called when a launch needs more than the kernel already has -- once per
@@ -546,9 +567,13 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows};
+                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows, b->d_keep_tmp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (unsigned char *p : b->d_keep)
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : b->ev_keep)
+        if (e) (void)hipEventDestroy(e);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -682,6 +707,8 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     for (auto &d : b->h_desc) d.status = ST_IDLE;
     b->ran_gen.assign((size_t)Q, 0);
     b->ran_og.assign((size_t)Q, nullptr);
+    b->d_keep.assign((size_t)Q, nullptr);
+    b->keep_alive.assign((size_t)Q, -1);
     const size_t q = (size_t)Q;
 #define ALLOC(ptr, bytes)                                   \
     do {                                                    \
@@ -797,6 +824,7 @@ extern "C" int rrt_batch_set_query(rrt_batch *b, int32_t q, const rrt_query *qu)
         b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
     }
     QDesc &d = b->h_desc[(size_t)q];
+    drop_keep_views(b, q);  // from here on the query is replaced; a call refused above leaves it, and its view, as they were
     d = QDesc{};
     d.alg = qu->alg;
     d.n = qu->n;
@@ -856,6 +884,7 @@ extern "C" int rrt_batch_rearm(rrt_batch *b) {
     if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_rearm: NULL");
     rrt_ctx *ctx = b->ctx;
     b->route_rows = -1;
+    drop_keep_views(b);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (auto &d : b->h_desc)
         if (d.status != ST_IDLE) arm_desc(d);
@@ -1034,6 +1063,7 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
     if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_launch: NULL");
     rrt_ctx *ctx = b->ctx;
     b->route_rows = -1;
+    drop_keep_views(b);
     if (!ctx->og) return fail(ctx, RRT_E_NOGRID, "rrt_batch_launch: no grid");
     if (b->gridW != ctx->W || b->gridH != ctx->H) return fail(ctx, RRT_E_ARG, "rrt_batch_launch: grid changed shape");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1332,15 +1362,30 @@ static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
     gv.nodes = b->d_nodes + (size_t)q * b->node_stride;
     gv.vcost = b->d_vcost + (size_t)q * b->node_stride;
     gv.j = d.j;
+    if (gv.j < 0 || gv.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, gv.j, b->n_cap);
+    // a query that was kept on this grid (rrt_batch_keep_tree): the decision over the view of its alive vertices, dense and in the
+    // original order; the kernel answers in indices of the view, rrt_keep_remap_kernel turns them into the original ones
+    const int32_t kept = b->keep_alive[(size_t)q];
+    const int32_t *live_id = nullptr;
+    if (kept >= 0) {
+        const double *live_vcost = reinterpret_cast<const double *>(b->d_keep[(size_t)q]);
+        const uint32_t *live_nodes = reinterpret_cast<const uint32_t *>(live_vcost + b->n_cap);
+        live_id = reinterpret_cast<const int32_t *>(live_nodes + b->n_cap);
+        gv.nodes = live_nodes;
+        gv.vcost = live_vcost;
+        gv.j = kept <= d.j ? kept : d.j;
+    }
     gv.goals = b->d_goals;
     gv.m = m;
     gv.order = b->d_goal_order;
     gv.slab_words = b->n_cap;
     gv.vertex = b->d_goal_vertex;
     gv.cost = b->d_goal_cost;
-    if (gv.j < 0 || gv.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, gv.j, b->n_cap);
     HIPCHK(ctx, hipMemcpyAsync(b->d_goals, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
+    if (live_id)
+        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, b->d_goal_vertex, live_id, m,
+                           gv.j);
     HIPCHK(ctx, hipGetLastError());
     return RRT_OK;
 }
@@ -1363,6 +1408,125 @@ extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int
     if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_goals: NULL");
     if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_goals: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
     return connect_goals("rrt_plan_connect_goals", ctx->single, 0, goals_xy, m, vertex, cost);
+}
+
+// ---- keep a finished tree when the map changes (rrt_keep.h) ----
+// Adopts the context's current grid for query q and installs the view of the vertices that still hang on the root through edges
+// that are free on it.  Every call starts from the whole tree of the query.  A call refused for its arguments changes nothing.  Past
+// that, a view the query had is dropped together with the grid it was built for (drop_keep_views), so a call that fails half way
+// leaves a query that was kept before refused by goals_decide, never answered from the whole tree on a grid that cut it.
+static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
+    rrt_ctx *ctx = b->ctx;
+    if (!n_alive) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its edges are Dubins words between poses; these kernels test straight lines)", who);
+    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
+    const QDesc &d = b->h_desc[(size_t)q];
+    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
+        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
+                    d.status == ST_IDLE      ? "no query set"
+                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
+                    : d.status == ST_NEED_UB ? "it waits for its unit-ball stream"
+                                             : "its launch failed");
+    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid has another shape than the batch was created for (%dx%d)", who, b->gridW, b->gridH);
+    const int j = d.j;
+    if (j < 0 || j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, j, b->n_cap);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    drop_keep_views(b, q);
+    b->keep_timed = false;
+    const size_t cap = ((size_t)b->n_cap + 7) & ~(size_t)7;
+    if (!b->d_keep_tmp) HIPCHK(ctx, hipMalloc((void **)&b->d_keep_tmp, cap * 10 + 8));
+    if (!b->d_keep[(size_t)q]) HIPCHK(ctx, hipMalloc((void **)&b->d_keep[(size_t)q], (size_t)b->n_cap * 16));
+    for (hipEvent_t &e : b->ev_keep)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    int32_t *anc[2] = {reinterpret_cast<int32_t *>(b->d_keep_tmp), reinterpret_cast<int32_t *>(b->d_keep_tmp) + cap};
+    uint8_t *ok[2] = {b->d_keep_tmp + cap * 8, b->d_keep_tmp + cap * 9};
+    int32_t *d_count = reinterpret_cast<int32_t *>(b->d_keep_tmp + cap * 10);
+    int32_t count = 0;
+    if (j > 0) {
+        KeepView kv{};
+        kv.og = ctx->og;
+        kv.H = ctx->H;
+        kv.nodes = b->d_nodes + (size_t)q * b->node_stride;
+        kv.parent = b->d_parent + (size_t)q * b->node_stride;
+        kv.vcost = b->d_vcost + (size_t)q * b->node_stride;
+        kv.j = j;
+        kv.ok = ok[0];
+        kv.anc = anc[0];
+        const int per_wg = KEEP_TPB / 64;
+        const unsigned edge_wgs = (unsigned)((j + per_wg - 1) / per_wg > KEEP_MAX_WG ? KEEP_MAX_WG : (j + per_wg - 1) / per_wg);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[0], ctx->stream));
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
+                           ctx->stream, kv);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[1], ctx->stream));
+        // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
+        int rounds = 1;
+        while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
+        int cur = 0;
+        for (int r = 0; r < rounds; ++r, cur ^= 1)
+            hipLaunchKernelGGL(rrt_keep_jump_kernel, dim3((unsigned)((j + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, (const uint8_t *)ok[cur],
+                               (const int32_t *)anc[cur], ok[cur ^ 1], anc[cur ^ 1], j);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[2], ctx->stream));
+        KeepCompact kc{};
+        kc.nodes = kv.nodes;
+        kc.vcost = kv.vcost;
+        kc.ok = ok[cur];
+        kc.anc = anc[cur];
+        kc.j = j;
+        kc.alive = ok[cur ^ 1];
+        kc.live_vcost = reinterpret_cast<double *>(b->d_keep[(size_t)q]);
+        kc.live_nodes = reinterpret_cast<uint32_t *>(kc.live_vcost + b->n_cap);
+        kc.live_id = reinterpret_cast<int32_t *>(kc.live_nodes + b->n_cap);
+        kc.count = d_count;
+        hipLaunchKernelGGL(rrt_keep_compact_kernel, dim3(1), dim3(TPB), 0, ctx->stream, kc);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[3], ctx->stream));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        if (alive) HIPCHK(ctx, hipMemcpyAsync(alive, kc.alive, (size_t)j, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        if (count < 0 || count > j) return fail(ctx, RRT_E_HIP, "%s: %d of %d vertices alive", who, count, j);
+        b->keep_timed = true;
+    }
+    b->ran_gen[(size_t)q] = ctx->grid_gen;
+    b->ran_og[(size_t)q] = ctx->og;
+    b->keep_alive[(size_t)q] = count;
+    b->route_rows = -1;  // the rows of an earlier routes call belong to another view
+    *n_alive = count;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
+    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree: NULL");
+    return keep_tree("rrt_batch_keep_tree", b, q, n_alive, alive);
+}
+
+extern "C" int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_keep_tree: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_keep_tree: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
+    return keep_tree("rrt_plan_keep_tree", ctx->single, 0, n_alive, alive);
+}
+
+extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree_ms: NULL");
+    if (!b->keep_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_keep_tree_ms: no rrt_batch_keep_tree on this batch yet, or its last one failed");
+    for (int k = 0; k < 3; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_keep[k], b->ev_keep[k + 1]));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_keep_tree_ms: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_keep_tree_ms: no rrt_plan on this context yet, or its batch is gone");
+    return rrt_batch_keep_tree_ms(ctx->single, ms);
+}
+
+extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
+    if (!ctx || !j) return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: NULL");
+    rrt_batch *s = ctx->single;
+    if (!s || (s->h_desc[0].status != ST_DONE && s->h_desc[0].status != ST_UNREACHABLE))
+        return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
+    *j = s->h_desc[0].j;
+    return RRT_OK;
 }
 
 // ---- finished routes to many goals (rrt_routes.h) ----

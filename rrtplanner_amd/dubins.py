@@ -189,6 +189,13 @@ class _DubinsBase(RRT):
     def routes_to(self, goals, shortcut=False):
         return self.connect_goals(goals)
 
+    def keep_tree(self, og_new):
+        raise ValueError("keep_tree: a Dubins planner's edge is a Dubins word between poses; the edge test walks straight lines "
+                         "(RRTStandard, RRTStar, RRTStarInformed only)")
+
+    def keep_tree_resident(self, grids, k=0):
+        return self.keep_tree(None)
+
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""
         legs = []

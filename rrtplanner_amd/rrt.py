@@ -591,6 +591,53 @@ class RRT(object):
         self._grid_dirty = False
         self._tree_resident = None
 
+    def _keep_guard(self, who: str, shape):
+        if self._tree_resident is None:
+            raise RuntimeError(f"{who}: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        if self._tree_resident == "host":
+            raise ValueError(f"{who}: the last plan() ran on the host route (a custom cost function has no device cost; a grid or n beyond "
+                             "the kernels' range is not planned on the device), so its tree is not resident on the device")
+        if tuple(shape) != tuple(np.asarray(self.og).shape):
+            raise ValueError(f"{who}: the new grid is {tuple(shape)}, the tree was planned on {tuple(np.asarray(self.og).shape)}")
+
+    def keep_tree(self, og_new: np.ndarray) -> np.ndarray:
+        """The map changed: keep the tree of the last plan() instead of planning again (rrt_plan_keep_tree).  Like set_og(og_new)
+        -- og, free, the upload; a later plan() plans on og_new -- except that the tree stays on the device.  Returns alive bool[j]:
+        the vertices whose every edge on the way to the root is free on og_new, each edge walked from the parent to the child
+        (collisionfree(og_new, points[parent[k]], points[k])); the root's cell must be free.  From here on connect_goals, paths_to
+        and routes_to take their lines of sight on og_new and consider only the alive vertices; the vertex numbers they return are
+        those of the T plan() returned, and no cost changes.  No vertex alive: every goal answers -1 / inf.  Not cumulative: every
+        call starts from the whole tree, so keeping it for the first map again restores every vertex.
+
+        On a tree of RRTStar(rewire="correct") an edge may be cut even on an unchanged map: its rewire tested the edge from the
+        child's side, and the line walk is not symmetric.
+
+        ValueError if og_new has another shape than the grid of the last plan(); RuntimeError / ValueError as connect_goals."""
+        og_new = np.asarray(og_new)
+        self._keep_guard("keep_tree", og_new.shape)
+        self._tree_resident = None  # (until the call below has succeeded: a failure leaves no tree for this grid)
+        self.og = og_new
+        self.free = np.argwhere(og_new == 0)
+        self._grid_dirty = True
+        alive = self._device().keep_tree()
+        self._tree_resident = "device"
+        return alive
+
+    def keep_tree_resident(self, grids, k: int = 0) -> np.ndarray:
+        """keep_tree(grids.host[k]) for grids generated on this planner's device (oggen.DeviceGrids): frame k becomes the active
+        grid without an upload, and the tree of the last plan() is kept on it.  Raises like keep_tree and set_og_resident."""
+        if self._ctx is None or grids.ctx is not self._ctx:
+            raise ValueError("grids were generated on a different device context: use oggen.DeviceGrids(planner.device_context(), ...)")
+        self._keep_guard("keep_tree_resident", grids.host[k].shape)
+        grids.select(k)  # checks the context's grid generation; when it raises nothing has changed and the tree stays
+        self._tree_resident = None  # (until the call below has succeeded: a failure leaves no tree for this grid)
+        self.og = grids.host[k]
+        self.free = np.argwhere(self.og == 0)
+        self._grid_dirty = False
+        alive = self._ctx.keep_tree()
+        self._tree_resident = "device"
+        return alive
+
     def device_context(self) -> "_ffi.Context":
         """The planner's device context (created on demand, without uploading a grid)."""
         if self._ctx is None:
