@@ -244,6 +244,35 @@ int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *aliv
 /* kernel time in ms of the three stages of the last successful rrt_batch_keep_tree on this batch, from events on the stream:
  * edge test, pointer jumping, compaction.  RRT_E_ARG when there is none (or its tree had no vertex). */
 int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]);
+/* Grow the finished tree of query q with m more samples (rrt_seed.h): seed + arm, then rrt_batch_launch / rrt_batch_sync /
+ * rrt_batch_get_result as after rrt_batch_set_query.  RRTStandard and RRTStar, the default cost, the reference's rewire.
+ *   seed   the alive vertices of the query's view (rrt_batch_keep_tree), in their original order, become vertices 0 .. *j0-1 of a new
+ *          tree; without a view the whole tree [0, j), *j0 = j.  Points and costs are copied bit for bit, parents renumbered (the
+ *          root keeps -1).  old_id (host, *j0 int32, may be NULL; give it room for the query's n) = the original number of each.
+ *   sampled = the cells of the seed vertices 1 .. *j0-1 and nothing else: xstart is never in it (rrt.py:407-413), the cell of a
+ *          vertex that was cut can be sampled again; with nothing cut it is the set the query's own run left.
+ *   loop   m iterations of rrt.py:418-437 / :498-548 on the context's CURRENT grid with j starting at *j0, samples_xy (host, (m, 2)
+ *          int32) their samples; lowest index among equal distances, stable (cost, index) order.  j0 + m <= n (the query's own n)
+ *          is required, so the capacity rule j != n never binds.
+ *   goal   go2goal to the query's xgoal on the current grid, both fall-backs of the reference included (against the query's n).
+ * Afterwards the batch holds an ordinary finished query of n samples on the current grid, in the new numbering and with no view:
+ * rrt_batch_get_result (rows follow n; status, j, vgoal, found of the grown tree; the statistics count the m iterations alone),
+ * the goals and routes calls, rrt_batch_keep_tree and a further rrt_batch_grow all work on it.  *log0 = the log row of the first of
+ * the m iterations (RRT_FLAG_LOGS): rows [*log0, *log0 + m) hold the grow, the rows below it are those of earlier runs.  The m samples
+ * replace rows [*j0, *j0 + m) of the query's sample buffer: an rrt_batch_rearm replays the buffer as it then stands.
+ * The launch is an ordinary one: it drops the views of ALL queries of the batch, so the other queries that had one are refused by
+ * the goals calls until they are kept again; finished queries are not run again, their results stay.  m == 0: the seed, then go2goal.
+ * The call itself is synchronous on the context's stream.  RRT_E_ARG: NULL (b, j0, log0, or samples_xy with m > 0); q out of
+ * range; a query that has not finished; m < 0 or *j0 + m > n; a sample outside the grid; a view without an alive vertex (the root is
+ * blocked); a context grid of another shape, or one replaced since the query ran without an rrt_batch_keep_tree for it (the
+ * validation of rrt_batch_connect_goals).  RRT_E_UNSUPPORTED: an Informed query; a batch created with RRT_FLAG_DUBINS,
+ * RRT_FLAG_REWIRE or RRT_FLAG_LARGE_GRID.  Such a refusal changes nothing.  A call that fails later (an allocation, a device
+ * error) leaves the query without a tree (as before any rrt_batch_set_query). */
+int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
+/* kernel time in ms of the seed's stages of the last successful rrt_batch_grow on this batch, from events on the stream: ms[0]
+ * renumbering and node slots, ms[1] the `sampled` bitmap, ms[2] the cell records; the first `count` (1 .. 3) are written.
+ * RRT_E_ARG when there is none. */
+int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -294,6 +323,11 @@ int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]);
 /* *j = vertices of the finished tree of the context's last rrt_plan / rrt_plan_resume: the bytes rrt_plan_keep_tree writes into
  * `alive`.  RRT_E_ARG: NULL; no finished rrt_plan on this context. */
 int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j);
+/* rrt_batch_grow on the tree of the context's last rrt_plan / rrt_plan_resume, launch, sync and result included: returns like
+ * rrt_plan (out as rrt_plan fills it, for the query's n).  rrt_plan_grow_ms: rrt_batch_grow_ms of that batch -- the companion
+ * rrt_plan_keep_tree_ms is to rrt_plan_keep_tree: a caller of rrt_plan holds no rrt_batch to ask (RRT.grow, tools/grow_wall.py). */
+int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
+int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

@@ -73,6 +73,7 @@ SYMBOLS = (
     "rrt_batch_connect_goals", "rrt_plan_connect_goals",
     "rrt_batch_routes", "rrt_batch_routes_rows", "rrt_plan_routes", "rrt_plan_routes_rows",
     "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
+    "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
 )
 
 
@@ -178,6 +179,10 @@ def lib():
             "rrt_plan_keep_tree": ([vp, C.POINTER(i32), vp], C.c_int),
             "rrt_plan_keep_tree_ms": ([vp, C.POINTER(C.c_float * 3)], C.c_int),
             "rrt_plan_tree_size": ([vp, C.POINTER(i32)], C.c_int),
+            "rrt_batch_grow": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
+            "rrt_batch_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
+            "rrt_plan_grow": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
+            "rrt_plan_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -247,6 +252,15 @@ def _keep_tree(handle, call, size, j):
     if int(alive.sum()) != n_alive.value:
         raise RRTError(RRT_E_HIP, f"keep_tree: {n_alive.value} vertices alive, {int(alive.sum())} flags set")
     return alive
+
+
+def _grow_samples(samples):
+    """the samples of a grow call as contiguous int32 (m, 2); packed uint32 samples (x | y << 16) are unpacked"""
+    s = np.asarray(samples)
+    if s.dtype == np.uint32 and s.ndim == 1:
+        s = np.stack([s & 0xFFFF, s >> 16], axis=1)
+    s = np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 2)
+    return s
 
 
 class ResultArrays:
@@ -447,6 +461,27 @@ class Context:
         """kernel time in ms of the last keep_tree(): (edge test, pointer jumping, compaction)"""
         ms = (C.c_float * 3)()
         _check(self._h, lib().rrt_plan_keep_tree_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def grow(self, samples, n, logs=False):
+        """rrt_plan_grow: Batch.grow on the tree of this context's last plan() / plan_resume(), launch and result included.  n: the
+        n of that plan (the result arrays are sized by it).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
+        s = _grow_samples(samples)
+        res = ResultArrays(int(n), logs)
+        j0 = C.c_int32(-1)
+        old_id = np.full(int(n) + 1, -1, dtype=np.int32)
+        rc = lib().rrt_plan_grow(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+        try:
+            _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
+        except RRTError as e:
+            e.seeded = j0.value >= 0  # False: the call refused before the seed and changed nothing
+            raise
+        return rc, res, j0.value, old_id[:j0.value].copy()
+
+    def grow_ms(self):
+        """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
+        ms = (C.c_float * 3)()
+        _check(self._h, lib().rrt_plan_grow_ms(self._h, C.byref(ms), 3))
         return tuple(ms)
 
     def plan_batch(self, queries, ns):
@@ -655,6 +690,23 @@ class Batch:
         """kernel time in ms of the last keep_tree(): (edge test, pointer jumping, compaction)"""
         ms = (C.c_float * 3)()
         _check(self.ctx.handle, lib().rrt_batch_keep_tree_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def grow(self, q, samples):
+        """rrt_batch_grow: seed query q from its finished tree (the alive vertices of its keep_tree view, else the whole tree) and arm
+        it for len(samples) more iterations on the context's current grid; then launch() / sync() / get_result(q) as after set_query.
+        Returns (j0, old_id int32[j0], log0): the seed's vertices, the original number of each, the log row of the first new
+        iteration."""
+        s = _grow_samples(samples)
+        j0, log0 = C.c_int32(-1), C.c_int32(-1)
+        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_grow(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
+        return j0.value, old_id[:j0.value].copy(), log0.value
+
+    def grow_ms(self):
+        """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
+        ms = (C.c_float * 3)()
+        _check(self.ctx.handle, lib().rrt_batch_grow_ms(self._h, C.byref(ms), 3))
         return tuple(ms)
 
     def routes_rows(self, rows):

@@ -37,6 +37,10 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #elif RRT_TU == 7  // keep a finished tree when the map changes: the view of its alive vertices (rrt_keep_*_kernel): not a team kernel
 #include "rrt_keep.h"
 
+#elif RRT_TU == 8  // grow a finished tree: its loop state rebuilt from the alive vertices (rrt_seed_*_kernel): not a team kernel
+#define RRT_SERIAL_DECL_ONLY
+#include "rrt_seed.h"
+
 #else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_block.h"

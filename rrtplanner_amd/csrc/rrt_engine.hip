@@ -30,6 +30,8 @@
 #include "rrt_routes.h"
 #define RRT_KEEP_DECL_ONLY
 #include "rrt_keep.h"
+#define RRT_SEED_DECL_ONLY
+#include "rrt_seed.h"
 #include "rrt_prims.h"
 
 using namespace rrtdev;
@@ -215,6 +217,11 @@ struct rrt_batch {
     unsigned char *d_keep_tmp = nullptr;    // [anc i32 x 2 | ok u8 x 2 | count i32 at the end], each array of n_cap (rounded up to 8 bytes)
     hipEvent_t ev_keep[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_keep_tree
     bool keep_timed = false;
+    // rrt_batch_grow: a query armed as a loop stopped mid-way runs with D->n = j0 + m (rrt_seed.h)
+    std::vector<int32_t> grow_n;            // [Q] the query's own n while it is armed so; -1 otherwise (rrt_batch_sync puts it back)
+    unsigned char *d_seed_tmp = nullptr;    // [rank i32 | new_parent i32 | err i32], the arrays of n_cap
+    hipEvent_t ev_seed[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_grow
+    bool seed_timed = false;
 };
 
 // no query of the batch has a view any more (a launch, a rearm), or only query q (a new query in its place, a keep_tree that starts
@@ -567,12 +574,14 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows, b->d_keep_tmp};
+                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows, b->d_keep_tmp, b->d_seed_tmp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (unsigned char *p : b->d_keep)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : b->ev_keep)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : b->ev_seed)
         if (e) (void)hipEventDestroy(e);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
@@ -709,6 +718,7 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     b->ran_og.assign((size_t)Q, nullptr);
     b->d_keep.assign((size_t)Q, nullptr);
     b->keep_alive.assign((size_t)Q, -1);
+    b->grow_n.assign((size_t)Q, -1);
     const size_t q = (size_t)Q;
 #define ALLOC(ptr, bytes)                                   \
     do {                                                    \
@@ -825,6 +835,7 @@ extern "C" int rrt_batch_set_query(rrt_batch *b, int32_t q, const rrt_query *qu)
     }
     QDesc &d = b->h_desc[(size_t)q];
     drop_keep_views(b, q);  // from here on the query is replaced; a call refused above leaves it, and its view, as they were
+    b->grow_n[(size_t)q] = -1;
     d = QDesc{};
     d.alg = qu->alg;
     d.n = qu->n;
@@ -886,8 +897,12 @@ extern "C" int rrt_batch_rearm(rrt_batch *b) {
     b->route_rows = -1;
     drop_keep_views(b);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (auto &d : b->h_desc)
+    for (int q = 0; q < b->Q; ++q) {
+        QDesc &d = b->h_desc[(size_t)q];
+        if (b->grow_n[(size_t)q] >= 0) d.n = b->grow_n[(size_t)q];  // (a grow that was armed and never launched: the query's own n again)
+        b->grow_n[(size_t)q] = -1;
         if (d.status != ST_IDLE) arm_desc(d);
+    }
     HIPCHK(ctx, hipMemcpyAsync(b->d_desc, b->h_desc.data(), (size_t)b->Q * sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
     return RRT_OK;
 }
@@ -1174,6 +1189,21 @@ extern "C" int rrt_batch_sync(rrt_batch *b) {
         cu_release(ctx->device, b->claimed_cus);
         b->claimed_cus = 0;
     }
+    // A query that ran as a grow (rrt_batch_grow) ran with n = j0 + m: from here on it is a finished query of its own n again, on the
+    // host and on the device.  go2goal's second fall-back goes by that n: no vertex sees the goal and rows are left -> rrt.py:318 faults.
+    bool regrown = false;
+    for (int q = 0; q < b->Q; ++q) {
+        QDesc &d = b->h_desc[(size_t)q];
+        const int32_t own_n = b->grow_n[(size_t)q];
+        if (own_n < 0 || d.status == ST_RUNNING) continue;  // (RUNNING: armed and not launched yet)
+        b->grow_n[(size_t)q] = -1;
+        d.n = own_n;
+        d.i_switch = own_n;
+        if (d.status == ST_DONE && !d.found && d.j < own_n) d.status = ST_UNREACHABLE;
+        HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+        regrown = true;
+    }
+    if (regrown) HIPCHK(ctx, wait_stream_spin(ctx->stream));
     return RRT_OK;
 }
 
@@ -1526,6 +1556,155 @@ extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
     if (!s || (s->h_desc[0].status != ST_DONE && s->h_desc[0].status != ST_UNREACHABLE))
         return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
     *j = s->h_desc[0].j;
+    return RRT_OK;
+}
+
+
+// ---- grow a finished tree with new samples (rrt_seed.h) ----
+// The seed kernels turn the finished tree of query q -- the view of its alive vertices, if it was kept on a new map -- into the loop
+// state the expansion kernels resume from, and the descriptor is armed as a loop that stopped at iteration j0 of j0 + m:
+//     D->n = j0 + m,  D->i = D->j = j0,  status RUNNING,  statistics zero,  the m samples at rows [j0, j0 + m) of the sample buffer.
+// i != 0 keeps rrt_init_kernel away; every expansion kernel reads (i, j) from the descriptor and samples[i] by absolute row, and
+// none of them depends on i == 0 or on i being a multiple of its block ("Growing a finished tree").  rrt_batch_sync puts
+// the query's own n back (grow_n).  A refusal changes nothing; past the refusals a failure leaves the query idle.
+static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0) {
+    rrt_ctx *ctx = b->ctx;
+    if (!j0_out || !log0 || (m > 0 && !samples_xy)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (the seed kernels carry no headings)", who);
+    if (b->flags & RRT_FLAG_REWIRE)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_REWIRE (its kernel keeps child lists, which the seed does not rebuild)", who);
+    if (b->flags & RRT_FLAG_LARGE_GRID)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_LARGE_GRID", who);
+    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
+    QDesc &d = b->h_desc[(size_t)q];
+    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
+        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
+                    d.status == ST_IDLE      ? "no query set"
+                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
+                    : d.status == ST_NEED_UB ? "it waits for its unit-ball stream"
+                                             : "its launch failed");
+    if (d.alg == RRT_ALG_INFORMED)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d is an Informed RRT* query (its ellipse state is not rebuilt); RRTStandard and RRTStar only", who, q);
+    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid changed shape since the batch was created (%dx%d)", who, b->gridW, b->gridH);
+    if (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now) and the tree was not kept "
+                    "on it (rrt_batch_keep_tree)", who, q, (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen);
+    if (m < 0) return fail(ctx, RRT_E_ARG, "%s: m=%d", who, m);
+    const int32_t kept = b->keep_alive[(size_t)q];
+    const int j_old = d.j, own_n = d.n;
+    if (j_old < 1 || j_old > b->n_cap || own_n < 1 || own_n > b->n_cap)
+        return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices of %d, capacity %d", who, q, j_old, own_n, b->n_cap);
+    if (kept == 0) return fail(ctx, RRT_E_ARG, "%s: no vertex of query %d is alive on this grid (the root is blocked): there is nothing to grow from", who, q);
+    const int j0 = kept > 0 ? (kept <= j_old ? kept : j_old) : j_old;
+    if ((long long)j0 + m > own_n)
+        return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j0, m, own_n, own_n - j0);
+    const int W = ctx->W, H = ctx->H;
+    for (int k = 0; k < m; ++k) {
+        const int x = samples_xy[2 * k], y = samples_xy[2 * k + 1];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: sample %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+    }
+    b->stage.resize((size_t)m);  // (past the last refusal: the staging buffer is the first thing of the batch this call touches)
+    for (int k = 0; k < m; ++k)
+        b->stage[(size_t)k] = ((uint32_t)samples_xy[2 * k] & 0xffffu) | ((uint32_t)samples_xy[2 * k + 1] << 16);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t cap = (size_t)b->n_cap;
+    if (!b->d_seed_tmp) HIPCHK(ctx, hipMalloc((void **)&b->d_seed_tmp, (2 * cap + 2) * sizeof(int32_t)));
+    for (hipEvent_t &e : b->ev_seed)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    // ---- from here on the query is being replaced ----
+    b->seed_timed = false;
+    b->route_rows = -1;
+    d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
+    SeedView sv{};
+    sv.nodes = b->d_nodes + (size_t)q * b->node_stride;
+    sv.vcost = b->d_vcost + (size_t)q * b->node_stride;
+    sv.parent = b->d_parent + (size_t)q * b->node_stride;
+    sv.j_old = j_old;
+    sv.j0 = j0;
+    sv.node_stride = b->node_stride;
+    sv.rank = reinterpret_cast<int32_t *>(b->d_seed_tmp);
+    sv.new_parent = sv.rank + cap;
+    sv.err = sv.rank + 2 * cap;
+    sv.bitmap = b->d_bitmap + (size_t)q * b->bitmap_words;
+    sv.bitmap_words = b->bitmap_words;
+    sv.H = H;
+    if (kept > 0) {
+        sv.live_vcost = reinterpret_cast<const double *>(b->d_keep[(size_t)q]);
+        sv.live_nodes = reinterpret_cast<const uint32_t *>(sv.live_vcost + b->n_cap);
+        sv.live_id = reinterpret_cast<const int32_t *>(sv.live_nodes + b->n_cap);
+    }
+    auto blocks = [](int items) { return dim3((unsigned)((items + SEED_TPB - 1) / SEED_TPB)); };
+    HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[0], ctx->stream));
+    if (sv.live_id) {
+        HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)j_old * sizeof(int32_t), ctx->stream));
+        hipLaunchKernelGGL(rrt_seed_rank_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
+        hipLaunchKernelGGL(rrt_seed_parent_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
+    }
+    hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[1], ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
+    if (j0 > 1) hipLaunchKernelGGL(rrt_seed_bitmap_kernel, blocks(j0 - 1), dim3(SEED_TPB), 0, ctx->stream, sv);
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[2], ctx->stream));
+    if (b->d_cellcnt) {  // (a batch without cell records, RRT_FLAG_SERIAL: its kernel scans the node array)
+        SeedRecords sr{};
+        sr.nodes = sv.nodes;
+        sr.vcost = sv.vcost;
+        sr.j0 = j0;
+        sr.cshift = d.cell_shift;
+        sr.ncx = d.ncx;
+        sr.ncy = d.ncy;
+        sr.ccap = d.cell_cap;
+        sr.rec_stride = b->rec_stride;
+        sr.cellrec = reinterpret_cast<u32x4 *>(b->d_cellrec) + (size_t)q * (size_t)b->rec_stride;
+        sr.cellcnt = b->d_cellcnt + (size_t)q * (size_t)MAX_CELLS;
+        sr.err = sv.err;
+        hipLaunchKernelGGL(rrt_seed_records_kernel, dim3(SEED_WG), dim3(SEED_TPB), 0, ctx->stream, sr);
+    }
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[3], ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    if (old_id) {
+        if (sv.live_id) HIPCHK(ctx, hipMemcpyAsync(old_id, sv.live_id, (size_t)j0 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        else
+            for (int k = 0; k < j0; ++k) old_id[k] = k;
+    }
+    if (m > 0)
+        HIPCHK(ctx, hipMemcpyAsync(b->d_samples + (size_t)q * b->n_cap + j0, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    drop_keep_views(b, q);  // the view is used up: the tree arrays hold its vertices now
+    if (err) {
+        HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        return fail(ctx, RRT_E_HIP, "%s: the tree of query %d on the device is not one the seed can place (a parent that is not alive, a vertex outside the "
+                    "record grid or a cell past its capacity): the query is left without a tree", who, q);
+    }
+    arm_desc(d);
+    d.n = j0 + m;
+    d.i = d.j = j0;
+    d.i_switch = own_n;
+    b->grow_n[(size_t)q] = own_n;
+    HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    b->seed_timed = true;
+    *j0_out = j0;
+    *log0 = j0;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
+    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
+    return batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0);
+}
+
+extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
+    if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
+    if (!b->seed_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
+    for (int k = 0; k < count; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_seed[k], b->ev_seed[k + 1]));
     return RRT_OK;
 }
 
@@ -1916,6 +2095,21 @@ extern "C" int rrt_plan_resume(rrt_ctx *ctx, const double *unitball, int32_t cou
     int rc = rrt_batch_set_unitball(s, 0, unitball, count, s->h_desc[0].i);
     if (rc != RRT_OK) return rc;
     return run_single(ctx, out);
+}
+
+extern "C" int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    if (!ctx || !out) return fail(ctx, RRT_E_ARG, "rrt_plan_grow: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_grow: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
+    int32_t log0 = 0;
+    const int rc = batch_grow("rrt_plan_grow", ctx->single, 0, samples_xy, m, j0, old_id, &log0);
+    if (rc != RRT_OK) return rc;
+    return run_single(ctx, out);
+}
+
+extern "C" int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_grow_ms: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_grow_ms: no rrt_plan on this context yet, or its batch is gone");
+    return rrt_batch_grow_ms(ctx->single, ms, count);
 }
 
 extern "C" int rrt_plan_batch(rrt_ctx *ctx, int32_t Q, const rrt_query *queries, rrt_result *out) {

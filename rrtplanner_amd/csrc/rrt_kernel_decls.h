@@ -1,7 +1,7 @@
 // rrt_kernel_decls.h -- the expansion kernels that are plain (non-template) functions, declared for the translation unit that
 // launches them (rrt_engine.hip).  Definitions: rrt_pipe.h and rrt_dubins_block.h, compiled by kernels_tu.hip.
-// (The kernels of rrt_goals.h, rrt_routes.h and rrt_keep.h come with their view structs: the engine includes those headers in their
-// RRT_GOALS_DECL_ONLY / RRT_ROUTES_DECL_ONLY / RRT_KEEP_DECL_ONLY form, units 5, 6 and 7 of kernels_tu.hip define them.)
+// (The kernels of rrt_goals.h, rrt_routes.h, rrt_keep.h and rrt_seed.h come with their view structs: the engine includes those headers in
+// their RRT_GOALS_DECL_ONLY / RRT_ROUTES_DECL_ONLY / RRT_KEEP_DECL_ONLY / RRT_SEED_DECL_ONLY form, units 5 to 8 of kernels_tu.hip define them.)
 #pragma once
 
 #include "rrt_kernels.h"

@@ -478,6 +478,7 @@ class RRT(object):
     """Base class: holds the grid, the sample budget and the RNG (reference rrt.py:50-86)."""
 
     _ALG = None
+    _GROWS = False  # does grow() take this class's trees?  (RRTStandard and RRTStar)
 
     def __init__(self, og: np.ndarray, n: int, costfn: callable = None, pbar: bool = True, seed: int = 0):
         self.pbar = pbar
@@ -621,6 +622,7 @@ class RRT(object):
         self._grid_dirty = True
         alive = self._device().keep_tree()
         self._tree_resident = "device"
+        self._grow_j0 = int(alive.sum())
         return alive
 
     def keep_tree_resident(self, grids, k: int = 0) -> np.ndarray:
@@ -636,7 +638,71 @@ class RRT(object):
         self._grid_dirty = False
         alive = self._ctx.keep_tree()
         self._tree_resident = "device"
+        self._grow_j0 = int(alive.sum())
         return alive
+
+    def grow(self, m: int) -> Tuple[nx.DiGraph, int]:
+        """Spend m more samples on the tree of the last plan() (rrt_plan_grow): after keep_tree the region behind a new obstacle has
+        no vertices and its goals answer -1 / inf; grow puts vertices there again without planning from scratch.  RRT* is an anytime
+        algorithm: the same call refines an uncut tree.
+
+        The alive vertices (all of them without a keep_tree) become vertices 0 .. j0-1 of a new tree, in their original order and
+        with their costs unchanged; `sampled` is the set of their cells without xstart's, so the cell of a cut vertex can be drawn
+        again; then m iterations of plan()'s loop run on the current grid with m samples drawn from self.free exactly as plan()
+        draws its n, and go2goal connects plan()'s xgoal.  m must fit: j0 + m <= self.n.
+
+        Returns (T, gv) with the row contract of plan() for self.n.  self.last_grow_ids[k] is the number vertex k had in the tree
+        before the call; last_stats counts the m iterations.  connect_goals, routes_to, keep_tree and a further grow work on the
+        grown tree in its new numbering.
+
+        RuntimeError / ValueError as connect_goals; ValueError when m does not fit (it names the room), for RRTStarInformed, the
+        Dubins planners, rewire="correct", the large-grid route and a custom cost function."""
+        if not self._GROWS:
+            raise ValueError("grow: RRTStandard and RRTStar only (an Informed tree carries ellipse state, a Dubins tree headings, which the seed does not rebuild)")
+        if self._custom_cost:
+            raise ValueError("grow: a custom cost function runs on the host route: its tree is not resident on the device")
+        if _rewire_mode(getattr(self, "rewire", "reference")):
+            raise ValueError('grow: rewire="correct" keeps child lists on the device, which the seed does not rebuild')
+        if self.last_route == "kernel-large" or self._on_the_large_grid_kernel():
+            raise ValueError("grow: the large-grid route (grids beyond 2048 cells a side) is not grown")
+        self._keep_guard("grow", np.asarray(self.og).shape)
+        m = int(m)
+        if m < 0:
+            raise ValueError(f"grow: m={m}")
+        ctx = self._device()
+        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow(), or the alive ones of the last keep_tree
+        if j0 == 0:
+            raise ValueError("grow: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
+        if j0 + m > int(self.n):
+            raise ValueError(f"grow: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
+        if getattr(self, "_free_packed_of", None) is not self.free:
+            self._free_packed, self._free_packed_of = hostprep.pack_cells(self.free), self.free
+        samples = hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, m)
+        bar = tqdm(total=m) if self.pbar else None
+        try:
+            self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
+            try:
+                rc, res, j0, old_id = ctx.grow(samples, int(self.n))
+            except _ffi.RRTError as e:
+                if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
+                    self._tree_resident = "device"
+                raise
+            self._tree_resident = "device"
+            self.last_route = "kernel"
+            self.last_grow_ids = old_id
+            self._grow_j0 = int(res.j)
+            self.last_stats = {k: getattr(res, k) for k in ("j", "i_switch", "sum_j", "sum_cells_nn", "sum_near",
+                                                              "sum_cells_cand", "n_los_cand", "n_rewired", "n_propagated")}
+            if rc == _ffi.RRT_E_GOAL_UNREACHABLE:  # (as plan(): the grown tree is complete and resident all the same)
+                raise IndexError(f"index {INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")
+            res.xg = self._grow_xg
+            out = self._materialise(res)
+            if bar is not None:
+                bar.update(m)
+        finally:
+            if bar is not None:
+                bar.close()
+        return out
 
     def device_context(self) -> "_ffi.Context":
         """The planner's device context (created on demand, without uploading a grid)."""
@@ -704,6 +770,7 @@ class RRT(object):
             ub = hostprep.draw_unitball(self.rand_gen, n - i_sw)
             rc = ctx.plan_resume(ub, res)
         self._tree_resident = "device"  # (also when the plan's own goal is unreachable: the tree is complete)
+        self._grow_xg, self._grow_j0 = xg, int(res.j)  # (grow connects the same goal, also after a plan that did not reach it)
         if rc == _ffi.RRT_E_GOAL_UNREACHABLE:
             # rrt.py:317-318: the next argsort entry is an unfilled row -> og[INT64_MIN, ...]
             raise IndexError(f"index {INT64_MIN} is out of bounds for axis 0 with size {W}")
@@ -911,6 +978,7 @@ class RRTStandard(RRT):
     """Plain RRT: the parent of a new node is its nearest node (reference rrt.py:375-447)."""
 
     LARGE_GRID_KERNEL = True
+    _GROWS = True
 
     def __init__(self, og: np.ndarray, n: int, costfn: callable = None, pbar=True, seed: int = 0):
         super().__init__(og, n, costfn=costfn, pbar=pbar, seed=seed)
@@ -935,6 +1003,7 @@ class RRTStar(RRT):
     acceptance, choose-parent, go2goal, the returned graph) is unchanged."""
 
     LARGE_GRID_KERNEL = True
+    _GROWS = True
 
     def __init__(self, og: np.ndarray, n: int, r_rewire: float, costfn: callable = None, pbar=True, seed: int = 0, rewire: str = "reference"):
         super().__init__(og, n, costfn=costfn, pbar=pbar, seed=seed)
