@@ -260,6 +260,9 @@ int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]);
  * the goals and routes calls, rrt_batch_keep_tree and a further rrt_batch_grow all work on it.  *log0 = the log row of the first of
  * the m iterations (RRT_FLAG_LOGS): rows [*log0, *log0 + m) hold the grow, the rows below it are those of earlier runs.  The m samples
  * replace rows [*j0, *j0 + m) of the query's sample buffer: an rrt_batch_rearm replays the buffer as it then stands.
+ * The seed belongs to the grid of this call: rrt_batch_launch is refused with RRT_E_ARG, before anything is queued or dropped, while
+ * a query is armed so and the context's grid is another one (rrt_set_grid, even of the same cells: a new generation; rrt_select_frame
+ * to another frame); rrt_batch_rearm or an rrt_batch_set_query in its place lifts the refusal, the seeded frame selected again too.
  * The launch is an ordinary one: it drops the views of ALL queries of the batch, so the other queries that had one are refused by
  * the goals calls until they are kept again; finished queries are not run again, their results stay.  m == 0: the seed, then go2goal.
  * The call itself is synchronous on the context's stream.  RRT_E_ARG: NULL (b, j0, log0, or samples_xy with m > 0); q out of

@@ -219,6 +219,8 @@ struct rrt_batch {
     bool keep_timed = false;
     // rrt_batch_grow: a query armed as a loop stopped mid-way runs with D->n = j0 + m (rrt_seed.h)
     std::vector<int32_t> grow_n;            // [Q] the query's own n while it is armed so; -1 otherwise (rrt_batch_sync puts it back)
+    std::vector<uint64_t> grow_gen;         // [Q] while it is armed so: the grid generation the seed was built on (rrt_batch_launch asks for it)
+    std::vector<const uint8_t *> grow_og;   // [Q] ... and that grid
     unsigned char *d_seed_tmp = nullptr;    // [rank i32 | new_parent i32 | err i32], the arrays of n_cap
     hipEvent_t ev_seed[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_grow
     bool seed_timed = false;
@@ -719,6 +721,8 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     b->d_keep.assign((size_t)Q, nullptr);
     b->keep_alive.assign((size_t)Q, -1);
     b->grow_n.assign((size_t)Q, -1);
+    b->grow_gen.assign((size_t)Q, 0);
+    b->grow_og.assign((size_t)Q, nullptr);
     const size_t q = (size_t)Q;
 #define ALLOC(ptr, bytes)                                   \
     do {                                                    \
@@ -1077,6 +1081,14 @@ static int plan_launch(rrt_batch *b, LaunchPlan &p) {
 extern "C" int rrt_batch_launch(rrt_batch *b) {
     if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_launch: NULL");
     rrt_ctx *ctx = b->ctx;
+    // A query armed by rrt_batch_grow holds a seed whose edges were tested on the grid of that call, and this launch would stamp the
+    // current grid on the whole of it: refused before anything is queued or dropped.  rrt_batch_rearm and rrt_batch_set_query lift it.
+    for (int q = 0; q < b->Q; ++q)
+        if (b->grow_n[(size_t)q] >= 0 && b->h_desc[(size_t)q].status == ST_RUNNING &&
+            (b->grow_gen[(size_t)q] != ctx->grid_gen || b->grow_og[(size_t)q] != ctx->og))
+            return fail(ctx, RRT_E_ARG, "rrt_batch_launch: the context's grid was replaced since query %d was seeded by rrt_batch_grow (grid generation %llu then, "
+                        "%llu now): its seed belongs to the other grid (rrt_batch_rearm drops the grow)", q, (unsigned long long)b->grow_gen[(size_t)q],
+                        (unsigned long long)ctx->grid_gen);
     b->route_rows = -1;
     drop_keep_views(b);
     if (!ctx->og) return fail(ctx, RRT_E_NOGRID, "rrt_batch_launch: no grid");
@@ -1687,6 +1699,8 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     d.i = d.j = j0;
     d.i_switch = own_n;
     b->grow_n[(size_t)q] = own_n;
+    b->grow_gen[(size_t)q] = ctx->grid_gen;
+    b->grow_og[(size_t)q] = ctx->og;
     HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     b->seed_timed = true;
