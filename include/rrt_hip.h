@@ -192,6 +192,25 @@ int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out);
  * RRT_FLAG_DUBINS.  The first call allocates scratch on the batch (at most 512 slabs of n_cap words and 128 MiB, at least one slab),
  * freed with the batch. */
 int rrt_batch_connect_goals(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost);
+/* The same for a batch created with RRT_FLAG_DUBINS (rrt_pose_goals_kernel): connect m goal POSES to the tree that query q left on
+ * the device.  poses_xyh is host (m,3): cell and heading index, 0 <= h < the query's nh.  Per pose the decision the Dubins planners
+ * take for their own goal pose, over the vertices [0, j), with the rho and nh of query q:
+ *   c[k] = vcost[k] + the length of the shortest Dubins word from the pose of vertex k to the goal pose (include/rrt_dubins.h), the
+ *   vertices tried in stable (c, index) order, the first one whose sweep is free -- every sample k * DUB_DS of the word inside the
+ *   grid and on a free cell, the goal cell free -- wins:  vertex[g] = that vertex, cost[g] = its c[k]
+ * (for the query's own goal pose: parent[vgoal] and vcost[vgoal] of its result when found).  Nothing connects, or the goal on an
+ * obstacle cell: vertex[g] = -1, cost[g] = +inf; the fall-backs of plan() are not reproduced.  A query that ended with
+ * RRT_E_GOAL_UNREACHABLE is accepted: its tree is complete.
+ * Synchronous on the context's stream; the batch is left as it was.  m == 0: RRT_OK, nothing is launched.
+ * RRT_E_ARG: NULL; q out of range; m < 0 or m > 2^20; a cell outside the grid; a heading outside [0, nh) of query q; a query that
+ * has not finished; a context whose grid changed shape or was replaced since the query ran (the conditions of
+ * rrt_batch_connect_goals).  RRT_E_UNSUPPORTED: a batch created without RRT_FLAG_DUBINS (rrt_batch_connect_goals is its call).
+ * The first call allocates scratch on the batch (at most 512 slabs of n_cap words and 128 MiB, 25 bytes a goal), later calls grow
+ * it, the batch frees it. */
+int rrt_batch_connect_poses(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost);
+/* diagnostic: out[0] = Dubins words evaluated, out[1] = sweeps run, summed over the goals of the last successful
+ * rrt_batch_connect_poses on this batch (per-goal counters the kernel writes).  RRT_E_ARG when there is none. */
+int rrt_batch_connect_poses_counts(rrt_batch *b, int64_t out[2]);
 /* Finished routes from the start to m goals over the tree that query q left on the device, in one call and without leaving the
  * device until the answer is read back (rrt_routes.h); optionally shortened by greedy line-of-sight shortcuts.
  *   vertex[g], cost[g]: exactly what rrt_batch_connect_goals gives (the same kernel decides them).
@@ -317,6 +336,8 @@ int rrt_plan_resume(rrt_ctx *ctx, const double *unitball, int32_t count, rrt_res
 int rrt_plan_batch(rrt_ctx *ctx, int32_t Q, const rrt_query *queries, rrt_result *out);
 /* rrt_batch_connect_goals on the tree of the context's last rrt_plan / rrt_plan_resume (the batch behind them stays resident) */
 int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost);
+/* rrt_batch_connect_poses on the tree of the context's last rrt_plan of a Dubins query (the batch behind it stays resident) */
+int rrt_plan_connect_poses(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost);
 /* rrt_batch_routes / rrt_batch_routes_rows on the tree of the context's last rrt_plan / rrt_plan_resume */
 int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets);
 int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows);

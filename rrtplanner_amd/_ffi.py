@@ -74,6 +74,7 @@ SYMBOLS = (
     "rrt_batch_routes", "rrt_batch_routes_rows", "rrt_plan_routes", "rrt_plan_routes_rows",
     "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
     "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
+    "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
 )
 
 
@@ -183,6 +184,9 @@ def lib():
             "rrt_batch_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
             "rrt_plan_grow": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
             "rrt_plan_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
+            "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
+            "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
+            "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -222,6 +226,17 @@ def _goal_arrays(goals):
         g = g[np.newaxis, :]
     if g.ndim != 2 or g.shape[1] != 2:
         raise ValueError(f"goals must have shape (M, 2) or (2,), got {g.shape}")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    return g, np.full(g.shape[0], -1, dtype=np.int32), np.full(g.shape[0], np.inf, dtype=np.float64)
+
+
+def _pose_arrays(poses):
+    """(poses as contiguous int32 (M, 3), vertex int32[M], cost float64[M]) for the connect_poses calls; a single pose is M = 1"""
+    g = np.asarray(poses)
+    if g.ndim == 1 and g.shape == (3,):
+        g = g[np.newaxis, :]
+    if g.ndim != 2 or g.shape[1] != 3:
+        raise ValueError(f"poses must have shape (M, 3) or (3,), got {g.shape}")
     g = np.ascontiguousarray(g, dtype=np.int32)
     return g, np.full(g.shape[0], -1, dtype=np.int32), np.full(g.shape[0], np.inf, dtype=np.float64)
 
@@ -443,6 +458,12 @@ class Context:
         """rrt_plan_connect_goals: Batch.connect_goals on the tree of this context's last plan() / plan_resume()"""
         g, vertex, cost = _goal_arrays(goals)
         _check(self._h, lib().rrt_plan_connect_goals(self._h, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
+        return vertex, cost
+
+    def connect_poses(self, poses):
+        """rrt_plan_connect_poses: Batch.connect_poses on the Dubins tree of this context's last plan()"""
+        g, vertex, cost = _pose_arrays(poses)
+        _check(self._h, lib().rrt_plan_connect_poses(self._h, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
         return vertex, cost
 
     def routes(self, goals, shortcut=False):
@@ -667,6 +688,21 @@ class Batch:
         g, vertex, cost = _goal_arrays(goals)
         _check(self.ctx.handle, lib().rrt_batch_connect_goals(self._h, int(q), g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
         return vertex, cost
+
+    def connect_poses(self, q, poses):
+        """rrt_batch_connect_poses: connect the goal poses (M, 3) = (x, y, heading index) to the finished Dubins tree of query q in one
+        launch.  Returns (vertex int32[M], cost float64[M]): per pose the first vertex of [0, j), in stable (cost, index) order of
+        cost = vcost[k] + length of the Dubins word from vertex k's pose to it, whose sweep is free, and that cost; (-1, inf) where
+        no vertex connects."""
+        g, vertex, cost = _pose_arrays(poses)
+        _check(self.ctx.handle, lib().rrt_batch_connect_poses(self._h, int(q), g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
+        return vertex, cost
+
+    def connect_poses_counts(self):
+        """rrt_batch_connect_poses_counts: (words evaluated, sweeps run) summed over the goals of the last connect_poses"""
+        out = (C.c_int64 * 2)()
+        _check(self.ctx.handle, lib().rrt_batch_connect_poses_counts(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
 
     def routes(self, q, goals, shortcut=False):
         """rrt_batch_routes + rrt_batch_routes_rows: finished routes from the start to the goals (M, 2) over the tree of query q, built

@@ -41,6 +41,10 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_seed.h"
 
+#elif RRT_TU == 9  // many goal poses against a finished Dubins tree (rrt_pose_goals_kernel): not a team kernel
+#define RRT_SERIAL_DECL_ONLY
+#include "rrt_pose_goals.h"
+
 #else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
 #define RRT_SERIAL_DECL_ONLY
 #include "rrt_block.h"

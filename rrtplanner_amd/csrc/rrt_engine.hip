@@ -32,6 +32,8 @@
 #include "rrt_keep.h"
 #define RRT_SEED_DECL_ONLY
 #include "rrt_seed.h"
+#define RRT_POSES_DECL_ONLY
+#include "rrt_pose_goals.h"
 #include "rrt_prims.h"
 
 using namespace rrtdev;
@@ -205,6 +207,16 @@ struct rrt_batch {
     int32_t *d_goal_vertex = nullptr;    // [goal_cap]
     double *d_goal_cost = nullptr;       // [goal_cap]
     int32_t goal_cap = 0;
+    // rrt_batch_connect_poses (RRT_FLAG_DUBINS): scratch allocated at the first call, grown by later ones (rrt_pose_goals.h)
+    uint32_t *d_pose_order = nullptr;    // [pose_slabs][n_cap] the sorted vertex order, one slab per workgroup
+    int32_t pose_slabs = 0;
+    uint32_t *d_pose_xy = nullptr;       // [pose_cap] packed goal cells
+    uint8_t *d_pose_h = nullptr;         // [pose_cap] goal heading indices
+    int32_t *d_pose_vertex = nullptr;    // [pose_cap]
+    double *d_pose_cost = nullptr;       // [pose_cap]
+    uint32_t *d_pose_counts = nullptr;   // [pose_cap][2] words evaluated, sweeps run
+    int32_t pose_cap = 0;
+    int32_t pose_last_m = -1;            // goals of the last successful rrt_batch_connect_poses; -1: none
     // rrt_batch_routes: per-goal arrays and the rows of the routes, allocated at the first call, grown by later ones (rrt_routes.h)
     unsigned char *d_route_goal = nullptr;  // [length | raw_off | fin_off | cnt | kept | err] for route_goal_cap goals
     int32_t route_goal_cap = 0;
@@ -576,7 +588,8 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows, b->d_keep_tmp, b->d_seed_tmp};
+                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows, b->d_keep_tmp, b->d_seed_tmp,
+                    b->d_pose_order, b->d_pose_xy, b->d_pose_h, b->d_pose_vertex, b->d_pose_cost, b->d_pose_counts};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (unsigned char *p : b->d_keep)
@@ -1450,6 +1463,134 @@ extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int
     if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_goals: NULL");
     if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_goals: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
     return connect_goals("rrt_plan_connect_goals", ctx->single, 0, goals_xy, m, vertex, cost);
+}
+
+// ---- many goal poses against a finished Dubins tree (rrt_pose_goals.h) ----
+// The conditions are goals_decide's, for a batch created with RRT_FLAG_DUBINS; a goal is a pose (x, y, h), h < the query's nh.
+static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    if (!poses_xyh || !vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (!(b->flags & RRT_FLAG_DUBINS))
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use rrt_batch_connect_goals)", who);
+    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
+    if (m < 0 || m > POSES_MAX) return fail(ctx, RRT_E_ARG, "%s: m=%d, at most %d goal poses per call", who, m, POSES_MAX);
+    const QDesc &d = b->h_desc[(size_t)q];
+    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
+        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
+                    d.status == ST_IDLE      ? "no query set"
+                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
+                                             : "its launch failed");
+    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid changed shape since the batch was created (%dx%d)", who, b->gridW, b->gridH);
+    if (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now): the tree belongs to the "
+                    "other grid", who, q, (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen);
+    const int W = ctx->W, H = ctx->H;
+    if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
+    b->stage.resize((size_t)m);
+    b->stage8.resize((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        const int x = poses_xyh[3 * k], y = poses_xyh[3 * k + 1], h = poses_xyh[3 * k + 2];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+        if (h < 0 || h >= d.nh) return fail(ctx, RRT_E_ARG, "%s: goal %d has heading %d, query %d has headings [0, %d)", who, k, h, q, d.nh);
+        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
+        b->stage8[(size_t)k] = (uint8_t)h;
+    }
+    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    if (m == 0) {
+        b->pose_last_m = 0;
+        return RRT_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    b->pose_last_m = -1;  // (until this call has succeeded: the counters are being rewritten)
+    // one slab of n_cap words per workgroup, at most POSES_MAX_SLABS of them and POSES_SLAB_BUDGET bytes, never fewer than one
+    int slabs = (int)(POSES_SLAB_BUDGET / ((size_t)b->n_cap * sizeof(uint32_t)));
+    slabs = slabs > POSES_MAX_SLABS ? POSES_MAX_SLABS : (slabs < 1 ? 1 : slabs);
+    slabs = slabs > m ? m : slabs;
+    if (slabs > b->pose_slabs) {
+        if (b->d_pose_order) HIPCHK(ctx, hipFree(b->d_pose_order));
+        b->d_pose_order = nullptr;
+        b->pose_slabs = 0;
+        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_order, (size_t)slabs * (size_t)b->n_cap * sizeof(uint32_t)));
+        b->pose_slabs = slabs;
+    }
+    if (m > b->pose_cap) {
+        // each pointer freed and cleared on its own: a failure half way leaves no pointer that is freed twice or overwritten
+        b->pose_cap = 0;
+        if (b->d_pose_xy) HIPCHK(ctx, hipFree(b->d_pose_xy));
+        b->d_pose_xy = nullptr;
+        if (b->d_pose_h) HIPCHK(ctx, hipFree(b->d_pose_h));
+        b->d_pose_h = nullptr;
+        if (b->d_pose_vertex) HIPCHK(ctx, hipFree(b->d_pose_vertex));
+        b->d_pose_vertex = nullptr;
+        if (b->d_pose_cost) HIPCHK(ctx, hipFree(b->d_pose_cost));
+        b->d_pose_cost = nullptr;
+        if (b->d_pose_counts) HIPCHK(ctx, hipFree(b->d_pose_counts));
+        b->d_pose_counts = nullptr;
+        // (a malloc that fails leaves the earlier ones in place with pose_cap == 0: the next call frees them above)
+        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_xy, (size_t)m * sizeof(uint32_t)));
+        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_h, (size_t)m));
+        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_vertex, (size_t)m * sizeof(int32_t)));
+        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_cost, (size_t)m * sizeof(double)));
+        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_counts, (size_t)m * 2 * sizeof(uint32_t)));
+        b->pose_cap = m;
+    }
+    PoseGoalsView pv{};
+    pv.og = ctx->og;
+    pv.W = W;
+    pv.H = H;
+    pv.nodes = b->d_nodes + (size_t)q * b->node_stride;
+    pv.vcost = b->d_vcost + (size_t)q * b->node_stride;
+    pv.heading = b->d_heading + (size_t)q * b->node_stride;
+    pv.j = d.j;
+    pv.nh = d.nh;
+    pv.rho = d.rho;
+    pv.goals = b->d_pose_xy;
+    pv.goal_h = b->d_pose_h;
+    pv.m = m;
+    pv.slab_words = b->n_cap;
+    pv.order = b->d_pose_order;
+    pv.vertex = b->d_pose_vertex;
+    pv.cost = b->d_pose_cost;
+    pv.counts = b->d_pose_counts;
+    HIPCHK(ctx, hipMemcpyAsync(b->d_pose_xy, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b->d_pose_h, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_pose_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cost, b->d_pose_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (also: the staging buffers are reused)
+    b->pose_last_m = m;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_connect_poses(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_poses: NULL");
+    return connect_poses("rrt_batch_connect_poses", b, q, poses_xyh, m, vertex, cost);
+}
+
+extern "C" int rrt_plan_connect_poses(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_poses: NULL");
+    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_poses: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
+    return connect_poses("rrt_plan_connect_poses", ctx->single, 0, poses_xyh, m, vertex, cost);
+}
+
+extern "C" int rrt_batch_connect_poses_counts(rrt_batch *b, int64_t out[2]) {
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_poses_counts: NULL");
+    rrt_ctx *ctx = b->ctx;
+    if (b->pose_last_m < 0) return fail(ctx, RRT_E_ARG, "rrt_batch_connect_poses_counts: no rrt_batch_connect_poses on this batch yet, or its last one failed");
+    out[0] = out[1] = 0;
+    const size_t m = (size_t)b->pose_last_m;
+    if (m == 0) return RRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    b->stage.resize(2 * m);
+    HIPCHK(ctx, hipMemcpyAsync(b->stage.data(), b->d_pose_counts, 2 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    for (size_t k = 0; k < m; ++k) {
+        out[0] += (int64_t)b->stage[2 * k];
+        out[1] += (int64_t)b->stage[2 * k + 1];
+    }
+    return RRT_OK;
 }
 
 // ---- keep a finished tree when the map changes (rrt_keep.h) ----

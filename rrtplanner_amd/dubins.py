@@ -144,7 +144,9 @@ class _DubinsBase(RRT):
         alg = _ffi.ALG_DUBINS_STAR if self._STAR else _ffi.ALG_DUBINS
         query, keep = _ffi.make_query(alg, n, xs, xg, samples, r2_rewire=hostprep.radius_threshold(r_rewire) if r_rewire is not None else 0,
                                       headings=headings, rho=self.rho, nh=self.n_headings)
+        self._tree_resident = None
         rc, res = ctx.plan(query, n, logs=logs)
+        self._tree_resident = "device"  # (also when the plan's own goal is unreachable: the tree is complete)
         if rc == _ffi.RRT_E_GOAL_UNREACHABLE:
             raise IndexError(f"index {hostprep.INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")  # as rrt.py:317-318
         res.xs, res.xg = xs, xg
@@ -185,6 +187,89 @@ class _DubinsBase(RRT):
 
     def paths_to(self, T, goals):
         return self.connect_goals(goals)
+
+    def _pose_array(self, poses):
+        """goal poses as int64 (M, 3), validated on the host: integer cells inside the grid, headings in [0, n_headings) or -1"""
+        g = np.asarray(poses)
+        if g.ndim == 1 and g.shape == (3,):
+            g = g[np.newaxis, :]
+        if g.ndim != 2 or g.shape[1] != 3:
+            raise ValueError(f"poses must have shape (M, 3) or (3,), got {g.shape}")
+        if g.dtype.kind not in "iu":
+            gf = np.asarray(g, dtype=np.float64)
+            if not np.all(np.isfinite(gf)) or np.any(gf != np.floor(gf)):
+                raise ValueError("poses must be integer cells and heading indices")
+            g = gf
+        W, H = np.asarray(self.og).shape
+        out = (g[:, 0] < 0) | (g[:, 0] >= W) | (g[:, 1] < 0) | (g[:, 1] >= H)
+        if np.any(out):
+            k = int(np.flatnonzero(out)[0])
+            raise ValueError(f"pose {k} = {g[k].astype(np.int64).tolist()} lies outside the {W}x{H} occupancy grid")
+        bad = (g[:, 2] < -1) | (g[:, 2] >= self.n_headings)
+        if np.any(bad):
+            k = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"pose {k}: heading index must be an integer in [0, {self.n_headings}), or -1 for any heading")
+        return g.astype(np.int64)
+
+    def connect_poses(self, poses):
+        """Connect many goal poses to the tree of this planner's last plan(), in one device call (rrt_plan_connect_poses): the
+        vehicle's cost to further poses needs no second plan().
+
+        poses: (M, 3) integer (x, y, heading index), or one pose.  Returns (vertex int32[M], cost float64[M], heading int64[M]): per
+        pose what plan() decides for its own goal pose over the tree vertices [0, j): the first vertex, in stable (cost, index) order
+        of cost = vcosts[k] + length of the Dubins word from vertex k's pose to the goal pose, whose sweep is free, and that cost.
+        For plan()'s own xgoal this is the parent and the cost of its goal vertex.  Nothing connects (or the goal on an obstacle
+        cell): vertex -1, cost inf.  Heading -1 asks for any arrival heading: the (cost, heading)-smallest connected one of the
+        n_headings poses on that cell is returned, with its heading; -1 if none connects.
+
+        RuntimeError before any plan() and after set_og / set_og_resident / set_n until the next plan(); ValueError for a pose
+        outside the grid or a heading outside [0, n_headings) other than -1."""
+        g = self._pose_array(poses)
+        if self._tree_resident is None:
+            raise RuntimeError("connect_poses: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        nh = self.n_headings
+        anyh = g[:, 2] < 0
+        rows = np.where(anyh, nh, 1)
+        start = np.concatenate([[0], np.cumsum(rows)])
+        full = np.repeat(g, rows, axis=0)
+        for k in np.flatnonzero(anyh).tolist():
+            full[start[k]:start[k + 1], 2] = np.arange(nh)
+        v, c = self._device().connect_poses(full)
+        vertex, cost, heading = np.full(len(g), -1, dtype=np.int32), np.full(len(g), np.inf), g[:, 2].copy()
+        for k in range(len(g)):
+            vk, ck = v[start[k]:start[k + 1]], c[start[k]:start[k + 1]]
+            e = int(np.argmin(ck))  # (the first among equal costs: the smallest heading)
+            if vk[e] >= 0:
+                vertex[k], cost[k], heading[k] = vk[e], ck[e], full[start[k] + e, 2]
+        return vertex, cost, heading
+
+    def paths_to_poses(self, T, poses):
+        """Routes from xstart to many goal poses over the tree T of the last plan(): one connect_poses call, then per pose the (k, 3)
+        int64 array of poses (x, y, heading index) along the tree to the vertex the goal connects to, followed by the goal pose (with
+        the heading that was chosen, where -1 was asked); None where nothing connects.  (The parent walks run on the host.)"""
+        vertex, _, heading = self.connect_poses(poses)
+        g = self._pose_array(poses)
+        lazy_pts = T.lazy_points() if isinstance(T, TreeDiGraph) else None  # (a tree that was not materialised stays so)
+        heads = T.__dict__.get("_dub", (None,))[0]
+        out = []
+        for v, goal, h in zip(vertex.tolist(), g, heading.tolist()):
+            if v < 0:
+                out.append(None)
+                continue
+            path = self.route2gv(T, v)
+            if lazy_pts is not None and heads is not None:
+                rows = [(int(lazy_pts[u][0]), int(lazy_pts[u][1]), int(heads[u])) for u in path]
+            else:
+                rows = [(int(T.nodes[u]["pt"][0]), int(T.nodes[u]["pt"][1]), int(T.nodes[u]["heading"])) for u in path]
+            out.append(np.array(rows + [(int(goal[0]), int(goal[1]), int(h))], dtype=np.int64).reshape(-1, 3))
+        return out
+
+    def poses_polyline(self, route, ds: float = 0.5) -> np.ndarray:
+        """(M, 2) float polyline of the vehicle's path along a route of paths_to_poses: the Dubins word of every leg, a point every
+        `ds` cells of arc length."""
+        route = np.asarray(route)
+        legs = [dubins_polyline(a, b, self.rho, self.n_headings, ds) for a, b in zip(route[:-1], route[1:])]
+        return np.concatenate(legs) if legs else np.zeros((0, 2))
 
     def routes_to(self, goals, shortcut=False):
         return self.connect_goals(goals)

@@ -916,6 +916,10 @@ class RRT(object):
                              "the kernels' range is not planned on the device), so its tree is not resident on the device")
         return self._device().connect_goals(g)
 
+    def connect_poses(self, poses):
+        raise ValueError("connect_poses: a goal pose (x, y, heading) belongs to the Dubins planners (RRTDubins, RRTStarDubins); the goals of "
+                         "this planner are cells: use connect_goals")
+
     def paths_to(self, T: nx.DiGraph, goals) -> list:
         """Routes from xstart to many goals over the tree T of the last plan(): one connect_goals call, then per goal the (k, 2)
         array of points along the tree to the vertex the goal connects to, followed by the goal itself; None where no vertex

@@ -1,0 +1,272 @@
+"""GPU: many goal poses connected to a finished Dubins tree in one device call (rrt_pose_goals_kernel, rrt_batch_connect_poses /
+rrt_plan_connect_poses, RRTDubins / RRTStarDubins .connect_poses / .paths_to_poses).
+
+Every comparison is exact: vertices and costs with ==.  The check is poseref.py (the oracle's word and sweep, a stable argsort) on
+the workloads it defines, and for the planners' own goals plan() itself and oracle.dubins_plan."""
+import numpy as np
+import pytest
+
+import oracle
+import poseref
+from rrtplanner_amd import _ffi, hostprep
+from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
+
+pytestmark = pytest.mark.gpu
+
+MAX_WORKGROUPS = 512  # POSES_MAX_SLABS of rrt_pose_goals.h: the workgroups of one launch, each deciding goals g, g + 512, ...
+INF = np.inf
+
+
+def _query(w):
+    return _ffi.make_query(_ffi.ALG_DUBINS_STAR if w.star else _ffi.ALG_DUBINS, w.n, w.xs, w.xg, w.samples, r2_rewire=w.r2, headings=w.heads,
+                           rho=w.rho, nh=w.nh)
+
+
+def _run(ctx, w):
+    """workload w on a batch of its own, launched and synchronised, its tree the oracle's: (batch, result)"""
+    ctx.set_grid(w.og8)
+    b = _ffi.Batch(ctx, 1, w.n, dubins=True)
+    q, keep = _query(w)
+    b.set_query(0, q)
+    b.launch()
+    b.sync()
+    res = b.get_result(0)
+    assert res.status == w.status and res.j == w.j
+    assert np.array_equal(res.vcost[:w.j], w.ro.vcost[:w.j]) and np.array_equal(res.head[:w.j], w.ro.head[:w.j])
+    return b, res
+
+
+def _same(got, w, rows=slice(None)):
+    vertex, cost = got
+    assert vertex.dtype == np.int32 and cost.dtype == np.float64
+    assert np.array_equal(vertex, w.vertex[rows]), np.flatnonzero(vertex != w.vertex[rows])[:8]
+    assert np.array_equal(cost, w.cost[rows]), np.flatnonzero(cost != w.cost[rows])[:8]
+
+
+# ------------------------------------------------------------------------------------------------ against the restatement
+@pytest.mark.parametrize("name", sorted(poseref.SPECS))
+def test_workloads_against_the_restatement(gpu_ctx, name):
+    w = poseref.workload(name)
+    poseref.check_conditions(w)
+    b, res = _run(gpu_ctx, w)
+    _same(b.connect_poses(0, w.goals), w)
+    words, sweeps = b.connect_poses_counts()
+    swept = w.rank[w.vertex >= 0] + 1
+    free_unconnected = int(((w.vertex < 0) & (w.og8[w.goals[:, 0], w.goals[:, 1]] == 0)).sum())
+    assert swept.sum() + free_unconnected * w.j <= sweeps <= words
+    b.close()
+
+
+def test_more_goals_than_workgroups_and_scratch_that_grows(gpu_ctx):
+    """700 goals on at most 512 workgroups: every workgroup decides one or two, reusing its slab and its LDS tables; around it
+    calls of 5 goals: the scratch grows once and is reused"""
+    w = poseref.workload("E", 700 - 4)
+    assert len(w.goals) == 700 > MAX_WORKGROUPS
+    poseref.check_conditions(w)
+    b, res = _run(gpu_ctx, w)
+    _same(b.connect_poses(0, w.goals[:5]), w, slice(0, 5))
+    _same(b.connect_poses(0, w.goals), w)
+    _same(b.connect_poses(0, w.goals[-5:]), w, slice(695, 700))
+    v0, c0 = b.connect_poses(0, np.zeros((0, 3), dtype=np.int64))
+    assert v0.shape == c0.shape == (0,) and b.connect_poses_counts() == (0, 0)
+    b.close()
+
+
+def test_a_batch_of_three_queries_each_with_its_own_rho_headings_and_tree(gpu_ctx):
+    w = poseref.workload("A")
+    gpu_ctx.set_grid(w.og8)
+    free = np.argwhere(w.og8 == 0)
+    par = [(4.0, 16, 1, 900), (5.0, 8, 0, 500), (6.0, 32, 1, 1400)]  # rho, nh, star, n
+    b = _ffi.Batch(gpu_ctx, 3, 1400, dubins=True)
+    keeps, refs = [], []
+    for q, (rho, nh, star, n) in enumerate(par):
+        rng = np.random.default_rng(40 + q)
+        samples, heads = hostprep.draw_free_samples(rng, free, n), rng.integers(0, nh, n)
+        xs, xg, r2 = (w.xs[0], w.xs[1], q % nh), (w.xg[0], w.xg[1], (3 + q) % nh), hostprep.radius_threshold(20) if star else 0
+        qu, keep = _ffi.make_query(_ffi.ALG_DUBINS_STAR if star else _ffi.ALG_DUBINS, n, xs, xg, samples, r2_rewire=r2, headings=heads, rho=rho, nh=nh)
+        keeps.append(keep)
+        b.set_query(q, qu)
+        refs.append(oracle.dubins_plan(w.og8, n, star, xs, xg, samples, heads, r2_rewire=r2, rho=rho, nh=nh, logs=False)[1])
+    b.launch()
+    b.sync()
+    for q in (2, 0, 1):
+        rho, nh, star, n = par[q]
+        ro, res = refs[q], b.get_result(q)
+        assert res.j == ro.j > 50 and np.array_equal(res.vcost[:ro.j], ro.vcost[:ro.j])
+        goals = np.column_stack([free[np.random.default_rng(50).integers(0, len(free), 12)], np.random.default_rng(51).integers(0, 8, 12)])
+        goals = np.concatenate([goals, [(ro.pts[ro.j, 0], ro.pts[ro.j, 1], ro.head[ro.j])] if ro.found else np.zeros((0, 3), dtype=np.int64)])
+        rv, rc, rank = poseref.connect(w.og8, ro.pts, ro.head, ro.vcost, ro.j, goals, rho, nh)
+        vertex, cost = b.connect_poses(q, goals)
+        assert np.array_equal(vertex, rv) and np.array_equal(cost, rc) and (rv >= 0).sum() >= 6
+        if ro.found:
+            assert (vertex[-1], cost[-1]) == (ro.parent[ro.vgoal], ro.vcost[ro.vgoal])
+    b.close()
+
+
+# ------------------------------------------------------------------------------------------------ the counters
+def test_counts_of_single_goals(gpu_ctx):
+    w = poseref.workload("B")
+    b, res = _run(gpu_ctx, w)
+    with pytest.raises(_ffi.RRTError) as e:
+        b.connect_poses_counts()
+    assert e.value.code == _ffi.RRT_E_ARG
+    b.connect_poses(0, w.goals[w.i_obstacle])
+    assert b.connect_poses_counts() == (0, 0)  # a goal on an obstacle cell: decided without a word
+    unreachable = [g for g in range(len(w.goals)) if w.vertex[g] < 0 and w.og8[w.goals[g, 0], w.goals[g, 1]] == 0]
+    assert unreachable
+    v, c = b.connect_poses(0, w.goals[unreachable[0]])
+    assert (v[0], c[0]) == (-1, INF)
+    assert b.connect_poses_counts() == (w.j, w.j)  # nothing passes: every vertex is priced and swept
+    seen = 0
+    for g in np.flatnonzero(w.vertex >= 0)[:8].tolist():
+        _same(b.connect_poses(0, w.goals[g]), w, slice(g, g + 1))
+        words, sweeps = b.connect_poses_counts()
+        assert w.rank[g] + 1 <= sweeps <= w.j and sweeps <= words <= w.j, (g, w.rank[g], words, sweeps)
+        seen += w.rank[g] > 0
+    assert seen >= 2
+    b.close()
+
+
+# ------------------------------------------------------------------------------------------------ the planners
+@pytest.mark.parametrize("cls", [RRTStarDubins, RRTDubins])
+def test_planners_end_to_end(cls):
+    w = poseref.workload("A" if cls is RRTStarDubins else "D")
+    args = (w.og, w.n) + ((20,) if cls is RRTStarDubins else ()) + (w.rho,)
+    p = cls(*args, n_headings=w.nh, pbar=False, seed=SEEDS[w.name])
+    T, gv = p.plan(np.array(w.xs), np.array(w.xg))
+    j = p.last_stats["j"]
+    assert j == w.j and gv == j  # the planner draws the workload's stream: its tree is the oracle's, the goal row behind it
+    vertex, cost, heading = p.connect_poses(w.goals)
+    assert np.array_equal(vertex, w.vertex) and np.array_equal(cost, w.cost) and np.array_equal(heading, w.goals[:, 2])
+    (u,) = T.pred[gv]
+    assert vertex[w.i_own] == u and cost[w.i_own] == T.edges[u, gv]["cost"]
+    # any heading: against the restatement over all headings of the cell
+    cell = w.goals[0, :2]
+    v1, c1, h1 = p.connect_poses((cell[0], cell[1], -1))
+    assert (v1[0], c1[0], h1[0]) == poseref.any_heading(w.og8, w.ro.pts, w.ro.head, w.ro.vcost, w.j, cell, w.rho, w.nh)
+    # routes: tree edges from the root, then the goal
+    poses = np.concatenate([w.goals[:6], [(cell[0], cell[1], -1)], w.goals[w.i_obstacle:w.i_obstacle + 2]])
+    vertex, cost, heading = p.connect_poses(poses)
+    routes = p.paths_to_poses(T, poses)
+    assert [r is None for r in routes] == (vertex < 0).tolist() and routes[7] is None and sum(r is not None for r in routes) >= 4
+    for r, g, v, h in zip(routes, poses, vertex, heading):
+        if r is None:
+            continue
+        assert r.dtype == np.int64 and r.shape[1] == 3 and tuple(r[0]) == tuple(w.xs) and tuple(r[-1]) == (g[0], g[1], h)
+        assert tuple(r[-2]) == (*w.ro.pts[v], w.ro.head[v])
+        ids = p.route2gv(T, int(v))
+        assert len(ids) == len(r) - 1
+        for a, bb, row in zip(ids[:-1], ids[1:], r[1:]):
+            assert w.ro.parent[bb] == a and tuple(row) == (*w.ro.pts[bb], w.ro.head[bb])
+        line = p.poses_polyline(r)
+        assert line.ndim == 2 and line.shape[1] == 2 and np.allclose(line[0], r[0, :2]) and np.allclose(line[-1], r[-1, :2], atol=1e-6)
+    # state: a new n invalidates the tree until the next plan()
+    p.set_n(w.n)
+    with pytest.raises(RuntimeError, match="plan"):
+        p.connect_poses(w.goals[:2])
+
+
+SEEDS = {name: spec[7] for name, spec in poseref.SPECS.items()}
+
+
+# ------------------------------------------------------------------------------------------------ the batch afterwards
+def _snapshot(res):
+    live = res.j + (1 if res.found else 0)
+    return (res.status, res.j, res.vgoal, res.found, res.sum_j, res.sum_near, res.pts[:live].copy(), res.head[:live].copy(), res.parent[:live].copy(),
+            res.vcost[:live].copy())
+
+
+def _same_snapshot(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _refused(code, word, fn, *args):
+    with pytest.raises(_ffi.RRTError) as e:
+        fn(*args)
+    assert e.value.code == code and word in str(e.value), str(e.value)
+
+
+def test_the_batch_is_left_as_it_was(gpu_ctx):
+    w = poseref.workload("A")
+    b, res = _run(gpu_ctx, w)
+    before = _snapshot(res)
+    _same(b.connect_poses(0, w.goals), w)
+    assert _same_snapshot(before, _snapshot(b.get_result(0)))
+    b.rearm()
+    _refused(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)  # until the query has finished again
+    b.launch()
+    _refused(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)
+    b.sync()
+    assert _same_snapshot(before, _snapshot(b.get_result(0)))
+    _same(b.connect_poses(0, w.goals), w)
+    b.close()
+
+
+def test_refusals():
+    w = poseref.workload("E")
+    ctx = _ffi.Context(0)
+    ctx.set_grid(w.og8)
+    W, H = w.og8.shape
+    ok = [(5, 5, 0)]
+    _refused(_ffi.RRT_E_ARG, "no rrt_plan", ctx.connect_poses, ok)
+    b = _ffi.Batch(ctx, 2, w.n, dubins=True)
+    _refused(_ffi.RRT_E_ARG, "no query set", b.connect_poses, 0, ok)
+    q, keep = _query(w)
+    b.set_query(0, q)
+    _refused(_ffi.RRT_E_ARG, "not launched", b.connect_poses, 0, ok)
+    b.launch()
+    b.sync()
+    want = b.connect_poses(0, w.goals[:3])
+    _same(want, w, slice(0, 3))
+    _refused(_ffi.RRT_E_ARG, "q=2", b.connect_poses, 2, ok)
+    _refused(_ffi.RRT_E_ARG, "q=-1", b.connect_poses, -1, ok)
+    _refused(_ffi.RRT_E_ARG, "no query set", b.connect_poses, 1, ok)
+    _refused(_ffi.RRT_E_ARG, "outside", b.connect_poses, 0, [(5, 5, 0), (W, 5, 0)])
+    _refused(_ffi.RRT_E_ARG, "outside", b.connect_poses, 0, [(5, -1, 0)])
+    _refused(_ffi.RRT_E_ARG, "heading", b.connect_poses, 0, [(5, 5, w.nh)])
+    _refused(_ffi.RRT_E_ARG, "heading", b.connect_poses, 0, [(5, 5, 0), (5, 5, -1)])  # the C ABI takes concrete headings only
+    _refused(_ffi.RRT_E_ARG, "at most", b.connect_poses, 0, np.zeros(((1 << 20) + 1, 3), dtype=np.int32))
+    lib = _ffi.lib()
+    v, c, g = np.zeros(1, dtype=np.int32), np.zeros(1), np.zeros((1, 3), dtype=np.int32)
+    assert lib.rrt_batch_connect_poses(b._h, 0, None, 1, v.ctypes.data, c.ctypes.data) == _ffi.RRT_E_ARG
+    assert lib.rrt_batch_connect_poses(b._h, 0, g.ctypes.data, 1, None, c.ctypes.data) == _ffi.RRT_E_ARG
+    assert lib.rrt_batch_connect_poses(b._h, 0, g.ctypes.data, 1, v.ctypes.data, None) == _ffi.RRT_E_ARG
+    assert lib.rrt_batch_connect_poses(None, 0, g.ctypes.data, 1, v.ctypes.data, c.ctypes.data) == _ffi.RRT_E_ARG
+    assert lib.rrt_batch_connect_poses(b._h, 0, g.ctypes.data, -1, v.ctypes.data, c.ctypes.data) == _ffi.RRT_E_ARG
+    assert lib.rrt_batch_connect_poses_counts(b._h, None) == _ffi.RRT_E_ARG
+    # the refused calls changed nothing: the counts are still those of the last call that ran
+    assert b.connect_poses_counts()[1] >= int((w.rank[:3] + 1)[w.vertex[:3] >= 0].sum())
+    # the grid replaced between run and call: same shape, another generation
+    ctx.set_grid(w.og8)
+    _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, ok)
+    b.rearm()
+    b.launch()
+    b.sync()
+    _same(b.connect_poses(0, w.goals[:3]), w, slice(0, 3))
+    ctx.set_grid(np.zeros((W + 8, H), dtype=np.uint8))
+    _refused(_ffi.RRT_E_ARG, "shape", b.connect_poses, 0, ok)
+    b.close()
+    # a batch of a straight-line planner: its call is connect_goals
+    ctx.set_grid(w.og8)
+    b = _ffi.Batch(ctx, 1, w.n)
+    q, keep = _ffi.make_query(1, w.n, w.xs[:2], w.xg[:2], w.samples, r2_rewire=w.r2)
+    b.set_query(0, q)
+    b.launch()
+    b.sync()
+    _refused(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_connect_goals", b.connect_poses, 0, ok)
+    b.connect_goals(0, [(5, 5)])
+    b.close()
+    ctx.close()
+
+
+def test_a_tree_whose_own_goal_is_unreachable_is_accepted():
+    """workload F through rrt_plan: status -2, the tree is the start alone and complete; its own goal and a free pose answer -1 / inf"""
+    w = poseref.workload("F")
+    ctx = _ffi.Context(0)
+    ctx.set_grid(w.og8)
+    q, keep = _query(w)
+    rc, res = ctx.plan(q, w.n)
+    assert rc == _ffi.RRT_E_GOAL_UNREACHABLE and res.j == 1
+    vertex, cost = ctx.connect_poses(w.goals)
+    assert np.array_equal(vertex, w.vertex) and np.array_equal(cost, w.cost) and np.all(vertex == -1)
+    ctx.close()
