@@ -264,6 +264,17 @@ class _DubAudit(C.Structure):
     ]
 
 
+class _DubGoalsAudit(C.Structure):
+    _fields_ = [
+        ("W", C.c_int32), ("H", C.c_int32), ("og", C.c_void_p), ("rho", C.c_double), ("nh", C.c_int32), ("j", C.c_int32),
+        ("pts", C.c_void_p), ("head", C.c_void_p), ("vcost", C.c_void_p),
+        ("m", C.c_int32), ("pad_", C.c_int32), ("goals", C.c_void_p), ("vertex", C.c_void_p), ("cost", C.c_void_p),
+        ("n_connected", C.c_int64), ("answer_is_argmin", C.c_int64), ("answer_within_tol", C.c_int64), ("answer_wrong", C.c_int64),
+        ("answer_blocked", C.c_int64), ("answer_blocked_ambiguous", C.c_int64), ("cost_mismatch", C.c_int64), ("max_cost_err", C.c_double),
+        ("missed", C.c_int64), ("phantom", C.c_int64), ("words", C.c_int64), ("sweeps", C.c_int64), ("first_bad_goal", C.c_int64),
+    ]
+
+
 def dubref_lib():
     """libdubref.so: textbook Dubins words on libm with their own sweep; does NOT include include/rrt_dubins.h."""
     global _dubref
@@ -276,6 +287,8 @@ def dubref_lib():
         L.dubref_audit.restype = C.c_int
         L.dubref_shortest.argtypes = [C.c_double] * 7 + [C.c_void_p]
         L.dubref_shortest.restype = None
+        L.dubref_goals_audit.argtypes = [C.POINTER(_DubGoalsAudit)]
+        L.dubref_goals_audit.restype = C.c_int
         _dubref = L
     return _dubref
 
@@ -305,3 +318,25 @@ def dubins_audit(og8, n, star, samples, headings, pts, head, vcost, parent, j, r
     if rc != 0:
         raise ValueError("dubref_audit: bad argument")
     return {k: getattr(a, k) for k, _ in _DubAudit._fields_[17:]}
+
+
+def dubins_goals_audit(og8, pts, head, vcost, j, goals, vertex, cost, rho=8.0, nh=64):
+    """Recompute the goal decision behind every answer (vertex[g], cost[g]) for the goal pose goals[g] = (x, y, heading index)
+    against the tree (pts, head, vcost; j vertices) with dubins_ref.c's own arithmetic, over every vertex, and count where they
+    differ (see dubref_goals_audit there).  Returns a dict of the counters."""
+    og8 = np.ascontiguousarray(og8, dtype=np.uint8)
+    pts = np.ascontiguousarray(np.asarray(pts)[:j], dtype=np.int32)
+    head = np.ascontiguousarray(np.asarray(head)[:j], dtype=np.int32)
+    vcost = np.ascontiguousarray(np.asarray(vcost)[:j], dtype=np.float64)
+    goals = np.ascontiguousarray(np.asarray(goals).reshape(-1, 3), dtype=np.int32)
+    vertex = np.ascontiguousarray(vertex, dtype=np.int32)
+    cost = np.ascontiguousarray(cost, dtype=np.float64)
+    assert vertex.shape == cost.shape == (goals.shape[0],)
+    a = _DubGoalsAudit()
+    a.W, a.H, a.og, a.rho, a.nh, a.j = og8.shape[0], og8.shape[1], og8.ctypes.data, float(rho), int(nh), int(j)
+    a.pts, a.head, a.vcost = pts.ctypes.data, head.ctypes.data, vcost.ctypes.data
+    a.m, a.goals, a.vertex, a.cost = goals.shape[0], goals.ctypes.data, vertex.ctypes.data, cost.ctypes.data
+    rc = dubref_lib().dubref_goals_audit(C.byref(a))
+    if rc != 0:
+        raise ValueError("dubref_goals_audit: bad argument")
+    return {k: getattr(a, k) for k, _ in _DubGoalsAudit._fields_[14:]}

@@ -330,6 +330,110 @@ int dubref_audit(ref_audit_t *a) {
     return 0;
 }
 
+/* ------------------------------------------------------------------------------------------------ the goal decisions for M poses
+ * connect_poses answers, per goal pose, the (cost, index)-smallest vertex of [0, j) whose word to the pose sweeps free, or -1.  This
+ * audit takes the answers (vertex, cost) and, for every goal, works through EVERY vertex with this file's arithmetic: ref_shortest
+ * for the price, ref_edge for the sweep.  Nothing is pruned by a bound: the kernel's chord bound is one of the things under audit.
+ * As above it cannot demand equal bits, so the classes are those of ref_audit_t with "parent" read as "answer". */
+typedef struct {
+    /* inputs: the map, the tree (j vertices) ... */
+    int32_t W, H;
+    const uint8_t *og;
+    double rho;
+    int32_t nh, j;
+    const int32_t *pts;  /* (j, 2) */
+    const int32_t *head; /* (j) */
+    const double *vcost; /* (j) */
+    /* ... the goal poses and the answers under audit */
+    int32_t m, pad_;
+    const int32_t *goals;  /* (m, 3): x, y, heading index */
+    const int32_t *vertex; /* (m): the vertex, or -1 */
+    const double *cost;    /* (m): the cost through it, or +inf */
+    /* outputs */
+    int64_t n_connected;       /* answers other than -1 for a goal on a free cell */
+    int64_t answer_is_argmin;  /* the answer == first minimum, in index order, of this file's costs over the vertices its sweep sees */
+    int64_t answer_within_tol; /* another vertex, with a cost within REF_TOL of that minimum, or a cheaper candidate whose sweep is ambiguous */
+    int64_t answer_wrong;      /* neither */
+    int64_t answer_blocked;    /* this file's sweep calls the answered edge blocked (not ambiguous) */
+    int64_t answer_blocked_ambiguous;
+    int64_t cost_mismatch;     /* stored cost differs from this file's cost through the answered vertex by more than REF_TOL */
+    double max_cost_err;       /* largest such difference seen (absolute) */
+    int64_t missed;            /* the answer is -1 although some vertex connects without ambiguity */
+    int64_t phantom;           /* an answer other than -1 for a goal on an obstacle cell */
+    int64_t words, sweeps;     /* evaluations this audit made */
+    int64_t first_bad_goal;    /* the first goal counted in answer_wrong / answer_blocked / cost_mismatch / missed / phantom (-1: none) */
+} ref_goals_audit_t;
+
+int dubref_goals_audit(ref_goals_audit_t *a) {
+    const int W = a->W, H = a->H, j = a->j, m = a->m;
+    if (j < 1 || m < 0 || W < 1 || H < 1 || !(a->rho > 0.0) || a->nh < 1) return -1;
+    a->n_connected = a->answer_is_argmin = a->answer_within_tol = a->answer_wrong = a->answer_blocked = a->answer_blocked_ambiguous = 0;
+    a->cost_mismatch = a->missed = a->phantom = a->words = a->sweeps = 0;
+    a->max_cost_err = 0.0;
+    a->first_bad_goal = -1;
+    for (int g = 0; g < m; g++) {
+        const int gx = a->goals[3 * g], gy = a->goals[3 * g + 1], gh = a->goals[3 * g + 2], v = a->vertex[g];
+        if (gx < 0 || gx >= W || gy < 0 || gy >= H || gh < 0 || gh >= a->nh || v < -1 || v >= j) return -1;
+    }
+    double *c = (double *)malloc(sizeof(double) * (size_t)j);
+    uint8_t *fr = (uint8_t *)malloc((size_t)j), *am = (uint8_t *)malloc((size_t)j);
+    if (!c || !fr || !am) {
+        free(c);
+        free(fr);
+        free(am);
+        return -1;
+    }
+    for (int g = 0; g < m; g++) {
+        const int gx = a->goals[3 * g], gy = a->goals[3 * g + 1], gh = a->goals[3 * g + 2], v = a->vertex[g];
+        int bad = 0;
+        if (a->og[(int64_t)gx * H + gy] != 0) { /* every sweep ends on the goal cell: nothing connects, whatever the words say */
+            if (v != -1) a->phantom++, bad = 1;
+            if (bad && a->first_bad_goal < 0) a->first_bad_goal = g;
+            continue;
+        }
+        int vmin = -1, clean = 0;
+        double cmin = HUGE_VAL;
+        for (int k = 0; k < j; k++) {
+            int f = 0, amb = 0;
+            const ref_path w = ref_edge(a->og, W, H, a->nh, a->rho, a->pts[2 * k], a->pts[2 * k + 1], a->head[k], gx, gy, gh, &f, &amb);
+            a->words++, a->sweeps++;
+            c[k] = a->vcost[k] + w.len;
+            fr[k] = (uint8_t)f, am[k] = (uint8_t)amb;
+            if (f && c[k] < cmin) cmin = c[k], vmin = k; /* strict <: the first minimum in index order */
+            if (f && !amb) clean = 1;
+        }
+        if (v < 0) {
+            if (clean) a->missed++, bad = 1;
+            if (bad && a->first_bad_goal < 0) a->first_bad_goal = g;
+            continue;
+        }
+        a->n_connected++;
+        const double c_dev = c[v];
+        const double tol = REF_TOL * (1.0 + fabs(c_dev));
+        const double err = fabs(a->cost[g] - c_dev);
+        if (!(err <= a->max_cost_err)) a->max_cost_err = err; /* (a NaN or an infinity among the costs lands here, too) */
+        if (!(err <= tol)) a->cost_mismatch++, bad = 1;
+        if (!fr[v]) {
+            if (am[v]) a->answer_blocked_ambiguous++;
+            else a->answer_blocked++, bad = 1;
+        }
+        /* the answer is plainly wrong only if a vertex cheaper than it by more than the tolerance connects without ambiguity; short of
+         * that, a first minimum other than the answer is a cost within the tolerance or a candidate whose visibility hangs on the
+         * last bits of a sample: either answer is defensible */
+        int ahead_clean = 0;
+        for (int k = 0; k < j && !ahead_clean; k++)
+            if (k != v && fr[k] && !am[k] && c[k] < c_dev - tol) ahead_clean = 1;
+        if (vmin == v) a->answer_is_argmin++;
+        else if (!ahead_clean && (fr[v] || am[v])) a->answer_within_tol++;
+        else a->answer_wrong++, bad = 1;
+        if (bad && a->first_bad_goal < 0) a->first_bad_goal = g;
+    }
+    free(c);
+    free(fr);
+    free(am);
+    return 0;
+}
+
 /* primitives for the tests: the word between two poses, the cells of its sweep */
 void dubref_shortest(double x0, double y0, double th0, double x1, double y1, double th1, double rho, double out[5]) {
     const ref_path w = ref_shortest(x0, y0, th0, x1, y1, th1, rho);

@@ -2,7 +2,9 @@
 rrt_plan_connect_poses, RRTDubins / RRTStarDubins .connect_poses / .paths_to_poses).
 
 Every comparison is exact: vertices and costs with ==.  The check is poseref.py (the oracle's word and sweep, a stable argsort) on
-the workloads it defines, and for the planners' own goals plan() itself and oracle.dubins_plan."""
+the workloads it defines, and for the planners' own goals plan() itself and oracle.dubins_plan.  The conditions that make the made-up
+trees below worth running (the ties are ties, the trees have exactly j vertices, the fuzz connects) are asserted without a GPU, in
+test_connect_poses_cpu.py.  Only the independent audit (oracle/dubins_ref.c: libm, no shared header) has tolerances: its own."""
 import numpy as np
 import pytest
 
@@ -10,6 +12,7 @@ import oracle
 import poseref
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
+from rrtplanner_amd.oggen import DeviceGrids
 
 pytestmark = pytest.mark.gpu
 
@@ -270,3 +273,164 @@ def test_a_tree_whose_own_goal_is_unreachable_is_accepted():
     vertex, cost = ctx.connect_poses(w.goals)
     assert np.array_equal(vertex, w.vertex) and np.array_equal(cost, w.cost) and np.all(vertex == -1)
     ctx.close()
+
+
+# ------------------------------------------------------------------------------------------------ exact ties
+def _goal_row_of_plan(ctx, w):
+    """the query through rrt_plan, both kernels: the tree and the goal row (go2goal_phase<true>'s decision) are the oracle's"""
+    ctx.set_grid(w.og8)
+    for serial in (False, True):
+        q, keep = _query(w)
+        rc, res = ctx.plan(q, w.n, serial=serial)
+        ro = w.ro
+        live = ro.j + (1 if ro.found else 0)
+        assert rc == w.status and (res.j, res.found, res.vgoal) == (ro.j, ro.found, ro.vgoal), (w.name, serial)
+        assert np.array_equal(res.parent[:live], ro.parent[:live]) and np.array_equal(res.vcost[:live], ro.vcost[:live]), (w.name, serial)
+        assert np.array_equal(res.pts[:live], ro.pts[:live]) and np.array_equal(res.head[:live], ro.head[:live]), (w.name, serial)
+        _same(ctx.connect_poses(w.goals), w)  # ... and rrt_plan_connect_poses on that tree
+
+
+def _asked_twice(ctx, w):
+    """the order inside a bucket may differ between launches, the answer may not"""
+    b, res = _run(ctx, w)
+    first = b.connect_poses(0, w.goals)
+    _same(first, w)
+    _same(b.connect_poses(0, w.goals), w)
+    for g in range(min(3, len(w.goals))):  # ... nor with the goal asked alone
+        _same(b.connect_poses(0, w.goals[g]), w, slice(g, g + 1))
+    b.close()
+    return first
+
+
+@pytest.mark.parametrize("place", list(poseref.TIE_PLACES))
+@pytest.mark.parametrize("rho,nh", poseref.TIE_PAIRS)
+def test_a_duplicate_of_the_start_pose_never_wins(gpu_ctx, rho, nh, place):
+    for star in (0, 1):
+        w = poseref.tie_duplicate(rho, nh, star, place)
+        poseref.check_tie_duplicate(w, place)
+        vertex, cost = _asked_twice(gpu_ctx, w)
+        assert not np.any(vertex == w.dup) and (vertex == 0).sum() >= 8
+        _goal_row_of_plan(gpu_ctx, w)
+
+
+@pytest.mark.parametrize("fillers", [0, 100])
+def test_equal_costs_go_to_the_lower_index(gpu_ctx, fillers):
+    for rho, nh in poseref.TIE_PAIRS:
+        for star in (0, 1):
+            a, b, iL, iR = poseref.tie_collinear(rho, nh, star, fillers)
+            poseref.check_tie_collinear(a, b, iL, iR)
+            vertex, cost = _asked_twice(gpu_ctx, a)
+            assert (vertex[0], cost[0]) == (0, 70.0)
+            vertex, cost = _asked_twice(gpu_ctx, b)
+            assert vertex[0] == iL and cost[0] == b.c[0, iL] == b.c[0, iR]
+            _goal_row_of_plan(gpu_ctx, a)
+            _goal_row_of_plan(gpu_ctx, b)
+
+
+def test_a_chain_in_which_every_cost_is_equal(gpu_ctx):
+    """1100 vertices, one bucket, two rounds, every cost 1288.0: vertex 0.  Every merge of lanes and of waves is a tie here; the
+    merge of the two rounds is one only if the scatter puts vertex 0 behind position 1023, which it does not in practice (see
+    poseref.tie_chain and DESIGN.md 4.2g: the round merge's order on equal costs is not pinned by any test)"""
+    w = poseref.tie_chain()
+    poseref.check_tie_chain(w)
+    vertex, cost = _asked_twice(gpu_ctx, w)
+    assert (vertex[0], cost[0]) == (0, 1288.0)
+    _goal_row_of_plan(gpu_ctx, w)
+
+
+# ------------------------------------------------------------------------------------------------ trees around the strides
+@pytest.mark.parametrize("j", poseref.STRIDE_J)
+def test_tree_sizes_around_the_strides(gpu_ctx, j):
+    for star in (0, 1):
+        w = poseref.stride_tree(j, star)
+        poseref.check_stride_tree(w, j)
+        b, res = _run(gpu_ctx, w)
+        _same(b.connect_poses(0, w.goals), w)
+        for g, goal in enumerate(w.goals):  # asked alone: what the counters must say follows from the semantics
+            _same(b.connect_poses(0, goal), w, slice(g, g + 1))
+            words, sweeps = b.connect_poses_counts()
+            if w.vertex[g] >= 0:
+                assert w.rank[g] + 1 <= sweeps <= words <= j, (w.name, g, w.rank[g], words, sweeps)
+            elif w.og8[goal[0], goal[1]] == 0:
+                assert (words, sweeps) == (j, j), (w.name, g, words, sweeps)
+            else:
+                assert (words, sweeps) == (0, 0), (w.name, g, words, sweeps)
+        b.close()
+
+
+# ------------------------------------------------------------------------------------------------ a fuzz over small trees
+def test_pose_goals_fuzz_small(gpu_ctx):
+    cases = poseref.fuzz_cases()
+    assert len(cases) >= 100
+    for w in cases:
+        try:
+            gpu_ctx.set_grid(w.og8)
+            q, keep = _query(w)
+            rc, res = gpu_ctx.plan(q, w.n, logs=True, serial=w.serial)
+            ro = w.ro
+            live = ro.j + (1 if ro.found else 0)
+            assert rc == w.status and (res.j, res.found, res.vgoal) == (ro.j, ro.found, ro.vgoal)
+            assert np.array_equal(res.nearest_log, ro.nearest_log) and np.array_equal(res.accept_log, ro.accept_log)
+            assert np.array_equal(res.pts[:live], ro.pts[:live]) and np.array_equal(res.head[:live], ro.head[:live])
+            assert np.array_equal(res.parent[:live], ro.parent[:live]) and np.array_equal(res.vcost[:live], ro.vcost[:live])
+            assert res.sum_j == ro.sum_j and res.sum_cells_nn == ro.sum_cells_nn and res.sum_near == ro.sum_near
+            _same(gpu_ctx.connect_poses(w.goals), w)
+        except AssertionError as e:
+            raise AssertionError(w.name) from e
+    goals, connected, past_blocked = poseref.fuzz_coverage(cases)
+    assert 4 * connected >= goals and 20 * past_blocked >= goals
+
+
+# ------------------------------------------------------------------------------------------------ the independent audit
+def _audit_of_the_devices_answers(ctx, w):
+    b, res = _run(ctx, w)
+    vertex, cost = b.connect_poses(0, w.goals)
+    b.close()
+    a = poseref.goals_audit(w, vertex, cost)
+    poseref.assert_goals_audit_clean(a, vertex)
+    _same((vertex, cost), w)
+    return a, vertex
+
+
+def test_independent_audit_of_the_devices_answers(gpu_ctx):
+    """the DEVICE's (vertex, cost) for every goal against oracle/dubins_ref.c, which shares no header with the kernel: on more than
+    two rounds of vertices, on the stride tree of 2049, and on a tie tree -- where the duplicate has the start's pose, so libm gives
+    both the same cost and the audit's first minimum must be the answer itself"""
+    a, vertex = _audit_of_the_devices_answers(gpu_ctx, poseref.workload("C"))
+    assert a["n_connected"] >= 6
+    a, vertex = _audit_of_the_devices_answers(gpu_ctx, poseref.stride_tree(2049, 1))
+    assert a["n_connected"] >= 4
+    w = poseref.tie_duplicate(4.0, 16, 1, "above_1024")
+    a, vertex = _audit_of_the_devices_answers(gpu_ctx, w)
+    assert a["answer_is_argmin"] == a["n_connected"] == len(w.goals) and a["answer_within_tol"] == 0
+
+
+# ------------------------------------------------------------------------------------------------ resident frames
+def test_a_tree_of_one_resident_frame_is_refused_on_the_other(gpu_ctx):
+    """Resident frames share one grid generation: only the grid's address tells the tree's frame from the active one."""
+    grids = DeviceGrids(gpu_ctx, 96, 100, thresh=0.33, frames=2, seed=5)
+    og = [np.ascontiguousarray(f != 0, dtype=np.uint8) for f in grids.host]
+    assert not np.array_equal(og[0], og[1])
+    free = np.argwhere(og[0] == 0)
+    rng = np.random.default_rng(8)
+    n, rho, nh = 400, 3.0, 16
+    a, c = free[rng.integers(0, len(free), 2)]
+    goals = np.column_stack([free[rng.integers(0, len(free), 12)], rng.integers(0, nh, 12)])
+    w = poseref.made("frames", og[0], n, 1, 15, rho, nh, (a[0], a[1], 3), (c[0], c[1], 7), hostprep.draw_free_samples(rng, free, n), rng.integers(0, nh, n), goals)
+    assert w.j > 50 and (w.vertex >= 0).sum() >= 4
+    grids.select(0)
+    generation = gpu_ctx.grid_generation()
+    b = _ffi.Batch(gpu_ctx, 1, n, dubins=True)
+    q, keep = _query(w)
+    b.set_query(0, q)
+    b.launch()
+    b.sync()
+    assert b.get_result(0).j == w.j
+    _same(b.connect_poses(0, w.goals), w)
+    counts = b.connect_poses_counts()
+    grids.select(1)
+    _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, w.goals)
+    assert gpu_ctx.grid_generation() == generation and b.connect_poses_counts() == counts  # (the refused call ran nothing)
+    grids.select(0)
+    _same(b.connect_poses(0, w.goals), w)  # the tree is still there: no new launch of the query
+    b.close()
