@@ -1,101 +1,13 @@
 // rrt_engine.hip -- C ABI (include/rrt_hip.h) over the gfx950 kernels of rrt_kernels.h.
-// Host side: HIP memory, one stream per context, events for kernel timing.  No torch.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>  // types only: the library is opened on demand (rrt_comm_init), the single-GPU path never loads it
-#include <dlfcn.h>
-
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <tuple>
-#include <vector>
-
-// The expansion kernels are only LAUNCHED from this translation unit; kernels_tu.hip holds their definitions, dealt to several
-// translation units that compile side by side (the single unit of round 3 took two and a half minutes).
-#define RRT_BLOCK_DECL_ONLY
-#define RRT_SERIAL_DECL_ONLY
-#include "rrt_hip.h"
-#include "rrt_kernels.h"
-#include "rrt_block.h"
-#include "rrt_block_variants.def"
-#include "rrt_kernel_decls.h"
-#define RRT_GOALS_DECL_ONLY
-#include "rrt_goals.h"
-#define RRT_ROUTES_DECL_ONLY
-#include "rrt_routes.h"
-#define RRT_KEEP_DECL_ONLY
-#include "rrt_keep.h"
-#define RRT_SEED_DECL_ONLY
-#include "rrt_seed.h"
-#define RRT_POSES_DECL_ONLY
-#include "rrt_pose_goals.h"
+// Host side: HIP memory, one stream per context, events for kernel timing.  No torch.  The calls on a finished tree: rrt_tree_calls.hip.
+#include "rrt_engine.h"
 #include "rrt_prims.h"
 
-using namespace rrtdev;
-
-static thread_local std::string g_last_error;
+static thread_local std::string g_last_error;  // (the only one: fail() is defined here)
 
 constexpr int RRT_GRID_FAST = 2048;  // the expansion kernels: coordinates below 2^11, squared distances below 2^24 (packed scan keys, sqrt_u24)
 constexpr int RRT_GRID_LARGE = 4096; // RRT_FLAG_LARGE_GRID (rrt_pipe_large_kernel): coordinates below 2^12, squared distances below 2^25
 constexpr int RRT_GRID_MAX = 32767;  // the host-driven path (rrt_tree_query, rrt_prim_collisionfree): 16-bit packed coordinates whose differences fit int16
-
-// Host copy of a batch's query descriptors in page-locked memory: the per-step copies to and from the device (rrt_batch_rearm,
-// rrt_batch_sync) are then plain DMA transfers in stream order, with no staging copy and no hidden synchronisation.
-struct PinnedDescs {
-    QDesc *p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count) {
-        release();
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(QDesc), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return e;
-        }
-        n = count;
-        for (size_t k = 0; k < n; ++k) p[k] = QDesc{};
-        return hipSuccess;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    QDesc *data() { return p; }
-    QDesc *begin() { return p; }
-    QDesc *end() { return p + n; }
-    QDesc &operator[](size_t k) { return p[k]; }
-};
-
-struct rrt_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // pipelined teams of 8 and more: the committers' kernel runs here, next to the workers' on `stream`
-    uint8_t *og = nullptr;      // active grid, device (W,H): og_buf + frame * W * H
-    uint8_t *og_buf = nullptr;  // allocation holding 1 uploaded grid or `nframes` generated grids
-    size_t og_buf_bytes = 0;
-    int32_t nframes = 1;
-    int32_t W = 0, H = 0;
-    std::string err;
-    rrt_batch *single = nullptr;  // batch behind rrt_plan / rrt_plan_resume
-    uint32_t single_flags = 0;
-    int max_lds = 0;
-    int num_cu = 0;
-    uint64_t grid_gen = 0;  // bumped by every call that rewrites or reallocates og_buf (rrt_set_grid, rrt_noise_grids)
-    // multi-GPU result gather (RCCL over xGMI); all null / 1 until rrt_comm_init
-    ncclComm_t comm = nullptr;
-    int32_t comm_rank = 0, comm_world = 1;
-    unsigned char *gather_buf = nullptr;  // [world][slab bytes of the batch gathered last]
-    size_t gather_bytes = 0;
-    const rrt_batch *gather_owner = nullptr;  // the batch whose slabs gather_buf holds (rrt_gather_fetch serves no other)
-    double *d_red = nullptr;  // small device scratch of rrt_comm_allreduce_f64
-};
-
-typedef void (*block_kernel_fn)(BatchView);
 
 // A launchable variant of the team kernels: one row per entry of rrt_block_variants.def, the only list of them.  A K entry is one
 // kernel (`one`); an S entry is the pipelined team <G, BSM, true, INF> as two kernels (`commit`, `work`).
@@ -135,114 +47,11 @@ static size_t block_kernel_static_lds(int team) {
     return (worst + 255) & ~(size_t)255;
 }
 
-// What one launch decided (plan_launch).  The batch keeps the plan of its last launch for the questions asked afterwards
-// (rrt_batch_kernel_name, rrt_batch_team_info, rrt_batch_pipelined, the continuation in rrt_batch_sync).
-struct LaunchPlan {
-    int team = 0;               // workers per query (1 after a hand-off timed out; 0: nothing launched yet)
-    int qpad = 0;               // block = member * qpad + query
-    bool pipe = false;          // the pipelined team kernel: one more workgroup per query, which only commits
-    bool inf = false;           // the Informed instantiation
-    bool wide = false;          // a team variant with more than 16 samples per member
-    bool split = false;         // committers and workers as two kernels (rrt_block_commit_kernel + rrt_block_work_kernel)
-    bool pipe1 = false;         // the barrier-free one-CU kernel (rrt_pipe.h)
-    bool large = false;         // ... in its form for grids up to 4096 x 4096 (RRT_FLAG_LARGE_GRID: the only kernel such a batch runs)
-    bool continuation = false;  // of a launch that stopped at a block boundary: one CU per query, and the block kernel takes it from there
-    const BlockVariant *row = nullptr;  // the team variant, or nullptr for a kernel that is none (pipe1, Dubins, one sample per iteration)
-    block_kernel_fn kern = nullptr;     // the kernel of a launch that is one kernel (row->one, or the plain kernel)
-    unsigned grid = 0;          // its workgroups (split: qpad committers, qpad * team workers)
-    int lds_chunks = 1;         // node chunks cached in LDS
-    size_t lds_bytes = 0;       // dynamic LDS per workgroup
-};
-
-struct rrt_batch {
-    rrt_ctx *ctx = nullptr;
-    int32_t Q = 0, n_cap = 0, node_stride = 0, bitmap_words = 0, lds_chunks = 1, spill_stride = 0;
-    int32_t gridW = 0, gridH = 0;
-    uint32_t flags = 0;
-    bool use_block = false;     // block-parallel kernel (rrt_block.h) instead of the one-sample-per-iteration kernel
-    bool dub_block = false;     // Dubins planners on the 16-samples-per-round kernel (rrt_dubins_block.h); RRT_FLAG_SERIAL keeps the one-sample kernel
-    int32_t blk_lds_chunks = 1; // node chunks cached in LDS by the block kernel: teams of 8 and more workers ...
-    int32_t blk_lds_chunks16 = 1; // ... and the kernels that also keep their parked-entry lists there
-    int32_t team = 1;           // workgroups (CUs) per query of the block kernel that scan and resolve (rrt_block.h, teams)
-    bool pipe_team = false;     // the team is pipelined: one more workgroup per query, which only commits
-    LaunchPlan last;            // the plan of the last launch
-    int32_t team_fallbacks = 0; // launches repeated with one CU per query after a team hand-off timed out
-    int32_t team_qpad = 0;      // Q rounded up to a multiple of 8: block = member * team_qpad + query
-    int32_t team_want = TEAM_MAX;  // the caller's cap on the team size
-    int32_t claimed_cus = 0;    // compute units this batch's launch in flight holds in the device's registry (0: nothing in flight)
-    int32_t shrunk = 0;         // launches that ran a smaller team than the batch was created with because other launches held CUs
-    unsigned char *d_team = nullptr;  // [Q][TEAM_BYTES] sync words, state, exchanged records; zeroed before every launch
-    QDesc *d_desc = nullptr;
-    PinnedDescs h_desc;  // page-locked
-    size_t serial_lds_static = 0;  // static LDS of the one-sample-per-iteration kernel + 1 (0 = not asked yet)
-    uint32_t *d_samples = nullptr, *d_nodes = nullptr, *d_bitmap = nullptr;
-    double *d_vcost = nullptr, *d_unitball = nullptr, *d_cbest_log = nullptr;
-    int32_t *d_parent = nullptr, *d_nearest_log = nullptr, *d_j_log = nullptr;
-    uint8_t *d_accept_log = nullptr;
-    uint2 *d_spill = nullptr;
-    int32_t *d_kids = nullptr;      // RRT_FLAG_REWIRE: [3][Q][node_stride] first child / next sibling / previous sibling
-    uint32_t *d_frontier = nullptr; //                  [Q][2 * node_stride]
-    int32_t *d_vsoln = nullptr;     //                  [Q][node_stride]
-    uint8_t *d_heading = nullptr;   // RRT_FLAG_DUBINS: [Q][node_stride] node headings
-    uint8_t *d_shead = nullptr;     //                  [Q][n_cap] sample headings
-    double *d_dubpath = nullptr;    //                  [Q][NWAVE * WCAP][5] the words of the current iteration's near-set entries
-    std::vector<uint8_t> stage8;
-    uint4 *d_cellrec = nullptr;    // block kernel: near-set records, [Q][rec_stride]
-    uint32_t *d_cellcnt = nullptr; // [Q][MAX_CELLS]
-    int64_t rec_stride = 0;
-    unsigned char *d_slab = nullptr;  // result slab: [vcost f64 | nodes u32 | parent i32], each [Q][node_stride]
-    size_t slab_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the split team kernels: stream -> stream2 behind the init kernel, back in front of ev1
-    bool timed = false;
-    float ms_before = 0.f;      // kernel time of the launch a fallback relaunch replaced (rrt_batch_elapsed_ms adds it)
-    bool one_cu_once = false;   // the next launch runs one CU per query whatever b->team says (continuation after a timeout)
-    std::vector<uint32_t> stage;  // host staging for packed samples
-    // rrt_batch_connect_goals: the grid every query last ran on (recorded at launch), and device memory allocated at the first call
-    std::vector<uint64_t> ran_gen;       // [Q] the context's grid generation
-    std::vector<const uint8_t *> ran_og; // [Q] ... and its active grid
-    uint32_t *d_goal_order = nullptr;    // [goal_slabs][n_cap] go2goal_phase's scratch, one slab per workgroup (never `spill`: a later launch needs it)
-    int32_t goal_slabs = 0;
-    uint32_t *d_goals = nullptr;         // [goal_cap] packed goals
-    int32_t *d_goal_vertex = nullptr;    // [goal_cap]
-    double *d_goal_cost = nullptr;       // [goal_cap]
-    int32_t goal_cap = 0;
-    // rrt_batch_connect_poses (RRT_FLAG_DUBINS): scratch allocated at the first call, grown by later ones (rrt_pose_goals.h)
-    uint32_t *d_pose_order = nullptr;    // [pose_slabs][n_cap] the sorted vertex order, one slab per workgroup
-    int32_t pose_slabs = 0;
-    uint32_t *d_pose_xy = nullptr;       // [pose_cap] packed goal cells
-    uint8_t *d_pose_h = nullptr;         // [pose_cap] goal heading indices
-    int32_t *d_pose_vertex = nullptr;    // [pose_cap]
-    double *d_pose_cost = nullptr;       // [pose_cap]
-    uint32_t *d_pose_counts = nullptr;   // [pose_cap][2] words evaluated, sweeps run
-    int32_t pose_cap = 0;
-    int32_t pose_last_m = -1;            // goals of the last successful rrt_batch_connect_poses; -1: none
-    // rrt_batch_routes: per-goal arrays and the rows of the routes, allocated at the first call, grown by later ones (rrt_routes.h)
-    unsigned char *d_route_goal = nullptr;  // [length | raw_off | fin_off | cnt | kept | err] for route_goal_cap goals
-    int32_t route_goal_cap = 0;
-    unsigned char *d_route_rows = nullptr;  // [row_xy | row_id | out_xy | out_id] for route_row_cap rows
-    int64_t route_row_cap = 0;
-    int64_t route_rows = -1;                // dense rows the last rrt_batch_routes left for rrt_batch_routes_rows; -1: none (launch, rearm)
-    // rrt_batch_keep_tree: the views of the queries that were kept on a new map (rrt_keep.h), allocated at the first call per query
-    std::vector<unsigned char *> d_keep;    // [Q] nullptr, or [live_vcost f64 | live_nodes u32 | live_id i32], each of n_cap
-    std::vector<int32_t> keep_alive;        // [Q] vertices of the view; -1: no view, the goals and routes calls see the whole tree
-    unsigned char *d_keep_tmp = nullptr;    // [anc i32 x 2 | ok u8 x 2 | count i32 at the end], each array of n_cap (rounded up to 8 bytes)
-    hipEvent_t ev_keep[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_keep_tree
-    bool keep_timed = false;
-    // rrt_batch_grow: a query armed as a loop stopped mid-way runs with D->n = j0 + m (rrt_seed.h)
-    std::vector<int32_t> grow_n;            // [Q] the query's own n while it is armed so; -1 otherwise (rrt_batch_sync puts it back)
-    std::vector<uint64_t> grow_gen;         // [Q] while it is armed so: the grid generation the seed was built on (rrt_batch_launch asks for it)
-    std::vector<const uint8_t *> grow_og;   // [Q] ... and that grid
-    unsigned char *d_seed_tmp = nullptr;    // [rank i32 | new_parent i32 | err i32], the arrays of n_cap
-    hipEvent_t ev_seed[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_grow
-    bool seed_timed = false;
-};
-
 // no query of the batch has a view any more (a launch, a rearm), or only query q (a new query in its place, a keep_tree that starts
 // over).  The grid a view was built for goes with it: that grid was adopted for the alive vertices only, so without the view the
 // whole tree has no grid it is known to be valid on, and goals_decide refuses the query until it is kept or launched again.  A query
 // without a view keeps its recorded grid: that is the grid its whole tree ran on.
-static void drop_keep_views(rrt_batch *b, int32_t q = -1) {
+void drop_keep_views(rrt_batch *b, int32_t q) {
     for (size_t k = 0; k < b->keep_alive.size(); ++k)
         if ((q < 0 || (size_t)q == k) && b->keep_alive[k] >= 0) {
             b->keep_alive[k] = -1;
@@ -270,7 +79,7 @@ static hipError_t raise_dynamic_lds(int device, const void *kern, int bytes) {
     return e;
 }
 
-static int fail(rrt_ctx *ctx, int code, const char *fmt, ...) {
+int fail(rrt_ctx *ctx, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -279,28 +88,6 @@ static int fail(rrt_ctx *ctx, int code, const char *fmt, ...) {
     g_last_error = buf;
     if (ctx) ctx->err = buf;
     return code;
-}
-
-#define HIPCHK(ctx, call)                                                                              \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) return fail(ctx, RRT_E_HIP, "%s: %s", #call, hipGetErrorString(e_));     \
-    } while (0)
-
-// Wait for the context's stream by polling (no interrupt wake-up of a sleeping host thread: on a host that parks the waiting
-// thread the default wait costs up to a millisecond per step, against a 9 ms launch).  A wait that lasts longer than
-// `spin_ms` falls through to the blocking wait, where the wake-up no longer matters and a spinning core would.
-static hipError_t wait_stream_spin(hipStream_t stream, double spin_ms = 100.0) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned it = 0;; ++it) {
-        const hipError_t e = hipStreamQuery(stream);
-        if (e != hipErrorNotReady) return e;
-        if ((it & 1023u) == 1023u && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > spin_ms)
-            return hipStreamSynchronize(stream);
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#endif
-    }
 }
 
 // device temporaries of one call: freed on every return path
@@ -588,11 +375,8 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath, b->d_goal_order, b->d_goals, b->d_goal_vertex, b->d_goal_cost, b->d_route_goal, b->d_route_rows, b->d_keep_tmp, b->d_seed_tmp,
-                    b->d_pose_order, b->d_pose_xy, b->d_pose_h, b->d_pose_vertex, b->d_pose_cost, b->d_pose_counts};
+                    b->d_dubpath};  // (the scratch of the tree calls, every DevBuf, goes with `delete b`)
     for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (unsigned char *p : b->d_keep)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : b->ev_keep)
         if (e) (void)hipEventDestroy(e);
@@ -731,7 +515,7 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     for (auto &d : b->h_desc) d.status = ST_IDLE;
     b->ran_gen.assign((size_t)Q, 0);
     b->ran_og.assign((size_t)Q, nullptr);
-    b->d_keep.assign((size_t)Q, nullptr);
+    b->keep = std::vector<DevBuf>((size_t)Q);
     b->keep_alive.assign((size_t)Q, -1);
     b->grow_n.assign((size_t)Q, -1);
     b->grow_gen.assign((size_t)Q, 0);
@@ -790,7 +574,7 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     return RRT_OK;
 }
 
-static void arm_desc(QDesc &d) {
+void arm_desc(QDesc &d) {
     d.status = ST_RUNNING;
     d.i = 0;
     d.j = 1;
@@ -1353,638 +1137,6 @@ extern "C" int rrt_batch_get_result(rrt_batch *b, int32_t q, rrt_result *out) {
     return d.status < 0 ? d.status : RRT_OK;
 }
 
-// ---- many goals against a finished tree (rrt_goals.h) ----
-// The part that rrt_batch_connect_goals and rrt_batch_routes share: every refusal, the goals packed and uploaded, the scratch of the
-// first call, and the goals kernel launched on the context's stream.  Nothing is read back and nothing waited for: vertex and cost
-// of the m goals are in b->d_goal_vertex / b->d_goal_cost once the stream gets there.  m == 0: RRT_OK, nothing launched.
-static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, bool null_out) {
-    rrt_ctx *ctx = b->ctx;
-    if (!goals_xy || null_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (b->flags & RRT_FLAG_DUBINS)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (an edge to a goal is a Dubins word to a goal pose; these kernels price straight lines)", who);
-    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
-    if (m < 0 || m > GOALS_MAX) return fail(ctx, RRT_E_ARG, "%s: m=%d, at most %d goals per call", who, m, GOALS_MAX);
-    const QDesc &d = b->h_desc[(size_t)q];
-    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
-        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
-                    d.status == ST_IDLE      ? "no query set"
-                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
-                    : d.status == ST_NEED_UB ? "it waits for its unit-ball stream"
-                                             : "its launch failed");
-    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid changed shape since the batch was created (%dx%d)", who, b->gridW, b->gridH);
-    if (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now): the tree belongs to the "
-                    "other grid", who, q, (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen);
-    const int W = ctx->W, H = ctx->H;
-    b->stage.resize((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        const int x = goals_xy[2 * k], y = goals_xy[2 * k + 1];
-        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
-        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
-    }
-    if (m == 0) return RRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // one slab of n_cap words per workgroup, at most GOALS_MAX_SLABS of them and GOALS_SLAB_BUDGET bytes, never fewer than one
-    int slabs = (int)(GOALS_SLAB_BUDGET / ((size_t)b->n_cap * sizeof(uint32_t)));
-    slabs = slabs > GOALS_MAX_SLABS ? GOALS_MAX_SLABS : (slabs < 1 ? 1 : slabs);
-    slabs = slabs > m ? m : slabs;
-    if (slabs > b->goal_slabs) {
-        if (b->d_goal_order) HIPCHK(ctx, hipFree(b->d_goal_order));
-        b->d_goal_order = nullptr;
-        b->goal_slabs = 0;
-        HIPCHK(ctx, hipMalloc((void **)&b->d_goal_order, (size_t)slabs * (size_t)b->n_cap * sizeof(uint32_t)));
-        b->goal_slabs = slabs;
-    }
-    if (m > b->goal_cap) {
-        // each pointer freed and cleared on its own: a failure half way leaves no pointer that is freed twice or overwritten
-        b->goal_cap = 0;
-        if (b->d_goals) HIPCHK(ctx, hipFree(b->d_goals));
-        b->d_goals = nullptr;
-        if (b->d_goal_vertex) HIPCHK(ctx, hipFree(b->d_goal_vertex));
-        b->d_goal_vertex = nullptr;
-        if (b->d_goal_cost) HIPCHK(ctx, hipFree(b->d_goal_cost));
-        b->d_goal_cost = nullptr;
-        // (a malloc that fails leaves the earlier ones in place with goal_cap == 0: the next call frees them above)
-        HIPCHK(ctx, hipMalloc((void **)&b->d_goals, (size_t)m * sizeof(uint32_t)));
-        HIPCHK(ctx, hipMalloc((void **)&b->d_goal_vertex, (size_t)m * sizeof(int32_t)));
-        HIPCHK(ctx, hipMalloc((void **)&b->d_goal_cost, (size_t)m * sizeof(double)));
-        b->goal_cap = m;
-    }
-    GoalsView gv{};
-    gv.og = ctx->og;
-    gv.H = H;
-    gv.nodes = b->d_nodes + (size_t)q * b->node_stride;
-    gv.vcost = b->d_vcost + (size_t)q * b->node_stride;
-    gv.j = d.j;
-    if (gv.j < 0 || gv.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, gv.j, b->n_cap);
-    // a query that was kept on this grid (rrt_batch_keep_tree): the decision over the view of its alive vertices, dense and in the
-    // original order; the kernel answers in indices of the view, rrt_keep_remap_kernel turns them into the original ones
-    const int32_t kept = b->keep_alive[(size_t)q];
-    const int32_t *live_id = nullptr;
-    if (kept >= 0) {
-        const double *live_vcost = reinterpret_cast<const double *>(b->d_keep[(size_t)q]);
-        const uint32_t *live_nodes = reinterpret_cast<const uint32_t *>(live_vcost + b->n_cap);
-        live_id = reinterpret_cast<const int32_t *>(live_nodes + b->n_cap);
-        gv.nodes = live_nodes;
-        gv.vcost = live_vcost;
-        gv.j = kept <= d.j ? kept : d.j;
-    }
-    gv.goals = b->d_goals;
-    gv.m = m;
-    gv.order = b->d_goal_order;
-    gv.slab_words = b->n_cap;
-    gv.vertex = b->d_goal_vertex;
-    gv.cost = b->d_goal_cost;
-    HIPCHK(ctx, hipMemcpyAsync(b->d_goals, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
-    if (live_id)
-        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, b->d_goal_vertex, live_id, m,
-                           gv.j);
-    HIPCHK(ctx, hipGetLastError());
-    return RRT_OK;
-}
-
-static int connect_goals(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
-    rrt_ctx *ctx = b->ctx;
-    if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost); rc != RRT_OK || m == 0) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_goal_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cost, b->d_goal_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (also: the staging buffer is reused)
-    return RRT_OK;
-}
-
-extern "C" int rrt_batch_connect_goals(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
-    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_goals: NULL");
-    return connect_goals("rrt_batch_connect_goals", b, q, goals_xy, m, vertex, cost);
-}
-
-extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_goals: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_goals: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
-    return connect_goals("rrt_plan_connect_goals", ctx->single, 0, goals_xy, m, vertex, cost);
-}
-
-// ---- many goal poses against a finished Dubins tree (rrt_pose_goals.h) ----
-// The conditions are goals_decide's, for a batch created with RRT_FLAG_DUBINS; a goal is a pose (x, y, h), h < the query's nh.
-static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
-    rrt_ctx *ctx = b->ctx;
-    if (!poses_xyh || !vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (!(b->flags & RRT_FLAG_DUBINS))
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use rrt_batch_connect_goals)", who);
-    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
-    if (m < 0 || m > POSES_MAX) return fail(ctx, RRT_E_ARG, "%s: m=%d, at most %d goal poses per call", who, m, POSES_MAX);
-    const QDesc &d = b->h_desc[(size_t)q];
-    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
-        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
-                    d.status == ST_IDLE      ? "no query set"
-                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
-                                             : "its launch failed");
-    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid changed shape since the batch was created (%dx%d)", who, b->gridW, b->gridH);
-    if (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now): the tree belongs to the "
-                    "other grid", who, q, (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen);
-    const int W = ctx->W, H = ctx->H;
-    if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
-    b->stage.resize((size_t)m);
-    b->stage8.resize((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        const int x = poses_xyh[3 * k], y = poses_xyh[3 * k + 1], h = poses_xyh[3 * k + 2];
-        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
-        if (h < 0 || h >= d.nh) return fail(ctx, RRT_E_ARG, "%s: goal %d has heading %d, query %d has headings [0, %d)", who, k, h, q, d.nh);
-        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
-        b->stage8[(size_t)k] = (uint8_t)h;
-    }
-    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
-    if (m == 0) {
-        b->pose_last_m = 0;
-        return RRT_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    b->pose_last_m = -1;  // (until this call has succeeded: the counters are being rewritten)
-    // one slab of n_cap words per workgroup, at most POSES_MAX_SLABS of them and POSES_SLAB_BUDGET bytes, never fewer than one
-    int slabs = (int)(POSES_SLAB_BUDGET / ((size_t)b->n_cap * sizeof(uint32_t)));
-    slabs = slabs > POSES_MAX_SLABS ? POSES_MAX_SLABS : (slabs < 1 ? 1 : slabs);
-    slabs = slabs > m ? m : slabs;
-    if (slabs > b->pose_slabs) {
-        if (b->d_pose_order) HIPCHK(ctx, hipFree(b->d_pose_order));
-        b->d_pose_order = nullptr;
-        b->pose_slabs = 0;
-        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_order, (size_t)slabs * (size_t)b->n_cap * sizeof(uint32_t)));
-        b->pose_slabs = slabs;
-    }
-    if (m > b->pose_cap) {
-        // each pointer freed and cleared on its own: a failure half way leaves no pointer that is freed twice or overwritten
-        b->pose_cap = 0;
-        if (b->d_pose_xy) HIPCHK(ctx, hipFree(b->d_pose_xy));
-        b->d_pose_xy = nullptr;
-        if (b->d_pose_h) HIPCHK(ctx, hipFree(b->d_pose_h));
-        b->d_pose_h = nullptr;
-        if (b->d_pose_vertex) HIPCHK(ctx, hipFree(b->d_pose_vertex));
-        b->d_pose_vertex = nullptr;
-        if (b->d_pose_cost) HIPCHK(ctx, hipFree(b->d_pose_cost));
-        b->d_pose_cost = nullptr;
-        if (b->d_pose_counts) HIPCHK(ctx, hipFree(b->d_pose_counts));
-        b->d_pose_counts = nullptr;
-        // (a malloc that fails leaves the earlier ones in place with pose_cap == 0: the next call frees them above)
-        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_xy, (size_t)m * sizeof(uint32_t)));
-        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_h, (size_t)m));
-        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_vertex, (size_t)m * sizeof(int32_t)));
-        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_cost, (size_t)m * sizeof(double)));
-        HIPCHK(ctx, hipMalloc((void **)&b->d_pose_counts, (size_t)m * 2 * sizeof(uint32_t)));
-        b->pose_cap = m;
-    }
-    PoseGoalsView pv{};
-    pv.og = ctx->og;
-    pv.W = W;
-    pv.H = H;
-    pv.nodes = b->d_nodes + (size_t)q * b->node_stride;
-    pv.vcost = b->d_vcost + (size_t)q * b->node_stride;
-    pv.heading = b->d_heading + (size_t)q * b->node_stride;
-    pv.j = d.j;
-    pv.nh = d.nh;
-    pv.rho = d.rho;
-    pv.goals = b->d_pose_xy;
-    pv.goal_h = b->d_pose_h;
-    pv.m = m;
-    pv.slab_words = b->n_cap;
-    pv.order = b->d_pose_order;
-    pv.vertex = b->d_pose_vertex;
-    pv.cost = b->d_pose_cost;
-    pv.counts = b->d_pose_counts;
-    HIPCHK(ctx, hipMemcpyAsync(b->d_pose_xy, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->d_pose_h, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_pose_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cost, b->d_pose_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (also: the staging buffers are reused)
-    b->pose_last_m = m;
-    return RRT_OK;
-}
-
-extern "C" int rrt_batch_connect_poses(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
-    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_poses: NULL");
-    return connect_poses("rrt_batch_connect_poses", b, q, poses_xyh, m, vertex, cost);
-}
-
-extern "C" int rrt_plan_connect_poses(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_connect_poses: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_connect_poses: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
-    return connect_poses("rrt_plan_connect_poses", ctx->single, 0, poses_xyh, m, vertex, cost);
-}
-
-extern "C" int rrt_batch_connect_poses_counts(rrt_batch *b, int64_t out[2]) {
-    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_poses_counts: NULL");
-    rrt_ctx *ctx = b->ctx;
-    if (b->pose_last_m < 0) return fail(ctx, RRT_E_ARG, "rrt_batch_connect_poses_counts: no rrt_batch_connect_poses on this batch yet, or its last one failed");
-    out[0] = out[1] = 0;
-    const size_t m = (size_t)b->pose_last_m;
-    if (m == 0) return RRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    b->stage.resize(2 * m);
-    HIPCHK(ctx, hipMemcpyAsync(b->stage.data(), b->d_pose_counts, 2 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    for (size_t k = 0; k < m; ++k) {
-        out[0] += (int64_t)b->stage[2 * k];
-        out[1] += (int64_t)b->stage[2 * k + 1];
-    }
-    return RRT_OK;
-}
-
-// ---- keep a finished tree when the map changes (rrt_keep.h) ----
-// Adopts the context's current grid for query q and installs the view of the vertices that still hang on the root through edges
-// that are free on it.  Every call starts from the whole tree of the query.  A call refused for its arguments changes nothing.  Past
-// that, a view the query had is dropped together with the grid it was built for (drop_keep_views), so a call that fails half way
-// leaves a query that was kept before refused by goals_decide, never answered from the whole tree on a grid that cut it.
-static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
-    rrt_ctx *ctx = b->ctx;
-    if (!n_alive) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (b->flags & RRT_FLAG_DUBINS)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its edges are Dubins words between poses; these kernels test straight lines)", who);
-    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
-    const QDesc &d = b->h_desc[(size_t)q];
-    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
-        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
-                    d.status == ST_IDLE      ? "no query set"
-                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
-                    : d.status == ST_NEED_UB ? "it waits for its unit-ball stream"
-                                             : "its launch failed");
-    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid has another shape than the batch was created for (%dx%d)", who, b->gridW, b->gridH);
-    const int j = d.j;
-    if (j < 0 || j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, j, b->n_cap);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    drop_keep_views(b, q);
-    b->keep_timed = false;
-    const size_t cap = ((size_t)b->n_cap + 7) & ~(size_t)7;
-    if (!b->d_keep_tmp) HIPCHK(ctx, hipMalloc((void **)&b->d_keep_tmp, cap * 10 + 8));
-    if (!b->d_keep[(size_t)q]) HIPCHK(ctx, hipMalloc((void **)&b->d_keep[(size_t)q], (size_t)b->n_cap * 16));
-    for (hipEvent_t &e : b->ev_keep)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    int32_t *anc[2] = {reinterpret_cast<int32_t *>(b->d_keep_tmp), reinterpret_cast<int32_t *>(b->d_keep_tmp) + cap};
-    uint8_t *ok[2] = {b->d_keep_tmp + cap * 8, b->d_keep_tmp + cap * 9};
-    int32_t *d_count = reinterpret_cast<int32_t *>(b->d_keep_tmp + cap * 10);
-    int32_t count = 0;
-    if (j > 0) {
-        KeepView kv{};
-        kv.og = ctx->og;
-        kv.H = ctx->H;
-        kv.nodes = b->d_nodes + (size_t)q * b->node_stride;
-        kv.parent = b->d_parent + (size_t)q * b->node_stride;
-        kv.vcost = b->d_vcost + (size_t)q * b->node_stride;
-        kv.j = j;
-        kv.ok = ok[0];
-        kv.anc = anc[0];
-        const int per_wg = KEEP_TPB / 64;
-        const unsigned edge_wgs = (unsigned)((j + per_wg - 1) / per_wg > KEEP_MAX_WG ? KEEP_MAX_WG : (j + per_wg - 1) / per_wg);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[0], ctx->stream));
-        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
-                           ctx->stream, kv);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[1], ctx->stream));
-        // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
-        int rounds = 1;
-        while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
-        int cur = 0;
-        for (int r = 0; r < rounds; ++r, cur ^= 1)
-            hipLaunchKernelGGL(rrt_keep_jump_kernel, dim3((unsigned)((j + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, (const uint8_t *)ok[cur],
-                               (const int32_t *)anc[cur], ok[cur ^ 1], anc[cur ^ 1], j);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[2], ctx->stream));
-        KeepCompact kc{};
-        kc.nodes = kv.nodes;
-        kc.vcost = kv.vcost;
-        kc.ok = ok[cur];
-        kc.anc = anc[cur];
-        kc.j = j;
-        kc.alive = ok[cur ^ 1];
-        kc.live_vcost = reinterpret_cast<double *>(b->d_keep[(size_t)q]);
-        kc.live_nodes = reinterpret_cast<uint32_t *>(kc.live_vcost + b->n_cap);
-        kc.live_id = reinterpret_cast<int32_t *>(kc.live_nodes + b->n_cap);
-        kc.count = d_count;
-        hipLaunchKernelGGL(rrt_keep_compact_kernel, dim3(1), dim3(TPB), 0, ctx->stream, kc);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[3], ctx->stream));
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
-        if (alive) HIPCHK(ctx, hipMemcpyAsync(alive, kc.alive, (size_t)j, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, wait_stream_spin(ctx->stream));
-        if (count < 0 || count > j) return fail(ctx, RRT_E_HIP, "%s: %d of %d vertices alive", who, count, j);
-        b->keep_timed = true;
-    }
-    b->ran_gen[(size_t)q] = ctx->grid_gen;
-    b->ran_og[(size_t)q] = ctx->og;
-    b->keep_alive[(size_t)q] = count;
-    b->route_rows = -1;  // the rows of an earlier routes call belong to another view
-    *n_alive = count;
-    return RRT_OK;
-}
-
-extern "C" int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
-    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree: NULL");
-    return keep_tree("rrt_batch_keep_tree", b, q, n_alive, alive);
-}
-
-extern "C" int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_keep_tree: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_keep_tree: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
-    return keep_tree("rrt_plan_keep_tree", ctx->single, 0, n_alive, alive);
-}
-
-extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree_ms: NULL");
-    if (!b->keep_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_keep_tree_ms: no rrt_batch_keep_tree on this batch yet, or its last one failed");
-    for (int k = 0; k < 3; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_keep[k], b->ev_keep[k + 1]));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_keep_tree_ms: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_keep_tree_ms: no rrt_plan on this context yet, or its batch is gone");
-    return rrt_batch_keep_tree_ms(ctx->single, ms);
-}
-
-extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
-    if (!ctx || !j) return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: NULL");
-    rrt_batch *s = ctx->single;
-    if (!s || (s->h_desc[0].status != ST_DONE && s->h_desc[0].status != ST_UNREACHABLE))
-        return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
-    *j = s->h_desc[0].j;
-    return RRT_OK;
-}
-
-
-// ---- grow a finished tree with new samples (rrt_seed.h) ----
-// The seed kernels turn the finished tree of query q -- the view of its alive vertices, if it was kept on a new map -- into the loop
-// state the expansion kernels resume from, and the descriptor is armed as a loop that stopped at iteration j0 of j0 + m:
-//     D->n = j0 + m,  D->i = D->j = j0,  status RUNNING,  statistics zero,  the m samples at rows [j0, j0 + m) of the sample buffer.
-// i != 0 keeps rrt_init_kernel away; every expansion kernel reads (i, j) from the descriptor and samples[i] by absolute row, and
-// none of them depends on i == 0 or on i being a multiple of its block ("Growing a finished tree").  rrt_batch_sync puts
-// the query's own n back (grow_n).  A refusal changes nothing; past the refusals a failure leaves the query idle.
-static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0) {
-    rrt_ctx *ctx = b->ctx;
-    if (!j0_out || !log0 || (m > 0 && !samples_xy)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (b->flags & RRT_FLAG_DUBINS)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (the seed kernels carry no headings)", who);
-    if (b->flags & RRT_FLAG_REWIRE)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_REWIRE (its kernel keeps child lists, which the seed does not rebuild)", who);
-    if (b->flags & RRT_FLAG_LARGE_GRID)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_LARGE_GRID", who);
-    if (q < 0 || q >= b->Q) return fail(ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q);
-    QDesc &d = b->h_desc[(size_t)q];
-    if (d.status != ST_DONE && d.status != ST_UNREACHABLE)
-        return fail(ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
-                    d.status == ST_IDLE      ? "no query set"
-                    : d.status == ST_RUNNING ? "not launched, or launched and not synchronised"
-                    : d.status == ST_NEED_UB ? "it waits for its unit-ball stream"
-                                             : "its launch failed");
-    if (d.alg == RRT_ALG_INFORMED)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d is an Informed RRT* query (its ellipse state is not rebuilt); RRTStandard and RRTStar only", who, q);
-    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid changed shape since the batch was created (%dx%d)", who, b->gridW, b->gridH);
-    if (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og)
-        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now) and the tree was not kept "
-                    "on it (rrt_batch_keep_tree)", who, q, (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen);
-    if (m < 0) return fail(ctx, RRT_E_ARG, "%s: m=%d", who, m);
-    const int32_t kept = b->keep_alive[(size_t)q];
-    const int j_old = d.j, own_n = d.n;
-    if (j_old < 1 || j_old > b->n_cap || own_n < 1 || own_n > b->n_cap)
-        return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices of %d, capacity %d", who, q, j_old, own_n, b->n_cap);
-    if (kept == 0) return fail(ctx, RRT_E_ARG, "%s: no vertex of query %d is alive on this grid (the root is blocked): there is nothing to grow from", who, q);
-    const int j0 = kept > 0 ? (kept <= j_old ? kept : j_old) : j_old;
-    if ((long long)j0 + m > own_n)
-        return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j0, m, own_n, own_n - j0);
-    const int W = ctx->W, H = ctx->H;
-    for (int k = 0; k < m; ++k) {
-        const int x = samples_xy[2 * k], y = samples_xy[2 * k + 1];
-        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: sample %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
-    }
-    b->stage.resize((size_t)m);  // (past the last refusal: the staging buffer is the first thing of the batch this call touches)
-    for (int k = 0; k < m; ++k)
-        b->stage[(size_t)k] = ((uint32_t)samples_xy[2 * k] & 0xffffu) | ((uint32_t)samples_xy[2 * k + 1] << 16);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t cap = (size_t)b->n_cap;
-    if (!b->d_seed_tmp) HIPCHK(ctx, hipMalloc((void **)&b->d_seed_tmp, (2 * cap + 2) * sizeof(int32_t)));
-    for (hipEvent_t &e : b->ev_seed)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    // ---- from here on the query is being replaced ----
-    b->seed_timed = false;
-    b->route_rows = -1;
-    d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
-    SeedView sv{};
-    sv.nodes = b->d_nodes + (size_t)q * b->node_stride;
-    sv.vcost = b->d_vcost + (size_t)q * b->node_stride;
-    sv.parent = b->d_parent + (size_t)q * b->node_stride;
-    sv.j_old = j_old;
-    sv.j0 = j0;
-    sv.node_stride = b->node_stride;
-    sv.rank = reinterpret_cast<int32_t *>(b->d_seed_tmp);
-    sv.new_parent = sv.rank + cap;
-    sv.err = sv.rank + 2 * cap;
-    sv.bitmap = b->d_bitmap + (size_t)q * b->bitmap_words;
-    sv.bitmap_words = b->bitmap_words;
-    sv.H = H;
-    if (kept > 0) {
-        sv.live_vcost = reinterpret_cast<const double *>(b->d_keep[(size_t)q]);
-        sv.live_nodes = reinterpret_cast<const uint32_t *>(sv.live_vcost + b->n_cap);
-        sv.live_id = reinterpret_cast<const int32_t *>(sv.live_nodes + b->n_cap);
-    }
-    auto blocks = [](int items) { return dim3((unsigned)((items + SEED_TPB - 1) / SEED_TPB)); };
-    HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[0], ctx->stream));
-    if (sv.live_id) {
-        HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)j_old * sizeof(int32_t), ctx->stream));
-        hipLaunchKernelGGL(rrt_seed_rank_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
-        hipLaunchKernelGGL(rrt_seed_parent_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
-    }
-    hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[1], ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
-    if (j0 > 1) hipLaunchKernelGGL(rrt_seed_bitmap_kernel, blocks(j0 - 1), dim3(SEED_TPB), 0, ctx->stream, sv);
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[2], ctx->stream));
-    if (b->d_cellcnt) {  // (a batch without cell records, RRT_FLAG_SERIAL: its kernel scans the node array)
-        SeedRecords sr{};
-        sr.nodes = sv.nodes;
-        sr.vcost = sv.vcost;
-        sr.j0 = j0;
-        sr.cshift = d.cell_shift;
-        sr.ncx = d.ncx;
-        sr.ncy = d.ncy;
-        sr.ccap = d.cell_cap;
-        sr.rec_stride = b->rec_stride;
-        sr.cellrec = reinterpret_cast<u32x4 *>(b->d_cellrec) + (size_t)q * (size_t)b->rec_stride;
-        sr.cellcnt = b->d_cellcnt + (size_t)q * (size_t)MAX_CELLS;
-        sr.err = sv.err;
-        hipLaunchKernelGGL(rrt_seed_records_kernel, dim3(SEED_WG), dim3(SEED_TPB), 0, ctx->stream, sr);
-    }
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[3], ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    if (old_id) {
-        if (sv.live_id) HIPCHK(ctx, hipMemcpyAsync(old_id, sv.live_id, (size_t)j0 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        else
-            for (int k = 0; k < j0; ++k) old_id[k] = k;
-    }
-    if (m > 0)
-        HIPCHK(ctx, hipMemcpyAsync(b->d_samples + (size_t)q * b->n_cap + j0, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    drop_keep_views(b, q);  // the view is used up: the tree arrays hold its vertices now
-    if (err) {
-        HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, wait_stream_spin(ctx->stream));
-        return fail(ctx, RRT_E_HIP, "%s: the tree of query %d on the device is not one the seed can place (a parent that is not alive, a vertex outside the "
-                    "record grid or a cell past its capacity): the query is left without a tree", who, q);
-    }
-    arm_desc(d);
-    d.n = j0 + m;
-    d.i = d.j = j0;
-    d.i_switch = own_n;
-    b->grow_n[(size_t)q] = own_n;
-    b->grow_gen[(size_t)q] = ctx->grid_gen;
-    b->grow_og[(size_t)q] = ctx->og;
-    HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    b->seed_timed = true;
-    *j0_out = j0;
-    *log0 = j0;
-    return RRT_OK;
-}
-
-extern "C" int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
-    return batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0);
-}
-
-extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
-    if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
-    if (!b->seed_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
-    for (int k = 0; k < count; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_seed[k], b->ev_seed[k + 1]));
-    return RRT_OK;
-}
-
-// ---- finished routes to many goals (rrt_routes.h) ----
-static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
-                        double *length, int64_t *offsets) {
-    rrt_ctx *ctx = b->ctx;
-    b->route_rows = -1;  // whatever happens below, the rows of an earlier call are gone
-    if (flags & ~(uint32_t)RRT_ROUTES_SHORTCUT) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_ROUTES_SHORTCUT is defined", who, flags);
-    if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost || !length || !offsets); rc != RRT_OK) return rc;
-    if (m == 0) {
-        offsets[0] = 0;
-        b->route_rows = 0;
-        return RRT_OK;
-    }
-    if (m > b->route_goal_cap) {
-        b->route_goal_cap = 0;
-        if (b->d_route_goal) HIPCHK(ctx, hipFree(b->d_route_goal));
-        b->d_route_goal = nullptr;
-        // [length f64 m | raw_off i64 m+1 | fin_off i64 m+1 | cnt i32 m | kept i32 m | err i32]
-        HIPCHK(ctx, hipMalloc((void **)&b->d_route_goal, (size_t)m * 32 + 2 * sizeof(int64_t) + sizeof(int32_t)));
-        b->route_goal_cap = m;
-    }
-    const bool cut = (flags & RRT_ROUTES_SHORTCUT) != 0;
-    const size_t cap = (size_t)b->route_goal_cap;
-    RoutesView rv{};
-    rv.og = ctx->og;
-    rv.H = ctx->H;
-    rv.nodes = b->d_nodes + (size_t)q * b->node_stride;
-    rv.parent = b->d_parent + (size_t)q * b->node_stride;
-    rv.j = b->h_desc[(size_t)q].j;
-    rv.goals = b->d_goals;
-    rv.vertex = b->d_goal_vertex;
-    rv.m = m;
-    rv.length = reinterpret_cast<double *>(b->d_route_goal);
-    rv.raw_off = reinterpret_cast<int64_t *>(rv.length + cap);
-    rv.fin_off = cut ? rv.raw_off + cap + 1 : rv.raw_off;
-    rv.cnt = reinterpret_cast<int32_t *>(rv.raw_off + 2 * (cap + 1));
-    rv.kept = rv.cnt + cap;
-    rv.err = rv.kept + cap;
-    const unsigned lanes_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB), waves_grid = (unsigned)((m + ROUTE_TPB / 64 - 1) / (ROUTE_TPB / 64));
-    HIPCHK(ctx, hipMemsetAsync(rv.err, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.cnt, rv.raw_off, m);
-    HIPCHK(ctx, hipGetLastError());
-    // the one wait that the sizes force: the rows of all routes together decide how much memory the rows need
-    int64_t raw_rows = 0;
-    int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&raw_rows, rv.raw_off + m, sizeof raw_rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&err, rv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (err)
-        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
-    if (raw_rows < 0 || (uint64_t)raw_rows > ROUTE_ROW_BUDGET)
-        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d goals have %lld rows together, at most %zu per call: pass fewer goals at a time", who, m,
-                    (long long)raw_rows, ROUTE_ROW_BUDGET);
-    if (raw_rows > b->route_row_cap) {
-        b->route_row_cap = 0;
-        if (b->d_route_rows) HIPCHK(ctx, hipFree(b->d_route_rows));
-        b->d_route_rows = nullptr;
-        // [row_xy u32 | row_id i32 | out_xy i32 x 2 | out_id i32], each of raw_rows (shortcuts only ever drop rows)
-        HIPCHK(ctx, hipMalloc((void **)&b->d_route_rows, (size_t)raw_rows * 5 * sizeof(int32_t)));
-        b->route_row_cap = raw_rows;
-    }
-    const size_t rcap = (size_t)b->route_row_cap;
-    rv.row_xy = reinterpret_cast<uint32_t *>(b->d_route_rows);
-    rv.row_id = reinterpret_cast<int32_t *>(rv.row_xy + rcap);
-    rv.out_xy = rv.row_id + rcap;
-    rv.out_id = rv.out_xy + 2 * rcap;
-    hipLaunchKernelGGL(rrt_route_fill_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv, cut ? 0 : 1);
-    if (cut) {
-        const unsigned wgs = (unsigned)(m < ROUTE_CUT_MAX_WG ? m : ROUTE_CUT_MAX_WG);
-        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_route_cut_large_kernel : rrt_route_cut_kernel, dim3(wgs), dim3(TPB), 0, ctx->stream, rv);
-        hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.kept, rv.fin_off, m);
-    }
-    hipLaunchKernelGGL(rrt_route_pack_kernel, dim3(waves_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(vertex, b->d_goal_vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cost, b->d_goal_cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(length, rv.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(offsets, rv.fin_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (offsets[m] < 0 || offsets[m] > raw_rows) return fail(ctx, RRT_E_HIP, "%s: %lld rows kept of %lld", who, (long long)offsets[m], (long long)raw_rows);
-    b->route_rows = offsets[m];
-    return RRT_OK;
-}
-
-static int batch_routes_rows(const char *who, rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
-    rrt_ctx *ctx = b->ctx;
-    if (b->route_rows < 0)
-        return fail(ctx, RRT_E_ARG, "%s: no routes on this batch (no rrt_batch_routes call yet, one that failed, or a launch or rearm since)", who);
-    if (rows != b->route_rows) return fail(ctx, RRT_E_ARG, "%s: rows=%lld, the last rrt_batch_routes call left %lld", who, (long long)rows, (long long)b->route_rows);
-    if (rows == 0) return RRT_OK;
-    if (!xy || !id) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int32_t *out_xy = reinterpret_cast<int32_t *>(b->d_route_rows) + 2 * (size_t)b->route_row_cap;
-    HIPCHK(ctx, hipMemcpyAsync(xy, out_xy, (size_t)rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(id, out_xy + 2 * (size_t)b->route_row_cap, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    return RRT_OK;
-}
-
-extern "C" int rrt_batch_routes(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
-                                int64_t *offsets) {
-    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_routes: NULL");
-    return batch_routes("rrt_batch_routes", b, q, goals_xy, m, flags, vertex, cost, length, offsets);
-}
-
-extern "C" int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
-    if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_routes_rows: NULL");
-    return batch_routes_rows("rrt_batch_routes_rows", b, xy, id, rows);
-}
-
-extern "C" int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_routes: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_routes: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
-    return batch_routes("rrt_plan_routes", ctx->single, 0, goals_xy, m, flags, vertex, cost, length, offsets);
-}
-
-extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_routes_rows: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_routes_rows: no routes (no rrt_plan on this context yet, or its batch is gone)");
-    return batch_routes_rows("rrt_plan_routes_rows", ctx->single, xy, id, rows);
-}
-
 extern "C" int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]) {
     if (!b || !out || q < 0 || q >= b->Q) return fail(nullptr, RRT_E_ARG, "rrt_batch_debug_cycles: bad argument");
     for (int k = 0; k < 6; ++k) out[k] = b->h_desc[(size_t)q].cyc[k];
@@ -2221,7 +1373,7 @@ static int ensure_single(rrt_ctx *ctx, int32_t n, uint32_t flags) {
     return RRT_OK;
 }
 
-static int run_single(rrt_ctx *ctx, rrt_result *out) {
+int run_single(rrt_ctx *ctx, rrt_result *out) {
     rrt_batch *s = ctx->single;
     int rc = rrt_batch_launch(s);
     if (rc != RRT_OK) return rc;
@@ -2250,21 +1402,6 @@ extern "C" int rrt_plan_resume(rrt_ctx *ctx, const double *unitball, int32_t cou
     int rc = rrt_batch_set_unitball(s, 0, unitball, count, s->h_desc[0].i);
     if (rc != RRT_OK) return rc;
     return run_single(ctx, out);
-}
-
-extern "C" int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    if (!ctx || !out) return fail(ctx, RRT_E_ARG, "rrt_plan_grow: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_grow: query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)");
-    int32_t log0 = 0;
-    const int rc = batch_grow("rrt_plan_grow", ctx->single, 0, samples_xy, m, j0, old_id, &log0);
-    if (rc != RRT_OK) return rc;
-    return run_single(ctx, out);
-}
-
-extern "C" int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count) {
-    if (!ctx) return fail(nullptr, RRT_E_ARG, "rrt_plan_grow_ms: NULL");
-    if (!ctx->single) return fail(ctx, RRT_E_ARG, "rrt_plan_grow_ms: no rrt_plan on this context yet, or its batch is gone");
-    return rrt_batch_grow_ms(ctx->single, ms, count);
 }
 
 extern "C" int rrt_plan_batch(rrt_ctx *ctx, int32_t Q, const rrt_query *queries, rrt_result *out) {

@@ -1,0 +1,613 @@
+// rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
+// routes, keep_tree, grow and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h, rrt_pose_goals.h,
+// rrt_routes.h, rrt_keep.h and rrt_seed.h.  What the calls share comes first and is written once: the refusals (refuse_*), the
+// pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the batch behind rrt_plan.
+#include "rrt_engine.h"
+
+// ---- the gate: a finished tree on the grid it belongs to ----
+// Every call makes these in this order, after the refusals that are its own (NULL, the batch's flags).  0: not refused.
+static int refuse_q(const char *who, rrt_batch *b, int32_t q) {
+    return q < 0 || q >= b->Q ? fail(b->ctx, RRT_E_ARG, "%s: q=%d of %d", who, q, b->Q) : RRT_OK;
+}
+
+static int refuse_unfinished(const char *who, rrt_batch *b, int32_t q) {
+    const int32_t status = b->h_desc[(size_t)q].status;
+    if (status == ST_DONE || status == ST_UNREACHABLE) return RRT_OK;
+    return fail(b->ctx, RRT_E_ARG, "%s: query %d has not finished (%s): its tree is not complete", who, q,
+                status == ST_IDLE      ? "no query set"
+                : status == ST_RUNNING ? "not launched, or launched and not synchronised"
+                : status == ST_NEED_UB ? "it waits for its unit-ball stream"
+                                       : "its launch failed");
+}
+
+// The grid's shape, then its generation.  how: what the call says happened to the shape; so: what a replaced grid means for the call,
+// nullptr for the call that adopts the new grid and so never asks (rrt_batch_keep_tree).
+static int refuse_grid(const char *who, rrt_batch *b, int32_t q, const char *how = "changed shape since the batch was created",
+                       const char *so = ": the tree belongs to the other grid") {
+    rrt_ctx *ctx = b->ctx;
+    if (!ctx->og || b->gridW != ctx->W || b->gridH != ctx->H)
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid %s (%dx%d)", who, how, b->gridW, b->gridH);
+    if (so && (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og))
+        return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now)%s", who, q,
+                    (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen, so);
+    return RRT_OK;
+}
+
+// rrt_batch_connect_goals and rrt_batch_connect_poses: q, the number of goals (`goals`: what the call names them), then the tree
+static int refuse_goals_call(const char *who, rrt_batch *b, int32_t q, int32_t m, const char *goals) {
+    if (const int rc = refuse_q(who, b, q)) return rc;
+    if (m < 0 || m > GOALS_MAX) return fail(b->ctx, RRT_E_ARG, "%s: m=%d, at most %d %s per call", who, m, GOALS_MAX, goals);
+    if (const int rc = refuse_unfinished(who, b, q)) return rc;
+    return refuse_grid(who, b, q);
+}
+
+// ---- the tree of one query: its arrays in the batch's slab, and its kept view (rrt_keep.h) ----
+struct TreeRef {
+    uint32_t *nodes;  // [node_stride] each
+    double *vcost;
+    int32_t *parent;
+    uint8_t *heading;     // (nullptr unless the batch is a Dubins batch)
+    double *live_vcost;   // [n_cap] each: the alive vertices, dense and in the original order (nullptr before the query's first keep_tree)
+    uint32_t *live_nodes;
+    int32_t *live_id;     // ... and the original number of each
+    int32_t kept;         // vertices of the view, at most the tree's j; -1: no view, the calls see the whole tree
+};
+
+static TreeRef tree_ref(rrt_batch *b, int32_t q) {
+    const size_t at = (size_t)q * b->node_stride;
+    TreeRef t{b->d_nodes + at, b->d_vcost + at, b->d_parent + at, b->d_heading ? b->d_heading + at : nullptr};
+    if (b->keep[(size_t)q].p) {
+        t.live_vcost = b->keep[(size_t)q].as<double>();
+        t.live_nodes = reinterpret_cast<uint32_t *>(t.live_vcost + b->n_cap);
+        t.live_id = reinterpret_cast<int32_t *>(t.live_nodes + b->n_cap);
+    }
+    t.kept = std::min(b->keep_alive[(size_t)q], b->h_desc[(size_t)q].j);
+    return t;
+}
+
+// ---- the scratch of the goals and poses calls ----
+static_assert(POSES_MAX == GOALS_MAX && POSES_MAX_SLABS == GOALS_MAX_SLABS && POSES_SLAB_BUDGET == GOALS_SLAB_BUDGET,
+              "rrt_batch_connect_goals and rrt_batch_connect_poses share the batch's scratch and its limits");
+
+// Room for m goals (m >= 1): their packed cells, vertex and cost, and the order slabs.  One slab of n_cap words per workgroup, at most
+// GOALS_MAX_SLABS of them and GOALS_SLAB_BUDGET bytes, never fewer than one nor more than goals: `slabs` is the grid of the launch.
+static hipError_t goal_scratch(rrt_batch *b, int32_t m, int &slabs) {
+    const size_t fit = GOALS_SLAB_BUDGET / ((size_t)b->n_cap * sizeof(uint32_t));
+    slabs = (int)std::clamp<size_t>(fit, 1, std::min<size_t>(GOALS_MAX_SLABS, (size_t)m));
+    hipError_t e = hipSetDevice(b->ctx->device);
+    if (e == hipSuccess) e = b->goal_order.reserve(slabs, (size_t)slabs * (size_t)b->n_cap * sizeof(uint32_t));
+    if (e == hipSuccess) e = b->goal_xy.reserve(m, (size_t)m * sizeof(uint32_t));
+    if (e == hipSuccess) e = b->goal_vertex.reserve(m, (size_t)m * sizeof(int32_t));
+    if (e == hipSuccess) e = b->goal_cost.reserve(m, (size_t)m * sizeof(double));
+    return e;
+}
+
+// vertex and cost of the m goals the last kernel decided, to the caller; waits for the stream (also: the staging buffers are reused)
+static int fetch_goal_answers(rrt_batch *b, int32_t m, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    HIPCHK(ctx, hipMemcpyAsync(vertex, b->goal_vertex.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cost, b->goal_cost.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    return RRT_OK;
+}
+
+// ---- the batch behind rrt_plan ----
+// nullptr: refused with RRT_E_ARG and the message recorded, for a NULL context, or for no batch, which `sentence` puts in the call's words
+static rrt_batch *plan_batch(rrt_ctx *ctx, const char *who, const char *sentence) {
+    if (!ctx) fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    else if (!ctx->single) fail(ctx, RRT_E_ARG, "%s: %s", who, sentence);
+    return ctx ? ctx->single : nullptr;
+}
+static const char NO_PLAN[] = "no rrt_plan on this context yet, or its batch is gone";
+static const char NO_PLAN_NO_TREE[] = "query 0 has not finished (no rrt_plan on this context yet, or its batch is gone)";
+
+// ---- many goals against a finished tree (rrt_goals.h) ----
+// The part that rrt_batch_connect_goals and rrt_batch_routes share: every refusal, the goals packed and uploaded, the scratch of the
+// first call, and the goals kernel launched on the context's stream.  Nothing is read back and nothing waited for: vertex and cost
+// of the m goals are in b->goal_vertex / b->goal_cost once the stream gets there.  m == 0: RRT_OK, nothing launched.
+static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, bool null_out) {
+    rrt_ctx *ctx = b->ctx;
+    if (!goals_xy || null_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (an edge to a goal is a Dubins word to a goal pose; these kernels price straight lines)", who);
+    if (const int rc = refuse_goals_call(who, b, q, m, "goals")) return rc;
+    const QDesc &d = b->h_desc[(size_t)q];
+    const int W = ctx->W, H = ctx->H;
+    b->stage.resize((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        const int x = goals_xy[2 * k], y = goals_xy[2 * k + 1];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
+    }
+    if (m == 0) return RRT_OK;
+    int slabs = 0;
+    HIPCHK(ctx, goal_scratch(b, m, slabs));
+    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    // a query that was kept on this grid (rrt_batch_keep_tree): the decision over the view of its alive vertices, dense and in the
+    // original order; the kernel answers in indices of the view, rrt_keep_remap_kernel turns them into the original ones
+    const TreeRef t = tree_ref(b, q);
+    const bool view = t.kept >= 0;
+    GoalsView gv{};
+    gv.og = ctx->og;
+    gv.H = H;
+    gv.nodes = view ? t.live_nodes : t.nodes;
+    gv.vcost = view ? t.live_vcost : t.vcost;
+    gv.j = view ? t.kept : d.j;
+    gv.goals = b->goal_xy.as<uint32_t>();
+    gv.m = m;
+    gv.order = b->goal_order.as<uint32_t>();
+    gv.slab_words = b->n_cap;
+    gv.vertex = b->goal_vertex.as<int32_t>();
+    gv.cost = b->goal_cost.as<double>();
+    HIPCHK(ctx, hipMemcpyAsync(b->goal_xy.p, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
+    if (view)
+        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, gv.vertex,
+                           (const int32_t *)t.live_id, m, gv.j);
+    HIPCHK(ctx, hipGetLastError());
+    return RRT_OK;
+}
+
+static int connect_goals(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost); rc != RRT_OK || m == 0) return rc;
+    return fetch_goal_answers(b, m, vertex, cost);
+}
+
+extern "C" int rrt_batch_connect_goals(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    return b ? connect_goals("rrt_batch_connect_goals", b, q, goals_xy, m, vertex, cost) : fail(nullptr, RRT_E_ARG, "rrt_batch_connect_goals: NULL");
+}
+
+extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, int32_t *vertex, double *cost) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_connect_goals", NO_PLAN_NO_TREE);
+    return s ? connect_goals("rrt_plan_connect_goals", s, 0, goals_xy, m, vertex, cost) : RRT_E_ARG;
+}
+
+// ---- many goal poses against a finished Dubins tree (rrt_pose_goals.h) ----
+// The conditions are goals_decide's, for a batch created with RRT_FLAG_DUBINS; a goal is a pose (x, y, h), h < the query's nh.
+static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    if (!poses_xyh || !vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (!(b->flags & RRT_FLAG_DUBINS))
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use rrt_batch_connect_goals)", who);
+    if (const int rc = refuse_goals_call(who, b, q, m, "goal poses")) return rc;
+    const QDesc &d = b->h_desc[(size_t)q];
+    const int W = ctx->W, H = ctx->H;
+    if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
+    b->stage.resize((size_t)m);
+    b->stage8.resize((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        const int x = poses_xyh[3 * k], y = poses_xyh[3 * k + 1], h = poses_xyh[3 * k + 2];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+        if (h < 0 || h >= d.nh) return fail(ctx, RRT_E_ARG, "%s: goal %d has heading %d, query %d has headings [0, %d)", who, k, h, q, d.nh);
+        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
+        b->stage8[(size_t)k] = (uint8_t)h;
+    }
+    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    b->pose_last_m = m == 0 ? 0 : -1;  // (-1 until this call has succeeded: the counters are being rewritten)
+    if (m == 0) return RRT_OK;
+    int slabs = 0;
+    HIPCHK(ctx, goal_scratch(b, m, slabs));
+    HIPCHK(ctx, b->pose_h.reserve(m, (size_t)m));
+    HIPCHK(ctx, b->pose_counts.reserve(m, (size_t)m * 2 * sizeof(uint32_t)));
+    const TreeRef t = tree_ref(b, q);
+    PoseGoalsView pv{};
+    pv.og = ctx->og;
+    pv.W = W;
+    pv.H = H;
+    pv.nodes = t.nodes;
+    pv.vcost = t.vcost;
+    pv.heading = t.heading;
+    pv.j = d.j;
+    pv.nh = d.nh;
+    pv.rho = d.rho;
+    pv.goals = b->goal_xy.as<uint32_t>();
+    pv.goal_h = b->pose_h.as<uint8_t>();
+    pv.m = m;
+    pv.slab_words = b->n_cap;
+    pv.order = b->goal_order.as<uint32_t>();
+    pv.vertex = b->goal_vertex.as<int32_t>();
+    pv.cost = b->goal_cost.as<double>();
+    pv.counts = b->pose_counts.as<uint32_t>();
+    HIPCHK(ctx, hipMemcpyAsync(b->goal_xy.p, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b->pose_h.p, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
+    HIPCHK(ctx, hipGetLastError());
+    if (const int rc = fetch_goal_answers(b, m, vertex, cost)) return rc;
+    b->pose_last_m = m;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_connect_poses(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    return b ? connect_poses("rrt_batch_connect_poses", b, q, poses_xyh, m, vertex, cost) : fail(nullptr, RRT_E_ARG, "rrt_batch_connect_poses: NULL");
+}
+
+extern "C" int rrt_plan_connect_poses(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_connect_poses", NO_PLAN_NO_TREE);
+    return s ? connect_poses("rrt_plan_connect_poses", s, 0, poses_xyh, m, vertex, cost) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_connect_poses_counts(rrt_batch *b, int64_t out[2]) {
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_connect_poses_counts: NULL");
+    rrt_ctx *ctx = b->ctx;
+    if (b->pose_last_m < 0) return fail(ctx, RRT_E_ARG, "rrt_batch_connect_poses_counts: no rrt_batch_connect_poses on this batch yet, or its last one failed");
+    out[0] = out[1] = 0;
+    const size_t m = (size_t)b->pose_last_m;
+    if (m == 0) return RRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    b->stage.resize(2 * m);
+    HIPCHK(ctx, hipMemcpyAsync(b->stage.data(), b->pose_counts.p, 2 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    for (size_t k = 0; k < m; ++k) {
+        out[0] += (int64_t)b->stage[2 * k];
+        out[1] += (int64_t)b->stage[2 * k + 1];
+    }
+    return RRT_OK;
+}
+
+// ---- keep a finished tree when the map changes (rrt_keep.h) ----
+// Adopts the context's current grid for query q and installs the view of the vertices that still hang on the root through edges
+// that are free on it.  Every call starts from the whole tree of the query.  A call refused for its arguments changes nothing.  Past
+// that, a view the query had is dropped together with the grid it was built for (drop_keep_views), so a call that fails half way
+// leaves a query that was kept before refused by goals_decide, never answered from the whole tree on a grid that cut it.
+static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
+    rrt_ctx *ctx = b->ctx;
+    if (!n_alive) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its edges are Dubins words between poses; these kernels test straight lines)", who);
+    if (const int rc = refuse_q(who, b, q)) return rc;
+    if (const int rc = refuse_unfinished(who, b, q)) return rc;
+    if (const int rc = refuse_grid(who, b, q, "has another shape than the batch was created for", nullptr)) return rc;
+    const int j = b->h_desc[(size_t)q].j;
+    if (j < 0 || j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, j, b->n_cap);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    drop_keep_views(b, q);
+    b->keep_timed = false;
+    const size_t cap = ((size_t)b->n_cap + 7) & ~(size_t)7;
+    HIPCHK(ctx, b->keep_tmp.reserve(1, cap * 10 + 8));
+    HIPCHK(ctx, b->keep[(size_t)q].reserve(1, (size_t)b->n_cap * 16));
+    for (hipEvent_t &e : b->ev_keep)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    int32_t *anc[2] = {b->keep_tmp.as<int32_t>(), b->keep_tmp.as<int32_t>() + cap};
+    uint8_t *ok[2] = {b->keep_tmp.as<uint8_t>() + cap * 8, b->keep_tmp.as<uint8_t>() + cap * 9};
+    int32_t *d_count = reinterpret_cast<int32_t *>(ok[1] + cap);
+    int32_t count = 0;
+    if (j > 0) {
+        const TreeRef t = tree_ref(b, q);
+        KeepView kv{};
+        kv.og = ctx->og;
+        kv.H = ctx->H;
+        kv.nodes = t.nodes;
+        kv.parent = t.parent;
+        kv.vcost = t.vcost;
+        kv.j = j;
+        kv.ok = ok[0];
+        kv.anc = anc[0];
+        const int per_wg = KEEP_TPB / 64;
+        const unsigned edge_wgs = (unsigned)((j + per_wg - 1) / per_wg > KEEP_MAX_WG ? KEEP_MAX_WG : (j + per_wg - 1) / per_wg);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[0], ctx->stream));
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
+                           ctx->stream, kv);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[1], ctx->stream));
+        // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
+        int rounds = 1;
+        while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
+        int cur = 0;
+        for (int r = 0; r < rounds; ++r, cur ^= 1)
+            hipLaunchKernelGGL(rrt_keep_jump_kernel, dim3((unsigned)((j + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, (const uint8_t *)ok[cur],
+                               (const int32_t *)anc[cur], ok[cur ^ 1], anc[cur ^ 1], j);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[2], ctx->stream));
+        KeepCompact kc{};
+        kc.nodes = kv.nodes;
+        kc.vcost = kv.vcost;
+        kc.ok = ok[cur];
+        kc.anc = anc[cur];
+        kc.j = j;
+        kc.alive = ok[cur ^ 1];
+        kc.live_vcost = t.live_vcost;
+        kc.live_nodes = t.live_nodes;
+        kc.live_id = t.live_id;
+        kc.count = d_count;
+        hipLaunchKernelGGL(rrt_keep_compact_kernel, dim3(1), dim3(TPB), 0, ctx->stream, kc);
+        HIPCHK(ctx, hipEventRecord(b->ev_keep[3], ctx->stream));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        if (alive) HIPCHK(ctx, hipMemcpyAsync(alive, kc.alive, (size_t)j, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        if (count < 0 || count > j) return fail(ctx, RRT_E_HIP, "%s: %d of %d vertices alive", who, count, j);
+        b->keep_timed = true;
+    }
+    b->ran_gen[(size_t)q] = ctx->grid_gen;
+    b->ran_og[(size_t)q] = ctx->og;
+    b->keep_alive[(size_t)q] = count;
+    b->route_rows = -1;  // the rows of an earlier routes call belong to another view
+    *n_alive = count;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
+    return b ? keep_tree("rrt_batch_keep_tree", b, q, n_alive, alive) : fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree: NULL");
+}
+
+extern "C" int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_keep_tree", NO_PLAN_NO_TREE);
+    return s ? keep_tree("rrt_plan_keep_tree", s, 0, n_alive, alive) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree_ms: NULL");
+    if (!b->keep_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_keep_tree_ms: no rrt_batch_keep_tree on this batch yet, or its last one failed");
+    for (int k = 0; k < 3; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_keep[k], b->ev_keep[k + 1]));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_keep_tree_ms", NO_PLAN);
+    return s ? rrt_batch_keep_tree_ms(s, ms) : RRT_E_ARG;
+}
+
+extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
+    if (!ctx || !j) return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: NULL");
+    rrt_batch *s = ctx->single;
+    if (!s || (s->h_desc[0].status != ST_DONE && s->h_desc[0].status != ST_UNREACHABLE))
+        return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: %s", NO_PLAN_NO_TREE);
+    *j = s->h_desc[0].j;
+    return RRT_OK;
+}
+
+// ---- grow a finished tree with new samples (rrt_seed.h) ----
+// The seed kernels turn the finished tree of query q -- the view of its alive vertices, if it was kept on a new map -- into the loop
+// state the expansion kernels resume from, and the descriptor is armed as a loop that stopped at iteration j0 of j0 + m:
+//     D->n = j0 + m,  D->i = D->j = j0,  status RUNNING,  statistics zero,  the m samples at rows [j0, j0 + m) of the sample buffer.
+// i != 0 keeps rrt_init_kernel away; every expansion kernel reads (i, j) from the descriptor and samples[i] by absolute row, and
+// none of them depends on i == 0 or on i being a multiple of its block ("Growing a finished tree").  rrt_batch_sync puts
+// the query's own n back (grow_n).  A refusal changes nothing; past the refusals a failure leaves the query idle.
+static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0) {
+    rrt_ctx *ctx = b->ctx;
+    if (!j0_out || !log0 || (m > 0 && !samples_xy)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (the seed kernels carry no headings)", who);
+    if (b->flags & RRT_FLAG_REWIRE)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_REWIRE (its kernel keeps child lists, which the seed does not rebuild)", who);
+    if (b->flags & RRT_FLAG_LARGE_GRID)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_LARGE_GRID", who);
+    if (const int rc = refuse_q(who, b, q)) return rc;
+    if (const int rc = refuse_unfinished(who, b, q)) return rc;
+    QDesc &d = b->h_desc[(size_t)q];
+    if (d.alg == RRT_ALG_INFORMED)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d is an Informed RRT* query (its ellipse state is not rebuilt); RRTStandard and RRTStar only", who, q);
+    if (const int rc = refuse_grid(who, b, q, "changed shape since the batch was created", " and the tree was not kept on it (rrt_batch_keep_tree)")) return rc;
+    if (m < 0) return fail(ctx, RRT_E_ARG, "%s: m=%d", who, m);
+    const int j_old = d.j, own_n = d.n;
+    if (j_old < 1 || j_old > b->n_cap || own_n < 1 || own_n > b->n_cap)
+        return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices of %d, capacity %d", who, q, j_old, own_n, b->n_cap);
+    const TreeRef t = tree_ref(b, q);
+    if (t.kept == 0) return fail(ctx, RRT_E_ARG, "%s: no vertex of query %d is alive on this grid (the root is blocked): there is nothing to grow from", who, q);
+    const int j0 = t.kept > 0 ? t.kept : j_old;
+    if ((long long)j0 + m > own_n)
+        return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j0, m, own_n, own_n - j0);
+    const int W = ctx->W, H = ctx->H;
+    for (int k = 0; k < m; ++k) {
+        const int x = samples_xy[2 * k], y = samples_xy[2 * k + 1];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: sample %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+    }
+    b->stage.resize((size_t)m);  // (past the last refusal: the staging buffer is the first thing of the batch this call touches)
+    for (int k = 0; k < m; ++k)
+        b->stage[(size_t)k] = ((uint32_t)samples_xy[2 * k] & 0xffffu) | ((uint32_t)samples_xy[2 * k + 1] << 16);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t cap = (size_t)b->n_cap;
+    HIPCHK(ctx, b->seed_tmp.reserve(1, (2 * cap + 2) * sizeof(int32_t)));
+    for (hipEvent_t &e : b->ev_seed)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    // ---- from here on the query is being replaced ----
+    b->seed_timed = false;
+    b->route_rows = -1;
+    d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
+    SeedView sv{};
+    sv.nodes = t.nodes;
+    sv.vcost = t.vcost;
+    sv.parent = t.parent;
+    sv.j_old = j_old;
+    sv.j0 = j0;
+    sv.node_stride = b->node_stride;
+    sv.rank = b->seed_tmp.as<int32_t>();
+    sv.new_parent = sv.rank + cap;
+    sv.err = sv.rank + 2 * cap;
+    sv.bitmap = b->d_bitmap + (size_t)q * b->bitmap_words;
+    sv.bitmap_words = b->bitmap_words;
+    sv.H = H;
+    sv.live_vcost = t.kept > 0 ? t.live_vcost : nullptr;
+    sv.live_nodes = t.kept > 0 ? t.live_nodes : nullptr;
+    sv.live_id = t.kept > 0 ? t.live_id : nullptr;
+    auto blocks = [](int items) { return dim3((unsigned)((items + SEED_TPB - 1) / SEED_TPB)); };
+    HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[0], ctx->stream));
+    if (sv.live_id) {
+        HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)j_old * sizeof(int32_t), ctx->stream));
+        hipLaunchKernelGGL(rrt_seed_rank_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
+        hipLaunchKernelGGL(rrt_seed_parent_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
+    }
+    hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[1], ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
+    if (j0 > 1) hipLaunchKernelGGL(rrt_seed_bitmap_kernel, blocks(j0 - 1), dim3(SEED_TPB), 0, ctx->stream, sv);
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[2], ctx->stream));
+    if (b->d_cellcnt) {  // (a batch without cell records, RRT_FLAG_SERIAL: its kernel scans the node array)
+        SeedRecords sr{};
+        sr.nodes = sv.nodes;
+        sr.vcost = sv.vcost;
+        sr.j0 = j0;
+        sr.cshift = d.cell_shift;
+        sr.ncx = d.ncx;
+        sr.ncy = d.ncy;
+        sr.ccap = d.cell_cap;
+        sr.rec_stride = b->rec_stride;
+        sr.cellrec = reinterpret_cast<u32x4 *>(b->d_cellrec) + (size_t)q * (size_t)b->rec_stride;
+        sr.cellcnt = b->d_cellcnt + (size_t)q * (size_t)MAX_CELLS;
+        sr.err = sv.err;
+        hipLaunchKernelGGL(rrt_seed_records_kernel, dim3(SEED_WG), dim3(SEED_TPB), 0, ctx->stream, sr);
+    }
+    HIPCHK(ctx, hipEventRecord(b->ev_seed[3], ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    if (old_id) {
+        if (sv.live_id) HIPCHK(ctx, hipMemcpyAsync(old_id, sv.live_id, (size_t)j0 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        else
+            for (int k = 0; k < j0; ++k) old_id[k] = k;
+    }
+    if (m > 0)
+        HIPCHK(ctx, hipMemcpyAsync(b->d_samples + (size_t)q * b->n_cap + j0, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    drop_keep_views(b, q);  // the view is used up: the tree arrays hold its vertices now
+    if (err) {
+        HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        return fail(ctx, RRT_E_HIP, "%s: the tree of query %d on the device is not one the seed can place (a parent that is not alive, a vertex outside the "
+                    "record grid or a cell past its capacity): the query is left without a tree", who, q);
+    }
+    arm_desc(d);
+    d.n = j0 + m;
+    d.i = d.j = j0;
+    d.i_switch = own_n;
+    b->grow_n[(size_t)q] = own_n;
+    b->grow_gen[(size_t)q] = ctx->grid_gen;
+    b->grow_og[(size_t)q] = ctx->og;
+    HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    b->seed_timed = true;
+    *j0_out = j0;
+    *log0 = j0;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
+    return b ? batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
+}
+
+extern "C" int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    if (ctx && !out) return fail(ctx, RRT_E_ARG, "rrt_plan_grow: NULL");
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_grow", NO_PLAN_NO_TREE);
+    if (!s) return RRT_E_ARG;
+    int32_t log0 = 0;
+    const int rc = batch_grow("rrt_plan_grow", s, 0, samples_xy, m, j0, old_id, &log0);
+    return rc != RRT_OK ? rc : run_single(ctx, out);
+}
+
+extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
+    if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
+    if (!b->seed_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
+    for (int k = 0; k < count; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_seed[k], b->ev_seed[k + 1]));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_grow_ms", NO_PLAN);
+    return s ? rrt_batch_grow_ms(s, ms, count) : RRT_E_ARG;
+}
+
+// ---- finished routes to many goals (rrt_routes.h) ----
+static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
+                        double *length, int64_t *offsets) {
+    rrt_ctx *ctx = b->ctx;
+    b->route_rows = -1;  // whatever happens below, the rows of an earlier call are gone
+    if (flags & ~(uint32_t)RRT_ROUTES_SHORTCUT) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_ROUTES_SHORTCUT is defined", who, flags);
+    if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost || !length || !offsets); rc != RRT_OK) return rc;
+    if (m == 0) {
+        offsets[0] = 0;
+        b->route_rows = 0;
+        return RRT_OK;
+    }
+    // [length f64 m | raw_off i64 m+1 | fin_off i64 m+1 | cnt i32 m | kept i32 m | err i32]
+    HIPCHK(ctx, b->route_goal.reserve(m, (size_t)m * 32 + 2 * sizeof(int64_t) + sizeof(int32_t)));
+    const bool cut = (flags & RRT_ROUTES_SHORTCUT) != 0;
+    const size_t cap = (size_t)b->route_goal.cap;
+    const TreeRef t = tree_ref(b, q);
+    RoutesView rv{};
+    rv.og = ctx->og;
+    rv.H = ctx->H;
+    rv.nodes = t.nodes;
+    rv.parent = t.parent;
+    rv.j = b->h_desc[(size_t)q].j;
+    rv.goals = b->goal_xy.as<uint32_t>();
+    rv.vertex = b->goal_vertex.as<int32_t>();
+    rv.m = m;
+    rv.length = b->route_goal.as<double>();
+    rv.raw_off = reinterpret_cast<int64_t *>(rv.length + cap);
+    rv.fin_off = cut ? rv.raw_off + cap + 1 : rv.raw_off;
+    rv.cnt = reinterpret_cast<int32_t *>(rv.raw_off + 2 * (cap + 1));
+    rv.kept = rv.cnt + cap;
+    rv.err = rv.kept + cap;
+    const unsigned lanes_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB), waves_grid = (unsigned)((m + ROUTE_TPB / 64 - 1) / (ROUTE_TPB / 64));
+    HIPCHK(ctx, hipMemsetAsync(rv.err, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.cnt, rv.raw_off, m);
+    HIPCHK(ctx, hipGetLastError());
+    // the one wait that the sizes force: the rows of all routes together decide how much memory the rows need
+    int64_t raw_rows = 0;
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&raw_rows, rv.raw_off + m, sizeof raw_rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, rv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err)
+        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
+    if (raw_rows < 0 || (uint64_t)raw_rows > ROUTE_ROW_BUDGET)
+        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d goals have %lld rows together, at most %zu per call: pass fewer goals at a time", who, m,
+                    (long long)raw_rows, ROUTE_ROW_BUDGET);
+    // [row_xy u32 | row_id i32 | out_xy i32 x 2 | out_id i32], each of raw_rows (shortcuts only ever drop rows)
+    HIPCHK(ctx, b->route_row.reserve(raw_rows, (size_t)raw_rows * 5 * sizeof(int32_t)));
+    const size_t rcap = (size_t)b->route_row.cap;
+    rv.row_xy = b->route_row.as<uint32_t>();
+    rv.row_id = reinterpret_cast<int32_t *>(rv.row_xy + rcap);
+    rv.out_xy = rv.row_id + rcap;
+    rv.out_id = rv.out_xy + 2 * rcap;
+    hipLaunchKernelGGL(rrt_route_fill_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv, cut ? 0 : 1);
+    if (cut) {
+        const unsigned wgs = (unsigned)(m < ROUTE_CUT_MAX_WG ? m : ROUTE_CUT_MAX_WG);
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_route_cut_large_kernel : rrt_route_cut_kernel, dim3(wgs), dim3(TPB), 0, ctx->stream, rv);
+        hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.kept, rv.fin_off, m);
+    }
+    hipLaunchKernelGGL(rrt_route_pack_kernel, dim3(waves_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(length, rv.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(offsets, rv.fin_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (const int rc = fetch_goal_answers(b, m, vertex, cost)) return rc;
+    if (offsets[m] < 0 || offsets[m] > raw_rows) return fail(ctx, RRT_E_HIP, "%s: %lld rows kept of %lld", who, (long long)offsets[m], (long long)raw_rows);
+    b->route_rows = offsets[m];
+    return RRT_OK;
+}
+
+static int batch_routes_rows(const char *who, rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
+    rrt_ctx *ctx = b->ctx;
+    if (b->route_rows < 0)
+        return fail(ctx, RRT_E_ARG, "%s: no routes on this batch (no rrt_batch_routes call yet, one that failed, or a launch or rearm since)", who);
+    if (rows != b->route_rows) return fail(ctx, RRT_E_ARG, "%s: rows=%lld, the last rrt_batch_routes call left %lld", who, (long long)rows, (long long)b->route_rows);
+    if (rows == 0) return RRT_OK;
+    if (!xy || !id) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t rcap = (size_t)b->route_row.cap;
+    const int32_t *out_xy = b->route_row.as<int32_t>() + 2 * rcap;
+    HIPCHK(ctx, hipMemcpyAsync(xy, out_xy, (size_t)rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(id, out_xy + 2 * rcap, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_routes(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                                int64_t *offsets) {
+    return b ? batch_routes("rrt_batch_routes", b, q, goals_xy, m, flags, vertex, cost, length, offsets) : fail(nullptr, RRT_E_ARG, "rrt_batch_routes: NULL");
+}
+
+extern "C" int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
+    return b ? batch_routes_rows("rrt_batch_routes_rows", b, xy, id, rows) : fail(nullptr, RRT_E_ARG, "rrt_batch_routes_rows: NULL");
+}
+
+extern "C" int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_routes", NO_PLAN_NO_TREE);
+    return s ? batch_routes("rrt_plan_routes", s, 0, goals_xy, m, flags, vertex, cost, length, offsets) : RRT_E_ARG;
+}
+
+extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_routes_rows", "no routes (no rrt_plan on this context yet, or its batch is gone)");
+    return s ? batch_routes_rows("rrt_plan_routes_rows", s, xy, id, rows) : RRT_E_ARG;
+}
