@@ -1,34 +1,30 @@
 // kernels_tu.hip -- the definitions of the expansion kernels, dealt to translation units (make passes -DRRT_TU=k) so that they
-// compile side by side; rrt_engine.hip only launches them.  No unit calls device code of another, so the objects link without
-// relocatable device code.
+// compile side by side; the host units only launch them, through the declarations of rrt_kernel_abi.h.  No unit calls device code of
+// another, so the objects link without relocatable device code.
 #include <hip/hip_runtime.h>
 
 #if RRT_TU == 1  // one CU per query, no barrier in the loop (RRTStandard / RRTStar)
-#define RRT_BLOCK_DECL_ONLY
-#define RRT_SERIAL_DECL_ONLY
 #include "rrt_pipe.h"
 
 #elif RRT_TU == 4  // the same pipeline for grids up to 4096 x 4096 (RRT_FLAG_LARGE_GRID): rrt_pipe_large_kernel
-#define RRT_BLOCK_DECL_ONLY
-#define RRT_SERIAL_DECL_ONLY
 #define RRT_PIPE_LARGE_TU
 #include "rrt_pipe.h"
 
 #elif RRT_TU == 2  // Dubins planners: the pipeline, and the one-sample-per-iteration kernel kept as its cross-check
 #include "rrt_dubins_block.h"
+#include "rrt_serial.h"
 namespace rrtdev {
 template __global__ void rrt_expand_kernel<false, true>(BatchView);
 }
 
 #elif RRT_TU == 3  // one sample per iteration: cross-check of the block kernel, and the opt-in true rewire
-#include "rrt_kernels.h"
+#include "rrt_serial.h"
 namespace rrtdev {
 template __global__ void rrt_expand_kernel<false, false>(BatchView);
 template __global__ void rrt_expand_kernel<true, false>(BatchView);
 }
 
 #elif RRT_TU == 5  // many goals against a finished tree (rrt_goals_kernel, rrt_goals_large_kernel): not a team kernel
-#define RRT_SERIAL_DECL_ONLY
 #include "rrt_goals.h"
 
 #elif RRT_TU == 6  // finished routes to many goals, with line-of-sight shortcuts (rrt_route_*_kernel): not a team kernel
@@ -38,17 +34,13 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #include "rrt_keep.h"
 
 #elif RRT_TU == 8  // grow a finished tree: its loop state rebuilt from the alive vertices (rrt_seed_*_kernel): not a team kernel
-#define RRT_SERIAL_DECL_ONLY
 #include "rrt_seed.h"
 
 #elif RRT_TU == 9  // many goal poses against a finished Dubins tree (rrt_pose_goals_kernel): not a team kernel
-#define RRT_SERIAL_DECL_ONLY
 #include "rrt_pose_goals.h"
 
-#else  // teams of compute units: the variants that rrt_block_variants.def deals to this unit
-#define RRT_SERIAL_DECL_ONLY
+#else  // teams of compute units: the variants that rrt_block_variants.def (included by rrt_block.h) deals to this unit
 #include "rrt_block.h"
-#include "rrt_block_variants.def"
 namespace rrtdev {
 #define K(G, BSM, PIPE, INF) template __global__ void rrt_expand_block_kernel<G, BSM, PIPE, INF>(BatchView);
 // a pipelined team as two kernels: the committer (8 waves, 256 vector registers) and the workers

@@ -29,7 +29,7 @@
 //      -- member 0 publishes the new state; barrier --
 #pragma once
 
-#include "rrt_kernels.h"
+#include "rrt_go2goal.h"
 #include "rrt_cell_stream.h"
 
 namespace rrtdev {
@@ -53,7 +53,6 @@ constexpr int BS = 16;  // most samples one workgroup resolves per pass (see BSM
 // that only commits, the workers two blocks ahead of it.  All members must be resident together (the launch keeps teams x members <= CUs); every spin is bounded
 // by a wall-clock limit that fails the query (status ST_TEAM_FAIL, the host then continues it with one CU) instead of
 // hanging the device.
-constexpr int TEAM_MAX = 64;
 #ifndef RRT_PIPE_LAG
 #define RRT_PIPE_LAG 2  // blocks a pipelined team's workers run ahead of the commit (a batch without Informed queries)
 #endif
@@ -66,26 +65,6 @@ constexpr int TEAM_MAX = 64;
 #ifndef RRT_PIPE_LAG_INF
 #define RRT_PIPE_LAG_INF 2  // ... when the batch may hold Informed queries (a commit that moves the ellipse voids the blocks in flight)
 #endif
-#ifndef RRT_NPMAX
-#define RRT_NPMAX 2  // most blocks in flight a record can carry interaction masks for (>= both RRT_PIPE_LAG values)
-#endif
-constexpr int NPMAX = RRT_NPMAX;
-// Owners on big teams (a group of waves per sample) also test the lines of sight from every sample IN FLIGHT within r_rewire to
-// their sample -- positions come from the sample stream, not from the tree -- and hand the answers over as a list of up to PL_MAX
-// 16-bit entries, so that the committer settles "an inserted sample in flight is a cheaper parent" (nine in ten of the samples a
-// commit has to look at again) lane-parallel, without a line-of-sight test of its own.  Entry: bits 0-5 sample, 6-7 set (0 = oldest
-// previous block ... NP = this block), 8-14 cells the test read, 15 free; order: oldest block first, sample order = node order.
-#ifndef RRT_PL_MAX
-#define RRT_PL_MAX 12
-#endif
-constexpr int PL_MAX = RRT_PL_MAX, PL_WORDS = (RRT_PL_MAX + 3) / 4;
-constexpr int BREC_WORDS = 10 + 3 * NPMAX + PL_WORDS;  // 8-byte words of an owner's record (BRec below): 152 bytes for two blocks in flight
-// per query: [go | fail | state (NPMAX + 1 slots of 64 bytes) | records (NPMAX + 1 slots of 64) | arrival flags (65 x 128) | go2goal answers (65 x 16)]
-constexpr int TEAM_OFF_GO = 128, TEAM_OFF_FAIL = 256, TEAM_OFF_STATE = 384, TEAM_OFF_REC = 1024;
-constexpr int TEAM_OFF_ARRIVE = (TEAM_OFF_REC + (NPMAX + 1) * 64 * BREC_WORDS * 8 + 127) / 128 * 128;
-constexpr int TEAM_OFF_RES = TEAM_OFF_ARRIVE + 65 * 128;
-constexpr int TEAM_BYTES = (TEAM_OFF_RES + 65 * 16 + 1023) / 1024 * 1024;
-static_assert(TEAM_OFF_STATE + (NPMAX + 1) * 64 <= TEAM_OFF_REC, "state slots");
 constexpr unsigned long long TEAM_TIMEOUT_TICKS = 50000000ull;  // 0.5 s of the 100 MHz wall clock
 
 typedef unsigned long long u64;
@@ -175,43 +154,6 @@ __device__ __forceinline__ bool team_wait(gu32 *word, uint32_t target, gu32 *fai
         }
         __builtin_amdgcn_s_sleep(4);
     }
-}
-
-// exact sqrt of an integer below 2^24 (0 included): rsq seed + coupled Goldschmidt / Newton steps in
-// f64.  tests/test_gpu_parity.py checks every input against the host's correctly rounded sqrt.
-__device__ __forceinline__ double sqrt_u24(uint32_t d2) {
-    const double x = (double)d2;
-    double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    return d2 == 0 ? 0.0 : g;
-}
-
-// The same for an integer below 2^25 (grids up to 4096 x 4096, the large-grid pipeline of rrt_pipe.h).  The coupled step leaves g and h
-// with relative errors of the order of the seed's squared (~2^-50); each correction g += (x - g*g) * h squares the error again, so
-// the first leaves g within an ulp and the later ones can only move it onto the correctly rounded root (x - g*g is exact in the
-// fma, and the root of an integer is never half way between two doubles).  One correction more than sqrt_u24: nothing in the
-// argument depends on x < 2^24, but that bound is all its test covers.  tests/test_large_grid_gpu.py checks every input below 2^25.
-__device__ __forceinline__ double sqrt_u25(uint32_t d2) {
-    const double x = (double)d2;
-    double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    return d2 == 0 ? 0.0 : g;
 }
 
 // key = 256*d2 + tag of one node against one sample (both pre-scaled by 16): v_pk_sub_i16 + v_dot2_i32_i16.
@@ -506,10 +448,7 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
 #endif
 
 #if defined(RRT_STAMPS)
-    // wall-clock stamp of event ev of block ep (32 blocks of the run from RRT_TS_BASE on), by one lane
-#ifndef RRT_TS_BASE
-#define RRT_TS_BASE 300
-#endif
+    // wall-clock stamp of event ev of block ep (32 blocks of the run from RRT_TS_BASE on, rrt_kernel_abi.h), by one lane
 #define TSMARK(ep, ev)                                                                                          \
     do {                                                                                                        \
         if ((int)(ep) >= RRT_TS_BASE && (int)(ep) < RRT_TS_BASE + 32 && lane == 0) D->ts[((int)(ep) - RRT_TS_BASE) * 16 + (ev)] = wall_clock64(); \
@@ -958,14 +897,9 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
 #endif
 }
 
-// (RRT_BLOCK_DECL_ONLY: a translation unit that only launches the kernel; csrc/kernels_tu.hip holds the instantiations, dealt to
-//  several translation units so that they compile side by side)
+// (csrc/kernels_tu.hip holds the instantiations, dealt to several translation units so that they compile side by side)
 template <int G, int BSM, bool PIPE, bool INF>
-__global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv)
-#ifdef RRT_BLOCK_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv) {
     __shared__ BlockLds<G, BSM, PIPE, INF> L;
     if constexpr (PIPE) {
 #if defined(RRT_ONLY_ROLE) && RRT_ONLY_ROLE == 1  // (resource analysis of one role; never run)
@@ -980,7 +914,6 @@ __global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv)
         rrt_block_body<G, BSM, PIPE, INF, ROLE_ALL>(bv, L);
     }
 }
-#endif
 
 // The two halves of a pipelined team of 8 and more workers as two kernels, launched on two streams of the context (the default;
 // RRT_FLAG_ONEBODY keeps rrt_expand_block_kernel).  Register allocation is per kernel: the committer, a workgroup of 8 waves, gets
@@ -988,25 +921,17 @@ __global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv)
 // compiled without the committer's code.  The committer kernel has one workgroup per team (blockIdx.x = query slot), the workers'
 // kernel team_qpad * G of them, launched with bv.member0 = 1.
 template <int G, int BSM, bool INF>
-__global__ __launch_bounds__(512) void rrt_block_commit_kernel(BatchView bv)
-#ifdef RRT_BLOCK_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(512) void rrt_block_commit_kernel(BatchView bv) {
     __shared__ BlockLds<G, BSM, true, INF> L;
     rrt_block_body<G, BSM, true, INF, ROLE_COMMIT, 8>(bv, L);
 }
-#endif
 
 template <int G, int BSM, bool INF>
-__global__ __launch_bounds__(TPB) void rrt_block_work_kernel(BatchView bv)
-#ifdef RRT_BLOCK_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_block_work_kernel(BatchView bv) {
     __shared__ BlockLds<G, BSM, true, INF> L;
     rrt_block_body<G, BSM, true, INF, ROLE_WORK>(bv, L);
 }
-#endif
 
 }  // namespace rrtdev
+
+#include "rrt_block_variants.def"  // which of them exist, and the unit each is dealt to

@@ -1,24 +1,15 @@
-// rrt_device.h -- device-side building blocks shared by the kernels of rrt_engine.hip.
+// rrt_device.h -- device-side building blocks shared by the kernel files and by the engine's own kernels (rrt_prims.h): wave
+// reductions, the exact roots, the lines of sight, the per-wave near-set lists.  The structs and constants that the host shares
+// with the kernels come with rrt_kernel_abi.h.
 // gfx950 only (wave64, DPP row_bcast, v_pk_sub_i16 / v_dot2c_i32_i16).
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "rrt_kernel_abi.h"
 #include "rrt_line.h"
 
 namespace rrtdev {
 
-constexpr int TPB = 1024;          // threads of one query workgroup (16 waves, one CU)
-constexpr int NWAVE = TPB / 64;
-constexpr int CHUNK = TPB * 4;     // nodes per scan chunk: one 16-byte load per thread
-constexpr int MAX_LDS_CHUNKS = 8;  // node chunks cached in LDS (8 * 16 KiB = 128 KiB)
-constexpr int WSLOTS = 3;          // near-set entries a lane prices in registers
-constexpr int WCAP = 64 * WSLOTS;  // near-set entries per wave in LDS (16 waves * 1.5 KiB)
-constexpr uint32_t NONE = 0xffffffffu;
-
 typedef short short2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 // explicit address spaces: LDS accesses must be ds_* instructions, never flat_* (a pointer
 // select between LDS and HBM silently degrades to flat loads with full waits)
@@ -112,6 +103,43 @@ __device__ __forceinline__ bool key_lt(double c1, uint32_t i1, double c2, uint32
 
 // r2norm of an integer difference (rrt.py:24): sqrt of an exact integer < 2^53.
 __device__ __forceinline__ double sqrt_u32(uint32_t d2) { return sqrt((double)d2); }
+
+// exact sqrt of an integer below 2^24 (0 included): rsq seed + coupled Goldschmidt / Newton steps in
+// f64.  tests/test_gpu_parity.py checks every input against the host's correctly rounded sqrt.
+__device__ __forceinline__ double sqrt_u24(uint32_t d2) {
+    const double x = (double)d2;
+    double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+    double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    double d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    return d2 == 0 ? 0.0 : g;
+}
+
+// The same for an integer below 2^25 (grids up to 4096 x 4096, the large-grid pipeline of rrt_pipe.h).  The coupled step leaves g and h
+// with relative errors of the order of the seed's squared (~2^-50); each correction g += (x - g*g) * h squares the error again, so
+// the first leaves g within an ulp and the later ones can only move it onto the correctly rounded root (x - g*g is exact in the
+// fma, and the root of an integer is never half way between two doubles).  One correction more than sqrt_u24: nothing in the
+// argument depends on x < 2^24, but that bound is all its test covers.  tests/test_large_grid_gpu.py checks every input below 2^25.
+__device__ __forceinline__ double sqrt_u25(uint32_t d2) {
+    const double x = (double)d2;
+    double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+    double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    double d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    return d2 == 0 ? 0.0 : g;
+}
 
 // A SHORT segment a -> b (fewer than 64 steps) for one cell per lane: the closed form of include/rrt_line.h with the segment's data in
 // scalar registers (a and b are wave-uniform), the cell as one byte offset into the grid, and the quotient without the fix-ups:
@@ -316,5 +344,95 @@ __device__ __forceinline__ void los_batch(const uint8_t *__restrict__ og, int H,
                                           bool (&ok)[LOSB], int (&cells)[LOSB]) {
     los_batch_n<LOSB>(og, H, a, nc, b, lane, ok, cells);
 }
+
+// Lane-local running best and second best in (cost, index) order.
+struct Top2 {
+    double c1, c2;
+    uint32_t i1, i2;
+    __device__ __forceinline__ void init() {
+        c1 = c2 = f64_inf();
+        i1 = i2 = NONE;
+    }
+    __device__ __forceinline__ void fold(double c, uint32_t i) {
+        if (key_lt(c, i, c1, i1)) {
+            c2 = c1;
+            i2 = i1;
+            c1 = c;
+            i1 = i;
+        } else if (key_lt(c, i, c2, i2)) {
+            c2 = c;
+            i2 = i;
+        }
+    }
+    // wave-wide best and second best of all lanes' entries (uniform result)
+    __device__ __forceinline__ void wave_reduce() {
+        double bc = c1;
+        uint32_t bi = i1;
+        wave_min_f64_idx(bc, bi);
+        const bool own = (c1 == bc && i1 == bi);
+        double sc = own ? c2 : c1;
+        uint32_t si = own ? i2 : i1;
+        wave_min_f64_idx(sc, si);
+        c1 = bc;
+        i1 = bi;
+        c2 = sc;
+        i2 = si;
+    }
+};
+
+// Near set of one wave: every wave keeps the within-radius nodes of its own stripe in its own LDS
+// region (WCAP entries {idx, d2}, overflow to its own HBM region) and later prices them itself, so
+// the append needs no atomics: the fill count is a wave-uniform register.
+struct WaveList {
+    RRT_LDS u32x2 *list;  // LDS [WCAP] of this wave
+    u32x2 *spill;         // HBM overflow of this wave
+};
+
+__device__ __forceinline__ void wl_store(const WaveList &wl, uint32_t pos, uint32_t idx, uint32_t d2) {
+    u32x2 v = {idx, d2};
+    if (pos < (uint32_t)WCAP) wl.list[pos] = v;
+    if (pos >= (uint32_t)WCAP) wl.spill[pos - WCAP] = v;
+}
+
+// Append the lanes flagged in h0..h3 (element e of each lane's 4-node load).  Wave-uniform control flow.
+__device__ __forceinline__ void wl_append4(const WaveList &wl, uint32_t &wcnt, bool h0, bool h1, bool h2, bool h3,
+                                           uint32_t idx0, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, int lane) {
+    const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
+    if ((m0 | m1 | m2 | m3) == 0) return;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    if (h0) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m0 & lt), idx0, d0);
+    wcnt += (uint32_t)__builtin_popcountll(m0);
+    if (h1) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m1 & lt), idx0 + 1, d1);
+    wcnt += (uint32_t)__builtin_popcountll(m1);
+    if (h2) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m2 & lt), idx0 + 2, d2);
+    wcnt += (uint32_t)__builtin_popcountll(m2);
+    if (h3) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m3 & lt), idx0 + 3, d3);
+    wcnt += (uint32_t)__builtin_popcountll(m3);
+}
+
+template <bool STAR>
+__device__ __forceinline__ void eval4(u32x4 v, uint32_t q, uint32_t tag0, uint32_t idx0, uint32_t r2, uint32_t &best,
+                                      const WaveList &wl, uint32_t &wcnt, int lane) {
+    uint32_t d0 = dist2(v.x, q), d1 = dist2(v.y, q), d2 = dist2(v.z, q), d3 = dist2(v.w, q);
+    best = min(best, (d0 << 8) + tag0);
+    best = min(best, (d1 << 8) + tag0 + 1);
+    best = min(best, (d2 << 8) + tag0 + 2);
+    best = min(best, (d3 << 8) + tag0 + 3);
+    if (STAR) wl_append4(wl, wcnt, d0 < r2, d1 < r2, d2 < r2, d3 < r2, idx0, d0, d1, d2, d3, lane);
+}
+
+// (diagnostic build) the expansion kernels' phase stamps: cycles since the last stamp go to cyc[k]; the kernel declares `cyc` and `tstamp`
+#if defined(RRT_STAMPS) && !defined(RRT_STAMPS_LIGHT)
+#define STAMP(k)                                                \
+    do {                                                        \
+        unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
+        cyc[k] += now_ - tstamp;                                \
+        tstamp = now_;                                          \
+    } while (0)
+#else
+#define STAMP(k) \
+    do {         \
+    } while (0)
+#endif
 
 }  // namespace rrtdev

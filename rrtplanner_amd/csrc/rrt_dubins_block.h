@@ -32,7 +32,7 @@
 //             with a bound below the (tightening) best cost are collected in LDS and priced 64 at a time.
 #pragma once
 
-#include "rrt_kernels.h"
+#include "rrt_go2goal.h"
 #include "rrt_cell_stream.h"
 
 #ifndef RRT_DUB_STREAM_DEPTH

@@ -18,25 +18,12 @@
 #include <tuple>
 #include <vector>
 
-// The kernels are only LAUNCHED from the host units; kernels_tu.hip holds their definitions, dealt to several translation units
-// that compile side by side (the single unit of round 3 took two and a half minutes).
-#define RRT_BLOCK_DECL_ONLY
-#define RRT_SERIAL_DECL_ONLY
+// The kernels are only LAUNCHED from the host units, through the declarations of rrt_kernel_abi.h; kernels_tu.hip holds their
+// definitions, dealt to several translation units that compile side by side (the single unit of round 3 took two and a half minutes).
+// (The engine's own small kernels -- init, primitives, tree query, noise, slab meta -- are rrt_engine.hip's: rrt_prims.h and the file itself.)
 #include "rrt_hip.h"
-#include "rrt_kernels.h"
-#include "rrt_block.h"
+#include "rrt_kernel_abi.h"
 #include "rrt_block_variants.def"
-#include "rrt_kernel_decls.h"
-#define RRT_GOALS_DECL_ONLY
-#include "rrt_goals.h"
-#define RRT_ROUTES_DECL_ONLY
-#include "rrt_routes.h"
-#define RRT_KEEP_DECL_ONLY
-#include "rrt_keep.h"
-#define RRT_SEED_DECL_ONLY
-#include "rrt_seed.h"
-#define RRT_POSES_DECL_ONLY
-#include "rrt_pose_goals.h"
 
 using namespace rrtdev;
 

@@ -1,4 +1,4 @@
-// rrt_engine.hip -- C ABI (include/rrt_hip.h) over the gfx950 kernels of rrt_kernels.h.
+// rrt_engine.hip -- C ABI (include/rrt_hip.h) over the gfx950 kernels declared in rrt_kernel_abi.h.
 // Host side: HIP memory, one stream per context, events for kernel timing.  No torch.  The calls on a finished tree: rrt_tree_calls.hip.
 #include "rrt_engine.h"
 #include "rrt_prims.h"

@@ -9,36 +9,17 @@
 //   The reference's fall-backs for that case (vgoal = 0, the IndexError) belong to plan() and are not reproduced.
 //
 // One workgroup of TPB threads decides one goal at a time, goals g = blockIdx.x, blockIdx.x + gridDim.x, ..., by go2goal_phase
-// (rrt_kernels.h), the decision plan() itself takes; its `order` scratch is this workgroup's slab.
+// (rrt_go2goal.h), the decision plan() itself takes; its `order` scratch is this workgroup's slab.
 // (A first stage in front of it -- one pass for the (cost, index)-smallest vertex and one line of sight, the answer if that line is
 // free -- was measured and lost: 17.4 ms against 15.9 ms per 4096 goals at bench scale, where the cheapest vertex sees one goal in
 // eight.  profiles/goals_wall.json has both numbers, tools/archive/goals_first_stage.patch the code.)
-// (RRT_GOALS_DECL_ONLY: a translation unit that only launches the kernels; csrc/kernels_tu.hip defines them)
+// (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_kernels.h"
+#include "rrt_go2goal.h"
 
 namespace rrtdev {
 
-constexpr int GOALS_MAX_SLABS = 512;                    // workgroups of a launch == `order` slabs of n_cap words each
-constexpr size_t GOALS_SLAB_BUDGET = (size_t)128 << 20; // bytes of slabs a batch may hold (never fewer than one slab)
-constexpr int GOALS_MAX = 1 << 20;                      // goals of one call
-
-struct GoalsView {
-    const uint8_t *og;      // (W,H) x-major occupancy, != 0 is obstacle
-    int32_t H;
-    const uint32_t *nodes;  // the query's packed vertices
-    const double *vcost;
-    int32_t j;              // vertices considered: [0, j)
-    const uint32_t *goals;  // [m] packed like vertices
-    int32_t m;
-    uint32_t *order;        // [gridDim.x][slab_words] go2goal_phase's scratch, one slab per workgroup
-    int32_t slab_words;     // >= j
-    int32_t *vertex;        // [m] out: the vertex the goal connects to, or -1
-    double *cost;           // [m] out: the cost of the goal through it, or +inf
-};
-
-#ifndef RRT_GOALS_DECL_ONLY
 template <bool LARGE>
 __device__ __forceinline__ void goals_body(const GoalsView &gv, RRT_LDS uint32_t *lds16k, BSlot *bslots) {
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -63,29 +44,18 @@ __device__ __forceinline__ void goals_body(const GoalsView &gv, RRT_LDS uint32_t
         __syncthreads();  // the next goal rewrites the slots and tables that slower waves may still be reading
     }
 }
-#endif
 
-__global__ __launch_bounds__(TPB) void rrt_goals_kernel(GoalsView gv)
-#ifdef RRT_GOALS_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_goals_kernel(GoalsView gv) {
     __shared__ __attribute__((aligned(16))) uint32_t lds16k[2 * G2G_NB];
     __shared__ __attribute__((aligned(16))) BSlot bslots[2 * NWAVE];
     goals_body<false>(gv, (RRT_LDS uint32_t *)lds16k, bslots);
 }
-#endif
 
 // grids up to 4096 x 4096 (a batch created with RRT_FLAG_LARGE_GRID): the lines of sight by los_wave_large
-__global__ __launch_bounds__(TPB) void rrt_goals_large_kernel(GoalsView gv)
-#ifdef RRT_GOALS_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_goals_large_kernel(GoalsView gv) {
     __shared__ __attribute__((aligned(16))) uint32_t lds16k[2 * G2G_NB];
     __shared__ __attribute__((aligned(16))) BSlot bslots[2 * NWAVE];
     goals_body<true>(gv, (RRT_LDS uint32_t *)lds16k, bslots);
 }
-#endif
 
 }  // namespace rrtdev

@@ -13,7 +13,7 @@
 // Costs are not recomputed: a surviving vertex keeps its vcost bit for bit.
 //
 // The direction of the walk.  The Bresenham walk of rrt.py:202-229 is not symmetric.  plan() tested every edge of a reference-mode
-// tree from the parent to the child (rrt_kernels.h, the nearest / choose-parent test), so on an unchanged map every such edge is
+// tree from the parent to the child (rrt_serial.h, the nearest / choose-parent test), so on an unchanged map every such edge is
 // free here too and the view is the whole tree.  The rewire of rewire="correct" tests its new edges from the child to the new
 // parent: on such a tree a rewired edge may be cut on an unchanged map, where the walk from the parent's side crosses an occupied
 // cell that the walk from the child's side misses.  Only the one direction is tested.
@@ -28,41 +28,13 @@
 //                                  waves' counts through LDS, the carry in a register.  alive[k] = ok[k] and anc[k] == 0 (a walk
 //                                  that is not at the root after j steps belongs to no tree: not alive).
 //   4. rrt_keep_remap_kernel       vertex[g] = vertex[g] < 0 ? -1 : live_id[vertex[g]], behind the goals kernel.
-// (RRT_KEEP_DECL_ONLY: a translation unit that only launches the kernels; csrc/kernels_tu.hip defines them)
+// (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
 #include "rrt_device.h"
 
 namespace rrtdev {
 
-constexpr int KEEP_TPB = 256;       // edge test: 4 vertices a workgroup (one per wave); pointer jumping and remap: one per lane
-constexpr int KEEP_MAX_WG = 2048;   // workgroups of the edge test, grid-stride beyond
-
-struct KeepView {
-    const uint8_t *og;       // (W,H) x-major occupancy of the new map, != 0 is obstacle
-    int32_t H;
-    const uint32_t *nodes;   // the query's packed vertices
-    const int32_t *parent;
-    const double *vcost;
-    int32_t j;               // tree vertices: [0, j)
-    uint8_t *ok;             // [j] out of the edge test: edge_ok
-    int32_t *anc;            // [j] out of the edge test: the parent, 0 for the root, k itself for a parent outside [0, j)
-};
-
-struct KeepCompact {
-    const uint32_t *nodes;
-    const double *vcost;
-    const uint8_t *ok;       // [j] after the last round
-    const int32_t *anc;      // [j] after the last round
-    int32_t j;
-    uint8_t *alive;          // [j] out
-    uint32_t *live_nodes;    // [count] out, original order
-    double *live_vcost;      // [count]
-    int32_t *live_id;        // [count] the original index
-    int32_t *count;          // out
-};
-
-#ifndef RRT_KEEP_DECL_ONLY
 template <bool LARGE>
 __device__ __forceinline__ void keep_edge_body(const KeepView &kv) {
     const int lane = (int)threadIdx.x & 63;
@@ -82,47 +54,27 @@ __device__ __forceinline__ void keep_edge_body(const KeepView &kv) {
         }
     }
 }
-#endif
 
-__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_kernel(KeepView kv)
-#ifdef RRT_KEEP_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_kernel(KeepView kv) {
     keep_edge_body<false>(kv);
 }
-#endif
 
 // grids up to 4096 x 4096 (a batch created with RRT_FLAG_LARGE_GRID): the lines of sight by los_wave_large
-__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_large_kernel(KeepView kv)
-#ifdef RRT_KEEP_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_large_kernel(KeepView kv) {
     keep_edge_body<true>(kv);
 }
-#endif
 
 // one round of pointer jumping; every anc[k] is in [0, j) (the edge test wrote it so, and a round keeps it so)
-__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_jump_kernel(const uint8_t *ok, const int32_t *anc, uint8_t *ok2, int32_t *anc2, int32_t j)
-#ifdef RRT_KEEP_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_jump_kernel(const uint8_t *ok, const int32_t *anc, uint8_t *ok2, int32_t *anc2, int32_t j) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= j) return;
     const int a = anc[k];
     ok2[k] = ok[k] & ok[a];
     anc2[k] = anc[a];
 }
-#endif
 
 // order-preserving compaction of the alive vertices by ONE workgroup of TPB threads
-__global__ __launch_bounds__(TPB) void rrt_keep_compact_kernel(KeepCompact kc)
-#ifdef RRT_KEEP_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_keep_compact_kernel(KeepCompact kc) {
     __shared__ uint32_t wcnt[2][NWAVE];
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int j = kc.j;
@@ -153,19 +105,13 @@ __global__ __launch_bounds__(TPB) void rrt_keep_compact_kernel(KeepCompact kc)
     }
     if (t == 0) *kc.count = (int32_t)carry;
 }
-#endif
 
 // the goals kernel answered in indices of the view: back to the original vertex numbers
-__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_remap_kernel(int32_t *vertex, const int32_t *live_id, int32_t m, int32_t count)
-#ifdef RRT_KEEP_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_remap_kernel(int32_t *vertex, const int32_t *live_id, int32_t m, int32_t count) {
     const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (g >= m) return;
     const int v = vertex[g];
     vertex[g] = (v < 0 || v >= count) ? -1 : live_id[v];
 }
-#endif
 
 }  // namespace rrtdev

@@ -1,0 +1,282 @@
+// rrt_kernel_abi.h -- what the host units (rrt_engine.hip, rrt_tree_calls.hip) and the kernel units (kernels_tu.hip) share, and nothing
+// else: the structs a kernel takes by value, the constants the engine sizes buffers and launches by, and a declaration of every kernel
+// a host unit launches.  The definitions live in the kernel files (one per unit of kernels_tu.hip); no host unit includes those.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rrtdev {
+
+constexpr int TPB = 1024;          // threads of one query workgroup (16 waves, one CU)
+constexpr int NWAVE = TPB / 64;
+constexpr int CHUNK = TPB * 4;     // nodes per scan chunk: one 16-byte load per thread
+constexpr int MAX_LDS_CHUNKS = 8;  // node chunks cached in LDS (8 * 16 KiB = 128 KiB)
+constexpr int WSLOTS = 3;          // near-set entries a lane prices in registers
+constexpr int WCAP = 64 * WSLOTS;  // near-set entries per wave in LDS (16 waves * 1.5 KiB)
+constexpr uint32_t NONE = 0xffffffffu;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+#ifndef RRT_TS_BASE
+#define RRT_TS_BASE 300  // diagnostic build: QDesc::ts holds the stamps of the 32 blocks of a run from this one on (TSMARK, rrt_block.h)
+#endif
+
+enum : int32_t { ST_DONE = 0, ST_NEED_UB = 1, ST_UNREACHABLE = -2, ST_TEAM_FAIL = -3, ST_RUNNING = 100, ST_IDLE = 101 };
+
+// Per-query descriptor in HBM: inputs, resumable loop state, statistics.
+struct QDesc {
+    int32_t alg, n;
+    int32_t xs[2], xg[2];
+    uint32_t r2_rewire, goal_d2;
+    double C[4];
+    int32_t ub_offset, ub_count;
+    int32_t cell_shift, ncx, ncy, cell_cap;  // block kernel: near-set record grid of this query (cell = 2^shift pixels)
+    int32_t status, i, j, nsoln, vbest_soln, vgoal, found, i_switch;
+    double cmin_soln;
+    unsigned long long sum_j, sum_cells_nn, sum_near, sum_cells_cand, n_los_cand;
+    unsigned long long wcyc[32]; // diagnostic build: per-wave cycles in the block kernel's owner phase [0..15] and its LoS part [16..31]
+    unsigned long long cyc[6];  // diagnostic build (-DRRT_STAMPS): wave-0 cycles in scan / pre-barrier / barrier / B+C / D / go2goal
+    unsigned long long n_rewired, n_propagated;  // opt-in true rewire (RRT_FLAG_REWIRE): nodes re-parented, descendant costs recomputed
+    double rho;          // Dubins planners (alg 3 / 4): turning radius in cells, number of headings, start / goal heading index
+    int32_t nh, hs, hg, pad_;
+    unsigned long long n_words;  // Dubins planners: dub_shortest() evaluations made (the byte / flop model counts one per near-set entry)
+#ifdef RRT_STAMPS
+    // diagnostic build, pipelined teams: per worker m = member - 1: [m] polls of the committer's record fetch during which m's records were
+    // still missing, [64 + m] blocks in which m was the LAST to arrive, [128 + m] the worker's own cycles in its resolve phase
+    unsigned long long dbg2[448];  // (+ [192 + m], [256 + m], [320 + m]: blocks whose resolve phase took m more than 26 k / 32 k / 40 k cycles, [384 + m]: its longest)
+    unsigned long long ts[32 * 16];  // wall-clock (10 ns) time stamps of 32 consecutive blocks, 16 events each (rrt_block.h: TSMARK)
+#endif
+};
+
+struct BatchView {
+    QDesc *desc;
+    const uint32_t *samples;  // [Q][n_cap]         packed free-space samples
+    uint32_t *nodes;          // [Q][node_stride]   packed tree nodes
+    double *vcost;            // [Q][node_stride]
+    int32_t *parent;          // [Q][node_stride]
+    uint32_t *bitmap;         // [Q][bitmap_words]  `sampled` set (rrt.py:407)
+    uint2 *spill;             // [Q][spill_stride]  per-wave near-set overflow / go2goal costs
+    const double *unitball;   // [Q][2*n_cap] or null
+    int32_t *nearest_log;     // optional logs [Q][n_cap]
+    uint8_t *accept_log;
+    double *cbest_log;
+    int32_t *j_log;
+    const uint8_t *og;        // (W,H) x-major occupancy, != 0 is obstacle
+    int32_t W, H;
+    int32_t n_cap, node_stride, bitmap_words, lds_chunks, spill_stride;
+    uint4 *cellrec;           // [Q][rec_stride]    block kernel: per-cell arrays of {xy, index, vcost} records
+    uint32_t *cellcnt;        // [Q][MAX_CELLS]     fill counts of the cells
+    int64_t rec_stride;
+    unsigned char *team;      // [Q][TEAM_BYTES]    block kernel with teams: sync words, state, exchanged records
+    int32_t Q, team_qpad;     // queries of the batch; block stride between the members of a team (block = member * team_qpad + query)
+    int32_t team_fault;       // testing: member 1 of every team leaves at once (the others' hand-offs time out)
+    int32_t member0;          // added to the member number a team kernel derives from its block index (1: a launch of the workers only)
+    // opt-in true rewire (RRT_FLAG_REWIRE; serial kernel only), null otherwise
+    int32_t *kid_first, *kid_next, *kid_prev;  // [Q][node_stride] child lists: first child, next / previous sibling (-1 = none)
+    uint32_t *frontier;                        // [Q][2 * node_stride] two propagation frontiers
+    int32_t *vsoln;                            // [Q][node_stride] Informed: solution vertices in insertion order
+    // Dubins planners (RRT_FLAG_DUBINS; serial kernel only), null otherwise
+    uint8_t *heading;               // [Q][node_stride] heading index of every node
+    const uint8_t *sample_heading;  // [Q][n_cap]       heading index of sample i
+    double *dub_path;               // [Q][NWAVE * WCAP][5] {t, p, q, len, word} of every priced near-set entry of the current iteration
+};
+
+constexpr int BLOCK_LIST_CAP = 256;                                  // block kernel, one wave per sample: parked entries per wave kept in LDS
+constexpr size_t BLOCK_LIST_LDS_BYTES = (size_t)NWAVE * BLOCK_LIST_CAP * 16;  // 64 KiB
+constexpr int MAX_CELLS = 4096;  // cells per query (their fill counts live in LDS: 16 KiB)
+
+// ---- the team area of a query (rrt_block.h, "teams"): what a record carries decides its size ----
+constexpr int TEAM_MAX = 64;
+#ifndef RRT_NPMAX
+#define RRT_NPMAX 2  // most blocks in flight a record can carry interaction masks for (>= both RRT_PIPE_LAG values)
+#endif
+constexpr int NPMAX = RRT_NPMAX;
+// Owners on big teams (a group of waves per sample) also test the lines of sight from every sample IN FLIGHT within r_rewire to
+// their sample -- positions come from the sample stream, not from the tree -- and hand the answers over as a list of up to PL_MAX
+// 16-bit entries, so that the committer settles "an inserted sample in flight is a cheaper parent" (nine in ten of the samples a
+// commit has to look at again) lane-parallel, without a line-of-sight test of its own.  Entry: bits 0-5 sample, 6-7 set (0 = oldest
+// previous block ... NP = this block), 8-14 cells the test read, 15 free; order: oldest block first, sample order = node order.
+#ifndef RRT_PL_MAX
+#define RRT_PL_MAX 12
+#endif
+constexpr int PL_MAX = RRT_PL_MAX, PL_WORDS = (RRT_PL_MAX + 3) / 4;
+constexpr int BREC_WORDS = 10 + 3 * NPMAX + PL_WORDS;  // 8-byte words of an owner's record (BRec, rrt_block.h): 152 bytes for two blocks in flight
+// per query: [go | fail | state (NPMAX + 1 slots of 64 bytes) | records (NPMAX + 1 slots of 64) | arrival flags (65 x 128) | go2goal answers (65 x 16)]
+constexpr int TEAM_OFF_GO = 128, TEAM_OFF_FAIL = 256, TEAM_OFF_STATE = 384, TEAM_OFF_REC = 1024;
+constexpr int TEAM_OFF_ARRIVE = (TEAM_OFF_REC + (NPMAX + 1) * 64 * BREC_WORDS * 8 + 127) / 128 * 128;
+constexpr int TEAM_OFF_RES = TEAM_OFF_ARRIVE + 65 * 128;
+constexpr int TEAM_BYTES = (TEAM_OFF_RES + 65 * 16 + 1023) / 1024 * 1024;
+static_assert(TEAM_OFF_STATE + (NPMAX + 1) * 64 <= TEAM_OFF_REC, "state slots");
+
+// ---- rrt_goals.h ----
+constexpr int GOALS_MAX_SLABS = 512;                    // workgroups of a launch == `order` slabs of n_cap words each
+constexpr size_t GOALS_SLAB_BUDGET = (size_t)128 << 20; // bytes of slabs a batch may hold (never fewer than one slab)
+constexpr int GOALS_MAX = 1 << 20;                      // goals of one call
+
+struct GoalsView {
+    const uint8_t *og;      // (W,H) x-major occupancy, != 0 is obstacle
+    int32_t H;
+    const uint32_t *nodes;  // the query's packed vertices
+    const double *vcost;
+    int32_t j;              // vertices considered: [0, j)
+    const uint32_t *goals;  // [m] packed like vertices
+    int32_t m;
+    uint32_t *order;        // [gridDim.x][slab_words] go2goal_phase's scratch, one slab per workgroup
+    int32_t slab_words;     // >= j
+    int32_t *vertex;        // [m] out: the vertex the goal connects to, or -1
+    double *cost;           // [m] out: the cost of the goal through it, or +inf
+};
+
+// ---- rrt_pose_goals.h ----
+constexpr int POSES_MAX_SLABS = 512;                    // workgroups of a launch == `order` slabs of n_cap words each
+constexpr size_t POSES_SLAB_BUDGET = (size_t)128 << 20; // bytes of slabs a batch may hold (never fewer than one slab)
+constexpr int POSES_MAX = 1 << 20;                      // goal poses of one call
+
+struct PoseGoalsView {
+    const uint8_t *og;       // (W,H) x-major occupancy, != 0 is obstacle
+    int32_t W, H;
+    const uint32_t *nodes;   // the query's packed vertices
+    const double *vcost;
+    const uint8_t *heading;  // ... and their heading indices
+    int32_t j;               // vertices considered: [0, j)
+    int32_t nh;              // the query's discrete headings
+    double rho;              // ... and turning radius
+    const uint32_t *goals;   // [m] cells packed like vertices
+    const uint8_t *goal_h;   // [m] heading indices, < nh
+    int32_t m;
+    int32_t slab_words;      // >= j
+    uint32_t *order;         // [gridDim.x][slab_words] the sorted vertex order, one slab per workgroup
+    int32_t *vertex;         // [m] out: the vertex the goal connects to, or -1
+    double *cost;            // [m] out: the cost of the goal through it, or +inf
+    uint32_t *counts;        // [m][2] out: words evaluated, sweeps run
+};
+
+// ---- rrt_routes.h ----
+constexpr int ROUTE_TPB = 256;                            // depth, fill and pack: goals per workgroup (lanes), or 4 goals (waves)
+constexpr int ROUTE_CUT_MAX_WG = 1024;                    // workgroups of the shortcut kernel, each loops over goals
+constexpr size_t ROUTE_ROW_BUDGET = (size_t)1 << 28;      // raw rows of one call (20 bytes of device memory each)
+
+struct RoutesView {
+    const uint8_t *og;       // (W,H) x-major occupancy, != 0 is obstacle
+    int32_t H;
+    const uint32_t *nodes;   // the query's packed vertices
+    const int32_t *parent;
+    int32_t j;               // tree vertices: [0, j)
+    const uint32_t *goals;   // [m] packed
+    const int32_t *vertex;   // [m] what the goals kernel decided
+    int32_t m;
+    int32_t *cnt;            // [m] raw rows of a goal
+    int32_t *kept;           // [m] rows after shortcutting
+    int64_t *raw_off;        // [m + 1] exclusive scan of cnt
+    int64_t *fin_off;        // [m + 1] exclusive scan of kept (== raw_off without shortcuts)
+    double *length;          // [m]
+    int32_t *err;            // != 0: a parent walk did not end at vertex 0
+    uint32_t *row_xy;        // [raw rows] packed points; the shortcut kernel rewrites the front of a goal's rows in place
+    int32_t *row_id;         // [raw rows]
+    int32_t *out_xy;         // [final rows][2]
+    int32_t *out_id;         // [final rows]
+};
+
+// ---- rrt_keep.h ----
+constexpr int KEEP_TPB = 256;       // edge test: 4 vertices a workgroup (one per wave); pointer jumping and remap: one per lane
+constexpr int KEEP_MAX_WG = 2048;   // workgroups of the edge test, grid-stride beyond
+
+struct KeepView {
+    const uint8_t *og;       // (W,H) x-major occupancy of the new map, != 0 is obstacle
+    int32_t H;
+    const uint32_t *nodes;   // the query's packed vertices
+    const int32_t *parent;
+    const double *vcost;
+    int32_t j;               // tree vertices: [0, j)
+    uint8_t *ok;             // [j] out of the edge test: edge_ok
+    int32_t *anc;            // [j] out of the edge test: the parent, 0 for the root, k itself for a parent outside [0, j)
+};
+
+struct KeepCompact {
+    const uint32_t *nodes;
+    const double *vcost;
+    const uint8_t *ok;       // [j] after the last round
+    const int32_t *anc;      // [j] after the last round
+    int32_t j;
+    uint8_t *alive;          // [j] out
+    uint32_t *live_nodes;    // [count] out, original order
+    double *live_vcost;      // [count]
+    int32_t *live_id;        // [count] the original index
+    int32_t *count;          // out
+};
+
+// ---- rrt_seed.h ----
+constexpr int SEED_TPB = 256;                             // one slot / vertex per lane; records: 4 wavefronts a workgroup
+constexpr int SEED_WG = 64;                               // workgroups of the records kernel
+constexpr int SEED_WAVES = SEED_WG * (SEED_TPB / 64);     // wavefronts that share the cells: 256
+constexpr int SEED_OWN = MAX_CELLS / SEED_WAVES;          // cells a wavefront owns: 16 (cell = slot * SEED_WAVES + wavefront)
+static_assert(SEED_OWN * SEED_WAVES == MAX_CELLS && SEED_OWN <= 64, "every cell has one owner, one count per lane at the end");
+
+struct SeedView {
+    uint32_t *nodes;             // the query's tree arrays
+    double *vcost;
+    int32_t *parent;
+    int32_t j_old, j0, node_stride;  // vertices of the finished tree, of the seed, slots of the node array
+    const uint32_t *live_nodes;  // the view (rrt_keep.h), dense; all three null without a view (then j0 == j_old)
+    const double *live_vcost;
+    const int32_t *live_id;
+    int32_t *rank;               // [j_old] scratch, filled with -1
+    int32_t *new_parent;         // [j0] scratch
+    uint32_t *bitmap;
+    int32_t bitmap_words, H;
+    int32_t *err;                // set to 1 by any kernel that met something it could not place
+};
+
+struct SeedRecords {
+    const uint32_t *nodes;
+    const double *vcost;
+    int32_t j0;
+    int32_t cshift, ncx, ncy, ccap;
+    int64_t rec_stride;
+    u32x4 *cellrec;
+    uint32_t *cellcnt;           // [MAX_CELLS]
+    int32_t *err;
+};
+
+// ---- the kernels a host unit launches, by the file that defines them ----
+// rrt_serial.h (units 2 and 3 instantiate it)
+template <bool RW, bool DUB = false>
+__global__ __launch_bounds__(TPB) void rrt_expand_kernel(BatchView bv);
+// rrt_pipe.h (unit 1; unit 4: grids up to 4096 x 4096), rrt_dubins_block.h (unit 2)
+__global__ __launch_bounds__(TPB) void rrt_pipe_kernel(BatchView bv);
+__global__ __launch_bounds__(TPB) void rrt_pipe_large_kernel(BatchView bv);
+__global__ __launch_bounds__(TPB) void rrt_dubins_block_kernel(BatchView bv);
+// rrt_block.h (units 10 and up instantiate the rows of rrt_block_variants.def)
+template <int G, int BSM, bool PIPE, bool INF>
+__global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv);
+template <int G, int BSM, bool INF>
+__global__ __launch_bounds__(512) void rrt_block_commit_kernel(BatchView bv);
+template <int G, int BSM, bool INF>
+__global__ __launch_bounds__(TPB) void rrt_block_work_kernel(BatchView bv);
+// rrt_goals.h (unit 5), rrt_pose_goals.h (unit 9)
+__global__ __launch_bounds__(TPB) void rrt_goals_kernel(GoalsView gv);
+__global__ __launch_bounds__(TPB) void rrt_goals_large_kernel(GoalsView gv);
+__global__ __launch_bounds__(TPB) void rrt_pose_goals_kernel(PoseGoalsView pv);
+// rrt_routes.h (unit 6)
+__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_depth_kernel(RoutesView rv);
+__global__ __launch_bounds__(TPB) void rrt_route_scan_kernel(const int32_t *in, int64_t *out, int32_t m);
+__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_fill_kernel(RoutesView rv, int32_t with_len);
+__global__ __launch_bounds__(TPB) void rrt_route_cut_kernel(RoutesView rv);
+__global__ __launch_bounds__(TPB) void rrt_route_cut_large_kernel(RoutesView rv);
+__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_pack_kernel(RoutesView rv);
+// rrt_keep.h (unit 7)
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_kernel(KeepView kv);
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_large_kernel(KeepView kv);
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_jump_kernel(const uint8_t *ok, const int32_t *anc, uint8_t *ok2, int32_t *anc2, int32_t j);
+__global__ __launch_bounds__(TPB) void rrt_keep_compact_kernel(KeepCompact kc);
+__global__ __launch_bounds__(KEEP_TPB) void rrt_keep_remap_kernel(int32_t *vertex, const int32_t *live_id, int32_t m, int32_t count);
+// rrt_seed.h (unit 8)
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv);
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv);
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_install_kernel(SeedView sv);
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_bitmap_kernel(SeedView sv);
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords sr);
+
+}  // namespace rrtdev

@@ -27,7 +27,7 @@
 // scalar mask operations -- the retirement cost 1 000 - 2 000 cycles per sample and decided the run time.
 #pragma once
 
-#include "rrt_block.h"
+#include "rrt_go2goal.h"
 #include "rrt_cell_stream.h"
 
 #ifndef RRT_PIPE_STREAM_DEPTH
@@ -114,7 +114,7 @@ __device__ __forceinline__ bool pp_los(const uint8_t *__restrict__ og, int H, ui
 // text rather than as a function template behind two kernels: through such a wrapper the compiler schedules the plain kernel
 // differently, and its object code is to stay what it was.
 // LARGE: coordinates below 2^12, squared distances below 2^25, rewire radii squared up to 2^26.  What differs from the plain form:
-//   - prices by sqrt_u25 (rrt_block.h) instead of sqrt_u24;
+//   - prices by sqrt_u25 (rrt_device.h) instead of sqrt_u24;
 //   - long lines of sight by los_wave_large (rrt_line_cell_u26), go2goal's included;
 //   - the stream radius is the true integer root of r2 - 1 up to r2 = 2^26 (no saturation): rad0 <= 8191, after the doubling
 //     radn <= 16383, and rad0 * rad0, radn * radn < 2^28 do not wrap;

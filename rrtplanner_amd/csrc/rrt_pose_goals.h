@@ -1,7 +1,7 @@
 // rrt_pose_goals.h -- connect many goal POSES to a finished Dubins tree: rrt_pose_goals_kernel.
 //
 // rrt_goals.h serves the straight-line planners; a Dubins goal is a pose (x, y, h) and its edge a Dubins word, so the decision is
-// go2goal_phase<DUB = true>'s (rrt_kernels.h), the one plan() takes for its own goal pose, taken for M poses against the tree a
+// go2goal_phase<DUB = true>'s (rrt_go2goal.h), the one plan() takes for its own goal pose, taken for M poses against the tree a
 // finished query left on the device:
 //
 //   c[k] = vcost[k] + dub_between(pose_k, goal).len for the vertices k in [0, j), tried in stable (c, k) order; the first vertex
@@ -28,38 +28,14 @@
 // (The exhaustive form -- goals_body with go2goal_phase<true> -- was the correctness anchor and the other side of the measurement: the
 // same answers at 313.4 ms against 160.6 ms per 4096 goal poses at bench scale.  profiles/poses_wall.json has both numbers,
 // tools/archive/poses_exhaustive.patch the code.)
-// (RRT_POSES_DECL_ONLY: a translation unit that only launches the kernel; csrc/kernels_tu.hip defines it)
+// (The view, the launch constants and the kernel's declaration: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_kernels.h"
+#include "rrt_go2goal.h"
 #include "rrt_cell_stream.h"
 
 namespace rrtdev {
 
-constexpr int POSES_MAX_SLABS = 512;                    // workgroups of a launch == `order` slabs of n_cap words each
-constexpr size_t POSES_SLAB_BUDGET = (size_t)128 << 20; // bytes of slabs a batch may hold (never fewer than one slab)
-constexpr int POSES_MAX = 1 << 20;                      // goal poses of one call
-
-struct PoseGoalsView {
-    const uint8_t *og;       // (W,H) x-major occupancy, != 0 is obstacle
-    int32_t W, H;
-    const uint32_t *nodes;   // the query's packed vertices
-    const double *vcost;
-    const uint8_t *heading;  // ... and their heading indices
-    int32_t j;               // vertices considered: [0, j)
-    int32_t nh;              // the query's discrete headings
-    double rho;              // ... and turning radius
-    const uint32_t *goals;   // [m] cells packed like vertices
-    const uint8_t *goal_h;   // [m] heading indices, < nh
-    int32_t m;
-    int32_t slab_words;      // >= j
-    uint32_t *order;         // [gridDim.x][slab_words] the sorted vertex order, one slab per workgroup
-    int32_t *vertex;         // [m] out: the vertex the goal connects to, or -1
-    double *cost;            // [m] out: the cost of the goal through it, or +inf
-    uint32_t *counts;        // [m][2] out: words evaluated, sweeps run
-};
-
-#ifndef RRT_POSES_DECL_ONLY
 // The decision for one goal pose; pc / pi = +inf / NONE when nothing connects.  words / sweeps: what it evaluated (uniform).
 __device__ __forceinline__ void pose_goal_bounded(const PoseGoalsView &pv, const DubCfg &dc, uint32_t xg, int hg, uint32_t *order, RRT_LDS uint32_t *lds16k,
                                                   BSlot *bslots, int t, int lane, int wave, double &pc, uint32_t &pi, uint32_t &words, uint32_t &sweeps) {
@@ -245,18 +221,12 @@ __device__ __forceinline__ void pose_goals_body(const PoseGoalsView &pv, RRT_LDS
         __syncthreads();  // the next goal rewrites the slots and tables that slower waves may still be reading
     }
 }
-#endif
 
-__global__ __launch_bounds__(TPB) void rrt_pose_goals_kernel(PoseGoalsView pv)
-#ifdef RRT_POSES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_pose_goals_kernel(PoseGoalsView pv) {
     __shared__ __attribute__((aligned(16))) uint32_t lds16k[2 * G2G_NB];
     __shared__ __attribute__((aligned(16))) BSlot bslots[2 * NWAVE];
     __shared__ __attribute__((aligned(16))) double htab[3 * 256];
     pose_goals_body(pv, (RRT_LDS uint32_t *)lds16k, bslots, (RRT_LDS double *)htab);
 }
-#endif
 
 }  // namespace rrtdev

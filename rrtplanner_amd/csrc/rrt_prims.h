@@ -1,11 +1,44 @@
-// rrt_prims.h -- the path's primitives as stand-alone kernels (parity tests, micro-benchmarks).
-// They call the same device functions as rrt_expand_kernel.
+// rrt_prims.h -- the engine's own small kernels, compiled by rrt_engine.hip: rrt_init_kernel, which arms a query, and the path's
+// primitives as stand-alone kernels (parity tests, micro-benchmarks; they call the same device functions as rrt_expand_kernel).
 #pragma once
 
-#include "rrt_block.h"
-#include "rrt_kernels.h"
+#include "rrt_device.h"
 
 namespace rrtdev {
+
+// Arms query state in HBM: clears the `sampled` bitmap, writes node 0 (rrt.py:411-413) and fills the unfilled
+// node slots with a copy of node 0 (the block kernel scans whole 4096-node steps; such a slot can never be the
+// nearest node -- equal distance, higher index -- and is dropped from near sets by its index).
+// (a template: instantiated where it is launched, rrt_batch_launch)
+template <int = 0>
+__global__ void rrt_init_kernel(BatchView bv) {
+    const int q = (int)blockIdx.y;
+    const QDesc *D = bv.desc + q;
+    if (D->status != ST_RUNNING || D->i != 0) return;
+    uint32_t *bitmap = bv.bitmap + (size_t)q * bv.bitmap_words;
+    for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < bv.bitmap_words; k += (int)(gridDim.x * blockDim.x))
+        bitmap[k] = 0;
+    const uint32_t n0 = pack_xy(D->xs[0], D->xs[1]);
+    for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < bv.node_stride; k += (int)(gridDim.x * blockDim.x))
+        bv.nodes[(size_t)q * bv.node_stride + k] = n0;
+    if (bv.cellcnt) {  // near-set record grid: empty cells, then node 0 in its cell
+        const int c0 = (D->xs[0] >> D->cell_shift) * D->ncy + (D->xs[1] >> D->cell_shift);
+        for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < MAX_CELLS; k += (int)(gridDim.x * blockDim.x))
+            bv.cellcnt[(size_t)q * MAX_CELLS + k] = (k == c0) ? 1u : 0u;
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            bv.cellrec[(size_t)q * (size_t)bv.rec_stride + (size_t)c0 * (size_t)D->cell_cap] = make_uint4(n0, 0u, 0u, 0u);  // vcost 0.0
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        bv.vcost[(size_t)q * bv.node_stride] = 0.0;
+        bv.parent[(size_t)q * bv.node_stride] = -1;
+        if (bv.heading) bv.heading[(size_t)q * bv.node_stride] = (uint8_t)D->hs;
+        if (bv.kid_first) {
+            bv.kid_first[(size_t)q * bv.node_stride] = -1;
+            bv.kid_next[(size_t)q * bv.node_stride] = -1;
+            bv.kid_prev[(size_t)q * bv.node_stride] = -1;
+        }
+    }
+}
 
 // RRT.collisionfree (rrt.py:183-229): one wavefront per segment.  WALK: 0 los_wave (grids up to 2048 x 2048), 1 los_wave<true> (64-bit
 // division, any grid), 2 los_wave_large (grids up to 4096 x 4096: what rrt_pipe_large_kernel runs).

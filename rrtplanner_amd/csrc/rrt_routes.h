@@ -15,39 +15,13 @@
 // Rows live in global memory (a route has up to j + 1 rows, far beyond LDS); the engine sizes it from the total the first scan gives.
 // length[g] is the f64 sum, left to right from the root, of sqrt((double)d2) over the legs; d2 < 2^25 is exact in f64 and the root
 // correctly rounded (sqrt_u32), so numpy gives the same bits.
-// (RRT_ROUTES_DECL_ONLY: a translation unit that only launches the kernels; csrc/kernels_tu.hip defines them)
+// (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
 #include "rrt_device.h"
 
 namespace rrtdev {
 
-constexpr int ROUTE_TPB = 256;                            // depth, fill and pack: goals per workgroup (lanes), or 4 goals (waves)
-constexpr int ROUTE_CUT_MAX_WG = 1024;                    // workgroups of the shortcut kernel, each loops over goals
-constexpr size_t ROUTE_ROW_BUDGET = (size_t)1 << 28;      // raw rows of one call (20 bytes of device memory each)
-
-struct RoutesView {
-    const uint8_t *og;       // (W,H) x-major occupancy, != 0 is obstacle
-    int32_t H;
-    const uint32_t *nodes;   // the query's packed vertices
-    const int32_t *parent;
-    int32_t j;               // tree vertices: [0, j)
-    const uint32_t *goals;   // [m] packed
-    const int32_t *vertex;   // [m] what the goals kernel decided
-    int32_t m;
-    int32_t *cnt;            // [m] raw rows of a goal
-    int32_t *kept;           // [m] rows after shortcutting
-    int64_t *raw_off;        // [m + 1] exclusive scan of cnt
-    int64_t *fin_off;        // [m + 1] exclusive scan of kept (== raw_off without shortcuts)
-    double *length;          // [m]
-    int32_t *err;            // != 0: a parent walk did not end at vertex 0
-    uint32_t *row_xy;        // [raw rows] packed points; the shortcut kernel rewrites the front of a goal's rows in place
-    int32_t *row_id;         // [raw rows]
-    int32_t *out_xy;         // [final rows][2]
-    int32_t *out_id;         // [final rows]
-};
-
-#ifndef RRT_ROUTES_DECL_ONLY
 // Greedy shortcutting of one route P[0..k) by the whole workgroup.  From the anchor a (row 0 first) the next row is the LARGEST
 // b in (a, k-1] with b == a+1 or a free line P[a] -> P[b], walked from the start side (the walk is not symmetric).  Candidates go
 // from the far end downwards in rounds of NW, one line per wave; the first round that holds a free line ends the anchor with its
@@ -110,14 +84,9 @@ __device__ __forceinline__ void cut_body(const RoutesView &rv, RRT_LDS int *res 
         }
     }
 }
-#endif
 
 // one goal per lane: the rows of its raw route, 0 for a goal that nothing connects to
-__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_depth_kernel(RoutesView rv)
-#ifdef RRT_ROUTES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_depth_kernel(RoutesView rv) {
     const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (g >= rv.m) return;
     const int j = rv.j;
@@ -133,15 +102,10 @@ __global__ __launch_bounds__(ROUTE_TPB) void rrt_route_depth_kernel(RoutesView r
     }
     rv.cnt[g] = rows;
 }
-#endif
 
 // exclusive scan of in[0, m) into out[0, m]: one workgroup of TPB threads, TPB values a pass (each at most j + 1 < 2^19: a pass sums
 // below 2^32), the carry in 64 bits
-__global__ __launch_bounds__(TPB) void rrt_route_scan_kernel(const int32_t *in, int64_t *out, int32_t m)
-#ifdef RRT_ROUTES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_route_scan_kernel(const int32_t *in, int64_t *out, int32_t m) {
     __shared__ uint32_t wsum[2][NWAVE];
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     int64_t carry = 0;
@@ -165,14 +129,9 @@ __global__ __launch_bounds__(TPB) void rrt_route_scan_kernel(const int32_t *in, 
     }
     if (t == 0) out[m] = carry;
 }
-#endif
 
 // one goal per lane: its rows, written from the goal back to the root; WITH_LEN (no shortcut pass follows): kept, and the length
-__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_fill_kernel(RoutesView rv, int32_t with_len)
-#ifdef RRT_ROUTES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_fill_kernel(RoutesView rv, int32_t with_len) {
     const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (g >= rv.m) return;
     const int k = rv.cnt[g];
@@ -203,35 +162,20 @@ __global__ __launch_bounds__(ROUTE_TPB) void rrt_route_fill_kernel(RoutesView rv
         rv.length[g] = len;
     }
 }
-#endif
 
-__global__ __launch_bounds__(TPB) void rrt_route_cut_kernel(RoutesView rv)
-#ifdef RRT_ROUTES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_route_cut_kernel(RoutesView rv) {
     __shared__ int res[2 * NWAVE];
     cut_body<false, NWAVE>(rv, (RRT_LDS int *)res);
 }
-#endif
 
 // grids up to 4096 x 4096 (a batch created with RRT_FLAG_LARGE_GRID): the lines of sight by los_wave_large
-__global__ __launch_bounds__(TPB) void rrt_route_cut_large_kernel(RoutesView rv)
-#ifdef RRT_ROUTES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(TPB) void rrt_route_cut_large_kernel(RoutesView rv) {
     __shared__ int res[2 * NWAVE];
     cut_body<true, NWAVE>(rv, (RRT_LDS int *)res);
 }
-#endif
 
 // one goal per wave: the first kept[g] rows of its raw rows to the dense rows fin_off[g] ...
-__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_pack_kernel(RoutesView rv)
-#ifdef RRT_ROUTES_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(ROUTE_TPB) void rrt_route_pack_kernel(RoutesView rv) {
     const int lane = (int)threadIdx.x & 63;
     const int g = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     if (g >= rv.m) return;
@@ -246,6 +190,5 @@ __global__ __launch_bounds__(ROUTE_TPB) void rrt_route_pack_kernel(RoutesView rv
         rv.out_id[dst + i] = id[i];
     }
 }
-#endif
 
 }  // namespace rrtdev

@@ -25,50 +25,14 @@
 //                                order.  A cell is written by one wave only, in index order, with its counts in that wave's LDS:
 //                                ordered placement without a wait across wavefronts or workgroups, and without atomics.
 // Every store is bounds-checked; a vertex outside the record grid or a cell past its capacity sets *err and stores nothing.
-// (RRT_SEED_DECL_ONLY: a translation unit that only launches the kernels; csrc/kernels_tu.hip defines them)
+// (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_kernels.h"
+#include "rrt_device.h"
 
 namespace rrtdev {
 
-constexpr int SEED_TPB = 256;                             // one slot / vertex per lane; records: 4 wavefronts a workgroup
-constexpr int SEED_WG = 64;                               // workgroups of the records kernel
-constexpr int SEED_WAVES = SEED_WG * (SEED_TPB / 64);     // wavefronts that share the cells: 256
-constexpr int SEED_OWN = MAX_CELLS / SEED_WAVES;          // cells a wavefront owns: 16 (cell = slot * SEED_WAVES + wavefront)
-static_assert(SEED_OWN * SEED_WAVES == MAX_CELLS && SEED_OWN <= 64, "every cell has one owner, one count per lane at the end");
-
-struct SeedView {
-    uint32_t *nodes;             // the query's tree arrays
-    double *vcost;
-    int32_t *parent;
-    int32_t j_old, j0, node_stride;  // vertices of the finished tree, of the seed, slots of the node array
-    const uint32_t *live_nodes;  // the view (rrt_keep.h), dense; all three null without a view (then j0 == j_old)
-    const double *live_vcost;
-    const int32_t *live_id;
-    int32_t *rank;               // [j_old] scratch, filled with -1
-    int32_t *new_parent;         // [j0] scratch
-    uint32_t *bitmap;
-    int32_t bitmap_words, H;
-    int32_t *err;                // set to 1 by any kernel that met something it could not place
-};
-
-struct SeedRecords {
-    const uint32_t *nodes;
-    const double *vcost;
-    int32_t j0;
-    int32_t cshift, ncx, ncy, ccap;
-    int64_t rec_stride;
-    u32x4 *cellrec;
-    uint32_t *cellcnt;           // [MAX_CELLS]
-    int32_t *err;
-};
-
-__global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv)
-#ifdef RRT_SEED_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= sv.j0) return;
     const int id = sv.live_id[k];
@@ -78,13 +42,8 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv)
     }
     sv.rank[id] = k;
 }
-#endif
 
-__global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv)
-#ifdef RRT_SEED_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= sv.j0) return;
     const int id = sv.live_id[k];
@@ -96,13 +55,8 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv)
     }
     sv.new_parent[k] = np;
 }
-#endif
 
-__global__ __launch_bounds__(SEED_TPB) void rrt_seed_install_kernel(SeedView sv)
-#ifdef RRT_SEED_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_install_kernel(SeedView sv) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= sv.node_stride) return;
     if (sv.live_id) {
@@ -115,13 +69,8 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_install_kernel(SeedView sv)
         sv.nodes[k] = sv.nodes[0];  // (slot 0 is written by nobody: j0 >= 1)
     }
 }
-#endif
 
-__global__ __launch_bounds__(SEED_TPB) void rrt_seed_bitmap_kernel(SeedView sv)
-#ifdef RRT_SEED_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_bitmap_kernel(SeedView sv) {
     const int k = 1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);  // (never vertex 0: rrt.py:407-413)
     if (k >= sv.j0) return;
     const uint32_t xy = sv.nodes[k];
@@ -132,13 +81,8 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_bitmap_kernel(SeedView sv)
     }
     atomicOr(&sv.bitmap[cell >> 5], 1u << (cell & 31));  // rrt.py:426
 }
-#endif
 
-__global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords sr)
-#ifdef RRT_SEED_DECL_ONLY
-    ;
-#else
-{
+__global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords sr) {
     __shared__ uint32_t cnt_lds[SEED_TPB / 64][SEED_OWN];
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int gw = (int)blockIdx.x * (SEED_TPB / 64) + wave;  // this wavefront's number: it owns the cells c with c % SEED_WAVES == gw
@@ -179,6 +123,5 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords 
     }
     if (lane < SEED_OWN) sr.cellcnt[lane * SEED_WAVES + gw] = cnt[lane];  // every cell of [0, MAX_CELLS), the empty ones too
 }
-#endif
 
 }  // namespace rrtdev

@@ -1,4 +1,4 @@
-// rrt_kernels.h -- the tree-expansion kernel: one persistent 1024-thread workgroup per query.
+// rrt_serial.h -- the one-sample-per-iteration tree-expansion kernel: one persistent 1024-thread workgroup per query.
 //
 // Replaces the loops of rrtplanner/rrt.py:418-437 (RRTStandard), :498-548 (RRTStar),
 // :690-748 (RRTStarInformed) and go2goal (:311-332) of the reference.  One barrier per iteration:
@@ -25,115 +25,9 @@
 // (lowest index among equal distance / equal cost).
 #pragma once
 
-#include "rrt_device.h"
-#include "rrt_dubins_dev.h"
+#include "rrt_go2goal.h"
 
 namespace rrtdev {
-
-enum : int32_t { ST_DONE = 0, ST_NEED_UB = 1, ST_UNREACHABLE = -2, ST_TEAM_FAIL = -3, ST_RUNNING = 100, ST_IDLE = 101 };
-
-// Per-query descriptor in HBM: inputs, resumable loop state, statistics.
-struct QDesc {
-    int32_t alg, n;
-    int32_t xs[2], xg[2];
-    uint32_t r2_rewire, goal_d2;
-    double C[4];
-    int32_t ub_offset, ub_count;
-    int32_t cell_shift, ncx, ncy, cell_cap;  // block kernel: near-set record grid of this query (cell = 2^shift pixels)
-    int32_t status, i, j, nsoln, vbest_soln, vgoal, found, i_switch;
-    double cmin_soln;
-    unsigned long long sum_j, sum_cells_nn, sum_near, sum_cells_cand, n_los_cand;
-    unsigned long long wcyc[32]; // diagnostic build: per-wave cycles in the block kernel's owner phase [0..15] and its LoS part [16..31]
-    unsigned long long cyc[6];  // diagnostic build (-DRRT_STAMPS): wave-0 cycles in scan / pre-barrier / barrier / B+C / D / go2goal
-    unsigned long long n_rewired, n_propagated;  // opt-in true rewire (RRT_FLAG_REWIRE): nodes re-parented, descendant costs recomputed
-    double rho;          // Dubins planners (alg 3 / 4): turning radius in cells, number of headings, start / goal heading index
-    int32_t nh, hs, hg, pad_;
-    unsigned long long n_words;  // Dubins planners: dub_shortest() evaluations made (the byte / flop model counts one per near-set entry)
-#ifdef RRT_STAMPS
-    // diagnostic build, pipelined teams: per worker m = member - 1: [m] polls of the committer's record fetch during which m's records were
-    // still missing, [64 + m] blocks in which m was the LAST to arrive, [128 + m] the worker's own cycles in its resolve phase
-    unsigned long long dbg2[448];  // (+ [192 + m], [256 + m], [320 + m]: blocks whose resolve phase took m more than 26 k / 32 k / 40 k cycles, [384 + m]: its longest)
-    unsigned long long ts[32 * 16];  // wall-clock (10 ns) time stamps of 32 consecutive blocks, 16 events each (rrt_block.h: TSMARK)
-#endif
-};
-
-struct BatchView {
-    QDesc *desc;
-    const uint32_t *samples;  // [Q][n_cap]         packed free-space samples
-    uint32_t *nodes;          // [Q][node_stride]   packed tree nodes
-    double *vcost;            // [Q][node_stride]
-    int32_t *parent;          // [Q][node_stride]
-    uint32_t *bitmap;         // [Q][bitmap_words]  `sampled` set (rrt.py:407)
-    uint2 *spill;             // [Q][spill_stride]  per-wave near-set overflow / go2goal costs
-    const double *unitball;   // [Q][2*n_cap] or null
-    int32_t *nearest_log;     // optional logs [Q][n_cap]
-    uint8_t *accept_log;
-    double *cbest_log;
-    int32_t *j_log;
-    const uint8_t *og;        // (W,H) x-major occupancy, != 0 is obstacle
-    int32_t W, H;
-    int32_t n_cap, node_stride, bitmap_words, lds_chunks, spill_stride;
-    uint4 *cellrec;           // [Q][rec_stride]    block kernel: per-cell arrays of {xy, index, vcost} records
-    uint32_t *cellcnt;        // [Q][MAX_CELLS]     fill counts of the cells
-    int64_t rec_stride;
-    unsigned char *team;      // [Q][TEAM_BYTES]    block kernel with teams: sync words, state, exchanged records
-    int32_t Q, team_qpad;     // queries of the batch; block stride between the members of a team (block = member * team_qpad + query)
-    int32_t team_fault;       // testing: member 1 of every team leaves at once (the others' hand-offs time out)
-    int32_t member0;          // added to the member number a team kernel derives from its block index (1: a launch of the workers only)
-    // opt-in true rewire (RRT_FLAG_REWIRE; serial kernel only), null otherwise
-    int32_t *kid_first, *kid_next, *kid_prev;  // [Q][node_stride] child lists: first child, next / previous sibling (-1 = none)
-    uint32_t *frontier;                        // [Q][2 * node_stride] two propagation frontiers
-    int32_t *vsoln;                            // [Q][node_stride] Informed: solution vertices in insertion order
-    // Dubins planners (RRT_FLAG_DUBINS; serial kernel only), null otherwise
-    uint8_t *heading;               // [Q][node_stride] heading index of every node
-    const uint8_t *sample_heading;  // [Q][n_cap]       heading index of sample i
-    double *dub_path;               // [Q][NWAVE * WCAP][5] {t, p, q, len, word} of every priced near-set entry of the current iteration
-};
-
-constexpr int BLOCK_LIST_CAP = 256;                                  // block kernel, one wave per sample: parked entries per wave kept in LDS
-constexpr size_t BLOCK_LIST_LDS_BYTES = (size_t)NWAVE * BLOCK_LIST_CAP * 16;  // 64 KiB
-constexpr int MAX_CELLS = 4096;  // cells per query (their fill counts live in LDS: 16 KiB)
-
-// Near set of one wave: every wave keeps the within-radius nodes of its own stripe in its own LDS
-// region (WCAP entries {idx, d2}, overflow to its own HBM region) and later prices them itself, so
-// the append needs no atomics: the fill count is a wave-uniform register.
-struct WaveList {
-    RRT_LDS u32x2 *list;  // LDS [WCAP] of this wave
-    u32x2 *spill;         // HBM overflow of this wave
-};
-
-__device__ __forceinline__ void wl_store(const WaveList &wl, uint32_t pos, uint32_t idx, uint32_t d2) {
-    u32x2 v = {idx, d2};
-    if (pos < (uint32_t)WCAP) wl.list[pos] = v;
-    if (pos >= (uint32_t)WCAP) wl.spill[pos - WCAP] = v;
-}
-
-// Append the lanes flagged in h0..h3 (element e of each lane's 4-node load).  Wave-uniform control flow.
-__device__ __forceinline__ void wl_append4(const WaveList &wl, uint32_t &wcnt, bool h0, bool h1, bool h2, bool h3,
-                                           uint32_t idx0, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, int lane) {
-    const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
-    if ((m0 | m1 | m2 | m3) == 0) return;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    if (h0) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m0 & lt), idx0, d0);
-    wcnt += (uint32_t)__builtin_popcountll(m0);
-    if (h1) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m1 & lt), idx0 + 1, d1);
-    wcnt += (uint32_t)__builtin_popcountll(m1);
-    if (h2) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m2 & lt), idx0 + 2, d2);
-    wcnt += (uint32_t)__builtin_popcountll(m2);
-    if (h3) wl_store(wl, wcnt + (uint32_t)__builtin_popcountll(m3 & lt), idx0 + 3, d3);
-    wcnt += (uint32_t)__builtin_popcountll(m3);
-}
-
-template <bool STAR>
-__device__ __forceinline__ void eval4(u32x4 v, uint32_t q, uint32_t tag0, uint32_t idx0, uint32_t r2, uint32_t &best,
-                                      const WaveList &wl, uint32_t &wcnt, int lane) {
-    uint32_t d0 = dist2(v.x, q), d1 = dist2(v.y, q), d2 = dist2(v.z, q), d3 = dist2(v.w, q);
-    best = min(best, (d0 << 8) + tag0);
-    best = min(best, (d1 << 8) + tag0 + 1);
-    best = min(best, (d2 << 8) + tag0 + 2);
-    best = min(best, (d3 << 8) + tag0 + 3);
-    if (STAR) wl_append4(wl, wcnt, d0 < r2, d1 < r2, d2 < r2, d3 < r2, idx0, d0, d1, d2, d3, lane);
-}
 
 // One wave's publication for the iteration's barrier (64 bytes).
 struct Slot {
@@ -148,212 +42,6 @@ struct Slot {
 };
 static_assert(sizeof(Slot) == 64, "Slot must be 64 bytes");
 
-// Lane-local running best and second best in (cost, index) order.
-struct Top2 {
-    double c1, c2;
-    uint32_t i1, i2;
-    __device__ __forceinline__ void init() {
-        c1 = c2 = f64_inf();
-        i1 = i2 = NONE;
-    }
-    __device__ __forceinline__ void fold(double c, uint32_t i) {
-        if (key_lt(c, i, c1, i1)) {
-            c2 = c1;
-            i2 = i1;
-            c1 = c;
-            i1 = i;
-        } else if (key_lt(c, i, c2, i2)) {
-            c2 = c;
-            i2 = i;
-        }
-    }
-    // wave-wide best and second best of all lanes' entries (uniform result)
-    __device__ __forceinline__ void wave_reduce() {
-        double bc = c1;
-        uint32_t bi = i1;
-        wave_min_f64_idx(bc, bi);
-        const bool own = (c1 == bc && i1 == bi);
-        double sc = own ? c2 : c1;
-        uint32_t si = own ? i2 : i1;
-        wave_min_f64_idx(sc, si);
-        c1 = bc;
-        i1 = bi;
-        c2 = sc;
-        i2 = si;
-    }
-};
-
-// Workgroup exchange for the (rare) extra branch-and-bound rounds.
-struct BSlot {
-    double pc, uc;  // passing key of this round (or inf), best still-untested key (or inf)
-    uint32_t pi, ui;
-    uint32_t cells, tested;
-};
-
-// ---------------------------------------------------------------------------------------------------------------
-// go2goal (rrt.py:311-332): the goal connects to the first node, in stable (cost, index) order of
-// cost = vcost[k] + dist(k, goal), that has line of sight to it.  Nodes are counting-sorted into G2G_NB cost buckets
-// (LDS histogram, monotone bucket function), then tested in bucket order, 16 waves x G2G_U nodes per round; the
-// search ends once every node of the bucket that holds the cheapest passing node has been tested.
-constexpr int G2G_NB = 2048;  // cost buckets (2 x 8 KiB of LDS: fill cursors and bucket ends)
-constexpr int G2G_U = 4;      // nodes a wave tests per round
-
-// The nodes considered are kfirst + m * kstep, m < cnt (all of them: 0, 1, j; a team gives each member a stripe and takes the
-// minimum of the stripes' answers).
-// NT: threads of the calling workgroup (a pipelined team's committer may run as a workgroup of its own with fewer waves).
-// LARGE: grids up to 4096 x 4096 (the lines of sight by los_wave_large; the costs are sqrt_u32's, exact for any radicand).
-template <bool DUB = false, int NT = TPB, bool LARGE = false>
-__device__ __forceinline__ void go2goal_phase(const uint8_t *og, int H, const uint32_t *nodes_g, const double *vcost, int kfirst, int kstep,
-                                              int cnt, uint32_t xg, uint32_t *order, RRT_LDS uint32_t *lds16k, BSlot *bslots, int t, int lane,
-                                              int wave, double &pc, uint32_t &pi, const uint8_t *heading = nullptr, int hg = 0, DubCfg dc = DubCfg{}) {
-    RRT_LDS uint32_t *cursor = lds16k;          // [G2G_NB]
-    RRT_LDS uint32_t *bend = lds16k + G2G_NB;   // [G2G_NB]
-    auto cost_of = [&](int k) -> double {  // rrt.py:313-314
-        if (DUB) return vcost[k] + dub_between_dev(nodes_g[k], heading[k], xg, hg, dc).len;
-        return vcost[k] + sqrt_u32(dist2(nodes_g[k], xg));
-    };
-    // ---- cost range ----
-    double cmin = f64_inf(), cmax = 0.0;
-    for (int m = t; m < cnt; m += NT) {
-        const double c = cost_of(kfirst + m * kstep);
-        cmin = c < cmin ? c : cmin;
-        cmax = c > cmax ? c : cmax;
-    }
-    {
-        uint32_t dummy = 0;
-        wave_min_f64_idx(cmin, dummy);
-        double neg = -cmax;  // max via min on the order-reversed bit pattern is not available for negatives: use bits of cmax directly
-        (void)neg;
-        // max of non-negative doubles == max of their bit patterns; reduce as min of the complement
-        unsigned long long mb = ~(unsigned long long)__double_as_longlong(cmax);
-        uint32_t hi = (uint32_t)(mb >> 32), lo = (uint32_t)mb;
-        const uint32_t mh = wave_min_u32(hi);
-        const uint32_t ml = wave_min_u32(hi == mh ? lo : NONE);
-        cmax = __longlong_as_double((long long)~(((unsigned long long)mh << 32) | ml));
-        if (lane == 0) {
-            bslots[wave].pc = cmin;
-            bslots[wave].uc = cmax;
-        }
-        __syncthreads();
-        double a = f64_inf(), b = 0.0;
-        for (int w = 0; w < NT / 64; ++w) {
-            const double x = bslots[w].pc, y = bslots[w].uc;
-            a = x < a ? x : a;
-            b = y > b ? y : b;
-        }
-        cmin = a;
-        cmax = b;
-        __syncthreads();
-    }
-    const double scale = (cmax > cmin) ? (double)(G2G_NB - 1) / (cmax - cmin) : 0.0;
-    auto bucket_of = [&](double c) -> uint32_t {  // monotone non-decreasing in c
-        const double f = (c - cmin) * scale;
-        uint32_t b = (uint32_t)f;
-        return b > (uint32_t)(G2G_NB - 1) ? (uint32_t)(G2G_NB - 1) : b;
-    };
-    // ---- histogram, exclusive scan, scatter ----
-    for (int b = t; b < 2 * G2G_NB; b += NT) lds16k[b] = 0;
-    __syncthreads();
-    for (int m = t; m < cnt; m += NT)
-        __hip_atomic_fetch_add(&cursor[bucket_of(cost_of(kfirst + m * kstep))], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __syncthreads();
-    {
-        // thread t owns the PB consecutive buckets PB t .. PB t + PB - 1 (G2G_NB == PB * NT)
-        constexpr int PB = G2G_NB / NT;
-        static_assert(PB * NT == G2G_NB, "buckets per thread");
-        uint32_t cb[PB], own = 0;
-#pragma unroll
-        for (int e = 0; e < PB; ++e) {
-            cb[e] = cursor[PB * t + e];
-            own += cb[e];
-        }
-        uint32_t incl = own;  // (a variable of its own, then the call: as the initialiser of a constant the same sum compiles to the loops below in another order)
-        incl = wave_incl_sum_u32(incl);
-        if (lane == 63) bslots[wave].pi = incl;  // wave total
-        __syncthreads();
-        uint32_t base = 0;
-        for (int w = 0; w < wave; ++w) base += bslots[w].pi;
-        uint32_t ex = base + incl - own;
-#pragma unroll
-        for (int e = 0; e < PB; ++e) {
-            cursor[PB * t + e] = ex;
-            ex += cb[e];
-            bend[PB * t + e] = ex;
-        }
-        __syncthreads();
-    }
-    for (int m = t; m < cnt; m += NT) {
-        const int k = kfirst + m * kstep;
-        const uint32_t pos = __hip_atomic_fetch_add(&cursor[bucket_of(cost_of(k))], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        order[pos] = (uint32_t)k;
-    }
-    __syncthreads();
-    // ---- test in bucket order ----
-    pc = f64_inf();
-    pi = NONE;
-    uint32_t limit = (uint32_t)cnt;
-    int round = 0;
-    for (uint32_t pos0 = 0; pos0 < limit; pos0 += (NT / 64) * G2G_U) {
-        double bc = f64_inf();
-        uint32_t bi = NONE;
-#pragma unroll
-        for (int u = 0; u < G2G_U; ++u) {
-            const uint32_t p = pos0 + (uint32_t)(u * (NT / 64) + wave);
-            if (p < limit) {
-                const uint32_t k = order[p];
-                int cc = 0;
-                bool free_k;
-                if (DUB) {
-                    const dub_path_t pth = dub_between_dev(nodes_g[k], heading[k], xg, hg, dc);
-                    free_k = dub_sweep_wave(og, dc, nodes_g[k], heading[k], xg, pth, lane, cc);
-                } else {
-                    free_k = LARGE ? los_wave_large(og, H, nodes_g[k], xg, lane, cc) : los_wave(og, H, nodes_g[k], xg, lane, cc);
-                }
-                if (free_k) {  // rrt.py:318
-                    const double c = cost_of((int)k);
-                    if (key_lt(c, k, bc, bi)) {
-                        bc = c;
-                        bi = k;
-                    }
-                }
-            }
-        }
-        BSlot *sl = bslots + (round & 1) * NWAVE;
-        if (lane == 0) {
-            sl[wave].pc = bc;
-            sl[wave].pi = bi;
-        }
-        __syncthreads();
-        double rc = f64_inf();
-        uint32_t ri = NONE;
-        if (lane < NT / 64) {
-            rc = sl[lane].pc;
-            ri = sl[lane].pi;
-        }
-        wave_min_f64_idx(rc, ri);
-        ++round;
-        if (key_lt(rc, ri, pc, pi)) {
-            pc = rc;
-            pi = ri;
-            const uint32_t e = bend[bucket_of(pc)];  // every node that could sort before it lies before this position
-            limit = e < limit ? e : limit;
-        }
-    }
-}
-
-#if defined(RRT_STAMPS) && !defined(RRT_STAMPS_LIGHT)
-#define STAMP(k)                                                \
-    do {                                                        \
-        unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        cyc[k] += now_ - tstamp;                                \
-        tstamp = now_;                                          \
-    } while (0)
-#else
-#define STAMP(k) \
-    do {         \
-    } while (0)
-#endif
-
 // RW = true: the opt-in true RRT* rewire of SURVEY.md 8(f) row 4 (NOT the reference's behaviour; oracle/rrt_oracle.c states
 // the semantics): after an insertion every near-set entry vn with vcost[vnew] + dist < vcost[vn] and a free line of sight
 // vn -> xnew is re-parented to the new node, all decisions taken against the costs right after the insertion; then the costs
@@ -361,13 +49,9 @@ __device__ __forceinline__ void go2goal_phase(const uint8_t *og, int H, const ui
 // DUB = true: the Dubins planners (alg 3 Dubins-RRT, 4 Dubins-RRT*; no reference counterpart, include/rrt_dubins.h): every
 // node and sample carries a heading, an edge is the shortest Dubins word between the two poses, its cost the word's arc
 // length, its collision test the sampled sweep of the word; nearest / within / accept / choose-parent order are unchanged.
-// (RRT_SERIAL_DECL_ONLY: a translation unit that only launches the kernel; csrc/kernels_tu.hip instantiates it)
-template <bool RW, bool DUB = false>
-__global__ __launch_bounds__(TPB) void rrt_expand_kernel(BatchView bv)
-#ifdef RRT_SERIAL_DECL_ONLY
-    ;
-#else
-{
+// (csrc/kernels_tu.hip instantiates it, units 2 and 3)
+template <bool RW, bool DUB>
+__global__ __launch_bounds__(TPB) void rrt_expand_kernel(BatchView bv) {
     static_assert(!(RW && DUB), "the opt-in rewire is not built for the Dubins planners");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // node cache: lds_chunks * 16 KiB
     __shared__ __attribute__((aligned(16))) u32x2 wlist_lds[NWAVE * WCAP];
@@ -1113,41 +797,6 @@ __global__ __launch_bounds__(TPB) void rrt_expand_kernel(BatchView bv)
 #ifdef RRT_STAMPS
         for (int k = 0; k < 6; ++k) D->cyc[k] = cyc[k];
 #endif
-    }
-}
-#endif  // RRT_SERIAL_DECL_ONLY
-
-// Arms query state in HBM: clears the `sampled` bitmap, writes node 0 (rrt.py:411-413) and fills the unfilled
-// node slots with a copy of node 0 (the block kernel scans whole 4096-node steps; such a slot can never be the
-// nearest node -- equal distance, higher index -- and is dropped from near sets by its index).
-// (a template only so that every translation unit may see the definition: instantiated where it is launched)
-template <int = 0>
-__global__ void rrt_init_kernel(BatchView bv) {
-    const int q = (int)blockIdx.y;
-    const QDesc *D = bv.desc + q;
-    if (D->status != ST_RUNNING || D->i != 0) return;
-    uint32_t *bitmap = bv.bitmap + (size_t)q * bv.bitmap_words;
-    for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < bv.bitmap_words; k += (int)(gridDim.x * blockDim.x))
-        bitmap[k] = 0;
-    const uint32_t n0 = pack_xy(D->xs[0], D->xs[1]);
-    for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < bv.node_stride; k += (int)(gridDim.x * blockDim.x))
-        bv.nodes[(size_t)q * bv.node_stride + k] = n0;
-    if (bv.cellcnt) {  // near-set record grid: empty cells, then node 0 in its cell
-        const int c0 = (D->xs[0] >> D->cell_shift) * D->ncy + (D->xs[1] >> D->cell_shift);
-        for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < MAX_CELLS; k += (int)(gridDim.x * blockDim.x))
-            bv.cellcnt[(size_t)q * MAX_CELLS + k] = (k == c0) ? 1u : 0u;
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-            bv.cellrec[(size_t)q * (size_t)bv.rec_stride + (size_t)c0 * (size_t)D->cell_cap] = make_uint4(n0, 0u, 0u, 0u);  // vcost 0.0
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        bv.vcost[(size_t)q * bv.node_stride] = 0.0;
-        bv.parent[(size_t)q * bv.node_stride] = -1;
-        if (bv.heading) bv.heading[(size_t)q * bv.node_stride] = (uint8_t)D->hs;
-        if (bv.kid_first) {
-            bv.kid_first[(size_t)q * bv.node_stride] = -1;
-            bv.kid_next[(size_t)q * bv.node_stride] = -1;
-            bv.kid_prev[(size_t)q * bv.node_stride] = -1;
-        }
     }
 }
 

@@ -31,7 +31,7 @@ import oracle
 from rrtplanner_amd import hostprep
 
 TINY = 64          # PP_TINY (rrt_pipe.h), DB_TINY (rrt_dubins_block.h)
-MAX_CELLS = 4096   # rrt_kernels.h
+MAX_CELLS = 4096   # rrt_kernel_abi.h
 DIV_PIPE, DIV_OTHER = 4.0, 2.0  # RRT_CELL_DIV_PIPE, RRT_CELL_DIV (rrt_engine.hip)
 
 

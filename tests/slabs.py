@@ -1,8 +1,8 @@
 """Which iterations of a query make the near-set record stream go past its first 64 cells.
 
 Every cell-record kernel streams the records of the cells in the bounding box of the rewire ball 64 cells at a time
-(`stream_cells` in rrt_block_nearset.inc: `for (cbase = 0; cbase < ncr; cbase += 64)`; the same loop in rrt_pipe.h and
-rrt_dubins_block.h).  Counters, list positions and screens carry over from one slab of 64 cells to the next.  A box has more
+(`stream_cells` in rrt_block_nearset.inc: `for (cbase = 0; cbase < ncr; cbase += 64)`; the same loop in rrt_cell_stream.h, which
+rrt_pipe.h and rrt_dubins_block.h run).  Counters, list positions and screens carry over from one slab of 64 cells to the next.  A box has more
 than 64 cells only where the radius is large against the cell: for cells r/4 to r/2 wide (divisor 2) that is the top eighth
 below a power of two ([56, 64), [112, 128), [224, 256)); a kernel that runs on the other kernel's cell size (divisor 4 cells
 under a divisor 2 kernel) gets there at every radius from 64 on.

@@ -14,7 +14,7 @@ from rrtplanner_amd.dubins import RRTStarDubins
 
 pytestmark = pytest.mark.gpu
 
-TPB = 1024  # threads of the workgroup that decides a goal (rrt_device.h)
+TPB = 1024  # threads of the workgroup that decides a goal (rrt_kernel_abi.h)
 INF = np.inf
 
 

@@ -16,7 +16,7 @@ from rrtplanner_amd.oggen import DeviceGrids
 
 pytestmark = pytest.mark.gpu
 
-MAX_WORKGROUPS = 512  # POSES_MAX_SLABS of rrt_pose_goals.h: the workgroups of one launch, each deciding goals g, g + 512, ...
+MAX_WORKGROUPS = 512  # POSES_MAX_SLABS of rrt_kernel_abi.h: the workgroups of one launch, each deciding goals g, g + 512, ...
 INF = np.inf
 
 

@@ -18,7 +18,7 @@ LARGE_KERNEL = "rrt_pipe_large_kernel"
 
 # ------------------------------------------------------------------------------------------------------------ primitives
 def test_wide_sqrt_is_exact_for_every_radicand_below_2_25(gpu_ctx):
-    """sqrt_u25 (rrt_block.h) against the host's correctly rounded f64 root, every integer in [0, 2^25)"""
+    """sqrt_u25 (rrt_device.h) against the host's correctly rounded f64 root, every integer in [0, 2^25)"""
     step = 1 << 22
     for lo in range(0, 1 << 25, step):
         got = gpu_ctx.prim_sqrt_u25(lo, step)
