@@ -260,9 +260,21 @@ int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows);
  * that cut it.  An rrt_batch_set_query that is refused leaves the query and its view as they were.  The first call allocates
  * scratch on the batch (10 bytes a vertex of capacity, and 16 for each query that is kept), freed with the batch. */
 int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive);
-/* kernel time in ms of the three stages of the last successful rrt_batch_keep_tree on this batch, from events on the stream:
- * edge test, pointer jumping, compaction.  RRT_E_ARG when there is none (or its tree had no vertex). */
+/* kernel time in ms of the three stages of the last successful rrt_batch_keep_tree (or rrt_batch_keep_pose_tree) on this batch, from
+ * events on the stream: edge test, pointer jumping, compaction.  RRT_E_ARG when there is none (or its tree had no vertex). */
 int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]);
+/* rrt_batch_keep_tree for a batch created with RRT_FLAG_DUBINS (rrt_pose_keep.h): the same call with a Dubins edge.  With
+ * pose[k] = (nodes[k], heading[k]):
+ *   edge_ok[0] = the root's cell is free in og';  edge_ok[k] = the sweep of the shortest word from pose[parent[k]] to pose[k] is free
+ *   on og' for k > 0 (include/rrt_dubins.h: every sample k * DUB_DS inside the grid and on a free cell, then the child's cell);
+ *   alive[k] = edge_ok[k] and alive[parent[k]].
+ * That is the test plan() accepted the edge by, and the Dubins loop has no rewire: on an unchanged map every vertex stays alive.
+ * Afterwards rrt_batch_connect_poses accepts the new grid for query q, sweeps on it, considers only the alive vertices (the view
+ * carries their heading bytes) and answers in the original vertex numbers.  Everything else -- *n_alive, alive, no cost changes, the
+ * tree arrays untouched, not cumulative, the other queries, what drops the view, what a failure half way leaves, the three stage
+ * times of rrt_batch_keep_tree_ms -- is rrt_batch_keep_tree's.  RRT_E_ARG as there.  RRT_E_UNSUPPORTED: not a Dubins batch (its call
+ * is rrt_batch_keep_tree).  The scratch: 10 bytes a vertex of capacity, and 17 for each query that is kept. */
+int rrt_batch_keep_pose_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive);
 /* Grow the finished tree of query q with m more samples (rrt_seed.h): seed + arm, then rrt_batch_launch / rrt_batch_sync /
  * rrt_batch_get_result as after rrt_batch_set_query.  RRTStandard and RRTStar, the default cost, the reference's rewire.
  *   seed   the alive vertices of the query's view (rrt_batch_keep_tree), in their original order, become vertices 0 .. *j0-1 of a new
@@ -344,6 +356,8 @@ int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows);
 /* rrt_batch_keep_tree / rrt_batch_keep_tree_ms on the tree of the context's last rrt_plan / rrt_plan_resume */
 int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive);
 int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]);
+/* rrt_batch_keep_pose_tree on the Dubins tree of the context's last rrt_plan (its stage times: rrt_plan_keep_tree_ms) */
+int rrt_plan_keep_pose_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive);
 /* *j = vertices of the finished tree of the context's last rrt_plan / rrt_plan_resume: the bytes rrt_plan_keep_tree writes into
  * `alive`.  RRT_E_ARG: NULL; no finished rrt_plan on this context. */
 int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j);

@@ -75,6 +75,7 @@ SYMBOLS = (
     "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
     "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
     "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
+    "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
 )
 
 
@@ -187,6 +188,8 @@ def lib():
             "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
             "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
             "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
+            "rrt_batch_keep_pose_tree": ([vp, i32, C.POINTER(i32), vp], C.c_int),
+            "rrt_plan_keep_pose_tree": ([vp, C.POINTER(i32), vp], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -478,8 +481,15 @@ class Context:
         _check(self._h, L.rrt_plan_tree_size(self._h, C.byref(j)))
         return _keep_tree(self._h, lambda *a: L.rrt_plan_keep_tree(self._h, *a), j.value, lambda: j.value)
 
+    def keep_pose_tree(self):
+        """rrt_plan_keep_pose_tree: Batch.keep_pose_tree on the Dubins tree of this context's last plan()"""
+        L = lib()
+        j = C.c_int32(0)
+        _check(self._h, L.rrt_plan_tree_size(self._h, C.byref(j)))
+        return _keep_tree(self._h, lambda *a: L.rrt_plan_keep_pose_tree(self._h, *a), j.value, lambda: j.value)
+
     def keep_tree_ms(self):
-        """kernel time in ms of the last keep_tree(): (edge test, pointer jumping, compaction)"""
+        """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
         ms = (C.c_float * 3)()
         _check(self._h, lib().rrt_plan_keep_tree_ms(self._h, C.byref(ms)))
         return tuple(ms)
@@ -722,8 +732,24 @@ class Batch:
         L = lib()
         return _keep_tree(self.ctx.handle, lambda *a: L.rrt_batch_keep_tree(self._h, int(q), *a), self.n_cap, lambda: self.get_result(q, arrays=False).j)
 
+    def keep_pose_tree(self, q):
+        """rrt_batch_keep_pose_tree: keep_tree for a Dubins batch.  An edge is the shortest Dubins word from the parent's pose to the
+        child's, free if its sweep is (include/rrt_dubins.h) -- the test plan() accepted it by, so an unchanged grid keeps every
+        vertex.  Returns alive bool[j].  Afterwards connect_poses of query q runs on the new grid over the alive vertices only and
+        answers in the original vertex numbers; everything else as keep_tree."""
+        L = lib()
+        return _keep_tree(self.ctx.handle, lambda *a: L.rrt_batch_keep_pose_tree(self._h, int(q), *a), self.n_cap, lambda: self.get_result(q, arrays=False).j)
+
+    def keep_pose_tree_resident(self, grids, k, q=0):
+        """keep_pose_tree(q) on frame k of grids generated on this batch's context (oggen.DeviceGrids): the frame becomes the
+        context's active grid without an upload.  RuntimeError when the frames are no longer on the device."""
+        if grids.ctx is not self.ctx:
+            raise ValueError("grids were generated on a different device context")
+        grids.select(k)
+        return self.keep_pose_tree(q)
+
     def keep_tree_ms(self):
-        """kernel time in ms of the last keep_tree(): (edge test, pointer jumping, compaction)"""
+        """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
         ms = (C.c_float * 3)()
         _check(self.ctx.handle, lib().rrt_batch_keep_tree_ms(self._h, C.byref(ms)))
         return tuple(ms)

@@ -189,8 +189,9 @@ struct rrt_batch {
     DevBuf route_goal;                   // [length | raw_off | fin_off | cnt | kept | err] for route_goal.cap goals
     DevBuf route_row;                    // [row_xy | row_id | out_xy | out_id] for route_row.cap rows
     int64_t route_rows = -1;             // dense rows the last rrt_batch_routes left for rrt_batch_routes_rows; -1: none (launch, rearm)
-    // rrt_batch_keep_tree: the views of the queries that were kept on a new map (rrt_keep.h), allocated at the first call per query
-    std::vector<DevBuf> keep;            // [Q] empty, or [live_vcost f64 | live_nodes u32 | live_id i32], each of n_cap
+    // rrt_batch_keep_tree / rrt_batch_keep_pose_tree: the views of the queries that were kept on a new map (rrt_keep.h, rrt_pose_keep.h),
+    // allocated at the first call per query
+    std::vector<DevBuf> keep;            // [Q] empty, or [live_vcost f64 | live_nodes u32 | live_id i32 | a Dubins batch: live_heading u8], each of n_cap
     std::vector<int32_t> keep_alive;     // [Q] vertices of the view; -1: no view, the goals and routes calls see the whole tree
     DevBuf keep_tmp;                     // [anc i32 x 2 | ok u8 x 2 | count i32 at the end], each array of n_cap (rounded up to 8 bytes)
     hipEvent_t ev_keep[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_keep_tree

@@ -207,8 +207,25 @@ struct KeepCompact {
     int32_t *count;          // out
 };
 
+// ---- rrt_pose_keep.h ----
+constexpr int POSE_KEEP_TPB = 64;       // edge test: one wavefront a workgroup, 64 edges a round (one per lane); gather: one vertex per lane
+constexpr int POSE_KEEP_MAX_WG = 2048;  // workgroups of the edge test, grid-stride beyond
+
+struct PoseKeepView {
+    const uint8_t *og;       // (W,H) x-major occupancy of the new map, != 0 is obstacle
+    int32_t W, H;
+    const uint32_t *nodes;   // the query's packed vertices
+    const int32_t *parent;
+    const uint8_t *heading;  // ... and their heading indices
+    int32_t j;               // tree vertices: [0, j)
+    int32_t nh;              // the query's discrete headings
+    double rho;              // ... and turning radius
+    uint8_t *ok;             // [j] out of the edge test: edge_ok
+    int32_t *anc;            // [j] out of the edge test: the parent, 0 for the root, k itself for a parent outside [0, j)
+};
+
 // ---- rrt_seed.h ----
-constexpr int SEED_TPB = 256;                             // one slot / vertex per lane; records: 4 wavefronts a workgroup
+constexpr int SEED_TPB = 256;                            // one slot / vertex per lane; records: 4 wavefronts a workgroup
 constexpr int SEED_WG = 64;                               // workgroups of the records kernel
 constexpr int SEED_WAVES = SEED_WG * (SEED_TPB / 64);     // wavefronts that share the cells: 256
 constexpr int SEED_OWN = MAX_CELLS / SEED_WAVES;          // cells a wavefront owns: 16 (cell = slot * SEED_WAVES + wavefront)
@@ -272,6 +289,10 @@ __global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_large_kernel(KeepView 
 __global__ __launch_bounds__(KEEP_TPB) void rrt_keep_jump_kernel(const uint8_t *ok, const int32_t *anc, uint8_t *ok2, int32_t *anc2, int32_t j);
 __global__ __launch_bounds__(TPB) void rrt_keep_compact_kernel(KeepCompact kc);
 __global__ __launch_bounds__(KEEP_TPB) void rrt_keep_remap_kernel(int32_t *vertex, const int32_t *live_id, int32_t m, int32_t count);
+// rrt_pose_keep.h (unit 9, beside the pose goals)
+__global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_edge_kernel(PoseKeepView kv);
+__global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_gather_kernel(const uint8_t *heading, const int32_t *live_id, const int32_t *count,
+                                                                            uint8_t *live_heading, int32_t j);
 // rrt_seed.h (unit 8)
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv);

@@ -1,7 +1,8 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, keep_tree, grow and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h, rrt_pose_goals.h,
-// rrt_routes.h, rrt_keep.h and rrt_seed.h.  What the calls share comes first and is written once: the refusals (refuse_*), the
-// pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the batch behind rrt_plan.
+// routes, keep_tree, keep_pose_tree, grow and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_keep.h, rrt_pose_keep.h and rrt_seed.h.  What the calls share comes first and is written once:
+// the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
+// batch behind rrt_plan.
 #include "rrt_engine.h"
 
 // ---- the gate: a finished tree on the grid it belongs to ----
@@ -21,7 +22,7 @@ static int refuse_unfinished(const char *who, rrt_batch *b, int32_t q) {
 }
 
 // The grid's shape, then its generation.  how: what the call says happened to the shape; so: what a replaced grid means for the call,
-// nullptr for the call that adopts the new grid and so never asks (rrt_batch_keep_tree).
+// nullptr for the calls that adopt the new grid and so never ask (rrt_batch_keep_tree, rrt_batch_keep_pose_tree).
 static int refuse_grid(const char *who, rrt_batch *b, int32_t q, const char *how = "changed shape since the batch was created",
                        const char *so = ": the tree belongs to the other grid") {
     rrt_ctx *ctx = b->ctx;
@@ -50,6 +51,7 @@ struct TreeRef {
     double *live_vcost;   // [n_cap] each: the alive vertices, dense and in the original order (nullptr before the query's first keep_tree)
     uint32_t *live_nodes;
     int32_t *live_id;     // ... and the original number of each
+    uint8_t *live_heading;  // ... and its heading index (a Dubins batch; nullptr otherwise)
     int32_t kept;         // vertices of the view, at most the tree's j; -1: no view, the calls see the whole tree
 };
 
@@ -60,6 +62,7 @@ static TreeRef tree_ref(rrt_batch *b, int32_t q) {
         t.live_vcost = b->keep[(size_t)q].as<double>();
         t.live_nodes = reinterpret_cast<uint32_t *>(t.live_vcost + b->n_cap);
         t.live_id = reinterpret_cast<int32_t *>(t.live_nodes + b->n_cap);
+        if (b->d_heading) t.live_heading = reinterpret_cast<uint8_t *>(t.live_id + b->n_cap);
     }
     t.kept = std::min(b->keep_alive[(size_t)q], b->h_desc[(size_t)q].j);
     return t;
@@ -189,15 +192,17 @@ static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t
     HIPCHK(ctx, goal_scratch(b, m, slabs));
     HIPCHK(ctx, b->pose_h.reserve(m, (size_t)m));
     HIPCHK(ctx, b->pose_counts.reserve(m, (size_t)m * 2 * sizeof(uint32_t)));
+    // a query that was kept on this grid (rrt_batch_keep_pose_tree): the decision over the view, as in goals_decide
     const TreeRef t = tree_ref(b, q);
+    const bool view = t.kept >= 0;
     PoseGoalsView pv{};
     pv.og = ctx->og;
     pv.W = W;
     pv.H = H;
-    pv.nodes = t.nodes;
-    pv.vcost = t.vcost;
-    pv.heading = t.heading;
-    pv.j = d.j;
+    pv.nodes = view ? t.live_nodes : t.nodes;
+    pv.vcost = view ? t.live_vcost : t.vcost;
+    pv.heading = view ? t.live_heading : t.heading;
+    pv.j = view ? t.kept : d.j;
     pv.nh = d.nh;
     pv.rho = d.rho;
     pv.goals = b->goal_xy.as<uint32_t>();
@@ -211,6 +216,9 @@ static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t
     HIPCHK(ctx, hipMemcpyAsync(b->goal_xy.p, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->pose_h.p, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
+    if (view)
+        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, pv.vertex,
+                           (const int32_t *)t.live_id, m, pv.j);
     HIPCHK(ctx, hipGetLastError());
     if (const int rc = fetch_goal_answers(b, m, vertex, cost)) return rc;
     b->pose_last_m = m;
@@ -244,27 +252,33 @@ extern "C" int rrt_batch_connect_poses_counts(rrt_batch *b, int64_t out[2]) {
     return RRT_OK;
 }
 
-// ---- keep a finished tree when the map changes (rrt_keep.h) ----
+// ---- keep a finished tree when the map changes (rrt_keep.h; a Dubins tree: rrt_pose_keep.h) ----
+// rrt_batch_keep_tree (poses == false: straight-line batches) and rrt_batch_keep_pose_tree (poses == true: Dubins batches) are one call
+// with two edge tests; the Dubins view carries one more array, the heading bytes, gathered behind the compaction.
 // Adopts the context's current grid for query q and installs the view of the vertices that still hang on the root through edges
 // that are free on it.  Every call starts from the whole tree of the query.  A call refused for its arguments changes nothing.  Past
 // that, a view the query had is dropped together with the grid it was built for (drop_keep_views), so a call that fails half way
 // leaves a query that was kept before refused by goals_decide, never answered from the whole tree on a grid that cut it.
-static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
+static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive, bool poses) {
     rrt_ctx *ctx = b->ctx;
     if (!n_alive) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (b->flags & RRT_FLAG_DUBINS)
+    if (!poses && (b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its edges are Dubins words between poses; these kernels test straight lines)", who);
+    if (poses && !(b->flags & RRT_FLAG_DUBINS))
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its edges are straight lines: use rrt_batch_keep_tree)", who);
     if (const int rc = refuse_q(who, b, q)) return rc;
     if (const int rc = refuse_unfinished(who, b, q)) return rc;
     if (const int rc = refuse_grid(who, b, q, "has another shape than the batch was created for", nullptr)) return rc;
-    const int j = b->h_desc[(size_t)q].j;
+    const QDesc &d = b->h_desc[(size_t)q];
+    const int j = d.j;
     if (j < 0 || j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, j, b->n_cap);
+    if (poses && (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0))) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     drop_keep_views(b, q);
     b->keep_timed = false;
     const size_t cap = ((size_t)b->n_cap + 7) & ~(size_t)7;
     HIPCHK(ctx, b->keep_tmp.reserve(1, cap * 10 + 8));
-    HIPCHK(ctx, b->keep[(size_t)q].reserve(1, (size_t)b->n_cap * 16));
+    HIPCHK(ctx, b->keep[(size_t)q].reserve(1, (size_t)b->n_cap * (poses ? 17 : 16)));  // (a batch is a Dubins batch or not for life)
     for (hipEvent_t &e : b->ev_keep)
         if (!e) HIPCHK(ctx, hipEventCreate(&e));
     int32_t *anc[2] = {b->keep_tmp.as<int32_t>(), b->keep_tmp.as<int32_t>() + cap};
@@ -273,20 +287,37 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
     int32_t count = 0;
     if (j > 0) {
         const TreeRef t = tree_ref(b, q);
-        KeepView kv{};
-        kv.og = ctx->og;
-        kv.H = ctx->H;
-        kv.nodes = t.nodes;
-        kv.parent = t.parent;
-        kv.vcost = t.vcost;
-        kv.j = j;
-        kv.ok = ok[0];
-        kv.anc = anc[0];
-        const int per_wg = KEEP_TPB / 64;
-        const unsigned edge_wgs = (unsigned)((j + per_wg - 1) / per_wg > KEEP_MAX_WG ? KEEP_MAX_WG : (j + per_wg - 1) / per_wg);
         HIPCHK(ctx, hipEventRecord(b->ev_keep[0], ctx->stream));
-        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
-                           ctx->stream, kv);
+        if (poses) {  // one edge per lane, 64 a wavefront and round
+            PoseKeepView kv{};
+            kv.og = ctx->og;
+            kv.W = ctx->W;
+            kv.H = ctx->H;
+            kv.nodes = t.nodes;
+            kv.parent = t.parent;
+            kv.heading = t.heading;
+            kv.j = j;
+            kv.nh = d.nh;
+            kv.rho = d.rho;
+            kv.ok = ok[0];
+            kv.anc = anc[0];
+            hipLaunchKernelGGL(rrt_pose_keep_edge_kernel, dim3((unsigned)std::min((j + POSE_KEEP_TPB - 1) / POSE_KEEP_TPB, POSE_KEEP_MAX_WG)),
+                               dim3(POSE_KEEP_TPB), 0, ctx->stream, kv);
+        } else {  // one edge per wavefront
+            KeepView kv{};
+            kv.og = ctx->og;
+            kv.H = ctx->H;
+            kv.nodes = t.nodes;
+            kv.parent = t.parent;
+            kv.vcost = t.vcost;
+            kv.j = j;
+            kv.ok = ok[0];
+            kv.anc = anc[0];
+            const int per_wg = KEEP_TPB / 64;
+            const unsigned edge_wgs = (unsigned)((j + per_wg - 1) / per_wg > KEEP_MAX_WG ? KEEP_MAX_WG : (j + per_wg - 1) / per_wg);
+            hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
+                               ctx->stream, kv);
+        }
         HIPCHK(ctx, hipEventRecord(b->ev_keep[1], ctx->stream));
         // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
         int rounds = 1;
@@ -297,8 +328,8 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
                                (const int32_t *)anc[cur], ok[cur ^ 1], anc[cur ^ 1], j);
         HIPCHK(ctx, hipEventRecord(b->ev_keep[2], ctx->stream));
         KeepCompact kc{};
-        kc.nodes = kv.nodes;
-        kc.vcost = kv.vcost;
+        kc.nodes = t.nodes;
+        kc.vcost = t.vcost;
         kc.ok = ok[cur];
         kc.anc = anc[cur];
         kc.j = j;
@@ -308,6 +339,9 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
         kc.live_id = t.live_id;
         kc.count = d_count;
         hipLaunchKernelGGL(rrt_keep_compact_kernel, dim3(1), dim3(TPB), 0, ctx->stream, kc);
+        if (poses)
+            hipLaunchKernelGGL(rrt_pose_keep_gather_kernel, dim3((unsigned)((j + POSE_KEEP_TPB - 1) / POSE_KEEP_TPB)), dim3(POSE_KEEP_TPB), 0, ctx->stream,
+                               (const uint8_t *)t.heading, (const int32_t *)t.live_id, (const int32_t *)d_count, t.live_heading, j);
         HIPCHK(ctx, hipEventRecord(b->ev_keep[3], ctx->stream));
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
@@ -325,12 +359,21 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
 }
 
 extern "C" int rrt_batch_keep_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
-    return b ? keep_tree("rrt_batch_keep_tree", b, q, n_alive, alive) : fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree: NULL");
+    return b ? keep_tree("rrt_batch_keep_tree", b, q, n_alive, alive, false) : fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree: NULL");
 }
 
 extern "C" int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_keep_tree", NO_PLAN_NO_TREE);
-    return s ? keep_tree("rrt_plan_keep_tree", s, 0, n_alive, alive) : RRT_E_ARG;
+    return s ? keep_tree("rrt_plan_keep_tree", s, 0, n_alive, alive, false) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_keep_pose_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive) {
+    return b ? keep_tree("rrt_batch_keep_pose_tree", b, q, n_alive, alive, true) : fail(nullptr, RRT_E_ARG, "rrt_batch_keep_pose_tree: NULL");
+}
+
+extern "C" int rrt_plan_keep_pose_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_keep_pose_tree", NO_PLAN_NO_TREE);
+    return s ? keep_tree("rrt_plan_keep_pose_tree", s, 0, n_alive, alive, true) : RRT_E_ARG;
 }
 
 extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) {

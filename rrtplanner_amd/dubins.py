@@ -281,6 +281,24 @@ class _DubinsBase(RRT):
     def keep_tree_resident(self, grids, k=0):
         return self.keep_tree(None)
 
+    def keep_pose_tree(self, og_new):
+        """The map changed: keep the Dubins tree of the last plan() instead of planning again (rrt_plan_keep_pose_tree).  Like
+        set_og(og_new) -- og, free, the upload; a later plan() plans on og_new -- except that the tree stays on the device.  Returns
+        alive bool[j]: the vertices whose every edge on the way to the root is free on og_new.  An edge is the shortest Dubins word
+        from the parent's pose to the child's, swept as plan() swept it when it accepted the edge (a sample every 0.5 cells of arc
+        length, each inside the grid and on a free cell, then the child's cell); the root's cell must be free.  The Dubins loop
+        has no rewire, so an unchanged map keeps every vertex.  From here on connect_poses and paths_to_poses sweep on og_new and
+        consider only the alive vertices; the vertex numbers they return are those of the T plan() returned, and no cost changes.
+        No vertex alive: every pose answers -1 / inf.  Not cumulative: every call starts from the whole tree.
+
+        ValueError if og_new has another shape than the grid of the last plan(); RuntimeError as connect_poses."""
+        return self._keep_on("keep_pose_tree", og_new)
+
+    def keep_pose_tree_resident(self, grids, k=0):
+        """keep_pose_tree(grids.host[k]) for grids generated on this planner's device (oggen.DeviceGrids): frame k becomes the active
+        grid without an upload.  Raises like keep_pose_tree and set_og_resident."""
+        return self._keep_on_resident("keep_pose_tree", grids, k)
+
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""
         legs = []

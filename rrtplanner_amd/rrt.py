@@ -614,13 +614,17 @@ class RRT(object):
         child's side, and the line walk is not symmetric.
 
         ValueError if og_new has another shape than the grid of the last plan(); RuntimeError / ValueError as connect_goals."""
+        return self._keep_on("keep_tree", og_new)
+
+    def _keep_on(self, who: str, og_new) -> np.ndarray:
+        """the host steps of keep_tree and of the Dubins planners' keep_pose_tree; `who` is also the context's call"""
         og_new = np.asarray(og_new)
-        self._keep_guard("keep_tree", og_new.shape)
+        self._keep_guard(who, og_new.shape)
         self._tree_resident = None  # (until the call below has succeeded: a failure leaves no tree for this grid)
         self.og = og_new
         self.free = np.argwhere(og_new == 0)
         self._grid_dirty = True
-        alive = self._device().keep_tree()
+        alive = getattr(self._device(), who)()
         self._tree_resident = "device"
         self._grow_j0 = int(alive.sum())
         return alive
@@ -628,15 +632,19 @@ class RRT(object):
     def keep_tree_resident(self, grids, k: int = 0) -> np.ndarray:
         """keep_tree(grids.host[k]) for grids generated on this planner's device (oggen.DeviceGrids): frame k becomes the active
         grid without an upload, and the tree of the last plan() is kept on it.  Raises like keep_tree and set_og_resident."""
+        return self._keep_on_resident("keep_tree", grids, k)
+
+    def _keep_on_resident(self, who: str, grids, k: int) -> np.ndarray:
+        """the host steps of keep_tree_resident and of the Dubins planners' keep_pose_tree_resident; `who` is the context's call"""
         if self._ctx is None or grids.ctx is not self._ctx:
             raise ValueError("grids were generated on a different device context: use oggen.DeviceGrids(planner.device_context(), ...)")
-        self._keep_guard("keep_tree_resident", grids.host[k].shape)
+        self._keep_guard(who + "_resident", grids.host[k].shape)
         grids.select(k)  # checks the context's grid generation; when it raises nothing has changed and the tree stays
         self._tree_resident = None  # (until the call below has succeeded: a failure leaves no tree for this grid)
         self.og = grids.host[k]
         self.free = np.argwhere(self.og == 0)
         self._grid_dirty = False
-        alive = self._ctx.keep_tree()
+        alive = getattr(self._ctx, who)()
         self._tree_resident = "device"
         self._grow_j0 = int(alive.sum())
         return alive
@@ -919,6 +927,13 @@ class RRT(object):
     def connect_poses(self, poses):
         raise ValueError("connect_poses: a goal pose (x, y, heading) belongs to the Dubins planners (RRTDubins, RRTStarDubins); the goals of "
                          "this planner are cells: use connect_goals")
+
+    def keep_pose_tree(self, og_new):
+        raise ValueError("keep_pose_tree: an edge that is a Dubins word between poses belongs to the Dubins planners (RRTDubins, RRTStarDubins); "
+                         "the edges of this planner are straight lines: use keep_tree")
+
+    def keep_pose_tree_resident(self, grids, k=0):
+        return self.keep_pose_tree(None)
 
     def paths_to(self, T: nx.DiGraph, goals) -> list:
         """Routes from xstart to many goals over the tree T of the last plan(): one connect_goals call, then per goal the (k, 2)
