@@ -275,6 +275,45 @@ int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]);
  * times of rrt_batch_keep_tree_ms -- is rrt_batch_keep_tree's.  RRT_E_ARG as there.  RRT_E_UNSUPPORTED: not a Dubins batch (its call
  * is rrt_batch_keep_tree).  The scratch: 10 bytes a vertex of capacity, and 17 for each query that is kept. */
 int rrt_batch_keep_pose_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive);
+/* Finished routes from the start pose to m goal poses over the Dubins tree that query q left on the device, and optionally the path
+ * the vehicle drives along them, in one call (rrt_pose_routes.h).  rrt_batch_routes for a batch created with RRT_FLAG_DUBINS; there
+ * are no shortcuts (a shortcut changes words and headings).
+ *   vertex[g], cost[g]: exactly what rrt_batch_connect_poses gives (the same kernel decides them; after rrt_batch_keep_pose_tree over
+ *   the same view, in the original vertex numbers).
+ *   vertex[g] == -1: the route of g has 0 rows, no points, and length[g] = +inf.
+ *   Otherwise the route is root = vertex 0, ..., vertex[g] along the parent pointers, then the goal pose: k rows (x, y, h, id), id the
+ *   tree vertex, -1 for the goal row.
+ *   length[g]: the f64 sum, left to right from 0.0, of the lengths of the shortest Dubins words between consecutive rows.  The Dubins
+ *   loop prices vcost[child] = vcost[parent] + len and never rewires: length[g] == cost[g] bit for bit.
+ *   offsets[0..m]: CSR offsets into the rows of all goals, in goal order; offsets[m] is the row count.
+ *   flags & RRT_POSE_ROUTES_POINTS: the points of the routes as well.  Per leg, row r to row r + 1, the samples k * DUB_DS,
+ *   k = 0 .. floor(len / DUB_DS), of its word, in order: the f64 pair whose round-half-up is the cell the planner tested for that sample
+ *   (include/rrt_dubins_points.h); behind the last leg one more point, the goal cell.  Sample 0 of a leg is its start pose exactly; the
+ *   end pose of a leg is the next leg's sample 0 and is not repeated, except on a leg whose length is an exact multiple of DUB_DS,
+ *   whose last sample is its end pose: that point appears twice.  point_offsets[0..m]: CSR offsets into the points of all goals;
+ *   point_offsets[m] is the point count.  Without the flag point_offsets may be NULL and is not written.
+ * The rows and points stay on the batch: rrt_batch_pose_routes_rows and rrt_batch_pose_routes_points copy them out.  Refusals, and
+ * the batch afterwards, as for rrt_batch_connect_poses (one validation serves both calls; RRT_E_UNSUPPORTED for a batch created
+ * without RRT_FLAG_DUBINS, whose call is rrt_batch_routes); RRT_E_ARG also for flags other than RRT_POSE_ROUTES_POINTS, for poses whose
+ * routes have more than 2^24 rows or 2^27 points together (pass fewer poses per call).  m == 0: RRT_OK, offsets[0] = 0, nothing is
+ * launched.  RRT_E_HIP, before any row is written: a parent walk that is not at vertex 0 after j steps; before any point is written:
+ * a leg without a word or with a length that is not finite.  The first call allocates scratch on the batch (28 bytes a pose, 29 a
+ * row; with points 176 more a row and 16 a point), later calls grow it, the batch frees it.  Synchronous on the context's stream: it
+ * waits for the row count, for the answer and the point count, and with points for the points kernel. */
+#define RRT_POSE_ROUTES_POINTS 0x1u
+int rrt_batch_pose_routes(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                          int64_t *offsets, int64_t *point_offsets);
+/* The rows of the last rrt_batch_pose_routes on this batch: xyh is host (rows, 3) int32, id host int32[rows], rows == its offsets[m].
+ * RRT_E_ARG: NULL (with rows > 0); no rrt_batch_pose_routes on this batch yet, or its last one failed; rows differs from that call's
+ * total; an rrt_batch_launch, rrt_batch_rearm, rrt_batch_keep_pose_tree since. */
+int rrt_batch_pose_routes_rows(rrt_batch *b, int32_t *xyh, int32_t *id, int64_t rows);
+/* The points of the last rrt_batch_pose_routes with RRT_POSE_ROUTES_POINTS on this batch: xy is host (points, 2) f64,
+ * points == its point_offsets[m].  RRT_E_ARG as for the rows, and when that call did not ask for points. */
+int rrt_batch_pose_routes_points(rrt_batch *b, double *xy, int64_t points);
+/* kernel time in ms of the stages of the last successful rrt_batch_pose_routes (m > 0) on this batch, from events on the stream: the
+ * decision (the kernel of rrt_batch_connect_poses), depth and scan, rows + legs + lengths (+ the scan of the point counts), the points
+ * kernel (0 without points).  RRT_E_ARG when there is none. */
+int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]);
 /* Grow the finished tree of query q with m more samples (rrt_seed.h): seed + arm, then rrt_batch_launch / rrt_batch_sync /
  * rrt_batch_get_result as after rrt_batch_set_query.  RRTStandard and RRTStar, the default cost, the reference's rewire.
  *   seed   the alive vertices of the query's view (rrt_batch_keep_tree), in their original order, become vertices 0 .. *j0-1 of a new
@@ -358,6 +397,12 @@ int rrt_plan_keep_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive);
 int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]);
 /* rrt_batch_keep_pose_tree on the Dubins tree of the context's last rrt_plan (its stage times: rrt_plan_keep_tree_ms) */
 int rrt_plan_keep_pose_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *alive);
+/* rrt_batch_pose_routes and its companions on the Dubins tree of the context's last rrt_plan */
+int rrt_plan_pose_routes(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                         int64_t *offsets, int64_t *point_offsets);
+int rrt_plan_pose_routes_rows(rrt_ctx *ctx, int32_t *xyh, int32_t *id, int64_t rows);
+int rrt_plan_pose_routes_points(rrt_ctx *ctx, double *xy, int64_t points);
+int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]);
 /* *j = vertices of the finished tree of the context's last rrt_plan / rrt_plan_resume: the bytes rrt_plan_keep_tree writes into
  * `alive`.  RRT_E_ARG: NULL; no finished rrt_plan on this context. */
 int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j);

@@ -35,6 +35,7 @@ FLAG_ONEBODY = 128
 FLAG_NOPIPE1 = 32768
 FLAG_LARGE_GRID = 65536
 RRT_ROUTES_SHORTCUT = 1  # flags of rrt_batch_routes / rrt_plan_routes
+RRT_POSE_ROUTES_POINTS = 1  # flags of rrt_batch_pose_routes / rrt_plan_pose_routes
 WALK_AUTO, WALK_U24, WALK_U26, WALK_WIDE = 0, 1, 2, 3  # rrt_prim_collisionfree_walk
 
 
@@ -76,6 +77,8 @@ SYMBOLS = (
     "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
     "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
     "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
+    "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
+    "rrt_plan_pose_routes", "rrt_plan_pose_routes_rows", "rrt_plan_pose_routes_points", "rrt_plan_pose_routes_ms",
 )
 
 
@@ -190,6 +193,14 @@ def lib():
             "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
             "rrt_batch_keep_pose_tree": ([vp, i32, C.POINTER(i32), vp], C.c_int),
             "rrt_plan_keep_pose_tree": ([vp, C.POINTER(i32), vp], C.c_int),
+            "rrt_batch_pose_routes": ([vp, i32, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
+            "rrt_batch_pose_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
+            "rrt_batch_pose_routes_points": ([vp, vp, C.c_int64], C.c_int),
+            "rrt_batch_pose_routes_ms": ([vp, C.POINTER(C.c_float * 4)], C.c_int),
+            "rrt_plan_pose_routes": ([vp, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
+            "rrt_plan_pose_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
+            "rrt_plan_pose_routes_points": ([vp, vp, C.c_int64], C.c_int),
+            "rrt_plan_pose_routes_ms": ([vp, C.POINTER(C.c_float * 4)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -257,6 +268,28 @@ def _routes(handle, call, rows_call, goals, shortcut):
     ids = np.empty(rows, dtype=np.int32)
     _check(handle, rows_call(xy.ctypes.data, ids.ctypes.data, rows))
     return vertex, cost, length, offsets, xy, ids
+
+
+def _pose_routes(handle, call, rows_call, points_call, poses, points):
+    """the steps of a pose routes call: `call` decides and builds the routes on the device and gives the CSR offsets, `rows_call` and,
+    with points, `points_call` copy the rows and the points out.  (vertex, cost, length, offsets int64[M + 1], xyh int32[(rows, 3)],
+    ids int32[rows]) and with points (point_offsets int64[M + 1], pts float64[(P, 2)]) behind them"""
+    g, vertex, cost = _pose_arrays(poses)
+    m = g.shape[0]
+    length = np.full(m, np.inf, dtype=np.float64)
+    offsets = np.zeros(m + 1, dtype=np.int64)
+    point_offsets = np.zeros(m + 1, dtype=np.int64) if points else None
+    _check(handle, call(g.ctypes.data, m, RRT_POSE_ROUTES_POINTS if points else 0, vertex.ctypes.data, cost.ctypes.data, length.ctypes.data,
+                        offsets.ctypes.data, point_offsets.ctypes.data if points else None))
+    rows = int(offsets[m])
+    xyh = np.empty((rows, 3), dtype=np.int32)
+    ids = np.empty(rows, dtype=np.int32)
+    _check(handle, rows_call(xyh.ctypes.data, ids.ctypes.data, rows))
+    if not points:
+        return vertex, cost, length, offsets, xyh, ids
+    pts = np.empty((int(point_offsets[m]), 2), dtype=np.float64)
+    _check(handle, points_call(pts.ctypes.data, pts.shape[0]))
+    return vertex, cost, length, offsets, xyh, ids, point_offsets, pts
 
 
 def _keep_tree(handle, call, size, j):
@@ -473,6 +506,19 @@ class Context:
         """rrt_plan_routes + rrt_plan_routes_rows: Batch.routes on the tree of this context's last plan() / plan_resume()"""
         L = lib()
         return _routes(self._h, lambda *a: L.rrt_plan_routes(self._h, *a), lambda *a: L.rrt_plan_routes_rows(self._h, *a), goals, shortcut)
+
+    def pose_routes(self, poses, points=False):
+        """rrt_plan_pose_routes + rrt_plan_pose_routes_rows (+ rrt_plan_pose_routes_points): Batch.pose_routes on the Dubins tree of this
+        context's last plan()"""
+        L = lib()
+        return _pose_routes(self._h, lambda *a: L.rrt_plan_pose_routes(self._h, *a), lambda *a: L.rrt_plan_pose_routes_rows(self._h, *a),
+                            lambda *a: L.rrt_plan_pose_routes_points(self._h, *a), poses, points)
+
+    def pose_routes_ms(self):
+        """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
+        ms = (C.c_float * 4)()
+        _check(self._h, lib().rrt_plan_pose_routes_ms(self._h, C.byref(ms)))
+        return tuple(ms)
 
     def keep_tree(self):
         """rrt_plan_keep_tree: Batch.keep_tree on the tree of this context's last plan() / plan_resume()"""
@@ -723,6 +769,24 @@ class Batch:
         L = lib()
         return _routes(self.ctx.handle, lambda *a: L.rrt_batch_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_routes_rows(self._h, *a), goals, shortcut)
 
+    def pose_routes(self, q, poses, points=False):
+        """rrt_batch_pose_routes + rrt_batch_pose_routes_rows (+ rrt_batch_pose_routes_points): finished routes from the start pose to
+        the goal poses (M, 3) over the Dubins tree of query q, built on the device.  Returns (vertex, cost, length float64[M], offsets
+        int64[M + 1], xyh int32[(rows, 3)], ids int32[rows]): vertex and cost as connect_poses gives them; the route of pose g is
+        xyh[offsets[g]:offsets[g + 1]], the poses root .. vertex[g] along the tree and then the goal pose, ids the tree vertices and -1
+        for the goal row; no rows and length inf where vertex is -1; length == cost bit for bit elsewhere.  points=True: two more,
+        (point_offsets int64[M + 1], pts float64[(P, 2)]): the vehicle's path of pose g is pts[point_offsets[g]:point_offsets[g + 1]],
+        per leg the samples every 0.5 cells of arc length of its Dubins word that the planner tested, then the goal cell."""
+        L = lib()
+        return _pose_routes(self.ctx.handle, lambda *a: L.rrt_batch_pose_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_pose_routes_rows(self._h, *a),
+                            lambda *a: L.rrt_batch_pose_routes_points(self._h, *a), poses, points)
+
+    def pose_routes_ms(self):
+        """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
+        ms = (C.c_float * 4)()
+        _check(self.ctx.handle, lib().rrt_batch_pose_routes_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
     def keep_tree(self, q):
         """rrt_batch_keep_tree: keep the finished tree of query q on the context's CURRENT grid (set_grid / select_frame since the
         query ran; same shape).  Returns alive bool[j]: the vertices whose edges up to the root are all free on it, each edge walked
@@ -770,6 +834,19 @@ class Batch:
         ms = (C.c_float * 3)()
         _check(self.ctx.handle, lib().rrt_batch_grow_ms(self._h, C.byref(ms), 3))
         return tuple(ms)
+
+    def pose_routes_rows(self, rows):
+        """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, which left `rows` rows"""
+        xyh = np.empty((int(rows), 3), dtype=np.int32)
+        ids = np.empty(int(rows), dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_pose_routes_rows(self._h, xyh.ctypes.data, ids.ctypes.data, int(rows)))
+        return xyh, ids
+
+    def pose_routes_points(self, points):
+        """rrt_batch_pose_routes_points alone: the points of the last pose_routes(points=True) call, which left `points` points"""
+        pts = np.empty((int(points), 2), dtype=np.float64)
+        _check(self.ctx.handle, lib().rrt_batch_pose_routes_points(self._h, pts.ctypes.data, int(points)))
+        return pts
 
     def routes_rows(self, rows):
         """rrt_batch_routes_rows alone: (xy, ids) of the last routes() call, which left `rows` rows"""

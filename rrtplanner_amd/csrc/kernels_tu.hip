@@ -36,10 +36,12 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #elif RRT_TU == 8  // grow a finished tree: its loop state rebuilt from the alive vertices (rrt_seed_*_kernel): not a team kernel
 #include "rrt_seed.h"
 
-#elif RRT_TU == 9  // a finished Dubins tree: many goal poses against it (rrt_pose_goals_kernel), and the tree kept when the map changes
-                   // (rrt_pose_keep_*_kernel): not team kernels
+#elif RRT_TU == 9  // a finished Dubins tree: many goal poses against it (rrt_pose_goals_kernel), the tree kept when the map changes
+                   // (rrt_pose_keep_*_kernel), routes to many goal poses and the vehicle's path along them (rrt_pose_route_*_kernel):
+                   // not team kernels
 #include "rrt_pose_goals.h"
 #include "rrt_pose_keep.h"
+#include "rrt_pose_routes.h"
 
 #else  // teams of compute units: the variants that rrt_block_variants.def (included by rrt_block.h) deals to this unit
 #include "rrt_block.h"

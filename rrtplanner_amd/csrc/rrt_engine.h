@@ -189,6 +189,16 @@ struct rrt_batch {
     DevBuf route_goal;                   // [length | raw_off | fin_off | cnt | kept | err] for route_goal.cap goals
     DevBuf route_row;                    // [row_xy | row_id | out_xy | out_id] for route_row.cap rows
     int64_t route_rows = -1;             // dense rows the last rrt_batch_routes left for rrt_batch_routes_rows; -1: none (launch, rearm)
+    // rrt_batch_pose_routes: per-goal arrays, per-row arrays, the legs' sweeps and the points (rrt_pose_routes.h).  Carved by the capacity
+    // they were allocated with; the last two are allocated by the first call that asks for points.
+    DevBuf pose_route_goal;              // [length f64 | raw_off i64 + 1 | goal_pt_off i64 + 1 | cnt i32 | err i32] for pose_route_goal.cap goals
+    DevBuf pose_route_row;               // [leg_len f64 | pt_off i64 + 1 | row_xy u32 | row_id i32 | npts i32 | row_h u8] for pose_route_row.cap rows
+    DevBuf pose_route_sweep;             // dub_sweep_t [rows]
+    DevBuf pose_route_pts;               // f64 [points][2]
+    int64_t pose_route_rows = -1;        // rows the last rrt_batch_pose_routes left for rrt_batch_pose_routes_rows; -1: none (launch, rearm, keep, grow)
+    int64_t pose_route_points = -1;      // ... and points for rrt_batch_pose_routes_points; -1: none, or that call did not ask for points
+    hipEvent_t ev_pose_route[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // a pair around each of its four stages
+    int pose_route_timed = 0;            // stages of the last successful rrt_batch_pose_routes that ran (0: none, 3: no points, 4)
     // rrt_batch_keep_tree / rrt_batch_keep_pose_tree: the views of the queries that were kept on a new map (rrt_keep.h, rrt_pose_keep.h),
     // allocated at the first call per query
     std::vector<DevBuf> keep;            // [Q] empty, or [live_vcost f64 | live_nodes u32 | live_id i32 | a Dubins batch: live_heading u8], each of n_cap

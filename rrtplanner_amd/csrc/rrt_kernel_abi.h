@@ -224,6 +224,42 @@ struct PoseKeepView {
     int32_t *anc;            // [j] out of the edge test: the parent, 0 for the root, k itself for a parent outside [0, j)
 };
 
+// ---- rrt_pose_routes.h ----
+constexpr int POSE_ROUTE_TPB = 256;                         // goals, rows or points per workgroup (one per lane)
+constexpr int POSE_ROUTE_MAX_WG = 2048;                     // workgroups of the leg and the points kernel, grid-stride beyond
+constexpr size_t POSE_ROUTE_SWEEP_BYTES = 176;              // sizeof(dub_sweep_t) (include/rrt_dubins.h), which no host unit includes
+constexpr size_t POSE_ROUTE_ROW_BUDGET = (size_t)1 << 24;   // rows of one call (33 bytes of device memory each, 209 with points: 3.3 GiB)
+constexpr size_t POSE_ROUTE_POINT_BUDGET = (size_t)1 << 27; // points of one call (16 bytes of device memory each: 2 GiB)
+constexpr int POSE_ROUTE_LEG_POINTS = 1 << 19;              // samples of one leg the kernels accept (rrt_route_scan_kernel sums 1024 counts in 32 bits)
+
+struct PoseRoutesView {
+    int32_t W, H;
+    const uint32_t *nodes;   // the query's packed vertices
+    const int32_t *parent;
+    const uint8_t *heading;  // ... and their heading indices
+    int32_t nh;              // the query's discrete headings
+    double rho;              // ... and turning radius
+    const uint32_t *goals;   // [m] cells packed like vertices
+    const uint8_t *goal_h;   // [m] heading indices
+    const int32_t *vertex;   // [m] what the pose goals kernel decided
+    int32_t m;
+    const int32_t *cnt;      // [m] rows of a goal (rrt_route_depth_kernel)
+    const int64_t *raw_off;  // [m + 1] exclusive scan of cnt
+    double *length;          // [m]
+    int64_t *goal_pt_off;    // [m + 1] the point offset of a goal's first row; null without points
+    int32_t *err;            // bit 0: a parent walk did not end at vertex 0; bit 1: a leg without a word, or one too long
+    int64_t rows;            // raw_off[m]
+    uint32_t *row_xy;        // [rows] packed cells
+    uint8_t *row_h;          // [rows] heading indices
+    int32_t *row_id;         // [rows] the vertex, -1 for a goal row
+    double *leg_len;         // [rows] length of the word from row r to row r + 1; 0 for a goal row
+    int32_t *npts;           // [rows] points of the leg; null without points
+    int64_t *pt_off;         // [rows + 1] exclusive scan of npts
+    void *sweep_bytes;       // [rows] dub_sweep_t of the legs (POSE_ROUTE_SWEEP_BYTES each); null without points
+    int64_t npoints;         // pt_off[rows]
+    double2 *points;         // [npoints]
+};
+
 // ---- rrt_seed.h ----
 constexpr int SEED_TPB = 256;                            // one slot / vertex per lane; records: 4 wavefronts a workgroup
 constexpr int SEED_WG = 64;                               // workgroups of the records kernel
@@ -293,6 +329,11 @@ __global__ __launch_bounds__(KEEP_TPB) void rrt_keep_remap_kernel(int32_t *verte
 __global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_edge_kernel(PoseKeepView kv);
 __global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_gather_kernel(const uint8_t *heading, const int32_t *live_id, const int32_t *count,
                                                                             uint8_t *live_heading, int32_t j);
+// rrt_pose_routes.h (unit 9, beside the other pose kernels)
+__global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_fill_kernel(PoseRoutesView pr);
+__global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_leg_kernel(PoseRoutesView pr);
+__global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_length_kernel(PoseRoutesView pr);
+__global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_points_kernel(PoseRoutesView pr);
 // rrt_seed.h (unit 8)
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv);

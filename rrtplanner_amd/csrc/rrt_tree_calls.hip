@@ -1,6 +1,6 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, keep_tree, keep_pose_tree, grow and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_keep.h, rrt_pose_keep.h and rrt_seed.h.  What the calls share comes first and is written once:
+// routes, pose_routes, keep_tree, keep_pose_tree, grow and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h and rrt_seed.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
@@ -167,11 +167,17 @@ extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int
 
 // ---- many goal poses against a finished Dubins tree (rrt_pose_goals.h) ----
 // The conditions are goals_decide's, for a batch created with RRT_FLAG_DUBINS; a goal is a pose (x, y, h), h < the query's nh.
-static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+// The part that rrt_batch_connect_poses and rrt_batch_pose_routes share, as goals_decide serves the straight-line calls: every refusal
+// (`use`: the call a straight-line batch is sent to), the poses packed and uploaded, the scratch, and the pose goals kernel launched
+// on the context's stream.  Nothing is read back and nothing waited for.  m == 0: RRT_OK, nothing launched.  pose_last_m is left at -1
+// (the counters are being rewritten) for the caller to set once its call has succeeded.
+// ev: nullptr, or two events to create if need be and to record around the upload and the kernel.
+static int poses_decide(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, bool null_out, const char *use,
+                        hipEvent_t *ev = nullptr) {
     rrt_ctx *ctx = b->ctx;
-    if (!poses_xyh || !vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (!poses_xyh || null_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     if (!(b->flags & RRT_FLAG_DUBINS))
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use rrt_batch_connect_goals)", who);
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use %s)", who, use);
     if (const int rc = refuse_goals_call(who, b, q, m, "goal poses")) return rc;
     const QDesc &d = b->h_desc[(size_t)q];
     const int W = ctx->W, H = ctx->H;
@@ -213,13 +219,22 @@ static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t
     pv.vertex = b->goal_vertex.as<int32_t>();
     pv.cost = b->goal_cost.as<double>();
     pv.counts = b->pose_counts.as<uint32_t>();
+    for (int k = 0; ev && k < 2; ++k)
+        if (!ev[k]) HIPCHK(ctx, hipEventCreate(&ev[k]));
+    if (ev) HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->goal_xy.p, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->pose_h.p, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
     if (view)
         hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, pv.vertex,
                            (const int32_t *)t.live_id, m, pv.j);
+    if (ev) HIPCHK(ctx, hipEventRecord(ev[1], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
+    return RRT_OK;
+}
+
+static int connect_poses(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, int32_t *vertex, double *cost) {
+    if (const int rc = poses_decide(who, b, q, poses_xyh, m, !vertex || !cost, "rrt_batch_connect_goals"); rc != RRT_OK || m == 0) return rc;
     if (const int rc = fetch_goal_answers(b, m, vertex, cost)) return rc;
     b->pose_last_m = m;
     return RRT_OK;
@@ -353,7 +368,7 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
     b->ran_gen[(size_t)q] = ctx->grid_gen;
     b->ran_og[(size_t)q] = ctx->og;
     b->keep_alive[(size_t)q] = count;
-    b->route_rows = -1;  // the rows of an earlier routes call belong to another view
+    b->route_rows = b->pose_route_rows = b->pose_route_points = -1;  // the rows of an earlier routes call belong to another view
     *n_alive = count;
     return RRT_OK;
 }
@@ -443,7 +458,7 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
         if (!e) HIPCHK(ctx, hipEventCreate(&e));
     // ---- from here on the query is being replaced ----
     b->seed_timed = false;
-    b->route_rows = -1;
+    b->route_rows = b->pose_route_rows = b->pose_route_points = -1;
     d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
     SeedView sv{};
     sv.nodes = t.nodes;
@@ -653,4 +668,225 @@ extern "C" int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m,
 extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_routes_rows", "no routes (no rrt_plan on this context yet, or its batch is gone)");
     return s ? batch_routes_rows("rrt_plan_routes_rows", s, xy, id, rows) : RRT_E_ARG;
+}
+
+// ---- finished routes to many goal poses, and the vehicle's path along them (rrt_pose_routes.h) ----
+static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
+                             double *length, int64_t *offsets, int64_t *point_offsets) {
+    rrt_ctx *ctx = b->ctx;
+    b->pose_route_rows = b->pose_route_points = -1;  // whatever happens below, the rows and points of an earlier call are gone
+    b->pose_route_timed = 0;
+    if (flags & ~(uint32_t)RRT_POSE_ROUTES_POINTS) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_POSE_ROUTES_POINTS is defined", who, flags);
+    const bool pts = (flags & RRT_POSE_ROUTES_POINTS) != 0;
+    if (const int rc = poses_decide(who, b, q, poses_xyh, m, !vertex || !cost || !length || !offsets || (pts && !point_offsets), "rrt_batch_routes",
+                                    b->ev_pose_route);
+        rc != RRT_OK)
+        return rc;
+    if (m == 0) {
+        offsets[0] = 0;
+        if (point_offsets) point_offsets[0] = 0;
+        b->pose_route_rows = 0;
+        b->pose_route_points = pts ? 0 : -1;
+        return RRT_OK;
+    }
+    for (hipEvent_t &e : b->ev_pose_route)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    // [length f64 m | raw_off i64 m+1 | goal_pt_off i64 m+1 | cnt i32 m | err i32]
+    HIPCHK(ctx, b->pose_route_goal.reserve(m, (size_t)m * 28 + 2 * sizeof(int64_t) + sizeof(int32_t)));
+    const size_t cap = (size_t)b->pose_route_goal.cap;
+    const QDesc &d = b->h_desc[(size_t)q];
+    const TreeRef t = tree_ref(b, q);  // (the whole tree: the vertex numbers the decision answers in are its own, after a keep too)
+    PoseRoutesView pr{};
+    pr.W = ctx->W;
+    pr.H = ctx->H;
+    pr.nodes = t.nodes;
+    pr.parent = t.parent;
+    pr.heading = t.heading;
+    pr.nh = d.nh;
+    pr.rho = d.rho;
+    pr.goals = b->goal_xy.as<uint32_t>();
+    pr.goal_h = b->pose_h.as<uint8_t>();
+    pr.vertex = b->goal_vertex.as<int32_t>();
+    pr.m = m;
+    pr.length = b->pose_route_goal.as<double>();
+    int64_t *raw_off = reinterpret_cast<int64_t *>(pr.length + cap);
+    pr.raw_off = raw_off;
+    pr.goal_pt_off = pts ? raw_off + cap + 1 : nullptr;
+    int32_t *cnt = reinterpret_cast<int32_t *>(raw_off + 2 * (cap + 1));
+    pr.cnt = cnt;
+    pr.err = cnt + cap;
+    // the depth pass and the scan are rrt_routes.h's, as they are: they read vertex / parent / j / m and write cnt / err / raw_off
+    RoutesView rv{};
+    rv.parent = t.parent;
+    rv.j = d.j;
+    rv.vertex = pr.vertex;
+    rv.m = m;
+    rv.cnt = cnt;
+    rv.raw_off = raw_off;
+    rv.err = pr.err;
+    const unsigned goals_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB);
+    HIPCHK(ctx, hipMemsetAsync(pr.err, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[2], ctx->stream));
+    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(goals_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)cnt, raw_off, m);
+    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[3], ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    // the first wait that the sizes force: the rows of all routes together decide how much memory the rows need
+    int64_t rows = 0;
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&rows, raw_off + m, sizeof rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, pr.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err)
+        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
+    if (rows < 0 || (uint64_t)rows > POSE_ROUTE_ROW_BUDGET)
+        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d poses have %lld rows together, at most %zu per call: pass fewer poses at a time", who, m,
+                    (long long)rows, POSE_ROUTE_ROW_BUDGET);
+    int64_t npoints = 0;
+    // [leg_len f64 | pt_off i64 + 1 | row_xy u32 | row_id i32 | npts i32 | row_h u8], each of rows (no row: pt_off alone, one zero)
+    HIPCHK(ctx, b->pose_route_row.reserve(std::max<int64_t>(rows, 1), (size_t)std::max<int64_t>(rows, 1) * 29 + sizeof(int64_t)));
+    if (pts && rows > 0) HIPCHK(ctx, b->pose_route_sweep.reserve(rows, (size_t)rows * POSE_ROUTE_SWEEP_BYTES));
+    const size_t rcap = (size_t)b->pose_route_row.cap;
+    pr.rows = rows;
+    pr.leg_len = b->pose_route_row.as<double>();
+    pr.pt_off = reinterpret_cast<int64_t *>(pr.leg_len + rcap);
+    pr.row_xy = reinterpret_cast<uint32_t *>(pr.pt_off + rcap + 1);
+    pr.row_id = reinterpret_cast<int32_t *>(pr.row_xy + rcap);
+    pr.npts = pts ? pr.row_id + rcap : nullptr;
+    pr.row_h = reinterpret_cast<uint8_t *>(pr.row_id + 2 * rcap);
+    pr.sweep_bytes = pts ? b->pose_route_sweep.p : nullptr;
+    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[4], ctx->stream));
+    if (rows > 0) {
+        const unsigned rows_grid = (unsigned)std::min<int64_t>((rows + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
+        hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+        hipLaunchKernelGGL(rrt_pose_route_leg_kernel, dim3(rows_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+        // a leg's count is at most POSE_ROUTE_LEG_POINTS = 2^19 (the leg kernel raises err beyond, and a word whose every sample lies inside
+        // a grid of 2048 x 2048 cells has some 55 000 at most): the 1024 counts of a pass of the scan sum below 2^32, as its rows do
+        if (pts) hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)pr.npts, pr.pt_off, (int32_t)rows);
+    } else if (pts) {
+        HIPCHK(ctx, hipMemsetAsync(pr.pt_off, 0, sizeof(int64_t), ctx->stream));  // (nothing connects: no point)
+    }
+    hipLaunchKernelGGL(rrt_pose_route_length_kernel, dim3((unsigned)((m + 1 + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[5], ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(length, pr.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(offsets, raw_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, pr.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    if (pts) HIPCHK(ctx, hipMemcpyAsync(point_offsets, pr.goal_pt_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    // the second wait (with points: the points of all legs together decide how much memory the points need)
+    if (const int rc = fetch_goal_answers(b, m, vertex, cost)) return rc;
+    if (err)
+        return fail(ctx, RRT_E_HIP, "%s: a leg of a route of query %d has no Dubins word, or a length that is not finite or beyond %d samples: the tree on the "
+                    "device is not one the planner built", who, q, POSE_ROUTE_LEG_POINTS);
+    if (offsets[m] != rows) return fail(ctx, RRT_E_HIP, "%s: %lld rows of %lld", who, (long long)offsets[m], (long long)rows);
+    if (pts) {
+        npoints = point_offsets[m];
+        if (npoints < 0 || (uint64_t)npoints > POSE_ROUTE_POINT_BUDGET)
+            return fail(ctx, RRT_E_ARG, "%s: the routes of these %d poses have %lld points together, at most %zu per call: pass fewer poses at a time", who, m,
+                        (long long)npoints, POSE_ROUTE_POINT_BUDGET);
+        if (npoints > 0) {
+            HIPCHK(ctx, b->pose_route_pts.reserve(npoints, (size_t)npoints * sizeof(double2)));
+            pr.npoints = npoints;
+            pr.points = b->pose_route_pts.as<double2>();
+            const unsigned pts_grid = (unsigned)std::min<int64_t>((npoints + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
+            HIPCHK(ctx, hipEventRecord(b->ev_pose_route[6], ctx->stream));
+            hipLaunchKernelGGL(rrt_pose_route_points_kernel, dim3(pts_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+            HIPCHK(ctx, hipEventRecord(b->ev_pose_route[7], ctx->stream));
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (so that a fault of the kernel is this call's, and the stage times are there)
+        }
+    }
+    b->pose_last_m = m;
+    b->pose_route_rows = rows;
+    b->pose_route_points = pts ? npoints : -1;
+    b->pose_route_timed = pts && npoints > 0 ? 4 : 3;
+    return RRT_OK;
+}
+
+static int batch_pose_routes_rows(const char *who, rrt_batch *b, int32_t *xyh, int32_t *id, int64_t rows) {
+    rrt_ctx *ctx = b->ctx;
+    if (b->pose_route_rows < 0)
+        return fail(ctx, RRT_E_ARG, "%s: no routes on this batch (no rrt_batch_pose_routes call yet, one that failed, or a launch, rearm, keep or grow since)", who);
+    if (rows != b->pose_route_rows)
+        return fail(ctx, RRT_E_ARG, "%s: rows=%lld, the last rrt_batch_pose_routes call left %lld", who, (long long)rows, (long long)b->pose_route_rows);
+    if (rows == 0) return RRT_OK;
+    if (!xyh || !id) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t rcap = (size_t)b->pose_route_row.cap;
+    const uint32_t *row_xy = reinterpret_cast<const uint32_t *>(reinterpret_cast<const int64_t *>(b->pose_route_row.as<double>() + rcap) + rcap + 1);
+    const int32_t *row_id = reinterpret_cast<const int32_t *>(row_xy + rcap);
+    const uint8_t *row_h = reinterpret_cast<const uint8_t *>(row_id + 2 * rcap);
+    b->stage.resize((size_t)rows);
+    b->stage8.resize((size_t)rows);
+    HIPCHK(ctx, hipMemcpyAsync(b->stage.data(), row_xy, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b->stage8.data(), row_h, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(id, row_id, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    for (int64_t r = 0; r < rows; ++r) {
+        const uint32_t p = b->stage[(size_t)r];
+        xyh[3 * r] = (int32_t)(p & 0xffffu);
+        xyh[3 * r + 1] = (int32_t)(p >> 16);
+        xyh[3 * r + 2] = (int32_t)b->stage8[(size_t)r];
+    }
+    return RRT_OK;
+}
+
+static int batch_pose_routes_points(const char *who, rrt_batch *b, double *xy, int64_t points) {
+    rrt_ctx *ctx = b->ctx;
+    if (b->pose_route_points < 0)
+        return fail(ctx, RRT_E_ARG, "%s: no points on this batch (no rrt_batch_pose_routes call with RRT_POSE_ROUTES_POINTS yet, one that failed, or a launch, "
+                    "rearm, keep or grow since)", who);
+    if (points != b->pose_route_points)
+        return fail(ctx, RRT_E_ARG, "%s: points=%lld, the last rrt_batch_pose_routes call left %lld", who, (long long)points, (long long)b->pose_route_points);
+    if (points == 0) return RRT_OK;
+    if (!xy) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(xy, b->pose_route_pts.p, (size_t)points * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_pose_routes(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                                     int64_t *offsets, int64_t *point_offsets) {
+    return b ? batch_pose_routes("rrt_batch_pose_routes", b, q, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets)
+             : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes: NULL");
+}
+
+extern "C" int rrt_batch_pose_routes_rows(rrt_batch *b, int32_t *xyh, int32_t *id, int64_t rows) {
+    return b ? batch_pose_routes_rows("rrt_batch_pose_routes_rows", b, xyh, id, rows) : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes_rows: NULL");
+}
+
+extern "C" int rrt_batch_pose_routes_points(rrt_batch *b, double *xy, int64_t points) {
+    return b ? batch_pose_routes_points("rrt_batch_pose_routes_points", b, xy, points) : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes_points: NULL");
+}
+
+extern "C" int rrt_plan_pose_routes(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                                    int64_t *offsets, int64_t *point_offsets) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes", NO_PLAN_NO_TREE);
+    return s ? batch_pose_routes("rrt_plan_pose_routes", s, 0, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets) : RRT_E_ARG;
+}
+
+extern "C" int rrt_plan_pose_routes_rows(rrt_ctx *ctx, int32_t *xyh, int32_t *id, int64_t rows) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes_rows", "no routes (no rrt_plan on this context yet, or its batch is gone)");
+    return s ? batch_pose_routes_rows("rrt_plan_pose_routes_rows", s, xyh, id, rows) : RRT_E_ARG;
+}
+
+extern "C" int rrt_plan_pose_routes_points(rrt_ctx *ctx, double *xy, int64_t points) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes_points", "no points (no rrt_plan on this context yet, or its batch is gone)");
+    return s ? batch_pose_routes_points("rrt_plan_pose_routes_points", s, xy, points) : RRT_E_ARG;
+}
+
+// kernel time in ms of the stages of the last successful rrt_batch_pose_routes: the decision (the pose goals kernel), depth and scan,
+// rows + legs + lengths (+ the scan of the point counts), the points (0 for a call without points, or without a point)
+extern "C" int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes_ms: NULL");
+    if (!b->pose_route_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_routes_ms: no rrt_batch_pose_routes with a pose on this batch yet, or its last one failed");
+    ms[3] = 0.f;
+    for (int k = 0; k < b->pose_route_timed; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_pose_route[2 * k], b->ev_pose_route[2 * k + 1]));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes_ms", NO_PLAN);
+    return s ? rrt_batch_pose_routes_ms(s, ms) : RRT_E_ARG;
 }

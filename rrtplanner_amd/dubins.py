@@ -274,6 +274,36 @@ class _DubinsBase(RRT):
     def routes_to(self, goals, shortcut=False):
         return self.connect_goals(goals)
 
+    def routes_to_poses(self, poses, points=False):
+        """Finished routes from xstart to many goal poses over the tree of the last plan(), built on the device in one call
+        (rrt_plan_pose_routes): connect_poses' decision, the parent walks, the lengths and, with points=True, the path the vehicle
+        drives.
+
+        Returns (routes, length) or, with points=True, (routes, length, paths).  routes[g] is the (k, 3) int64 array of poses
+        (x, y, heading index) xstart .. goal pose that paths_to_poses gives, or None where no vertex connects; length float64[M] is the
+        sum of the legs' Dubins words from xstart on -- equal to connect_poses' cost bit for bit --, inf for None.  paths[g] is the
+        (P, 2) float64 path: per leg the points every 0.5 cells of arc length from its start pose on, the very samples whose cells
+        plan() / connect_poses / keep_pose_tree tested (floor(p + 0.5) of every point is a free cell), then the goal cell; a leg's end
+        pose is the next leg's first point and is not repeated, except where a leg's length is an exact multiple of 0.5: that point
+        appears twice.  None where no vertex connects.
+        Heading -1 (any arrival heading) is resolved first, by one connect_poses call for those poses.  It takes no T: the tree is the
+        one resident on the device.  RuntimeError / ValueError as connect_poses."""
+        g = self._pose_array(poses)
+        if self._tree_resident is None:
+            raise RuntimeError("routes_to_poses: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        anyh = np.flatnonzero(g[:, 2] < 0)
+        if anyh.size:
+            g = g.copy()
+            vertex, _, heading = self.connect_poses(g[anyh])
+            g[anyh, 2] = np.where(vertex >= 0, heading, 0)  # (nothing connects under any heading: nor under heading 0)
+        out = self._device().pose_routes(g, points=points)
+        vertex, length, offsets, xyh = out[0], out[2], out[3], out[4].astype(np.int64)
+        routes = [xyh[offsets[k]:offsets[k + 1]] if vertex[k] >= 0 else None for k in range(len(g))]
+        if not points:
+            return routes, length
+        po, pts = out[6], out[7]
+        return routes, length, [pts[po[k]:po[k + 1]] if vertex[k] >= 0 else None for k in range(len(g))]
+
     def keep_tree(self, og_new):
         raise ValueError("keep_tree: a Dubins planner's edge is a Dubins word between poses; the edge test walks straight lines "
                          "(RRTStandard, RRTStar, RRTStarInformed only)")

@@ -928,6 +928,10 @@ class RRT(object):
         raise ValueError("connect_poses: a goal pose (x, y, heading) belongs to the Dubins planners (RRTDubins, RRTStarDubins); the goals of "
                          "this planner are cells: use connect_goals")
 
+    def routes_to_poses(self, poses, points=False):
+        raise ValueError("routes_to_poses: a goal pose (x, y, heading) belongs to the Dubins planners (RRTDubins, RRTStarDubins); the goals of "
+                         "this planner are cells: use routes_to")
+
     def keep_pose_tree(self, og_new):
         raise ValueError("keep_pose_tree: an edge that is a Dubins word between poses belongs to the Dubins planners (RRTDubins, RRTStarDubins); "
                          "the edges of this planner are straight lines: use keep_tree")
