@@ -346,6 +346,17 @@ int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m
  * renumbering and node slots, ms[1] the `sampled` bitmap, ms[2] the cell records; the first `count` (1 .. 3) are written.
  * RRT_E_ARG when there is none. */
 int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count);
+/* rrt_batch_grow for a batch created with RRT_FLAG_DUBINS (Dubins-RRT and Dubins-RRT*): samples_xyh holds m rows (x, y, h) of int32, a
+ * cell and a heading index in [0, nh) of the query.  The seed is rrt_batch_grow's -- the alive vertices of the view that
+ * rrt_batch_keep_pose_tree installed, else the whole tree -- and keeps every vertex's heading beside its point and cost; `sampled` is
+ * keyed on the cell, as the Dubins loop keys it, so the cell of a cut vertex and the start's can be drawn again; the loop is the Dubins
+ * planners' (nearest on (x, y), the shortest word nearest -> sample and its sweep, choose parent in ascending index with strict <), the
+ * goal decision the one for the query's own goal pose.  Afterwards rrt_batch_connect_poses, rrt_batch_pose_routes,
+ * rrt_batch_keep_pose_tree and a further rrt_batch_grow_poses work on the grown tree in its new numbering.  The stage times are
+ * rrt_batch_grow_ms's (the heading bytes are part of ms[0]).  Refusals as rrt_batch_grow, and RRT_E_ARG for a heading outside
+ * [0, nh); RRT_E_UNSUPPORTED for a batch created without RRT_FLAG_DUBINS (rrt_batch_grow is its call).  rrt_batch_grow keeps
+ * refusing a Dubins batch. */
+int rrt_batch_grow_poses(rrt_batch *b, int32_t q, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -411,6 +422,9 @@ int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j);
  * rrt_plan_keep_tree_ms is to rrt_plan_keep_tree: a caller of rrt_plan holds no rrt_batch to ask (RRT.grow, tools/grow_wall.py). */
 int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
 int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count);
+/* rrt_batch_grow_poses on the Dubins tree of the context's last rrt_plan, launch, sync and result included (out->head too);
+ * rrt_plan_grow_ms gives its stage times. */
+int rrt_plan_grow_poses(rrt_ctx *ctx, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

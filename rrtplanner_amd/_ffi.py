@@ -75,6 +75,7 @@ SYMBOLS = (
     "rrt_batch_routes", "rrt_batch_routes_rows", "rrt_plan_routes", "rrt_plan_routes_rows",
     "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
     "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
+    "rrt_batch_grow_poses", "rrt_plan_grow_poses",
     "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
     "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
     "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
@@ -188,6 +189,8 @@ def lib():
             "rrt_batch_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
             "rrt_plan_grow": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
             "rrt_plan_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
+            "rrt_batch_grow_poses": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
+            "rrt_plan_grow_poses": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
             "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
             "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
             "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
@@ -312,6 +315,14 @@ def _grow_samples(samples):
         s = np.stack([s & 0xFFFF, s >> 16], axis=1)
     s = np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 2)
     return s
+
+
+def _grow_pose_samples(samples):
+    """the samples of a grow_poses call as contiguous int32 (m, 3): rows (x, y, heading index)"""
+    s = np.asarray(samples)
+    if s.size and (s.ndim != 2 or s.shape[1] != 3):
+        raise ValueError(f"pose samples must have shape (m, 3), got {s.shape}")
+    return np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 3)
 
 
 class ResultArrays:
@@ -548,6 +559,21 @@ class Context:
         j0 = C.c_int32(-1)
         old_id = np.full(int(n) + 1, -1, dtype=np.int32)
         rc = lib().rrt_plan_grow(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+        try:
+            _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
+        except RRTError as e:
+            e.seeded = j0.value >= 0  # False: the call refused before the seed and changed nothing
+            raise
+        return rc, res, j0.value, old_id[:j0.value].copy()
+
+    def grow_poses(self, samples, n, logs=False):
+        """rrt_plan_grow_poses: Batch.grow_poses on the Dubins tree of this context's last plan(), launch and result (headings
+        included) as grow().  samples: (m, 3) rows (x, y, heading index).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
+        s = _grow_pose_samples(samples)
+        res = ResultArrays(int(n), logs, headings=True)
+        j0 = C.c_int32(-1)
+        old_id = np.full(int(n) + 1, -1, dtype=np.int32)
+        rc = lib().rrt_plan_grow_poses(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
         try:
             _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
         except RRTError as e:
@@ -827,6 +853,15 @@ class Batch:
         j0, log0 = C.c_int32(-1), C.c_int32(-1)
         old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
         _check(self.ctx.handle, lib().rrt_batch_grow(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
+        return j0.value, old_id[:j0.value].copy(), log0.value
+
+    def grow_poses(self, q, samples):
+        """rrt_batch_grow_poses: grow() for a Dubins batch.  samples: (m, 3) rows (x, y, heading index); the seed keeps every vertex's
+        heading (the view of keep_pose_tree, else the whole tree).  Returns (j0, old_id int32[j0], log0) as grow()."""
+        s = _grow_pose_samples(samples)
+        j0, log0 = C.c_int32(-1), C.c_int32(-1)
+        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_grow_poses(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
         return j0.value, old_id[:j0.value].copy(), log0.value
 
     def grow_ms(self):

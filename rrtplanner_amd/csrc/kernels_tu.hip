@@ -33,8 +33,10 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #elif RRT_TU == 7  // keep a finished tree when the map changes: the view of its alive vertices (rrt_keep_*_kernel): not a team kernel
 #include "rrt_keep.h"
 
-#elif RRT_TU == 8  // grow a finished tree: its loop state rebuilt from the alive vertices (rrt_seed_*_kernel): not a team kernel
+#elif RRT_TU == 8  // grow a finished tree: its loop state rebuilt from the alive vertices (rrt_seed_*_kernel), and the heading bytes of
+                   // a Dubins tree's seed (rrt_pose_seed_heading_kernel): not team kernels
 #include "rrt_seed.h"
+#include "rrt_pose_seed.h"
 
 #elif RRT_TU == 9  // a finished Dubins tree: many goal poses against it (rrt_pose_goals_kernel), the tree kept when the map changes
                    // (rrt_pose_keep_*_kernel), routes to many goal poses and the vehicle's path along them (rrt_pose_route_*_kernel):

@@ -340,5 +340,7 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_install_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_bitmap_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords sr);
+// rrt_pose_seed.h (unit 8, beside the seed kernels)
+__global__ __launch_bounds__(SEED_TPB) void rrt_pose_seed_heading_kernel(uint8_t *heading, const uint8_t *live_heading, int32_t j0, int32_t node_stride);
 
 }  // namespace rrtdev

@@ -1,6 +1,6 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, keep_tree, keep_pose_tree, grow and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h and rrt_seed.h.  What the calls share comes first and is written once:
+// routes, pose_routes, keep_tree, keep_pose_tree, grow, grow_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h and rrt_pose_seed.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
@@ -419,11 +419,18 @@ extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
 // i != 0 keeps rrt_init_kernel away; every expansion kernel reads (i, j) from the descriptor and samples[i] by absolute row, and
 // none of them depends on i == 0 or on i being a multiple of its block ("Growing a finished tree").  rrt_batch_sync puts
 // the query's own n back (grow_n).  A refusal changes nothing; past the refusals a failure leaves the query idle.
-static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0) {
+// rrt_batch_grow (poses == false: straight-line batches, rows (x, y)) and rrt_batch_grow_poses (poses == true: Dubins batches, rows
+// (x, y, h)) are one call: the Dubins seed carries one more array, the heading bytes (rrt_pose_seed.h), and the m sample headings go
+// to rows [j0, j0 + m) of the sample heading buffer, which both Dubins kernels read by absolute row like the samples.
+static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
+                      bool poses) {
     rrt_ctx *ctx = b->ctx;
-    if (!j0_out || !log0 || (m > 0 && !samples_xy)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (b->flags & RRT_FLAG_DUBINS)
+    const int row = poses ? 3 : 2;  // int32 words of a sample
+    if (!j0_out || !log0 || (m > 0 && !samples)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (!poses && (b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (the seed kernels carry no headings)", who);
+    if (poses && !(b->flags & RRT_FLAG_DUBINS))
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its samples are cells and its edges straight lines: use rrt_batch_grow)", who);
     if (b->flags & RRT_FLAG_REWIRE)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_REWIRE (its kernel keeps child lists, which the seed does not rebuild)", who);
     if (b->flags & RRT_FLAG_LARGE_GRID)
@@ -433,8 +440,11 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     QDesc &d = b->h_desc[(size_t)q];
     if (d.alg == RRT_ALG_INFORMED)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d is an Informed RRT* query (its ellipse state is not rebuilt); RRTStandard and RRTStar only", who, q);
-    if (const int rc = refuse_grid(who, b, q, "changed shape since the batch was created", " and the tree was not kept on it (rrt_batch_keep_tree)")) return rc;
+    if (const int rc = refuse_grid(who, b, q, "changed shape since the batch was created",
+                                   poses ? " and the tree was not kept on it (rrt_batch_keep_pose_tree)" : " and the tree was not kept on it (rrt_batch_keep_tree)"))
+        return rc;
     if (m < 0) return fail(ctx, RRT_E_ARG, "%s: m=%d", who, m);
+    if (poses && (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0))) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
     const int j_old = d.j, own_n = d.n;
     if (j_old < 1 || j_old > b->n_cap || own_n < 1 || own_n > b->n_cap)
         return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices of %d, capacity %d", who, q, j_old, own_n, b->n_cap);
@@ -445,12 +455,18 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
         return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j0, m, own_n, own_n - j0);
     const int W = ctx->W, H = ctx->H;
     for (int k = 0; k < m; ++k) {
-        const int x = samples_xy[2 * k], y = samples_xy[2 * k + 1];
+        const int x = samples[row * k], y = samples[row * k + 1];
         if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: sample %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
+        if (poses && (samples[row * k + 2] < 0 || samples[row * k + 2] >= d.nh))
+            return fail(ctx, RRT_E_ARG, "%s: sample %d has heading %d, query %d has headings [0, %d)", who, k, samples[row * k + 2], q, d.nh);
     }
-    b->stage.resize((size_t)m);  // (past the last refusal: the staging buffer is the first thing of the batch this call touches)
+    b->stage.resize((size_t)m);  // (past the last refusal: the staging buffers are the first thing of the batch this call touches)
     for (int k = 0; k < m; ++k)
-        b->stage[(size_t)k] = ((uint32_t)samples_xy[2 * k] & 0xffffu) | ((uint32_t)samples_xy[2 * k + 1] << 16);
+        b->stage[(size_t)k] = ((uint32_t)samples[row * k] & 0xffffu) | ((uint32_t)samples[row * k + 1] << 16);
+    if (poses) {
+        b->stage8.resize((size_t)m);
+        for (int k = 0; k < m; ++k) b->stage8[(size_t)k] = (uint8_t)samples[row * k + 2];
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t cap = (size_t)b->n_cap;
     HIPCHK(ctx, b->seed_tmp.reserve(1, (2 * cap + 2) * sizeof(int32_t)));
@@ -485,6 +501,9 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
         hipLaunchKernelGGL(rrt_seed_parent_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
     }
     hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
+    if (poses && sv.live_id)  // (without a view heading[0, j0) already stands; rrt_pose_seed.h says why the slots behind j0 are left)
+        hipLaunchKernelGGL(rrt_pose_seed_heading_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, t.heading, (const uint8_t *)t.live_heading, j0,
+                           b->node_stride);
     HIPCHK(ctx, hipEventRecord(b->ev_seed[1], ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
     if (j0 > 1) hipLaunchKernelGGL(rrt_seed_bitmap_kernel, blocks(j0 - 1), dim3(SEED_TPB), 0, ctx->stream, sv);
@@ -515,6 +534,8 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     }
     if (m > 0)
         HIPCHK(ctx, hipMemcpyAsync(b->d_samples + (size_t)q * b->n_cap + j0, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (poses && m > 0)
+        HIPCHK(ctx, hipMemcpyAsync(b->d_shead + (size_t)q * b->n_cap + j0, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     drop_keep_views(b, q);  // the view is used up: the tree arrays hold its vertices now
     if (err) {
@@ -539,16 +560,28 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
 }
 
 extern "C" int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
+    return b ? batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0, false) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
+}
+
+extern "C" int rrt_batch_grow_poses(rrt_batch *b, int32_t q, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
+    return b ? batch_grow("rrt_batch_grow_poses", b, q, samples_xyh, m, j0, old_id, log0, true) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow_poses: NULL");
+}
+
+static int plan_grow(const char *who, rrt_ctx *ctx, const int32_t *samples, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out, bool poses) {
+    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
+    if (!s) return RRT_E_ARG;
+    int32_t log0 = 0;
+    const int rc = batch_grow(who, s, 0, samples, m, j0, old_id, &log0, poses);
+    return rc != RRT_OK ? rc : run_single(ctx, out);
 }
 
 extern "C" int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    if (ctx && !out) return fail(ctx, RRT_E_ARG, "rrt_plan_grow: NULL");
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_grow", NO_PLAN_NO_TREE);
-    if (!s) return RRT_E_ARG;
-    int32_t log0 = 0;
-    const int rc = batch_grow("rrt_plan_grow", s, 0, samples_xy, m, j0, old_id, &log0);
-    return rc != RRT_OK ? rc : run_single(ctx, out);
+    return plan_grow("rrt_plan_grow", ctx, samples_xy, m, j0, old_id, out, false);
+}
+
+extern "C" int rrt_plan_grow_poses(rrt_ctx *ctx, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    return plan_grow("rrt_plan_grow_poses", ctx, samples_xyh, m, j0, old_id, out, true);
 }
 
 extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {

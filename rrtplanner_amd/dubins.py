@@ -147,6 +147,7 @@ class _DubinsBase(RRT):
         self._tree_resident = None
         rc, res = ctx.plan(query, n, logs=logs)
         self._tree_resident = "device"  # (also when the plan's own goal is unreachable: the tree is complete)
+        self._grow_xg, self._grow_j0 = xg, int(res.j)  # (grow_poses connects the same goal pose, also after a plan that did not reach it)
         if rc == _ffi.RRT_E_GOAL_UNREACHABLE:
             raise IndexError(f"index {hostprep.INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")  # as rrt.py:317-318
         res.xs, res.xg = xs, xg
@@ -328,6 +329,62 @@ class _DubinsBase(RRT):
         """keep_pose_tree(grids.host[k]) for grids generated on this planner's device (oggen.DeviceGrids): frame k becomes the active
         grid without an upload.  Raises like keep_pose_tree and set_og_resident."""
         return self._keep_on_resident("keep_pose_tree", grids, k)
+
+    def grow_poses(self, m: int) -> Tuple[nx.DiGraph, int]:
+        """Spend m more pose samples on the Dubins tree of the last plan() (rrt_plan_grow_poses): after keep_pose_tree the region
+        behind a new obstacle has no vertices and its poses answer -1 / inf; grow_poses puts vertices there again without planning
+        from scratch.  The same call refines an uncut tree.
+
+        The alive vertices (all of them without a keep_pose_tree) become vertices 0 .. j0-1 of a new tree, in their original order
+        and with their costs and headings unchanged; `sampled` is the set of their cells without xstart's, so the cell of a cut
+        vertex can be drawn again; then m iterations of plan()'s loop run on the current grid with m free cells and then m heading
+        indices drawn from self.rand_gen exactly as plan() draws its n and n, and the goal decision connects plan()'s xgoal.  m must
+        fit: j0 + m <= self.n.
+
+        Returns (T, gv) with the row contract of plan() for self.n.  self.last_grow_ids[k] is the number vertex k had in the tree
+        before the call; last_stats counts the m iterations.  connect_poses, paths_to_poses, routes_to_poses, keep_pose_tree and a
+        further grow_poses work on the grown tree in its new numbering.
+
+        RuntimeError / ValueError as connect_poses; ValueError when m does not fit (it names the room); IndexError as plan() when
+        the goal pose is unreachable and rows are left (the grown tree stays resident)."""
+        if self._custom_cost:
+            raise ValueError("grow_poses: the Dubins planners run with the arc-length cost on the device; a Python costfn has no tree there")
+        self._keep_guard("grow_poses", np.asarray(self.og).shape)
+        m = int(m)
+        if m < 0:
+            raise ValueError(f"grow_poses: m={m}")
+        ctx = self._device()
+        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow_poses(), or the alive ones of the last keep_pose_tree
+        if j0 == 0:
+            raise ValueError("grow_poses: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
+        if j0 + m > int(self.n):
+            raise ValueError(f"grow_poses: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
+        cells = hostprep.draw_free_samples(self.rand_gen, self.free, m)
+        headings = self.rand_gen.integers(0, self.n_headings, size=m)
+        samples = np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), headings])
+        bar = tqdm(total=m) if self.pbar else None
+        try:
+            self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
+            try:
+                rc, res, j0, old_id = ctx.grow_poses(samples, int(self.n))
+            except _ffi.RRTError as e:
+                if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
+                    self._tree_resident = "device"
+                raise
+            self._tree_resident = "device"
+            self.last_grow_ids = old_id
+            self._grow_j0 = int(res.j)
+            self.last_stats = {k: getattr(res, k) for k in ("j", "sum_j", "sum_cells_nn", "sum_near", "sum_cells_cand", "n_los_cand")}
+            if rc == _ffi.RRT_E_GOAL_UNREACHABLE:  # (as plan(): the grown tree is complete and resident all the same)
+                raise IndexError(f"index {hostprep.INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")
+            res.xs, res.xg = None, self._grow_xg
+            out = self._materialise_dubins(res)
+            if bar is not None:
+                bar.update(m)
+        finally:
+            if bar is not None:
+                bar.close()
+        return out
 
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""

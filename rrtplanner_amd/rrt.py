@@ -712,6 +712,10 @@ class RRT(object):
                 bar.close()
         return out
 
+    def grow_poses(self, m: int):
+        raise ValueError("grow_poses: this planner's samples are cells and its edges straight lines: use grow (pose samples belong to "
+                         "RRTDubins and RRTStarDubins)")
+
     def device_context(self) -> "_ffi.Context":
         """The planner's device context (created on demand, without uploading a grid)."""
         if self._ctx is None:
