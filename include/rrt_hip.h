@@ -276,8 +276,8 @@ int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]);
  * is rrt_batch_keep_tree).  The scratch: 10 bytes a vertex of capacity, and 17 for each query that is kept. */
 int rrt_batch_keep_pose_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t *alive);
 /* Finished routes from the start pose to m goal poses over the Dubins tree that query q left on the device, and optionally the path
- * the vehicle drives along them, in one call (rrt_pose_routes.h).  rrt_batch_routes for a batch created with RRT_FLAG_DUBINS; there
- * are no shortcuts (a shortcut changes words and headings).
+ * the vehicle drives along them, in one call (rrt_pose_routes.h).  rrt_batch_routes for a batch created with RRT_FLAG_DUBINS; the
+ * shortcuts are a call of their own, rrt_batch_pose_shortcuts below.
  *   vertex[g], cost[g]: exactly what rrt_batch_connect_poses gives (the same kernel decides them; after rrt_batch_keep_pose_tree over
  *   the same view, in the original vertex numbers).
  *   vertex[g] == -1: the route of g has 0 rows, no points, and length[g] = +inf.
@@ -303,17 +303,35 @@ int rrt_batch_keep_pose_tree(rrt_batch *b, int32_t q, int32_t *n_alive, uint8_t 
 #define RRT_POSE_ROUTES_POINTS 0x1u
 int rrt_batch_pose_routes(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                           int64_t *offsets, int64_t *point_offsets);
-/* The rows of the last rrt_batch_pose_routes on this batch: xyh is host (rows, 3) int32, id host int32[rows], rows == its offsets[m].
- * RRT_E_ARG: NULL (with rows > 0); no rrt_batch_pose_routes on this batch yet, or its last one failed; rows differs from that call's
- * total; an rrt_batch_launch, rrt_batch_rearm, rrt_batch_keep_pose_tree since. */
+/* rrt_batch_pose_routes with shortcuts: the same arguments, validation, budgets (2^24 on the rows of the walks, 2^27 on the points of
+ * the kept legs) and scratch, flags RRT_POSE_ROUTES_POINTS or 0.  Per goal with vertex[g] >= 0, over the rows P[0..k) that
+ * rrt_batch_pose_routes gives: from the anchor a = 0 the next kept row is the LARGEST b in (a, k-1] with b == a + 1 (never tested) or
+ * for which the shortest Dubins word from pose P[a] to pose P[b], swept from P[a] on the context's active grid as
+ * rrt_batch_connect_poses sweeps (every sample k * DUB_DS inside the grid and on a free cell, then the end cell), is free; on from
+ * a = b until a == k - 1.  The kept rows are a subsequence of the raw rows with their ids, the first row and the goal row (id -1)
+ * always among them; both poses of a shortcut stay as they are, the legs between them become that one word.
+ *   vertex[g], cost[g]: rrt_batch_connect_poses' answers, unchanged.  length[g]: the f64 sum, left to right from 0.0, of the kept
+ *   legs' word lengths; the shortest word is never longer than the legs it replaces, so length[g] <= cost[g] up to rounding, and no
+ *   longer equal.  offsets, point_offsets and the points: those of the kept rows and the kept legs' words, under the rules above;
+ *   every point is a sample whose cell the shortcut kernel or the planner tested.
+ * It adds 12 bytes a pose and 9 a row of scratch, and one more wait (for the number of kept rows).  Its refusals name it.  The rows and
+ * points stay on the batch exactly as rrt_batch_pose_routes leaves its own: one pair of read-back calls serves both. */
+int rrt_batch_pose_shortcuts(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                             int64_t *offsets, int64_t *point_offsets);
+/* The rows of the last rrt_batch_pose_routes or rrt_batch_pose_shortcuts on this batch, whichever ran last: xyh is host (rows, 3)
+ * int32, id host int32[rows], rows == its offsets[m].  RRT_E_ARG: NULL (with rows > 0); no such call on this batch yet, or the last
+ * one failed; rows differs from that call's total; an rrt_batch_launch, rrt_batch_rearm, rrt_batch_keep_pose_tree since. */
 int rrt_batch_pose_routes_rows(rrt_batch *b, int32_t *xyh, int32_t *id, int64_t rows);
-/* The points of the last rrt_batch_pose_routes with RRT_POSE_ROUTES_POINTS on this batch: xy is host (points, 2) f64,
- * points == its point_offsets[m].  RRT_E_ARG as for the rows, and when that call did not ask for points. */
+/* The points of the last rrt_batch_pose_routes or rrt_batch_pose_shortcuts on this batch, if it ran with RRT_POSE_ROUTES_POINTS: xy
+ * is host (points, 2) f64, points == its point_offsets[m].  RRT_E_ARG as for the rows, and when that call did not ask for points. */
 int rrt_batch_pose_routes_points(rrt_batch *b, double *xy, int64_t points);
 /* kernel time in ms of the stages of the last successful rrt_batch_pose_routes (m > 0) on this batch, from events on the stream: the
  * decision (the kernel of rrt_batch_connect_poses), depth and scan, rows + legs + lengths (+ the scan of the point counts), the points
  * kernel (0 without points).  RRT_E_ARG when there is none. */
 int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]);
+/* ... and of the last successful rrt_batch_pose_shortcuts (m > 0), which rrt_batch_pose_routes_ms does not report: the decision, depth
+ * and scan, rows + shortcuts + scan + pack, legs + lengths (+ the scan of the point counts), the points kernel (0 without points). */
+int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]);
 /* Grow the finished tree of query q with m more samples (rrt_seed.h): seed + arm, then rrt_batch_launch / rrt_batch_sync /
  * rrt_batch_get_result as after rrt_batch_set_query.  RRTStandard and RRTStar, the default cost, the reference's rewire.
  *   seed   the alive vertices of the query's view (rrt_batch_keep_tree), in their original order, become vertices 0 .. *j0-1 of a new
@@ -414,6 +432,11 @@ int rrt_plan_pose_routes(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint
 int rrt_plan_pose_routes_rows(rrt_ctx *ctx, int32_t *xyh, int32_t *id, int64_t rows);
 int rrt_plan_pose_routes_points(rrt_ctx *ctx, double *xy, int64_t points);
 int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]);
+/* rrt_batch_pose_shortcuts and its stage times on the Dubins tree of the context's last rrt_plan; the rows and points are read back
+ * by rrt_plan_pose_routes_rows / rrt_plan_pose_routes_points */
+int rrt_plan_pose_shortcuts(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                            int64_t *offsets, int64_t *point_offsets);
+int rrt_plan_pose_shortcuts_ms(rrt_ctx *ctx, float ms[5]);
 /* *j = vertices of the finished tree of the context's last rrt_plan / rrt_plan_resume: the bytes rrt_plan_keep_tree writes into
  * `alive`.  RRT_E_ARG: NULL; no finished rrt_plan on this context. */
 int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j);

@@ -80,6 +80,7 @@ SYMBOLS = (
     "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
     "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
     "rrt_plan_pose_routes", "rrt_plan_pose_routes_rows", "rrt_plan_pose_routes_points", "rrt_plan_pose_routes_ms",
+    "rrt_batch_pose_shortcuts", "rrt_batch_pose_shortcuts_ms", "rrt_plan_pose_shortcuts", "rrt_plan_pose_shortcuts_ms",
 )
 
 
@@ -204,6 +205,10 @@ def lib():
             "rrt_plan_pose_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
             "rrt_plan_pose_routes_points": ([vp, vp, C.c_int64], C.c_int),
             "rrt_plan_pose_routes_ms": ([vp, C.POINTER(C.c_float * 4)], C.c_int),
+            "rrt_batch_pose_shortcuts": ([vp, i32, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
+            "rrt_batch_pose_shortcuts_ms": ([vp, C.POINTER(C.c_float * 5)], C.c_int),
+            "rrt_plan_pose_shortcuts": ([vp, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
+            "rrt_plan_pose_shortcuts_ms": ([vp, C.POINTER(C.c_float * 5)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -518,12 +523,20 @@ class Context:
         L = lib()
         return _routes(self._h, lambda *a: L.rrt_plan_routes(self._h, *a), lambda *a: L.rrt_plan_routes_rows(self._h, *a), goals, shortcut)
 
-    def pose_routes(self, poses, points=False):
-        """rrt_plan_pose_routes + rrt_plan_pose_routes_rows (+ rrt_plan_pose_routes_points): Batch.pose_routes on the Dubins tree of this
-        context's last plan()"""
+    def pose_routes(self, poses, points=False, shortcut=False):
+        """rrt_plan_pose_routes (shortcut=True: rrt_plan_pose_shortcuts) + rrt_plan_pose_routes_rows (+ rrt_plan_pose_routes_points):
+        Batch.pose_routes on the Dubins tree of this context's last plan()"""
         L = lib()
-        return _pose_routes(self._h, lambda *a: L.rrt_plan_pose_routes(self._h, *a), lambda *a: L.rrt_plan_pose_routes_rows(self._h, *a),
+        call = L.rrt_plan_pose_shortcuts if shortcut else L.rrt_plan_pose_routes
+        return _pose_routes(self._h, lambda *a: call(self._h, *a), lambda *a: L.rrt_plan_pose_routes_rows(self._h, *a),
                             lambda *a: L.rrt_plan_pose_routes_points(self._h, *a), poses, points)
+
+    def pose_shortcuts_ms(self):
+        """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
+        lengths, points)"""
+        ms = (C.c_float * 5)()
+        _check(self._h, lib().rrt_plan_pose_shortcuts_ms(self._h, C.byref(ms)))
+        return tuple(ms)
 
     def pose_routes_ms(self):
         """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
@@ -795,17 +808,29 @@ class Batch:
         L = lib()
         return _routes(self.ctx.handle, lambda *a: L.rrt_batch_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_routes_rows(self._h, *a), goals, shortcut)
 
-    def pose_routes(self, q, poses, points=False):
+    def pose_routes(self, q, poses, points=False, shortcut=False):
         """rrt_batch_pose_routes + rrt_batch_pose_routes_rows (+ rrt_batch_pose_routes_points): finished routes from the start pose to
         the goal poses (M, 3) over the Dubins tree of query q, built on the device.  Returns (vertex, cost, length float64[M], offsets
         int64[M + 1], xyh int32[(rows, 3)], ids int32[rows]): vertex and cost as connect_poses gives them; the route of pose g is
         xyh[offsets[g]:offsets[g + 1]], the poses root .. vertex[g] along the tree and then the goal pose, ids the tree vertices and -1
         for the goal row; no rows and length inf where vertex is -1; length == cost bit for bit elsewhere.  points=True: two more,
         (point_offsets int64[M + 1], pts float64[(P, 2)]): the vehicle's path of pose g is pts[point_offsets[g]:point_offsets[g + 1]],
-        per leg the samples every 0.5 cells of arc length of its Dubins word that the planner tested, then the goal cell."""
+        per leg the samples every 0.5 cells of arc length of its Dubins word that the planner tested, then the goal cell.
+        shortcut=True (rrt_batch_pose_shortcuts): from each kept row the route jumps to the farthest later row of the raw route to
+        which the shortest Dubins word from the kept row's pose sweeps free on the active grid (the next row is never tested); the
+        poses stay, the words between them change.  The rows are a subsequence of the raw rows with their ids, length the sum of the
+        kept legs' words (<= cost up to rounding), the points those of the kept legs."""
         L = lib()
-        return _pose_routes(self.ctx.handle, lambda *a: L.rrt_batch_pose_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_pose_routes_rows(self._h, *a),
+        call = L.rrt_batch_pose_shortcuts if shortcut else L.rrt_batch_pose_routes
+        return _pose_routes(self.ctx.handle, lambda *a: call(self._h, int(q), *a), lambda *a: L.rrt_batch_pose_routes_rows(self._h, *a),
                             lambda *a: L.rrt_batch_pose_routes_points(self._h, *a), poses, points)
+
+    def pose_shortcuts_ms(self):
+        """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
+        lengths, points)"""
+        ms = (C.c_float * 5)()
+        _check(self.ctx.handle, lib().rrt_batch_pose_shortcuts_ms(self._h, C.byref(ms)))
+        return tuple(ms)
 
     def pose_routes_ms(self):
         """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
@@ -871,7 +896,7 @@ class Batch:
         return tuple(ms)
 
     def pose_routes_rows(self, rows):
-        """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, which left `rows` rows"""
+        """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, with shortcuts or without, which left `rows` rows"""
         xyh = np.empty((int(rows), 3), dtype=np.int32)
         ids = np.empty(int(rows), dtype=np.int32)
         _check(self.ctx.handle, lib().rrt_batch_pose_routes_rows(self._h, xyh.ctypes.data, ids.ctypes.data, int(rows)))

@@ -39,7 +39,7 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #include "rrt_pose_seed.h"
 
 #elif RRT_TU == 9  // a finished Dubins tree: many goal poses against it (rrt_pose_goals_kernel), the tree kept when the map changes
-                   // (rrt_pose_keep_*_kernel), routes to many goal poses and the vehicle's path along them (rrt_pose_route_*_kernel):
+                   // (rrt_pose_keep_*_kernel), routes to many goal poses, their shortcuts and the vehicle's path along them (rrt_pose_route_*_kernel):
                    // not team kernels
 #include "rrt_pose_goals.h"
 #include "rrt_pose_keep.h"

@@ -195,10 +195,16 @@ struct rrt_batch {
     DevBuf pose_route_row;               // [leg_len f64 | pt_off i64 + 1 | row_xy u32 | row_id i32 | npts i32 | row_h u8] for pose_route_row.cap rows
     DevBuf pose_route_sweep;             // dub_sweep_t [rows]
     DevBuf pose_route_pts;               // f64 [points][2]
-    int64_t pose_route_rows = -1;        // rows the last rrt_batch_pose_routes left for rrt_batch_pose_routes_rows; -1: none (launch, rearm, keep, grow)
+    int64_t pose_route_rows = -1;        // rows the last rrt_batch_pose_routes / rrt_batch_pose_shortcuts left for rrt_batch_pose_routes_rows; -1: none (launch, rearm, keep, grow)
     int64_t pose_route_points = -1;      // ... and points for rrt_batch_pose_routes_points; -1: none, or that call did not ask for points
     hipEvent_t ev_pose_route[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // a pair around each of its four stages
     int pose_route_timed = 0;            // stages of the last successful rrt_batch_pose_routes that ran (0: none, 3: no points, 4)
+    // rrt_batch_pose_shortcuts: rrt_batch_pose_routes with the shortcut pass.  It shares everything above but the stage times (its rows
+    // and points are what pose_route_rows / pose_route_points count), and adds the raw rows that the pass rewrites in place.
+    DevBuf pose_cut_goal;                // [fin_off i64 + 1 | kept i32] for pose_cut_goal.cap goals
+    DevBuf pose_cut_row;                 // [row_xy u32 | row_id i32 | row_h u8] for pose_cut_row.cap raw rows
+    hipEvent_t ev_pose_cut[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // a pair around each of its five stages
+    int pose_cut_timed = 0;              // stages of the last successful rrt_batch_pose_shortcuts that ran (0: none, 4: no points, 5)
     // rrt_batch_keep_tree / rrt_batch_keep_pose_tree: the views of the queries that were kept on a new map (rrt_keep.h, rrt_pose_keep.h),
     // allocated at the first call per query
     std::vector<DevBuf> keep;            // [Q] empty, or [live_vcost f64 | live_nodes u32 | live_id i32 | a Dubins batch: live_heading u8], each of n_cap

@@ -384,6 +384,8 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : b->ev_pose_route)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : b->ev_pose_cut)
+        if (e) (void)hipEventDestroy(e);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);

@@ -260,6 +260,28 @@ struct PoseRoutesView {
     double2 *points;         // [npoints]
 };
 
+// the shortcut pass of rrt_batch_pose_shortcuts: the raw rows of the routes, rewritten in place, and the dense rows they are packed to
+constexpr int POSE_CUT_TPB = 256;      // 4 goals a workgroup (one per wavefront); the pack: the same
+constexpr int POSE_CUT_MAX_WG = 2048;  // workgroups of the shortcut kernel, grid-stride beyond
+
+struct PoseCutView {
+    const uint8_t *og;       // (W,H) x-major occupancy of the active grid, != 0 is obstacle
+    int32_t W, H;
+    int32_t nh;              // the query's discrete headings
+    double rho;              // ... and turning radius
+    int32_t m;
+    const int32_t *cnt;      // [m] raw rows of a goal (rrt_route_depth_kernel)
+    const int64_t *raw_off;  // [m + 1] exclusive scan of cnt
+    int32_t *kept;           // [m] rows after shortcutting
+    const int64_t *fin_off;  // [m + 1] exclusive scan of kept (the pack reads it)
+    uint32_t *row_xy;        // [raw rows] packed cells; the shortcut kernel rewrites the front of a goal's rows in place
+    uint8_t *row_h;          // [raw rows] heading indices
+    int32_t *row_id;         // [raw rows] the vertex, -1 for a goal row
+    uint32_t *out_xy;        // [kept rows] the dense rows: PoseRoutesView's row_xy / row_h / row_id of the kernels that follow
+    uint8_t *out_h;
+    int32_t *out_id;
+};
+
 // ---- rrt_seed.h ----
 constexpr int SEED_TPB = 256;                            // one slot / vertex per lane; records: 4 wavefronts a workgroup
 constexpr int SEED_WG = 64;                               // workgroups of the records kernel
@@ -334,6 +356,8 @@ __global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_fill_kernel(Pos
 __global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_leg_kernel(PoseRoutesView pr);
 __global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_length_kernel(PoseRoutesView pr);
 __global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_points_kernel(PoseRoutesView pr);
+__global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_cut_kernel(PoseCutView pc);
+__global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_pack_kernel(PoseCutView pc);
 // rrt_seed.h (unit 8)
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_rank_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_parent_kernel(SeedView sv);

@@ -3,11 +3,30 @@
 // rrt_pose_goals_kernel (rrt_pose_goals.h) answers which vertex a goal pose connects to.  These kernels turn that answer into routes
 // without leaving the device, as rrt_routes.h does for the straight-line planners: per goal g with vertex[g] >= 0 the route is
 // root = 0, ..., vertex[g] along the parent pointers, then the goal pose; k rows of (packed xy, heading byte, id), the goal row with
-// id -1.  vertex[g] == -1: no rows, length +inf, no points.  There is no shortcut pass (a shortcut changes words and headings), so the
-// rows are written straight into their final place and nothing is packed afterwards.
+// id -1.  vertex[g] == -1: no rows, length +inf, no points.  Without shortcuts (rrt_batch_pose_routes) the rows are written straight
+// into their final place and nothing is packed afterwards; with them (rrt_batch_pose_shortcuts) steps 2a - 2c come between 2 and 3.
 //
 //   1. rrt_route_depth_kernel, rrt_route_scan_kernel (rrt_routes.h, as they are): rows per goal, and their 64-bit offsets.
 //   2. rrt_pose_route_fill_kernel    one goal per lane: walks the parents and writes its rows back to front.
+//  2a. rrt_pose_route_cut_kernel     (shortcuts only) ONE WAVEFRONT PER GOAL, grid-stride: the greedy pass over the raw route P[0..k).
+//                                    A shortcut from a pose of the route to a later one keeps both poses and replaces the legs between
+//                                    them by the shortest word from the first to the second: the words change, the poses do not.  From
+//                                    the anchor a (row 0 first) the next kept row is the LARGEST b in (a, k-1] with b == a + 1 -- never
+//                                    tested: a tree edge that holds on the active grid, or the goal edge the decision swept -- or a free
+//                                    sweep (dub_sweep_wave on the active grid) of dub_between_dev(P[a], P[b]) from P[a].  Candidates go
+//                                    from the far end downwards in batches of 64: lane l evaluates the word to candidate hi - l once
+//                                    (the 64-words-at-a-time form of rrt_pose_keep_edge_kernel), then the wavefront sweeps the batch
+//                                    from the farthest candidate down, the word handed over by readlane, and stops at the first free
+//                                    one: nothing nearer can be larger.  A word that is DUB_NONE, not finite or beyond
+//                                    POSE_ROUTE_LEG_POINTS samples (none can be: dub_shortest tries six words) is not free and raises
+//                                    nothing.  Kept row e <= b goes to slot e of the same rows: slots at or below a + 1 are never read
+//                                    again (the candidates of the next anchor b are above b + 1 > e), the anchor's pose is held in
+//                                    registers, and slot e == b receives what it holds.  kept[g] = e at the end, 0 without rows.  The
+//                                    heading table is the leg kernel's; behind its barrier there is none: routes differ in length
+//                                    and no wavefront waits for another.
+//  2b. rrt_route_scan_kernel again   (shortcuts only) over kept: the 64-bit offsets of the kept rows.
+//  2c. rrt_pose_route_pack_kernel    (shortcuts only) one goal per wavefront: its kept rows to the dense rows that steps 3 - 6 read as
+//                                    they read the rows of step 2.  The words and lengths of the kept legs are step 3's: one definition.
 //   3. rrt_pose_route_leg_kernel     one ROW per lane, grid-stride.  A row with id -1 is the last of its route: leg length 0, one point
 //                                    (the goal cell).  Any other row r evaluates dub_between_dev(row r, row r + 1) once, with the heading
 //                                    table in LDS exactly as rrt_pose_keep_edge_kernel builds it: the words are the planner's bits.  With
@@ -19,7 +38,8 @@
 //   4. rrt_route_scan_kernel again   (points only) over the rows' point counts: the 64-bit point offset of every row.
 //   5. rrt_pose_route_length_kernel  one goal per lane: length[g] = the f64 sum of its legs' lengths, left to right from 0.0.  The
 //                                    Dubins loop sets vcost[child] = vcost[parent] + len and never rewires, and rrt_pose_goals_kernel
-//                                    prices vcost[v] + len: this sum IS cost[g], bit for bit.  The order is the semantics: no fold.
+//                                    prices vcost[v] + len: without shortcuts this sum IS cost[g], bit for bit (with them it is at most
+//                                    cost[g], up to rounding).  The order is the semantics: no fold.
 //                                    Also the goal's point offset, which is that of its first row.
 //   6. rrt_pose_route_points_kernel  (points only) ONE POINT PER LANE, grid-stride over all points of the call.  Tree legs are short (at
 //                                    most r_rewire cells, a few dozen samples): a wavefront per leg would idle most of its lanes
@@ -61,6 +81,101 @@ __global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_fill_kernel(Pos
         hd[i] = pr.heading[u];
         id[i] = u;
         if (i > 0) u = pr.parent[u];
+    }
+}
+
+// one wavefront per goal: the greedy shortcut pass over its raw rows, the kept rows compacted to their front
+__global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_cut_kernel(PoseCutView pc) {
+    __shared__ __attribute__((aligned(16))) double htab_s[3 * 256];
+    RRT_LDS double *htab = (RRT_LDS double *)htab_s;
+    const int t = (int)threadIdx.x, lane = t & 63;
+    for (int h = t; h < pc.nh && h < 256; h += POSE_CUT_TPB) {  // exactly the table of rrt_pose_route_leg_kernel
+        const double th = dub_heading(h, pc.nh);
+        double sn, cs;
+        dub_sincos(th, &sn, &cs);
+        htab[h] = th;
+        htab[256 + h] = sn;
+        htab[512 + h] = cs;
+    }
+    DubCfg dc{pc.rho, pc.nh, pc.W, pc.H};
+    dc.htab = htab;
+    dc.inv_rho = 1.0 / pc.rho;
+    __syncthreads();  // the only barrier: from here on every wavefront is on its own
+    const uint8_t *og = pc.og;
+    const int waves = POSE_CUT_TPB / 64;
+    for (int g = (int)blockIdx.x * waves + (t >> 6); g < pc.m; g += (int)gridDim.x * waves) {  // (g is wave-uniform)
+        const int k = pc.cnt[g];
+        if (k == 0) {
+            if (lane == 0) pc.kept[g] = 0;
+            continue;
+        }
+        const int64_t at = pc.raw_off[g];
+        uint32_t *xy = pc.row_xy + at;
+        uint8_t *hd = pc.row_h + at;
+        int32_t *id = pc.row_id + at;
+        int a = 0, e = 1;
+        uint32_t pa = (uint32_t)__builtin_amdgcn_readfirstlane((int)xy[0]);
+        int ha = __builtin_amdgcn_readfirstlane((int)hd[0]);
+        while (a < k - 1) {
+            int b = a + 1;
+            for (int hi = k - 1; hi > a + 1 && b == a + 1; hi -= 64) {
+                const int c = hi - lane;  // this lane's candidate: its word, once
+                uint32_t pcell = 0;
+                dub_path_t pth;
+                pth.t = pth.p = pth.q = 0.0;
+                pth.len = f64_inf();
+                pth.word = DUB_NONE;
+                if (c > a + 1) {
+                    pcell = xy[c];
+                    pth = dub_between_dev(pa, ha, pcell, (int)hd[c], dc);
+                    // (the comparison is false for a NaN, too)
+                    if (!(pth.len >= 0.0 && pth.len < (double)POSE_ROUTE_LEG_POINTS * DUB_DS)) pth.word = DUB_NONE;
+                }
+                const int cnt = hi - (a + 1) < 64 ? hi - (a + 1) : 64;
+                for (int l = 0; l < cnt; ++l) {  // (l is wave-uniform) the farthest candidate first
+                    dub_path_t wp;
+                    wp.word = __builtin_amdgcn_readlane(pth.word, l);
+                    if (wp.word == DUB_NONE) continue;
+                    wp.t = dub_lane_f64(pth.t, l);
+                    wp.p = dub_lane_f64(pth.p, l);
+                    wp.q = dub_lane_f64(pth.q, l);
+                    wp.len = dub_lane_f64(pth.len, l);
+                    const uint32_t pb = (uint32_t)__builtin_amdgcn_readlane((int)pcell, l);
+                    int cc = 0;
+                    if (dub_sweep_wave(og, dc, pa, ha, pb, wp, lane, cc)) {
+                        b = hi - l;
+                        break;
+                    }
+                }
+            }
+            const uint32_t pb = (uint32_t)__builtin_amdgcn_readfirstlane((int)xy[b]);
+            const int hb = __builtin_amdgcn_readfirstlane((int)hd[b]);
+            const int32_t ib = id[b];
+            if (lane == 0) {  // (e <= b: slot e is never read again, or holds this row already)
+                xy[e] = pb;
+                hd[e] = (uint8_t)hb;
+                id[e] = ib;
+            }
+            ++e;
+            a = b;
+            pa = pb;
+            ha = hb;
+        }
+        if (lane == 0) pc.kept[g] = e;
+    }
+}
+
+// one goal per wavefront: the first kept[g] rows of its raw rows to the dense rows fin_off[g] ...
+__global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_pack_kernel(PoseCutView pc) {
+    const int lane = (int)threadIdx.x & 63;
+    const int g = (int)(blockIdx.x * (POSE_CUT_TPB / 64) + (threadIdx.x >> 6));
+    if (g >= pc.m) return;
+    const int n = pc.kept[g];
+    const int64_t src = pc.raw_off[g], dst = pc.fin_off[g];
+    for (int i = lane; i < n; i += 64) {
+        pc.out_xy[dst + i] = pc.row_xy[src + i];
+        pc.out_h[dst + i] = pc.row_h[src + i];
+        pc.out_id[dst + i] = pc.row_id[src + i];
     }
 }
 

@@ -1,5 +1,5 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, keep_tree, keep_pose_tree, grow, grow_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
 // rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h and rrt_pose_seed.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
@@ -167,7 +167,7 @@ extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int
 
 // ---- many goal poses against a finished Dubins tree (rrt_pose_goals.h) ----
 // The conditions are goals_decide's, for a batch created with RRT_FLAG_DUBINS; a goal is a pose (x, y, h), h < the query's nh.
-// The part that rrt_batch_connect_poses and rrt_batch_pose_routes share, as goals_decide serves the straight-line calls: every refusal
+// The part that rrt_batch_connect_poses, rrt_batch_pose_routes and rrt_batch_pose_shortcuts share, as goals_decide serves the straight-line calls: every refusal
 // (`use`: the call a straight-line batch is sent to), the poses packed and uploaded, the scratch, and the pose goals kernel launched
 // on the context's stream.  Nothing is read back and nothing waited for.  m == 0: RRT_OK, nothing launched.  pose_last_m is left at -1
 // (the counters are being rewritten) for the caller to set once its call has succeeded.
@@ -704,15 +704,20 @@ extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int6
 }
 
 // ---- finished routes to many goal poses, and the vehicle's path along them (rrt_pose_routes.h) ----
+// rrt_batch_pose_routes (cut == false) and rrt_batch_pose_shortcuts (cut == true) are one call: with `cut` the rows of the walks go to
+// scratch of their own, the shortcut kernel keeps some of them, and the dense rows that the leg, length and points kernels read are
+// the kept ones under their own offsets.  The rows and points either call leaves are what the _rows / _points calls serve; the stage
+// times are kept apart (ev_pose_route / ev_pose_cut), so that rrt_batch_pose_routes_ms goes on reporting the last plain call.
 static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
-                             double *length, int64_t *offsets, int64_t *point_offsets) {
+                             double *length, int64_t *offsets, int64_t *point_offsets, bool cut) {
     rrt_ctx *ctx = b->ctx;
     b->pose_route_rows = b->pose_route_points = -1;  // whatever happens below, the rows and points of an earlier call are gone
-    b->pose_route_timed = 0;
+    (cut ? b->pose_cut_timed : b->pose_route_timed) = 0;
+    hipEvent_t *ev = cut ? b->ev_pose_cut : b->ev_pose_route;
+    const int nev = cut ? 10 : 8, leg_ev = cut ? 6 : 4;  // (the events around legs + lengths, and behind them those around the points)
     if (flags & ~(uint32_t)RRT_POSE_ROUTES_POINTS) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_POSE_ROUTES_POINTS is defined", who, flags);
     const bool pts = (flags & RRT_POSE_ROUTES_POINTS) != 0;
-    if (const int rc = poses_decide(who, b, q, poses_xyh, m, !vertex || !cost || !length || !offsets || (pts && !point_offsets), "rrt_batch_routes",
-                                    b->ev_pose_route);
+    if (const int rc = poses_decide(who, b, q, poses_xyh, m, !vertex || !cost || !length || !offsets || (pts && !point_offsets), "rrt_batch_routes", ev);
         rc != RRT_OK)
         return rc;
     if (m == 0) {
@@ -722,8 +727,8 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         b->pose_route_points = pts ? 0 : -1;
         return RRT_OK;
     }
-    for (hipEvent_t &e : b->ev_pose_route)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    for (int k = 0; k < nev; ++k)
+        if (!ev[k]) HIPCHK(ctx, hipEventCreate(&ev[k]));
     // [length f64 m | raw_off i64 m+1 | goal_pt_off i64 m+1 | cnt i32 m | err i32]
     HIPCHK(ctx, b->pose_route_goal.reserve(m, (size_t)m * 28 + 2 * sizeof(int64_t) + sizeof(int32_t)));
     const size_t cap = (size_t)b->pose_route_goal.cap;
@@ -759,10 +764,10 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     rv.err = pr.err;
     const unsigned goals_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB);
     HIPCHK(ctx, hipMemsetAsync(pr.err, 0, sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev[2], ctx->stream));
     hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(goals_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
     hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)cnt, raw_off, m);
-    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[3], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev[3], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     // the first wait that the sizes force: the rows of all routes together decide how much memory the rows need
     int64_t rows = 0;
@@ -788,10 +793,58 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     pr.npts = pts ? pr.row_id + rcap : nullptr;
     pr.row_h = reinterpret_cast<uint8_t *>(pr.row_id + 2 * rcap);
     pr.sweep_bytes = pts ? b->pose_route_sweep.p : nullptr;
-    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[4], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev[4], ctx->stream));
+    if (cut && rows > 0) {
+        // the raw rows [row_xy u32 | row_id i32 | row_h u8] of rows, and per goal [fin_off i64 + 1 | kept i32]: the walks fill the raw
+        // rows, the shortcut kernel compacts each goal's kept rows to the front of its own, the pack makes them the dense rows above
+        HIPCHK(ctx, b->pose_cut_row.reserve(rows, (size_t)rows * 9));
+        HIPCHK(ctx, b->pose_cut_goal.reserve(m, (size_t)m * 12 + sizeof(int64_t)));
+        const size_t ccap = (size_t)b->pose_cut_row.cap, gcap = (size_t)b->pose_cut_goal.cap;
+        PoseCutView pc{};
+        pc.og = ctx->og;
+        pc.W = ctx->W;
+        pc.H = ctx->H;
+        pc.nh = d.nh;
+        pc.rho = d.rho;
+        pc.m = m;
+        pc.cnt = cnt;
+        pc.raw_off = raw_off;
+        int64_t *fin_off = b->pose_cut_goal.as<int64_t>();
+        pc.fin_off = fin_off;
+        pc.kept = reinterpret_cast<int32_t *>(fin_off + gcap + 1);
+        pc.row_xy = b->pose_cut_row.as<uint32_t>();
+        pc.row_id = reinterpret_cast<int32_t *>(pc.row_xy + ccap);
+        pc.row_h = reinterpret_cast<uint8_t *>(pc.row_id + ccap);
+        pc.out_xy = pr.row_xy;
+        pc.out_h = pr.row_h;
+        pc.out_id = pr.row_id;
+        PoseRoutesView raw = pr;
+        raw.row_xy = pc.row_xy;
+        raw.row_h = pc.row_h;
+        raw.row_id = pc.row_id;
+        const unsigned waves_grid = (unsigned)((m + POSE_CUT_TPB / 64 - 1) / (POSE_CUT_TPB / 64));
+        hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, raw);
+        hipLaunchKernelGGL(rrt_pose_route_cut_kernel, dim3(std::min<unsigned>(waves_grid, POSE_CUT_MAX_WG)), dim3(POSE_CUT_TPB), 0, ctx->stream, pc);
+        hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)pc.kept, fin_off, m);
+        hipLaunchKernelGGL(rrt_pose_route_pack_kernel, dim3(waves_grid), dim3(POSE_CUT_TPB), 0, ctx->stream, pc);
+        HIPCHK(ctx, hipEventRecord(ev[5], ctx->stream));
+        HIPCHK(ctx, hipGetLastError());
+        // a wait of the shortcut call alone: the leg and the points kernel take the number of dense rows by value
+        int64_t kept_rows = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&kept_rows, fin_off + m, sizeof kept_rows, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        if (kept_rows < 1 || kept_rows > rows) return fail(ctx, RRT_E_HIP, "%s: %lld rows kept of %lld", who, (long long)kept_rows, (long long)rows);
+        pr.cnt = pc.kept;
+        pr.raw_off = fin_off;
+        pr.rows = rows = kept_rows;
+        HIPCHK(ctx, hipEventRecord(ev[6], ctx->stream));
+    } else if (cut) {
+        HIPCHK(ctx, hipEventRecord(ev[5], ctx->stream));  // (nothing connects: no row to cut; cnt and raw_off, all zero, are the kept ones)
+        HIPCHK(ctx, hipEventRecord(ev[6], ctx->stream));
+    }
     if (rows > 0) {
         const unsigned rows_grid = (unsigned)std::min<int64_t>((rows + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
-        hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+        if (!cut) hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
         hipLaunchKernelGGL(rrt_pose_route_leg_kernel, dim3(rows_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
         // a leg's count is at most POSE_ROUTE_LEG_POINTS = 2^19 (the leg kernel raises err beyond, and a word whose every sample lies inside
         // a grid of 2048 x 2048 cells has some 55 000 at most): the 1024 counts of a pass of the scan sum below 2^32, as its rows do
@@ -800,10 +853,10 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         HIPCHK(ctx, hipMemsetAsync(pr.pt_off, 0, sizeof(int64_t), ctx->stream));  // (nothing connects: no point)
     }
     hipLaunchKernelGGL(rrt_pose_route_length_kernel, dim3((unsigned)((m + 1 + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
-    HIPCHK(ctx, hipEventRecord(b->ev_pose_route[5], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev[leg_ev + 1], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(length, pr.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(offsets, raw_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(offsets, pr.raw_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&err, pr.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
     if (pts) HIPCHK(ctx, hipMemcpyAsync(point_offsets, pr.goal_pt_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     // the second wait (with points: the points of all legs together decide how much memory the points need)
@@ -822,9 +875,9 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
             pr.npoints = npoints;
             pr.points = b->pose_route_pts.as<double2>();
             const unsigned pts_grid = (unsigned)std::min<int64_t>((npoints + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
-            HIPCHK(ctx, hipEventRecord(b->ev_pose_route[6], ctx->stream));
+            HIPCHK(ctx, hipEventRecord(ev[leg_ev + 2], ctx->stream));
             hipLaunchKernelGGL(rrt_pose_route_points_kernel, dim3(pts_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
-            HIPCHK(ctx, hipEventRecord(b->ev_pose_route[7], ctx->stream));
+            HIPCHK(ctx, hipEventRecord(ev[leg_ev + 3], ctx->stream));
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (so that a fault of the kernel is this call's, and the stage times are there)
         }
@@ -832,7 +885,7 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     b->pose_last_m = m;
     b->pose_route_rows = rows;
     b->pose_route_points = pts ? npoints : -1;
-    b->pose_route_timed = pts && npoints > 0 ? 4 : 3;
+    (cut ? b->pose_cut_timed : b->pose_route_timed) = (pts && npoints > 0 ? 4 : 3) + (cut ? 1 : 0);
     return RRT_OK;
 }
 
@@ -881,7 +934,7 @@ static int batch_pose_routes_points(const char *who, rrt_batch *b, double *xy, i
 
 extern "C" int rrt_batch_pose_routes(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                                      int64_t *offsets, int64_t *point_offsets) {
-    return b ? batch_pose_routes("rrt_batch_pose_routes", b, q, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets)
+    return b ? batch_pose_routes("rrt_batch_pose_routes", b, q, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, false)
              : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes: NULL");
 }
 
@@ -896,7 +949,20 @@ extern "C" int rrt_batch_pose_routes_points(rrt_batch *b, double *xy, int64_t po
 extern "C" int rrt_plan_pose_routes(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                                     int64_t *offsets, int64_t *point_offsets) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes", NO_PLAN_NO_TREE);
-    return s ? batch_pose_routes("rrt_plan_pose_routes", s, 0, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets) : RRT_E_ARG;
+    return s ? batch_pose_routes("rrt_plan_pose_routes", s, 0, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, false) : RRT_E_ARG;
+}
+
+// the same call with the shortcut pass (rrt_pose_route_cut_kernel) between the walks and the legs
+extern "C" int rrt_batch_pose_shortcuts(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
+                                        double *length, int64_t *offsets, int64_t *point_offsets) {
+    return b ? batch_pose_routes("rrt_batch_pose_shortcuts", b, q, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, true)
+             : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_shortcuts: NULL");
+}
+
+extern "C" int rrt_plan_pose_shortcuts(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
+                                       int64_t *offsets, int64_t *point_offsets) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_shortcuts", NO_PLAN_NO_TREE);
+    return s ? batch_pose_routes("rrt_plan_pose_shortcuts", s, 0, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, true) : RRT_E_ARG;
 }
 
 extern "C" int rrt_plan_pose_routes_rows(rrt_ctx *ctx, int32_t *xyh, int32_t *id, int64_t rows) {
@@ -922,4 +988,20 @@ extern "C" int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]) {
 extern "C" int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes_ms", NO_PLAN);
     return s ? rrt_batch_pose_routes_ms(s, ms) : RRT_E_ARG;
+}
+
+// kernel time in ms of the stages of the last successful rrt_batch_pose_shortcuts: the decision, depth and scan, rows + shortcuts + scan
+// + pack, legs + lengths (+ the scan of the point counts), the points (0 for a call without points, or without a point)
+extern "C" int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_pose_shortcuts_ms: NULL");
+    if (!b->pose_cut_timed)
+        return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_shortcuts_ms: no rrt_batch_pose_shortcuts with a pose on this batch yet, or its last one failed");
+    ms[4] = 0.f;
+    for (int k = 0; k < b->pose_cut_timed; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_pose_cut[2 * k], b->ev_pose_cut[2 * k + 1]));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_pose_shortcuts_ms(rrt_ctx *ctx, float ms[5]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_shortcuts_ms", NO_PLAN);
+    return s ? rrt_batch_pose_shortcuts_ms(s, ms) : RRT_E_ARG;
 }

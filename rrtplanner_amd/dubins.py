@@ -275,7 +275,7 @@ class _DubinsBase(RRT):
     def routes_to(self, goals, shortcut=False):
         return self.connect_goals(goals)
 
-    def routes_to_poses(self, poses, points=False):
+    def routes_to_poses(self, poses, points=False, shortcut=False):
         """Finished routes from xstart to many goal poses over the tree of the last plan(), built on the device in one call
         (rrt_plan_pose_routes): connect_poses' decision, the parent walks, the lengths and, with points=True, the path the vehicle
         drives.
@@ -287,6 +287,12 @@ class _DubinsBase(RRT):
         plan() / connect_poses / keep_pose_tree tested (floor(p + 0.5) of every point is a free cell), then the goal cell; a leg's end
         pose is the next leg's first point and is not repeated, except where a leg's length is an exact multiple of 0.5: that point
         appears twice.  None where no vertex connects.
+        shortcut=True (rrt_plan_pose_shortcuts): the routes are shortened on the device.  Starting at xstart, a route goes on to the
+        farthest later pose of the raw route that the shortest Dubins word from the current pose reaches with a free sweep on the
+        current map (the sweep of connect_poses); the pose that follows directly is taken as it is.  Every pose that stays keeps its
+        cell and heading, so routes[g] is a subsequence of the raw route that begins at xstart and ends at the goal pose; only the
+        words between the poses change, and the shortest word is never longer than the legs it replaces: length <= connect_poses'
+        cost up to rounding, no longer equal to it.  paths[g] is then the path along the shortened route, under the same rules.
         Heading -1 (any arrival heading) is resolved first, by one connect_poses call for those poses.  It takes no T: the tree is the
         one resident on the device.  RuntimeError / ValueError as connect_poses."""
         g = self._pose_array(poses)
@@ -297,7 +303,7 @@ class _DubinsBase(RRT):
             g = g.copy()
             vertex, _, heading = self.connect_poses(g[anyh])
             g[anyh, 2] = np.where(vertex >= 0, heading, 0)  # (nothing connects under any heading: nor under heading 0)
-        out = self._device().pose_routes(g, points=points)
+        out = self._device().pose_routes(g, points=points, shortcut=shortcut)
         vertex, length, offsets, xyh = out[0], out[2], out[3], out[4].astype(np.int64)
         routes = [xyh[offsets[k]:offsets[k + 1]] if vertex[k] >= 0 else None for k in range(len(g))]
         if not points:

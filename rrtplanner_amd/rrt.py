@@ -932,7 +932,7 @@ class RRT(object):
         raise ValueError("connect_poses: a goal pose (x, y, heading) belongs to the Dubins planners (RRTDubins, RRTStarDubins); the goals of "
                          "this planner are cells: use connect_goals")
 
-    def routes_to_poses(self, poses, points=False):
+    def routes_to_poses(self, poses, points=False, shortcut=False):
         raise ValueError("routes_to_poses: a goal pose (x, y, heading) belongs to the Dubins planners (RRTDubins, RRTStarDubins); the goals of "
                          "this planner are cells: use routes_to")
 
