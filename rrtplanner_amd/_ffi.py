@@ -241,26 +241,20 @@ def comm_unique_id() -> bytes:
     return bytes(buf)
 
 
-def _goal_arrays(goals):
-    """(goals as contiguous int32 (M, 2), vertex int32[M], cost float64[M]) for the connect_goals calls; a single point is M = 1"""
+def _goal_arrays(goals, cols=2):
+    """(goals as contiguous int32 (M, cols), vertex int32[M], cost float64[M]) for the connect_goals (cols = 2: cells) and
+    connect_poses (cols = 3: poses) calls and the routes calls; a single goal is M = 1"""
     g = np.asarray(goals)
-    if g.ndim == 1 and g.shape == (2,):
+    if g.ndim == 1 and g.shape == (cols,):
         g = g[np.newaxis, :]
-    if g.ndim != 2 or g.shape[1] != 2:
-        raise ValueError(f"goals must have shape (M, 2) or (2,), got {g.shape}")
+    if g.ndim != 2 or g.shape[1] != cols:
+        raise ValueError(f"{'goals' if cols == 2 else 'poses'} must have shape (M, {cols}) or ({cols},), got {g.shape}")
     g = np.ascontiguousarray(g, dtype=np.int32)
     return g, np.full(g.shape[0], -1, dtype=np.int32), np.full(g.shape[0], np.inf, dtype=np.float64)
 
 
 def _pose_arrays(poses):
-    """(poses as contiguous int32 (M, 3), vertex int32[M], cost float64[M]) for the connect_poses calls; a single pose is M = 1"""
-    g = np.asarray(poses)
-    if g.ndim == 1 and g.shape == (3,):
-        g = g[np.newaxis, :]
-    if g.ndim != 2 or g.shape[1] != 3:
-        raise ValueError(f"poses must have shape (M, 3) or (3,), got {g.shape}")
-    g = np.ascontiguousarray(g, dtype=np.int32)
-    return g, np.full(g.shape[0], -1, dtype=np.int32), np.full(g.shape[0], np.inf, dtype=np.float64)
+    return _goal_arrays(poses, 3)
 
 
 def _routes(handle, call, rows_call, goals, shortcut):
@@ -313,21 +307,26 @@ def _keep_tree(handle, call, size, j):
     return alive
 
 
-def _grow_samples(samples):
-    """the samples of a grow call as contiguous int32 (m, 2); packed uint32 samples (x | y << 16) are unpacked"""
+def _grow_samples(samples, poses=False):
+    """the samples of a grow call as contiguous int32 (m, 2), packed uint32 samples (x | y << 16) unpacked; of a grow_poses call
+    (poses) as contiguous int32 (m, 3): rows (x, y, heading index)"""
     s = np.asarray(samples)
-    if s.dtype == np.uint32 and s.ndim == 1:
+    if not poses and s.dtype == np.uint32 and s.ndim == 1:
         s = np.stack([s & 0xFFFF, s >> 16], axis=1)
-    s = np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 2)
-    return s
+    if poses and s.size and (s.ndim != 2 or s.shape[1] != 3):
+        raise ValueError(f"pose samples must have shape (m, 3), got {s.shape}")
+    return np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 3 if poses else 2)
 
 
 def _grow_pose_samples(samples):
-    """the samples of a grow_poses call as contiguous int32 (m, 3): rows (x, y, heading index)"""
-    s = np.asarray(samples)
-    if s.size and (s.ndim != 2 or s.shape[1] != 3):
-        raise ValueError(f"pose samples must have shape (m, 3), got {s.shape}")
-    return np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 3)
+    return _grow_samples(samples, True)
+
+
+def _stage_ms(handle, call, stages, *count):
+    """a *_ms call: the kernel time in ms of the `stages` stages of the last call it reports on, as a tuple"""
+    ms = (C.c_float * stages)()
+    _check(handle, call(C.byref(ms), *count))
+    return tuple(ms)
 
 
 class ResultArrays:
@@ -534,15 +533,11 @@ class Context:
     def pose_shortcuts_ms(self):
         """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
         lengths, points)"""
-        ms = (C.c_float * 5)()
-        _check(self._h, lib().rrt_plan_pose_shortcuts_ms(self._h, C.byref(ms)))
-        return tuple(ms)
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_pose_shortcuts_ms(self._h, *a), 5)
 
     def pose_routes_ms(self):
         """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
-        ms = (C.c_float * 4)()
-        _check(self._h, lib().rrt_plan_pose_routes_ms(self._h, C.byref(ms)))
-        return tuple(ms)
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_pose_routes_ms(self._h, *a), 4)
 
     def keep_tree(self):
         """rrt_plan_keep_tree: Batch.keep_tree on the tree of this context's last plan() / plan_resume()"""
@@ -560,18 +555,20 @@ class Context:
 
     def keep_tree_ms(self):
         """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
-        ms = (C.c_float * 3)()
-        _check(self._h, lib().rrt_plan_keep_tree_ms(self._h, C.byref(ms)))
-        return tuple(ms)
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_keep_tree_ms(self._h, *a), 3)
 
     def grow(self, samples, n, logs=False):
         """rrt_plan_grow: Batch.grow on the tree of this context's last plan() / plan_resume(), launch and result included.  n: the
         n of that plan (the result arrays are sized by it).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
-        s = _grow_samples(samples)
-        res = ResultArrays(int(n), logs)
+        return self._grow(samples, n, logs, False)
+
+    def _grow(self, samples, n, logs, poses):
+        s = _grow_samples(samples, poses)
+        res = ResultArrays(int(n), logs, headings=poses)
         j0 = C.c_int32(-1)
         old_id = np.full(int(n) + 1, -1, dtype=np.int32)
-        rc = lib().rrt_plan_grow(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+        call = lib().rrt_plan_grow_poses if poses else lib().rrt_plan_grow
+        rc = call(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
         try:
             _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
         except RRTError as e:
@@ -582,23 +579,11 @@ class Context:
     def grow_poses(self, samples, n, logs=False):
         """rrt_plan_grow_poses: Batch.grow_poses on the Dubins tree of this context's last plan(), launch and result (headings
         included) as grow().  samples: (m, 3) rows (x, y, heading index).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
-        s = _grow_pose_samples(samples)
-        res = ResultArrays(int(n), logs, headings=True)
-        j0 = C.c_int32(-1)
-        old_id = np.full(int(n) + 1, -1, dtype=np.int32)
-        rc = lib().rrt_plan_grow_poses(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
-        try:
-            _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
-        except RRTError as e:
-            e.seeded = j0.value >= 0  # False: the call refused before the seed and changed nothing
-            raise
-        return rc, res, j0.value, old_id[:j0.value].copy()
+        return self._grow(samples, n, logs, True)
 
     def grow_ms(self):
         """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
-        ms = (C.c_float * 3)()
-        _check(self._h, lib().rrt_plan_grow_ms(self._h, C.byref(ms), 3))
-        return tuple(ms)
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_grow_ms(self._h, *a), 3, 3)
 
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
@@ -828,15 +813,11 @@ class Batch:
     def pose_shortcuts_ms(self):
         """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
         lengths, points)"""
-        ms = (C.c_float * 5)()
-        _check(self.ctx.handle, lib().rrt_batch_pose_shortcuts_ms(self._h, C.byref(ms)))
-        return tuple(ms)
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_pose_shortcuts_ms(self._h, *a), 5)
 
     def pose_routes_ms(self):
         """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
-        ms = (C.c_float * 4)()
-        _check(self.ctx.handle, lib().rrt_batch_pose_routes_ms(self._h, C.byref(ms)))
-        return tuple(ms)
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_pose_routes_ms(self._h, *a), 4)
 
     def keep_tree(self, q):
         """rrt_batch_keep_tree: keep the finished tree of query q on the context's CURRENT grid (set_grid / select_frame since the
@@ -865,35 +846,31 @@ class Batch:
 
     def keep_tree_ms(self):
         """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
-        ms = (C.c_float * 3)()
-        _check(self.ctx.handle, lib().rrt_batch_keep_tree_ms(self._h, C.byref(ms)))
-        return tuple(ms)
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_keep_tree_ms(self._h, *a), 3)
 
     def grow(self, q, samples):
         """rrt_batch_grow: seed query q from its finished tree (the alive vertices of its keep_tree view, else the whole tree) and arm
         it for len(samples) more iterations on the context's current grid; then launch() / sync() / get_result(q) as after set_query.
         Returns (j0, old_id int32[j0], log0): the seed's vertices, the original number of each, the log row of the first new
         iteration."""
-        s = _grow_samples(samples)
+        return self._grow(q, samples, False)
+
+    def _grow(self, q, samples, poses):
+        s = _grow_samples(samples, poses)
         j0, log0 = C.c_int32(-1), C.c_int32(-1)
         old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_grow(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
+        call = lib().rrt_batch_grow_poses if poses else lib().rrt_batch_grow
+        _check(self.ctx.handle, call(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
         return j0.value, old_id[:j0.value].copy(), log0.value
 
     def grow_poses(self, q, samples):
         """rrt_batch_grow_poses: grow() for a Dubins batch.  samples: (m, 3) rows (x, y, heading index); the seed keeps every vertex's
         heading (the view of keep_pose_tree, else the whole tree).  Returns (j0, old_id int32[j0], log0) as grow()."""
-        s = _grow_pose_samples(samples)
-        j0, log0 = C.c_int32(-1), C.c_int32(-1)
-        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_grow_poses(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
-        return j0.value, old_id[:j0.value].copy(), log0.value
+        return self._grow(q, samples, True)
 
     def grow_ms(self):
         """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
-        ms = (C.c_float * 3)()
-        _check(self.ctx.handle, lib().rrt_batch_grow_ms(self._h, C.byref(ms), 3))
-        return tuple(ms)
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_grow_ms(self._h, *a), 3, 3)
 
     def pose_routes_rows(self, rows):
         """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, with shortcuts or without, which left `rows` rows"""

@@ -24,6 +24,7 @@
 #include "rrt_hip.h"
 #include "rrt_kernel_abi.h"
 #include "rrt_block_variants.def"
+#include "rrt_scratch.h"
 
 using namespace rrtdev;
 
@@ -100,7 +101,7 @@ struct LaunchPlan {
     size_t lds_bytes = 0;       // dynamic LDS per workgroup
 };
 
-// Grow-only device scratch: a pointer and its capacity in the caller's units (goals, slabs, rows; 1 for a buffer of one fixed size).
+// Grow-only device scratch: a pointer and its capacity in the caller's units (goals, slabs, rows, vertices).
 struct RRT_PRIVATE DevBuf {
     void *p = nullptr;
     int64_t cap = 0;
@@ -127,6 +128,51 @@ struct RRT_PRIVATE DevBuf {
     template <typename T>
     T *as() const {
         return static_cast<T *>(p);
+    }
+    // A buffer of several arrays (rrt_scratch.h): room for `want` units of Layout, whose constructor says how many bytes that is,
+    // and the arrays of what is allocated.  A buffer is carved by its capacity, never by the count of the call at hand.
+    template <typename Layout, typename... Extra>
+    hipError_t reserve(int64_t want, Extra... extra) {
+        return reserve(want, Layout(nullptr, (size_t)want, extra...).bytes);
+    }
+    template <typename Layout, typename... Extra>
+    Layout carve(Extra... extra) const {
+        return Layout(p, (size_t)cap, extra...);
+    }
+};
+
+// The kernel times of the stages of a call.  The call records marks (events, created by the first call) on its stream; the timer's
+// table says between which two marks each stage lies, so that stages may share a mark or have a pair each.
+constexpr int STAGE_MARKS = 10;
+constexpr int STAGES_IN_A_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}};               // four marks around three stages
+constexpr int STAGES_IN_PAIRS[][2] = {{0, 1}, {2, 3}, {4, 5}, {6, 7}, {8, 9}};  // a pair around each stage
+struct RRT_PRIVATE StageTimer {
+    const int (*stages)[2];
+    hipEvent_t ev[STAGE_MARKS] = {};
+    int ran = 0;  // stages of the last successful call that ran, the table's first ones; 0: no call yet, or the last one failed
+    explicit StageTimer(const int (*stages_)[2]) : stages(stages_) {}
+    StageTimer(const StageTimer &) = delete;
+    StageTimer &operator=(const StageTimer &) = delete;
+    ~StageTimer() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    // the first n marks exist: a call makes sure of it before it records any, so that no stage has the creation of an event in it
+    hipError_t create(int n) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < n && e == hipSuccess; ++k)
+            if (!ev[k]) e = hipEventCreate(&ev[k]);
+        return e;
+    }
+    hipError_t mark(int k, hipStream_t stream) { return hipEventRecord(ev[k], stream); }
+    // ms[0, count): the time of every stage that ran, 0 for one that did not
+    hipError_t read(float *ms, int count) const {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < count && e == hipSuccess; ++k) {
+            ms[k] = 0.f;
+            if (k < ran) e = hipEventElapsedTime(&ms[k], ev[stages[k][0]], ev[stages[k][1]]);
+        }
+        return e;
     }
 };
 
@@ -185,40 +231,38 @@ struct rrt_batch {
     DevBuf pose_h;                       // u8  [goals] rrt_batch_connect_poses: goal heading indices
     DevBuf pose_counts;                  // u32 [goals][2] ... words evaluated, sweeps run
     int32_t pose_last_m = -1;            // goals of the last successful rrt_batch_connect_poses; -1: none
-    // rrt_batch_routes: per-goal arrays and the rows of the routes (rrt_routes.h).  Both are carved by the capacity they were allocated with.
-    DevBuf route_goal;                   // [length | raw_off | fin_off | cnt | kept | err] for route_goal.cap goals
-    DevBuf route_row;                    // [row_xy | row_id | out_xy | out_id] for route_row.cap rows
+    // rrt_batch_routes: per-goal arrays and the rows of the routes (rrt_routes.h)
+    DevBuf route_goal;                   // RouteGoalScratch
+    DevBuf route_row;                    // RouteRowScratch
     int64_t route_rows = -1;             // dense rows the last rrt_batch_routes left for rrt_batch_routes_rows; -1: none (launch, rearm)
-    // rrt_batch_pose_routes: per-goal arrays, per-row arrays, the legs' sweeps and the points (rrt_pose_routes.h).  Carved by the capacity
-    // they were allocated with; the last two are allocated by the first call that asks for points.
-    DevBuf pose_route_goal;              // [length f64 | raw_off i64 + 1 | goal_pt_off i64 + 1 | cnt i32 | err i32] for pose_route_goal.cap goals
-    DevBuf pose_route_row;               // [leg_len f64 | pt_off i64 + 1 | row_xy u32 | row_id i32 | npts i32 | row_h u8] for pose_route_row.cap rows
+    // rrt_batch_pose_routes: per-goal arrays, per-row arrays, the legs' sweeps and the points (rrt_pose_routes.h).  The last two are
+    // allocated by the first call that asks for points.
+    DevBuf pose_route_goal;              // PoseRouteGoalScratch
+    DevBuf pose_route_row;               // PoseRouteRowScratch
     DevBuf pose_route_sweep;             // dub_sweep_t [rows]
     DevBuf pose_route_pts;               // f64 [points][2]
     int64_t pose_route_rows = -1;        // rows the last rrt_batch_pose_routes / rrt_batch_pose_shortcuts left for rrt_batch_pose_routes_rows; -1: none (launch, rearm, keep, grow)
     int64_t pose_route_points = -1;      // ... and points for rrt_batch_pose_routes_points; -1: none, or that call did not ask for points
-    hipEvent_t ev_pose_route[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // a pair around each of its four stages
-    int pose_route_timed = 0;            // stages of the last successful rrt_batch_pose_routes that ran (0: none, 3: no points, 4)
+    StageTimer pose_route_time{STAGES_IN_PAIRS};  // its four stages; 3 ran: no points
     // rrt_batch_pose_shortcuts: rrt_batch_pose_routes with the shortcut pass.  It shares everything above but the stage times (its rows
     // and points are what pose_route_rows / pose_route_points count), and adds the raw rows that the pass rewrites in place.
-    DevBuf pose_cut_goal;                // [fin_off i64 + 1 | kept i32] for pose_cut_goal.cap goals
-    DevBuf pose_cut_row;                 // [row_xy u32 | row_id i32 | row_h u8] for pose_cut_row.cap raw rows
-    hipEvent_t ev_pose_cut[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // a pair around each of its five stages
-    int pose_cut_timed = 0;              // stages of the last successful rrt_batch_pose_shortcuts that ran (0: none, 4: no points, 5)
+    DevBuf pose_cut_goal;                // PoseCutGoalScratch
+    DevBuf pose_cut_row;                 // PoseCutRowScratch
+    StageTimer pose_cut_time{STAGES_IN_PAIRS};  // its five stages; 4 ran: no points
     // rrt_batch_keep_tree / rrt_batch_keep_pose_tree: the views of the queries that were kept on a new map (rrt_keep.h, rrt_pose_keep.h),
     // allocated at the first call per query
-    std::vector<DevBuf> keep;            // [Q] empty, or [live_vcost f64 | live_nodes u32 | live_id i32 | a Dubins batch: live_heading u8], each of n_cap
+    std::vector<DevBuf> keep;            // [Q] empty, or KeepScratch of n_cap vertices
     std::vector<int32_t> keep_alive;     // [Q] vertices of the view; -1: no view, the goals and routes calls see the whole tree
-    DevBuf keep_tmp;                     // [anc i32 x 2 | ok u8 x 2 | count i32 at the end], each array of n_cap (rounded up to 8 bytes)
-    hipEvent_t ev_keep[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_keep_tree
-    bool keep_timed = false;
+    DevBuf keep_tmp;                     // KeepTmpScratch of n_cap vertices
+    StageTimer keep_time{STAGES_IN_A_ROW};  // the three stages of the last rrt_batch_keep_tree
     // rrt_batch_grow: a query armed as a loop stopped mid-way runs with D->n = j0 + m (rrt_seed.h)
     std::vector<int32_t> grow_n;            // [Q] the query's own n while it is armed so; -1 otherwise (rrt_batch_sync puts it back)
     std::vector<uint64_t> grow_gen;         // [Q] while it is armed so: the grid generation the seed was built on (rrt_batch_launch asks for it)
     std::vector<const uint8_t *> grow_og;   // [Q] ... and that grid
-    DevBuf seed_tmp;                        // [rank i32 | new_parent i32 | err i32], the arrays of n_cap
-    hipEvent_t ev_seed[4] = {nullptr, nullptr, nullptr, nullptr};  // around the three stages of the last rrt_batch_grow
-    bool seed_timed = false;
+    DevBuf seed_tmp;                        // SeedTmpScratch of n_cap vertices
+    StageTimer seed_time{STAGES_IN_A_ROW};  // the three stages of the last rrt_batch_grow
+    // the rows and points an earlier routes call left are gone (a launch, a rearm, a keep, a grow: they belong to another tree or view)
+    void drop_routes() { route_rows = pose_route_rows = pose_route_points = -1; }
 };
 
 // ---- defined in rrt_engine.hip ----

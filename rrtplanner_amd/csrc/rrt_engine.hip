@@ -375,17 +375,9 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
     void *ptrs[] = {b->d_desc,  b->d_samples,   b->d_slab,        b->d_bitmap, b->d_unitball,  b->d_cellrec,
                     b->d_spill, b->d_cbest_log, b->d_nearest_log, b->d_j_log,  b->d_accept_log, b->d_cellcnt,
                     b->d_team,  b->d_kids,      b->d_frontier,    b->d_vsoln,  b->d_heading,   b->d_shead,
-                    b->d_dubpath};  // (the scratch of the tree calls, every DevBuf, goes with `delete b`)
+                    b->d_dubpath};  // (the scratch of the tree calls and their stage timers, every DevBuf and StageTimer, go with `delete b`)
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (hipEvent_t e : b->ev_keep)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : b->ev_seed)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : b->ev_pose_route)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : b->ev_pose_cut)
-        if (e) (void)hipEventDestroy(e);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -699,7 +691,7 @@ extern "C" int rrt_batch_set_unitball(rrt_batch *b, int32_t q, const double *uni
 extern "C" int rrt_batch_rearm(rrt_batch *b) {
     if (!b) return fail(nullptr, RRT_E_ARG, "rrt_batch_rearm: NULL");
     rrt_ctx *ctx = b->ctx;
-    b->route_rows = b->pose_route_rows = b->pose_route_points = -1;
+    b->drop_routes();
     drop_keep_views(b);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (int q = 0; q < b->Q; ++q) {
@@ -890,7 +882,7 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
             return fail(ctx, RRT_E_ARG, "rrt_batch_launch: the context's grid was replaced since query %d was seeded by rrt_batch_grow (grid generation %llu then, "
                         "%llu now): its seed belongs to the other grid (rrt_batch_rearm drops the grow)", q, (unsigned long long)b->grow_gen[(size_t)q],
                         (unsigned long long)ctx->grid_gen);
-    b->route_rows = b->pose_route_rows = b->pose_route_points = -1;
+    b->drop_routes();
     drop_keep_views(b);
     if (!ctx->og) return fail(ctx, RRT_E_NOGRID, "rrt_batch_launch: no grid");
     if (b->gridW != ctx->W || b->gridH != ctx->H) return fail(ctx, RRT_E_ARG, "rrt_batch_launch: grid changed shape");

@@ -59,13 +59,50 @@ static TreeRef tree_ref(rrt_batch *b, int32_t q) {
     const size_t at = (size_t)q * b->node_stride;
     TreeRef t{b->d_nodes + at, b->d_vcost + at, b->d_parent + at, b->d_heading ? b->d_heading + at : nullptr};
     if (b->keep[(size_t)q].p) {
-        t.live_vcost = b->keep[(size_t)q].as<double>();
-        t.live_nodes = reinterpret_cast<uint32_t *>(t.live_vcost + b->n_cap);
-        t.live_id = reinterpret_cast<int32_t *>(t.live_nodes + b->n_cap);
-        if (b->d_heading) t.live_heading = reinterpret_cast<uint8_t *>(t.live_id + b->n_cap);
+        const KeepScratch k = b->keep[(size_t)q].carve<KeepScratch>(b->d_heading != nullptr);
+        t.live_vcost = k.live_vcost;
+        t.live_nodes = k.live_nodes;
+        t.live_id = k.live_id;
+        t.live_heading = k.live_heading;
     }
     t.kept = std::min(b->keep_alive[(size_t)q], b->h_desc[(size_t)q].j);
     return t;
+}
+
+// What a decision (goals_decide, poses_decide) runs over: the whole tree of query q, or, for a query that was kept on this grid
+// (rrt_batch_keep_tree, rrt_batch_keep_pose_tree), the view of its alive vertices, dense and in the original order.  `launch` gets
+// (nodes, vcost, heading, j) and launches the kernel, which answers in indices of what it was given; rrt_keep_remap_kernel then turns
+// those of a view into the original ones.
+template <typename Launch>
+static void decide_over(rrt_batch *b, int32_t q, int32_t *vertex, int32_t m, Launch launch) {
+    const TreeRef t = tree_ref(b, q);
+    const bool view = t.kept >= 0;
+    const int32_t j = view ? t.kept : b->h_desc[(size_t)q].j;
+    launch(view ? t.live_nodes : t.nodes, view ? t.live_vcost : t.vcost, view ? t.live_heading : t.heading, j);
+    if (view)
+        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, b->ctx->stream, vertex,
+                           (const int32_t *)t.live_id, m, j);
+}
+
+// The m rows (x, y) or, with nh > 0, (x, y, heading index < nh) of a call, checked against the grid one after the other and then
+// packed into the batch's staging buffers (stage: x | y << 16, stage8: the headings).  noun: what the call names a row.  A refusal
+// leaves the staging buffers as they were.
+static int stage_cells(const char *who, rrt_batch *b, int32_t q, const char *noun, const int32_t *rows, int32_t m, int nh) {
+    rrt_ctx *ctx = b->ctx;
+    const int W = ctx->W, H = ctx->H, row = nh > 0 ? 3 : 2;
+    for (int k = 0; k < m; ++k) {
+        const int x = rows[row * k], y = rows[row * k + 1];
+        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: %s %d = (%d, %d) outside the %dx%d grid", who, noun, k, x, y, W, H);
+        if (nh > 0 && (rows[row * k + 2] < 0 || rows[row * k + 2] >= nh))
+            return fail(ctx, RRT_E_ARG, "%s: %s %d has heading %d, query %d has headings [0, %d)", who, noun, k, rows[row * k + 2], q, nh);
+    }
+    b->stage.resize((size_t)m);
+    if (nh > 0) b->stage8.resize((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        b->stage[(size_t)k] = ((uint32_t)rows[row * k] & 0xffffu) | ((uint32_t)rows[row * k + 1] << 16);
+        if (nh > 0) b->stage8[(size_t)k] = (uint8_t)rows[row * k + 2];
+    }
+    return RRT_OK;
 }
 
 // ---- the scratch of the goals and poses calls ----
@@ -115,27 +152,14 @@ static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (an edge to a goal is a Dubins word to a goal pose; these kernels price straight lines)", who);
     if (const int rc = refuse_goals_call(who, b, q, m, "goals")) return rc;
     const QDesc &d = b->h_desc[(size_t)q];
-    const int W = ctx->W, H = ctx->H;
-    b->stage.resize((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        const int x = goals_xy[2 * k], y = goals_xy[2 * k + 1];
-        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
-        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
-    }
+    if (const int rc = stage_cells(who, b, q, "goal", goals_xy, m, 0)) return rc;
     if (m == 0) return RRT_OK;
     int slabs = 0;
     HIPCHK(ctx, goal_scratch(b, m, slabs));
     if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
-    // a query that was kept on this grid (rrt_batch_keep_tree): the decision over the view of its alive vertices, dense and in the
-    // original order; the kernel answers in indices of the view, rrt_keep_remap_kernel turns them into the original ones
-    const TreeRef t = tree_ref(b, q);
-    const bool view = t.kept >= 0;
     GoalsView gv{};
     gv.og = ctx->og;
-    gv.H = H;
-    gv.nodes = view ? t.live_nodes : t.nodes;
-    gv.vcost = view ? t.live_vcost : t.vcost;
-    gv.j = view ? t.kept : d.j;
+    gv.H = ctx->H;
     gv.goals = b->goal_xy.as<uint32_t>();
     gv.m = m;
     gv.order = b->goal_order.as<uint32_t>();
@@ -143,10 +167,12 @@ static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
     gv.vertex = b->goal_vertex.as<int32_t>();
     gv.cost = b->goal_cost.as<double>();
     HIPCHK(ctx, hipMemcpyAsync(b->goal_xy.p, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
-    if (view)
-        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, gv.vertex,
-                           (const int32_t *)t.live_id, m, gv.j);
+    decide_over(b, q, gv.vertex, m, [&](const uint32_t *nodes, const double *vcost, const uint8_t *, int32_t j) {
+        gv.nodes = nodes;
+        gv.vcost = vcost;
+        gv.j = j;
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_goals_large_kernel : rrt_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, gv);
+    });
     HIPCHK(ctx, hipGetLastError());
     return RRT_OK;
 }
@@ -171,26 +197,17 @@ extern "C" int rrt_plan_connect_goals(rrt_ctx *ctx, const int32_t *goals_xy, int
 // (`use`: the call a straight-line batch is sent to), the poses packed and uploaded, the scratch, and the pose goals kernel launched
 // on the context's stream.  Nothing is read back and nothing waited for.  m == 0: RRT_OK, nothing launched.  pose_last_m is left at -1
 // (the counters are being rewritten) for the caller to set once its call has succeeded.
-// ev: nullptr, or two events to create if need be and to record around the upload and the kernel.
+// time: nullptr, or the timer whose marks 0 and 1 to create if need be and to record around the upload and the kernel.
 static int poses_decide(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, bool null_out, const char *use,
-                        hipEvent_t *ev = nullptr) {
+                        StageTimer *time = nullptr) {
     rrt_ctx *ctx = b->ctx;
     if (!poses_xyh || null_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     if (!(b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use %s)", who, use);
     if (const int rc = refuse_goals_call(who, b, q, m, "goal poses")) return rc;
     const QDesc &d = b->h_desc[(size_t)q];
-    const int W = ctx->W, H = ctx->H;
     if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
-    b->stage.resize((size_t)m);
-    b->stage8.resize((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        const int x = poses_xyh[3 * k], y = poses_xyh[3 * k + 1], h = poses_xyh[3 * k + 2];
-        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: goal %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
-        if (h < 0 || h >= d.nh) return fail(ctx, RRT_E_ARG, "%s: goal %d has heading %d, query %d has headings [0, %d)", who, k, h, q, d.nh);
-        b->stage[(size_t)k] = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
-        b->stage8[(size_t)k] = (uint8_t)h;
-    }
+    if (const int rc = stage_cells(who, b, q, "goal", poses_xyh, m, d.nh)) return rc;
     if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
     b->pose_last_m = m == 0 ? 0 : -1;  // (-1 until this call has succeeded: the counters are being rewritten)
     if (m == 0) return RRT_OK;
@@ -198,17 +215,10 @@ static int poses_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
     HIPCHK(ctx, goal_scratch(b, m, slabs));
     HIPCHK(ctx, b->pose_h.reserve(m, (size_t)m));
     HIPCHK(ctx, b->pose_counts.reserve(m, (size_t)m * 2 * sizeof(uint32_t)));
-    // a query that was kept on this grid (rrt_batch_keep_pose_tree): the decision over the view, as in goals_decide
-    const TreeRef t = tree_ref(b, q);
-    const bool view = t.kept >= 0;
     PoseGoalsView pv{};
     pv.og = ctx->og;
-    pv.W = W;
-    pv.H = H;
-    pv.nodes = view ? t.live_nodes : t.nodes;
-    pv.vcost = view ? t.live_vcost : t.vcost;
-    pv.heading = view ? t.live_heading : t.heading;
-    pv.j = view ? t.kept : d.j;
+    pv.W = ctx->W;
+    pv.H = ctx->H;
     pv.nh = d.nh;
     pv.rho = d.rho;
     pv.goals = b->goal_xy.as<uint32_t>();
@@ -219,16 +229,18 @@ static int poses_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
     pv.vertex = b->goal_vertex.as<int32_t>();
     pv.cost = b->goal_cost.as<double>();
     pv.counts = b->pose_counts.as<uint32_t>();
-    for (int k = 0; ev && k < 2; ++k)
-        if (!ev[k]) HIPCHK(ctx, hipEventCreate(&ev[k]));
-    if (ev) HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
+    if (time) HIPCHK(ctx, time->create(2));
+    if (time) HIPCHK(ctx, time->mark(0, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->goal_xy.p, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->pose_h.p, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
-    if (view)
-        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, pv.vertex,
-                           (const int32_t *)t.live_id, m, pv.j);
-    if (ev) HIPCHK(ctx, hipEventRecord(ev[1], ctx->stream));
+    decide_over(b, q, pv.vertex, m, [&](const uint32_t *nodes, const double *vcost, const uint8_t *heading, int32_t j) {
+        pv.nodes = nodes;
+        pv.vcost = vcost;
+        pv.heading = heading;
+        pv.j = j;
+        hipLaunchKernelGGL(rrt_pose_goals_kernel, dim3((unsigned)slabs), dim3(TPB), 0, ctx->stream, pv);
+    });
+    if (time) HIPCHK(ctx, time->mark(1, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     return RRT_OK;
 }
@@ -290,19 +302,19 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
     if (poses && (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0))) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     drop_keep_views(b, q);
-    b->keep_timed = false;
-    const size_t cap = ((size_t)b->n_cap + 7) & ~(size_t)7;
-    HIPCHK(ctx, b->keep_tmp.reserve(1, cap * 10 + 8));
-    HIPCHK(ctx, b->keep[(size_t)q].reserve(1, (size_t)b->n_cap * (poses ? 17 : 16)));  // (a batch is a Dubins batch or not for life)
-    for (hipEvent_t &e : b->ev_keep)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    int32_t *anc[2] = {b->keep_tmp.as<int32_t>(), b->keep_tmp.as<int32_t>() + cap};
-    uint8_t *ok[2] = {b->keep_tmp.as<uint8_t>() + cap * 8, b->keep_tmp.as<uint8_t>() + cap * 9};
-    int32_t *d_count = reinterpret_cast<int32_t *>(ok[1] + cap);
+    StageTimer &time = b->keep_time;
+    time.ran = 0;
+    HIPCHK(ctx, b->keep_tmp.reserve<KeepTmpScratch>(b->n_cap));
+    HIPCHK(ctx, b->keep[(size_t)q].reserve<KeepScratch>(b->n_cap, poses));  // (a batch is a Dubins batch or not for life)
+    HIPCHK(ctx, time.create(4));
+    const KeepTmpScratch tmp = b->keep_tmp.carve<KeepTmpScratch>();
+    auto &anc = tmp.anc;
+    auto &ok = tmp.ok;
+    int32_t *d_count = tmp.count;
     int32_t count = 0;
     if (j > 0) {
         const TreeRef t = tree_ref(b, q);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[0], ctx->stream));
+        HIPCHK(ctx, time.mark(0, ctx->stream));
         if (poses) {  // one edge per lane, 64 a wavefront and round
             PoseKeepView kv{};
             kv.og = ctx->og;
@@ -333,7 +345,7 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
             hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
                                ctx->stream, kv);
         }
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[1], ctx->stream));
+        HIPCHK(ctx, time.mark(1, ctx->stream));
         // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
         int rounds = 1;
         while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
@@ -341,7 +353,7 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
         for (int r = 0; r < rounds; ++r, cur ^= 1)
             hipLaunchKernelGGL(rrt_keep_jump_kernel, dim3((unsigned)((j + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, (const uint8_t *)ok[cur],
                                (const int32_t *)anc[cur], ok[cur ^ 1], anc[cur ^ 1], j);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[2], ctx->stream));
+        HIPCHK(ctx, time.mark(2, ctx->stream));
         KeepCompact kc{};
         kc.nodes = t.nodes;
         kc.vcost = t.vcost;
@@ -357,18 +369,18 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
         if (poses)
             hipLaunchKernelGGL(rrt_pose_keep_gather_kernel, dim3((unsigned)((j + POSE_KEEP_TPB - 1) / POSE_KEEP_TPB)), dim3(POSE_KEEP_TPB), 0, ctx->stream,
                                (const uint8_t *)t.heading, (const int32_t *)t.live_id, (const int32_t *)d_count, t.live_heading, j);
-        HIPCHK(ctx, hipEventRecord(b->ev_keep[3], ctx->stream));
+        HIPCHK(ctx, time.mark(3, ctx->stream));
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
         if (alive) HIPCHK(ctx, hipMemcpyAsync(alive, kc.alive, (size_t)j, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, wait_stream_spin(ctx->stream));
         if (count < 0 || count > j) return fail(ctx, RRT_E_HIP, "%s: %d of %d vertices alive", who, count, j);
-        b->keep_timed = true;
+        time.ran = 3;
     }
     b->ran_gen[(size_t)q] = ctx->grid_gen;
     b->ran_og[(size_t)q] = ctx->og;
     b->keep_alive[(size_t)q] = count;
-    b->route_rows = b->pose_route_rows = b->pose_route_points = -1;  // the rows of an earlier routes call belong to another view
+    b->drop_routes();  // the rows of an earlier routes call belong to another view
     *n_alive = count;
     return RRT_OK;
 }
@@ -393,8 +405,8 @@ extern "C" int rrt_plan_keep_pose_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *
 
 extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) {
     if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree_ms: NULL");
-    if (!b->keep_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_keep_tree_ms: no rrt_batch_keep_tree on this batch yet, or its last one failed");
-    for (int k = 0; k < 3; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_keep[k], b->ev_keep[k + 1]));
+    if (!b->keep_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_keep_tree_ms: no rrt_batch_keep_tree on this batch yet, or its last one failed");
+    HIPCHK(b->ctx, b->keep_time.read(ms, 3));
     return RRT_OK;
 }
 
@@ -425,7 +437,6 @@ extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
 static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
                       bool poses) {
     rrt_ctx *ctx = b->ctx;
-    const int row = poses ? 3 : 2;  // int32 words of a sample
     if (!j0_out || !log0 || (m > 0 && !samples)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     if (!poses && (b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (the seed kernels carry no headings)", who);
@@ -453,28 +464,16 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     const int j0 = t.kept > 0 ? t.kept : j_old;
     if ((long long)j0 + m > own_n)
         return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j0, m, own_n, own_n - j0);
-    const int W = ctx->W, H = ctx->H;
-    for (int k = 0; k < m; ++k) {
-        const int x = samples[row * k], y = samples[row * k + 1];
-        if (x < 0 || x >= W || y < 0 || y >= H) return fail(ctx, RRT_E_ARG, "%s: sample %d = (%d, %d) outside the %dx%d grid", who, k, x, y, W, H);
-        if (poses && (samples[row * k + 2] < 0 || samples[row * k + 2] >= d.nh))
-            return fail(ctx, RRT_E_ARG, "%s: sample %d has heading %d, query %d has headings [0, %d)", who, k, samples[row * k + 2], q, d.nh);
-    }
-    b->stage.resize((size_t)m);  // (past the last refusal: the staging buffers are the first thing of the batch this call touches)
-    for (int k = 0; k < m; ++k)
-        b->stage[(size_t)k] = ((uint32_t)samples[row * k] & 0xffffu) | ((uint32_t)samples[row * k + 1] << 16);
-    if (poses) {
-        b->stage8.resize((size_t)m);
-        for (int k = 0; k < m; ++k) b->stage8[(size_t)k] = (uint8_t)samples[row * k + 2];
-    }
+    // (the last refusal: the staging buffers, written once every sample has passed, are the first thing of the batch this call touches)
+    if (const int rc = stage_cells(who, b, q, "sample", samples, m, poses ? d.nh : 0)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t cap = (size_t)b->n_cap;
-    HIPCHK(ctx, b->seed_tmp.reserve(1, (2 * cap + 2) * sizeof(int32_t)));
-    for (hipEvent_t &e : b->ev_seed)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
+    const SeedTmpScratch tmp = b->seed_tmp.carve<SeedTmpScratch>();
+    StageTimer &time = b->seed_time;
+    HIPCHK(ctx, time.create(4));
     // ---- from here on the query is being replaced ----
-    b->seed_timed = false;
-    b->route_rows = b->pose_route_rows = b->pose_route_points = -1;
+    time.ran = 0;
+    b->drop_routes();
     d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
     SeedView sv{};
     sv.nodes = t.nodes;
@@ -483,18 +482,18 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     sv.j_old = j_old;
     sv.j0 = j0;
     sv.node_stride = b->node_stride;
-    sv.rank = b->seed_tmp.as<int32_t>();
-    sv.new_parent = sv.rank + cap;
-    sv.err = sv.rank + 2 * cap;
+    sv.rank = tmp.rank;
+    sv.new_parent = tmp.new_parent;
+    sv.err = tmp.err;
     sv.bitmap = b->d_bitmap + (size_t)q * b->bitmap_words;
     sv.bitmap_words = b->bitmap_words;
-    sv.H = H;
+    sv.H = ctx->H;
     sv.live_vcost = t.kept > 0 ? t.live_vcost : nullptr;
     sv.live_nodes = t.kept > 0 ? t.live_nodes : nullptr;
     sv.live_id = t.kept > 0 ? t.live_id : nullptr;
     auto blocks = [](int items) { return dim3((unsigned)((items + SEED_TPB - 1) / SEED_TPB)); };
     HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[0], ctx->stream));
+    HIPCHK(ctx, time.mark(0, ctx->stream));
     if (sv.live_id) {
         HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)j_old * sizeof(int32_t), ctx->stream));
         hipLaunchKernelGGL(rrt_seed_rank_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
@@ -504,10 +503,10 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     if (poses && sv.live_id)  // (without a view heading[0, j0) already stands; rrt_pose_seed.h says why the slots behind j0 are left)
         hipLaunchKernelGGL(rrt_pose_seed_heading_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, t.heading, (const uint8_t *)t.live_heading, j0,
                            b->node_stride);
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[1], ctx->stream));
+    HIPCHK(ctx, time.mark(1, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
     if (j0 > 1) hipLaunchKernelGGL(rrt_seed_bitmap_kernel, blocks(j0 - 1), dim3(SEED_TPB), 0, ctx->stream, sv);
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[2], ctx->stream));
+    HIPCHK(ctx, time.mark(2, ctx->stream));
     if (b->d_cellcnt) {  // (a batch without cell records, RRT_FLAG_SERIAL: its kernel scans the node array)
         SeedRecords sr{};
         sr.nodes = sv.nodes;
@@ -523,7 +522,7 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
         sr.err = sv.err;
         hipLaunchKernelGGL(rrt_seed_records_kernel, dim3(SEED_WG), dim3(SEED_TPB), 0, ctx->stream, sr);
     }
-    HIPCHK(ctx, hipEventRecord(b->ev_seed[3], ctx->stream));
+    HIPCHK(ctx, time.mark(3, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     int32_t err = 0;
     HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
@@ -553,7 +552,7 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     b->grow_og[(size_t)q] = ctx->og;
     HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    b->seed_timed = true;
+    time.ran = 3;
     *j0_out = j0;
     *log0 = j0;
     return RRT_OK;
@@ -587,8 +586,8 @@ extern "C" int rrt_plan_grow_poses(rrt_ctx *ctx, const int32_t *samples_xyh, int
 extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
     if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
     if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
-    if (!b->seed_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
-    for (int k = 0; k < count; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_seed[k], b->ev_seed[k + 1]));
+    if (!b->seed_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
+    HIPCHK(b->ctx, b->seed_time.read(ms, count));
     return RRT_OK;
 }
 
@@ -609,10 +608,9 @@ static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t 
         b->route_rows = 0;
         return RRT_OK;
     }
-    // [length f64 m | raw_off i64 m+1 | fin_off i64 m+1 | cnt i32 m | kept i32 m | err i32]
-    HIPCHK(ctx, b->route_goal.reserve(m, (size_t)m * 32 + 2 * sizeof(int64_t) + sizeof(int32_t)));
+    HIPCHK(ctx, b->route_goal.reserve<RouteGoalScratch>(m));
+    const RouteGoalScratch goal = b->route_goal.carve<RouteGoalScratch>();
     const bool cut = (flags & RRT_ROUTES_SHORTCUT) != 0;
-    const size_t cap = (size_t)b->route_goal.cap;
     const TreeRef t = tree_ref(b, q);
     RoutesView rv{};
     rv.og = ctx->og;
@@ -623,12 +621,12 @@ static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t 
     rv.goals = b->goal_xy.as<uint32_t>();
     rv.vertex = b->goal_vertex.as<int32_t>();
     rv.m = m;
-    rv.length = b->route_goal.as<double>();
-    rv.raw_off = reinterpret_cast<int64_t *>(rv.length + cap);
-    rv.fin_off = cut ? rv.raw_off + cap + 1 : rv.raw_off;
-    rv.cnt = reinterpret_cast<int32_t *>(rv.raw_off + 2 * (cap + 1));
-    rv.kept = rv.cnt + cap;
-    rv.err = rv.kept + cap;
+    rv.length = goal.length;
+    rv.raw_off = goal.raw_off;
+    rv.fin_off = cut ? goal.fin_off : goal.raw_off;
+    rv.cnt = goal.cnt;
+    rv.kept = goal.kept;
+    rv.err = goal.err;
     const unsigned lanes_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB), waves_grid = (unsigned)((m + ROUTE_TPB / 64 - 1) / (ROUTE_TPB / 64));
     HIPCHK(ctx, hipMemsetAsync(rv.err, 0, sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
@@ -645,13 +643,12 @@ static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t 
     if (raw_rows < 0 || (uint64_t)raw_rows > ROUTE_ROW_BUDGET)
         return fail(ctx, RRT_E_ARG, "%s: the routes of these %d goals have %lld rows together, at most %zu per call: pass fewer goals at a time", who, m,
                     (long long)raw_rows, ROUTE_ROW_BUDGET);
-    // [row_xy u32 | row_id i32 | out_xy i32 x 2 | out_id i32], each of raw_rows (shortcuts only ever drop rows)
-    HIPCHK(ctx, b->route_row.reserve(raw_rows, (size_t)raw_rows * 5 * sizeof(int32_t)));
-    const size_t rcap = (size_t)b->route_row.cap;
-    rv.row_xy = b->route_row.as<uint32_t>();
-    rv.row_id = reinterpret_cast<int32_t *>(rv.row_xy + rcap);
-    rv.out_xy = rv.row_id + rcap;
-    rv.out_id = rv.out_xy + 2 * rcap;
+    HIPCHK(ctx, b->route_row.reserve<RouteRowScratch>(raw_rows));
+    const RouteRowScratch row = b->route_row.carve<RouteRowScratch>();
+    rv.row_xy = row.row_xy;
+    rv.row_id = row.row_id;
+    rv.out_xy = row.out_xy;
+    rv.out_id = row.out_id;
     hipLaunchKernelGGL(rrt_route_fill_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv, cut ? 0 : 1);
     if (cut) {
         const unsigned wgs = (unsigned)(m < ROUTE_CUT_MAX_WG ? m : ROUTE_CUT_MAX_WG);
@@ -676,10 +673,9 @@ static int batch_routes_rows(const char *who, rrt_batch *b, int32_t *xy, int32_t
     if (rows == 0) return RRT_OK;
     if (!xy || !id) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t rcap = (size_t)b->route_row.cap;
-    const int32_t *out_xy = b->route_row.as<int32_t>() + 2 * rcap;
-    HIPCHK(ctx, hipMemcpyAsync(xy, out_xy, (size_t)rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(id, out_xy + 2 * rcap, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    const RouteRowScratch row = b->route_row.carve<RouteRowScratch>();
+    HIPCHK(ctx, hipMemcpyAsync(xy, row.out_xy, (size_t)rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(id, row.out_id, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     return RRT_OK;
 }
@@ -707,17 +703,17 @@ extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int6
 // rrt_batch_pose_routes (cut == false) and rrt_batch_pose_shortcuts (cut == true) are one call: with `cut` the rows of the walks go to
 // scratch of their own, the shortcut kernel keeps some of them, and the dense rows that the leg, length and points kernels read are
 // the kept ones under their own offsets.  The rows and points either call leaves are what the _rows / _points calls serve; the stage
-// times are kept apart (ev_pose_route / ev_pose_cut), so that rrt_batch_pose_routes_ms goes on reporting the last plain call.
+// times are kept apart (pose_route_time / pose_cut_time), so that rrt_batch_pose_routes_ms goes on reporting the last plain call.
 static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
                              double *length, int64_t *offsets, int64_t *point_offsets, bool cut) {
     rrt_ctx *ctx = b->ctx;
     b->pose_route_rows = b->pose_route_points = -1;  // whatever happens below, the rows and points of an earlier call are gone
-    (cut ? b->pose_cut_timed : b->pose_route_timed) = 0;
-    hipEvent_t *ev = cut ? b->ev_pose_cut : b->ev_pose_route;
-    const int nev = cut ? 10 : 8, leg_ev = cut ? 6 : 4;  // (the events around legs + lengths, and behind them those around the points)
+    StageTimer &time = cut ? b->pose_cut_time : b->pose_route_time;
+    time.ran = 0;
+    const int leg_ev = cut ? 6 : 4;  // (the marks around legs + lengths, and behind them those around the points)
     if (flags & ~(uint32_t)RRT_POSE_ROUTES_POINTS) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_POSE_ROUTES_POINTS is defined", who, flags);
     const bool pts = (flags & RRT_POSE_ROUTES_POINTS) != 0;
-    if (const int rc = poses_decide(who, b, q, poses_xyh, m, !vertex || !cost || !length || !offsets || (pts && !point_offsets), "rrt_batch_routes", ev);
+    if (const int rc = poses_decide(who, b, q, poses_xyh, m, !vertex || !cost || !length || !offsets || (pts && !point_offsets), "rrt_batch_routes", &time);
         rc != RRT_OK)
         return rc;
     if (m == 0) {
@@ -727,11 +723,9 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         b->pose_route_points = pts ? 0 : -1;
         return RRT_OK;
     }
-    for (int k = 0; k < nev; ++k)
-        if (!ev[k]) HIPCHK(ctx, hipEventCreate(&ev[k]));
-    // [length f64 m | raw_off i64 m+1 | goal_pt_off i64 m+1 | cnt i32 m | err i32]
-    HIPCHK(ctx, b->pose_route_goal.reserve(m, (size_t)m * 28 + 2 * sizeof(int64_t) + sizeof(int32_t)));
-    const size_t cap = (size_t)b->pose_route_goal.cap;
+    HIPCHK(ctx, time.create(leg_ev + 4));
+    HIPCHK(ctx, b->pose_route_goal.reserve<PoseRouteGoalScratch>(m));
+    const PoseRouteGoalScratch goal = b->pose_route_goal.carve<PoseRouteGoalScratch>();
     const QDesc &d = b->h_desc[(size_t)q];
     const TreeRef t = tree_ref(b, q);  // (the whole tree: the vertex numbers the decision answers in are its own, after a keep too)
     PoseRoutesView pr{};
@@ -746,33 +740,31 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     pr.goal_h = b->pose_h.as<uint8_t>();
     pr.vertex = b->goal_vertex.as<int32_t>();
     pr.m = m;
-    pr.length = b->pose_route_goal.as<double>();
-    int64_t *raw_off = reinterpret_cast<int64_t *>(pr.length + cap);
-    pr.raw_off = raw_off;
-    pr.goal_pt_off = pts ? raw_off + cap + 1 : nullptr;
-    int32_t *cnt = reinterpret_cast<int32_t *>(raw_off + 2 * (cap + 1));
-    pr.cnt = cnt;
-    pr.err = cnt + cap;
+    pr.length = goal.length;
+    pr.raw_off = goal.raw_off;
+    pr.goal_pt_off = pts ? goal.goal_pt_off : nullptr;
+    pr.cnt = goal.cnt;
+    pr.err = goal.err;
     // the depth pass and the scan are rrt_routes.h's, as they are: they read vertex / parent / j / m and write cnt / err / raw_off
     RoutesView rv{};
     rv.parent = t.parent;
     rv.j = d.j;
     rv.vertex = pr.vertex;
     rv.m = m;
-    rv.cnt = cnt;
-    rv.raw_off = raw_off;
-    rv.err = pr.err;
+    rv.cnt = goal.cnt;
+    rv.raw_off = goal.raw_off;
+    rv.err = goal.err;
     const unsigned goals_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB);
     HIPCHK(ctx, hipMemsetAsync(pr.err, 0, sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ev[2], ctx->stream));
+    HIPCHK(ctx, time.mark(2, ctx->stream));
     hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(goals_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)cnt, raw_off, m);
-    HIPCHK(ctx, hipEventRecord(ev[3], ctx->stream));
+    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)goal.cnt, goal.raw_off, m);
+    HIPCHK(ctx, time.mark(3, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     // the first wait that the sizes force: the rows of all routes together decide how much memory the rows need
     int64_t rows = 0;
     int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&rows, raw_off + m, sizeof rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&rows, goal.raw_off + m, sizeof rows, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&err, pr.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     if (err)
@@ -781,25 +773,25 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         return fail(ctx, RRT_E_ARG, "%s: the routes of these %d poses have %lld rows together, at most %zu per call: pass fewer poses at a time", who, m,
                     (long long)rows, POSE_ROUTE_ROW_BUDGET);
     int64_t npoints = 0;
-    // [leg_len f64 | pt_off i64 + 1 | row_xy u32 | row_id i32 | npts i32 | row_h u8], each of rows (no row: pt_off alone, one zero)
-    HIPCHK(ctx, b->pose_route_row.reserve(std::max<int64_t>(rows, 1), (size_t)std::max<int64_t>(rows, 1) * 29 + sizeof(int64_t)));
+    HIPCHK(ctx, b->pose_route_row.reserve<PoseRouteRowScratch>(std::max<int64_t>(rows, 1)));  // (no row: pt_off alone, one zero)
     if (pts && rows > 0) HIPCHK(ctx, b->pose_route_sweep.reserve(rows, (size_t)rows * POSE_ROUTE_SWEEP_BYTES));
-    const size_t rcap = (size_t)b->pose_route_row.cap;
+    const PoseRouteRowScratch row = b->pose_route_row.carve<PoseRouteRowScratch>();
     pr.rows = rows;
-    pr.leg_len = b->pose_route_row.as<double>();
-    pr.pt_off = reinterpret_cast<int64_t *>(pr.leg_len + rcap);
-    pr.row_xy = reinterpret_cast<uint32_t *>(pr.pt_off + rcap + 1);
-    pr.row_id = reinterpret_cast<int32_t *>(pr.row_xy + rcap);
-    pr.npts = pts ? pr.row_id + rcap : nullptr;
-    pr.row_h = reinterpret_cast<uint8_t *>(pr.row_id + 2 * rcap);
+    pr.leg_len = row.leg_len;
+    pr.pt_off = row.pt_off;
+    pr.row_xy = row.row_xy;
+    pr.row_id = row.row_id;
+    pr.npts = pts ? row.npts : nullptr;
+    pr.row_h = row.row_h;
     pr.sweep_bytes = pts ? b->pose_route_sweep.p : nullptr;
-    HIPCHK(ctx, hipEventRecord(ev[4], ctx->stream));
+    HIPCHK(ctx, time.mark(4, ctx->stream));
     if (cut && rows > 0) {
-        // the raw rows [row_xy u32 | row_id i32 | row_h u8] of rows, and per goal [fin_off i64 + 1 | kept i32]: the walks fill the raw
-        // rows, the shortcut kernel compacts each goal's kept rows to the front of its own, the pack makes them the dense rows above
-        HIPCHK(ctx, b->pose_cut_row.reserve(rows, (size_t)rows * 9));
-        HIPCHK(ctx, b->pose_cut_goal.reserve(m, (size_t)m * 12 + sizeof(int64_t)));
-        const size_t ccap = (size_t)b->pose_cut_row.cap, gcap = (size_t)b->pose_cut_goal.cap;
+        // the raw rows and what is kept of them per goal: the walks fill the raw rows, the shortcut kernel compacts each goal's kept
+        // rows to the front of its own, the pack makes them the dense rows above
+        HIPCHK(ctx, b->pose_cut_row.reserve<PoseCutRowScratch>(rows));
+        HIPCHK(ctx, b->pose_cut_goal.reserve<PoseCutGoalScratch>(m));
+        const PoseCutRowScratch cut_row = b->pose_cut_row.carve<PoseCutRowScratch>();
+        const PoseCutGoalScratch cut_goal = b->pose_cut_goal.carve<PoseCutGoalScratch>();
         PoseCutView pc{};
         pc.og = ctx->og;
         pc.W = ctx->W;
@@ -807,14 +799,13 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         pc.nh = d.nh;
         pc.rho = d.rho;
         pc.m = m;
-        pc.cnt = cnt;
-        pc.raw_off = raw_off;
-        int64_t *fin_off = b->pose_cut_goal.as<int64_t>();
-        pc.fin_off = fin_off;
-        pc.kept = reinterpret_cast<int32_t *>(fin_off + gcap + 1);
-        pc.row_xy = b->pose_cut_row.as<uint32_t>();
-        pc.row_id = reinterpret_cast<int32_t *>(pc.row_xy + ccap);
-        pc.row_h = reinterpret_cast<uint8_t *>(pc.row_id + ccap);
+        pc.cnt = goal.cnt;
+        pc.raw_off = goal.raw_off;
+        pc.fin_off = cut_goal.fin_off;
+        pc.kept = cut_goal.kept;
+        pc.row_xy = cut_row.row_xy;
+        pc.row_id = cut_row.row_id;
+        pc.row_h = cut_row.row_h;
         pc.out_xy = pr.row_xy;
         pc.out_h = pr.row_h;
         pc.out_id = pr.row_id;
@@ -825,22 +816,22 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         const unsigned waves_grid = (unsigned)((m + POSE_CUT_TPB / 64 - 1) / (POSE_CUT_TPB / 64));
         hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, raw);
         hipLaunchKernelGGL(rrt_pose_route_cut_kernel, dim3(std::min<unsigned>(waves_grid, POSE_CUT_MAX_WG)), dim3(POSE_CUT_TPB), 0, ctx->stream, pc);
-        hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)pc.kept, fin_off, m);
+        hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)pc.kept, cut_goal.fin_off, m);
         hipLaunchKernelGGL(rrt_pose_route_pack_kernel, dim3(waves_grid), dim3(POSE_CUT_TPB), 0, ctx->stream, pc);
-        HIPCHK(ctx, hipEventRecord(ev[5], ctx->stream));
+        HIPCHK(ctx, time.mark(5, ctx->stream));
         HIPCHK(ctx, hipGetLastError());
         // a wait of the shortcut call alone: the leg and the points kernel take the number of dense rows by value
         int64_t kept_rows = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&kept_rows, fin_off + m, sizeof kept_rows, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&kept_rows, cut_goal.fin_off + m, sizeof kept_rows, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, wait_stream_spin(ctx->stream));
         if (kept_rows < 1 || kept_rows > rows) return fail(ctx, RRT_E_HIP, "%s: %lld rows kept of %lld", who, (long long)kept_rows, (long long)rows);
         pr.cnt = pc.kept;
-        pr.raw_off = fin_off;
+        pr.raw_off = cut_goal.fin_off;
         pr.rows = rows = kept_rows;
-        HIPCHK(ctx, hipEventRecord(ev[6], ctx->stream));
+        HIPCHK(ctx, time.mark(6, ctx->stream));
     } else if (cut) {
-        HIPCHK(ctx, hipEventRecord(ev[5], ctx->stream));  // (nothing connects: no row to cut; cnt and raw_off, all zero, are the kept ones)
-        HIPCHK(ctx, hipEventRecord(ev[6], ctx->stream));
+        HIPCHK(ctx, time.mark(5, ctx->stream));  // (nothing connects: no row to cut; cnt and raw_off, all zero, are the kept ones)
+        HIPCHK(ctx, time.mark(6, ctx->stream));
     }
     if (rows > 0) {
         const unsigned rows_grid = (unsigned)std::min<int64_t>((rows + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
@@ -853,7 +844,7 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         HIPCHK(ctx, hipMemsetAsync(pr.pt_off, 0, sizeof(int64_t), ctx->stream));  // (nothing connects: no point)
     }
     hipLaunchKernelGGL(rrt_pose_route_length_kernel, dim3((unsigned)((m + 1 + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
-    HIPCHK(ctx, hipEventRecord(ev[leg_ev + 1], ctx->stream));
+    HIPCHK(ctx, time.mark(leg_ev + 1, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(length, pr.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(offsets, pr.raw_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -875,9 +866,9 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
             pr.npoints = npoints;
             pr.points = b->pose_route_pts.as<double2>();
             const unsigned pts_grid = (unsigned)std::min<int64_t>((npoints + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
-            HIPCHK(ctx, hipEventRecord(ev[leg_ev + 2], ctx->stream));
+            HIPCHK(ctx, time.mark(leg_ev + 2, ctx->stream));
             hipLaunchKernelGGL(rrt_pose_route_points_kernel, dim3(pts_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
-            HIPCHK(ctx, hipEventRecord(ev[leg_ev + 3], ctx->stream));
+            HIPCHK(ctx, time.mark(leg_ev + 3, ctx->stream));
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, wait_stream_spin(ctx->stream));  // (so that a fault of the kernel is this call's, and the stage times are there)
         }
@@ -885,7 +876,7 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     b->pose_last_m = m;
     b->pose_route_rows = rows;
     b->pose_route_points = pts ? npoints : -1;
-    (cut ? b->pose_cut_timed : b->pose_route_timed) = (pts && npoints > 0 ? 4 : 3) + (cut ? 1 : 0);
+    time.ran = (pts && npoints > 0 ? 4 : 3) + (cut ? 1 : 0);
     return RRT_OK;
 }
 
@@ -898,15 +889,12 @@ static int batch_pose_routes_rows(const char *who, rrt_batch *b, int32_t *xyh, i
     if (rows == 0) return RRT_OK;
     if (!xyh || !id) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t rcap = (size_t)b->pose_route_row.cap;
-    const uint32_t *row_xy = reinterpret_cast<const uint32_t *>(reinterpret_cast<const int64_t *>(b->pose_route_row.as<double>() + rcap) + rcap + 1);
-    const int32_t *row_id = reinterpret_cast<const int32_t *>(row_xy + rcap);
-    const uint8_t *row_h = reinterpret_cast<const uint8_t *>(row_id + 2 * rcap);
+    const PoseRouteRowScratch row = b->pose_route_row.carve<PoseRouteRowScratch>();
     b->stage.resize((size_t)rows);
     b->stage8.resize((size_t)rows);
-    HIPCHK(ctx, hipMemcpyAsync(b->stage.data(), row_xy, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->stage8.data(), row_h, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(id, row_id, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b->stage.data(), row.row_xy, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b->stage8.data(), row.row_h, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(id, row.row_id, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     for (int64_t r = 0; r < rows; ++r) {
         const uint32_t p = b->stage[(size_t)r];
@@ -979,9 +967,8 @@ extern "C" int rrt_plan_pose_routes_points(rrt_ctx *ctx, double *xy, int64_t poi
 // rows + legs + lengths (+ the scan of the point counts), the points (0 for a call without points, or without a point)
 extern "C" int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]) {
     if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes_ms: NULL");
-    if (!b->pose_route_timed) return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_routes_ms: no rrt_batch_pose_routes with a pose on this batch yet, or its last one failed");
-    ms[3] = 0.f;
-    for (int k = 0; k < b->pose_route_timed; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_pose_route[2 * k], b->ev_pose_route[2 * k + 1]));
+    if (!b->pose_route_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_routes_ms: no rrt_batch_pose_routes with a pose on this batch yet, or its last one failed");
+    HIPCHK(b->ctx, b->pose_route_time.read(ms, 4));
     return RRT_OK;
 }
 
@@ -994,10 +981,9 @@ extern "C" int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]) {
 // + pack, legs + lengths (+ the scan of the point counts), the points (0 for a call without points, or without a point)
 extern "C" int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]) {
     if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_pose_shortcuts_ms: NULL");
-    if (!b->pose_cut_timed)
+    if (!b->pose_cut_time.ran)
         return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_shortcuts_ms: no rrt_batch_pose_shortcuts with a pose on this batch yet, or its last one failed");
-    ms[4] = 0.f;
-    for (int k = 0; k < b->pose_cut_timed; ++k) HIPCHK(b->ctx, hipEventElapsedTime(&ms[k], b->ev_pose_cut[2 * k], b->ev_pose_cut[2 * k + 1]));
+    HIPCHK(b->ctx, b->pose_cut_time.read(ms, 5));
     return RRT_OK;
 }
 

@@ -191,6 +191,48 @@ def long_chain():
     return chain(tuple(range(2, 1101)) + (1108,))
 
 
+def pick(r, sel):
+    """the Routes of the goals `sel` of r's alone, in that order: what a goal gets does not depend on the goals beside it"""
+    s = Routes()
+    s.vertex, s.cost, s.length = r.vertex[sel], r.cost[sel], r.length[sel]
+    s.offsets = np.concatenate([[0], np.cumsum(np.diff(r.offsets)[sel])]).astype(np.int64)
+    s.point_offsets = np.concatenate([[0], np.cumsum(np.diff(r.point_offsets)[sel])]).astype(np.int64)
+    s.rows = np.concatenate([r.route(g) for g in sel])
+    s.ids = np.concatenate([r.ids[r.offsets[g]:r.offsets[g + 1]] for g in sel])
+    s.points = np.concatenate([r.path(g) for g in sel])
+    return s
+
+
+def small_calls_after_a_large_one(run, c, want, shortcut):
+    """Scratch that was allocated for a large call serves a small one: on one batch (run() makes it) a call with 257 poses, the pose
+    with the longest route of `want` (the reference of case c) tiled, then a call with that pose alone and one with three different
+    poses.  Rows and points of each small call are read back through the stand-alone calls; every array equals, bit for bit, what
+    the same call gives on a batch that made no call before it, and the reference."""
+    by_rows = np.argsort(-np.diff(want.offsets), kind="stable")
+    g = int(by_rows[0])
+    three = [int(by_rows[1]), g, int(by_rows[2])]
+    k = int(want.offsets[g + 1] - want.offsets[g])
+    assert k >= 3 and len({tuple(c.goals[i]) for i in three}) == 3 and np.diff(want.offsets)[three].sum() < 257 * k
+    fresh = []
+    for sel in ([g], three):
+        f = run()
+        fresh.append(f.pose_routes(0, c.goals[sel], points=True, shortcut=shortcut))
+        f.close()
+    b = run()
+    large = b.pose_routes(0, np.tile(c.goals[g], (257, 1)), points=True, shortcut=shortcut)
+    assert np.array_equal(large[3], k * np.arange(258))
+    for sel, alone in zip(([g], three), fresh):
+        got = b.pose_routes(0, c.goals[sel], points=True, shortcut=shortcut)
+        rows, ids = b.pose_routes_rows(int(got[3][-1]))
+        points = b.pose_routes_points(int(got[6][-1]))
+        assert np.array_equal(rows, got[4]) and np.array_equal(ids, got[5]) and np.array_equal(points.view(np.int64), got[7].view(np.int64))
+        got = got[:4] + (rows, ids, got[6], points)
+        same(got, pick(want, sel))
+        for x, y in zip(got, alone):
+            assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.int64) if x.dtype == np.float64 else x, y.view(np.int64) if y.dtype == np.float64 else y)
+    b.close()
+
+
 def same(got, want, points=True):
     """every array of Batch.pose_routes against a Routes, exactly; the floats as raw bits"""
     names = ("vertex", "cost", "length", "offsets", "rows", "ids") + (("point_offsets", "points") if points else ())

@@ -161,6 +161,11 @@ def test_no_pose_one_pose_and_a_workgroup_of_them(gpu_ctx):
     b.close()
 
 
+def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx):
+    c = prr.case("E")
+    prr.small_calls_after_a_large_one(lambda: _run(gpu_ctx, c.w), c, c.routes, shortcut=False)
+
+
 # ------------------------------------------------------------------------------------------------ 5. after a keep
 def test_after_keep_pose_tree_and_back(gpu_ctx):
     c0, c1 = prr.case("A"), prr.kept_case("A")

@@ -132,6 +132,11 @@ def test_after_grow_poses_in_the_new_numbering(gpu_ctx):
     b.close()
 
 
+def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx):
+    c = prr.case("E")
+    prr.small_calls_after_a_large_one(lambda: _run(gpu_ctx, c.w), c, psr.of_case(c), shortcut=True)
+
+
 # ------------------------------------------------------------------------------------------------ 4. three queries, and the other ways in
 def test_a_batch_of_three_queries_asked_at_the_second_and_the_third(gpu_ctx):
     c0, c1 = prr.case("E"), prr.kept_case("E")

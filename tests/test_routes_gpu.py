@@ -292,6 +292,39 @@ def test_connect_goals_is_what_it_was_and_rows_go_with_their_call(gpu_ctx):
     b.close()
 
 
+@pytest.mark.parametrize("cut", [False, True])
+def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx, cut):
+    """scratch that was allocated for a large call serves a small one: 257 goals, the goal with the longest route tiled, then that
+    goal alone and three different goals, their rows read back through routes_rows"""
+    og = _wall_map()
+    og8 = oracle.og_u8(og)
+    gpu_ctx.set_grid(og8)
+
+    def run():
+        return _grow(gpu_ctx, 1, 1000, (5, 5), (190, 150), _samples(og, 1000, 15), r2=hostprep.radius_threshold(25))
+
+    b, res = run()
+    goals = _free_goals(og, 60, 16)
+    want = routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals, cut=cut)
+    by_rows = np.argsort(-np.diff(want[3]), kind="stable")
+    g = int(by_rows[0])
+    three = [int(by_rows[1]), g, int(by_rows[2])]
+    k = int(want[3][g + 1] - want[3][g])
+    assert k >= 3 and len({tuple(goals[i]) for i in three}) == 3 and np.diff(want[3])[three].sum() < 257 * k
+    large = b.routes(0, np.tile(goals[g], (257, 1)), shortcut=cut)
+    assert np.array_equal(large[3], k * np.arange(258))
+    for sel in ([g], three):
+        got = b.routes(0, goals[sel], shortcut=cut)
+        xy, ids = b.routes_rows(int(got[3][-1]))
+        assert np.array_equal(xy, got[4]) and np.array_equal(ids, got[5])
+        got = got[:4] + (xy, ids)
+        _same(got, routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals[sel], cut=cut))
+        f, _ = run()  # a batch that made no call before this one
+        _same(got, f.routes(0, goals[sel], shortcut=cut))
+        f.close()
+    b.close()
+
+
 def test_refusals():
     ctx = _ffi.Context(0)
     og = _wall_map()
