@@ -375,6 +375,33 @@ int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count);
  * [0, nh); RRT_E_UNSUPPORTED for a batch created without RRT_FLAG_DUBINS (rrt_batch_grow is its call).  rrt_batch_grow keeps
  * refusing a Dubins batch. */
 int rrt_batch_grow_poses(rrt_batch *b, int32_t q, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
+/* Re-root the finished tree of query q at its vertex `root`, then rrt_batch_grow from the re-rooted tree (rrt_reroot.h): for a start
+ * that moved along a route, whose rows carry vertex numbers.  RRTStandard and RRTStar, the default cost, the reference's rewire.
+ *   input    the whole tree [0, j), or with a view (rrt_batch_keep_tree) its alive vertices; `root` is a number of the tree as
+ *            rrt_batch_get_result gave it, and with a view it must be alive.
+ *   parents  with p_0 = root, p_1 = parent[root], ..., p_d = 0: new_parent[p_{i+1}] = p_i, new_parent[root] = -1, every other vertex
+ *            keeps its parent.
+ *   edges    the line walk is not symmetric and a valid edge is walked from the parent to the child, so each of the d reversed edges
+ *            is walked again on the context's CURRENT grid from its new parent to its new child.  The other edges stand tested on
+ *            this grid.  A vertex is alive iff every edge on its new way to `root` holds: a blocked reversed edge cuts everything
+ *            that hangs behind it, *j0 reports what is left, and the m samples can repair the gap.
+ *   numbers  the alive vertices ordered by (depth below `root`, previous number): `root` is vertex 0 and every parent is below its
+ *            child, also for root == 0.  old_id (host, *j0 int32, may be NULL; give it room for the query's n) = the number each
+ *            had before the call.
+ *   costs    cost[0] = 0, cost[k] = cost[parent[k]] + sqrt((double)d2) accumulated from the root down: the bits of the loop's own
+ *            sum along the new path, not old cost - cost[root].
+ *   then     rrt_batch_grow's seed from these arrays (`sampled` = the cells of vertices 1 .. *j0-1), its arming with the m samples,
+ *            and everything rrt_batch_grow says about the launch, the logs, *log0 and the query afterwards.  The query's start
+ *            becomes the cell of `root`: an rrt_batch_rearm + rrt_batch_launch plans from it.  m == 0: the plain re-root, then go2goal.
+ * j + m <= n is required with the vertices the call starts from (the view's, else the tree's), before any is cut.  Refusals: all of
+ * rrt_batch_grow's in its order (a batch created with RRT_FLAG_DUBINS: a Dubins word is not reversible), then RRT_E_ARG for `root`
+ * outside [0, j) and for a `root` that is not alive in the view.  A refusal changes nothing; a call that fails later leaves the
+ * query without a tree. */
+int rrt_batch_reroot(rrt_batch *b, int32_t q, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
+/* kernel time in ms of the stages of the last successful rrt_batch_reroot on this batch: ms[0] the path, ms[1] the reversed edges'
+ * test, ms[2] alive and depth (pointer jumping), ms[3] the order, ms[4] the costs, then ms[5 .. 7] the seed's stages as
+ * rrt_batch_grow_ms reports them; the first `count` (1 .. 8) are written.  RRT_E_ARG when there is none, or after a later rrt_batch_grow. */
+int rrt_batch_reroot_ms(rrt_batch *b, float *ms, int32_t count);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -448,6 +475,10 @@ int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count);
 /* rrt_batch_grow_poses on the Dubins tree of the context's last rrt_plan, launch, sync and result included (out->head too);
  * rrt_plan_grow_ms gives its stage times. */
 int rrt_plan_grow_poses(rrt_ctx *ctx, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
+/* rrt_batch_reroot on the tree of the context's last rrt_plan / rrt_plan_resume, launch, sync and result included: returns like
+ * rrt_plan_grow.  rrt_plan_reroot_ms: rrt_batch_reroot_ms of that batch. */
+int rrt_plan_reroot(rrt_ctx *ctx, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
+int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

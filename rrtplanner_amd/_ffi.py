@@ -76,6 +76,7 @@ SYMBOLS = (
     "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
     "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
     "rrt_batch_grow_poses", "rrt_plan_grow_poses",
+    "rrt_batch_reroot", "rrt_batch_reroot_ms", "rrt_plan_reroot", "rrt_plan_reroot_ms",
     "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
     "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
     "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
@@ -192,6 +193,10 @@ def lib():
             "rrt_plan_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
             "rrt_batch_grow_poses": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
             "rrt_plan_grow_poses": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
+            "rrt_batch_reroot": ([vp, i32, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
+            "rrt_batch_reroot_ms": ([vp, C.POINTER(C.c_float * 8), i32], C.c_int),
+            "rrt_plan_reroot": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
+            "rrt_plan_reroot_ms": ([vp, C.POINTER(C.c_float * 8), i32], C.c_int),
             "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
             "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
             "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
@@ -562,13 +567,16 @@ class Context:
         n of that plan (the result arrays are sized by it).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
         return self._grow(samples, n, logs, False)
 
-    def _grow(self, samples, n, logs, poses):
+    def _grow(self, samples, n, logs, poses, root=None):
         s = _grow_samples(samples, poses)
         res = ResultArrays(int(n), logs, headings=poses)
         j0 = C.c_int32(-1)
         old_id = np.full(int(n) + 1, -1, dtype=np.int32)
-        call = lib().rrt_plan_grow_poses if poses else lib().rrt_plan_grow
-        rc = call(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+        if root is not None:
+            rc = lib().rrt_plan_reroot(self._h, int(root), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+        else:
+            call = lib().rrt_plan_grow_poses if poses else lib().rrt_plan_grow
+            rc = call(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
         try:
             _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
         except RRTError as e:
@@ -584,6 +592,16 @@ class Context:
     def grow_ms(self):
         """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
         return _stage_ms(self._h, lambda *a: lib().rrt_plan_grow_ms(self._h, *a), 3, 3)
+
+    def reroot(self, root, samples, n, logs=False):
+        """rrt_plan_reroot: Batch.reroot on the tree of this context's last plan() / plan_resume(), launch and result included.
+        root: a vertex number of that tree; n: the n of that plan.  Returns (rc, ResultArrays, j0, old_id int32[j0]) as grow()."""
+        return self._grow(samples, n, logs, False, root=root)
+
+    def reroot_ms(self):
+        """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
+        seed's three as grow_ms() gives them"""
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_reroot_ms(self._h, *a), 8, 8)
 
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
@@ -871,6 +889,22 @@ class Batch:
     def grow_ms(self):
         """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
         return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_grow_ms(self._h, *a), 3, 3)
+
+    def reroot(self, q, root, samples=()):
+        """rrt_batch_reroot: re-root the finished tree of query q at its vertex `root` (a number of the tree as get_result gave it;
+        alive, if the query has a keep_tree view), then seed and arm it like grow() for len(samples) more iterations.  The reversed
+        edges are tested on the context's current grid; what hangs behind a blocked one is cut.  Returns (j0, old_id int32[j0],
+        log0): the vertices of the re-rooted tree, the number each had before, the log row of the first new iteration."""
+        s = _grow_samples(np.zeros((0, 2), dtype=np.int32) if len(samples) == 0 else samples)
+        j0, log0 = C.c_int32(-1), C.c_int32(-1)
+        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_reroot(self._h, int(q), int(root), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
+        return j0.value, old_id[:j0.value].copy(), log0.value
+
+    def reroot_ms(self):
+        """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
+        seed's three as grow_ms() gives them"""
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_reroot_ms(self._h, *a), 8, 8)
 
     def pose_routes_rows(self, rows):
         """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, with shortcuts or without, which left `rows` rows"""

@@ -3,6 +3,10 @@
 // another, so the objects link without relocatable device code.
 #include <hip/hip_runtime.h>
 
+#ifndef RRT_TU
+#error "kernels_tu.hip is compiled once per unit: pass -DRRT_TU=k (the Makefile's TUS)"
+#endif
+
 #if RRT_TU == 1  // one CU per query, no barrier in the loop (RRTStandard / RRTStar)
 #include "rrt_pipe.h"
 
@@ -44,6 +48,10 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #include "rrt_pose_goals.h"
 #include "rrt_pose_keep.h"
 #include "rrt_pose_routes.h"
+
+#elif RRT_TU == 0  // re-root a finished tree at one of its vertices: the reversed path tested, the alive vertices ordered by depth and
+                    // repriced (rrt_reroot_*_kernel), in front of the seed of unit 8: not team kernels
+#include "rrt_reroot.h"
 
 #else  // teams of compute units: the variants that rrt_block_variants.def (included by rrt_block.h) deals to this unit
 #include "rrt_block.h"

@@ -315,6 +315,41 @@ struct SeedRecords {
     int32_t *err;
 };
 
+// ---- rrt_reroot.h ----
+constexpr int REROOT_TPB = 256;                              // one vertex per lane; edge test: 4 reversed edges a workgroup (one per wave)
+constexpr int REROOT_MAX_WG = 2048;                          // workgroups of the edge test, grid-stride beyond
+constexpr int REROOT_WG = 64;                                // workgroups of the placement
+constexpr int REROOT_WAVES = REROOT_WG * (REROOT_TPB / 64);  // wavefronts that share the keys of the order: 256 (a key belongs to wavefront key % 256)
+constexpr int REROOT_SEGS = 64;                              // most segments of the index range a level is spread over (divides REROOT_WAVES)
+constexpr int REROOT_OWN = 1024;                             // keys a wavefront owns, their cursors in its LDS: trees of up to 262 144 vertices
+static_assert((REROOT_WAVES & (REROOT_WAVES - 1)) == 0 && REROOT_WAVES % REROOT_SEGS == 0 && (REROOT_SEGS & (REROOT_SEGS - 1)) == 0,
+              "the owner of a key is taken with a mask, and all keys of an owner lie in one segment");
+
+struct RerootView {
+    const uint8_t *og;       // (W,H) x-major occupancy of the context's grid, != 0 is obstacle
+    int32_t H;
+    const uint32_t *nodes;   // [j] the input tree, dense: the query's tree arrays, or its kept view
+    const int32_t *parent;   // [j] ... its parents in the same numbering; vertex 0 is its root, whatever parent[0] holds
+    const int32_t *id;       // [j] the number each input vertex has for the caller (the view's live_id); null: its own
+    int32_t j, root;         // input vertices [0, j); the new root, one of them
+    int32_t *path;           // [j] p_0 = root, p_1 = parent[root], ..., p_d = 0
+    int32_t *new_parent;     // [j] the parents after the reversal, input numbering; -1 for the new root
+    uint8_t *ok;             // [j] first buffer of the pointer jumping: the edge to new_parent holds (1 for every edge that was not reversed)
+    int32_t *anc, *dep;      // [j] ... the ancestor reached and the edges walked to it
+    int32_t *level_cnt;      // [j + 1] alive vertices per key (depth, segment); at most j keys (zeroed by the host)
+    int32_t *level_start;    // [j + 1] exclusive scan of level_cnt over the keys: level d is [level_start[d * segments], level_start[(d + 1) * segments])
+    int32_t *key;            // [j] depth * segments + segment of an alive vertex, -1 for one that is not
+    int32_t *rank;           // [j] the new number of an input vertex (filled with -1 by the host: a vertex that is not alive has none)
+    int32_t *src;            // [j] the input vertex behind a new number
+    uint32_t *out_nodes;     // [j] the re-rooted tree in its new numbering: what rrt_seed_install_kernel takes for a view
+    double *out_vcost;
+    int32_t *out_parent;
+    int32_t *out_id;
+    int32_t *head;           // [8] out: d, the alive count, err (!= 0: not a tree, or a vertex that cannot be placed), the new root's packed cell,
+                             //          the deepest level (-1 from the host)
+};
+enum : int { REROOT_D = 0, REROOT_COUNT = 1, REROOT_ERR = 2, REROOT_XY = 3, REROOT_MAXD = 4, REROOT_HEAD = 8 };
+
 // ---- the kernels a host unit launches, by the file that defines them ----
 // rrt_serial.h (units 2 and 3 instantiate it)
 template <bool RW, bool DUB = false>
@@ -366,5 +401,18 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_bitmap_kernel(SeedView sv);
 __global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords sr);
 // rrt_pose_seed.h (unit 8, beside the seed kernels)
 __global__ __launch_bounds__(SEED_TPB) void rrt_pose_seed_heading_kernel(uint8_t *heading, const uint8_t *live_heading, int32_t j0, int32_t node_stride);
+
+// rrt_reroot.h (unit 0; the numbers from 10 on belong to the team kernels)
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_path_kernel(RerootView rv);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_edge_kernel(RerootView rv);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_link_kernel(RerootView rv);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_jump_kernel(const uint8_t *ok, const int32_t *anc, const int32_t *dep, uint8_t *ok2, int32_t *anc2,
+                                                                     int32_t *dep2, int32_t j);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_count_kernel(RerootView rv, const uint8_t *ok, const int32_t *anc, const int32_t *dep);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_level_kernel(RerootView rv);
+__global__ __launch_bounds__(TPB) void rrt_reroot_scan_kernel(RerootView rv);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_place_kernel(RerootView rv);
+__global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_parent_kernel(RerootView rv);
+__global__ __launch_bounds__(TPB) void rrt_reroot_cost_kernel(RerootView rv);
 
 }  // namespace rrtdev

@@ -106,3 +106,25 @@ struct SeedTmpScratch : Carver {
     int32_t *new_parent = take<int32_t>(cap);
     int32_t *err = take<int32_t>(2);
 };
+
+// What a reroot call works in (rrt_reroot.h); cap = n_cap.  The pointer jumping goes between two sets of (anc, dep, ok) and back; the
+// flag arrays have cap rounded up to 8 elements and come last.  key takes the set of the jumping that the last round did not write.
+// head: d, the alive count, err, the new root's cell, the deepest level; eight words are reserved.
+struct RerootScratch : Carver {
+    using Carver::Carver;
+    size_t cap8 = (cap + 7) & ~(size_t)7;
+    double *out_vcost = take<double>(cap);
+    uint32_t *out_nodes = take<uint32_t>(cap);
+    int32_t *out_parent = take<int32_t>(cap);
+    int32_t *out_id = take<int32_t>(cap);
+    int32_t *path = take<int32_t>(cap);
+    int32_t *new_parent = take<int32_t>(cap);
+    int32_t *anc[2] = {take<int32_t>(cap), take<int32_t>(cap)};
+    int32_t *dep[2] = {take<int32_t>(cap), take<int32_t>(cap)};
+    int32_t *level_cnt = take<int32_t>(cap + 1);
+    int32_t *level_start = take<int32_t>(cap + 1);
+    int32_t *rank = take<int32_t>(cap);
+    int32_t *src = take<int32_t>(cap);
+    int32_t *head = take<int32_t>(8);
+    uint8_t *ok[2] = {take<uint8_t>(cap8), take<uint8_t>(cap8)};
+};

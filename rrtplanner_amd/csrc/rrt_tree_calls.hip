@@ -1,6 +1,6 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h and rrt_pose_seed.h.  What the calls share comes first and is written once:
+// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h and rrt_reroot.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
@@ -434,12 +434,15 @@ extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
 // rrt_batch_grow (poses == false: straight-line batches, rows (x, y)) and rrt_batch_grow_poses (poses == true: Dubins batches, rows
 // (x, y, h)) are one call: the Dubins seed carries one more array, the heading bytes (rrt_pose_seed.h), and the m sample headings go
 // to rows [j0, j0 + m) of the sample heading buffer, which both Dubins kernels read by absolute row like the samples.
-static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
-                      bool poses) {
+// What rrt_batch_grow and rrt_batch_reroot share comes in three parts: the refusals (refuse_grow), the seed stages and the arming
+// (seed_and_arm), and what the seed is made from (SeedFrom).
+
+// Every refusal of a grow call up to the room, in its order; `dubins`: why this call takes no Dubins batch.  0: not refused, and
+// j_in is what the call starts from: the vertices of the view, else of the tree.
+static int refuse_grow(const char *who, rrt_batch *b, int32_t q, bool null_arg, int32_t m, bool poses, const char *dubins, int &j_in) {
     rrt_ctx *ctx = b->ctx;
-    if (!j0_out || !log0 || (m > 0 && !samples)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    if (!poses && (b->flags & RRT_FLAG_DUBINS))
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (the seed kernels carry no headings)", who);
+    if (null_arg) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (!poses && (b->flags & RRT_FLAG_DUBINS)) return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (%s)", who, dubins);
     if (poses && !(b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its samples are cells and its edges straight lines: use rrt_batch_grow)", who);
     if (b->flags & RRT_FLAG_REWIRE)
@@ -448,7 +451,7 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_LARGE_GRID", who);
     if (const int rc = refuse_q(who, b, q)) return rc;
     if (const int rc = refuse_unfinished(who, b, q)) return rc;
-    QDesc &d = b->h_desc[(size_t)q];
+    const QDesc &d = b->h_desc[(size_t)q];
     if (d.alg == RRT_ALG_INFORMED)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d is an Informed RRT* query (its ellipse state is not rebuilt); RRTStandard and RRTStar only", who, q);
     if (const int rc = refuse_grid(who, b, q, "changed shape since the batch was created",
@@ -459,19 +462,49 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     const int j_old = d.j, own_n = d.n;
     if (j_old < 1 || j_old > b->n_cap || own_n < 1 || own_n > b->n_cap)
         return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices of %d, capacity %d", who, q, j_old, own_n, b->n_cap);
+    const int32_t kept = std::min(b->keep_alive[(size_t)q], j_old);
+    if (kept == 0) return fail(ctx, RRT_E_ARG, "%s: no vertex of query %d is alive on this grid (the root is blocked): there is nothing to grow from", who, q);
+    j_in = kept > 0 ? kept : j_old;
+    if ((long long)j_in + m > own_n)
+        return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j_in, m, own_n, own_n - j_in);
+    return RRT_OK;
+}
+
+// The j0 vertices a seed is made from, dense.  All null: the query's own tree arrays [0, j0), which stay where they are.  Otherwise
+// the arrays are copied in (rrt_seed_install_kernel); id: the number each had before; parent: its parent among the j0, or nullptr for
+// a kept view, whose parents are those of the tree renumbered through id (rrt_seed_rank_kernel, rrt_seed_parent_kernel).
+struct SeedFrom {
+    const uint32_t *nodes = nullptr;
+    const double *vcost = nullptr;
+    const int32_t *id = nullptr;
+    const int32_t *parent = nullptr;
+    const uint8_t *heading = nullptr;  // (a Dubins batch)
+    int32_t j0 = 0;
+};
+
+static SeedFrom seed_from_tree(const TreeRef &t, int32_t j_in) {
+    SeedFrom from;
+    if (t.kept > 0) {
+        from.nodes = t.live_nodes;
+        from.vcost = t.live_vcost;
+        from.id = t.live_id;
+        from.heading = t.live_heading;
+    }
+    from.j0 = j_in;
+    return from;
+}
+
+// The seed of query q from `from`, the m staged samples uploaded, and the descriptor armed at (j0, j0) of j0 + m.  The caller has
+// made every refusal, staged the samples (stage_cells) and reserved seed_tmp and the marks of seed_time.  From here on the query is
+// being replaced: a failure leaves it idle without a tree.
+static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom &from, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
+                        bool poses) {
+    rrt_ctx *ctx = b->ctx;
+    QDesc &d = b->h_desc[(size_t)q];
+    const int j_old = d.j, own_n = d.n, j0 = from.j0;
     const TreeRef t = tree_ref(b, q);
-    if (t.kept == 0) return fail(ctx, RRT_E_ARG, "%s: no vertex of query %d is alive on this grid (the root is blocked): there is nothing to grow from", who, q);
-    const int j0 = t.kept > 0 ? t.kept : j_old;
-    if ((long long)j0 + m > own_n)
-        return fail(ctx, RRT_E_ARG, "%s: %d vertices and m=%d samples exceed the query's n=%d: room for %d", who, j0, m, own_n, own_n - j0);
-    // (the last refusal: the staging buffers, written once every sample has passed, are the first thing of the batch this call touches)
-    if (const int rc = stage_cells(who, b, q, "sample", samples, m, poses ? d.nh : 0)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     const SeedTmpScratch tmp = b->seed_tmp.carve<SeedTmpScratch>();
     StageTimer &time = b->seed_time;
-    HIPCHK(ctx, time.create(4));
-    // ---- from here on the query is being replaced ----
     time.ran = 0;
     b->drop_routes();
     d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
@@ -483,26 +516,25 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     sv.j0 = j0;
     sv.node_stride = b->node_stride;
     sv.rank = tmp.rank;
-    sv.new_parent = tmp.new_parent;
+    sv.new_parent = from.parent ? const_cast<int32_t *>(from.parent) : tmp.new_parent;  // (only rrt_seed_parent_kernel writes it)
     sv.err = tmp.err;
     sv.bitmap = b->d_bitmap + (size_t)q * b->bitmap_words;
     sv.bitmap_words = b->bitmap_words;
     sv.H = ctx->H;
-    sv.live_vcost = t.kept > 0 ? t.live_vcost : nullptr;
-    sv.live_nodes = t.kept > 0 ? t.live_nodes : nullptr;
-    sv.live_id = t.kept > 0 ? t.live_id : nullptr;
+    sv.live_vcost = from.vcost;
+    sv.live_nodes = from.nodes;
+    sv.live_id = from.id;
     auto blocks = [](int items) { return dim3((unsigned)((items + SEED_TPB - 1) / SEED_TPB)); };
     HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, time.mark(0, ctx->stream));
-    if (sv.live_id) {
+    if (sv.live_id && !from.parent) {
         HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)j_old * sizeof(int32_t), ctx->stream));
         hipLaunchKernelGGL(rrt_seed_rank_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
         hipLaunchKernelGGL(rrt_seed_parent_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
     }
     hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
     if (poses && sv.live_id)  // (without a view heading[0, j0) already stands; rrt_pose_seed.h says why the slots behind j0 are left)
-        hipLaunchKernelGGL(rrt_pose_seed_heading_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, t.heading, (const uint8_t *)t.live_heading, j0,
-                           b->node_stride);
+        hipLaunchKernelGGL(rrt_pose_seed_heading_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, t.heading, from.heading, j0, b->node_stride);
     HIPCHK(ctx, time.mark(1, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
     if (j0 > 1) hipLaunchKernelGGL(rrt_seed_bitmap_kernel, blocks(j0 - 1), dim3(SEED_TPB), 0, ctx->stream, sv);
@@ -558,6 +590,154 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     return RRT_OK;
 }
 
+static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
+                      bool poses) {
+    rrt_ctx *ctx = b->ctx;
+    int j_in = 0;
+    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, poses, "the seed kernels carry no headings", j_in)) return rc;
+    // (the last refusal: the staging buffers, written once every sample has passed, are the first thing of the batch this call touches)
+    if (const int rc = stage_cells(who, b, q, "sample", samples, m, poses ? b->h_desc[(size_t)q].nh : 0)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
+    HIPCHK(ctx, b->seed_time.create(4));
+    b->reroot_time.ran = 0;  // (the seed's times are this call's from here on: rrt_batch_reroot_ms has nothing to report)
+    return seed_and_arm(who, b, q, seed_from_tree(tree_ref(b, q), j_in), m, j0_out, old_id, log0, poses);
+}
+
+// ---- re-root a finished tree at one of its vertices (rrt_reroot.h), then the seed and the arming of grow ----
+// `root` is a vertex number of the tree as the caller holds it: with a kept view an original number, which must be alive.  The stages
+// of rrt_reroot.h leave the re-rooted tree, renumbered by depth and repriced, in scratch; the seed installs it.  The descriptor's xs
+// becomes the new root's cell.  A refusal changes nothing; past the refusals a failure leaves the query idle without a tree.
+static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id,
+                        int32_t *log0) {
+    rrt_ctx *ctx = b->ctx;
+    int j_in = 0;
+    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, false, "a Dubins word is not reversible", j_in)) return rc;
+    QDesc &d = b->h_desc[(size_t)q];
+    if (root < 0 || root >= d.j) return fail(ctx, RRT_E_ARG, "%s: root=%d, query %d has the vertices [0, %d)", who, root, q, d.j);
+    if (b->n_cap > REROOT_WAVES * REROOT_OWN)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
+                    REROOT_WAVES * REROOT_OWN);
+    if (const int rc = stage_cells(who, b, q, "sample", samples, m, 0)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
+    HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
+    HIPCHK(ctx, b->seed_time.create(4));
+    HIPCHK(ctx, b->reroot_time.create(6));
+    const TreeRef t = tree_ref(b, q);
+    const SeedTmpScratch stmp = b->seed_tmp.carve<SeedTmpScratch>();
+    const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
+    auto blocks = [](int items) { return dim3((unsigned)((items + REROOT_TPB - 1) / REROOT_TPB)); };
+    RerootView rv{};
+    rv.og = ctx->og;
+    rv.H = ctx->H;
+    rv.nodes = t.nodes;
+    rv.parent = t.parent;
+    rv.j = j_in;
+    rv.root = root;
+    if (t.kept > 0) {  // the input is the view: its parents renumbered into scratch, and the root's number in it (-1: not alive)
+        SeedView sv{};
+        sv.parent = t.parent;
+        sv.j_old = d.j;
+        sv.j0 = j_in;
+        sv.live_id = t.live_id;
+        sv.rank = stmp.rank;
+        sv.new_parent = stmp.new_parent;
+        sv.err = stmp.err;
+        HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)d.j * sizeof(int32_t), ctx->stream));
+        const dim3 seed_blocks((unsigned)((j_in + SEED_TPB - 1) / SEED_TPB));
+        hipLaunchKernelGGL(rrt_seed_rank_kernel, seed_blocks, dim3(SEED_TPB), 0, ctx->stream, sv);
+        hipLaunchKernelGGL(rrt_seed_parent_kernel, seed_blocks, dim3(SEED_TPB), 0, ctx->stream, sv);
+        HIPCHK(ctx, hipGetLastError());
+        int32_t err = 0, in_view = -1;
+        HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&in_view, sv.rank + root, sizeof in_view, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        if (err || in_view >= j_in)
+            return fail(ctx, RRT_E_HIP, "%s: the kept view of query %d on the device is not a tree (a parent that is not alive)", who, q);
+        if (in_view < 0)
+            return fail(ctx, RRT_E_ARG, "%s: root=%d is not alive in the kept view of query %d (%d of %d vertices alive)", who, root, q, j_in, d.j);
+        rv.nodes = t.live_nodes;
+        rv.parent = stmp.new_parent;
+        rv.id = t.live_id;
+        rv.root = in_view;
+    }
+    rv.path = tmp.path;
+    rv.new_parent = tmp.new_parent;
+    rv.ok = tmp.ok[0];
+    rv.anc = tmp.anc[0];
+    rv.dep = tmp.dep[0];
+    rv.level_cnt = tmp.level_cnt;
+    rv.level_start = tmp.level_start;
+    rv.rank = tmp.rank;
+    rv.src = tmp.src;
+    rv.out_nodes = tmp.out_nodes;
+    rv.out_vcost = tmp.out_vcost;
+    rv.out_parent = tmp.out_parent;
+    rv.out_id = tmp.out_id;
+    rv.head = tmp.head;
+    // ---- from here on the query is being replaced ----
+    StageTimer &time = b->reroot_time;
+    time.ran = 0;
+    b->seed_time.ran = 0;
+    b->drop_routes();
+    d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
+    const int j = j_in;
+    const int32_t head0[REROOT_HEAD] = {0, 0, 0, 0, -1, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(rv.head, head0, sizeof head0, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.level_cnt, 0, ((size_t)j + 1) * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.rank, 0xff, (size_t)j * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, time.mark(0, ctx->stream));
+    hipLaunchKernelGGL(rrt_reroot_path_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(1, ctx->stream));
+    const int per_wg = REROOT_TPB / 64;  // one reversed edge per wavefront; how many there are only the device knows: at most j - 1
+    hipLaunchKernelGGL(rrt_reroot_edge_kernel, dim3((unsigned)std::clamp((j + per_wg - 1) / per_wg, 1, REROOT_MAX_WG)), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_link_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(2, ctx->stream));
+    // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
+    int rounds = 1;
+    while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
+    int cur = 0;
+    for (int r = 0; r < rounds; ++r, cur ^= 1)
+        hipLaunchKernelGGL(rrt_reroot_jump_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
+                           (const int32_t *)tmp.dep[cur], tmp.ok[cur ^ 1], tmp.anc[cur ^ 1], tmp.dep[cur ^ 1], j);
+    HIPCHK(ctx, time.mark(3, ctx->stream));
+    rv.key = tmp.dep[cur ^ 1];  // (the set the last round read: free from here on)
+    hipLaunchKernelGGL(rrt_reroot_count_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
+                       (const int32_t *)tmp.dep[cur]);
+    hipLaunchKernelGGL(rrt_reroot_level_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_place_kernel, dim3(REROOT_WG), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_parent_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(4, ctx->stream));
+    hipLaunchKernelGGL(rrt_reroot_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(5, ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    // the one wait that the sizes force: how many vertices are alive decides the launches of the seed
+    int32_t head[REROOT_HEAD] = {0, 0, 1, 0, -1, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(head, rv.head, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (head[REROOT_ERR] || head[REROOT_COUNT] < 1 || head[REROOT_COUNT] > j) {
+        drop_keep_views(b, q);
+        HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        return fail(ctx, RRT_E_HIP, "%s: the parent array of query %d on the device is not a tree (a walk that did not reach vertex 0 within %d steps, or a "
+                    "vertex that cannot be placed): the query is left without a tree", who, q, j);
+    }
+    d.xs[0] = (int32_t)((uint32_t)head[REROOT_XY] & 0xffffu);
+    d.xs[1] = (int32_t)((uint32_t)head[REROOT_XY] >> 16);
+    SeedFrom from;
+    from.nodes = tmp.out_nodes;
+    from.vcost = tmp.out_vcost;
+    from.id = tmp.out_id;
+    from.parent = tmp.out_parent;
+    from.j0 = head[REROOT_COUNT];
+    if (const int rc = seed_and_arm(who, b, q, from, m, j0_out, old_id, log0, false)) return rc;
+    time.ran = 5;
+    return RRT_OK;
+}
+
 extern "C" int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
     return b ? batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0, false) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
 }
@@ -594,6 +774,36 @@ extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
 extern "C" int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_grow_ms", NO_PLAN);
     return s ? rrt_batch_grow_ms(s, ms, count) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_reroot(rrt_batch *b, int32_t q, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
+    return b ? batch_reroot("rrt_batch_reroot", b, q, root, samples_xy, m, j0, old_id, log0) : fail(nullptr, RRT_E_ARG, "rrt_batch_reroot: NULL");
+}
+
+extern "C" int rrt_plan_reroot(rrt_ctx *ctx, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    const char *who = "rrt_plan_reroot";
+    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
+    if (!s) return RRT_E_ARG;
+    int32_t log0 = 0;
+    const int rc = batch_reroot(who, s, 0, root, samples_xy, m, j0, old_id, &log0);
+    return rc != RRT_OK ? rc : run_single(ctx, out);
+}
+
+// ms[0, 5): path, edge test, alive and depth, order, costs; ms[5, 8): the seed's stages, as rrt_batch_grow_ms reports them
+extern "C" int rrt_batch_reroot_ms(rrt_batch *b, float *ms, int32_t count) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_reroot_ms: NULL");
+    if (count < 1 || count > 8) return fail(b->ctx, RRT_E_ARG, "rrt_batch_reroot_ms: count=%d, a re-root has 5 stages and its seed 3", count);
+    if (!b->reroot_time.ran || !b->seed_time.ran)
+        return fail(b->ctx, RRT_E_ARG, "rrt_batch_reroot_ms: no rrt_batch_reroot on this batch yet, its last one failed, or a grow came after it");
+    HIPCHK(b->ctx, b->reroot_time.read(ms, std::min(count, 5)));
+    if (count > 5) HIPCHK(b->ctx, b->seed_time.read(ms + 5, count - 5));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_ms", NO_PLAN);
+    return s ? rrt_batch_reroot_ms(s, ms, count) : RRT_E_ARG;
 }
 
 // ---- finished routes to many goals (rrt_routes.h) ----

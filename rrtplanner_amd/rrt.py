@@ -665,35 +665,69 @@ class RRT(object):
 
         RuntimeError / ValueError as connect_goals; ValueError when m does not fit (it names the room), for RRTStarInformed, the
         Dubins planners, rewire="correct", the large-grid route and a custom cost function."""
+        return self._grow_or_reroot("grow", m, None)
+
+    def reroot(self, vertex: int, m: int = 0) -> Tuple[nx.DiGraph, int]:
+        """The start moved: re-root the tree of the last plan() at one of its vertices instead of planning again (rrt_plan_reroot).
+        A vehicle that drives a route stands on a vertex whose number the route rows carry (routes_to, paths_to).  `vertex` is a
+        number of the T the caller holds; after a keep_tree those are still the original numbers, and the vertex must be alive.
+
+        The point of that vertex becomes the start and vertex 0 of a new tree: the parent pointers on its way to the old root are
+        reversed, every other vertex keeps its parent.  The line walk is not symmetric, so each reversed edge is walked again on
+        the current grid from its new parent to its new child; a vertex stays iff every edge on its new way to the root holds, so
+        a blocked reversed edge cuts what hangs behind it (m > 0 repairs the gap).  The vertices are renumbered by (depth,
+        previous number) and repriced from the new root down, cost[k] = cost[parent[k]] + |edge|, in the loop's own arithmetic.
+        Then m more samples are spent exactly as grow(m) spends them, and go2goal connects plan()'s xgoal.  The room is checked
+        with the vertices before the call: they + m <= self.n.
+
+        Returns (T, gv) with the row contract of plan() for self.n, as grow.  self.last_grow_ids[k] is the number vertex k had
+        before the call.  connect_goals, paths_to, routes_to, keep_tree, grow and a further reroot work on the re-rooted tree in its
+        new numbering; a later plan() takes its own xstart as ever.
+
+        Raises as grow; ValueError for a vertex outside the tree or one that is not alive."""
+        return self._grow_or_reroot("reroot", m, vertex)
+
+    def _grow_or_reroot(self, who: str, m: int, vertex):
+        """grow (vertex is None) and reroot: the refusals of the classes, the draws and the context's call"""
         if not self._GROWS:
-            raise ValueError("grow: RRTStandard and RRTStar only (an Informed tree carries ellipse state, a Dubins tree headings, which the seed does not rebuild)")
+            raise ValueError(f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, a Dubins tree headings, which the seed does not rebuild)"
+                             if vertex is None else
+                             f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, which is not rebuilt; a Dubins word is not reversible)")
         if self._custom_cost:
-            raise ValueError("grow: a custom cost function runs on the host route: its tree is not resident on the device")
+            raise ValueError(f"{who}: a custom cost function runs on the host route: its tree is not resident on the device")
         if _rewire_mode(getattr(self, "rewire", "reference")):
-            raise ValueError('grow: rewire="correct" keeps child lists on the device, which the seed does not rebuild')
+            raise ValueError(f'{who}: rewire="correct" keeps child lists on the device, which the seed does not rebuild')
         if self.last_route == "kernel-large" or self._on_the_large_grid_kernel():
-            raise ValueError("grow: the large-grid route (grids beyond 2048 cells a side) is not grown")
-        self._keep_guard("grow", np.asarray(self.og).shape)
+            raise ValueError(f"{who}: the large-grid route (grids beyond 2048 cells a side) is not {'grown' if vertex is None else 're-rooted'}")
+        self._keep_guard(who, np.asarray(self.og).shape)
         m = int(m)
         if m < 0:
-            raise ValueError(f"grow: m={m}")
-        ctx = self._device()
-        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow(), or the alive ones of the last keep_tree
+            raise ValueError(f"{who}: m={m}")
+        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow() / reroot(), or the alive ones of the last keep_tree
         if j0 == 0:
-            raise ValueError("grow: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
+            raise ValueError(f"{who}: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
         if j0 + m > int(self.n):
-            raise ValueError(f"grow: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
+            raise ValueError(f"{who}: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
+        if vertex is not None:
+            vertex = int(vertex)
+            if vertex < 0:
+                raise ValueError(f"reroot: vertex={vertex}")
+        ctx = self._device()
         if getattr(self, "_free_packed_of", None) is not self.free:
             self._free_packed, self._free_packed_of = hostprep.pack_cells(self.free), self.free
+        state0 = self.rand_gen.bit_generator.state
         samples = hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, m)
         bar = tqdm(total=m) if self.pbar else None
         try:
             self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
             try:
-                rc, res, j0, old_id = ctx.grow(samples, int(self.n))
+                rc, res, j0, old_id = ctx.grow(samples, int(self.n)) if vertex is None else ctx.reroot(vertex, samples, int(self.n))
             except _ffi.RRTError as e:
                 if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
                     self._tree_resident = "device"
+                    if vertex is not None and e.code == _ffi.RRT_E_ARG and "root=" in str(e):
+                        self.rand_gen.bit_generator.state = state0  # (a refused vertex spends no draws)
+                        raise ValueError(f"reroot: {str(e).split(': ', 2)[-1]}") from e
                 raise
             self._tree_resident = "device"
             self.last_route = "kernel"
