@@ -17,10 +17,50 @@ struct DubCfg {
     double inv_rho = 0.0;  // 1.0 / rho, once per launch (the division dub_sweep_setup_sc makes per sweep: the same operation, the same bits)
 };
 
+// The heading table of a launch, filled by the workgroup's NT threads, and the DubCfg that points to it: ONE definition of the bits every
+// pose call prices and sweeps with (an unchanged map keeps every vertex, length == cost, the points of a leg are the samples plan()
+// tested).  htab: [3][256] doubles in LDS; the caller's barrier comes before the first use.  rrt_dubins_block_kernel
+// (rrt_dubins_block.h) holds the one remaining copy of this loop: adopting the function there moves that kernel's code.
+template <int NT>
+__device__ __forceinline__ DubCfg dub_cfg_fill(RRT_LDS double *htab, double rho, int nh, int W, int H) {
+    for (int h = (int)threadIdx.x; h < nh && h < 256; h += NT) {
+        const double th = dub_heading(h, nh);
+        double sn, cs;
+        dub_sincos(th, &sn, &cs);
+        htab[h] = th;
+        htab[256 + h] = sn;
+        htab[512 + h] = cs;
+    }
+    DubCfg dc{rho, nh, W, H};
+    dc.htab = htab;
+    dc.inv_rho = 1.0 / rho;
+    return dc;
+}
+
 __device__ __forceinline__ double dub_lane_f64(double v, int l) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// no word: what a lane without an edge holds, and what dub_sweep_wave refuses
+__device__ __forceinline__ dub_path_t dub_no_path() {
+    dub_path_t p;
+    p.t = p.p = p.q = 0.0;
+    p.len = f64_inf();
+    p.word = DUB_NONE;
+    return p;
+}
+
+// the word that lane l holds, in every lane (l uniform)
+__device__ __forceinline__ dub_path_t dub_path_from_lane(const dub_path_t &v, int l) {
+    dub_path_t p;
+    p.t = dub_lane_f64(v.t, l);
+    p.p = dub_lane_f64(v.p, l);
+    p.q = dub_lane_f64(v.q, l);
+    p.len = dub_lane_f64(v.len, l);
+    p.word = __builtin_amdgcn_readlane(v.word, l);
+    return p;
 }
 
 // dub_sweep_setup_sc for a wavefront (uniform operands, uniform result; needs DubCfg::inv_rho): the same values field by field.  The

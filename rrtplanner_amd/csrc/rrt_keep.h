@@ -20,18 +20,17 @@
 //
 //   1. rrt_keep_edge_kernel        one wavefront per vertex, grid-stride: edge_ok by los_wave (los_wave_large for a batch created with
 //                                  RRT_FLAG_LARGE_GRID), and anc[k] = parent[k] (anc[0] = 0).  A parent outside [0, j): not ok.
-//   2. rrt_keep_jump_kernel        one round of pointer jumping, one vertex per lane: ok2[k] = ok[k] & ok[anc[k]], anc2[k] = anc[anc[k]].
-//                                  After r rounds ok[k] covers the 2^r vertices from k towards the root, so ceil(log2(max(j, 2)))
-//                                  rounds cover any depth below j: the host queues that many launches, ping-ponging two buffers.
-//                                  parent[k] < k is not assumed.  Nothing is read back and nothing waits across workgroups.
+//   2. rrt_keep_jump_kernel        one round of pointer jumping (jump_round, rrt_tree_dev.h); ceil(log2(max(j, 2))) rounds.
 //   3. rrt_keep_compact_kernel     one workgroup walks [0, j) TPB vertices a pass: ballot / popcount prefixes inside a wave, the
-//                                  waves' counts through LDS, the carry in a register.  alive[k] = ok[k] and anc[k] == 0 (a walk
-//                                  that is not at the root after j steps belongs to no tree: not alive).
+//                                  waves' counts through LDS, the carry in a register -- wg_scan_step (rrt_tree_dev.h) written out: with
+//                                  the function the compiler moves the wave counts through scalar registers, 16 readfirstlanes a
+//                                  pass, and the stage measured 18 % slower (profiles/tree_kernels_shared_wall.json).  alive[k] = ok[k]
+//                                  and anc[k] == 0 (a walk that is not at the root after j steps belongs to no tree: not alive).
 //   4. rrt_keep_remap_kernel       vertex[g] = vertex[g] < 0 ? -1 : live_id[vertex[g]], behind the goals kernel.
 // (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_device.h"
+#include "rrt_tree_dev.h"
 
 namespace rrtdev {
 
@@ -64,13 +63,8 @@ __global__ __launch_bounds__(KEEP_TPB) void rrt_keep_edge_large_kernel(KeepView 
     keep_edge_body<true>(kv);
 }
 
-// one round of pointer jumping; every anc[k] is in [0, j) (the edge test wrote it so, and a round keeps it so)
 __global__ __launch_bounds__(KEEP_TPB) void rrt_keep_jump_kernel(const uint8_t *ok, const int32_t *anc, uint8_t *ok2, int32_t *anc2, int32_t j) {
-    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k >= j) return;
-    const int a = anc[k];
-    ok2[k] = ok[k] & ok[a];
-    anc2[k] = anc[a];
+    jump_round<false>(ok, anc, nullptr, ok2, anc2, nullptr, j);
 }
 
 // order-preserving compaction of the alive vertices by ONE workgroup of TPB threads

@@ -122,10 +122,7 @@ __device__ __forceinline__ void pose_goal_bounded(const PoseGoalsView &pv, const
         uint32_t k = NONE, nk = 0;
         int hk = 0;
         double c = f64_inf();
-        dub_path_t pth;
-        pth.t = pth.p = pth.q = 0.0;
-        pth.len = f64_inf();
-        pth.word = DUB_NONE;
+        dub_path_t pth = dub_no_path();
         if (p < limit) {
             k = order[p];
             nk = nodes[k];
@@ -144,12 +141,7 @@ __device__ __forceinline__ void pose_goal_bounded(const PoseGoalsView &pv, const
             wave_min_f64_idx(mc, mi);
             if (mi == NONE) break;
             const int l = (int)__builtin_ctzll(__ballot(pend && k == mi));  // (a vertex sits in one lane)
-            dub_path_t wp;
-            wp.t = dub_lane_f64(pth.t, l);
-            wp.p = dub_lane_f64(pth.p, l);
-            wp.q = dub_lane_f64(pth.q, l);
-            wp.len = dub_lane_f64(pth.len, l);
-            wp.word = __builtin_amdgcn_readlane(pth.word, l);
+            const dub_path_t wp = dub_path_from_lane(pth, l);
             const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)nk, l);
             const int ha = __builtin_amdgcn_readlane(hk, l);
             int cc = 0;
@@ -190,17 +182,7 @@ __device__ __forceinline__ void pose_goal_bounded(const PoseGoalsView &pv, const
 
 __device__ __forceinline__ void pose_goals_body(const PoseGoalsView &pv, RRT_LDS uint32_t *lds16k, BSlot *bslots, RRT_LDS double *htab) {
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    for (int h = t; h < pv.nh && h < 256; h += TPB) {  // exactly the table of rrt_dubins_block_kernel
-        const double th = dub_heading(h, pv.nh);
-        double sn, cs;
-        dub_sincos(th, &sn, &cs);
-        htab[h] = th;
-        htab[256 + h] = sn;
-        htab[512 + h] = cs;
-    }
-    DubCfg dc{pv.rho, pv.nh, pv.W, pv.H};
-    dc.htab = htab;
-    dc.inv_rho = 1.0 / pv.rho;
+    const DubCfg dc = dub_cfg_fill<TPB>(htab, pv.rho, pv.nh, pv.W, pv.H);
     __syncthreads();
     uint32_t *order = pv.order + (size_t)blockIdx.x * (size_t)pv.slab_words;
     for (int g = (int)blockIdx.x; g < pv.m; g += (int)gridDim.x) {

@@ -19,10 +19,10 @@
 //                                   compute the same word.  A wavefront takes 64 consecutive vertices a round, grid-stride, as a round
 //                                   of pose_goal_bounded (rrt_pose_goals.h) does: every lane evaluates the word of ITS edge once
 //                                   (dub_between_dev); then the wavefront sweeps the edges of the round one after the other
-//                                   (dub_sweep_wave), word and poses handed from the edge's lane by readlane / dub_lane_f64.  Every lane
+//                                   (dub_sweep_wave), word and poses handed from the edge's lane by dub_path_from_lane / readlane.  Every lane
 //                                   keeps the answer of its own edge and writes ok[k] and anc[k] = parent[k] (anc[0] = 0, k itself for
-//                                   a parent outside [0, j)) once, behind the round.  The heading table in LDS is pose_goals_body's, so
-//                                   DubCfg is the same and the words are the planner's bits.  Nothing waits across workgroups.
+//                                   a parent outside [0, j)) once, behind the round.  DubCfg and its heading table are dub_cfg_fill's
+//                                   (rrt_dubins_dev.h): the words are the planner's bits.  Nothing waits across workgroups.
 //                                   (Tree edges are short -- at most r_rewire --, so a sweep round of 128 samples is mostly empty lanes;
 //                                   packing several edges into one round is left to a measurement: profiles/pose_keep_wall.json.)
 //   2. rrt_pose_keep_gather_kernel  behind rrt_keep_compact_kernel, one alive vertex per lane: live_heading[i] = heading[live_id[i]]
@@ -38,17 +38,7 @@ __global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_edge_kernel(PoseK
     __shared__ __attribute__((aligned(16))) double htab_s[3 * 256];
     RRT_LDS double *htab = (RRT_LDS double *)htab_s;
     const int t = (int)threadIdx.x, lane = t & 63;
-    for (int h = t; h < kv.nh && h < 256; h += POSE_KEEP_TPB) {  // exactly the table of rrt_dubins_block_kernel and pose_goals_body
-        const double th = dub_heading(h, kv.nh);
-        double sn, cs;
-        dub_sincos(th, &sn, &cs);
-        htab[h] = th;
-        htab[256 + h] = sn;
-        htab[512 + h] = cs;
-    }
-    DubCfg dc{kv.rho, kv.nh, kv.W, kv.H};
-    dc.htab = htab;
-    dc.inv_rho = 1.0 / kv.rho;
+    const DubCfg dc = dub_cfg_fill<POSE_KEEP_TPB>(htab, kv.rho, kv.nh, kv.W, kv.H);
     __syncthreads();
     const uint8_t *og = kv.og;
     const int j = kv.j;
@@ -58,10 +48,7 @@ __global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_edge_kernel(PoseK
         const int k = base + lane;
         int p = -1, hp = 0;
         uint32_t np = 0, nk = 0;
-        dub_path_t pth;
-        pth.t = pth.p = pth.q = 0.0;
-        pth.len = f64_inf();
-        pth.word = DUB_NONE;
+        dub_path_t pth = dub_no_path();
         if (k < j) {
             p = k == 0 ? 0 : kv.parent[k];
             if (p >= 0 && p < j) {
@@ -77,13 +64,8 @@ __global__ __launch_bounds__(POSE_KEEP_TPB) void rrt_pose_keep_edge_kernel(PoseK
         bool mine = k == 0 && p == 0 && og[(uint32_t)(ux(nk) * kv.H + uy(nk))] == 0;
         const int cnt = j - base < 64 ? j - base : 64;
         for (int l = 0; l < cnt; ++l) {  // (l is wave-uniform)
-            dub_path_t wp;
-            wp.word = __builtin_amdgcn_readlane(pth.word, l);
+            const dub_path_t wp = dub_path_from_lane(pth, l);
             if (wp.word == DUB_NONE) continue;  // the root (decided above), a parent outside the tree, or no word: not ok
-            wp.t = dub_lane_f64(pth.t, l);
-            wp.p = dub_lane_f64(pth.p, l);
-            wp.q = dub_lane_f64(pth.q, l);
-            wp.len = dub_lane_f64(pth.len, l);
             const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)np, l), b = (uint32_t)__builtin_amdgcn_readlane((int)nk, l);
             const int ha = __builtin_amdgcn_readlane(hp, l);
             int cc = 0;

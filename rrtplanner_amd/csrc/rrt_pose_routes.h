@@ -22,14 +22,14 @@
 //                                    nothing.  Kept row e <= b goes to slot e of the same rows: slots at or below a + 1 are never read
 //                                    again (the candidates of the next anchor b are above b + 1 > e), the anchor's pose is held in
 //                                    registers, and slot e == b receives what it holds.  kept[g] = e at the end, 0 without rows.  The
-//                                    heading table is the leg kernel's; behind its barrier there is none: routes differ in length
+//                                    heading table is dub_cfg_fill's; behind its barrier there is none: routes differ in length
 //                                    and no wavefront waits for another.
 //  2b. rrt_route_scan_kernel again   (shortcuts only) over kept: the 64-bit offsets of the kept rows.
 //  2c. rrt_pose_route_pack_kernel    (shortcuts only) one goal per wavefront: its kept rows to the dense rows that steps 3 - 6 read as
 //                                    they read the rows of step 2.  The words and lengths of the kept legs are step 3's: one definition.
 //   3. rrt_pose_route_leg_kernel     one ROW per lane, grid-stride.  A row with id -1 is the last of its route: leg length 0, one point
 //                                    (the goal cell).  Any other row r evaluates dub_between_dev(row r, row r + 1) once, with the heading
-//                                    table in LDS exactly as rrt_pose_keep_edge_kernel builds it: the words are the planner's bits.  With
+//                                    table in LDS that dub_cfg_fill (rrt_dubins_dev.h) builds: the words are the planner's bits.  With
 //                                    points it also runs the sweep set-up once (dub_sweep_setup_sc with the table's sine / cosine) and
 //                                    stores the leg's dub_sweep_t and its nsamples = floor(len / DUB_DS) + 1.  DUB_NONE, a length that
 //                                    is not finite or more than POSE_ROUTE_LEG_POINTS samples cannot happen on a valid tree (every
@@ -89,17 +89,7 @@ __global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_cut_kernel(PoseCu
     __shared__ __attribute__((aligned(16))) double htab_s[3 * 256];
     RRT_LDS double *htab = (RRT_LDS double *)htab_s;
     const int t = (int)threadIdx.x, lane = t & 63;
-    for (int h = t; h < pc.nh && h < 256; h += POSE_CUT_TPB) {  // exactly the table of rrt_pose_route_leg_kernel
-        const double th = dub_heading(h, pc.nh);
-        double sn, cs;
-        dub_sincos(th, &sn, &cs);
-        htab[h] = th;
-        htab[256 + h] = sn;
-        htab[512 + h] = cs;
-    }
-    DubCfg dc{pc.rho, pc.nh, pc.W, pc.H};
-    dc.htab = htab;
-    dc.inv_rho = 1.0 / pc.rho;
+    const DubCfg dc = dub_cfg_fill<POSE_CUT_TPB>(htab, pc.rho, pc.nh, pc.W, pc.H);
     __syncthreads();  // the only barrier: from here on every wavefront is on its own
     const uint8_t *og = pc.og;
     const int waves = POSE_CUT_TPB / 64;
@@ -121,10 +111,7 @@ __global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_cut_kernel(PoseCu
             for (int hi = k - 1; hi > a + 1 && b == a + 1; hi -= 64) {
                 const int c = hi - lane;  // this lane's candidate: its word, once
                 uint32_t pcell = 0;
-                dub_path_t pth;
-                pth.t = pth.p = pth.q = 0.0;
-                pth.len = f64_inf();
-                pth.word = DUB_NONE;
+                dub_path_t pth = dub_no_path();
                 if (c > a + 1) {
                     pcell = xy[c];
                     pth = dub_between_dev(pa, ha, pcell, (int)hd[c], dc);
@@ -133,13 +120,8 @@ __global__ __launch_bounds__(POSE_CUT_TPB) void rrt_pose_route_cut_kernel(PoseCu
                 }
                 const int cnt = hi - (a + 1) < 64 ? hi - (a + 1) : 64;
                 for (int l = 0; l < cnt; ++l) {  // (l is wave-uniform) the farthest candidate first
-                    dub_path_t wp;
-                    wp.word = __builtin_amdgcn_readlane(pth.word, l);
+                    const dub_path_t wp = dub_path_from_lane(pth, l);
                     if (wp.word == DUB_NONE) continue;
-                    wp.t = dub_lane_f64(pth.t, l);
-                    wp.p = dub_lane_f64(pth.p, l);
-                    wp.q = dub_lane_f64(pth.q, l);
-                    wp.len = dub_lane_f64(pth.len, l);
                     const uint32_t pb = (uint32_t)__builtin_amdgcn_readlane((int)pcell, l);
                     int cc = 0;
                     if (dub_sweep_wave(og, dc, pa, ha, pb, wp, lane, cc)) {
@@ -184,17 +166,7 @@ __global__ __launch_bounds__(POSE_ROUTE_TPB) void rrt_pose_route_leg_kernel(Pose
     __shared__ __attribute__((aligned(16))) double htab_s[3 * 256];
     RRT_LDS double *htab = (RRT_LDS double *)htab_s;
     const int t = (int)threadIdx.x;
-    for (int h = t; h < pr.nh && h < 256; h += POSE_ROUTE_TPB) {  // exactly the table of rrt_dubins_block_kernel and pose_goals_body
-        const double th = dub_heading(h, pr.nh);
-        double sn, cs;
-        dub_sincos(th, &sn, &cs);
-        htab[h] = th;
-        htab[256 + h] = sn;
-        htab[512 + h] = cs;
-    }
-    DubCfg dc{pr.rho, pr.nh, pr.W, pr.H};
-    dc.htab = htab;
-    dc.inv_rho = 1.0 / pr.rho;
+    const DubCfg dc = dub_cfg_fill<POSE_ROUTE_TPB>(htab, pr.rho, pr.nh, pr.W, pr.H);
     __syncthreads();
     dub_sweep_t *sweep = static_cast<dub_sweep_t *>(pr.sweep_bytes);
     const int64_t rows = pr.rows, stride = (int64_t)gridDim.x * POSE_ROUTE_TPB;

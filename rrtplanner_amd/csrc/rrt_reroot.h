@@ -17,8 +17,8 @@
 //   2. rrt_reroot_edge_kernel     one wavefront per reversed edge i < d, grid-stride: ok[p_{i+1}] = los_wave(p_i -> p_{i+1}),
 //                                 new_parent[p_{i+1}] = p_i; new_parent[r] = -1.
 //      rrt_reroot_link_kernel     anc[k] = new_parent[k] (r: itself), dep[k] = 1 (r: 0): the start of the pointer jumping.
-//   3. rrt_reroot_jump_kernel     one round: ok2 = ok & ok[anc], dep2 = dep + dep[anc], anc2 = anc[anc]; dep[k] is the number of edges
-//                                 between k and anc[k] all along.  ceil(log2(max(j, 2))) rounds, queued by the host.  Afterwards
+//   3. rrt_reroot_jump_kernel     one round of pointer jumping with the depth (jump_round, rrt_tree_dev.h): dep[k] is the number of
+//                                 edges between k and anc[k] all along.  ceil(log2(max(j, 2))) rounds, queued by the host.  Afterwards
 //                                 alive[k] = ok[k] and anc[k] == r, and dep[k] is the depth of an alive vertex.
 //   4. The order is a stable counting sort on the key (depth, segment of the index range): the segments, up to 64 of them, only spread
 //      the vertices of one level over several wavefronts; the key ascends with the index inside a level, so the order is still
@@ -28,10 +28,9 @@
 //                                 key (integer atomics: a sum, no order).
 //      rrt_reroot_scan_kernel     one workgroup: level_start = exclusive scan of level_cnt over the keys, the alive count.
 //      rrt_reroot_place_kernel    every wavefront OWNS the keys with key % REROOT_WAVES == its number, which all lie in one segment, and
-//                                 walks that segment in index order, 256 keys a step; the owned ones go behind the key's cursor, lanes
-//                                 in ascending order.  The cursors of a wavefront start at level_start and live in its own LDS words:
-//                                 a stable placement without a wait across wavefronts, without a barrier and without atomics.
-//                                 It writes rank[k] and src[pos] and loads nothing but the keys.
+//                                 walks that segment in index order, 256 keys a step; the owned ones go behind the key's cursor, which
+//                                 starts at level_start (wave_place_by_key, rrt_tree_dev.h).  It writes rank[k] and src[pos] and loads
+//                                 nothing but the keys.
 //      rrt_reroot_parent_kernel   one new number per lane, behind the placement of every vertex: the point and the previous number of
 //                                 src[pos], and out_parent[pos] = rank[new_parent[src[pos]]].
 //   5. rrt_reroot_cost_kernel     one workgroup: a level is a contiguous range whose parents are in the level before; level after
@@ -40,7 +39,7 @@
 // (The view, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_device.h"
+#include "rrt_tree_dev.h"
 
 namespace rrtdev {
 
@@ -100,15 +99,9 @@ __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_link_kernel(RerootView 
     rv.dep[k] = top ? 0 : 1;
 }
 
-// one round of pointer jumping; every anc[k] is in [0, j) (the link kernel wrote it so, and a round keeps it so)
 __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_jump_kernel(const uint8_t *ok, const int32_t *anc, const int32_t *dep, uint8_t *ok2, int32_t *anc2,
                                                                      int32_t *dep2, int32_t j) {
-    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k >= j) return;
-    const int a = anc[k];
-    ok2[k] = ok[k] & ok[a];
-    anc2[k] = anc[a];
-    dep2[k] = (int32_t)((uint32_t)dep[k] + (uint32_t)dep[a]);  // (of a vertex on a cycle it may wrap: such a vertex never reaches the root)
+    jump_round<true>(ok, anc, dep, ok2, anc2, dep2, j);
 }
 
 // How many segments the index range [0, j) is cut into for the order: the largest power of two up to REROOT_SEGS for which the keys
@@ -144,21 +137,15 @@ __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_level_kernel(RerootView
     const bool live = d >= 0 && d <= maxd;
     const int key = live ? d * segs + k / seglen : -1;  // (below (maxd + 1) * segs <= j)
     if (k < j) rv.key[k] = key;
-    unsigned long long m = __ballot(live);
-    while (m) {  // one key of this wavefront after the other: its first lane adds the count
-        const int first = (int)__builtin_ctzll(m);
-        const int kl = __builtin_amdgcn_readlane(key, first);
-        const unsigned long long same = __ballot(live && key == kl);
-        if (lane == first) atomicAdd(&rv.level_cnt[kl], (int32_t)__builtin_popcountll(same));
-        m &= ~same;
-    }
+    wave_each_key(live, key, [&](int kl, unsigned long long same, bool) {  // the first lane of a key adds its count
+        if (lane == (int)__builtin_ctzll(same)) atomicAdd(&rv.level_cnt[kl], (int32_t)__builtin_popcountll(same));
+    });
 }
 
 // exclusive scan of level_cnt[0, L) into level_start[0, L], L = the number of keys, (maxd + 1) * segments <= j: one workgroup of TPB
 // threads, TPB values a pass.  Nothing reads level_start behind L.
 __global__ __launch_bounds__(TPB) void rrt_reroot_scan_kernel(RerootView rv) {
-    __shared__ uint32_t wsum[2][NWAVE];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = (int)threadIdx.x;
     const int maxd = rv.head[REROOT_MAXD];
     const int L = maxd < 0 || maxd >= rv.j ? 0 : (maxd + 1) * reroot_segments(rv.j, maxd);  // (uniform)
     uint32_t carry = 0;
@@ -167,18 +154,9 @@ __global__ __launch_bounds__(TPB) void rrt_reroot_scan_kernel(RerootView rv) {
         const int k = base + t;
         const uint32_t v = k < L ? (uint32_t)rv.level_cnt[k] : 0u;
         const uint32_t incl = wave_incl_sum_u32(v);
-        if (lane == 63) wsum[par][wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < NWAVE; ++w) {
-            const uint32_t s = wsum[par][w];
-            before += w < wave ? s : 0u;
-            total += s;
-        }
-        par ^= 1;  // (the next pass writes the other half: no second barrier)
-        if (k < L) rv.level_start[k] = (int32_t)(carry + before + incl - v);
-        carry += total;
+        const WgScan s = wg_scan_step(incl, par);
+        if (k < L) rv.level_start[k] = (int32_t)(carry + s.before + incl - v);
+        carry += s.total;
     }
     if (t == 0) {
         rv.level_start[L] = (int32_t)carry;
@@ -202,12 +180,11 @@ __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_place_kernel(RerootView
     // every key this wavefront owns has the segment gw % segs (segs divides REROOT_WAVES): it walks that segment alone
     const int seg = gw & (segs - 1);
     const int lo = seg * seglen, hi = min(j, lo + seglen);
-    volatile RRT_LDS int32_t *cur = (volatile RRT_LDS int32_t *)&cur_lds[wave][0];  // of this wavefront alone: no barrier, no atomics
+    volatile RRT_LDS int32_t *cur = (volatile RRT_LDS int32_t *)&cur_lds[wave][0];  // of this wavefront alone
     for (int slot = lane; slot < REROOT_OWN; slot += 64) {
         const int key = slot * REROOT_WAVES + gw;
         cur[slot] = key < keys ? rv.level_start[key] : j;  // (j: a position nothing is stored at)
     }
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int base = lo; base < hi; base += 256) {  // (wave-uniform trip count; the four loads of a step are in flight together)
         int key4[4];
 #pragma unroll
@@ -220,25 +197,14 @@ __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_place_kernel(RerootView
             const int k = base + 64 * u + lane;
             const int key = key4[u];
             const bool mine = key >= 0 && key < keys && (key & (REROOT_WAVES - 1)) == gw;
-            unsigned long long m = __ballot(mine);
-            while (m) {  // one key of this step after the other; its vertices are the lanes of `same`, in ascending index
-                const int kl = __builtin_amdgcn_readlane(key, (int)__builtin_ctzll(m));
-                const bool here = mine && key == kl;
-                const unsigned long long same = __ballot(here);
-                const int slot = kl / REROOT_WAVES;
-                const int32_t before = cur[slot];
-                if (here) {
-                    const int32_t pos = before + (int32_t)__builtin_popcountll(same & below);
-                    if (pos >= 0 && pos < j) {
-                        rv.rank[k] = pos;  // (stores only: nothing in this loop waits for global memory but the keys of a step)
-                        rv.src[pos] = k;
-                    } else {
-                        atomicOr(&rv.head[REROOT_ERR], 1);
-                    }
+            wave_place_by_key<REROOT_WAVES>(mine, key, cur, [&](int, int32_t pos) {
+                if (pos >= 0 && pos < j) {
+                    rv.rank[k] = pos;  // (stores only: nothing in this loop waits for global memory but the keys of a step)
+                    rv.src[pos] = k;
+                } else {
+                    atomicOr(&rv.head[REROOT_ERR], 1);
                 }
-                if (lane == 0) cur[slot] = before + (int32_t)__builtin_popcountll(same);
-                m &= ~same;
-            }
+            });
         }
     }
 }

@@ -18,7 +18,7 @@
 // (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_device.h"
+#include "rrt_tree_dev.h"
 
 namespace rrtdev {
 
@@ -106,26 +106,16 @@ __global__ __launch_bounds__(ROUTE_TPB) void rrt_route_depth_kernel(RoutesView r
 // exclusive scan of in[0, m) into out[0, m]: one workgroup of TPB threads, TPB values a pass (each at most j + 1 < 2^19: a pass sums
 // below 2^32), the carry in 64 bits
 __global__ __launch_bounds__(TPB) void rrt_route_scan_kernel(const int32_t *in, int64_t *out, int32_t m) {
-    __shared__ uint32_t wsum[2][NWAVE];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = (int)threadIdx.x;
     int64_t carry = 0;
     int par = 0;
     for (int base = 0; base < m; base += TPB) {
         const int i = base + t;
         const uint32_t v = i < m ? (uint32_t)in[i] : 0u;
         const uint32_t incl = wave_incl_sum_u32(v);
-        if (lane == 63) wsum[par][wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < NWAVE; ++w) {
-            const uint32_t s = wsum[par][w];
-            before += w < wave ? s : 0u;
-            total += s;
-        }
-        par ^= 1;  // (the next pass writes the other half: no second barrier)
-        if (i < m) out[i] = carry + (int64_t)(before + incl - v);
-        carry += (int64_t)total;
+        const WgScan s = wg_scan_step(incl, par);
+        if (i < m) out[i] = carry + (int64_t)(s.before + incl - v);
+        carry += (int64_t)s.total;
     }
     if (t == 0) out[m] = carry;
 }

@@ -21,14 +21,13 @@
 //   4. rrt_seed_bitmap_kernel    the bits of vertices 1 .. j0-1 (atomicOr, the layout of the expansion kernels: cell = x * H + y,
 //                                word cell >> 5, bit cell & 31); the words were cleared by a memset in front of it
 //   5. rrt_seed_records_kernel   every wavefront OWNS the cells c with c % SEED_WAVES == its number and walks ALL vertices in index
-//                                order, 64 a step: the owned ones of a step are placed behind the cell's count, lanes in ascending
-//                                order.  A cell is written by one wave only, in index order, with its counts in that wave's LDS:
-//                                ordered placement without a wait across wavefronts or workgroups, and without atomics.
+//                                order, 64 a step: the owned ones of a step are placed behind the cell's count
+//                                (wave_place_by_key, rrt_tree_dev.h).
 // Every store is bounds-checked; a vertex outside the record grid or a cell past its capacity sets *err and stores nothing.
 // (The views, the launch constants and the kernels' declarations: rrt_kernel_abi.h, which is all a host unit sees of this file.)
 #pragma once
 
-#include "rrt_device.h"
+#include "rrt_tree_dev.h"
 
 namespace rrtdev {
 
@@ -87,10 +86,9 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords 
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int gw = (int)blockIdx.x * (SEED_TPB / 64) + wave;  // this wavefront's number: it owns the cells c with c % SEED_WAVES == gw
     if (gw >= SEED_WAVES) return;                              // (a launch with more workgroups than SEED_WG: nothing left to own)
-    volatile RRT_LDS uint32_t *cnt = (volatile RRT_LDS uint32_t *)&cnt_lds[wave][0];  // of this wavefront alone: no barrier, no atomics
+    volatile RRT_LDS uint32_t *cnt = (volatile RRT_LDS uint32_t *)&cnt_lds[wave][0];  // of this wavefront alone
     if (lane < SEED_OWN) cnt[lane] = 0u;
     const int j0 = sr.j0;
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int base = 0; base < j0; base += 64) {  // (wave-uniform trip count)
         const int k = base + lane;
         const bool live = k < j0;
@@ -100,26 +98,15 @@ __global__ __launch_bounds__(SEED_TPB) void rrt_seed_records_kernel(SeedRecords 
         const bool inside = cx < sr.ncx && cy < sr.ncy;  // (then c < ncx * ncy <= MAX_CELLS)
         if (live && !inside) *sr.err = 1;
         const bool mine = live && inside && (c & (SEED_WAVES - 1)) == gw;
-        unsigned long long m = __ballot(mine);
-        while (m) {  // one cell of this step after the other; its vertices are the lanes of `same`, in ascending index
-            const int cl = __builtin_amdgcn_readlane(c, (int)__builtin_ctzll(m));
-            const bool here = mine && c == cl;
-            const unsigned long long same = __ballot(here);
-            const int slot = cl / SEED_WAVES;
-            const uint32_t before = cnt[slot];
-            if (here) {
-                const uint32_t pos = before + (uint32_t)__builtin_popcountll(same & below);
-                const int64_t at = (int64_t)cl * (int64_t)sr.ccap + (int64_t)pos;
-                if (pos < (uint32_t)sr.ccap && at < sr.rec_stride) {
-                    const unsigned long long cb = (unsigned long long)__double_as_longlong(sr.vcost[k]);
-                    sr.cellrec[at] = u32x4{xy, (uint32_t)k, (uint32_t)cb, (uint32_t)(cb >> 32)};
-                } else {
-                    *sr.err = 1;
-                }
+        wave_place_by_key<SEED_WAVES>(mine, c, cnt, [&](int cl, uint32_t pos) {
+            const int64_t at = (int64_t)cl * (int64_t)sr.ccap + (int64_t)pos;
+            if (pos < (uint32_t)sr.ccap && at < sr.rec_stride) {
+                const unsigned long long cb = (unsigned long long)__double_as_longlong(sr.vcost[k]);
+                sr.cellrec[at] = u32x4{xy, (uint32_t)k, (uint32_t)cb, (uint32_t)(cb >> 32)};
+            } else {
+                *sr.err = 1;
             }
-            if (lane == 0) cnt[slot] = before + (uint32_t)__builtin_popcountll(same);
-            m &= ~same;
-        }
+        });
     }
     if (lane < SEED_OWN) sr.cellcnt[lane * SEED_WAVES + gw] = cnt[lane];  // every cell of [0, MAX_CELLS), the empty ones too
 }

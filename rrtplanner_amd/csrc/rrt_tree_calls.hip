@@ -69,6 +69,30 @@ static TreeRef tree_ref(rrt_batch *b, int32_t q) {
     return t;
 }
 
+// ---- launches that several calls queue ----
+// the workgroups of `per` items each that cover `items`
+static unsigned wgs(int64_t items, int per) { return (unsigned)((items + per - 1) / per); }
+
+// The rounds of pointer jumping over j >= 1 vertices (jump_round, rrt_tree_dev.h): ceil(log2(max(j, 2))) of them, fixed from j -- nothing
+// is read back to stop early --, ping-ponging two sets of buffers.  round(cur) queues one round from set cur to set cur ^ 1.  Returns
+// the set that holds the result.
+template <typename Round>
+static int jump_rounds(int j, Round round) {
+    int rounds = 1, cur = 0;
+    while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
+    for (int r = 0; r < rounds; ++r, cur ^= 1) round(cur);
+    return cur;
+}
+
+// The parents of a kept view renumbered into sv.new_parent (rrt_seed_rank_kernel, rrt_seed_parent_kernel; sv: parent, j_old, j0, live_id,
+// rank, new_parent, err).  sv.err is the caller's word: it clears it in front and reads it behind.
+static int renumber_view_parents(rrt_ctx *ctx, const SeedView &sv) {
+    HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)sv.j_old * sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(rrt_seed_rank_kernel, dim3(wgs(sv.j0, SEED_TPB)), dim3(SEED_TPB), 0, ctx->stream, sv);
+    hipLaunchKernelGGL(rrt_seed_parent_kernel, dim3(wgs(sv.j0, SEED_TPB)), dim3(SEED_TPB), 0, ctx->stream, sv);
+    return RRT_OK;
+}
+
 // What a decision (goals_decide, poses_decide) runs over: the whole tree of query q, or, for a query that was kept on this grid
 // (rrt_batch_keep_tree, rrt_batch_keep_pose_tree), the view of its alive vertices, dense and in the original order.  `launch` gets
 // (nodes, vcost, heading, j) and launches the kernel, which answers in indices of what it was given; rrt_keep_remap_kernel then turns
@@ -80,7 +104,7 @@ static void decide_over(rrt_batch *b, int32_t q, int32_t *vertex, int32_t m, Lau
     const int32_t j = view ? t.kept : b->h_desc[(size_t)q].j;
     launch(view ? t.live_nodes : t.nodes, view ? t.live_vcost : t.vcost, view ? t.live_heading : t.heading, j);
     if (view)
-        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3((unsigned)((m + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, b->ctx->stream, vertex,
+        hipLaunchKernelGGL(rrt_keep_remap_kernel, dim3(wgs(m, KEEP_TPB)), dim3(KEEP_TPB), 0, b->ctx->stream, vertex,
                            (const int32_t *)t.live_id, m, j);
 }
 
@@ -328,8 +352,8 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
             kv.rho = d.rho;
             kv.ok = ok[0];
             kv.anc = anc[0];
-            hipLaunchKernelGGL(rrt_pose_keep_edge_kernel, dim3((unsigned)std::min((j + POSE_KEEP_TPB - 1) / POSE_KEEP_TPB, POSE_KEEP_MAX_WG)),
-                               dim3(POSE_KEEP_TPB), 0, ctx->stream, kv);
+            hipLaunchKernelGGL(rrt_pose_keep_edge_kernel, dim3(std::min<unsigned>(wgs(j, POSE_KEEP_TPB), POSE_KEEP_MAX_WG)), dim3(POSE_KEEP_TPB), 0, ctx->stream,
+                               kv);
         } else {  // one edge per wavefront
             KeepView kv{};
             kv.og = ctx->og;
@@ -340,19 +364,14 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
             kv.j = j;
             kv.ok = ok[0];
             kv.anc = anc[0];
-            const int per_wg = KEEP_TPB / 64;
-            const unsigned edge_wgs = (unsigned)((j + per_wg - 1) / per_wg > KEEP_MAX_WG ? KEEP_MAX_WG : (j + per_wg - 1) / per_wg);
-            hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel, dim3(edge_wgs), dim3(KEEP_TPB), 0,
-                               ctx->stream, kv);
+            hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_keep_edge_large_kernel : rrt_keep_edge_kernel,
+                               dim3(std::min<unsigned>(wgs(j, KEEP_TPB / 64), KEEP_MAX_WG)), dim3(KEEP_TPB), 0, ctx->stream, kv);
         }
         HIPCHK(ctx, time.mark(1, ctx->stream));
-        // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
-        int rounds = 1;
-        while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
-        int cur = 0;
-        for (int r = 0; r < rounds; ++r, cur ^= 1)
-            hipLaunchKernelGGL(rrt_keep_jump_kernel, dim3((unsigned)((j + KEEP_TPB - 1) / KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, (const uint8_t *)ok[cur],
-                               (const int32_t *)anc[cur], ok[cur ^ 1], anc[cur ^ 1], j);
+        const int cur = jump_rounds(j, [&](int from) {
+            hipLaunchKernelGGL(rrt_keep_jump_kernel, dim3(wgs(j, KEEP_TPB)), dim3(KEEP_TPB), 0, ctx->stream, (const uint8_t *)ok[from], (const int32_t *)anc[from],
+                               ok[from ^ 1], anc[from ^ 1], j);
+        });
         HIPCHK(ctx, time.mark(2, ctx->stream));
         KeepCompact kc{};
         kc.nodes = t.nodes;
@@ -367,7 +386,7 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
         kc.count = d_count;
         hipLaunchKernelGGL(rrt_keep_compact_kernel, dim3(1), dim3(TPB), 0, ctx->stream, kc);
         if (poses)
-            hipLaunchKernelGGL(rrt_pose_keep_gather_kernel, dim3((unsigned)((j + POSE_KEEP_TPB - 1) / POSE_KEEP_TPB)), dim3(POSE_KEEP_TPB), 0, ctx->stream,
+            hipLaunchKernelGGL(rrt_pose_keep_gather_kernel, dim3(wgs(j, POSE_KEEP_TPB)), dim3(POSE_KEEP_TPB), 0, ctx->stream,
                                (const uint8_t *)t.heading, (const int32_t *)t.live_id, (const int32_t *)d_count, t.live_heading, j);
         HIPCHK(ctx, time.mark(3, ctx->stream));
         HIPCHK(ctx, hipGetLastError());
@@ -524,14 +543,11 @@ static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom
     sv.live_vcost = from.vcost;
     sv.live_nodes = from.nodes;
     sv.live_id = from.id;
-    auto blocks = [](int items) { return dim3((unsigned)((items + SEED_TPB - 1) / SEED_TPB)); };
+    auto blocks = [](int items) { return dim3(wgs(items, SEED_TPB)); };
     HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, time.mark(0, ctx->stream));
-    if (sv.live_id && !from.parent) {
-        HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)j_old * sizeof(int32_t), ctx->stream));
-        hipLaunchKernelGGL(rrt_seed_rank_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
-        hipLaunchKernelGGL(rrt_seed_parent_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, sv);
-    }
+    if (sv.live_id && !from.parent)
+        if (const int rc = renumber_view_parents(ctx, sv)) return rc;
     hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
     if (poses && sv.live_id)  // (without a view heading[0, j0) already stands; rrt_pose_seed.h says why the slots behind j0 are left)
         hipLaunchKernelGGL(rrt_pose_seed_heading_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, t.heading, from.heading, j0, b->node_stride);
@@ -627,7 +643,7 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     const TreeRef t = tree_ref(b, q);
     const SeedTmpScratch stmp = b->seed_tmp.carve<SeedTmpScratch>();
     const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
-    auto blocks = [](int items) { return dim3((unsigned)((items + REROOT_TPB - 1) / REROOT_TPB)); };
+    auto blocks = [](int items) { return dim3(wgs(items, REROOT_TPB)); };
     RerootView rv{};
     rv.og = ctx->og;
     rv.H = ctx->H;
@@ -645,10 +661,7 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
         sv.new_parent = stmp.new_parent;
         sv.err = stmp.err;
         HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(sv.rank, 0xff, (size_t)d.j * sizeof(int32_t), ctx->stream));
-        const dim3 seed_blocks((unsigned)((j_in + SEED_TPB - 1) / SEED_TPB));
-        hipLaunchKernelGGL(rrt_seed_rank_kernel, seed_blocks, dim3(SEED_TPB), 0, ctx->stream, sv);
-        hipLaunchKernelGGL(rrt_seed_parent_kernel, seed_blocks, dim3(SEED_TPB), 0, ctx->stream, sv);
+        if (const int rc = renumber_view_parents(ctx, sv)) return rc;
         HIPCHK(ctx, hipGetLastError());
         int32_t err = 0, in_view = -1;
         HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
@@ -691,17 +704,14 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     HIPCHK(ctx, time.mark(0, ctx->stream));
     hipLaunchKernelGGL(rrt_reroot_path_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, time.mark(1, ctx->stream));
-    const int per_wg = REROOT_TPB / 64;  // one reversed edge per wavefront; how many there are only the device knows: at most j - 1
-    hipLaunchKernelGGL(rrt_reroot_edge_kernel, dim3((unsigned)std::clamp((j + per_wg - 1) / per_wg, 1, REROOT_MAX_WG)), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    // one reversed edge per wavefront; how many there are only the device knows: at most j - 1
+    hipLaunchKernelGGL(rrt_reroot_edge_kernel, dim3(std::clamp<unsigned>(wgs(j, REROOT_TPB / 64), 1, REROOT_MAX_WG)), dim3(REROOT_TPB), 0, ctx->stream, rv);
     hipLaunchKernelGGL(rrt_reroot_link_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, time.mark(2, ctx->stream));
-    // ceil(log2(max(j, 2))) rounds, fixed from j: nothing is read back to stop early
-    int rounds = 1;
-    while (((int64_t)1 << rounds) < (int64_t)j) ++rounds;
-    int cur = 0;
-    for (int r = 0; r < rounds; ++r, cur ^= 1)
-        hipLaunchKernelGGL(rrt_reroot_jump_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
-                           (const int32_t *)tmp.dep[cur], tmp.ok[cur ^ 1], tmp.anc[cur ^ 1], tmp.dep[cur ^ 1], j);
+    const int cur = jump_rounds(j, [&](int from) {
+        hipLaunchKernelGGL(rrt_reroot_jump_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, (const uint8_t *)tmp.ok[from], (const int32_t *)tmp.anc[from],
+                           (const int32_t *)tmp.dep[from], tmp.ok[from ^ 1], tmp.anc[from ^ 1], tmp.dep[from ^ 1], j);
+    });
     HIPCHK(ctx, time.mark(3, ctx->stream));
     rv.key = tmp.dep[cur ^ 1];  // (the set the last round read: free from here on)
     hipLaunchKernelGGL(rrt_reroot_count_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
@@ -806,6 +816,31 @@ extern "C" int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count) {
     return s ? rrt_batch_reroot_ms(s, ms, count) : RRT_E_ARG;
 }
 
+// ---- the rows of the routes to the goals a decision answered: what rrt_batch_routes and rrt_batch_pose_routes start with ----
+// The depth pass and the scan of rrt_routes.h (rv: parent, j, vertex, m, cnt, raw_off, err), then the one wait that the sizes force: the
+// rows of all routes together decide how much memory the rows need.  Its two refusals: a walk that is no tree's, and more rows than
+// `budget` (noun: what the call names its goals).  time: nullptr, or the timer whose marks 2 and 3 go around the two kernels.
+static int count_route_rows(const char *who, rrt_batch *b, int32_t q, const RoutesView &rv, size_t budget, const char *noun, StageTimer *time,
+                            int64_t &rows) {
+    rrt_ctx *ctx = b->ctx;
+    HIPCHK(ctx, hipMemsetAsync(rv.err, 0, sizeof(int32_t), ctx->stream));
+    if (time) HIPCHK(ctx, time->mark(2, ctx->stream));
+    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(wgs(rv.m, ROUTE_TPB)), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.cnt, rv.raw_off, rv.m);
+    if (time) HIPCHK(ctx, time->mark(3, ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&rows, rv.raw_off + rv.m, sizeof rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, rv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err)
+        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
+    if (rows < 0 || (uint64_t)rows > budget)
+        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d %s have %lld rows together, at most %zu per call: pass fewer %s at a time", who, rv.m, noun,
+                    (long long)rows, budget, noun);
+    return RRT_OK;
+}
+
 // ---- finished routes to many goals (rrt_routes.h) ----
 static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
                         double *length, int64_t *offsets) {
@@ -837,35 +872,21 @@ static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t 
     rv.cnt = goal.cnt;
     rv.kept = goal.kept;
     rv.err = goal.err;
-    const unsigned lanes_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB), waves_grid = (unsigned)((m + ROUTE_TPB / 64 - 1) / (ROUTE_TPB / 64));
-    HIPCHK(ctx, hipMemsetAsync(rv.err, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.cnt, rv.raw_off, m);
-    HIPCHK(ctx, hipGetLastError());
-    // the one wait that the sizes force: the rows of all routes together decide how much memory the rows need
     int64_t raw_rows = 0;
-    int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&raw_rows, rv.raw_off + m, sizeof raw_rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&err, rv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (err)
-        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
-    if (raw_rows < 0 || (uint64_t)raw_rows > ROUTE_ROW_BUDGET)
-        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d goals have %lld rows together, at most %zu per call: pass fewer goals at a time", who, m,
-                    (long long)raw_rows, ROUTE_ROW_BUDGET);
+    if (const int rc = count_route_rows(who, b, q, rv, ROUTE_ROW_BUDGET, "goals", nullptr, raw_rows)) return rc;
     HIPCHK(ctx, b->route_row.reserve<RouteRowScratch>(raw_rows));
     const RouteRowScratch row = b->route_row.carve<RouteRowScratch>();
     rv.row_xy = row.row_xy;
     rv.row_id = row.row_id;
     rv.out_xy = row.out_xy;
     rv.out_id = row.out_id;
-    hipLaunchKernelGGL(rrt_route_fill_kernel, dim3(lanes_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv, cut ? 0 : 1);
+    hipLaunchKernelGGL(rrt_route_fill_kernel, dim3(wgs(m, ROUTE_TPB)), dim3(ROUTE_TPB), 0, ctx->stream, rv, cut ? 0 : 1);
     if (cut) {
-        const unsigned wgs = (unsigned)(m < ROUTE_CUT_MAX_WG ? m : ROUTE_CUT_MAX_WG);
-        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_route_cut_large_kernel : rrt_route_cut_kernel, dim3(wgs), dim3(TPB), 0, ctx->stream, rv);
+        const unsigned cut_wgs = (unsigned)(m < ROUTE_CUT_MAX_WG ? m : ROUTE_CUT_MAX_WG);
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_route_cut_large_kernel : rrt_route_cut_kernel, dim3(cut_wgs), dim3(TPB), 0, ctx->stream, rv);
         hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)rv.kept, rv.fin_off, m);
     }
-    hipLaunchKernelGGL(rrt_route_pack_kernel, dim3(waves_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_route_pack_kernel, dim3(wgs(m, ROUTE_TPB / 64)), dim3(ROUTE_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(length, rv.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(offsets, rv.fin_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -964,25 +985,10 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     rv.cnt = goal.cnt;
     rv.raw_off = goal.raw_off;
     rv.err = goal.err;
-    const unsigned goals_grid = (unsigned)((m + ROUTE_TPB - 1) / ROUTE_TPB);
-    HIPCHK(ctx, hipMemsetAsync(pr.err, 0, sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, time.mark(2, ctx->stream));
-    hipLaunchKernelGGL(rrt_route_depth_kernel, dim3(goals_grid), dim3(ROUTE_TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)goal.cnt, goal.raw_off, m);
-    HIPCHK(ctx, time.mark(3, ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    // the first wait that the sizes force: the rows of all routes together decide how much memory the rows need
-    int64_t rows = 0;
-    int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&rows, goal.raw_off + m, sizeof rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&err, pr.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (err)
-        return fail(ctx, RRT_E_HIP, "%s: a parent walk of query %d did not reach vertex 0 within %d steps: the parent array on the device is not a tree", who, q, rv.j);
-    if (rows < 0 || (uint64_t)rows > POSE_ROUTE_ROW_BUDGET)
-        return fail(ctx, RRT_E_ARG, "%s: the routes of these %d poses have %lld rows together, at most %zu per call: pass fewer poses at a time", who, m,
-                    (long long)rows, POSE_ROUTE_ROW_BUDGET);
+    int64_t rows = 0;  // (the first wait of this call)
+    if (const int rc = count_route_rows(who, b, q, rv, POSE_ROUTE_ROW_BUDGET, "poses", &time, rows)) return rc;
     int64_t npoints = 0;
+    int32_t err = 0;
     HIPCHK(ctx, b->pose_route_row.reserve<PoseRouteRowScratch>(std::max<int64_t>(rows, 1)));  // (no row: pt_off alone, one zero)
     if (pts && rows > 0) HIPCHK(ctx, b->pose_route_sweep.reserve(rows, (size_t)rows * POSE_ROUTE_SWEEP_BYTES));
     const PoseRouteRowScratch row = b->pose_route_row.carve<PoseRouteRowScratch>();
@@ -1023,8 +1029,8 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         raw.row_xy = pc.row_xy;
         raw.row_h = pc.row_h;
         raw.row_id = pc.row_id;
-        const unsigned waves_grid = (unsigned)((m + POSE_CUT_TPB / 64 - 1) / (POSE_CUT_TPB / 64));
-        hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, raw);
+        const unsigned waves_grid = wgs(m, POSE_CUT_TPB / 64);
+        hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3(wgs(m, POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, raw);
         hipLaunchKernelGGL(rrt_pose_route_cut_kernel, dim3(std::min<unsigned>(waves_grid, POSE_CUT_MAX_WG)), dim3(POSE_CUT_TPB), 0, ctx->stream, pc);
         hipLaunchKernelGGL(rrt_route_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, (const int32_t *)pc.kept, cut_goal.fin_off, m);
         hipLaunchKernelGGL(rrt_pose_route_pack_kernel, dim3(waves_grid), dim3(POSE_CUT_TPB), 0, ctx->stream, pc);
@@ -1044,8 +1050,8 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
         HIPCHK(ctx, time.mark(6, ctx->stream));
     }
     if (rows > 0) {
-        const unsigned rows_grid = (unsigned)std::min<int64_t>((rows + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
-        if (!cut) hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3((unsigned)((m + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+        const unsigned rows_grid = std::min<unsigned>(wgs(rows, POSE_ROUTE_TPB), POSE_ROUTE_MAX_WG);
+        if (!cut) hipLaunchKernelGGL(rrt_pose_route_fill_kernel, dim3(wgs(m, POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
         hipLaunchKernelGGL(rrt_pose_route_leg_kernel, dim3(rows_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
         // a leg's count is at most POSE_ROUTE_LEG_POINTS = 2^19 (the leg kernel raises err beyond, and a word whose every sample lies inside
         // a grid of 2048 x 2048 cells has some 55 000 at most): the 1024 counts of a pass of the scan sum below 2^32, as its rows do
@@ -1053,7 +1059,7 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
     } else if (pts) {
         HIPCHK(ctx, hipMemsetAsync(pr.pt_off, 0, sizeof(int64_t), ctx->stream));  // (nothing connects: no point)
     }
-    hipLaunchKernelGGL(rrt_pose_route_length_kernel, dim3((unsigned)((m + 1 + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
+    hipLaunchKernelGGL(rrt_pose_route_length_kernel, dim3(wgs(m + 1, POSE_ROUTE_TPB)), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
     HIPCHK(ctx, time.mark(leg_ev + 1, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(length, pr.length, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1075,7 +1081,7 @@ static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int
             HIPCHK(ctx, b->pose_route_pts.reserve(npoints, (size_t)npoints * sizeof(double2)));
             pr.npoints = npoints;
             pr.points = b->pose_route_pts.as<double2>();
-            const unsigned pts_grid = (unsigned)std::min<int64_t>((npoints + POSE_ROUTE_TPB - 1) / POSE_ROUTE_TPB, POSE_ROUTE_MAX_WG);
+            const unsigned pts_grid = std::min<unsigned>(wgs(npoints, POSE_ROUTE_TPB), POSE_ROUTE_MAX_WG);
             HIPCHK(ctx, time.mark(leg_ev + 2, ctx->stream));
             hipLaunchKernelGGL(rrt_pose_route_points_kernel, dim3(pts_grid), dim3(POSE_ROUTE_TPB), 0, ctx->stream, pr);
             HIPCHK(ctx, time.mark(leg_ev + 3, ctx->stream));

@@ -10,10 +10,12 @@ import goalref
 import keepref
 import oracle
 import routeref
+import test_grow_gpu as tg
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.oggen import DeviceGrids, perlin_occupancygrid, random_connected_pair
 from test_connect_goals_gpu import _free_goals, _grow, _refused, _samples, _wall_map
+from test_reroot_gpu import SIZES, _case, _sized
 from test_routes_gpu import _corridor_map, _march, _same
 
 pytestmark = pytest.mark.gpu
@@ -370,6 +372,54 @@ def test_a_tree_of_the_start_alone(gpu_ctx):
     gpu_ctx.set_grid(og2)
     assert b.keep_tree(0).tolist() == [False]
     assert b.connect_goals(0, [(10, 100)])[0].tolist() == [-1]
+    b.close()
+
+
+def test_trees_of_exactly_1_2_63_to_65_and_1023_to_1025_vertices(gpu_ctx):
+    """the compaction's wave and pass edges (64 and 1024 vertices) and the one-round case of the pointer jumping (1 and 2 vertices): the
+    trees of test_reroot_gpu's sizes, the cells of vertex j // 2 and of the last vertex turned into obstacles"""
+    def check(b, q, c):
+        pts, parent, vcost, j = tg._tree_of(b.get_result(q))
+        assert j == c["ro"].j
+        og2 = c["og8"].copy()
+        for k in (j // 2, j - 1):
+            og2[pts[k][0], pts[k][1]] = 1
+        # four goals: two corners, and the cell behind either obstacle as the root sees it (on an empty map the root itself is the
+        # cheapest vertex for every goal it sees: triangle inequality)
+        goals = np.array([np.clip(pts[k] + np.sign(pts[k] - pts[0]), 0, 63) for k in (j // 2, j - 1)] + [(0, 0), (63, 63)])
+        want, v, cost = keepref.connect(og2, pts, parent, vcost, j, goals)
+        if j >= 3:
+            assert want[0] and not want[j // 2] and not want[j - 1] and 0 < want.sum() < j
+        else:
+            assert want.tolist() == [[False], [True, False]][j - 1]
+        gpu_ctx.set_grid(og2)
+        alive = b.keep_tree(q)
+        assert np.array_equal(alive, want), (j, np.flatnonzero(alive != want)[:8])
+        gv, gc = b.connect_goals(q, goals)
+        assert np.array_equal(gv, v) and np.array_equal(gc, cost), j
+
+    cs = []
+    for k in SIZES[1:]:
+        og8, xs, samples, n = _sized(k, 100 + k)
+        cs.append(_case(og8, 0, n, xs, (63, 63), samples, 0))
+    b = tg._batch(gpu_ctx, cs[0], "team", Q=len(cs), n_cap=1040)
+    for q, c in enumerate(cs):
+        tg._set_and_run(b, q, c)
+    b.launch()
+    b.sync()
+    for q, c in enumerate(cs):
+        assert c["ro"].j == SIZES[q + 1]
+        check(b, q, c)
+    b.close()
+    # the tree of one vertex: the start boxed in, on a map and in a batch of its own
+    og8, xs, samples, n = _sized(1, 101)
+    c = _case(og8, 0, n, xs, (63, 63) if tuple(xs) != (63, 63) else (0, 0), samples, 0)
+    assert c["ro"].j == 1
+    b = tg._batch(gpu_ctx, c, "team")
+    tg._set_and_run(b, 0, c)
+    b.launch()
+    b.sync()
+    check(b, 0, c)
     b.close()
 
 
