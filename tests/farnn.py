@@ -179,7 +179,7 @@ DUBINS_CASES = [
 
 
 def pipe_case(c):
-    """(og8, samples, r2) of a pipe case: the draws of test_gpu_parity._oracle_vs_device"""
+    """(og8, samples, r2) of a pipe case: the draws of devcheck.oracle_vs_device"""
     og8 = pocket_grid(c["W"], c["H"], c["rects"], c.get("field"))
     samples = hostprep.draw_free_samples(np.random.default_rng(c["seed"]), np.argwhere(og8 == 0), c["n"])
     r2 = hostprep.radius_threshold(c["rr"]) if c["rr"] is not None else 0

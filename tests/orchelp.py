@@ -190,6 +190,21 @@ def use_oracle(planner):
     return planner
 
 
+def bits(x):
+    """what an exact comparison compares: integers and booleans as they are, anything else as the int64 bit patterns of float64"""
+    x = np.asarray(x)
+    return x if x.dtype.kind in "iub" else np.ascontiguousarray(x, dtype=np.float64).view(np.int64)
+
+
+def differ(a, b):
+    """the message operand of an assert that compares two arrays exactly: the first few rows in which they differ, or the two shapes.
+    (Asserts in helper modules are not rewritten by pytest; this is what says where.)"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.ndim == 0:
+        return a.shape, b.shape
+    return np.flatnonzero(np.asarray(bits(a) != bits(b)).reshape(len(a), -1).any(axis=1))[:8]
+
+
 def rng_state_tuple(gen):
     s = gen.bit_generator.state
     return [str(s["state"]["state"]), str(s["state"]["inc"]), int(s["has_uint32"]), int(s["uinteger"])]

@@ -14,6 +14,7 @@ in the manner of growref.py.
 
 Nothing here is shortened.  (The words and sweeps are those of include/rrt_dubins.h through the oracle, which gcc and gfx950 evaluate
 bit for bit alike; the loop around them is written here, not called.)"""
+import functools
 import math
 
 import numpy as np
@@ -21,6 +22,7 @@ import numpy as np
 import oracle
 import posekeepref
 import poseref
+from rrtplanner_amd import hostprep
 
 ST_OK, ST_UNREACHABLE = 0, -2
 
@@ -149,7 +151,7 @@ def accepted_stream(w, pad_cell, pads):
 
 
 # The stream of the uncut grow of workload A by 600 samples that the GPU test also sends through oracle/dubins_ref.c's audit:
-# default_rng(UNCUT_A_SEED) draws 600 free cells, then 600 headings.  The audit's policy (test_dubins.py::_assert_audit_clean) allows 3
+# default_rng(UNCUT_A_SEED) draws 600 free cells, then 600 headings.  The audit's policy (posecalls.assert_audit_clean) allows 3
 # decisions of the ambiguous classes on a tree of this size, and how many a stream has is a property of the stream -- the ORACLE's own
 # tree of the 2000 samples has 1 ambiguous accept with seed 32 and 3 with 34, but 4 with 31 and 33, one more than the policy allows
 # for any tree.  test_grow_poses_cpu.py holds the oracle's tree of this stream to the policy, without a GPU.
@@ -182,8 +184,6 @@ def planted_stream(k, seed=77):
     planted ones -- up to 8 cells of cut vertices that are free on the new map (a random stream almost never lands on one), the start's
     cell with a heading that the start pose reaches, and one obstacle cell -- at random rows.  Returns (samples (m, 3) int64, rows of the cut cells, row of the start's cell, row
     of the obstacle cell)."""
-    from rrtplanner_amd import hostprep
-
     w = k.w
     ro = w.ro
     cut = np.flatnonzero(~k.alive)
@@ -215,3 +215,18 @@ def planted_stream(k, seed=77):
             s[where[-2], 2] = h
             break
     return s, where[:-2], int(where[-2]), int(where[-1])
+
+
+@functools.lru_cache(maxsize=None)
+def planted(name):
+    """(cut workload, its planted stream, rows of the cut cells, row of the start's cell, row of the obstacle cell, the restatement's grow)"""
+    k = posekeepref.changed(name)
+    s, rows, row_start, row_ob = planted_stream(k)
+    return k, s, rows, row_start, row_ob, grow_workload(k.w, k.og8, k.alive, s)
+
+
+def more_poses(w, og8, m, seed=31):
+    """m pose samples drawn as plan() draws its n: the free cells first, then the headings"""
+    rng = np.random.default_rng(seed)
+    cells = hostprep.draw_free_samples(rng, np.argwhere(og8 == 0), m)
+    return np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), rng.integers(0, w.nh, m)])

@@ -11,7 +11,8 @@ import math
 import numpy as np
 
 import oracle
-from rrtplanner_amd import hostprep, perlin_occupancygrid
+from rrtplanner_amd import _ffi, hostprep, perlin_occupancygrid
+from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
 from rrtplanner_amd.oggen import random_connected_pair
 
 TWOPI = 2.0 * math.pi  # == DUB_TWOPI as a double
@@ -365,10 +366,22 @@ def goals_audit(w, vertex, cost):
 
 
 def assert_goals_audit_clean(a, vertex):
-    """the policy of test_dubins.py::_assert_audit_clean for the goal decisions: every answer equal to dubins_ref.c's own, or within
+    """the policy of posecalls.assert_audit_clean for the goal decisions: every answer equal to dubins_ref.c's own, or within
     the stated tolerance / ambiguity -- never plainly different -- and the tolerance classes the exception, not the rule"""
     connected = int((np.asarray(vertex) >= 0).sum())
     assert a["answer_wrong"] == 0 and a["answer_blocked"] == 0 and a["cost_mismatch"] == 0 and a["missed"] == 0 and a["phantom"] == 0, a
     assert a["first_bad_goal"] == -1 and a["max_cost_err"] < 1e-8, a
     assert a["n_connected"] == connected and a["answer_is_argmin"] + a["answer_within_tol"] == connected, a
     assert a["answer_within_tol"] + a["answer_blocked_ambiguous"] <= max(3, len(vertex) // 1000), a
+
+
+# ------------------------------------------------------------------------------------- a workload as the device and the planners take it
+def device_query(w):
+    return _ffi.make_query(_ffi.ALG_DUBINS_STAR if w.star else _ffi.ALG_DUBINS, w.n, w.xs, w.xg, w.samples, r2_rewire=w.r2, headings=w.heads,
+                           rho=w.rho, nh=w.nh)
+
+
+def planner_of(w):
+    r = SPECS[w.name][4]
+    args = (w.og, w.n) + ((r,) if w.star else ()) + (w.rho,)
+    return (RRTStarDubins if w.star else RRTDubins)(*args, n_headings=w.nh, pbar=False, seed=SPECS[w.name][7])

@@ -21,7 +21,7 @@ import numpy as np
 
 import farnn
 import oracle
-from rrtplanner_amd import hostprep
+from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pair
 
 SLAB = 64            # cells per slab of the record stream
@@ -260,3 +260,56 @@ XGEO_B = dict(W=300, H=260, gseed=6, pair=13, n=2000,
 XGEO_C = dict(W=1024, H=1024, gseed=1, pair=43, n=8000, specs=[
     dict(alg=1, rr=64, n=8000, seed=800), dict(alg=1, rr=127.5, n=8000, seed=801), dict(alg=1, rr=64, n=6000, seed=802),
     dict(alg=1, rr=127.5, n=8000, seed=803)])
+
+
+# ------------------------------------------------------------------------------------------------ the cases on a device batch
+def same_as_oracle(res, st, ro, tag, logs=True, rewire=False):
+    """the comparison of devcheck.oracle_vs_device (rewire: that of test_rewire._device_vs_oracle_rewire, which has the
+    rewire counts in place of the tree-size log and the three sums)"""
+    live = ro.j + (1 if ro.found else 0)
+    assert res.status == st and res.j == ro.j and res.found == ro.found and res.vgoal == ro.vgoal and res.i_switch == ro.i_switch, tag
+    if logs:
+        assert np.array_equal(res.nearest_log, ro.nearest_log), tag
+        assert np.array_equal(res.accept_log, ro.accept_log), tag
+        assert rewire or np.array_equal(res.j_log, ro.jlog), tag
+        assert np.array_equal(res.cbest_log, ro.cbest_log, equal_nan=True), tag
+    assert np.array_equal(res.pts[:live], ro.pts[:live]), tag
+    assert np.array_equal(res.parent[:live], ro.parent[:live]), tag
+    assert np.array_equal(res.vcost[:live], ro.vcost[:live]), tag
+    if rewire:
+        assert (res.n_rewired, res.n_propagated) == (ro.n_rewired, ro.n_propagated), tag
+    else:
+        assert res.sum_j == ro.sum_j and res.sum_cells_nn == ro.sum_cells_nn and res.sum_near == ro.sum_near, tag
+
+
+def query_of(alg, n, xs, xg, samples, r2, rg):
+    kw = {}
+    if alg == 2:
+        kw = dict(goal_d2=hostprep.goal_threshold(rg), Cmat=hostprep.rotation_to_world_frame(np.asarray(xs, dtype=np.int64), np.asarray(xg, dtype=np.int64)))
+    return _ffi.make_query(alg, n, xs, xg, samples, r2_rewire=r2, **kw)
+
+
+def hand_over_unitballs(b, qs, tag):
+    """The queries of a launched batch whose oracle run took the unit-ball hand-over (d["ub"]): each must wait at the oracle's
+    i_switch; every one gets its stream and the batch is launched again.  Returns how many there were."""
+    waiting = 0
+    for q, d in enumerate(qs):
+        if d.get("ub") is None:
+            continue
+        r = b.get_result(q, arrays=False)
+        assert r.c.status == _ffi.RRT_NEED_UNITBALL and r.c.i_switch == d["ro"].i_switch, (tag, q)
+        b.set_unitball(q, d["ub"], r.c.i_switch)
+        waiting += 1
+    if waiting:
+        b.launch()
+        b.sync()
+    return waiting
+
+
+def fill_batch(b, qs):
+    keep = []
+    for q, d in enumerate(qs):
+        qu, k = query_of(d["alg"], d["n"], d["xs"], d["xg"], d["samples"], d["r2"], d["rg"])
+        keep.append(k)
+        b.set_query(q, qu)
+    return keep

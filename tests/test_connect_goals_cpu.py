@@ -6,71 +6,58 @@ import pytest
 import goalref
 import oracle
 import orchelp
+from plannedcases import WALL64_XG, WALL64_XS, pinned_goal_cases, wall64_og, wall64_planned
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
 
-XS, XG = np.array((3, 3)), np.array((55, 40))
-
-
-def _og():
-    og = np.zeros((64, 48), dtype=np.int64)
-    og[30:33, :36] = 1
-    return og
-
-
-def _planned(n=300):
-    p = orchelp.use_oracle(amd.RRTStar(_og(), n, 12, pbar=False, seed=0))
-    T, gv = p.plan(XS, XG)
-    return p, T, gv
-
 
 def test_no_tree_before_plan_and_after_the_setters():
-    p = amd.RRTStar(_og(), 300, 12, pbar=False)
+    p = amd.RRTStar(wall64_og(), 300, 12, pbar=False)
     with pytest.raises(RuntimeError, match="plan\\(\\) first"):
         p.connect_goals([(5, 5)])
     with pytest.raises(RuntimeError, match="plan\\(\\) first"):
         p.paths_to(None, [(5, 5)])
-    for setter in (lambda p: p.set_og(_og()), lambda p: p.set_n(300)):
-        p, T, gv = _planned()
+    for setter in (lambda p: p.set_og(wall64_og()), lambda p: p.set_n(300)):
+        p, T, gv = wall64_planned()
         assert p._tree_resident == "device"
         setter(p)
         with pytest.raises(RuntimeError, match="plan\\(\\) first"):
             p.connect_goals([(5, 5)])
-        p.plan(XS, XG)
+        p.plan(WALL64_XS, WALL64_XG)
         assert p._tree_resident == "device"
 
 
 def test_no_tree_after_set_og_resident():
     from types import SimpleNamespace
 
-    p, T, gv = _planned()
+    p, T, gv = wall64_planned()
     p._ctx = object()  # (the stand-in planner has no device context of its own; set_og_resident only compares identities)
-    grids = SimpleNamespace(ctx=p._ctx, host=[_og(), _og()], select=lambda k: None)
+    grids = SimpleNamespace(ctx=p._ctx, host=[wall64_og(), wall64_og()], select=lambda k: None)
     assert p._tree_resident == "device"
     p.set_og_resident(grids, 1)
     with pytest.raises(RuntimeError, match="plan\\(\\) first"):
         p.connect_goals([(5, 5)])
-    p.plan(XS, XG)
+    p.plan(WALL64_XS, WALL64_XG)
     assert p._tree_resident == "device"
 
 
 def test_a_host_plan_that_raised_leaves_no_tree():
-    p = amd.RRTStar(_og(), 50, 12, costfn=lambda vc, pts, v, x: vc[v] + 1.0, pbar=False, rewire="correct")
+    p = amd.RRTStar(wall64_og(), 50, 12, costfn=lambda vc, pts, v, x: vc[v] + 1.0, pbar=False, rewire="correct")
     with pytest.raises(ValueError, match="rewire"):
-        p.plan(XS, XG)
+        p.plan(WALL64_XS, WALL64_XG)
     with pytest.raises(RuntimeError, match="plan\\(\\) first"):
         p.connect_goals([(5, 5)])
 
 
 def test_the_host_route_has_no_resident_tree():
-    og = _og()
+    og = wall64_og()
 
     def costfn(vcosts, points, v, x):
         return vcosts[v] + 2.0 * amd.r2norm(points[v] - x)
 
     p = amd.RRTStar(og, 120, 12, costfn=costfn, pbar=False, seed=0)
     p._costfn_provider = orchelp.NumpyProvider(oracle.og_u8(og))
-    p.plan(XS, XG)
+    p.plan(WALL64_XS, WALL64_XG)
     assert p.last_route == "host"
     with pytest.raises(ValueError, match="host route.*cost function"):
         p.connect_goals([(5, 5)])
@@ -81,7 +68,7 @@ def test_the_host_route_has_no_resident_tree():
 @pytest.mark.parametrize("cls", [RRTDubins, RRTStarDubins])
 def test_the_dubins_planners_refuse(cls):
     kw = dict(r_rewire=10) if cls is RRTStarDubins else {}
-    p = cls(_og(), 100, rho=3.0, pbar=False, **kw)
+    p = cls(wall64_og(), 100, rho=3.0, pbar=False, **kw)
     with pytest.raises(ValueError, match="Dubins"):
         p.connect_goals([(5, 5)])
     with pytest.raises(ValueError, match="Dubins"):
@@ -90,15 +77,15 @@ def test_the_dubins_planners_refuse(cls):
 
 @pytest.mark.parametrize("bad", [[1, 2, 3], [[1, 2, 3]], [[[1, 2]]], 5, [[1.5, 2.0]], [[np.nan, 2.0]], [[64, 0]], [[0, 48]], [[-1, 0]], [(5, 5), (5, 99)]])
 def test_malformed_goals(bad):
-    p, T, gv = _planned(50)
+    p, T, gv = wall64_planned(50)
     with pytest.raises(ValueError, match="goal"):
         p.connect_goals(bad)
     with pytest.raises(ValueError, match="goal"):
-        amd.RRTStar(_og(), 50, 12, pbar=False).connect_goals(bad)  # (the argument is looked at first)
+        amd.RRTStar(wall64_og(), 50, 12, pbar=False).connect_goals(bad)  # (the argument is looked at first)
 
 
 def test_goal_arrays_that_are_taken():
-    p, T, gv = _planned(50)
+    p, T, gv = wall64_planned(50)
     seen = []
     p._device = lambda: type("Ctx", (), {"connect_goals": staticmethod(lambda g: seen.append(g) or (np.zeros(len(g), np.int32), np.zeros(len(g))))})
     for goals, m in (((5, 5), 1), ([[5.0, 6.0]], 1), (np.zeros((0, 2), dtype=int), 0), (np.array([[63, 47], [0, 0]], dtype=np.uint16), 2)):
@@ -139,18 +126,7 @@ def test_paths_to_walks_the_parents_of_a_golden_tree(monkeypatch):
         assert paths[3].tolist() == want[::-1] and paths[3].dtype == np.int64
 
 
-def _pinned_cases():
-    """three goldens of different grids and planners whose goal was connected"""
-    G = orchelp.golden("plans_A.npz")
-    seen, out = set(), []
-    for m in sorted(G.manifest, key=lambda m: -m["n"]):
-        if m["alg"] in (0, 1) and m.get("rows") == m["n"] + 1 and m["vgoal"] > 50 and (m["grid"], m["alg"]) not in seen and m["grid"] != "empty43x100":
-            seen.add((m["grid"], m["alg"]))
-            out.append(m["id"])
-    return out[:3]
-
-
-@pytest.mark.parametrize("cid", _pinned_cases())
+@pytest.mark.parametrize("cid", pinned_goal_cases())
 def test_the_host_check_reproduces_the_references_goal_row(cid):
     """goalref.connect_one on the golden tree before its goal row gives the row the reference appended: (parent, cost)"""
     G = orchelp.golden("plans_A.npz")
@@ -168,4 +144,4 @@ def test_the_host_check_reproduces_the_references_goal_row(cid):
 
 
 def test_pinned_cases_exist():
-    assert len(_pinned_cases()) == 3
+    assert len(pinned_goal_cases()) == 3

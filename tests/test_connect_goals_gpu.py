@@ -11,35 +11,12 @@ import oracle
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTStarDubins
+from treecalls import free_goals, free_samples, plan_on_own_batch, refused_with_word, same_snapshot, snapshot, wall_map
 
 pytestmark = pytest.mark.gpu
 
 TPB = 1024  # threads of the workgroup that decides a goal (rrt_kernel_abi.h)
 INF = np.inf
-
-
-def _wall_map(W=200, H=160):
-    """two walls across the map, each with a gap at one end, and a closed box"""
-    og = np.zeros((W, H), dtype=np.int64)
-    og[W // 3:W // 3 + 4, :H * 3 // 4] = 1
-    og[2 * W // 3:2 * W // 3 + 3, H // 4:] = 1
-    og[20:41, 120:141] = 1
-    og[22:39, 122:139] = 0  # the inside of the box is free and closed
-    return og
-
-
-def _samples(og, n, seed):
-    return hostprep.draw_free_samples(np.random.default_rng(seed), np.argwhere(og == 0), n)
-
-
-def _grow(ctx, alg, n, xs, xg, samples, r2=0, goal_d2=0, Cmat=None, **bkw):
-    """one query on a batch of its own, launched and synchronised: (batch, result)"""
-    b = _ffi.Batch(ctx, 1, n, **bkw)
-    q, keep = _ffi.make_query(alg, n, xs, xg, samples, r2_rewire=r2, goal_d2=goal_d2, Cmat=Cmat)
-    b.set_query(0, q)
-    b.launch()
-    b.sync()
-    return b, b.get_result(0)
 
 
 def _check_rows(og8, res, goals, vertex, cost):
@@ -49,15 +26,10 @@ def _check_rows(og8, res, goals, vertex, cost):
     return rv, rc, tried
 
 
-def _free_goals(og, m, seed):
-    free = np.argwhere(og == 0)
-    return free[np.random.default_rng(seed).integers(0, len(free), size=m)]
-
-
 # ------------------------------------------------------------------------------------------------ against plan() and the oracle
 @pytest.mark.parametrize("kind", ["std", "star", "informed"])
 def test_the_planners_own_goal_gets_the_parent_and_cost_plan_gave_it(kind):
-    og = _wall_map()
+    og = wall_map()
     xs, xg = np.array((5, 5)), np.array((190, 150))
     p = {"std": lambda: amd.RRTStandard(og, 2000, pbar=False, seed=1), "star": lambda: amd.RRTStar(og, 2000, 30, pbar=False, seed=1),
          "informed": lambda: amd.RRTStarInformed(og, 2000, 30, 25, pbar=False, seed=1)}[kind]()
@@ -75,16 +47,16 @@ def test_the_planners_own_goal_gets_the_parent_and_cost_plan_gave_it(kind):
 def test_other_goals_get_what_a_plan_towards_them_would_have_given(kind):
     """RRTStandard / RRTStar grow the same tree whatever the goal: oracle.plan on the same samples towards g_k connects g_k as
     row k of ONE connect_goals call on the tree grown towards another goal"""
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     n, seed, xs = 2000, 2, (5, 5)
     alg, kw = (0, {}) if kind == "std" else (1, dict(r_rewire=30))
     r2 = hostprep.radius_threshold(30) if alg else 0
-    goals = np.concatenate([_free_goals(og, 10, 3), [[30, 130], [100, 100]]])  # ... one in the closed box, one anywhere
+    goals = np.concatenate([free_goals(og, 10, 3), [[30, 130], [100, 100]]])  # ... one in the closed box, one anywhere
     p = (amd.RRTStar if alg else amd.RRTStandard)(og, n, pbar=False, seed=seed, **kw)
     p.plan(np.array(xs), np.array((190, 150)))
     vertex, cost = p.connect_goals(goals)
-    samples = _samples(og, n, seed)
+    samples = free_samples(og, n, seed)
     connected = 0
     for k, g in enumerate(goals):
         st, ro = oracle.plan(og8, n, alg, xs, g, samples, r2_rewire=r2, logs=False)
@@ -99,11 +71,11 @@ def test_other_goals_get_what_a_plan_towards_them_would_have_given(kind):
 # ------------------------------------------------------------------------------------------------ the kernel's own paths
 def test_more_goals_than_workgroups(gpu_ctx):
     """1500 goals on at most 512 workgroups: every workgroup decides several, reusing its slab and its LDS tables"""
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 1, 600, (5, 5), (190, 150), _samples(og, 600, 4), r2=hostprep.radius_threshold(30))
-    goals = np.concatenate([_free_goals(og, 1480, 5), np.argwhere(og != 0)[::45][:20]])
+    b, res = plan_on_own_batch(gpu_ctx, 1, 600, (5, 5), (190, 150), free_samples(og, 600, 4), r2=hostprep.radius_threshold(30))
+    goals = np.concatenate([free_goals(og, 1480, 5), np.argwhere(og != 0)[::45][:20]])
     assert len(goals) == 1500
     vertex, cost = b.connect_goals(0, goals)
     rv, rc, tried = _check_rows(og8, res, goals, vertex, cost)
@@ -118,7 +90,7 @@ def test_goals_whose_cheapest_vertex_is_behind_a_wall(gpu_ctx):
     og[100:104, :130] = 1
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 1, 2000, (10, 20), (190, 20), _samples(og, 2000, 6), r2=hostprep.radius_threshold(30))
+    b, res = plan_on_own_batch(gpu_ctx, 1, 2000, (10, 20), (190, 20), free_samples(og, 2000, 6), r2=hostprep.radius_threshold(30))
     behind = np.array([(106, y) for y in range(10, 100, 3)])
     open_ = np.array([(60, y) for y in range(10, 150, 5)])
     vertex, cost = b.connect_goals(0, np.concatenate([behind, open_]))
@@ -129,10 +101,10 @@ def test_goals_whose_cheapest_vertex_is_behind_a_wall(gpu_ctx):
 
 
 def test_unreachable_goals_get_minus_one_and_inf(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 1, 600, (5, 5), (190, 150), _samples(og, 600, 4), r2=hostprep.radius_threshold(30))
+    b, res = plan_on_own_batch(gpu_ctx, 1, 600, (5, 5), (190, 150), free_samples(og, 600, 4), r2=hostprep.radius_threshold(30))
     goals = np.array([(67, 10), (20, 120), (30, 130), (25, 125), (150, 150)])  # on a wall, on the box, two in the box, one free
     assert og[67, 10] == 1 and og[20, 120] == 1 and og[30, 130] == 0
     vertex, cost = b.connect_goals(0, goals)
@@ -140,16 +112,16 @@ def test_unreachable_goals_get_minus_one_and_inf(gpu_ctx):
     assert vertex[:4].tolist() == [-1] * 4 and np.all(cost[:4] == INF) and vertex[4] >= 0 and np.isfinite(cost[4])
     b.close()
     # a tree of the start alone (n = 1: j == 1) and a goal it does not see
-    b, res = _grow(gpu_ctx, 0, 1, (5, 5), (190, 150), np.array([[6, 6]]))
+    b, res = plan_on_own_batch(gpu_ctx, 0, 1, (5, 5), (190, 150), np.array([[6, 6]]))
     assert res.j == 1
     vertex, cost = b.connect_goals(0, [(150, 10), (10, 100)])
     _check_rows(og8, res, [(150, 10), (10, 100)], vertex, cost)
     assert vertex.tolist() == [-1, 0] and cost[0] == INF
     b.close()
     # xstart on an obstacle: nothing is ever accepted, and the start sees nothing
-    samples = _samples(og, 50, 7)
+    samples = free_samples(og, 50, 7)
     st, ro = oracle.plan(og8, 50, 1, (67, 10), (190, 150), samples, r2_rewire=900, logs=False)
-    b, res = _grow(gpu_ctx, 1, 50, (67, 10), (190, 150), samples, r2=900)
+    b, res = plan_on_own_batch(gpu_ctx, 1, 50, (67, 10), (190, 150), samples, r2=900)
     assert res.j == ro.j == 1 and not ro.found
     vertex, cost = b.connect_goals(0, [(60, 10), (150, 150)])
     assert vertex.tolist() == [-1, -1] and np.all(cost == INF)
@@ -161,7 +133,7 @@ def _tie_query(ctx, first, fillers, last):
     accepted.  Returns (batch, result, {cell: vertex})"""
     cells = list(first) + [(k, 5) for k in range(fillers)] + list(last)
     samples = np.array(cells + [(0, 0)])  # (one more, rejected: the tree is full)
-    b, res = _grow(ctx, 0, len(samples), (50, 50), (99, 99), samples)
+    b, res = plan_on_own_batch(ctx, 0, len(samples), (50, 50), (99, 99), samples)
     assert res.j == len(cells) + 1
     pts = [tuple(p) for p in res.pts[:res.j].tolist()]
     return b, res, {c: pts.index(c) for c in cells}
@@ -207,7 +179,7 @@ def test_tree_sizes_around_the_strides(gpu_ctx, j):
     gpu_ctx.set_grid(og8)
     cells = np.array([(x, y) for x in range(60) for y in range(96) if (x, y) != (0, 0)])
     samples = cells[np.random.default_rng(j).permutation(len(cells))[:j]]
-    b, res = _grow(gpu_ctx, 1, j, (0, 0), (120, 90), samples, r2=hostprep.radius_threshold(12))
+    b, res = plan_on_own_batch(gpu_ctx, 1, j, (0, 0), (120, 90), samples, r2=hostprep.radius_threshold(12))
     assert res.j == j
     goals = [(76, 5), (76, 40), (100, 70), (127, 0), (80, 90), (65, 50), (71, 10), (127, 95)]
     vertex, cost = b.connect_goals(0, goals)
@@ -219,14 +191,14 @@ def test_tree_sizes_around_the_strides(gpu_ctx, j):
 
 
 def test_every_way_a_tree_is_grown(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    n, samples, r2 = 2500, _samples(og, 2500, 8), hostprep.radius_threshold(25)
-    goals = _free_goals(og, 40, 9)
+    n, samples, r2 = 2500, free_samples(og, 2500, 8), hostprep.radius_threshold(25)
+    goals = free_goals(og, 40, 9)
     got, names = [], []
     for bkw in (dict(), dict(team=1), dict(serial=True)):
-        b, res = _grow(gpu_ctx, 1, n, (5, 5), (190, 150), samples, r2=r2, **bkw)
+        b, res = plan_on_own_batch(gpu_ctx, 1, n, (5, 5), (190, 150), samples, r2=r2, **bkw)
         names.append(b.kernel_name())
         got.append(b.connect_goals(0, goals))
         if not bkw:
@@ -238,19 +210,19 @@ def test_every_way_a_tree_is_grown(gpu_ctx):
 
 
 def test_a_batch_of_three_queries_with_different_n(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     ns = [300, 5000, 1200]
     b = _ffi.Batch(gpu_ctx, 3, max(ns))
     keeps = []
     for q, n in enumerate(ns):
-        qu, keep = _ffi.make_query(1, n, (5 + q, 5), (190, 150 - q), _samples(og, n, 10 + q), r2_rewire=hostprep.radius_threshold(25))
+        qu, keep = _ffi.make_query(1, n, (5 + q, 5), (190, 150 - q), free_samples(og, n, 10 + q), r2_rewire=hostprep.radius_threshold(25))
         keeps.append(keep)
         b.set_query(q, qu)
     b.launch()
     b.sync()
-    goals = _free_goals(og, 30, 13)
+    goals = free_goals(og, 30, 13)
     for q in (2, 0):
         res = b.get_result(q)
         assert res.pts[0].tolist() == [5 + q, 5]
@@ -266,7 +238,7 @@ def test_large_grid_batch_and_planner():
     og8 = oracle.og_u8(og)
     ctx = _ffi.Context(0)
     ctx.set_grid(og8)
-    b, res = _grow(ctx, 1, 400, (1, 1), (4090, 6), _samples(og, 400, 14), r2=hostprep.radius_threshold(500), large_grid=True)
+    b, res = plan_on_own_batch(ctx, 1, 400, (1, 1), (4090, 6), free_samples(og, 400, 14), r2=hostprep.radius_threshold(500), large_grid=True)
     assert b.kernel_name() == "rrt_pipe_large_kernel" and res.j > 100
     goals = [(0, 0), (4095, 7), (4095, 0), (0, 7), (2004, 2), (1999, 3), (2001, 3), (3000, 4)]
     rv, rc, tried = _check_rows(og8, res, goals, *b.connect_goals(0, goals))
@@ -284,29 +256,20 @@ def test_large_grid_batch_and_planner():
 
 
 # ------------------------------------------------------------------------------------------------ the batch afterwards
-def _snapshot(res):
-    live = res.j + (1 if res.found else 0)
-    return (res.status, res.j, res.vgoal, res.found, res.sum_j, res.sum_near, res.pts[:live].copy(), res.parent[:live].copy(), res.vcost[:live].copy())
-
-
-def _same_snapshot(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
 def test_the_batch_is_left_as_it_was(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     gpu_ctx.set_grid(oracle.og_u8(og))
-    b, res = _grow(gpu_ctx, 1, 3000, (5, 5), (190, 150), _samples(og, 3000, 15), r2=hostprep.radius_threshold(25))
-    before = _snapshot(res)
-    goals = _free_goals(og, 700, 16)
+    b, res = plan_on_own_batch(gpu_ctx, 1, 3000, (5, 5), (190, 150), free_samples(og, 3000, 15), r2=hostprep.radius_threshold(25))
+    before = snapshot(res)
+    goals = free_goals(og, 700, 16)
     first = b.connect_goals(0, goals)
-    assert _same_snapshot(before, _snapshot(b.get_result(0)))
+    assert same_snapshot(before, snapshot(b.get_result(0)))
     second = b.connect_goals(0, goals)
     assert np.array_equal(first[0], second[0]) and np.array_equal(first[1], second[1])
     b.rearm()
     b.launch()
     b.sync()
-    assert _same_snapshot(before, _snapshot(b.get_result(0)))
+    assert same_snapshot(before, snapshot(b.get_result(0)))
     third = b.connect_goals(0, goals[:5])  # (and fewer goals than before)
     assert np.array_equal(first[0][:5], third[0]) and np.array_equal(first[1][:5], third[1])
     v0, c0 = b.connect_goals(0, np.zeros((0, 2), dtype=np.int64))
@@ -314,47 +277,41 @@ def test_the_batch_is_left_as_it_was(gpu_ctx):
     b.close()
 
 
-def _refused(code, word, fn, *args):
-    with pytest.raises(_ffi.RRTError) as e:
-        fn(*args)
-    assert e.value.code == code and word in str(e.value), str(e.value)
-
-
 def test_refusals():
     ctx = _ffi.Context(0)
-    og = _wall_map()
+    og = wall_map()
     ctx.set_grid(oracle.og_u8(og))
-    _refused(_ffi.RRT_E_ARG, "no rrt_plan", ctx.connect_goals, [(5, 5)])
-    samples = _samples(og, 500, 17)
+    refused_with_word(_ffi.RRT_E_ARG, "no rrt_plan", ctx.connect_goals, [(5, 5)])
+    samples = free_samples(og, 500, 17)
     b = _ffi.Batch(ctx, 2, 500)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.connect_goals, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.connect_goals, 0, [(5, 5)])
     q, keep = _ffi.make_query(1, 500, (5, 5), (190, 150), samples, r2_rewire=900)
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.connect_goals, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "not launched", b.connect_goals, 0, [(5, 5)])
     b.launch()
     b.sync()
     b.connect_goals(0, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "q=2", b.connect_goals, 2, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "q=-1", b.connect_goals, -1, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "no query set", b.connect_goals, 1, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "outside", b.connect_goals, 0, [(5, 5), (200, 5)])
-    _refused(_ffi.RRT_E_ARG, "outside", b.connect_goals, 0, [(5, -1)])
-    _refused(_ffi.RRT_E_ARG, "at most", b.connect_goals, 0, np.zeros(((1 << 20) + 1, 2), dtype=np.int32))
+    refused_with_word(_ffi.RRT_E_ARG, "q=2", b.connect_goals, 2, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "q=-1", b.connect_goals, -1, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.connect_goals, 1, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.connect_goals, 0, [(5, 5), (200, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.connect_goals, 0, [(5, -1)])
+    refused_with_word(_ffi.RRT_E_ARG, "at most", b.connect_goals, 0, np.zeros(((1 << 20) + 1, 2), dtype=np.int32))
     b.rearm()
-    _refused(_ffi.RRT_E_ARG, "not finished", b.connect_goals, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.connect_goals, 0, [(5, 5)])
     b.launch()
     b.sync()
     want = b.connect_goals(0, [(150, 150)])
     # the grid replaced between run and call: same shape, another generation
     ctx.set_grid(oracle.og_u8(og))
-    _refused(_ffi.RRT_E_ARG, "replaced", b.connect_goals, 0, [(150, 150)])
+    refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_goals, 0, [(150, 150)])
     b.rearm()
     b.launch()
     b.sync()
     got = b.connect_goals(0, [(150, 150)])
     assert got[0][0] == want[0][0] and got[1][0] == want[1][0]
     ctx.set_grid(np.zeros((64, 64), dtype=np.uint8))
-    _refused(_ffi.RRT_E_ARG, "shape", b.connect_goals, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "shape", b.connect_goals, 0, [(5, 5)])
     b.close()
     # an Informed query that reached the goal region waits for its unit ball
     b = _ffi.Batch(ctx, 1, 300)
@@ -365,7 +322,7 @@ def test_refusals():
     b.launch()
     b.sync()
     assert b.get_result(0).status == _ffi.RRT_NEED_UNITBALL
-    _refused(_ffi.RRT_E_ARG, "unit-ball", b.connect_goals, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "unit-ball", b.connect_goals, 0, [(5, 5)])
     b.close()
     # a Dubins batch
     hd = np.random.default_rng(19).integers(0, 16, size=300)
@@ -374,7 +331,7 @@ def test_refusals():
     b.set_query(0, q)
     b.launch()
     b.sync()
-    _refused(_ffi.RRT_E_UNSUPPORTED, "Dubins", b.connect_goals, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "Dubins", b.connect_goals, 0, [(5, 5)])
     b.close()
     ctx.close()
     with pytest.raises(ValueError, match="Dubins"):
@@ -383,12 +340,12 @@ def test_refusals():
 
 # ------------------------------------------------------------------------------------------------ paths
 def test_paths_to():
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     xs = np.array((5, 5))
     p = amd.RRTStandard(og, 2500, pbar=False, seed=20)
     T, gv = p.plan(xs, np.array((190, 150)))
-    goals = np.concatenate([_free_goals(og, 25, 21), [[30, 130], [67, 10]]])
+    goals = np.concatenate([free_goals(og, 25, 21), [[30, 130], [67, 10]]])
     vertex, cost = p.connect_goals(goals)
     paths = p.paths_to(T, goals)
     assert len(paths) == len(goals) and [pt is None for pt in paths] == (vertex < 0).tolist()

@@ -12,31 +12,14 @@ import oracle
 import poseref
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
+from posecalls import planned_batch_and_result
 from rrtplanner_amd.oggen import DeviceGrids
+from treecalls import refused_with_word, same_snapshot, snapshot
 
 pytestmark = pytest.mark.gpu
 
 MAX_WORKGROUPS = 512  # POSES_MAX_SLABS of rrt_kernel_abi.h: the workgroups of one launch, each deciding goals g, g + 512, ...
 INF = np.inf
-
-
-def _query(w):
-    return _ffi.make_query(_ffi.ALG_DUBINS_STAR if w.star else _ffi.ALG_DUBINS, w.n, w.xs, w.xg, w.samples, r2_rewire=w.r2, headings=w.heads,
-                           rho=w.rho, nh=w.nh)
-
-
-def _run(ctx, w):
-    """workload w on a batch of its own, launched and synchronised, its tree the oracle's: (batch, result)"""
-    ctx.set_grid(w.og8)
-    b = _ffi.Batch(ctx, 1, w.n, dubins=True)
-    q, keep = _query(w)
-    b.set_query(0, q)
-    b.launch()
-    b.sync()
-    res = b.get_result(0)
-    assert res.status == w.status and res.j == w.j
-    assert np.array_equal(res.vcost[:w.j], w.ro.vcost[:w.j]) and np.array_equal(res.head[:w.j], w.ro.head[:w.j])
-    return b, res
 
 
 def _same(got, w, rows=slice(None)):
@@ -51,7 +34,7 @@ def _same(got, w, rows=slice(None)):
 def test_workloads_against_the_restatement(gpu_ctx, name):
     w = poseref.workload(name)
     poseref.check_conditions(w)
-    b, res = _run(gpu_ctx, w)
+    b, res = planned_batch_and_result(gpu_ctx, w)
     _same(b.connect_poses(0, w.goals), w)
     words, sweeps = b.connect_poses_counts()
     swept = w.rank[w.vertex >= 0] + 1
@@ -66,7 +49,7 @@ def test_more_goals_than_workgroups_and_scratch_that_grows(gpu_ctx):
     w = poseref.workload("E", 700 - 4)
     assert len(w.goals) == 700 > MAX_WORKGROUPS
     poseref.check_conditions(w)
-    b, res = _run(gpu_ctx, w)
+    b, res = planned_batch_and_result(gpu_ctx, w)
     _same(b.connect_poses(0, w.goals[:5]), w, slice(0, 5))
     _same(b.connect_poses(0, w.goals), w)
     _same(b.connect_poses(0, w.goals[-5:]), w, slice(695, 700))
@@ -109,7 +92,7 @@ def test_a_batch_of_three_queries_each_with_its_own_rho_headings_and_tree(gpu_ct
 # ------------------------------------------------------------------------------------------------ the counters
 def test_counts_of_single_goals(gpu_ctx):
     w = poseref.workload("B")
-    b, res = _run(gpu_ctx, w)
+    b, res = planned_batch_and_result(gpu_ctx, w)
     with pytest.raises(_ffi.RRTError) as e:
         b.connect_poses_counts()
     assert e.value.code == _ffi.RRT_E_ARG
@@ -173,34 +156,18 @@ SEEDS = {name: spec[7] for name, spec in poseref.SPECS.items()}
 
 
 # ------------------------------------------------------------------------------------------------ the batch afterwards
-def _snapshot(res):
-    live = res.j + (1 if res.found else 0)
-    return (res.status, res.j, res.vgoal, res.found, res.sum_j, res.sum_near, res.pts[:live].copy(), res.head[:live].copy(), res.parent[:live].copy(),
-            res.vcost[:live].copy())
-
-
-def _same_snapshot(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def _refused(code, word, fn, *args):
-    with pytest.raises(_ffi.RRTError) as e:
-        fn(*args)
-    assert e.value.code == code and word in str(e.value), str(e.value)
-
-
 def test_the_batch_is_left_as_it_was(gpu_ctx):
     w = poseref.workload("A")
-    b, res = _run(gpu_ctx, w)
-    before = _snapshot(res)
+    b, res = planned_batch_and_result(gpu_ctx, w)
+    before = snapshot(res)
     _same(b.connect_poses(0, w.goals), w)
-    assert _same_snapshot(before, _snapshot(b.get_result(0)))
+    assert same_snapshot(before, snapshot(b.get_result(0)))
     b.rearm()
-    _refused(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)  # until the query has finished again
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)  # until the query has finished again
     b.launch()
-    _refused(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)
     b.sync()
-    assert _same_snapshot(before, _snapshot(b.get_result(0)))
+    assert same_snapshot(before, snapshot(b.get_result(0)))
     _same(b.connect_poses(0, w.goals), w)
     b.close()
 
@@ -211,24 +178,24 @@ def test_refusals():
     ctx.set_grid(w.og8)
     W, H = w.og8.shape
     ok = [(5, 5, 0)]
-    _refused(_ffi.RRT_E_ARG, "no rrt_plan", ctx.connect_poses, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "no rrt_plan", ctx.connect_poses, ok)
     b = _ffi.Batch(ctx, 2, w.n, dubins=True)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.connect_poses, 0, ok)
-    q, keep = _query(w)
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.connect_poses, 0, ok)
+    q, keep = poseref.device_query(w)
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.connect_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "not launched", b.connect_poses, 0, ok)
     b.launch()
     b.sync()
     want = b.connect_poses(0, w.goals[:3])
     _same(want, w, slice(0, 3))
-    _refused(_ffi.RRT_E_ARG, "q=2", b.connect_poses, 2, ok)
-    _refused(_ffi.RRT_E_ARG, "q=-1", b.connect_poses, -1, ok)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.connect_poses, 1, ok)
-    _refused(_ffi.RRT_E_ARG, "outside", b.connect_poses, 0, [(5, 5, 0), (W, 5, 0)])
-    _refused(_ffi.RRT_E_ARG, "outside", b.connect_poses, 0, [(5, -1, 0)])
-    _refused(_ffi.RRT_E_ARG, "heading", b.connect_poses, 0, [(5, 5, w.nh)])
-    _refused(_ffi.RRT_E_ARG, "heading", b.connect_poses, 0, [(5, 5, 0), (5, 5, -1)])  # the C ABI takes concrete headings only
-    _refused(_ffi.RRT_E_ARG, "at most", b.connect_poses, 0, np.zeros(((1 << 20) + 1, 3), dtype=np.int32))
+    refused_with_word(_ffi.RRT_E_ARG, "q=2", b.connect_poses, 2, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "q=-1", b.connect_poses, -1, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.connect_poses, 1, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.connect_poses, 0, [(5, 5, 0), (W, 5, 0)])
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.connect_poses, 0, [(5, -1, 0)])
+    refused_with_word(_ffi.RRT_E_ARG, "heading", b.connect_poses, 0, [(5, 5, w.nh)])
+    refused_with_word(_ffi.RRT_E_ARG, "heading", b.connect_poses, 0, [(5, 5, 0), (5, 5, -1)])  # the C ABI takes concrete headings only
+    refused_with_word(_ffi.RRT_E_ARG, "at most", b.connect_poses, 0, np.zeros(((1 << 20) + 1, 3), dtype=np.int32))
     lib = _ffi.lib()
     v, c, g = np.zeros(1, dtype=np.int32), np.zeros(1), np.zeros((1, 3), dtype=np.int32)
     assert lib.rrt_batch_connect_poses(b._h, 0, None, 1, v.ctypes.data, c.ctypes.data) == _ffi.RRT_E_ARG
@@ -241,13 +208,13 @@ def test_refusals():
     assert b.connect_poses_counts()[1] >= int((w.rank[:3] + 1)[w.vertex[:3] >= 0].sum())
     # the grid replaced between run and call: same shape, another generation
     ctx.set_grid(w.og8)
-    _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, ok)
     b.rearm()
     b.launch()
     b.sync()
     _same(b.connect_poses(0, w.goals[:3]), w, slice(0, 3))
     ctx.set_grid(np.zeros((W + 8, H), dtype=np.uint8))
-    _refused(_ffi.RRT_E_ARG, "shape", b.connect_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_ARG, "shape", b.connect_poses, 0, ok)
     b.close()
     # a batch of a straight-line planner: its call is connect_goals
     ctx.set_grid(w.og8)
@@ -256,7 +223,7 @@ def test_refusals():
     b.set_query(0, q)
     b.launch()
     b.sync()
-    _refused(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_connect_goals", b.connect_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_connect_goals", b.connect_poses, 0, ok)
     b.connect_goals(0, [(5, 5)])
     b.close()
     ctx.close()
@@ -267,7 +234,7 @@ def test_a_tree_whose_own_goal_is_unreachable_is_accepted():
     w = poseref.workload("F")
     ctx = _ffi.Context(0)
     ctx.set_grid(w.og8)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     rc, res = ctx.plan(q, w.n)
     assert rc == _ffi.RRT_E_GOAL_UNREACHABLE and res.j == 1
     vertex, cost = ctx.connect_poses(w.goals)
@@ -280,7 +247,7 @@ def _goal_row_of_plan(ctx, w):
     """the query through rrt_plan, both kernels: the tree and the goal row (go2goal_phase<true>'s decision) are the oracle's"""
     ctx.set_grid(w.og8)
     for serial in (False, True):
-        q, keep = _query(w)
+        q, keep = poseref.device_query(w)
         rc, res = ctx.plan(q, w.n, serial=serial)
         ro = w.ro
         live = ro.j + (1 if ro.found else 0)
@@ -292,7 +259,7 @@ def _goal_row_of_plan(ctx, w):
 
 def _asked_twice(ctx, w):
     """the order inside a bucket may differ between launches, the answer may not"""
-    b, res = _run(ctx, w)
+    b, res = planned_batch_and_result(ctx, w)
     first = b.connect_poses(0, w.goals)
     _same(first, w)
     _same(b.connect_poses(0, w.goals), w)
@@ -344,7 +311,7 @@ def test_tree_sizes_around_the_strides(gpu_ctx, j):
     for star in (0, 1):
         w = poseref.stride_tree(j, star)
         poseref.check_stride_tree(w, j)
-        b, res = _run(gpu_ctx, w)
+        b, res = planned_batch_and_result(gpu_ctx, w)
         _same(b.connect_poses(0, w.goals), w)
         for g, goal in enumerate(w.goals):  # asked alone: what the counters must say follows from the semantics
             _same(b.connect_poses(0, goal), w, slice(g, g + 1))
@@ -365,7 +332,7 @@ def test_pose_goals_fuzz_small(gpu_ctx):
     for w in cases:
         try:
             gpu_ctx.set_grid(w.og8)
-            q, keep = _query(w)
+            q, keep = poseref.device_query(w)
             rc, res = gpu_ctx.plan(q, w.n, logs=True, serial=w.serial)
             ro = w.ro
             live = ro.j + (1 if ro.found else 0)
@@ -383,7 +350,7 @@ def test_pose_goals_fuzz_small(gpu_ctx):
 
 # ------------------------------------------------------------------------------------------------ the independent audit
 def _audit_of_the_devices_answers(ctx, w):
-    b, res = _run(ctx, w)
+    b, res = planned_batch_and_result(ctx, w)
     vertex, cost = b.connect_poses(0, w.goals)
     b.close()
     a = poseref.goals_audit(w, vertex, cost)
@@ -421,7 +388,7 @@ def test_a_tree_of_one_resident_frame_is_refused_on_the_other(gpu_ctx):
     grids.select(0)
     generation = gpu_ctx.grid_generation()
     b = _ffi.Batch(gpu_ctx, 1, n, dubins=True)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     b.set_query(0, q)
     b.launch()
     b.sync()
@@ -429,7 +396,7 @@ def test_a_tree_of_one_resident_frame_is_refused_on_the_other(gpu_ctx):
     _same(b.connect_poses(0, w.goals), w)
     counts = b.connect_poses_counts()
     grids.select(1)
-    _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, w.goals)
+    refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, w.goals)
     assert gpu_ctx.grid_generation() == generation and b.connect_poses_counts() == counts  # (the refused call ran nothing)
     grids.select(0)
     _same(b.connect_poses(0, w.goals), w)  # the tree is still there: no new launch of the query

@@ -13,6 +13,7 @@ import pytest
 
 import oracle
 import orchelp
+from posecalls import assert_audit_clean, check_dubins_tree, device_vs_oracle_dubins, independent_collision_witness
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import dubins as dub
 from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pair
@@ -101,66 +102,12 @@ def _dub_query(grid, n, seed, gseed=1):
     return og, og8, (int(xs[0]), int(xs[1]), 5), (int(xg[0]), int(xg[1]), 20), samples, heads
 
 
-def _independent_sweep(og8, a, b, rho, nh):
-    """The collision sweep of the edge a -> b WITHOUT include/rrt_dubins.h: the polyline of rrtplanner_amd/dubins.py (numpy /
-    libm, its own word construction) sampled every DUB_DS = 0.5 cells of arc length, a sample occupying the cell round-half-up
-    of its coordinates.  Returns (blocked, ambiguous) per sample: blocked = outside the grid or on an obstacle; ambiguous = a
-    coordinate within 1e-7 of a cell boundary (libm and the fixed-order arithmetic may then name neighbouring cells)."""
-    f = dub.dubins_polyline(a, b, rho, nh, ds=0.5) + 0.5
-    cells = np.floor(f).astype(np.int64)
-    amb = np.abs(f - np.round(f)).min(axis=1) < 1e-7
-    inside = (cells[:, 0] >= 0) & (cells[:, 0] < og8.shape[0]) & (cells[:, 1] >= 0) & (cells[:, 1] < og8.shape[1])
-    blocked = ~inside
-    blocked[inside] = og8[cells[inside, 0], cells[inside, 1]] != 0
-    return blocked, amb
-
-
-def _independent_collision_witness(og8, res, samples, heads, rho, nh, count=300):
-    """The device's collision DECISIONS against the independent sweep above (the oracle shares the kernel's geometry header, so
-    HIP == oracle says nothing about a wrong formula in it): every edge of the device's tree is free, and every iteration the
-    device rejected although its cell was new has a blocked (or boundary-ambiguous) sample on the word nearest -> sample."""
-    live = res.j + (1 if res.found else 0)
-    par, pts, hd = res.parent[:live].astype(np.int64), res.pts[:live].astype(np.int64), res.head[:live].astype(np.int64)
-    for c in range(1, live, max(1, live // count)):
-        p = par[c]
-        blocked, amb = _independent_sweep(og8, (pts[p, 0], pts[p, 1], hd[p]), (pts[c, 0], pts[c, 1], hd[c]), rho, nh)
-        assert not np.any(blocked & ~amb), f"edge {p} -> {c} of the device's tree crosses an obstacle"
-    first_index = {}
-    for k in range(res.j - 1, 0, -1):
-        first_index[(int(pts[k, 0]), int(pts[k, 1]))] = k
-    rej = np.flatnonzero(res.accept_log == 0)
-    seen = 0
-    for i in rej[:: max(1, rej.size // count)]:
-        x, y, h, jtop = int(samples[i, 0]), int(samples[i, 1]), int(heads[i]), int(res.j_log[i])
-        if first_index.get((x, y), jtop) < jtop or jtop >= res.n:
-            continue  # rejected as a duplicate of an earlier vertex (rrt.py:425) or because the tree is full
-        v = int(res.nearest_log[i])
-        blocked, amb = _independent_sweep(og8, (pts[v, 0], pts[v, 1], hd[v]), (x, y, h), rho, nh)
-        assert np.any(blocked | amb), f"iteration {i}: rejected, but the word from vertex {v} to the sample is free"
-        seen += 1
-    return seen
-
-
-def _check_dubins_tree(og8, r, rho, nh, xs):
-    live = r.j + (1 if r.found else 0)
-    par, pts, hd = r.parent[:live].astype(np.int64), r.pts[:live].astype(np.int64), r.head[:live].astype(np.int64)
-    assert par[0] == -1 and np.all(par[1:] >= 0) and np.all(par[1:] < np.arange(1, live)) and (pts[0, 0], pts[0, 1], hd[0]) == tuple(xs)
-    assert np.all(og8[pts[:, 0], pts[:, 1]] == 0) and np.all((0 <= hd) & (hd < nh))
-    assert len({(a, b) for a, b in pts[:r.j].tolist()}) >= r.j - 1  # one node per cell (xstart may repeat once, rrt.py:425)
-    L = dub.dubins_shortest(pts[par[1:], 0], pts[par[1:], 1], 2 * math.pi * hd[par[1:]] / nh, pts[1:, 0], pts[1:, 1], 2 * math.pi * hd[1:] / nh, rho)[3]
-    assert np.allclose(r.vcost[1:live], r.vcost[par[1:]] + L, rtol=0, atol=1e-8)
-    for c in range(1, live, max(1, live // 300)):  # every edge's sweep is free
-        p = par[c]
-        cells = oracle.dub_sweep_cells(pts[p, 0], pts[p, 1], 2 * math.pi * hd[p] / nh, pts[c, 0], pts[c, 1], 2 * math.pi * hd[c] / nh, rho)
-        assert np.all((cells >= 0) & (cells < og8.shape[0])) and np.all(og8[cells[:, 0], cells[:, 1]] == 0)
-
-
 @pytest.mark.parametrize("star", [0, 1])
 def test_oracle_dubins_plan_properties(star):
     og, og8, xs, xg, samples, heads = _dub_query(300, 4000, 0)
     st, r = oracle.dubins_plan(og8, 4000, star, xs, xg, samples, heads, r2_rewire=hostprep.radius_threshold(40), rho=6.0, nh=64)
     assert st == 0 and r.found and r.j > 1000
-    _check_dubins_tree(og8, r, 6.0, 64, xs)
+    check_dubins_tree(og8, r, 6.0, 64, xs)
     st0, r0 = oracle.dubins_plan(og8, 4000, 0, xs, xg, samples, heads, rho=6.0, nh=64)
     assert r.j == r0.j and np.array_equal(r.pts[:r.j], r0.pts[:r0.j])  # acceptance does not depend on choose-parent
     if star:
@@ -195,17 +142,6 @@ def test_planner_classes_on_the_oracle_stand_in():
     assert s.shape == (3,) and og[s[0], s[1]] == 0 and 0 <= s[2] < 32
 
 
-def _assert_audit_clean(a, star):
-    """What oracle/dubins_ref.c's second opinion must say about a tree (its head comment): every accept / reject and every
-    chosen parent either equal to its own, or within the stated tolerance / ambiguity -- never plainly different."""
-    assert a["nearest_mismatch"] == 0 and a["accept_mismatch"] == 0, a
-    assert a["parent_wrong"] == 0 and a["parent_blocked"] == 0 and a["cost_mismatch"] == 0, a
-    assert a["max_cost_err"] < 1e-8, a
-    assert a["parent_is_argmin"] + a["parent_within_tol"] == a["n_accepted"], a
-    # the tolerance classes are the exception, not the rule
-    assert a["parent_within_tol"] <= max(3, a["n_accepted"] // 1000) and a["accept_ambiguous"] + a["parent_blocked_ambiguous"] <= max(3, a["n_accepted"] // 1000), a
-
-
 def test_independent_reference_words_agree_with_the_shared_header():
     """dubins_ref.c (libm, textbook closed forms, no shared header) against include/rrt_dubins.h through the oracle, on random
     pose pairs: same word, lengths and segments to 1e-9."""
@@ -232,7 +168,7 @@ def test_independent_audit_of_the_oracles_tree(star, grid, n, rr, rho, seed):
     st, r = oracle.dubins_plan(og8, n, star, xs, xg, samples, heads, r2_rewire=r2, rho=rho, nh=64)
     a = oracle.dubins_audit(og8, n, star, samples, heads, r.pts, r.head, r.vcost, r.parent, r.j, r2_rewire=r2, rho=rho, nh=64)
     assert a["n_accepted"] == r.j - 1
-    _assert_audit_clean(a, star)
+    assert_audit_clean(a, star)
     # and the audit is not blind: a tree with one wrong parent / one wrong cost is caught
     if star and r.j > 50:
         bad = r.parent.copy()
@@ -247,24 +183,6 @@ def test_independent_audit_of_the_oracles_tree(star, grid, n, rr, rho, seed):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _device_vs_oracle_dubins(ctx, og8, star, n, xs, xg, samples, heads, rr, rho, nh=64, serial=False, counters=False):
-    """serial = False: the 16-samples-per-round kernel (rrt_dubins_block.h, the default); True: the one-sample-per-iteration
-    kernel (RRT_FLAG_SERIAL), kept as a second implementation of the same semantics."""
-    r2 = hostprep.radius_threshold(rr) if star else 0
-    q, keep = _ffi.make_query(_ffi.ALG_DUBINS_STAR if star else _ffi.ALG_DUBINS, n, xs, xg, samples, r2_rewire=r2, headings=heads, rho=rho, nh=nh)
-    rc, res = ctx.plan(q, n, logs=True, serial=serial)
-    st, ro = oracle.dubins_plan(og8, n, star, xs, xg, samples, heads, r2_rewire=r2, rho=rho, nh=nh, counters=counters)
-    assert rc == st
-    live = ro.j + (1 if ro.found else 0)
-    assert (res.j, res.found, res.vgoal) == (ro.j, ro.found, ro.vgoal)
-    assert np.array_equal(res.nearest_log, ro.nearest_log) and np.array_equal(res.accept_log, ro.accept_log)
-    assert np.array_equal(res.pts[:live], ro.pts[:live]) and np.array_equal(res.head[:live], ro.head[:live])
-    assert np.array_equal(res.parent[:live], ro.parent[:live])
-    assert np.array_equal(res.vcost[:live], ro.vcost[:live])  # bit-exact: one arithmetic on both sides
-    assert res.sum_j == ro.sum_j and res.sum_cells_nn == ro.sum_cells_nn and res.sum_near == ro.sum_near
-    return res, ro
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("star,grid,n,rr,rho,seed", [
     (0, 300, 4000, None, 6.0, 0), (1, 300, 4000, 40, 6.0, 0), (1, 1024, 20000, 64, 8.0, 1), (1, 64, 2500, 12, 2.0, 2),
@@ -273,10 +191,10 @@ def _device_vs_oracle_dubins(ctx, og8, star, n, xs, xg, samples, heads, rr, rho,
 def test_device_dubins_equals_the_oracle(gpu_ctx, star, grid, n, rr, rho, seed, serial):
     og, og8, xs, xg, samples, heads = _dub_query(grid, n, seed, gseed=3 if grid == 2048 else 1)
     gpu_ctx.set_grid(og8)
-    res, ro = _device_vs_oracle_dubins(gpu_ctx, og8, star, n, xs, xg, samples, heads, rr, rho, serial=serial)
-    _check_dubins_tree(og8, res, rho, 64, xs)
+    res, ro = device_vs_oracle_dubins(gpu_ctx, og8, star, n, xs, xg, samples, heads, rr, rho, serial=serial)
+    check_dubins_tree(og8, res, rho, 64, xs)
     if not serial:
-        _independent_collision_witness(og8, res, samples, heads, rho, 64)
+        independent_collision_witness(og8, res, samples, heads, rho, 64)
     assert res.n_words > 0 or serial  # (the one-sample-per-iteration kernel does not count its words)
 
 
@@ -302,11 +220,11 @@ def test_config5_full_size_equals_the_oracle(gpu_ctx):
     heads = rng.integers(0, cfg["nh"], size=n)
     xs, xg = (int(a[0]), int(a[1]), 0), (int(b[0]), int(b[1]), 5 % cfg["nh"])
     gpu_ctx.set_grid(og8)
-    res, ro = _device_vs_oracle_dubins(gpu_ctx, og8, 1, n, xs, xg, samples, heads, cfg["r_rewire"], cfg["rho"], cfg["nh"], counters=True)
+    res, ro = device_vs_oracle_dubins(gpu_ctx, og8, 1, n, xs, xg, samples, heads, cfg["r_rewire"], cfg["rho"], cfg["nh"], counters=True)
     assert ro.j > 80000 and ro.lb_violations == 0 and ro.lb_mismatch == 0
     assert 0 < res.n_words < ro.n_dubins // 2  # the oracle's walk prices every near-set entry; the kernel one per lane of a pass, up to 64
-    _check_dubins_tree(og8, res, cfg["rho"], cfg["nh"], xs)
-    assert _independent_collision_witness(og8, res, samples, heads, cfg["rho"], cfg["nh"], count=400) > 50
+    check_dubins_tree(og8, res, cfg["rho"], cfg["nh"], xs)
+    assert independent_collision_witness(og8, res, samples, heads, cfg["rho"], cfg["nh"], count=400) > 50
     # every accept / reject and every chosen parent of the DEVICE's tree recomputed by oracle/dubins_ref.c (libm,
     # no shared header) at the config's full size; the counts go to profiles/ via tools/gpu_round.sh
     a = oracle.dubins_audit(og8, n, 1, samples, heads, res.pts, res.head, res.vcost, res.parent, res.j, r2_rewire=hostprep.radius_threshold(cfg["r_rewire"]),
@@ -320,7 +238,7 @@ def test_config5_full_size_equals_the_oracle(gpu_ctx):
             json.dump({"workload": "BASELINE.json configs[4], query 0 (bench.py --config 5), the DEVICE's tree", "audit": a,
                        "by": "oracle/dubins_ref.c (libm, textbook words, own sweep; does not include include/rrt_dubins.h)"}, f, indent=1)
     assert a["n_accepted"] == res.j - 1
-    _assert_audit_clean(a, 1)
+    assert_audit_clean(a, 1)
 
 
 @pytest.mark.gpu
@@ -344,7 +262,7 @@ def test_device_dubins_fuzz_small(gpu_ctx):
         heads = srng.integers(0, nh, size=n)
         gpu_ctx.set_grid(og8)
         try:
-            _device_vs_oracle_dubins(gpu_ctx, og8, star, n, xs, xg, samples, heads, rr, rho, nh, serial=bool(case % 3 == 2))
+            device_vs_oracle_dubins(gpu_ctx, og8, star, n, xs, xg, samples, heads, rr, rho, nh, serial=bool(case % 3 == 2))
         except AssertionError as e:
             raise AssertionError(f"dubins fuzz case {case}: {w}x{h} star {star} n {n} nh {nh} rho {rho} r {rr} xs {xs} xg {xg}") from e
 

@@ -12,6 +12,8 @@ import pytest
 
 import farnn
 import oracle
+from devcheck import KERNELS_NOFAULT, oracle_vs_device
+from posecalls import assert_audit_clean, device_vs_oracle_dubins
 from rrtplanner_amd import _ffi, hostprep
 
 
@@ -82,13 +84,11 @@ def test_dubins_pocket_fuzz_reaches_the_terminal_pass():
 
 # ------------------------------------------------------------------------------------------------------------ GPU
 def _pipe_device_vs_oracle(ctx, c, kernel):
-    from test_gpu_parity import _oracle_vs_device
-
     og8 = farnn.pocket_grid(c["W"], c["H"], c["rects"], c.get("field"))
     ctx.set_grid(og8)
     try:
         # (the same draws as farnn.pipe_case: default_rng(seed), hostprep.draw_free_samples over the free cells)
-        return _oracle_vs_device(ctx, og8, c["alg"], c["n"], c["seed"], c["xs"], c["xg"], c["rr"], None, kernel=kernel)
+        return oracle_vs_device(ctx, og8, c["alg"], c["n"], c["seed"], c["xs"], c["xg"], c["rr"], None, kernel=kernel)
     except AssertionError as e:
         raise AssertionError(f"pocket case {c['id']} ({c['W']}x{c['H']} alg {c['alg']} r {c['rr']}) on {kernel}") from e
 
@@ -104,14 +104,8 @@ def _batch_vs_oracle(res, st, ro, tag):
     assert res.sum_j == ro.sum_j and res.sum_cells_nn == ro.sum_cells_nn and res.sum_near == ro.sum_near, tag
 
 
-def _kernels():
-    from test_gpu_parity import KERNELS_NOFAULT
-
-    return KERNELS_NOFAULT
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("kernel", _kernels())
+@pytest.mark.parametrize("kernel", KERNELS_NOFAULT)
 @pytest.mark.parametrize("c", farnn.PIPE_CASES, ids=lambda c: c["id"])
 def test_pipe_pocket_cases_vs_oracle(gpu_ctx, c, kernel):
     """`block` runs rrt_pipe_kernel (checked through a batch of one); the other kernels scan every vertex and are controls."""
@@ -171,13 +165,11 @@ def test_pipe_pocket_batch_one_cu_per_query(gpu_ctx):
 
 
 def _dubins_device_vs_oracle(ctx, c, serial, audit=True):
-    from test_dubins import _assert_audit_clean, _device_vs_oracle_dubins
-
     og8, samples, heads, r2 = farnn.dubins_case(c)
     ctx.set_grid(og8)
     try:
-        res, ro = _device_vs_oracle_dubins(ctx, og8, c["star"], c["n"], c["xs"], c["xg"], samples, heads, c["rr"], c["rho"],
-                                           serial=serial)
+        res, ro = device_vs_oracle_dubins(ctx, og8, c["star"], c["n"], c["xs"], c["xg"], samples, heads, c["rr"], c["rho"],
+                                          serial=serial)
     except AssertionError as e:
         raise AssertionError(f"Dubins pocket case {c['id']} ({c['W']}x{c['H']} star {c['star']}) serial={serial}") from e
     if not audit:
@@ -185,7 +177,7 @@ def _dubins_device_vs_oracle(ctx, c, serial, audit=True):
     a = oracle.dubins_audit(og8, c["n"], c["star"], samples, heads, res.pts, res.head, res.vcost, res.parent, res.j, r2_rewire=r2,
                             rho=c["rho"], nh=64)
     assert a["n_accepted"] == res.j - 1
-    _assert_audit_clean(a, c["star"])
+    assert_audit_clean(a, c["star"])
 
 
 @pytest.mark.gpu

@@ -10,6 +10,7 @@ import pytest
 
 import oracle
 import orchelp
+from devcheck import KERNELS, KERNELS_NOFAULT, oracle_vs_device
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pair
@@ -184,49 +185,7 @@ def test_replan_chain_rng_continues_and_set_og(tag):
         _run_case(GS, m, planner=p)
 
 
-# ------------------------------------------------------------------------------- device vs oracle, larger
-# teams of up to 64 workers per query (default: pipelined, one more CU that only commits), the same without the pipeline, capped
-# teams (2, 3 and 4 workers: 16 samples per member, pipelined and -- 4 -- not; 16: 4 samples per member, 4 waves per sample), one CU,
-# one sample per iteration, and a team that loses a member (must finish on one CU per query)
-KERNELS = ["team", "teamnp", "team2", "team3", "team4", "team4np", "team16", "block", "block16", "serial", "teamfault"]
-_KERNEL_ARGS = {"team": {}, "teamnp": {"pipe": False}, "team2": {"team": 2}, "team3": {"team": 3}, "team4": {"team": 4},
-                "team4np": {"team": 4, "pipe": False}, "team16": {"team": 16},
-                # one CU per query: the barrier-free pipeline (rrt_pipe.h; Informed queries run the block kernel), and the block kernel
-                "block": {"team": 1}, "block16": {"team": 1, "pipe1": False},
-                "serial": {"serial": True}, "teamfault": {"team": 8, "team_fault": True}}
-KERNELS_NOFAULT = [k for k in KERNELS if k != "teamfault"]
-
-
-def _oracle_vs_device(ctx, og8, alg, n, seed, xs, xg, r_rewire=None, r_goal=None, kernel="team"):
-    rng = np.random.default_rng(seed)
-    free = np.argwhere(og8 == 0)
-    samples = hostprep.draw_free_samples(rng, free, n)
-    r2 = hostprep.radius_threshold(r_rewire) if r_rewire is not None else 0
-    gd2 = hostprep.goal_threshold(r_goal) if r_goal is not None else 0
-    Cm = hostprep.rotation_to_world_frame(np.asarray(xs, dtype=np.int64), np.asarray(xg, dtype=np.int64)) if alg == 2 else None
-    q, keep = _ffi.make_query(alg, n, xs, xg, samples, r2_rewire=r2, goal_d2=gd2, Cmat=Cm)
-    rc, res = ctx.plan(q, n, logs=True, **_KERNEL_ARGS[kernel])
-    st, ro = oracle.plan(og8, n, alg, xs, xg, samples, r2_rewire=r2, r_goal=r_goal or 0.0, Cmat=Cm)
-    ub = None
-    if rc == _ffi.RRT_NEED_UNITBALL:
-        assert st == oracle.ORC_NEED_UNITBALL and res.i_switch == ro.i_switch
-        ub = hostprep.draw_unitball(rng, n - res.i_switch)
-        rc = ctx.plan_resume(ub, res)
-        st, ro = oracle.plan(og8, n, alg, xs, xg, samples, r2_rewire=r2, r_goal=r_goal, unitball=ub, ub_offset=res.i_switch, Cmat=Cm)
-    assert rc == st
-    assert res.j == ro.j and res.found == ro.found and res.vgoal == ro.vgoal and res.i_switch == ro.i_switch
-    live = ro.j + (1 if ro.found else 0)
-    assert np.array_equal(res.nearest_log, ro.nearest_log)
-    assert np.array_equal(res.accept_log, ro.accept_log)
-    assert np.array_equal(res.j_log, ro.jlog)
-    assert np.array_equal(res.pts[:live], ro.pts[:live])
-    assert np.array_equal(res.parent[:live], ro.parent[:live])
-    assert np.array_equal(res.vcost[:live], ro.vcost[:live])  # bit-exact f64 (tolerance stated by the north star: 1e-6)
-    assert np.array_equal(res.cbest_log, ro.cbest_log, equal_nan=True)
-    assert res.sum_j == ro.sum_j and res.sum_cells_nn == ro.sum_cells_nn and res.sum_near == ro.sum_near
-    return res, ro
-
-
+# ------------------------------------------------------------------------------- device vs oracle, larger (the shapes: devcheck.KERNELS)
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("alg,rr,rg", [(0, None, None), (1, 64, None), (2, 64, 12)])
 def test_device_vs_oracle_1024_n6000(gpu_ctx, alg, rr, rg, kernel):
@@ -234,7 +193,7 @@ def test_device_vs_oracle_1024_n6000(gpu_ctx, alg, rr, rg, kernel):
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(7))
-    _oracle_vs_device(gpu_ctx, og8, alg, 6000, 0, xs, xg, rr, rg, kernel=kernel)
+    oracle_vs_device(gpu_ctx, og8, alg, 6000, 0, xs, xg, rr, rg, kernel=kernel)
 
 
 @pytest.mark.parametrize("kernel", KERNELS_NOFAULT)
@@ -244,7 +203,7 @@ def test_device_vs_oracle_beyond_lds_capacity(gpu_ctx, kernel):
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(7))
-    _oracle_vs_device(gpu_ctx, og8, 1, 40000, 0, xs, xg, 64, None, kernel=kernel)
+    oracle_vs_device(gpu_ctx, og8, 1, 40000, 0, xs, xg, 64, None, kernel=kernel)
 
 
 @pytest.mark.parametrize("kernel", ["team", "block"])
@@ -254,7 +213,7 @@ def test_device_vs_oracle_informed_1024_n25000(gpu_ctx, kernel):
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(7))
-    res, ro = _oracle_vs_device(gpu_ctx, og8, 2, 25000, 0, xs, xg, 64, 12, kernel=kernel)
+    res, ro = oracle_vs_device(gpu_ctx, og8, 2, 25000, 0, xs, xg, 64, 12, kernel=kernel)
     assert res.i_switch < 25000  # the ellipse phase was reached
 
 
@@ -266,7 +225,7 @@ def test_device_vs_oracle_informed_config3_full_size(gpu_ctx, kernel):
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(7))
-    res, ro = _oracle_vs_device(gpu_ctx, og8, 2, 50000, 0, xs, xg, 64, 12, kernel=kernel)
+    res, ro = oracle_vs_device(gpu_ctx, og8, 2, 50000, 0, xs, xg, 64, 12, kernel=kernel)
     assert res.i_switch < 50000
 
 
@@ -277,7 +236,7 @@ def test_device_vs_oracle_near_set_spills(gpu_ctx, kernel):
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(1))
-    _oracle_vs_device(gpu_ctx, og8, 1, 5000, 3, xs, xg, 1e6, None, kernel=kernel)
+    oracle_vs_device(gpu_ctx, og8, 1, 5000, 3, xs, xg, 1e6, None, kernel=kernel)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -292,7 +251,7 @@ def test_device_vs_oracle_dense_interactions(gpu_ctx, alg, rr, rg, grid, n, seed
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(seed))
-    _oracle_vs_device(gpu_ctx, og8, alg, n, seed, xs, xg, rr, rg, kernel=kernel)
+    oracle_vs_device(gpu_ctx, og8, alg, n, seed, xs, xg, rr, rg, kernel=kernel)
 
 
 @pytest.mark.parametrize("kernel", KERNELS_NOFAULT)
@@ -302,8 +261,8 @@ def test_device_vs_oracle_2048_grid(gpu_ctx, kernel):
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     xs, xg = random_connected_pair(og, np.random.default_rng(11))
-    _oracle_vs_device(gpu_ctx, og8, 1, 30000, 5, xs, xg, 64, None, kernel=kernel)
-    _oracle_vs_device(gpu_ctx, og8, 2, 12000, 6, (3, 2044), (2040, 5), 200.5, 40, kernel=kernel) if og8[3, 2044] == 0 and og8[2040, 5] == 0 else None
+    oracle_vs_device(gpu_ctx, og8, 1, 30000, 5, xs, xg, 64, None, kernel=kernel)
+    oracle_vs_device(gpu_ctx, og8, 2, 12000, 6, (3, 2044), (2040, 5), 200.5, 40, kernel=kernel) if og8[3, 2044] == 0 and og8[2040, 5] == 0 else None
 
 
 @pytest.mark.parametrize("kernel", KERNELS_NOFAULT)
@@ -330,7 +289,7 @@ def test_fuzz_small_queries_vs_oracle(gpu_ctx, kernel):
             continue
         gpu_ctx.set_grid(og8)
         try:
-            _oracle_vs_device(gpu_ctx, og8, alg, n, case, xs, xg, rr if alg else None, rg if alg == 2 else None, kernel=kernel)
+            oracle_vs_device(gpu_ctx, og8, alg, n, case, xs, xg, rr if alg else None, rg if alg == 2 else None, kernel=kernel)
         except AssertionError as e:
             raise AssertionError(f"fuzz case {case}: grid {w}x{h} dens {dens} alg {alg} n {n} r {rr} rg {rg} xs {xs} xg {xg}") from e
 

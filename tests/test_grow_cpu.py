@@ -11,24 +11,10 @@ import pytest
 
 import growref
 import oracle
-import orchelp
+from plannedcases import GROW_CASES, grow_setup, hand_tree
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTStarDubins
-
-G = orchelp.golden("plans_A.npz")
-CASES = [("noise200", 0, 300, 200, 11), ("noise200", 1, 300, 200, 12), ("maze64x96", 1, 250, 150, 13), ("square100", 0, 200, 120, 14),
-         ("square100", 1, 200, 120, 15)]
-
-
-def _setup(grid, alg, n, m, seed):
-    og8 = oracle.og_u8(G.grid(grid))
-    free = np.argwhere(og8 == 0)
-    rng = np.random.default_rng(seed)
-    xs, xg = free[rng.integers(len(free))], free[rng.integers(len(free))]
-    samples = hostprep.draw_free_samples(rng, free, n + m)
-    r2 = hostprep.radius_threshold(12) if alg else 0
-    return og8, xs, xg, samples, r2
 
 
 def _same_tree(g, ro, rows):
@@ -37,9 +23,9 @@ def _same_tree(g, ro, rows):
     assert np.array_equal(g.vcost[:rows].view(np.int64), ro.vcost[:rows].view(np.int64))  # bit for bit
 
 
-@pytest.mark.parametrize("grid,alg,n,m,seed", CASES)
+@pytest.mark.parametrize("grid,alg,n,m,seed", GROW_CASES)
 def test_nothing_cut_one_grow_is_the_longer_plan(grid, alg, n, m, seed):
-    og8, xs, xg, samples, r2 = _setup(grid, alg, n, m, seed)
+    og8, xs, xg, samples, r2 = grow_setup(grid, alg, n, m, seed)
     st0, r0 = oracle.plan(og8, n, alg, xs, xg, samples[:n], r2_rewire=r2)
     assert r0.j < n and (r0.accept_log == 0).any()  # the n plan rejected samples: `j != n` never bound in it
     st1, r1 = oracle.plan(og8, n + m, alg, xs, xg, samples, r2_rewire=r2)
@@ -52,9 +38,9 @@ def test_nothing_cut_one_grow_is_the_longer_plan(grid, alg, n, m, seed):
     assert g.rows == r1.rows and g.j > r0.j
 
 
-@pytest.mark.parametrize("grid,alg,n,m,seed", CASES[:3])
+@pytest.mark.parametrize("grid,alg,n,m,seed", GROW_CASES[:3])
 def test_nothing_cut_two_grows_are_one_plan(grid, alg, n, m, seed):
-    og8, xs, xg, samples, r2 = _setup(grid, alg, n, m, seed)
+    og8, xs, xg, samples, r2 = grow_setup(grid, alg, n, m, seed)
     N, m1 = n + m, m // 3
     st0, r0 = oracle.plan(og8, n, alg, xs, xg, samples[:n], r2_rewire=r2)
     st1, r1 = oracle.plan(og8, N, alg, xs, xg, samples, r2_rewire=r2)
@@ -67,16 +53,8 @@ def test_nothing_cut_two_grows_are_one_plan(grid, alg, n, m, seed):
 
 
 # ------------------------------------------------------------------------------------------------ seed rules, hand-written trees
-def _hand_tree():
-    """root (2, 2); 1 and 2 hang on it, 3 on 1, 4 on 3, 5 sits on the ROOT's cell and hangs on 2"""
-    pts = np.array([(2, 2), (2, 10), (10, 2), (2, 16), (8, 16), (2, 2)])
-    parent = np.array([-1, 0, 0, 1, 3, 2])
-    vcost = np.array([0.0, 8.0, 8.0, 14.0, 20.0, 16.0])
-    return pts, parent, vcost
-
-
 def test_a_cut_vertex_leaves_sampled_and_its_cell_is_accepted_again():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     og[2, 13] = 1  # cuts the edge 1 -> 3, and 4 with it
     ids, sp, sc, spar = growref.seed(pts, parent, vcost, 6, og8_view=og)
@@ -88,7 +66,7 @@ def test_a_cut_vertex_leaves_sampled_and_its_cell_is_accepted_again():
 
 
 def test_the_roots_cell_is_sampled_only_through_another_vertex():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     _, sp, sc, spar = growref.seed(pts, parent, vcost, 6)
     assert (2, 2) in growref.sampled_of(sp)  # through vertex 5
@@ -103,7 +81,7 @@ def test_the_roots_cell_is_sampled_only_through_another_vertex():
 
 
 def test_a_blocked_root_has_no_seed():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     og[2, 2] = 1
     ids, sp, sc, spar = growref.seed(pts, parent, vcost, 6, og8_view=og)
@@ -113,7 +91,7 @@ def test_a_blocked_root_has_no_seed():
 
 
 def test_go2goal_fallbacks_follow_the_querys_own_n():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     og[17:20, 17:20] = 1  # the goal sits on an obstacle: no vertex sees it
     _, sp, sc, spar = growref.seed(pts, parent, vcost, 6)

@@ -8,185 +8,64 @@ import ctypes
 import numpy as np
 import pytest
 
-import goalref
 import growref
 import keepref
 import oracle
-import routeref
 import slabs
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
-from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pair
+from treecalls import (N, R2, RR, SHAPES, base, class_goals_and_routes, goals_and_routes, grow_checked, mixed_goals, refused_with_code, set_case_query,
+                       shaped_batch, tree_of, wall)
 
 pytestmark = pytest.mark.gpu
-
-N, RR = 2000, 24
-R2 = hostprep.radius_threshold(RR)
-SHAPES = {  # launch shape -> (Batch keywords, what the kernel's name has to say)
-    "team": (dict(), lambda s: s.startswith("rrt_expand_block_kernel<") and not s.startswith("rrt_expand_block_kernel<1,")),
-    "team8": (dict(team=8), lambda s: s.startswith("rrt_expand_block_kernel<8,")),
-    "team2": (dict(team=2), lambda s: s.startswith("rrt_expand_block_kernel<2,")),
-    "pipe1": (dict(team=1), lambda s: s == "rrt_pipe_kernel"),
-    "block1": (dict(team=1, pipe1=False), lambda s: s == "rrt_expand_block_kernel<1, 16, false, false>"),
-    "serial": (dict(serial=True), lambda s: s == "rrt_expand_kernel<false, false>"),
-}
-_cache = {}
-
-
-def _once(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
-
-
-def _base(W=200, gseed=3, pair=5, n=N, seed=21, alg=1, r2=R2):
-    """a noise map, a connected start / goal pair, n samples and the oracle's plan of them"""
-    def make():
-        og = perlin_occupancygrid(W, W, seed=gseed)
-        og8 = oracle.og_u8(og)
-        xs, xg = random_connected_pair(og, np.random.default_rng(pair))
-        samples = hostprep.draw_free_samples(np.random.default_rng(seed), np.argwhere(og8 == 0), n)
-        st, ro = oracle.plan(og8, n, alg, xs, xg, samples, r2_rewire=r2)
-        return dict(og8=og8, xs=xs, xg=xg, samples=samples, st=st, ro=ro, n=n, alg=alg, r2=r2)
-    return _once(("base", W, gseed, pair, n, seed, alg, r2), make)
-
-
-def _goals(og8, seed=9, m=64):
-    free = np.argwhere(og8 == 0)
-    g = free[np.random.default_rng(seed).integers(0, len(free), size=m - 4)]
-    return np.concatenate([g, np.argwhere(og8 != 0)[::max(1, int((og8 != 0).sum()) // 4)][:4]])[:m]
-
-
-def _wall(c):
-    """the base map with a wall stamped in, the restatement's seed on it and the samples of the grow"""
-    def make():
-        og2 = c["og8"].copy()
-        W = og2.shape[0]
-        og2[W // 2:W // 2 + 3, :] = 1  # a wall across the map ...
-        og2[W // 2:W // 2 + 3, (c["xs"][1] + W // 2) % W:(c["xs"][1] + W // 2) % W + 12] = 0  # ... with one gap
-        og2[c["xs"][0], c["xs"][1]] = 0
-        ro = c["ro"]
-        alive, ids, sp, sc, spar = keepref.view(og2, ro.pts, ro.parent, ro.vcost, ro.j)
-        cut = np.flatnonzero(~alive)
-        cut_free = [k for k in cut.tolist() if og2[ro.pts[k][0], ro.pts[k][1]] == 0]
-        m = c["n"] - len(ids)
-        rng = np.random.default_rng(77)
-        fill = hostprep.draw_free_samples(rng, np.argwhere(og2 == 0), m)
-        special = np.concatenate([ro.pts[cut_free[:40]], [c["xs"]], np.argwhere(og2 != 0)[:1]]).astype(fill.dtype)
-        where = rng.choice(m, size=len(special), replace=False)
-        fill[where] = special
-        return dict(og2=og2, alive=alive, ids=ids, seed=(sp, sc, spar), cut_free=cut_free, samples=fill, special=special, where=where)
-    return _once(("wall", id(c)), make)
-
-
-def _batch(ctx, c, shape, Q=1, n_cap=None, og8=None):
-    kw, _ = SHAPES[shape]
-    ctx.set_grid(c["og8"] if og8 is None else og8)
-    return _ffi.Batch(ctx, Q, n_cap or c["n"], logs=True, **kw)
-
-
-def _set_and_run(b, q, c):
-    qu, keep = _ffi.make_query(c["alg"], c["n"], c["xs"], c["xg"], c["samples"], r2_rewire=c["r2"])
-    b.set_query(q, qu)
-    return keep
-
-
-def _tree_of(res):
-    return np.array(res.pts, dtype=np.int64), np.array(res.parent, dtype=np.int64), np.array(res.vcost), res.j
-
-
-def _same_result(res, g, log0=None):
-    live = g.j + g.found
-    assert (res.status, res.j, res.found, res.vgoal, res.rows) == (g.status, g.j, g.found, g.vgoal, g.rows)
-    assert np.array_equal(res.pts[:live], g.pts[:live]) and np.array_equal(res.parent[:live], g.parent[:live])
-    assert np.array_equal(res.vcost[:live].view(np.int64), g.vcost[:live].view(np.int64))
-    if log0 is not None:
-        m = len(g.accept_log)
-        assert np.array_equal(res.nearest_log[log0:log0 + m], g.nearest_log) and np.array_equal(res.accept_log[log0:log0 + m], g.accept_log)
-        assert np.array_equal(res.j_log[log0:log0 + m], g.jlog)
-        assert res.sum_j == g.sum_j and res.sum_near == g.sum_near  # the statistics count the grown iterations alone
-
-
-def _goals_and_routes(b, q, og8, res, seed=9, connected=8):
-    """connect_goals and routes (shortcut) of query q for 64 goals against goalref / routeref on the arrays of `res`; at least
-    `connected` of the goals have to see a vertex"""
-    goals = _goals(og8, seed)
-    pts, parent, vcost, j = _tree_of(res)
-    v, cost = b.connect_goals(q, goals)
-    rv, rc, _ = goalref.connect(og8, pts, vcost, j, goals)
-    assert np.array_equal(v, rv) and np.array_equal(cost, rc) and (rv >= 0).sum() >= connected
-    got = b.routes(q, goals, shortcut=True)
-    want = routeref.routes(og8, pts, vcost, parent, j, goals, cut=True)
-    for x, y in zip(got, want):
-        assert np.array_equal(x, y)
-
-
-def _grow(b, q, og8, prev, view, samples, c, shape):
-    """one grow of query q on map og8 from the tree `prev` = (pts, parent, vcost, j); view: the tree was kept on og8.  Checked
-    against growref.  Returns (restatement, result)."""
-    ids, sp, sc, spar = growref.seed(*prev, og8_view=og8 if view else None)
-    g = growref.grow(og8, c["alg"], c["n"], c["xg"], c["r2"], sp, sc, spar, samples)
-    j0, old_id, log0 = b.grow(q, samples)
-    assert j0 == len(ids) == log0 and np.array_equal(old_id, ids)
-    b.launch()
-    b.sync()
-    res = b.get_result(q)
-    _same_result(res, g, log0)
-    info = b.team_info()
-    assert info["timeouts"] == 0 and b.team()[1] == 0, info
-    assert SHAPES[shape][1](b.kernel_name()), b.kernel_name()
-    ms = b.grow_ms()
-    assert len(ms) == 3 and all(t >= 0.0 for t in ms)
-    return g, res
-
 
 # ------------------------------------------------------------------------------------------------ 1. nothing cut
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_nothing_cut_is_the_longer_plan(gpu_ctx, shape):
-    c = _base()
+    c = base()
     ro = c["ro"]
     m = c["n"] - ro.j
     assert ro.j > 1000 and m >= 100 and (ro.accept_log == 0).any()  # room to grow: the plan rejected samples
     more = hostprep.draw_free_samples(np.random.default_rng(31), np.argwhere(c["og8"] == 0), m)
-    b = _batch(gpu_ctx, c, shape)
-    _set_and_run(b, 0, c)
+    b = shaped_batch(gpu_ctx, c, shape)
+    set_case_query(b, 0, c)
     b.launch()
     b.sync()
     r0 = b.get_result(0)
     assert r0.j == ro.j and np.array_equal(r0.vcost[:ro.j], ro.vcost[:ro.j])
-    g, res = _grow(b, 0, c["og8"], _tree_of(r0), False, more, c, shape)
+    g, res = grow_checked(b, 0, c["og8"], tree_of(r0), False, more, c, shape)
     st, rl = oracle.plan(c["og8"], c["n"] + m, c["alg"], c["xs"], c["xg"], np.concatenate([c["samples"], more]), r2_rewire=c["r2"])
     live = rl.j + rl.found
     assert g.j < c["n"] and res.j == rl.j > ro.j + 50 and res.found == rl.found
     assert np.array_equal(res.pts[:live], rl.pts[:live]) and np.array_equal(res.parent[:live], rl.parent[:live])
     assert np.array_equal(res.vcost[:live].view(np.int64), rl.vcost[:live].view(np.int64))
-    _goals_and_routes(b, 0, c["og8"], res)
+    goals_and_routes(b, 0, c["og8"], res)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 2. a wall stamped in
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_a_kept_tree_grows_back_behind_the_wall(gpu_ctx, shape):
-    c = _base()
-    w = _wall(c)
+    c = base()
+    w = wall(c)
     og2, ro = w["og2"], c["ro"]
     assert (~w["alive"]).sum() >= 100 and len(w["ids"]) >= 100 and len(w["ids"]) > 64  # above PP_TINY
     assert len(w["cut_free"]) >= 20 and len(w["samples"]) == c["n"] - len(w["ids"])
-    b = _batch(gpu_ctx, c, shape)
-    _set_and_run(b, 0, c)
+    b = shaped_batch(gpu_ctx, c, shape)
+    set_case_query(b, 0, c)
     b.launch()
     b.sync()
     r0 = b.get_result(0)
     gpu_ctx.set_grid(og2)
     assert np.array_equal(b.keep_tree(0), w["alive"])
-    g, res = _grow(b, 0, og2, _tree_of(r0), True, w["samples"], c, shape)
+    g, res = grow_checked(b, 0, og2, tree_of(r0), True, w["samples"], c, shape)
     acc = g.accept_log[w["where"]]
     assert acc[:-2].any() and not acc[-1]  # a cut vertex's cell is a vertex again; the obstacle cell is not
     assert g.j - g.j0 >= 100
-    _goals_and_routes(b, 0, og2, res)
+    goals_and_routes(b, 0, og2, res)
     # the grown tree is an ordinary finished query: kept again on the first map, every edge that crosses no new obstacle survives
     gpu_ctx.set_grid(c["og8"])
-    pts, parent, vcost, j = _tree_of(res)
+    pts, parent, vcost, j = tree_of(res)
     assert np.array_equal(b.keep_tree(0), keepref.alive(c["og8"], pts, parent, j))
     b.close()
 
@@ -194,33 +73,33 @@ def test_a_kept_tree_grows_back_behind_the_wall(gpu_ctx, shape):
 @pytest.mark.parametrize("shape", ["team", "pipe1", "serial"])
 def test_a_kept_rrtstandard_tree_grows_back(gpu_ctx, shape):
     """alg = 0: no near set, no cost comparison -- the same seed, the loop of rrt.py:418-437"""
-    c = _base(seed=25, alg=0, r2=0)
-    w = _wall(c)
+    c = base(seed=25, alg=0, r2=0)
+    w = wall(c)
     assert (~w["alive"]).sum() >= 100 and len(w["ids"]) > 64 and len(w["samples"]) == c["n"] - len(w["ids"])
-    b = _batch(gpu_ctx, c, shape)
-    _set_and_run(b, 0, c)
+    b = shaped_batch(gpu_ctx, c, shape)
+    set_case_query(b, 0, c)
     b.launch()
     b.sync()
     r0 = b.get_result(0)
     assert r0.j == c["ro"].j
     gpu_ctx.set_grid(w["og2"])
     assert np.array_equal(b.keep_tree(0), w["alive"])
-    g, res = _grow(b, 0, w["og2"], _tree_of(r0), True, w["samples"], c, shape)
+    g, res = grow_checked(b, 0, w["og2"], tree_of(r0), True, w["samples"], c, shape)
     assert g.j - g.j0 >= 100 and g.sum_near == 0
-    _goals_and_routes(b, 0, w["og2"], res)
+    goals_and_routes(b, 0, w["og2"], res)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 3. only the root alive
 @pytest.mark.parametrize("shape", ["team", "pipe1", "block1", "serial"])
 def test_only_the_root_alive_is_the_tiny_tree_path(gpu_ctx, shape):
-    c = _base()
+    c = base()
     xs = c["xs"]
     og2 = c["og8"].copy()
     og2[max(xs[0] - 3, 0):xs[0] + 4, max(xs[1] - 3, 0):xs[1] + 4] = 1
     og2[xs[0], xs[1]] = 0  # xstart alone in a filled block: every edge out of it is cut
-    b = _batch(gpu_ctx, c, shape)
-    _set_and_run(b, 0, c)
+    b = shaped_batch(gpu_ctx, c, shape)
+    set_case_query(b, 0, c)
     b.launch()
     b.sync()
     r0 = b.get_result(0)
@@ -228,73 +107,73 @@ def test_only_the_root_alive_is_the_tiny_tree_path(gpu_ctx, shape):
     alive = b.keep_tree(0)
     assert alive.sum() == 1 and alive[0]
     samples = np.concatenate([[xs], hostprep.draw_free_samples(np.random.default_rng(5), np.argwhere(og2 == 0), 40), [xs]])
-    g, res = _grow(b, 0, og2, _tree_of(r0), True, samples, c, shape)
+    g, res = grow_checked(b, 0, og2, tree_of(r0), True, samples, c, shape)
     # xstart drawn once becomes vertex 1 (rrt.py:425: it is never in `sampled`), the second time it is refused; nothing else is visible
     assert g.j0 == 1 and g.j == 2 and g.accept_log[0] == 1 and g.accept_log[-1] == 0 and not g.found and res.status == _ffi.RRT_E_GOAL_UNREACHABLE
-    _goals_and_routes(b, 0, og2, res, connected=0)  # (two vertices on xstart inside a filled block: no goal has to see them)
+    goals_and_routes(b, 0, og2, res, connected=0)  # (two vertices on xstart inside a filled block: no goal has to see them)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4. a seed across a scan chunk
 def test_a_seed_of_more_than_4096_vertices_grown_twice(gpu_ctx):
-    c = _base(W=512, gseed=4, pair=6, n=6000, seed=22)
+    c = base(W=512, gseed=4, pair=6, n=6000, seed=22)
     ro = c["ro"]
     room = c["n"] - ro.j
     assert ro.j > 4096 + 64 and room >= 100, (ro.j, room)
-    b = _batch(gpu_ctx, c, "team")
-    _set_and_run(b, 0, c)
+    b = shaped_batch(gpu_ctx, c, "team")
+    set_case_query(b, 0, c)
     b.launch()
     b.sync()
     r0 = b.get_result(0)
     free = np.argwhere(c["og8"] == 0)
-    g1, r1 = _grow(b, 0, c["og8"], _tree_of(r0), False, hostprep.draw_free_samples(np.random.default_rng(41), free, room // 2), c, "team")
+    g1, r1 = grow_checked(b, 0, c["og8"], tree_of(r0), False, hostprep.draw_free_samples(np.random.default_rng(41), free, room // 2), c, "team")
     assert g1.j0 > 4096 and g1.j > g1.j0
-    _goals_and_routes(b, 0, c["og8"], r1)
+    goals_and_routes(b, 0, c["og8"], r1)
     og2 = c["og8"].copy()
     far = np.argmax(np.abs(np.asarray(g1.pts[:g1.j]) - c["xs"]).sum(axis=1))
     fx, fy = (int(v) for v in g1.pts[far])
     og2[max(fx - 80, 0):fx + 80, max(fy - 80, 0):fy + 80] = 1  # a block far from the start: cuts some 200 vertices
     og2[c["xs"][0], c["xs"][1]] = 0
     gpu_ctx.set_grid(og2)
-    pts, parent, vcost, j = _tree_of(r1)
+    pts, parent, vcost, j = tree_of(r1)
     alive = b.keep_tree(0)
     assert np.array_equal(alive, keepref.alive(og2, pts, parent, j)) and 4096 < alive.sum() < j - 20
     m2 = min(c["n"] - int(alive.sum()), 600)
-    g2, r2 = _grow(b, 0, og2, (pts, parent, vcost, j), True, hostprep.draw_free_samples(np.random.default_rng(42), np.argwhere(og2 == 0), m2), c, "team")
+    g2, r2 = grow_checked(b, 0, og2, (pts, parent, vcost, j), True, hostprep.draw_free_samples(np.random.default_rng(42), np.argwhere(og2 == 0), m2), c, "team")
     assert g2.j0 > 4096 and g2.j > g2.j0 + 100
-    _goals_and_routes(b, 0, og2, r2)
+    goals_and_routes(b, 0, og2, r2)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 5. a ball of more than 64 cells
 def test_a_radius_whose_ball_takes_a_second_slab_of_cells(gpu_ctx):
     r2 = hostprep.radius_threshold(120)
-    c = _base(r2=r2, seed=23)
-    w = _wall(c)
+    c = base(r2=r2, seed=23)
+    w = wall(c)
     shift = slabs.cell_shift(200, 200, r2, slabs.DIV_PIPE)
     assert slabs.largest_box(200, 200, r2, shift) > 64
-    b = _batch(gpu_ctx, c, "pipe1")
-    _set_and_run(b, 0, c)
+    b = shaped_batch(gpu_ctx, c, "pipe1")
+    set_case_query(b, 0, c)
     b.launch()
     b.sync()
     r0 = b.get_result(0)
     gpu_ctx.set_grid(w["og2"])
     b.keep_tree(0)
-    g, res = _grow(b, 0, w["og2"], _tree_of(r0), True, w["samples"], c, "pipe1")
+    g, res = grow_checked(b, 0, w["og2"], tree_of(r0), True, w["samples"], c, "pipe1")
     cov = slabs.coverage(200, 200, r2, shift, w["samples"], np.ones(len(w["samples"]), dtype=bool), g.jlog, g.pts, g.nearest_log, g.accept_log, g.parent)
     assert cov["reach"] >= 1 and cov["max_box"] > 64, cov  # a grown iteration needs a record of the SEED from a later slab
-    _goals_and_routes(b, 0, w["og2"], res)
+    goals_and_routes(b, 0, w["og2"], res)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 6. a batch of three
 def test_one_query_of_three_grown_the_others_unchanged(gpu_ctx):
-    c = _base()
-    w = _wall(c)
-    cs = [c, _base(seed=24, pair=7), _base(seed=25, alg=0, r2=0)]
-    b = _batch(gpu_ctx, c, "team", Q=3)
+    c = base()
+    w = wall(c)
+    cs = [c, base(seed=24, pair=7), base(seed=25, alg=0, r2=0)]
+    b = shaped_batch(gpu_ctx, c, "team", Q=3)
     for q, cq in enumerate(cs):
-        _set_and_run(b, q, cq)
+        set_case_query(b, q, cq)
     b.launch()
     b.sync()
     before = [b.get_result(q) for q in range(3)]
@@ -303,7 +182,7 @@ def test_one_query_of_three_grown_the_others_unchanged(gpu_ctx):
     gpu_ctx.set_grid(w["og2"])
     b.keep_tree(0)
     b.keep_tree(2)
-    g, res = _grow(b, 0, w["og2"], _tree_of(before[0]), True, w["samples"], c, "team")
+    g, res = grow_checked(b, 0, w["og2"], tree_of(before[0]), True, w["samples"], c, "team")
     for q in (1, 2):
         r = b.get_result(q)
         assert (r.status, r.j, r.found, r.vgoal) == (before[q].status, before[q].j, before[q].found, before[q].vgoal)
@@ -312,47 +191,40 @@ def test_one_query_of_three_grown_the_others_unchanged(gpu_ctx):
         assert np.array_equal(r.vcost[:live].view(np.int64), before[q].vcost[:live].view(np.int64))
         with pytest.raises(_ffi.RRTError):  # the launch dropped the view of query 2; query 1 never had one for this grid
             b.connect_goals(q, [(5, 5)])
-    _goals_and_routes(b, 0, w["og2"], res)
+    goals_and_routes(b, 0, w["og2"], res)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 7. refusals and m == 0
-def _refused(code, call):
-    with pytest.raises(_ffi.RRTError) as e:
-        call()
-    assert e.value.code == code, e.value
-    return str(e.value)
-
-
 def test_refusals_change_nothing_and_m_zero_only_connects_the_goal(gpu_ctx):
-    c = _base()
-    w = _wall(c)
-    b = _batch(gpu_ctx, c, "pipe1")
-    _refused(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))  # no query set
-    _set_and_run(b, 0, c)
-    _refused(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))  # not launched
+    c = base()
+    w = wall(c)
+    b = shaped_batch(gpu_ctx, c, "pipe1")
+    refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))  # no query set
+    set_case_query(b, 0, c)
+    refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))  # not launched
     b.launch()
     b.sync()
     r0 = b.get_result(0)
-    goals = _goals(c["og8"])
+    goals = mixed_goals(c["og8"])
     ans0 = b.connect_goals(0, goals)
     j0, log0 = ctypes.c_int32(-1), ctypes.c_int32(-1)  # m < 0: below what _ffi.Batch.grow can pass
     assert _ffi.lib().rrt_batch_grow(b._h, 0, None, -1, ctypes.byref(j0), None, ctypes.byref(log0)) == _ffi.RRT_E_ARG
     assert (j0.value, log0.value) == (-1, -1) and b"m=-1" in _ffi.lib().rrt_last_error_string(gpu_ctx.handle)
     room = c["n"] - r0.j
-    _refused(_ffi.RRT_E_ARG, lambda: b.grow(1, c["samples"][:5]))
-    assert f"room for {room}" in _refused(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:room + 1]))  # one more than the room
-    _refused(_ffi.RRT_E_ARG, lambda: b.grow(0, np.array([(5, 5), (200, 5)])))  # outside the grid
+    refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(1, c["samples"][:5]))
+    assert f"room for {room}" in refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:room + 1]))  # one more than the room
+    refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(0, np.array([(5, 5), (200, 5)])))  # outside the grid
     # a new grid without keep_tree
     gpu_ctx.set_grid(w["og2"])
-    _refused(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))
+    refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))
     # the root blocked: refused, the view and its answers stay
     og3 = w["og2"].copy()
     og3[c["xs"][0], c["xs"][1]] = 1
     gpu_ctx.set_grid(og3)
     assert not b.keep_tree(0).any()
     v0, c0 = b.connect_goals(0, goals)
-    assert "root is blocked" in _refused(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))
+    assert "root is blocked" in refused_with_code(_ffi.RRT_E_ARG, lambda: b.grow(0, c["samples"][:5]))
     v1, c1 = b.connect_goals(0, goals)
     assert np.array_equal(v0, v1) and np.array_equal(c0, c1) and (v1 == -1).all()
     # after all these refusals the tree is what it was
@@ -365,19 +237,19 @@ def test_refusals_change_nothing_and_m_zero_only_connects_the_goal(gpu_ctx):
     # m == 0 on the wall map: the seed, then go2goal
     gpu_ctx.set_grid(w["og2"])
     b.keep_tree(0)
-    g, res = _grow(b, 0, w["og2"], _tree_of(r0), True, np.zeros((0, 2), dtype=np.int32), c, "pipe1")
+    g, res = grow_checked(b, 0, w["og2"], tree_of(r0), True, np.zeros((0, 2), dtype=np.int32), c, "pipe1")
     assert g.j == g.j0 == len(w["ids"]) and res.i_switch == c["n"]
-    _goals_and_routes(b, 0, w["og2"], res)
+    goals_and_routes(b, 0, w["og2"], res)
     b.close()
     # what the batch cannot grow
     for kw in (dict(rewire=True), dict(dubins=True), dict(large_grid=True)):
         bb = _ffi.Batch(gpu_ctx, 1, 100, **kw)
-        _refused(_ffi.RRT_E_UNSUPPORTED, lambda: bb.grow(0, c["samples"][:5]))
+        refused_with_code(_ffi.RRT_E_UNSUPPORTED, lambda: bb.grow(0, c["samples"][:5]))
         bb.close()
 
 
 def test_an_informed_query_is_refused(gpu_ctx):
-    c = _base()
+    c = base()
     gpu_ctx.set_grid(c["og8"])
     b = _ffi.Batch(gpu_ctx, 1, 300, logs=True)
     Cm = hostprep.rotation_to_world_frame(np.asarray(c["xs"], dtype=np.int64), np.asarray(c["xg"], dtype=np.int64))
@@ -386,29 +258,16 @@ def test_an_informed_query_is_refused(gpu_ctx):
     b.launch()
     b.sync()
     assert b.get_result(0).j > 10
-    _refused(_ffi.RRT_E_UNSUPPORTED, lambda: b.grow(0, c["samples"][:5]))
+    refused_with_code(_ffi.RRT_E_UNSUPPORTED, lambda: b.grow(0, c["samples"][:5]))
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 8. the class
-def _class_goals_and_routes(p, og8, g, goals):
-    """RRT.connect_goals and RRT.routes_to (shortcut) against goalref / routeref on the restatement's grown arrays"""
-    v, cost = p.connect_goals(goals)
-    rv, rc, _ = goalref.connect(og8, g.pts, g.vcost, g.j, goals)
-    assert np.array_equal(v, rv) and np.array_equal(cost, rc) and (rv >= 0).sum() >= 8
-    want = routeref.routes(og8, g.pts, g.vcost, g.parent, g.j, goals, cut=True)
-    routes, length = p.routes_to(goals, shortcut=True)
-    assert np.array_equal(length, want[2]) and len(routes) == len(goals)
-    for k, r in enumerate(routes):
-        lo, hi = want[3][k], want[3][k + 1]
-        assert (r is None and lo == hi) or np.array_equal(r, want[4][lo:hi])
-
-
 def test_grow_after_a_plan_that_did_not_reach_its_goal():
     """plan() raises IndexError (the goal boxed in): the tree is resident, and this is the case grow is for.  grow on the same map
     raises the same way and still leaves the grown tree; after keep_tree on the map without the box a further grow reaches the goal,
     and row n of T is the goal of that plan()."""
-    c = _base()
+    c = base()
     og8, xs, xg = c["og8"], c["xs"], c["xg"]
     boxed = og8.copy()
     boxed[max(xg[0] - 4, 0):xg[0] + 5, max(xg[1] - 4, 0):xg[1] + 5] = 1
@@ -432,8 +291,8 @@ def test_grow_after_a_plan_that_did_not_reach_its_goal():
         p.grow(m1)
     assert p.rand_gen.bit_generator.state == twin.bit_generator.state and p._tree_resident == "device"
     assert np.array_equal(p.last_grow_ids, ids) and p.last_stats["j"] == g1.j and p.last_stats["sum_j"] == g1.sum_j
-    goals = _goals(boxed)
-    _class_goals_and_routes(p, boxed, g1, goals)
+    goals = mixed_goals(boxed)
+    class_goals_and_routes(p, boxed, g1, goals)
     # 2. the box gone: keep_tree, then grow into the room that is left
     alive = p.keep_tree(og8.astype(np.int64))
     assert np.array_equal(alive, keepref.alive(og8, g1.pts, g1.parent, g1.j)) and alive.all()
@@ -448,12 +307,12 @@ def test_grow_after_a_plan_that_did_not_reach_its_goal():
     assert gv == vg == g2.vgoal and len(pts) == g2.rows == N + 1 and np.array_equal(pts[N], xg) and vc[N] == g2.vcost[g2.j]
     assert np.array_equal(pts[:live], g2.pts[:live]) and np.array_equal(par, g2.parent[:live])
     assert np.array_equal(np.asarray(vc[:live]).view(np.int64), g2.vcost[:live].view(np.int64))
-    _class_goals_and_routes(p, og8, g2, _goals(og8))
+    class_goals_and_routes(p, og8, g2, mixed_goals(og8))
 
 
 def test_rrtstar_grow_is_the_restatement_fed_with_the_same_draws():
-    c = _base()
-    w = _wall(c)
+    c = base()
+    w = wall(c)
     og = c["og8"].astype(np.int64)
     og2 = w["og2"].astype(np.int64)
     p = amd.RRTStar(og, N, RR, pbar=False, seed=3)
@@ -481,15 +340,15 @@ def test_rrtstar_grow_is_the_restatement_fed_with_the_same_draws():
     assert np.array_equal(np.asarray(vc2[:g.j + g.found]).view(np.int64), g.vcost[:g.j + g.found].view(np.int64))
     if g.found:
         assert np.array_equal(pts2[N], c["xg"]) and vc2[N] == g.vcost[g.j]
-    goals = _goals(w["og2"])
-    _class_goals_and_routes(p, w["og2"], g, goals)
+    goals = mixed_goals(w["og2"])
+    class_goals_and_routes(p, w["og2"], g, goals)
     T3, gv3 = p.grow(0)  # a further grow on the grown tree: nothing new, the same tree
     assert np.array_equal(p.last_grow_ids, np.arange(g.j)) and np.array_equal(T3.__dict__["_lazy"][2], par2)
 
 
 def test_the_classes_that_do_not_grow():
     """with a tree on the device (tests/test_grow_cpu.py has the same refusals, and the Dubins planner's, before any plan)"""
-    c = _base()
+    c = base()
     og = c["og8"].astype(np.int64)
     for p in (amd.RRTStarInformed(og, N, RR, 10, pbar=False), amd.RRTStar(og, N, RR, pbar=False, rewire="correct")):
         try:

@@ -2,7 +2,6 @@
 test_grow_poses_gpu.py worth something -- asserted on the restatement alone --, the binding, and the planners' refusals before any
 device call."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
@@ -11,25 +10,12 @@ import oracle
 import posegrowref
 import posekeepref
 import poseref
-from rrtplanner_amd import _ffi, hostprep
+from posecalls import assert_audit_clean
+from rrtplanner_amd import _ffi
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
 
 WORKLOADS = ["A", "D", "E", "G1", "G256"]
-
-
-def _more(w, og8, m, seed=31):
-    """m pose samples drawn as plan() draws its n: the free cells first, then the headings"""
-    rng = np.random.default_rng(seed)
-    cells = hostprep.draw_free_samples(rng, np.argwhere(og8 == 0), m)
-    return np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), rng.integers(0, w.nh, m)])
-
-
-@functools.lru_cache(maxsize=None)
-def _planted(name):
-    k = posekeepref.changed(name)
-    s, rows, row_start, row_ob = posegrowref.planted_stream(k)
-    return k, s, rows, row_start, row_ob, posegrowref.grow_workload(k.w, k.og8, k.alive, s)
 
 
 # ------------------------------------------------------------------------------------------------ a grown uncut tree IS the longer plan
@@ -38,7 +24,7 @@ def test_an_uncut_tree_grown_is_the_oracles_plan_of_the_longer_stream(name):
     w = poseref.workload(name)
     m = min(w.n - w.j, 300)
     assert m >= 100 and w.j > 64
-    s = _more(w, w.og8, m)
+    s = posegrowref.more_poses(w, w.og8, m)
     g = posegrowref.grow_workload(w, w.og8, None, s)
     st, rl = oracle.dubins_plan(w.og8, w.n + m, w.star, w.xs, w.xg, np.concatenate([w.samples, s[:, :2]]), np.concatenate([w.heads, s[:, 2]]),
                                 r2_rewire=w.r2, rho=w.rho, nh=w.nh)
@@ -58,18 +44,16 @@ def test_an_uncut_tree_grown_is_the_oracles_plan_of_the_longer_stream(name):
 
 
 def test_the_stream_of_the_audited_grow_is_one_the_audit_policy_takes():
-    """The GPU test sends the tree of uncut A grown by 600 samples through oracle/dubins_ref.c's audit under test_dubins.py's policy.
+    """The GPU test sends the tree of uncut A grown by 600 samples through oracle/dubins_ref.c's audit under posecalls.assert_audit_clean's policy.
     How many decisions fall into the audit's ambiguous classes is a property of the stream: the oracle's OWN tree of this one has to
     pass the policy, or no device could."""
-    from test_dubins import _assert_audit_clean
-
     w = poseref.workload("A")
-    s = _more(w, w.og8, 600, seed=posegrowref.UNCUT_A_SEED)
+    s = posegrowref.more_poses(w, w.og8, 600, seed=posegrowref.UNCUT_A_SEED)
     samples, heads = np.concatenate([w.samples, s[:, :2]]), np.concatenate([w.heads, s[:, 2]])
     st, rl = oracle.dubins_plan(w.og8, w.n + 600, w.star, w.xs, w.xg, samples, heads, r2_rewire=w.r2, rho=w.rho, nh=w.nh)
     a = oracle.dubins_audit(w.og8, w.n + 600, w.star, samples, heads, rl.pts, rl.head, rl.vcost, rl.parent, rl.j, r2_rewire=w.r2, rho=w.rho, nh=w.nh)
     assert a["n_accepted"] == rl.j - 1 and rl.j > w.j + 100 and w.j % 128 != 0
-    _assert_audit_clean(a, w.star)
+    assert_audit_clean(a, w.star)
 
 
 # ------------------------------------------------------------------------------------------------ what the cut workloads show
@@ -92,7 +76,7 @@ def test_a_random_stream_is_accepted_in_part_and_misses_the_cut_cells(name):
     k = posekeepref.changed(name)
     w = k.w
     m = int((~k.alive).sum())
-    s = _more(w, k.og8, m, seed=78)
+    s = posegrowref.more_poses(w, k.og8, m, seed=78)
     g = posegrowref.grow_workload(w, k.og8, k.alive, s)
     assert 0.20 <= g.accept_log.mean() <= 0.65, (name, g.accept_log.mean())
     cut_cells = {(int(x), int(y)) for x, y in w.ro.pts[:w.j][~k.alive]}
@@ -102,7 +86,7 @@ def test_a_random_stream_is_accepted_in_part_and_misses_the_cut_cells(name):
 
 @pytest.mark.parametrize("name", WORKLOADS)
 def test_the_planted_stream_lands_on_cut_cells_and_on_the_start(name):
-    k, s, rows, row_start, row_ob, g = _planted(name)
+    k, s, rows, row_start, row_ob, g = posegrowref.planted(name)
     w = k.w
     assert len(s) == int((~k.alive).sum()) == len(g.accept_log) and g.j0 == int(k.alive.sum()) and g.j0 + len(s) <= w.n
     cut_cells = {(int(x), int(y)) for x, y in w.ro.pts[:w.j][~k.alive]}
@@ -134,7 +118,7 @@ def test_the_seed_keeps_order_costs_and_headings_and_renumbers_parents():
 def test_go2goal_fallbacks_follow_the_querys_own_n():
     w = poseref.workload("F")  # rho too wide for the map: the tree is the start alone and nothing connects
     assert w.j == 1 and not w.ro.found
-    s = _more(w, w.og8, 3)
+    s = posegrowref.more_poses(w, w.og8, 3)
     g = posegrowref.grow_workload(w, w.og8, None, s)
     assert g.j == 1 and not g.found and g.status == posegrowref.ST_UNREACHABLE and g.vgoal == 0 and g.rows == w.n
 

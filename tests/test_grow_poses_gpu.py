@@ -17,78 +17,16 @@ import posegrowref
 import posekeepref
 import poseref
 import poseroutesref
+from posecalls import GROW_KERNELS, assert_audit_clean, grow_poses_checked, planned_logged_batch
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.dubins import RRTStarDubins
-from test_connect_poses_gpu import _query, _refused
-from test_dubins import _assert_audit_clean
+from treecalls import refused_with_word, tree_of
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = {"block": (False, "rrt_dubins_block_kernel"), "serial": (True, "rrt_expand_kernel<false, true>")}
 WORKLOADS = ["A", "D", "E", "G1", "G256"]
 STRIDE_J0 = (1, 2, 63, 64, 65, 1023, 1024, 1025)
 STRIDE_PAD = (71, 10)  # a cell of poseref._stride_map()'s wall
-
-
-def _more(w, og8, m, seed=31):
-    rng = np.random.default_rng(seed)
-    cells = hostprep.draw_free_samples(rng, np.argwhere(og8 == 0), m)
-    return np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), rng.integers(0, w.nh, m)])
-
-
-def _run(ctx, w, kernel, Q=1, stream=None):
-    """workload w in every query of a batch of its own, launched and synchronised, its trees the oracle's; stream: (samples, headings,
-    n) in place of the workload's"""
-    ctx.set_grid(w.og8)
-    samples, heads, n = stream if stream is not None else (w.samples, w.heads, w.n)
-    b = _ffi.Batch(ctx, Q, n, logs=True, dubins=True, serial=KERNELS[kernel][0])
-    keep = []
-    for q in range(Q):
-        qu, k = _ffi.make_query(_ffi.ALG_DUBINS_STAR if w.star else _ffi.ALG_DUBINS, n, w.xs, w.xg, samples, r2_rewire=w.r2, headings=heads, rho=w.rho,
-                                nh=w.nh)
-        keep.append(k)
-        b.set_query(q, qu)
-    b.launch()
-    b.sync()
-    for q in range(Q):
-        res = b.get_result(q)
-        j = w.j
-        assert res.j == j and np.array_equal(res.parent[:j], w.ro.parent[:j]) and np.array_equal(res.head[:j], w.ro.head[:j])
-        assert np.array_equal(res.vcost[:j].view(np.int64), w.ro.vcost[:j].view(np.int64))
-    b.own_n = n
-    return b
-
-
-def _tree_of(r):
-    """(pts, head, parent, vcost, j) of a result or a restatement"""
-    return np.array(r.pts, dtype=np.int64), np.array(r.head, dtype=np.int64), np.array(r.parent, dtype=np.int64), np.array(r.vcost), r.j
-
-
-def _same_result(res, g, log0):
-    live = g.j + g.found
-    assert (res.status, res.j, res.found, res.vgoal, res.rows) == (g.status, g.j, g.found, g.vgoal, g.rows)
-    assert np.array_equal(res.pts[:live], g.pts[:live]) and np.array_equal(res.head[:live], g.head[:live])
-    assert np.array_equal(res.parent[:live], g.parent[:live])
-    assert np.array_equal(res.vcost[:live].view(np.int64), g.vcost[:live].view(np.int64))
-    m = len(g.accept_log)
-    assert np.array_equal(res.nearest_log[log0:log0 + m], g.nearest_log) and np.array_equal(res.accept_log[log0:log0 + m], g.accept_log)
-    assert np.array_equal(res.j_log[log0:log0 + m], g.jlog)
-    # the statistics test_dubins.py compares between device and oracle; they count the grown iterations alone
-    assert (res.sum_j, res.sum_cells_nn, res.sum_near) == (g.sum_j, g.sum_cells_nn, g.sum_near)
-
-
-def _grow(b, q, w, g, ids, samples, kernel):
-    """one grow_poses of query q, launched, against the restatement g whose seed has the original numbers ids"""
-    j0, old_id, log0 = b.grow_poses(q, samples)
-    assert j0 == len(ids) == log0 == g.j0 and old_id.dtype == np.int32 and np.array_equal(old_id, ids)
-    b.launch()
-    b.sync()
-    res = b.get_result(q)
-    _same_result(res, g, log0)
-    assert b.team()[1] == 0 and b.kernel_name() == KERNELS[kernel][1], b.kernel_name()  # team_fallbacks == 0: this kernel ran it all
-    ms = b.grow_ms()
-    assert len(ms) == 3 and all(t >= 0.0 for t in ms)
-    return res
 
 
 def _poses_and_routes(b, q, og8, w, g, goals, connected=4):
@@ -101,46 +39,39 @@ def _poses_and_routes(b, q, og8, w, g, goals, connected=4):
 
 
 @functools.lru_cache(maxsize=None)
-def _planted(name):
-    k = posekeepref.changed(name)
-    s = posegrowref.planted_stream(k)[0]
-    return k, s, posegrowref.grow_workload(k.w, k.og8, k.alive, s)
-
-
-@functools.lru_cache(maxsize=None)
 def _uncut_a():
     w = poseref.workload("A")
-    s = _more(w, w.og8, 600, seed=posegrowref.UNCUT_A_SEED)
+    s = posegrowref.more_poses(w, w.og8, 600, seed=posegrowref.UNCUT_A_SEED)
     return w, s, posegrowref.grow_workload(w, w.og8, None, s)
 
 
 # ------------------------------------------------------------------------------------------------ 1. the cut workloads, planted streams
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 @pytest.mark.parametrize("name", WORKLOADS)
 def test_a_kept_tree_grows_back_behind_the_blocks(gpu_ctx, name, kernel):
-    k, s, g = _planted(name)
+    k, s, _, _, _, g = posegrowref.planted(name)
     w = k.w
-    b = _run(gpu_ctx, w, kernel)
+    b = planned_logged_batch(gpu_ctx, w, kernel)
     gpu_ctx.set_grid(k.og8)
     assert np.array_equal(b.keep_pose_tree(0), k.alive)
-    _grow(b, 0, w, g, g.ids, s, kernel)
+    grow_poses_checked(b, 0, w, g, g.ids, s, kernel)
     if name == "A":
         _poses_and_routes(b, 0, k.og8, w, g, w.goals)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 2. nothing cut, more than a ring
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 def test_an_uncut_tree_grown_by_600_samples_is_audited(gpu_ctx, kernel):
     w, s, g = _uncut_a()
     assert g.j0 % 128 != 0 and len(s) == 600 > 128 and g.j > g.j0 + 64  # more than DB_RING samples from a j0 that is no multiple of it
-    b = _run(gpu_ctx, w, kernel)
-    res = _grow(b, 0, w, g, np.arange(w.j), s, kernel)
+    b = planned_logged_batch(gpu_ctx, w, kernel)
+    res = grow_poses_checked(b, 0, w, g, np.arange(w.j), s, kernel)
     _poses_and_routes(b, 0, w.og8, w, g, w.goals)
     a = oracle.dubins_audit(w.og8, w.n + 600, w.star, np.concatenate([w.samples, s[:, :2]]), np.concatenate([w.heads, s[:, 2]]), res.pts, res.head, res.vcost,
                             res.parent, res.j, r2_rewire=w.r2, rho=w.rho, nh=w.nh)
     assert a["n_accepted"] == res.j - 1
-    _assert_audit_clean(a, w.star)
+    assert_audit_clean(a, w.star)
     b.close()
 
 
@@ -151,12 +82,12 @@ def test_seeds_around_the_lane_wave_and_workgroup_edges(gpu_ctx, j0):
         w = poseref.stride_tree(j0, star)
         assert w.j == j0
         stream = posegrowref.accepted_stream(w, STRIDE_PAD, 48)
-        s = _more(w, w.og8, 40, seed=j0)
+        s = posegrowref.more_poses(w, w.og8, 40, seed=j0)
         g = posegrowref.grow_workload(w, w.og8, None, s, n=stream[2])
         assert g.j0 == j0 and (g.j > g.j0 or j0 == 1)
-        for kernel in KERNELS:
-            b = _run(gpu_ctx, w, kernel, stream=stream)
-            _grow(b, 0, w, g, np.arange(j0), s, kernel)
+        for kernel in GROW_KERNELS:
+            b = planned_logged_batch(gpu_ctx, w, kernel, stream=stream)
+            grow_poses_checked(b, 0, w, g, np.arange(j0), s, kernel)
             b.close()
 
 
@@ -166,37 +97,37 @@ def test_a_cut_stride_tree_across_a_workgroup_of_the_seed_kernels(gpu_ctx):
     w = k.w
     assert k.alive.sum() > 256 and (~k.alive).sum() > 64
     stream = posegrowref.accepted_stream(w, STRIDE_PAD, 48)
-    s = _more(w, k.og8, 40, seed=3)
+    s = posegrowref.more_poses(w, k.og8, 40, seed=3)
     g = posegrowref.grow_workload(w, k.og8, k.alive, s, n=stream[2])
-    for kernel in KERNELS:
-        b = _run(gpu_ctx, w, kernel, stream=stream)
+    for kernel in GROW_KERNELS:
+        b = planned_logged_batch(gpu_ctx, w, kernel, stream=stream)
         gpu_ctx.set_grid(k.og8)
         assert np.array_equal(b.keep_pose_tree(0), k.alive)
-        _grow(b, 0, w, g, g.ids, s, kernel)
+        grow_poses_checked(b, 0, w, g, g.ids, s, kernel)
         b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4. no sample, one sample
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 @pytest.mark.parametrize("m", [0, 1])
 def test_no_sample_is_go2goal_alone_and_one_sample(gpu_ctx, m, kernel):
     k = posekeepref.changed("E")
     w = k.w
     s = posegrowref.planted_stream(k)[0]
-    first = int(np.flatnonzero(_planted("E")[2].accept_log)[0])  # a sample the seed accepts
+    first = int(np.flatnonzero(posegrowref.planted("E")[5].accept_log)[0])  # a sample the seed accepts
     s = s[first:first + m]
     g = posegrowref.grow_workload(w, k.og8, k.alive, s)
     assert g.j == g.j0 + m
-    b = _run(gpu_ctx, w, kernel)
+    b = planned_logged_batch(gpu_ctx, w, kernel)
     gpu_ctx.set_grid(k.og8)
     b.keep_pose_tree(0)
-    res = _grow(b, 0, w, g, g.ids, s, kernel)
+    res = grow_poses_checked(b, 0, w, g, g.ids, s, kernel)
     assert (res.sum_j, res.sum_near) == ((0, 0) if m == 0 else (g.j0, g.sum_near))
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 5. the query filled exactly
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 def test_a_stream_that_fills_the_query_exactly(gpu_ctx, kernel):
     w, s = posegrowref.fill_exactly()
     assert w.j == posegrowref.FILL_J and w.j + len(s) == w.n
@@ -205,11 +136,11 @@ def test_a_stream_that_fills_the_query_exactly(gpu_ctx, kernel):
     short = posegrowref.grow_workload(w, w.og8, None, s[:-1])
     assert short.j == w.n - 1 and not short.found and short.status == posegrowref.ST_UNREACHABLE  # the fall-back goes by the query's own n
     for g, stream in ((full, s), (short, s[:-1])):
-        b = _run(gpu_ctx, w, kernel)
-        res = _grow(b, 0, w, g, np.arange(w.j), stream, kernel)
+        b = planned_logged_batch(gpu_ctx, w, kernel)
+        res = grow_poses_checked(b, 0, w, g, np.arange(w.j), stream, kernel)
         assert res.status == (_ffi.RRT_OK if g is full else _ffi.RRT_E_GOAL_UNREACHABLE)
         if g is full:
-            _refused(_ffi.RRT_E_ARG, "room for 0", b.grow_poses, 0, s[:1])
+            refused_with_word(_ffi.RRT_E_ARG, "room for 0", b.grow_poses, 0, s[:1])
             j0, _, _ = b.grow_poses(0, s[:0])  # ... and none is asked for: go2goal alone, on a full tree
             assert j0 == w.n
             b.launch()
@@ -219,75 +150,75 @@ def test_a_stream_that_fills_the_query_exactly(gpu_ctx, kernel):
 
 
 # ------------------------------------------------------------------------------------------------ 6. the root blocked
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 def test_a_blocked_root_is_refused_and_the_tree_stays(gpu_ctx, kernel):
     w = poseref.workload("E")
     k = posekeepref.root_blocked(w)
-    b = _run(gpu_ctx, w, kernel)
+    b = planned_logged_batch(gpu_ctx, w, kernel)
     before = b.get_result(0)
     gpu_ctx.set_grid(k.og8)
     assert not b.keep_pose_tree(0).any()
-    _refused(_ffi.RRT_E_ARG, "rrt_batch_grow_poses: no vertex of query 0 is alive", b.grow_poses, 0, _more(w, k.og8, 5))
+    refused_with_word(_ffi.RRT_E_ARG, "rrt_batch_grow_poses: no vertex of query 0 is alive", b.grow_poses, 0, posegrowref.more_poses(w, k.og8, 5))
     after = b.get_result(0)
     for name in ("pts", "vcost", "parent", "head"):
         assert np.array_equal(getattr(before, name), getattr(after, name))
     assert (after.status, after.j, after.found, after.vgoal) == (before.status, before.j, before.found, before.vgoal)
     gpu_ctx.set_grid(w.og8)  # the first map again: every vertex is back, and the tree grows
     assert b.keep_pose_tree(0).all()
-    s = _more(w, w.og8, 30)
-    _grow(b, 0, w, posegrowref.grow_workload(w, w.og8, None, s), np.arange(w.j), s, kernel)
+    s = posegrowref.more_poses(w, w.og8, 30)
+    grow_poses_checked(b, 0, w, posegrowref.grow_workload(w, w.og8, None, s), np.arange(w.j), s, kernel)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 7. grown twice; kept, grown, kept, grown
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 def test_two_grows_in_a_row(gpu_ctx, kernel):
     w = poseref.workload("E")
-    s1, s2 = _more(w, w.og8, 50, seed=41), _more(w, w.og8, 50, seed=42)
+    s1, s2 = posegrowref.more_poses(w, w.og8, 50, seed=41), posegrowref.more_poses(w, w.og8, 50, seed=42)
     g1 = posegrowref.grow_workload(w, w.og8, None, s1)
-    pts, head, parent, vcost, j = _tree_of(g1)
+    pts, head, parent, vcost, j = tree_of(g1)
     ids, sp, sh, sc, spar = posegrowref.seed(pts, head, parent, vcost, j)
     g2 = posegrowref.grow(w.og8, w.star, w.n, w.xg, w.r2, w.rho, w.nh, sp, sh, sc, spar, s2)
     assert g1.j > g1.j0 and g2.j0 == g1.j and g2.j > g2.j0
-    b = _run(gpu_ctx, w, kernel)
-    _grow(b, 0, w, g1, np.arange(w.j), s1, kernel)
-    _grow(b, 0, w, g2, ids, s2, kernel)
+    b = planned_logged_batch(gpu_ctx, w, kernel)
+    grow_poses_checked(b, 0, w, g1, np.arange(w.j), s1, kernel)
+    grow_poses_checked(b, 0, w, g2, ids, s2, kernel)
     b.close()
 
 
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 def test_kept_grown_kept_on_a_third_map_and_grown(gpu_ctx, kernel):
-    k, s1, g1 = _planted("A")
+    k, s1, _, _, _, g1 = posegrowref.planted("A")
     w = k.w
     og3 = posekeepref.blocks_map(w.og8, w.xs, seed=8)
-    pts, head, parent, vcost, j = _tree_of(g1)
+    pts, head, parent, vcost, j = tree_of(g1)
     alive3 = posekeepref.alive(og3, pts, head, parent, j, w.rho, w.nh)
     ids, sp, sh, sc, spar = posegrowref.seed(pts, head, parent, vcost, j, alive3)
-    s2 = _more(w, og3, j - len(ids), seed=43)
+    s2 = posegrowref.more_poses(w, og3, j - len(ids), seed=43)
     g2 = posegrowref.grow(og3, w.star, w.n, w.xg, w.r2, w.rho, w.nh, sp, sh, sc, spar, s2)
     assert 8 < len(ids) < j - 8 and g2.j > g2.j0 and not np.array_equal(og3, k.og8)
-    b = _run(gpu_ctx, w, kernel)
+    b = planned_logged_batch(gpu_ctx, w, kernel)
     gpu_ctx.set_grid(k.og8)
     assert np.array_equal(b.keep_pose_tree(0), k.alive)
-    _grow(b, 0, w, g1, g1.ids, s1, kernel)
+    grow_poses_checked(b, 0, w, g1, g1.ids, s1, kernel)
     gpu_ctx.set_grid(og3)
-    _refused(_ffi.RRT_E_ARG, "not kept on it (rrt_batch_keep_pose_tree)", b.grow_poses, 0, s2)
+    refused_with_word(_ffi.RRT_E_ARG, "not kept on it (rrt_batch_keep_pose_tree)", b.grow_poses, 0, s2)
     assert np.array_equal(b.keep_pose_tree(0), alive3)
-    _grow(b, 0, w, g2, ids, s2, kernel)
+    grow_poses_checked(b, 0, w, g2, ids, s2, kernel)
     _poses_and_routes(b, 0, og3, w, g2, w.goals, connected=1)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 8. one query of three
-@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("kernel", list(GROW_KERNELS))
 def test_one_query_of_three_grows_and_the_others_stay(gpu_ctx, kernel):
-    k, s, g = _planted("E")
+    k, s, _, _, _, g = posegrowref.planted("E")
     w = k.w
-    b = _run(gpu_ctx, w, kernel, Q=3)
+    b = planned_logged_batch(gpu_ctx, w, kernel, Q=3)
     before = [b.get_result(q) for q in range(3)]
     gpu_ctx.set_grid(k.og8)
     assert np.array_equal(b.keep_pose_tree(1), k.alive)
-    _grow(b, 1, w, g, g.ids, s, kernel)
+    grow_poses_checked(b, 1, w, g, g.ids, s, kernel)
     for q in (0, 2):
         after = b.get_result(q)
         for name in ("pts", "vcost", "parent", "head", "nearest_log", "accept_log", "j_log"):
@@ -300,11 +231,11 @@ def test_one_query_of_three_grows_and_the_others_stay(gpu_ctx, kernel):
 def test_a_launch_after_set_grid_on_another_map_is_refused_and_rearm_lifts_it(gpu_ctx):
     k = posekeepref.changed("E")
     w = k.w
-    b = _run(gpu_ctx, w, "block")
-    s = _more(w, w.og8, 40)
+    b = planned_logged_batch(gpu_ctx, w, "block")
+    s = posegrowref.more_poses(w, w.og8, 40)
     j0, _, _ = b.grow_poses(0, s)
     gpu_ctx.set_grid(k.og8)
-    _refused(_ffi.RRT_E_ARG, "seeded by rrt_batch_grow", b.launch)
+    refused_with_word(_ffi.RRT_E_ARG, "seeded by rrt_batch_grow", b.launch)
     b.rearm()  # drops the grow: the query runs again from its sample buffer as it then stands, rows [j0, j0 + m) replaced
     b.launch()
     b.sync()
@@ -326,28 +257,28 @@ def _raw(b, q, s, m):
 def test_refusals_name_the_call_and_change_nothing(gpu_ctx):
     w = poseref.workload("E")
     W, H = w.og8.shape
-    b = _run(gpu_ctx, w, "block")
+    b = planned_logged_batch(gpu_ctx, w, "block")
     before = b.get_result(0)
-    ok = _more(w, w.og8, 4)
+    ok = posegrowref.more_poses(w, w.og8, 4)
     who = "rrt_batch_grow_poses: "
     bad = ok.copy()
     bad[2, 2] = w.nh
-    _refused(_ffi.RRT_E_ARG, who + f"sample 2 has heading {w.nh}, query 0 has headings [0, {w.nh})", b.grow_poses, 0, bad)
+    refused_with_word(_ffi.RRT_E_ARG, who + f"sample 2 has heading {w.nh}, query 0 has headings [0, {w.nh})", b.grow_poses, 0, bad)
     bad[2, 2] = -1
-    _refused(_ffi.RRT_E_ARG, who + "sample 2 has heading -1", b.grow_poses, 0, bad)
+    refused_with_word(_ffi.RRT_E_ARG, who + "sample 2 has heading -1", b.grow_poses, 0, bad)
     bad = ok.copy()
     bad[1, 0] = W
-    _refused(_ffi.RRT_E_ARG, who + f"sample 1 = ({W}, {bad[1, 1]}) outside the {W}x{H} grid", b.grow_poses, 0, bad)
-    _refused(_ffi.RRT_E_ARG, who + "m=-1", _raw, b, 0, np.ascontiguousarray(ok, dtype=np.int32), -1)
+    refused_with_word(_ffi.RRT_E_ARG, who + f"sample 1 = ({W}, {bad[1, 1]}) outside the {W}x{H} grid", b.grow_poses, 0, bad)
+    refused_with_word(_ffi.RRT_E_ARG, who + "m=-1", _raw, b, 0, np.ascontiguousarray(ok, dtype=np.int32), -1)
     room = w.n - w.j
-    _refused(_ffi.RRT_E_ARG, who + f"{w.j} vertices and m={room + 1} samples exceed the query's n={w.n}: room for {room}", b.grow_poses, 0, _more(w, w.og8, room + 1))
-    _refused(_ffi.RRT_E_ARG, who + "q=1 of 1", b.grow_poses, 1, ok)
+    refused_with_word(_ffi.RRT_E_ARG, who + f"{w.j} vertices and m={room + 1} samples exceed the query's n={w.n}: room for {room}", b.grow_poses, 0, posegrowref.more_poses(w, w.og8, room + 1))
+    refused_with_word(_ffi.RRT_E_ARG, who + "q=1 of 1", b.grow_poses, 1, ok)
     # the straight-line call keeps its answer for a Dubins batch
-    _refused(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_grow: a Dubins batch (the seed kernels carry no headings)", b.grow, 0, ok[:, :2])
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_grow: a Dubins batch (the seed kernels carry no headings)", b.grow, 0, ok[:, :2])
     gpu_ctx.set_grid(np.zeros((W + 1, H), dtype=np.uint8))
-    _refused(_ffi.RRT_E_ARG, who + "the context's grid changed shape since the batch was created", b.grow_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_ARG, who + "the context's grid changed shape since the batch was created", b.grow_poses, 0, ok)
     gpu_ctx.set_grid(w.og8)
-    _refused(_ffi.RRT_E_ARG, "not kept on it (rrt_batch_keep_pose_tree)", b.grow_poses, 0, ok)  # the same cells, another generation
+    refused_with_word(_ffi.RRT_E_ARG, "not kept on it (rrt_batch_keep_pose_tree)", b.grow_poses, 0, ok)  # the same cells, another generation
     assert b.keep_pose_tree(0).all()
     after = b.get_result(0)
     for name in ("pts", "vcost", "parent", "head"):
@@ -358,20 +289,20 @@ def test_refusals_name_the_call_and_change_nothing(gpu_ctx):
     b.close()
     # an unfinished query, and a batch that is not a Dubins batch
     u = _ffi.Batch(gpu_ctx, 1, w.n, dubins=True)
-    qu, keep = _query(w)
+    qu, keep = poseref.device_query(w)
     u.set_query(0, qu)
-    _refused(_ffi.RRT_E_ARG, who + "query 0 has not finished", u.grow_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_ARG, who + "query 0 has not finished", u.grow_poses, 0, ok)
     u.close()
     p = _ffi.Batch(gpu_ctx, 1, 100)
-    _refused(_ffi.RRT_E_UNSUPPORTED, who + "not a Dubins batch (its samples are cells and its edges straight lines: use rrt_batch_grow)", p.grow_poses, 0, ok)
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, who + "not a Dubins batch (its samples are cells and its edges straight lines: use rrt_batch_grow)", p.grow_poses, 0, ok)
     p.close()
 
 
 def test_through_rrt_plan(gpu_ctx):
-    k, s, g = _planted("D")  # RRTDubins: the planner without a near set
+    k, s, _, _, _, g = posegrowref.planted("D")  # RRTDubins: the planner without a near set
     w = k.w
     gpu_ctx.set_grid(w.og8)
-    qu, keep = _query(w)
+    qu, keep = poseref.device_query(w)
     rc, res = gpu_ctx.plan(qu, w.n)
     assert rc == w.status and res.j == w.j
     gpu_ctx.set_grid(k.og8)

@@ -13,28 +13,15 @@ import oracle
 import poseref
 import posekeepref
 from rrtplanner_amd import _ffi, hostprep
-from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
+from rrtplanner_amd.dubins import RRTStarDubins
+from posecalls import planned_batch
 from rrtplanner_amd.oggen import DeviceGrids
-from test_connect_poses_gpu import _query, _refused
+from treecalls import refused_with_word
 
 pytestmark = pytest.mark.gpu
 
 INF = np.inf
 WORKLOADS = ["E", "D", "A", "B"]
-
-
-def _run(ctx, w, serial=False):
-    """workload w on a batch of its own, launched and synchronised, its tree the oracle's"""
-    ctx.set_grid(w.og8)
-    b = _ffi.Batch(ctx, 1, w.n, dubins=True, serial=serial)
-    q, keep = _query(w)
-    b.set_query(0, q)
-    b.launch()
-    b.sync()
-    res = b.get_result(0)
-    assert res.status == w.status and res.j == w.j
-    assert np.array_equal(res.parent[:w.j], w.ro.parent[:w.j]) and np.array_equal(res.head[:w.j], w.ro.head[:w.j])
-    return b
 
 
 def _same(alive, got, k):
@@ -48,16 +35,10 @@ def _same(alive, got, k):
 
 def _keep_on_a_batch(ctx, k, serial=False):
     w = k.w
-    b = _run(ctx, w, serial)
+    b = planned_batch(ctx, w, serial)
     ctx.set_grid(k.og8)
     _same(b.keep_pose_tree(0), b.connect_poses(0, w.goals), k)
     return b
-
-
-def _planner(w):
-    r = poseref.SPECS[w.name][4]
-    args = (w.og, w.n) + ((r,) if w.star else ()) + (w.rho,)
-    return (RRTStarDubins if w.star else RRTDubins)(*args, n_headings=w.nh, pbar=False, seed=poseref.SPECS[w.name][7])
 
 
 # ------------------------------------------------------------------------------------------------ 1. the workloads, three ways
@@ -76,11 +57,11 @@ def test_workloads_through_rrt_plan(gpu_ctx, name):
     k = posekeepref.changed(name)
     w = k.w
     gpu_ctx.set_grid(w.og8)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     rc, res = gpu_ctx.plan(q, w.n)
     assert rc == w.status and res.j == w.j
     gpu_ctx.set_grid(k.og8)
-    _refused(_ffi.RRT_E_ARG, "replaced", gpu_ctx.connect_poses, w.goals)
+    refused_with_word(_ffi.RRT_E_ARG, "replaced", gpu_ctx.connect_poses, w.goals)
     _same(gpu_ctx.keep_pose_tree(), gpu_ctx.connect_poses(w.goals), k)
     assert len(gpu_ctx.keep_tree_ms()) == 3
 
@@ -89,7 +70,7 @@ def test_workloads_through_rrt_plan(gpu_ctx, name):
 def test_workloads_through_the_planners(name):
     k = posekeepref.changed(name)
     w = k.w
-    p = _planner(w)
+    p = poseref.planner_of(w)
     T, gv = p.plan(np.array(w.xs), np.array(w.xg))
     assert p.last_stats["j"] == w.j  # the planner draws the workload's stream: its tree is the oracle's
     og2 = k.og8.astype(np.int64)
@@ -170,7 +151,7 @@ def test_a_blocked_root_leaves_nothing(gpu_ctx):
 def test_keeping_the_tree_for_the_first_map_again_restores_every_answer(gpu_ctx):
     k = posekeepref.changed("A")
     w = k.w
-    b = _run(gpu_ctx, w)
+    b = planned_batch(gpu_ctx, w)
     first = b.connect_poses(0, w.goals)
     before = b.get_result(0)
     gpu_ctx.set_grid(k.og8)
@@ -189,8 +170,8 @@ def test_keeping_the_tree_for_the_first_map_again_restores_every_answer(gpu_ctx)
         assert np.array_equal(getattr(before, name), getattr(after, name))
     # rearm drops the view: the query is unfinished, then runs again on the new map and answers over its whole new tree
     b.rearm()
-    _refused(_ffi.RRT_E_ARG, "not finished", b.keep_pose_tree, 0)
-    _refused(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.keep_pose_tree, 0)
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.connect_poses, 0, w.goals)
     b.launch()
     b.sync()
     new = b.get_result(0)
@@ -218,7 +199,7 @@ def test_one_query_of_a_batch_is_kept_and_the_others_stay_refused(gpu_ctx):
         goals = np.column_stack([free[rng.integers(0, len(free), 10)], rng.integers(0, nh, 10)])
         m = poseref.made(f"three {q}", w.og8, n, star, 12, rho, nh, xs, xg, samples, heads, goals)
         made.append(m)
-        qu, keep = _query(m)
+        qu, keep = poseref.device_query(m)
         keeps.append(keep)
         b.set_query(q, qu)
     b.launch()
@@ -227,17 +208,17 @@ def test_one_query_of_a_batch_is_kept_and_the_others_stay_refused(gpu_ctx):
         assert b.get_result(q).j == m.j > 30
     gpu_ctx.set_grid(og2)
     for q, m in enumerate(made):
-        _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, q, m.goals)
+        refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_poses, q, m.goals)
     ks = [posekeepref.kept(m, og2) for m in made]
     _same(b.keep_pose_tree(1), b.connect_poses(1, made[1].goals), ks[1])
     assert 0 < ks[1].alive.sum() < made[1].j
     for q in (0, 2):
-        _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, q, made[q].goals)
+        refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_poses, q, made[q].goals)
     # a second query kept next to the first: each has its own view
     _same(b.keep_pose_tree(2), b.connect_poses(2, made[2].goals), ks[2])
     v, c = b.connect_poses(1, made[1].goals)
     assert np.array_equal(v, ks[1].vertex) and np.array_equal(c, ks[1].cost)
-    _refused(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, made[0].goals)
+    refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_poses, 0, made[0].goals)
     _same(b.keep_pose_tree(0), b.connect_poses(0, made[0].goals), ks[0])
     b.close()
 
@@ -258,7 +239,7 @@ def test_two_resident_frames(gpu_ctx):
     grids.select(0)
     generation = gpu_ctx.grid_generation()
     b = _ffi.Batch(gpu_ctx, 1, n, dubins=True)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     b.set_query(0, q)
     b.launch()
     b.sync()
@@ -311,7 +292,7 @@ def test_the_planner_keeps_its_tree_on_the_next_resident_frame():
 def test_paths_to_poses_after_a_keep_stay_on_alive_vertices_and_free_legs():
     k = posekeepref.changed("A")
     w = k.w
-    p = _planner(w)
+    p = poseref.planner_of(w)
     T, gv = p.plan(np.array(w.xs), np.array(w.xg))
     og2 = k.og8.astype(np.int64)
     alive = p.keep_pose_tree(og2)
@@ -339,7 +320,7 @@ def test_refusals_in_their_order():
     ctx.set_grid(w.og8)
     L = _ffi.lib()
     n_alive = _ffi.C.c_int32(0)
-    _refused(_ffi.RRT_E_ARG, "no rrt_plan", ctx.keep_pose_tree)
+    refused_with_word(_ffi.RRT_E_ARG, "no rrt_plan", ctx.keep_pose_tree)
     assert L.rrt_plan_keep_pose_tree(None, _ffi.C.byref(n_alive), None) == _ffi.RRT_E_ARG
     assert L.rrt_plan_keep_pose_tree(ctx.handle, _ffi.C.byref(n_alive), None) == _ffi.RRT_E_ARG
     assert L.rrt_last_error_string(ctx.handle).decode().startswith("rrt_plan_keep_pose_tree: query 0 has not finished (no rrt_plan")
@@ -348,37 +329,37 @@ def test_refusals_in_their_order():
     assert L.rrt_batch_keep_pose_tree(None, 0, _ffi.C.byref(n_alive), None) == _ffi.RRT_E_ARG
     assert L.rrt_batch_keep_pose_tree(s._h, 7, None, None) == _ffi.RRT_E_ARG
     assert L.rrt_last_error_string(ctx.handle).decode() == "rrt_batch_keep_pose_tree: NULL"
-    _refused(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_keep_pose_tree: not a Dubins batch (its edges are straight lines: use rrt_batch_keep_tree)", s.keep_pose_tree, 7)
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_keep_pose_tree: not a Dubins batch (its edges are straight lines: use rrt_batch_keep_tree)", s.keep_pose_tree, 7)
     q, keep = _ffi.make_query(1, w.n, w.xs[:2], w.xg[:2], w.samples, r2_rewire=w.r2)
     s.set_query(0, q)
     s.launch()
     s.sync()
-    _refused(_ffi.RRT_E_UNSUPPORTED, "use rrt_batch_keep_tree", s.keep_pose_tree, 0)
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "use rrt_batch_keep_tree", s.keep_pose_tree, 0)
     assert s.keep_tree(0).all()  # its own call
     s.close()
     # a Dubins batch: q, then the state of the query, then the grid's shape
     b = _ffi.Batch(ctx, 2, w.n, dubins=True)
     other = np.zeros((w.og8.shape[0] + 8, w.og8.shape[1]), dtype=np.uint8)
     ctx.set_grid(other)
-    _refused(_ffi.RRT_E_ARG, "rrt_batch_keep_pose_tree: q=2 of 2", b.keep_pose_tree, 2)
-    _refused(_ffi.RRT_E_ARG, "q=-1", b.keep_pose_tree, -1)
-    _refused(_ffi.RRT_E_ARG, "rrt_batch_keep_pose_tree: query 0 has not finished (no query set)", b.keep_pose_tree, 0)
+    refused_with_word(_ffi.RRT_E_ARG, "rrt_batch_keep_pose_tree: q=2 of 2", b.keep_pose_tree, 2)
+    refused_with_word(_ffi.RRT_E_ARG, "q=-1", b.keep_pose_tree, -1)
+    refused_with_word(_ffi.RRT_E_ARG, "rrt_batch_keep_pose_tree: query 0 has not finished (no query set)", b.keep_pose_tree, 0)
     ctx.set_grid(w.og8)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.keep_pose_tree, 0)
-    _refused(_ffi.RRT_E_ARG, "no rrt_batch_keep_tree", b.keep_tree_ms)
+    refused_with_word(_ffi.RRT_E_ARG, "not launched", b.keep_pose_tree, 0)
+    refused_with_word(_ffi.RRT_E_ARG, "no rrt_batch_keep_tree", b.keep_tree_ms)
     b.launch()
     b.sync()
-    _refused(_ffi.RRT_E_ARG, "no query set", b.keep_pose_tree, 1)
-    _refused(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_keep_tree: a Dubins batch (its edges are Dubins words between poses; these kernels test straight lines)",
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.keep_pose_tree, 1)
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "rrt_batch_keep_tree: a Dubins batch (its edges are Dubins words between poses; these kernels test straight lines)",
              b.keep_tree, 0)  # word for word what it was
     assert L.rrt_batch_keep_pose_tree(b._h, 0, _ffi.C.byref(n_alive), None) == _ffi.RRT_OK and n_alive.value == w.j  # no flags wanted
     want = b.connect_poses(0, w.goals)
     assert np.array_equal(want[0], w.vertex) and np.array_equal(want[1], w.cost)
     ctx.set_grid(other)
-    _refused(_ffi.RRT_E_ARG, "rrt_batch_keep_pose_tree: the context's grid has another shape than the batch was created for", b.keep_pose_tree, 0)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.keep_pose_tree, 1)  # (the query's state before the grid's shape)
+    refused_with_word(_ffi.RRT_E_ARG, "rrt_batch_keep_pose_tree: the context's grid has another shape than the batch was created for", b.keep_pose_tree, 0)
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.keep_pose_tree, 1)  # (the query's state before the grid's shape)
     # the refusals changed nothing: back on a grid of the batch's shape the query is kept
     k = posekeepref.changed("E")
     ctx.set_grid(k.og8)
@@ -387,6 +368,6 @@ def test_refusals_in_their_order():
     assert len(ms) == 3 and all(t >= 0.0 for t in ms)
     # a set_query in a kept query's place drops its view with its tree
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.connect_poses, 0, w.goals)
+    refused_with_word(_ffi.RRT_E_ARG, "not launched", b.connect_poses, 0, w.goals)
     b.close()
     ctx.close()

@@ -10,9 +10,9 @@ import keepref
 import oracle
 import orchelp
 import routeref
+from plannedcases import WALL64_XG, WALL64_XS, pinned_goal_cases, wall64_og, wall64_planned
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
-from test_connect_goals_cpu import XG, XS, _og, _pinned_cases, _planned
 
 INF = np.inf
 
@@ -97,7 +97,7 @@ def test_a_freed_cell_newly_connects_a_goal():
     assert got[5].tolist() == [0, 3, -1] and got[2].tolist() == [27.0]
 
 
-@pytest.mark.parametrize("cid", _pinned_cases())
+@pytest.mark.parametrize("cid", pinned_goal_cases())
 def test_an_unchanged_map_keeps_every_vertex_of_a_golden_tree(cid):
     """the reference tested every edge of its trees from the parent to the child: the same walk on the same map is free again, and
     the answers over the view are goalref's / routeref's over the tree"""
@@ -133,30 +133,30 @@ def _with_keep(p, seen):
 
 
 def test_keep_tree_does_what_set_og_does_and_keeps_the_tree():
-    p, T, gv = _planned()
+    p, T, gv = wall64_planned()
     seen = []
     _with_keep(p, seen)
-    og2 = _og()
+    og2 = wall64_og()
     og2[10:12, 20:30] = 1
     alive = p.keep_tree(og2)
     assert alive.tolist() == [True] * 3 and p._tree_resident == "device" and p.og is og2 and not p._grid_dirty
     assert np.array_equal(seen[0], oracle.og_u8(og2)) and np.array_equal(p.free, np.argwhere(og2 == 0))
-    T2, gv2 = p.plan(XS, XG)  # a later plan() plans on the new map
+    T2, gv2 = p.plan(WALL64_XS, WALL64_XG)  # a later plan() plans on the new map
     assert p.og is og2 and p._tree_resident == "device" and len(seen) == 1
     for pt in T2.__dict__["_lazy"][1][:p.last_stats["j"]]:
         assert og2[pt[0], pt[1]] == 0
 
 
 def test_keep_tree_refuses_what_connect_goals_refuses_and_another_shape():
-    og2 = _og()
+    og2 = wall64_og()
     with pytest.raises(RuntimeError, match="plan\\(\\) first"):
-        amd.RRTStar(_og(), 300, 12, pbar=False).keep_tree(og2)
-    for setter in (lambda p: p.set_og(_og()), lambda p: p.set_n(300)):
-        p, T, gv = _planned()
+        amd.RRTStar(wall64_og(), 300, 12, pbar=False).keep_tree(og2)
+    for setter in (lambda p: p.set_og(wall64_og()), lambda p: p.set_n(300)):
+        p, T, gv = wall64_planned()
         setter(p)
         with pytest.raises(RuntimeError, match="plan\\(\\) first"):
             p.keep_tree(og2)
-    p, T, gv = _planned()
+    p, T, gv = wall64_planned()
     _with_keep(p, [])
     with pytest.raises(ValueError, match="planned on"):
         p.keep_tree(np.zeros((64, 47), dtype=np.int64))
@@ -166,13 +166,13 @@ def test_keep_tree_refuses_what_connect_goals_refuses_and_another_shape():
     def costfn(vcosts, points, v, x):
         return vcosts[v] + 2.0 * amd.r2norm(points[v] - x)
 
-    h = amd.RRTStar(_og(), 120, 12, costfn=costfn, pbar=False, seed=0)
-    h._costfn_provider = orchelp.NumpyProvider(oracle.og_u8(_og()))
-    h.plan(XS, XG)
+    h = amd.RRTStar(wall64_og(), 120, 12, costfn=costfn, pbar=False, seed=0)
+    h._costfn_provider = orchelp.NumpyProvider(oracle.og_u8(wall64_og()))
+    h.plan(WALL64_XS, WALL64_XG)
     with pytest.raises(ValueError, match="host route"):
         h.keep_tree(og2)
     # a keep that fails on the device leaves no tree for the grid that is now uploaded
-    p, T, gv = _planned()
+    p, T, gv = wall64_planned()
 
     def boom():
         raise RuntimeError("device")
@@ -185,10 +185,10 @@ def test_keep_tree_refuses_what_connect_goals_refuses_and_another_shape():
 
 
 def test_keep_tree_resident_selects_the_frame_and_keeps_the_tree():
-    p, T, gv = _planned()
+    p, T, gv = wall64_planned()
     picked = []
     p._ctx = SimpleNamespace(keep_tree=lambda: np.ones(2, dtype=bool))
-    frames = [_og(), _og()]
+    frames = [wall64_og(), wall64_og()]
     frames[1][40:42, 10:20] = 1
     grids = SimpleNamespace(ctx=p._ctx, host=frames, select=picked.append)
     alive = p.keep_tree_resident(grids, 1)
@@ -205,7 +205,7 @@ def test_keep_tree_resident_selects_the_frame_and_keeps_the_tree():
         raise RuntimeError("the device frames of this DeviceGrids are gone")
 
     with pytest.raises(RuntimeError, match="gone"):
-        p.keep_tree_resident(SimpleNamespace(ctx=p._ctx, host=[_og(), _og()], select=gone), 0)
+        p.keep_tree_resident(SimpleNamespace(ctx=p._ctx, host=[wall64_og(), wall64_og()], select=gone), 0)
     assert p._tree_resident == "device" and p.og is frames[1]
     # a keep that fails on the device after the frame was selected leaves no tree for that frame
     boom = SimpleNamespace(keep_tree=gone)
@@ -223,8 +223,8 @@ def test_keep_tree_resident_selects_the_frame_and_keeps_the_tree():
 @pytest.mark.parametrize("cls", [RRTDubins, RRTStarDubins])
 def test_the_dubins_planners_refuse(cls):
     kw = dict(r_rewire=10) if cls is RRTStarDubins else {}
-    p = cls(_og(), 100, rho=3.0, pbar=False, **kw)
+    p = cls(wall64_og(), 100, rho=3.0, pbar=False, **kw)
     with pytest.raises(ValueError, match="Dubins"):
-        p.keep_tree(_og())
+        p.keep_tree(wall64_og())
     with pytest.raises(ValueError, match="Dubins"):
         p.keep_tree_resident(None, 0)

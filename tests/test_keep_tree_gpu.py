@@ -10,13 +10,10 @@ import goalref
 import keepref
 import oracle
 import routeref
-import test_grow_gpu as tg
+import treecalls as tc
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.oggen import DeviceGrids, perlin_occupancygrid, random_connected_pair
-from test_connect_goals_gpu import _free_goals, _grow, _refused, _samples, _wall_map
-from test_reroot_gpu import SIZES, _case, _sized
-from test_routes_gpu import _corridor_map, _march, _same
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +33,7 @@ def _new_map(og):
 
 def _goals(og2):
     """free goals of the new map, one in the box that was closed, some on obstacle cells"""
-    return np.concatenate([_free_goals(og2, 57, 31), [[30, 130]], np.argwhere(og2 != 0)[::400][:4]])
+    return np.concatenate([tc.free_goals(og2, 57, 31), [[30, 130]], np.argwhere(og2 != 0)[::400][:4]])
 
 
 def _tree(p, T):
@@ -62,9 +59,9 @@ def _check_planner(p, T, og2, goals):
     assert np.array_equal(alive, want_alive), np.flatnonzero(alive != want_alive)[:8]
     v, c = p.connect_goals(goals)
     assert np.array_equal(v, raw[0]) and np.array_equal(c, raw[1])
-    _same(p.device_context().routes(goals), raw)
-    _same(p.device_context().routes(goals, shortcut=True), cut)
-    _same(p.device_context().routes(goals), raw)
+    tc.same_routes(p.device_context().routes(goals), raw)
+    tc.same_routes(p.device_context().routes(goals, shortcut=True), cut)
+    tc.same_routes(p.device_context().routes(goals), raw)
     routes, length = p.routes_to(goals, shortcut=True)
     assert np.array_equal(length, cut[2])
     paths = p.paths_to(T, goals)  # the parent walks on the T the caller holds: the vertex numbers are the original ones
@@ -79,7 +76,7 @@ def _check_planner(p, T, og2, goals):
 # ------------------------------------------------------------------------------------------------ 1. the planner classes
 @pytest.mark.parametrize("kind", ["std", "star", "informed"])
 def test_the_planners_keep_their_tree_on_a_changed_map(kind):
-    og = _wall_map()
+    og = tc.wall_map()
     og2 = _new_map(og)
     goals = _goals(og2)
     p = _planner(kind, og)
@@ -103,7 +100,7 @@ def test_the_planners_keep_their_tree_on_a_changed_map(kind):
 
 # ------------------------------------------------------------------------------------------------ 2. an unchanged map
 def test_an_unchanged_map_keeps_every_vertex_of_a_reference_mode_tree():
-    og = _wall_map()
+    og = tc.wall_map()
     goals = _goals(_new_map(og))
     p = _planner("star", og, n=1200, seed=2)
     T, gv = p.plan(XS, XG)
@@ -119,7 +116,7 @@ def test_an_unchanged_map_keeps_every_vertex_of_a_reference_mode_tree():
 
 # ------------------------------------------------------------------------------------------------ 3. the root blocked
 def test_a_blocked_root_leaves_nothing():
-    og = _wall_map()
+    og = tc.wall_map()
     p = _planner("star", og, n=600, seed=3)
     T, gv = p.plan(XS, XG)
     og2 = og.copy()
@@ -139,12 +136,12 @@ def test_a_blocked_root_leaves_nothing():
 
 # ------------------------------------------------------------------------------------------------ 4. a deep tree
 def test_a_chain_deeper_than_128_edges_is_cut_near_its_start(gpu_ctx):
-    og, way = _corridor_map()
+    og, way = tc.corridor_map()
     og8 = oracle.og_u8(og)
-    samples = _march(way)
+    samples = tc.march(way)
     n = len(samples)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 0, n, way[0], (190, 150), samples)
+    b, res = tc.plan_on_own_batch(gpu_ctx, 0, n, way[0], (190, 150), samples)
     j = res.j
     depth = keepref.depth(res.parent, j)
     assert depth.max() >= 129  # 8 or more doubling rounds
@@ -162,13 +159,13 @@ def test_a_chain_deeper_than_128_edges_is_cut_near_its_start(gpu_ctx):
     gpu_ctx.set_grid(og8)
     assert b.keep_tree(0).all()
     goals = np.array([(190, 150), (100, 150), (30, 100), (5, 21)])
-    _same(b.routes(0, goals, shortcut=True), routeref.routes(og8, res.pts, res.vcost, res.parent, j, goals, cut=True))
+    tc.same_routes(b.routes(0, goals, shortcut=True), routeref.routes(og8, res.pts, res.vcost, res.parent, j, goals, cut=True))
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 5. parents with higher indices
 def test_a_rewired_tree_whose_parents_come_after_their_children():
-    og = _wall_map()
+    og = tc.wall_map()
     og2 = _new_map(og)
     goals = _goals(og2)
     p = _planner("correct", og)
@@ -192,7 +189,7 @@ def test_a_tree_of_the_large_grid_kernel():
     og2 = og.copy()
     og2[1100:1103, 10:] = 1         # a wall added
     og2[1500:1504, 30:40] = 0
-    goals = _free_goals(og2, 30, 5)
+    goals = tc.free_goals(og2, 30, 5)
     p = amd.RRTStar(og, 1500, 60, pbar=False, seed=3)
     T, gv = p.plan(np.array((5, 5)), np.array((2290, 40)))
     assert p.last_route == "kernel-large"
@@ -206,35 +203,35 @@ def test_a_tree_of_the_large_grid_kernel():
 
 # ------------------------------------------------------------------------------------------------ 7. a batch of three queries
 def test_one_query_of_a_batch_is_kept_and_the_others_stay_refused(gpu_ctx):
-    og = _wall_map()
+    og = tc.wall_map()
     og8, og28 = oracle.og_u8(og), oracle.og_u8(_new_map(og))
     gpu_ctx.set_grid(og8)
     ns = [300, 1500, 800]
     b = _ffi.Batch(gpu_ctx, 3, max(ns))
     keeps = []
     for q, n in enumerate(ns):
-        qu, keep = _ffi.make_query(1, n, (5 + q, 5), (190, 150 - q), _samples(og, n, 10 + q), r2_rewire=hostprep.radius_threshold(25))
+        qu, keep = _ffi.make_query(1, n, (5 + q, 5), (190, 150 - q), tc.free_samples(og, n, 10 + q), r2_rewire=hostprep.radius_threshold(25))
         keeps.append(keep)
         b.set_query(q, qu)
     b.launch()
     b.sync()
-    goals = _free_goals(_new_map(og), 40, 13)
+    goals = tc.free_goals(_new_map(og), 40, 13)
     res = [b.get_result(q) for q in range(3)]
     first = b.routes(1, goals, shortcut=True)
     gpu_ctx.set_grid(og28)
     for q in range(3):
-        _refused(_ffi.RRT_E_ARG, "replaced", b.connect_goals, q, goals)
+        tc.refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_goals, q, goals)
     alive = b.keep_tree(1)
     want_alive, want = keepref.routes(og28, res[1].pts, res[1].parent, res[1].vcost, res[1].j, goals, cut=True)
     assert np.array_equal(alive, want_alive) and 0 < alive.sum() < res[1].j
-    _same(b.routes(1, goals, shortcut=True), want)
+    tc.same_routes(b.routes(1, goals, shortcut=True), want)
     v, c = b.connect_goals(1, goals)
     assert np.array_equal(v, want[0]) and np.array_equal(c, want[1])
     ms = b.keep_tree_ms()
     assert len(ms) == 3 and all(t >= 0.0 for t in ms)
     for q in (0, 2):
-        _refused(_ffi.RRT_E_ARG, "replaced", b.connect_goals, q, goals)
-        _refused(_ffi.RRT_E_ARG, "replaced", b.routes, q, goals)
+        tc.refused_with_word(_ffi.RRT_E_ARG, "replaced", b.connect_goals, q, goals)
+        tc.refused_with_word(_ffi.RRT_E_ARG, "replaced", b.routes, q, goals)
     for q in range(3):  # the tree arrays are untouched
         again = b.get_result(q)
         assert again.j == res[q].j and again.vgoal == res[q].vgoal and again.found == res[q].found
@@ -243,20 +240,20 @@ def test_one_query_of_a_batch_is_kept_and_the_others_stay_refused(gpu_ctx):
     # a second query kept next to the first: each has its own view
     alive2 = b.keep_tree(2)
     assert np.array_equal(alive2, keepref.alive(og28, res[2].pts, res[2].parent, res[2].j))
-    _same(b.routes(1, goals, shortcut=True), want)
-    _same(b.routes(2, goals), keepref.routes(og28, res[2].pts, res[2].parent, res[2].vcost, res[2].j, goals)[1])
+    tc.same_routes(b.routes(1, goals, shortcut=True), want)
+    tc.same_routes(b.routes(2, goals), keepref.routes(og28, res[2].pts, res[2].parent, res[2].vcost, res[2].j, goals)[1])
     # rearm + launch drop the views: the queries run again, on the new map, and answer over their whole new trees
     b.rearm()
-    _refused(_ffi.RRT_E_ARG, "not finished", b.keep_tree, 1)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "not finished", b.keep_tree, 1)
     b.launch()
     b.sync()
     new = b.get_result(1)
-    _same(b.routes(1, goals, shortcut=True), routeref.routes(og28, new.pts, new.vcost, new.parent, new.j, goals, cut=True))
+    tc.same_routes(b.routes(1, goals, shortcut=True), routeref.routes(og28, new.pts, new.vcost, new.parent, new.j, goals, cut=True))
     gpu_ctx.set_grid(og8)
     b.rearm()
     b.launch()
     b.sync()
-    _same(b.routes(1, goals, shortcut=True), first)
+    tc.same_routes(b.routes(1, goals, shortcut=True), first)
     b.close()
 
 
@@ -264,32 +261,32 @@ def test_a_refused_set_query_leaves_a_kept_query_on_its_view(gpu_ctx):
     """A set_query that is refused replaces nothing: the query keeps its view and goes on answering over the alive vertices alone,
     never over its whole tree on the grid that cut it.  The same through rrt_plan, which reaches set_query on the context's own
     batch.  A set_query that is accepted drops the view with the tree."""
-    og = _wall_map()
+    og = tc.wall_map()
     og8, og28 = oracle.og_u8(og), oracle.og_u8(_new_map(og))
-    goals = _free_goals(_new_map(og), 40, 13)
+    goals = tc.free_goals(_new_map(og), 40, 13)
     n = 1500
-    samples = _samples(og, n, 11)
+    samples = tc.free_samples(og, n, 11)
     r2 = hostprep.radius_threshold(25)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 1, n, (5, 5), (190, 150), samples, r2=r2)
+    b, res = tc.plan_on_own_batch(gpu_ctx, 1, n, (5, 5), (190, 150), samples, r2=r2)
     gpu_ctx.set_grid(og28)
     alive = b.keep_tree(0)
     want_alive, want = keepref.routes(og28, res.pts, res.parent, res.vcost, res.j, goals, cut=True)
     assert np.array_equal(alive, want_alive) and 0 < alive.sum() < res.j
     whole = routeref.routes(og28, res.pts, res.vcost, res.parent, res.j, goals, cut=True)
     assert not np.array_equal(whole[0], want[0])  # (answering from the whole tree would show)
-    too_many, keep1 = _ffi.make_query(1, n + 1, (5, 5), (190, 150), _samples(og, n + 1, 12), r2_rewire=r2)
+    too_many, keep1 = _ffi.make_query(1, n + 1, (5, 5), (190, 150), tc.free_samples(og, n + 1, 12), r2_rewire=r2)
     bad_alg, keep2 = _ffi.make_query(1, n, (5, 5), (190, 150), samples, r2_rewire=r2)
     bad_alg.alg = -1
     outside, keep3 = _ffi.make_query(1, n, (5, 5), (og.shape[0], 150), samples, r2_rewire=r2)
     for qu, word in ((too_many, "capacity"), (bad_alg, "alg=-1"), (outside, "outside")):
-        _refused(_ffi.RRT_E_ARG, word, b.set_query, 0, qu)
-        _same(b.routes(0, goals, shortcut=True), want)
+        tc.refused_with_word(_ffi.RRT_E_ARG, word, b.set_query, 0, qu)
+        tc.same_routes(b.routes(0, goals, shortcut=True), want)
         v, c = b.connect_goals(0, goals)
         assert np.array_equal(v, want[0]) and np.array_equal(c, want[1])
     good, keep4 = _ffi.make_query(1, n, (5, 5), (190, 150), samples, r2_rewire=r2)
     b.set_query(0, good)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.connect_goals, 0, goals)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "not launched", b.connect_goals, 0, goals)
     b.close()
     # the context's own batch
     gpu_ctx.set_grid(og8)
@@ -300,15 +297,15 @@ def test_a_refused_set_query_leaves_a_kept_query_on_its_view(gpu_ctx):
     alive = gpu_ctx.keep_tree()
     want_alive, want = keepref.routes(og28, r1.pts, r1.parent, r1.vcost, r1.j, goals, cut=True)
     assert np.array_equal(alive, want_alive) and 0 < alive.sum() < r1.j
-    _refused(_ffi.RRT_E_ARG, "alg=-1", gpu_ctx.plan, bad_alg, n)
-    _same(gpu_ctx.routes(goals, shortcut=True), want)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "alg=-1", gpu_ctx.plan, bad_alg, n)
+    tc.same_routes(gpu_ctx.routes(goals, shortcut=True), want)
     v, c = gpu_ctx.connect_goals(goals)
     assert np.array_equal(v, want[0]) and np.array_equal(c, want[1])
 
 
 # ------------------------------------------------------------------------------------------------ 8. back to the first map
 def test_keeping_the_tree_for_the_first_map_again_restores_every_answer():
-    og = _wall_map()
+    og = tc.wall_map()
     og2 = _new_map(og)
     goals = _goals(og2)
     p = _planner("star", og, n=1000, seed=4)
@@ -324,7 +321,7 @@ def test_keeping_the_tree_for_the_first_map_again_restores_every_answer():
         for x, y in zip(a, b):
             assert x.dtype == y.dtype and np.array_equal(x, y)
     assert np.array_equal(p.keep_tree(og2), cut1)  # not cumulative in either direction
-    _same(ctx.routes(goals), changed)
+    tc.same_routes(ctx.routes(goals), changed)
     # a later plan() plans on the map that was kept last
     q = _planner("star", og2, n=1000, seed=4)
     q.rand_gen = np.random.default_rng(4)
@@ -344,23 +341,23 @@ def test_keep_tree_resident_on_the_next_frame():
     p.set_og_resident(grids, 0)
     T, gv = p.plan(xs, xg)
     pts, parent, vcost, j = _tree(p, T)
-    goals = _free_goals(frames[1], 40, 6)
+    goals = tc.free_goals(frames[1], 40, 6)
     og28 = oracle.og_u8(grids.host[1])
     want_alive, want = keepref.routes(og28, pts, parent, vcost, j, goals, cut=True)
     assert 0 < want_alive.sum() < j
     alive = p.keep_tree_resident(grids, 1)
     assert grids.valid() and np.shares_memory(p.og, grids.host[1]) and np.array_equal(p.og, frames[1])  # nothing was uploaded
     assert np.array_equal(alive, want_alive)
-    _same(p.device_context().routes(goals, shortcut=True), want)
+    tc.same_routes(p.device_context().routes(goals, shortcut=True), want)
     assert p.keep_tree_resident(grids, 0).all()
 
 
 # ------------------------------------------------------------------------------------------------ 10. one vertex, and refusals
 def test_a_tree_of_the_start_alone(gpu_ctx):
-    og = _wall_map()
+    og = tc.wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 0, 1, (5, 5), (190, 150), np.array([[6, 6]]))
+    b, res = tc.plan_on_own_batch(gpu_ctx, 0, 1, (5, 5), (190, 150), np.array([[6, 6]]))
     assert res.j == 1
     og2 = og8.copy()
     og2[40, 40] = 1
@@ -377,9 +374,9 @@ def test_a_tree_of_the_start_alone(gpu_ctx):
 
 def test_trees_of_exactly_1_2_63_to_65_and_1023_to_1025_vertices(gpu_ctx):
     """the compaction's wave and pass edges (64 and 1024 vertices) and the one-round case of the pointer jumping (1 and 2 vertices): the
-    trees of test_reroot_gpu's sizes, the cells of vertex j // 2 and of the last vertex turned into obstacles"""
+    trees of treecalls.SIZES, the cells of vertex j // 2 and of the last vertex turned into obstacles"""
     def check(b, q, c):
-        pts, parent, vcost, j = tg._tree_of(b.get_result(q))
+        pts, parent, vcost, j = tc.tree_of(b.get_result(q))
         assert j == c["ro"].j
         og2 = c["og8"].copy()
         for k in (j // 2, j - 1):
@@ -399,24 +396,24 @@ def test_trees_of_exactly_1_2_63_to_65_and_1023_to_1025_vertices(gpu_ctx):
         assert np.array_equal(gv, v) and np.array_equal(gc, cost), j
 
     cs = []
-    for k in SIZES[1:]:
-        og8, xs, samples, n = _sized(k, 100 + k)
-        cs.append(_case(og8, 0, n, xs, (63, 63), samples, 0))
-    b = tg._batch(gpu_ctx, cs[0], "team", Q=len(cs), n_cap=1040)
+    for k in tc.SIZES[1:]:
+        og8, xs, samples, n = tc.sized(k, 100 + k)
+        cs.append(tc.oracle_case(og8, 0, n, xs, (63, 63), samples, 0))
+    b = tc.shaped_batch(gpu_ctx, cs[0], "team", Q=len(cs), n_cap=1040)
     for q, c in enumerate(cs):
-        tg._set_and_run(b, q, c)
+        tc.set_case_query(b, q, c)
     b.launch()
     b.sync()
     for q, c in enumerate(cs):
-        assert c["ro"].j == SIZES[q + 1]
+        assert c["ro"].j == tc.SIZES[q + 1]
         check(b, q, c)
     b.close()
     # the tree of one vertex: the start boxed in, on a map and in a batch of its own
-    og8, xs, samples, n = _sized(1, 101)
-    c = _case(og8, 0, n, xs, (63, 63) if tuple(xs) != (63, 63) else (0, 0), samples, 0)
+    og8, xs, samples, n = tc.sized(1, 101)
+    c = tc.oracle_case(og8, 0, n, xs, (63, 63) if tuple(xs) != (63, 63) else (0, 0), samples, 0)
     assert c["ro"].j == 1
-    b = tg._batch(gpu_ctx, c, "team")
-    tg._set_and_run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    tc.set_case_query(b, 0, c)
     b.launch()
     b.sync()
     check(b, 0, c)
@@ -425,23 +422,23 @@ def test_trees_of_exactly_1_2_63_to_65_and_1023_to_1025_vertices(gpu_ctx):
 
 def test_refusals():
     ctx = _ffi.Context(0)
-    og = _wall_map()
+    og = tc.wall_map()
     og8 = oracle.og_u8(og)
     ctx.set_grid(og8)
     L = _ffi.lib()
-    _refused(_ffi.RRT_E_ARG, "no rrt_plan", ctx.keep_tree)
-    samples = _samples(og, 500, 17)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "no rrt_plan", ctx.keep_tree)
+    samples = tc.free_samples(og, 500, 17)
     b = _ffi.Batch(ctx, 2, 500)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.keep_tree, 0)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "no query set", b.keep_tree, 0)
     q, keep = _ffi.make_query(1, 500, (5, 5), (190, 150), samples, r2_rewire=900)
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.keep_tree, 0)
-    _refused(_ffi.RRT_E_ARG, "no rrt_batch_keep_tree", b.keep_tree_ms)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "not launched", b.keep_tree, 0)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "no rrt_batch_keep_tree", b.keep_tree_ms)
     b.launch()
     b.sync()
-    _refused(_ffi.RRT_E_ARG, "q=2", b.keep_tree, 2)
-    _refused(_ffi.RRT_E_ARG, "q=-1", b.keep_tree, -1)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.keep_tree, 1)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "q=2", b.keep_tree, 2)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "q=-1", b.keep_tree, -1)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "no query set", b.keep_tree, 1)
     n_alive = _ffi.C.c_int32(0)
     assert L.rrt_batch_keep_tree(None, 0, _ffi.C.byref(n_alive), None) == _ffi.RRT_E_ARG
     assert L.rrt_batch_keep_tree(b._h, 0, None, None) == _ffi.RRT_E_ARG
@@ -450,13 +447,13 @@ def test_refusals():
     want = b.routes(0, [(150, 150)], shortcut=True)
     # a set_query in a kept query's place drops its view with its tree
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.connect_goals, 0, [(150, 150)])
+    tc.refused_with_word(_ffi.RRT_E_ARG, "not launched", b.connect_goals, 0, [(150, 150)])
     b.launch()
     b.sync()
-    _same(b.routes(0, [(150, 150)], shortcut=True), want)
+    tc.same_routes(b.routes(0, [(150, 150)], shortcut=True), want)
     # another shape
     ctx.set_grid(np.zeros((64, 64), dtype=np.uint8))
-    _refused(_ffi.RRT_E_ARG, "shape", b.keep_tree, 0)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "shape", b.keep_tree, 0)
     b.close()
     # an Informed query that waits for its unit ball has no finished tree
     b = _ffi.Batch(ctx, 1, 300)
@@ -467,7 +464,7 @@ def test_refusals():
     b.launch()
     b.sync()
     assert b.get_result(0).status == _ffi.RRT_NEED_UNITBALL
-    _refused(_ffi.RRT_E_ARG, "unit-ball", b.keep_tree, 0)
+    tc.refused_with_word(_ffi.RRT_E_ARG, "unit-ball", b.keep_tree, 0)
     b.close()
     # a Dubins batch
     hd = np.random.default_rng(19).integers(0, 16, size=300)
@@ -476,13 +473,13 @@ def test_refusals():
     b.set_query(0, q)
     b.launch()
     b.sync()
-    _refused(_ffi.RRT_E_UNSUPPORTED, "Dubins", b.keep_tree, 0)
+    tc.refused_with_word(_ffi.RRT_E_UNSUPPORTED, "Dubins", b.keep_tree, 0)
     b.close()
     ctx.close()
 
 
 def test_the_planner_keeps_its_state_rules():
-    og = _wall_map()
+    og = tc.wall_map()
     og2 = _new_map(og)
     p = amd.RRTStandard(og, 500, pbar=False, seed=3)
     with pytest.raises(RuntimeError, match="plan"):

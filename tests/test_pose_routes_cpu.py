@@ -13,14 +13,11 @@ import oracle
 import poseref
 import posekeepref
 import poseroutesref as prr
+from orchelp import bits
 from rrtplanner_amd.dubins import WORDS, dubins_polyline, dubins_shortest
 
 WORKLOADS = ["A", "B", "D", "E", "G1", "G256"]
 TOL = 1e-8
-
-
-def _bits(x):
-    return np.asarray(x, dtype=np.float64).view(np.int64)
 
 
 def _own_walk(parent, v):
@@ -73,7 +70,7 @@ def _check_case(c, libm=True):
     m = len(c.goals)
     assert r.offsets[0] == 0 and r.point_offsets[0] == 0 and r.offsets[m] == len(r.rows) == len(r.ids) and r.point_offsets[m] == len(r.points)
     on = r.vertex >= 0
-    assert np.array_equal(_bits(r.length[on]), _bits(r.cost[on])), "length != cost"
+    assert np.array_equal(bits(r.length[on]), bits(r.cost[on])), "length != cost"
     assert np.all(np.isinf(r.length[~on])) and np.all(np.diff(r.offsets)[~on] == 0) and np.all(np.diff(r.point_offsets)[~on] == 0)
     for g in range(m):
         if not on[g]:
@@ -178,13 +175,13 @@ def test_the_chain_of_1100_vertices_is_one_route_of_1101_rows():
     assert c.w.j == 1100 and r.vertex.tolist() == [1099, 1099, -1] and np.diff(r.offsets).tolist() == [1101, 1101, 0]
     assert r.ids[:1101].tolist() == list(range(1100)) + [-1]
     _check_case(c, libm=False)  # (straight unit legs but the last two: the libm comparison is the other tests')
-    assert np.array_equal(_bits(r.length[:2]), _bits(r.cost[:2]))
+    assert np.array_equal(bits(r.length[:2]), bits(r.cost[:2]))
 
 
 @pytest.mark.parametrize("name", ["A", "E", "G256"])
 def test_after_a_keep_on_a_changed_map(name):
     c = prr.kept_case(name)
     k = posekeepref.changed(name)
-    assert 0 < k.alive.sum() < c.w.j and np.array_equal(c.vertex[:len(k.vertex)], k.vertex) and np.array_equal(_bits(c.cost[:len(k.cost)]), _bits(k.cost))
+    assert 0 < k.alive.sum() < c.w.j and np.array_equal(c.vertex[:len(k.vertex)], k.vertex) and np.array_equal(bits(c.cost[:len(k.cost)]), bits(k.cost))
     assert (c.vertex >= 0).sum() >= 8
     _check_case(c)  # alive vertices only, every cell free on the NEW map, length == cost

@@ -16,9 +16,8 @@ import pytest
 import poseref
 import posekeepref
 import poseroutesref as prr
+from posecalls import planned_batch, refused_with_golden_text
 from rrtplanner_amd import RRTStar, _ffi
-from test_connect_poses_gpu import _query
-from test_keep_pose_tree_gpu import _planner, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -36,21 +35,11 @@ def _both(b, c, q=0):
     return full
 
 
-def _refused(key, fn, *args, **fmt):
-    code, text = GOLDEN[key]
-    with pytest.raises(ValueError if code == "ValueError" else _ffi.RRTError) as e:
-        fn(*args)
-    if code == "ValueError":
-        assert str(e.value) == text, str(e.value)
-    else:
-        assert e.value.code == code and str(e.value) == f"librrt_hip error {code}: {text.format(**fmt)}", str(e.value)
-
-
 # ------------------------------------------------------------------------------------------------ 1. the workloads
 @pytest.mark.parametrize("name", ["A", "B", "D", "E", "F", "G1", "G256"])
 def test_workloads_on_a_batch(gpu_ctx, name):
     c = prr.case(name)
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     _both(b, c)
     ms = b.pose_routes_ms()
     assert len(ms) == 4 and all(t >= 0.0 for t in ms) and ms[3] == 0.0  # (the last call asked for no points)
@@ -62,7 +51,7 @@ def test_workloads_on_a_batch(gpu_ctx, name):
 
 def test_the_one_sample_kernel_builds_the_same_tree(gpu_ctx):
     c = prr.case("E")
-    b = _run(gpu_ctx, c.w, serial=True)
+    b = planned_batch(gpu_ctx, c.w, serial=True)
     _both(b, c)
     b.close()
 
@@ -70,7 +59,7 @@ def test_the_one_sample_kernel_builds_the_same_tree(gpu_ctx):
 def test_workload_c_of_4000_vertices(gpu_ctx):
     c = prr.case("C")
     assert c.w.j > 2 * 1024 and (c.vertex >= 0).sum() >= 6
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     _both(b, c)
     b.close()
 
@@ -78,7 +67,7 @@ def test_workload_c_of_4000_vertices(gpu_ctx):
 # ------------------------------------------------------------------------------------------------ 2. trees made for one purpose each
 def test_half_cell_legs_and_the_chain_of_1100_vertices(gpu_ctx):
     for c in (prr.half_cell_chain(), prr.long_chain()):
-        b = _run(gpu_ctx, c.w)
+        b = planned_batch(gpu_ctx, c.w)
         _both(b, c)
         b.close()
 
@@ -87,7 +76,7 @@ def test_half_cell_legs_and_the_chain_of_1100_vertices(gpu_ctx):
 def test_trees_of_exactly_j_vertices(gpu_ctx, j):
     for star in (0, 1):
         c = prr.made_case(poseref.stride_tree(j, star))
-        b = _run(gpu_ctx, c.w)
+        b = planned_batch(gpu_ctx, c.w)
         _both(b, c)
         b.close()
 
@@ -98,7 +87,7 @@ def test_through_rrt_plan(gpu_ctx, name):
     c = prr.case(name)
     w = c.w
     gpu_ctx.set_grid(w.og8)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     rc, res = gpu_ctx.plan(q, w.n)
     assert rc == w.status and res.j == w.j
     prr.same(gpu_ctx.pose_routes(c.goals, points=True), c.routes)
@@ -110,7 +99,7 @@ def test_through_rrt_plan(gpu_ctx, name):
 def test_through_the_planners_with_an_open_heading(name):
     c = prr.case(name)
     w, r = c.w, c.routes
-    p = _planner(w)
+    p = poseref.planner_of(w)
     T, gv = p.plan(np.array(w.xs), np.array(w.xg))
     assert p.last_stats["j"] == w.j
     routes, length, paths = p.routes_to_poses(c.goals, points=True)
@@ -147,7 +136,7 @@ def test_no_pose_one_pose_and_a_workgroup_of_them(gpu_ctx):
     c = prr.case("E")
     r = c.routes
     g = int(np.argmax(np.diff(r.offsets)))  # the pose with the longest route
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     got = b.pose_routes(0, np.zeros((0, 3), dtype=np.int32), points=True)
     assert [len(x) for x in got] == [0, 0, 0, 1, 0, 0, 1, 0] and got[3][0] == 0 and got[6][0] == 0
     assert b.pose_routes_rows(0)[0].shape == (0, 3) and b.pose_routes_points(0).shape == (0, 2)
@@ -163,14 +152,14 @@ def test_no_pose_one_pose_and_a_workgroup_of_them(gpu_ctx):
 
 def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx):
     c = prr.case("E")
-    prr.small_calls_after_a_large_one(lambda: _run(gpu_ctx, c.w), c, c.routes, shortcut=False)
+    prr.small_calls_after_a_large_one(lambda: planned_batch(gpu_ctx, c.w), c, c.routes, shortcut=False)
 
 
 # ------------------------------------------------------------------------------------------------ 5. after a keep
 def test_after_keep_pose_tree_and_back(gpu_ctx):
     c0, c1 = prr.case("A"), prr.kept_case("A")
     w = c0.w
-    b = _run(gpu_ctx, w)
+    b = planned_batch(gpu_ctx, w)
     _both(b, c0)
     gpu_ctx.set_grid(c1.og8)
     assert np.array_equal(b.keep_pose_tree(0), c1.alive)
@@ -187,7 +176,7 @@ def test_after_keep_pose_tree_and_back(gpu_ctx):
 def test_asked_twice_and_connect_poses_afterwards(gpu_ctx):
     c = prr.case("B")
     w = c.w
-    b = _run(gpu_ctx, w)
+    b = planned_batch(gpu_ctx, w)
     first = b.connect_poses(0, w.goals)
     one = b.pose_routes(0, c.goals, points=True)
     two = b.pose_routes(0, c.goals, points=True)
@@ -212,29 +201,29 @@ def test_refusals():
     ctx = _ffi.Context(0)
     ctx.set_grid(w.og8)
     L = _ffi.lib()
-    _refused("no_plan", ctx.pose_routes, w.goals)
+    refused_with_golden_text(GOLDEN, "no_plan", ctx.pose_routes, w.goals)
     s = _ffi.Batch(ctx, 1, w.n)
-    _refused("non_dubins_batch", s.pose_routes, 0, w.goals)
+    refused_with_golden_text(GOLDEN, "non_dubins_batch", s.pose_routes, 0, w.goals)
     s.close()
     b = _ffi.Batch(ctx, 1, w.n, dubins=True)
-    _refused("unfinished_query", b.pose_routes, 0, w.goals)
-    _refused("rows_none", b.pose_routes_rows, 0)
-    _refused("points_none", b.pose_routes_points, 0)
-    _refused("ms_none", b.pose_routes_ms)
-    q, keep = _query(w)
+    refused_with_golden_text(GOLDEN, "unfinished_query", b.pose_routes, 0, w.goals)
+    refused_with_golden_text(GOLDEN, "rows_none", b.pose_routes_rows, 0)
+    refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, 0)
+    refused_with_golden_text(GOLDEN, "ms_none", b.pose_routes_ms)
+    q, keep = poseref.device_query(w)
     b.set_query(0, q)
     b.launch()
     b.sync()
-    _refused("routes_on_a_dubins_batch", b.routes, 0, w.goals[:, :2])  # word for word what it was
+    refused_with_golden_text(GOLDEN, "routes_on_a_dubins_batch", b.routes, 0, w.goals[:, :2])  # word for word what it was
     full = b.pose_routes(0, c.goals, points=True)
     prr.same(full, c.routes)
     rows, points = len(c.routes.rows), len(c.routes.points)
-    _refused("rows_wrong_count", b.pose_routes_rows, rows + 1, asked=rows + 1, left=rows)
-    _refused("points_wrong_count", b.pose_routes_points, points - 1, asked=points - 1, left=points)
+    refused_with_golden_text(GOLDEN, "rows_wrong_count", b.pose_routes_rows, rows + 1, asked=rows + 1, left=rows)
+    refused_with_golden_text(GOLDEN, "points_wrong_count", b.pose_routes_points, points - 1, asked=points - 1, left=points)
     assert np.array_equal(b.pose_routes_rows(rows)[0], c.routes.rows)  # a wrong count drops nothing
     # a call without points leaves rows and no points
     b.pose_routes(0, c.goals)
-    _refused("points_none", b.pose_routes_points, points)
+    refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, points)
     # failed calls: each drops the rows and the points of the call before it
     g, vertex, cost = _ffi._pose_arrays(c.goals)
     m = len(g)
@@ -246,21 +235,21 @@ def test_refusals():
 
     for key, call in (("unknown_flag", lambda: raw(2, po.ctypes.data)), ("null_point_offsets", lambda: raw(1, None))):
         b.pose_routes(0, c.goals, points=True)
-        _refused(key, call)
-        _refused("rows_none", b.pose_routes_rows, rows)
-        _refused("points_none", b.pose_routes_points, points)
+        refused_with_golden_text(GOLDEN, key, call)
+        refused_with_golden_text(GOLDEN, "rows_none", b.pose_routes_rows, rows)
+        refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, points)
     raw(0, None)  # without the flag point_offsets may be NULL
     assert np.array_equal(offsets, c.routes.offsets)
     bad = g.copy()
     bad[1, 2] = w.nh
     b.pose_routes(0, c.goals, points=True)
-    _refused("heading_out_of_range", lambda: raw(1, po.ctypes.data, bad), nh=w.nh)
-    _refused("rows_none", b.pose_routes_rows, rows)
+    refused_with_golden_text(GOLDEN, "heading_out_of_range", lambda: raw(1, po.ctypes.data, bad), nh=w.nh)
+    refused_with_golden_text(GOLDEN, "rows_none", b.pose_routes_rows, rows)
     # a rearm
     b.pose_routes(0, c.goals, points=True)
     b.rearm()
-    _refused("rows_none", b.pose_routes_rows, rows)
-    _refused("points_none", b.pose_routes_points, points)
+    refused_with_golden_text(GOLDEN, "rows_none", b.pose_routes_rows, rows)
+    refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, points)
     b.launch()
     b.sync()
     prr.same(b.pose_routes(0, c.goals, points=True), c.routes)
@@ -272,7 +261,7 @@ def test_refusals():
     b2.launch()
     b2.sync()
     ctx2.set_grid(posekeepref.blocks_map(w.og8, w.xs))
-    _refused("grid_replaced", b2.pose_routes, 0, w.goals)
+    refused_with_golden_text(GOLDEN, "grid_replaced", b2.pose_routes, 0, w.goals)
     b2.close()
     ctx2.close()
     b.close()
@@ -282,4 +271,4 @@ def test_refusals():
 def test_the_straight_line_planners_refuse():
     w = poseref.workload("E")
     p = RRTStar(w.og, 50, 10, pbar=False)
-    _refused("straight_line_planner", p.routes_to_poses, w.goals)
+    refused_with_golden_text(GOLDEN, "straight_line_planner", p.routes_to_poses, w.goals)

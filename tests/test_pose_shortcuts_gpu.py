@@ -14,24 +14,19 @@ import os
 import numpy as np
 import pytest
 
+import posegrowref
 import poseref
 import posekeepref
 import poseroutesref as prr
 import poseshortref as psr
+from orchelp import bits
+from posecalls import grow_poses_checked, planned_batch, planned_logged_batch, refused_with_golden_text
 from rrtplanner_amd import RRTStar, _ffi
-from test_connect_poses_gpu import _query
-from test_grow_poses_gpu import _grow, _planted
-from test_grow_poses_gpu import _run as _run_logged
-from test_keep_pose_tree_gpu import _planner, _run
 
 pytestmark = pytest.mark.gpu
 
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_shortcuts_refusals.json")) as f:
     GOLDEN = json.load(f)
-
-
-def _bits(x):
-    return x.view(np.int64) if x.dtype == np.float64 else x
 
 
 def _free_cells(og8, points):
@@ -50,21 +45,11 @@ def _both(b, c, q=0, want=None):
     return full
 
 
-def _refused(key, fn, *args, **fmt):
-    code, text = GOLDEN[key]
-    with pytest.raises(ValueError if code == "ValueError" else _ffi.RRTError) as e:
-        fn(*args)
-    if code == "ValueError":
-        assert str(e.value) == text, str(e.value)
-    else:
-        assert e.value.code == code and str(e.value) == f"librrt_hip error {code}: {text.format(**fmt)}", str(e.value)
-
-
 # ------------------------------------------------------------------------------------------------ 1. the workloads
 @pytest.mark.parametrize("name", ["A", "B", "D", "E", "F", "G1", "G256"])
 def test_workloads_on_a_batch(gpu_ctx, name):
     c = prr.case(name)
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     _both(b, c)
     ms = b.pose_shortcuts_ms()
     assert len(ms) == 5 and all(t >= 0.0 for t in ms) and ms[4] == 0.0  # (the last call asked for no points)
@@ -76,14 +61,14 @@ def test_workloads_on_a_batch(gpu_ctx, name):
 
 def test_the_one_sample_kernel_builds_the_same_tree(gpu_ctx):
     c = prr.case("E")
-    b = _run(gpu_ctx, c.w, serial=True)
+    b = planned_batch(gpu_ctx, c.w, serial=True)
     _both(b, c)
     b.close()
 
 
 def test_workload_c_of_4000_vertices(gpu_ctx):
     c = prr.case("C")
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     _both(b, c)
     b.close()
 
@@ -92,14 +77,14 @@ def test_workload_c_of_4000_vertices(gpu_ctx):
 @pytest.mark.parametrize("name", ["small", "large"])
 def test_rings_whose_anchors_meet_batches_of_blocked_candidates(gpu_ctx, name):
     c = psr.ring(name)
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     _both(b, c)
     b.close()
 
 
 def test_the_half_cell_chain_keeps_the_duplicate_point_of_a_shortcut_leg(gpu_ctx):
     c = prr.half_cell_chain()
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     _both(b, c)
     b.close()
 
@@ -108,7 +93,7 @@ def test_the_half_cell_chain_keeps_the_duplicate_point_of_a_shortcut_leg(gpu_ctx
 @pytest.mark.parametrize("name", ["A", "C", "E"])
 def test_after_keep_pose_tree(gpu_ctx, name):
     c = prr.kept_case(name)
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     gpu_ctx.set_grid(c.og8)
     assert np.array_equal(b.keep_pose_tree(0), c.alive)
     _both(b, c)  # the sweeps on the new map, over the alive view, in the original vertex numbers
@@ -116,12 +101,12 @@ def test_after_keep_pose_tree(gpu_ctx, name):
 
 
 def test_after_grow_poses_in_the_new_numbering(gpu_ctx):
-    k, s, g = _planted("A")
+    k, s, _, _, _, g = posegrowref.planted("A")
     w = k.w
-    b = _run_logged(gpu_ctx, w, "block")
+    b = planned_logged_batch(gpu_ctx, w, "block")
     gpu_ctx.set_grid(k.og8)
     assert np.array_equal(b.keep_pose_tree(0), k.alive)
-    _grow(b, 0, w, g, g.ids, s, "block")
+    grow_poses_checked(b, 0, w, g, g.ids, s, "block")
     v, cost, _ = poseref.connect(k.og8, g.pts, g.head, g.vcost, g.j, w.goals, w.rho, w.nh)
     assert (v >= 0).sum() >= 4
     want = psr.routes(g.pts, g.head, g.parent, g.j, w.goals, v, cost, w.rho, w.nh, k.og8)
@@ -134,13 +119,13 @@ def test_after_grow_poses_in_the_new_numbering(gpu_ctx):
 
 def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx):
     c = prr.case("E")
-    prr.small_calls_after_a_large_one(lambda: _run(gpu_ctx, c.w), c, psr.of_case(c), shortcut=True)
+    prr.small_calls_after_a_large_one(lambda: planned_batch(gpu_ctx, c.w), c, psr.of_case(c), shortcut=True)
 
 
 # ------------------------------------------------------------------------------------------------ 4. three queries, and the other ways in
 def test_a_batch_of_three_queries_asked_at_the_second_and_the_third(gpu_ctx):
     c0, c1 = prr.case("E"), prr.kept_case("E")
-    b = _run_logged(gpu_ctx, c0.w, "block", Q=3)
+    b = planned_logged_batch(gpu_ctx, c0.w, "block", Q=3)
     _both(b, c0, q=1)
     _both(b, c0, q=2)
     gpu_ctx.set_grid(c1.og8)
@@ -153,7 +138,7 @@ def test_through_rrt_plan(gpu_ctx):
     c = prr.case("A")
     w, want = c.w, psr.of_case(c)
     gpu_ctx.set_grid(w.og8)
-    q, keep = _query(w)
+    q, keep = poseref.device_query(w)
     rc, res = gpu_ctx.plan(q, w.n)
     assert rc == w.status and res.j == w.j
     prr.same(gpu_ctx.pose_routes(c.goals, points=True, shortcut=True), want)
@@ -165,7 +150,7 @@ def test_through_rrt_plan(gpu_ctx):
 def test_through_the_planners_with_an_open_heading(name):
     c = prr.case(name)
     w, r = c.w, psr.of_case(c)
-    p = _planner(w)
+    p = poseref.planner_of(w)
     p.plan(np.array(w.xs), np.array(w.xg))
     assert p.last_stats["j"] == w.j
     routes, length, paths = p.routes_to_poses(c.goals, points=True, shortcut=True)
@@ -205,11 +190,11 @@ def test_asked_twice_and_in_turn_with_the_plain_call(gpu_ctx):
     c = prr.case("B")
     raw, cut = c.routes, psr.of_case(c)
     assert len(cut.rows) < len(raw.rows) and len(cut.points) != len(raw.points)
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     one = b.pose_routes(0, c.goals, points=True, shortcut=True)
     two = b.pose_routes(0, c.goals, points=True, shortcut=True)
     for x, y in zip(one, two):
-        assert x.dtype == y.dtype and np.array_equal(_bits(x), _bits(y))
+        assert x.dtype == y.dtype and np.array_equal(bits(x), bits(y))
     prr.same(two, cut)
     cut_ms = b.pose_shortcuts_ms()
     assert len(cut_ms) == 5 and all(t >= 0.0 for t in cut_ms)
@@ -218,14 +203,14 @@ def test_asked_twice_and_in_turn_with_the_plain_call(gpu_ctx):
     xyh, ids = b.pose_routes_rows(len(raw.rows))
     assert np.array_equal(xyh, raw.rows) and np.array_equal(ids, raw.ids)
     assert np.array_equal(b.pose_routes_points(len(raw.points)).view(np.int64), raw.points.view(np.int64))
-    _refused("rows_wrong_count", b.pose_routes_rows, len(cut.rows), asked=len(cut.rows), left=len(raw.rows))
+    refused_with_golden_text(GOLDEN, "rows_wrong_count", b.pose_routes_rows, len(cut.rows), asked=len(cut.rows), left=len(raw.rows))
     plain_ms = b.pose_routes_ms()
     assert len(plain_ms) == 4 and all(t >= 0.0 for t in plain_ms)
     # ... and a shortcut call behind that one: its own rows and points; the plain stage times stay those of the plain call
     prr.same(b.pose_routes(0, c.goals, shortcut=True), cut, points=False)
     xyh, ids = b.pose_routes_rows(len(cut.rows))
     assert np.array_equal(xyh, cut.rows) and np.array_equal(ids, cut.ids)
-    _refused("points_none", b.pose_routes_points, len(cut.points))  # (that call asked for none)
+    refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, len(cut.points))  # (that call asked for none)
     assert b.pose_routes_ms() == plain_ms and b.pose_shortcuts_ms()[4] == 0.0
     prr.same(b.pose_routes(0, c.goals, points=True, shortcut=True), cut)
     assert np.array_equal(b.pose_routes_points(len(cut.points)).view(np.int64), cut.points.view(np.int64))
@@ -239,7 +224,7 @@ def test_no_pose_one_pose_and_a_workgroup_of_them(gpu_ctx):
     r = psr.of_case(c)
     g = int(np.argmax(np.diff(c.routes.offsets) - np.diff(r.offsets)))  # the pose whose route loses the most rows
     assert r.offsets[g + 1] - r.offsets[g] < c.routes.offsets[g + 1] - c.routes.offsets[g]
-    b = _run(gpu_ctx, c.w)
+    b = planned_batch(gpu_ctx, c.w)
     got = b.pose_routes(0, np.zeros((0, 3), dtype=np.int32), points=True, shortcut=True)
     assert [len(x) for x in got] == [0, 0, 0, 1, 0, 0, 1, 0] and got[3][0] == 0 and got[6][0] == 0
     k, n = int(r.offsets[g + 1] - r.offsets[g]), int(r.point_offsets[g + 1] - r.point_offsets[g])
@@ -260,21 +245,21 @@ def test_refusals():
     ctx = _ffi.Context(0)
     ctx.set_grid(w.og8)
     L = _ffi.lib()
-    _refused("no_plan", lambda: ctx.pose_routes(w.goals, shortcut=True))
-    _refused("plan_ms_none", ctx.pose_shortcuts_ms)
+    refused_with_golden_text(GOLDEN, "no_plan", lambda: ctx.pose_routes(w.goals, shortcut=True))
+    refused_with_golden_text(GOLDEN, "plan_ms_none", ctx.pose_shortcuts_ms)
     s = _ffi.Batch(ctx, 1, w.n)
-    _refused("non_dubins_batch", lambda: s.pose_routes(0, w.goals, shortcut=True))
+    refused_with_golden_text(GOLDEN, "non_dubins_batch", lambda: s.pose_routes(0, w.goals, shortcut=True))
     s.close()
     b = _ffi.Batch(ctx, 1, w.n, dubins=True)
-    _refused("unfinished_query", lambda: b.pose_routes(0, w.goals, shortcut=True))
-    _refused("ms_none", b.pose_shortcuts_ms)
-    q, keep = _query(w)
+    refused_with_golden_text(GOLDEN, "unfinished_query", lambda: b.pose_routes(0, w.goals, shortcut=True))
+    refused_with_golden_text(GOLDEN, "ms_none", b.pose_shortcuts_ms)
+    q, keep = poseref.device_query(w)
     b.set_query(0, q)
     b.launch()
     b.sync()
     b.pose_routes(0, c.goals, points=True)  # a plain call does not make stage times of the shortcut call
-    _refused("ms_none", b.pose_shortcuts_ms)
-    _refused("q_out_of_range", lambda: b.pose_routes(1, w.goals, shortcut=True))
+    refused_with_golden_text(GOLDEN, "ms_none", b.pose_shortcuts_ms)
+    refused_with_golden_text(GOLDEN, "q_out_of_range", lambda: b.pose_routes(1, w.goals, shortcut=True))
     prr.same(b.pose_routes(0, c.goals, points=True, shortcut=True), cut)
     rows, points = len(cut.rows), len(cut.points)
     # failed calls: each drops the rows and the points of the call before it
@@ -293,9 +278,9 @@ def test_refusals():
                            ("heading_out_of_range", lambda: raw(1, po.ctypes.data, bad_h), dict(nh=w.nh)),
                            ("cell_outside", lambda: raw(1, po.ctypes.data, bad_x), dict(x=w.og8.shape[0], W=w.og8.shape[0], H=w.og8.shape[1]))):
         b.pose_routes(0, c.goals, points=True, shortcut=True)
-        _refused(key, call, **fmt)
-        _refused("rows_none", b.pose_routes_rows, rows)
-        _refused("points_none", b.pose_routes_points, points)
+        refused_with_golden_text(GOLDEN, key, call, **fmt)
+        refused_with_golden_text(GOLDEN, "rows_none", b.pose_routes_rows, rows)
+        refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, points)
     raw(0, None)  # without the flag point_offsets may be NULL
     assert np.array_equal(offsets, cut.offsets)
     # the plain call keeps its refusal of 0x2 with its own text: the shortcuts are not a flag of it
@@ -305,14 +290,14 @@ def test_refusals():
     # a rearm
     b.pose_routes(0, c.goals, points=True, shortcut=True)
     b.rearm()
-    _refused("rows_none", b.pose_routes_rows, rows)
-    _refused("points_none", b.pose_routes_points, points)
+    refused_with_golden_text(GOLDEN, "rows_none", b.pose_routes_rows, rows)
+    refused_with_golden_text(GOLDEN, "points_none", b.pose_routes_points, points)
     b.launch()
     b.sync()
     prr.same(b.pose_routes(0, c.goals, points=True, shortcut=True), cut)
     # the grid replaced by one of the same shape
     ctx.set_grid(posekeepref.blocks_map(w.og8, w.xs))
-    _refused("grid_replaced", lambda: b.pose_routes(0, w.goals, shortcut=True))
+    refused_with_golden_text(GOLDEN, "grid_replaced", lambda: b.pose_routes(0, w.goals, shortcut=True))
     b.close()
     ctx.close()
 
@@ -320,4 +305,4 @@ def test_refusals():
 def test_the_straight_line_planners_refuse():
     w = poseref.workload("E")
     p = RRTStar(w.og, 50, 10, pbar=False)
-    _refused("straight_line_planner", lambda: p.routes_to_poses(w.goals, shortcut=True))
+    refused_with_golden_text(GOLDEN, "straight_line_planner", lambda: p.routes_to_poses(w.goals, shortcut=True))

@@ -14,8 +14,11 @@ import pytest
 
 import oracle
 import slabs
+from devcheck import KERNEL_ARGS, KERNELS_NOFAULT, check_rewired_tree
+from posecalls import assert_audit_clean, check_dubins_tree, device_vs_oracle_dubins, independent_collision_witness
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.oggen import random_connected_pair
+from slabs import fill_batch, hand_over_unitballs, query_of, same_as_oracle
 
 
 def _id(c):
@@ -91,62 +94,15 @@ def test_cross_geometry_cases_differ_and_reach_a_later_slab(name, div):
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU
-def _same_as_oracle(res, st, ro, tag, logs=True, rewire=False):
-    """the comparison of test_gpu_parity._oracle_vs_device (rewire: that of test_rewire._device_vs_oracle_rewire, which has the
-    rewire counts in place of the tree-size log and the three sums)"""
-    live = ro.j + (1 if ro.found else 0)
-    assert res.status == st and res.j == ro.j and res.found == ro.found and res.vgoal == ro.vgoal and res.i_switch == ro.i_switch, tag
-    if logs:
-        assert np.array_equal(res.nearest_log, ro.nearest_log), tag
-        assert np.array_equal(res.accept_log, ro.accept_log), tag
-        assert rewire or np.array_equal(res.j_log, ro.jlog), tag
-        assert np.array_equal(res.cbest_log, ro.cbest_log, equal_nan=True), tag
-    assert np.array_equal(res.pts[:live], ro.pts[:live]), tag
-    assert np.array_equal(res.parent[:live], ro.parent[:live]), tag
-    assert np.array_equal(res.vcost[:live], ro.vcost[:live]), tag
-    if rewire:
-        assert (res.n_rewired, res.n_propagated) == (ro.n_rewired, ro.n_propagated), tag
-    else:
-        assert res.sum_j == ro.sum_j and res.sum_cells_nn == ro.sum_cells_nn and res.sum_near == ro.sum_near, tag
-
-
-def _query_of(alg, n, xs, xg, samples, r2, rg):
-    kw = {}
-    if alg == 2:
-        kw = dict(goal_d2=hostprep.goal_threshold(rg), Cmat=hostprep.rotation_to_world_frame(np.asarray(xs, dtype=np.int64), np.asarray(xg, dtype=np.int64)))
-    return _ffi.make_query(alg, n, xs, xg, samples, r2_rewire=r2, **kw)
-
-
 _GROUP1 = {"onebody": {"onebody": True}, "onebody8": {"team": 8, "onebody": True}}
 
 
 def _kernel_args(kernel):
-    from test_gpu_parity import _KERNEL_ARGS
-
-    return _GROUP1.get(kernel) or _KERNEL_ARGS[kernel]
+    return _GROUP1.get(kernel) or KERNEL_ARGS[kernel]
 
 
 def _group1_kernels():
-    from test_gpu_parity import KERNELS_NOFAULT
-
     return KERNELS_NOFAULT + list(_GROUP1)
-
-
-def _hand_over(b, qs, tag):
-    """The queries of a launched batch whose oracle run took the unit-ball hand-over (d["ub"]): each must wait at the oracle's
-    i_switch; every one gets its stream and the batch is launched again.  Returns how many there were."""
-    waiting = 0
-    for q, d in enumerate(qs):
-        if d.get("ub") is None:
-            continue
-        r = b.get_result(q, arrays=False)
-        assert r.c.status == _ffi.RRT_NEED_UNITBALL and r.c.i_switch == d["ro"].i_switch, (tag, q)
-        b.set_unitball(q, d["ub"], r.c.i_switch)
-        waiting += 1
-    if waiting:
-        b.launch()
-        b.sync()
-    return waiting
 
 
 def _run_slab_case(ctx, c, kernel):
@@ -154,13 +110,13 @@ def _run_slab_case(ctx, c, kernel):
     d = slabs.slab_case(c)
     ctx.set_grid(d["og8"])
     b = _ffi.Batch(ctx, 1, c["n"], logs=True, **_kernel_args(kernel))
-    qu, keep = _query_of(c["alg"], c["n"], d["xs"], d["xg"], d["samples"], d["r2"], c["rg"])
+    qu, keep = query_of(c["alg"], c["n"], d["xs"], d["xg"], d["samples"], d["r2"], c["rg"])
     b.set_query(0, qu)
     b.launch()
     b.sync()
     name = b.kernel_name()
-    _hand_over(b, [d], (c["id"], kernel))
-    _same_as_oracle(b.get_result(0), d["st"], d["ro"], (c["id"], kernel))
+    hand_over_unitballs(b, [d], (c["id"], kernel))
+    same_as_oracle(b.get_result(0), d["st"], d["ro"], (c["id"], kernel))
     info = b.team_info()
     b.close()
     return name, info
@@ -202,30 +158,19 @@ def test_slab_radius_on_a_team_that_loses_a_member(gpu_ctx):
 @pytest.mark.parametrize("serial", [False, True])
 @pytest.mark.parametrize("c", slabs.DUBINS_SLAB_CASES, ids=_id)
 def test_dubins_near_sets_past_64_cells(gpu_ctx, c, serial):
-    from test_dubins import _assert_audit_clean, _check_dubins_tree, _device_vs_oracle_dubins, _independent_collision_witness
-
     d = slabs.dubins_slab_case(c)
     gpu_ctx.set_grid(d["og8"])
-    res, ro = _device_vs_oracle_dubins(gpu_ctx, d["og8"], 1, c["n"], d["xs"], d["xg"], d["samples"], d["heads"], c["rr"], c["rho"], serial=serial)
-    _check_dubins_tree(d["og8"], res, c["rho"], 64, d["xs"])
+    res, ro = device_vs_oracle_dubins(gpu_ctx, d["og8"], 1, c["n"], d["xs"], d["xg"], d["samples"], d["heads"], c["rr"], c["rho"], serial=serial)
+    check_dubins_tree(d["og8"], res, c["rho"], 64, d["xs"])
     if not serial:
-        _independent_collision_witness(d["og8"], res, d["samples"], d["heads"], c["rho"], 64)
+        independent_collision_witness(d["og8"], res, d["samples"], d["heads"], c["rho"], 64)
     a = oracle.dubins_audit(d["og8"], c["n"], 1, d["samples"], d["heads"], res.pts, res.head, res.vcost, res.parent, res.j, r2_rewire=d["r2"],
                             rho=c["rho"], nh=64)
     assert a["n_accepted"] == res.j - 1
-    _assert_audit_clean(a, 1)
+    assert_audit_clean(a, 1)
 
 
 # ---- cross-geometry launches -----------------------------------------------------------------------------------------
-def _fill(b, qs):
-    keep = []
-    for q, d in enumerate(qs):
-        qu, k = _query_of(d["alg"], d["n"], d["xs"], d["xg"], d["samples"], d["r2"], d["rg"])
-        keep.append(k)
-        b.set_query(q, qu)
-    return keep
-
-
 def _resume_informed(b, og8, qs):
     """The Informed queries of a launched batch: hand each its unit-ball stream, launch again, compare with the oracle's run
     on the same stream (as test_pipelined_informed_batch_has_no_timeouts does).  Returns how many were resumed."""
@@ -248,7 +193,7 @@ def _resume_informed(b, og8, qs):
         kw = dict(unitball=waiting[q][0], ub_offset=waiting[q][1]) if q in waiting else {}
         Cm = hostprep.rotation_to_world_frame(np.asarray(d["xs"], dtype=np.int64), np.asarray(d["xg"], dtype=np.int64))
         st, ro = oracle.plan(og8, d["n"], 2, d["xs"], d["xg"], d["samples"], r2_rewire=d["r2"], r_goal=d["rg"], Cmat=Cm, **kw)
-        _same_as_oracle(b.get_result(q), st, ro, f"Informed query {q}")
+        same_as_oracle(b.get_result(q), st, ro, f"Informed query {q}")
     return len(waiting)
 
 
@@ -259,18 +204,18 @@ def test_block_kernel_on_the_pipelines_cells(gpu_ctx):
     X, (og8, qs) = _xgeo("XGEO_A", slabs.DIV_PIPE)
     gpu_ctx.set_grid(og8)
     b = _ffi.Batch(gpu_ctx, len(qs), X["n"], logs=True, team=1)
-    keep = _fill(b, qs)
+    keep = fill_batch(b, qs)
     b.launch()
     b.sync()
     assert b.kernel_name() == "rrt_expand_block_kernel<1, 16, false, true>" and b.team_info()["last"] == 1
     for q, d in enumerate(qs):
         if d["alg"] != 2:
-            _same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q}")
+            same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q}")
     assert _resume_informed(b, og8, qs) >= 1
     assert b.kernel_name() == "rrt_expand_block_kernel<1, 16, false, true>"
     for q, d in enumerate(qs):  # the finished queries are untouched by the second launch
         if d["alg"] != 2:
-            _same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q} after the resume")
+            same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q} after the resume")
     b.close()
     del keep
 
@@ -282,7 +227,7 @@ def test_team_of_two_on_the_pipelines_cells(gpu_ctx):
     X, (og8, qs) = _xgeo("XGEO_B", slabs.DIV_PIPE)
     gpu_ctx.set_grid(og8)
     b = _ffi.Batch(gpu_ctx, len(qs), X["n"], logs=True)
-    keep = _fill(b, qs)
+    keep = fill_batch(b, qs)
     b.launch()
     b.sync()
     assert b.kernel_name() == "rrt_expand_block_kernel<2, 16, false, true>", b.kernel_name()
@@ -290,7 +235,7 @@ def test_team_of_two_on_the_pipelines_cells(gpu_ctx):
     assert info["last"] == 2 and info["timeouts"] == 0, info
     for q, d in enumerate(qs):
         if d["alg"] != 2:
-            _same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q}")
+            same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q}")
     _resume_informed(b, og8, qs)
     assert b.team_info()["timeouts"] == 0
     b.close()
@@ -313,7 +258,7 @@ def test_pipeline_on_the_teams_cells(gpu_ctx):
     for q in range(Qh):
         hold.set_query(q, hq)
     b = _ffi.Batch(gpu_ctx, len(qs), X["n"], logs=True)
-    keep = _fill(b, qs)
+    keep = fill_batch(b, qs)
     created = b.team_info()["created"]
     assert created > 1 and b.team_info()["shrunk"] == 0
     hold.launch()
@@ -323,7 +268,7 @@ def test_pipeline_on_the_teams_cells(gpu_ctx):
     info = b.team_info()
     assert b.kernel_name() == "rrt_pipe_kernel" and info["last"] == 1 and info["shrunk"] == 1 and info["timeouts"] == 0, (b.kernel_name(), info)
     for q, d in enumerate(qs):
-        _same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q} on the pipeline")
+        same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q} on the pipeline")
     st, ro = oracle.plan(og8, nh, 0, qs[0]["xs"], qs[0]["xg"], hs)
     for q in (0, Qh - 1):
         r = hold.get_result(q)
@@ -335,7 +280,7 @@ def test_pipeline_on_the_teams_cells(gpu_ctx):
     info = b.team_info()
     assert info == dict(created=created, last=created, timeouts=0, shrunk=1) and b.kernel_name() != "rrt_pipe_kernel", (b.kernel_name(), info)
     for q, d in enumerate(qs):
-        _same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q} on the team")
+        same_as_oracle(b.get_result(q), d["st"], d["ro"], f"query {q} on the team")
     b.close()
     del keep, hkeep
 
@@ -380,7 +325,7 @@ def test_five_queries_on_the_one_sample_kernels(gpu_ctx, mode):
     if rewire:
         assert qs[3]["ub"] is not None and sum(d["ro"].n_rewired > 0 for d in qs) >= 3
     b = _ffi.Batch(gpu_ctx, len(qs), max(_MULTI_N), logs=True, rewire=rewire, serial=not rewire)
-    keep = _fill(b, qs)
+    keep = fill_batch(b, qs)
     for rep in range(2):
         b.launch()
         b.sync()
@@ -394,7 +339,7 @@ def test_five_queries_on_the_one_sample_kernels(gpu_ctx, mode):
                 b.sync()
         for q, d in enumerate(qs):
             res = b.get_result(q)
-            _same_as_oracle(res, d["st"], d["ro"], (mode, rep, q), rewire=rewire)
+            same_as_oracle(res, d["st"], d["ro"], (mode, rep, q), rewire=rewire)
             assert (res.n_rewired, res.n_propagated) == (d["ro"].n_rewired, d["ro"].n_propagated), (mode, rep, q)
         b.rearm()
     b.close()
@@ -448,8 +393,6 @@ def test_five_dubins_queries_with_logs(gpu_ctx, serial):
 def test_rewire_batch_of_more_queries_than_compute_units(gpu_ctx):
     """300 rewire queries of n = 300: more workgroups than the device has CUs, every per-query stride of the child lists and the
     frontier in use."""
-    from test_rewire import _check_tree
-
     og, og8 = slabs.grid_of(300, 260, 5)
     gpu_ctx.set_grid(og8)
     free = np.argwhere(og8 == 0)
@@ -471,8 +414,8 @@ def test_rewire_batch_of_more_queries_than_compute_units(gpu_ctx):
     assert b.kernel_name() == "rrt_expand_kernel<true, false>"
     for q, (xs, st, ro) in enumerate(refs):
         res = b.get_result(q)
-        _same_as_oracle(res, st, ro, f"query {q}", rewire=True)
+        same_as_oracle(res, st, ro, f"query {q}", rewire=True)
         if q in (0, 1, 150, 299):
-            _check_tree(og8, res, xs)
+            check_rewired_tree(og8, res, xs)
     b.close()
     del keep

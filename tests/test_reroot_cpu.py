@@ -17,48 +17,13 @@ import pytest
 import growref
 import keepref
 import oracle
-import orchelp
 import rerootref
+from plannedcases import GROW_CASES, MAZE, NOISE, grow_setup, hand_tree, one_way_edges, oracle_planned, roots_behind
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTDubins, RRTStarDubins
-from test_grow_cpu import CASES, _hand_tree, _setup
 
-G = orchelp.golden("plans_A.npz")
-_cache = {}
-
-
-def planned(grid, alg, n, seed):
-    """the recipe of the issue: xs, xg as test_grow_cpu._setup draws them, then n samples; the oracle's plan"""
-    key = (grid, alg, n, seed)
-    if key not in _cache:
-        og8 = oracle.og_u8(G.grid(grid))
-        free = np.argwhere(og8 == 0)
-        rng = np.random.default_rng(seed)
-        xs, xg = free[rng.integers(len(free))], free[rng.integers(len(free))]
-        samples = hostprep.draw_free_samples(rng, free, n)
-        r2 = hostprep.radius_threshold(12) if alg else 0
-        st, ro = oracle.plan(og8, n, alg, xs, xg, samples, r2_rewire=r2)
-        _cache[key] = dict(og8=og8, xs=xs, xg=xg, samples=samples, r2=r2, st=st, ro=ro, n=n, alg=alg)
-    return _cache[key]
-
-
-MAZE = ("maze64x96", 1, 250, 13)
-NOISE = ("noise200", 1, 1500, 16)
 CLEAN = [("noise200", 0, 300, 11), ("noise200", 1, 300, 12), ("square100", 0, 200, 14), ("square100", 1, 200, 15)]
-
-
-def one_way_edges(c):
-    """the vertices k whose edge is free parent -> child and blocked child -> parent"""
-    ro, og8 = c["ro"], c["og8"]
-    return [k for k in range(1, ro.j) if oracle.collisionfree(og8, ro.pts[int(ro.parent[k])], ro.pts[k])[0]
-            and not oracle.collisionfree(og8, ro.pts[k], ro.pts[int(ro.parent[k])])[0]]
-
-
-def roots_behind(c, edges):
-    """the candidate roots whose way to vertex 0 reverses one of `edges`"""
-    ro = c["ro"]
-    return [r for r in range(ro.j) if set(rerootref.path_to_root(ro.parent, ro.j, r)[:-1]) & set(edges)]
 
 
 def walked_cost(pts, new_parent, r, k):
@@ -90,9 +55,9 @@ def check_properties(c, R, r):
 
 
 # ------------------------------------------------------------------------------------------------ pinned on the oracle
-@pytest.mark.parametrize("grid,alg,n,m,seed", CASES)
+@pytest.mark.parametrize("grid,alg,n,m,seed", GROW_CASES)
 def test_reroot_at_zero_is_the_same_tree_renumbered(grid, alg, n, m, seed):
-    og8, xs, xg, samples, r2 = _setup(grid, alg, n, m, seed)
+    og8, xs, xg, samples, r2 = grow_setup(grid, alg, n, m, seed)
     st, ro = oracle.plan(og8, n, alg, xs, xg, samples[:n], r2_rewire=r2)
     R = rerootref.reroot(og8, ro.pts, ro.parent, ro.j, 0)
     assert R.d == 0 and not R.reversed_ok and sorted(R.ids.tolist()) == list(range(ro.j)) and R.ids[0] == 0
@@ -105,7 +70,7 @@ def test_reroot_at_zero_is_the_same_tree_renumbered(grid, alg, n, m, seed):
 
 # ------------------------------------------------------------------------------------------------ hand-written trees
 def test_hand_tree_rerooted_at_a_leaf():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     R = rerootref.reroot(og, pts, parent, 6, 4)
     assert R.d == 3 and R.path == [4, 3, 1, 0] and R.ids.tolist() == [4, 3, 1, 0, 2, 5] and R.parent.tolist() == [-1, 0, 1, 2, 3, 4]
@@ -118,7 +83,7 @@ def test_hand_tree_rerooted_at_a_leaf():
 
 
 def test_hand_tree_rerooted_at_an_inner_vertex():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     R = rerootref.reroot(og, pts, parent, 6, 1)
     assert R.d == 1 and R.ids.tolist() == [1, 0, 3, 2, 4, 5] and R.parent.tolist() == [-1, 0, 0, 1, 2, 3]
@@ -127,7 +92,7 @@ def test_hand_tree_rerooted_at_an_inner_vertex():
 
 
 def test_a_blocked_cell_on_a_reversed_edge_cuts_exactly_the_far_side():
-    pts, parent, vcost = _hand_tree()
+    pts, parent, vcost = hand_tree()
     og = np.zeros((20, 20), dtype=np.uint8)
     og[2, 13] = 1  # on the edge 1 - 3
     R = rerootref.reroot(og, pts, parent, 6, 4)
@@ -144,7 +109,7 @@ def test_a_blocked_cell_on_a_reversed_edge_cuts_exactly_the_far_side():
 
 # ------------------------------------------------------------------------------------------------ the inputs and their conditions
 def test_the_maze_input_has_one_one_way_edge():
-    c = planned(*MAZE)
+    c = oracle_planned(*MAZE)
     ro = c["ro"]
     assert ro.j == 77 and keepref.depth(ro.parent, ro.j).max() == 9
     assert one_way_edges(c) == [21] and len(roots_behind(c, [21])) == 2
@@ -157,7 +122,7 @@ def test_the_maze_input_has_one_one_way_edge():
 
 
 def test_the_noise_input_has_four_one_way_edges():
-    c = planned(*NOISE)
+    c = oracle_planned(*NOISE)
     ro = c["ro"]
     assert ro.j == 1363 and keepref.depth(ro.parent, ro.j).max() == 16
     edges = one_way_edges(c)
@@ -172,7 +137,7 @@ def test_the_noise_input_has_four_one_way_edges():
 
 @pytest.mark.parametrize("grid,alg,n,seed", CLEAN)
 def test_the_clean_inputs_have_none_and_round_trip(grid, alg, n, seed):
-    c = planned(grid, alg, n, seed)
+    c = oracle_planned(grid, alg, n, seed)
     ro, og8 = c["ro"], c["og8"]
     assert one_way_edges(c) == []
     dep = keepref.depth(ro.parent, ro.j)
@@ -193,7 +158,7 @@ def test_the_clean_inputs_have_none_and_round_trip(grid, alg, n, seed):
 
 
 def test_reroot_then_grow_feeds_the_loop_like_a_seed():
-    c = planned("noise200", 1, 300, 12)
+    c = oracle_planned("noise200", 1, 300, 12)
     ro = c["ro"]
     r = int(np.argmax(keepref.depth(ro.parent, ro.j)))
     R = rerootref.reroot(c["og8"], ro.pts, ro.parent, ro.j, r)

@@ -14,28 +14,23 @@ import keepref
 import oracle
 import rerootref
 import routeref
-import test_grow_gpu as tg
+import treecalls as tc
+from plannedcases import MAZE, NOISE, one_way_edges, oracle_planned, roots_behind
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
-from test_reroot_cpu import MAZE, NOISE, one_way_edges, planned, roots_behind
 
 pytestmark = pytest.mark.gpu
 
 
-def _case(og8, alg, n, xs, xg, samples, r2):
-    st, ro = oracle.plan(og8, n, alg, xs, xg, samples, r2_rewire=r2)
-    return dict(og8=og8, xs=np.asarray(xs), xg=np.asarray(xg), samples=samples, st=st, ro=ro, n=n, alg=alg, r2=r2)
-
-
-def _run(b, q, c):
+def _planned_tree(b, q, c):
     """query q planned on the device and equal to the oracle's plan; its tree"""
-    keep = tg._set_and_run(b, q, c)
+    keep = tc.set_case_query(b, q, c)
     b.launch()
     b.sync()
     res = b.get_result(q)
     ro = c["ro"]
     assert res.j == ro.j and np.array_equal(res.parent[:ro.j], ro.parent[:ro.j]) and np.array_equal(res.vcost[:ro.j].view(np.int64), ro.vcost[:ro.j].view(np.int64))
-    return tg._tree_of(res)
+    return tc.tree_of(res)
 
 
 def _restate(og8, prev, view, r, samples, c):
@@ -59,12 +54,12 @@ def _reroot(b, q, og8, prev, view, r, samples, c, shape=None):
     b.launch()
     b.sync()
     res = b.get_result(q)
-    tg._same_result(res, g, log0)
+    tc.same_result(res, g, log0)
     assert np.array_equal(res.pts[0], prev[0][r]) and res.vcost[0] == 0.0 and res.parent[0] == -1
     info = b.team_info()
     assert info["timeouts"] == 0 and b.team()[1] == 0, info
     if shape:
-        assert tg.SHAPES[shape][1](b.kernel_name()), b.kernel_name()
+        assert tc.SHAPES[shape][1](b.kernel_name()), b.kernel_name()
     return R, g, res
 
 
@@ -85,10 +80,10 @@ def _mid(prev):
 @pytest.mark.parametrize("inp", [("noise200", 1, 300, 12), ("square100", 0, 200, 14)])
 @pytest.mark.parametrize("which", ["root", "leaf", "mid"])
 def test_plain_reroot_on_a_clean_tree(gpu_ctx, which, inp):
-    c = planned(*inp)
+    c = oracle_planned(*inp)
     assert one_way_edges(c) == []
-    b = tg._batch(gpu_ctx, c, "team")
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    prev = _planned_tree(b, 0, c)
     r = dict(root=0, leaf=_deepest(prev), mid=_mid(prev))[which]
     R, g, res = _reroot(b, 0, c["og8"], prev, False, r, NONE, c, "team")
     assert len(R.ids) == prev[3] and all(R.reversed_ok.values()) and R.d == keepref.depth(prev[1], prev[3])[r] and res.i_switch == c["n"]
@@ -97,70 +92,50 @@ def test_plain_reroot_on_a_clean_tree(gpu_ctx, which, inp):
 
 @pytest.mark.parametrize("inp", [MAZE, NOISE])
 def test_a_root_behind_a_one_way_edge_cuts_the_far_side(gpu_ctx, inp):
-    c = planned(*inp)
+    c = oracle_planned(*inp)
     edges = one_way_edges(c)
     roots = roots_behind(c, edges)
     assert edges and roots
     ro = c["ro"]
     r = max(roots, key=lambda v: len(rerootref.path_to_root(ro.parent, ro.j, v)))  # the deepest of them
-    b = tg._batch(gpu_ctx, c, "team")
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    prev = _planned_tree(b, 0, c)
     R, g, res = _reroot(b, 0, c["og8"], prev, False, r, NONE, c, "team")
     assert not all(R.reversed_ok.values()) and 1 <= len(R.ids) < prev[3] - 1 and res.j == len(R.ids)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 2. shapes that can break a stage
-SIZES = [1, 2, 63, 64, 65, 1023, 1024, 1025]
-
-
-def _sized(k, seed):
-    """an empty 64 x 64 map and samples that leave a tree of exactly k vertices: k - 1 distinct cells, then repeats"""
-    og8 = np.zeros((64, 64), dtype=np.uint8)
-    rng = np.random.default_rng(seed)
-    cells = rng.permutation(64 * 64)
-    xs = np.array(divmod(int(cells[0]), 64))
-    distinct = np.array([divmod(int(v), 64) for v in cells[1:k]], dtype=np.int64).reshape(-1, 2)
-    n = 1040
-    fill = np.tile(distinct[:1] if k > 1 else xs[None, :], (n - (k - 1), 1))
-    if k == 1:
-        og8 = og8.copy()
-        og8[max(xs[0] - 1, 0):xs[0] + 2, max(xs[1] - 1, 0):xs[1] + 2] = 1
-        og8[xs[0], xs[1]] = 0  # the start boxed in: no sample is ever accepted
-        fill = np.tile(np.array([[(xs[0] + 5) % 64, (xs[1] + 5) % 64]]), (n, 1))
-    return og8, xs, np.concatenate([distinct, fill])[:n], n
-
-
 def test_trees_of_exactly_1_2_63_to_65_and_1023_to_1025_vertices(gpu_ctx):
     cs = []
-    for k in SIZES:
-        og8, xs, samples, n = _sized(k, 100 + k)
+    for k in tc.SIZES:
+        og8, xs, samples, n = tc.sized(k, 100 + k)
         if k != 1:
-            cs.append(_case(og8, 0, n, xs, (63, 63), samples, 0))
-    b = tg._batch(gpu_ctx, cs[0], "team", Q=len(cs), n_cap=1040)
+            cs.append(tc.oracle_case(og8, 0, n, xs, (63, 63), samples, 0))
+    b = tc.shaped_batch(gpu_ctx, cs[0], "team", Q=len(cs), n_cap=1040)
     prevs = [None] * len(cs)
     for q, c in enumerate(cs):
-        tg._set_and_run(b, q, c)
+        tc.set_case_query(b, q, c)
     b.launch()
     b.sync()
     armed = []
     for q, c in enumerate(cs):
-        prev = tg._tree_of(b.get_result(q))
-        assert prev[3] == c["ro"].j == SIZES[q + 1]
+        prev = tc.tree_of(b.get_result(q))
+        assert prev[3] == c["ro"].j == tc.SIZES[q + 1]
         r = _deepest(prev)
         R, g = _restate(c["og8"], prev, False, r, NONE, c)
         armed.append((g, _arm(b, q, r, NONE, R)))
     b.launch()
     b.sync()
     for q, (g, log0) in enumerate(armed):
-        tg._same_result(b.get_result(q), g, log0)
+        tc.same_result(b.get_result(q), g, log0)
     b.close()
     # the tree of one vertex: the start boxed in
-    og8, xs, samples, n = _sized(1, 101)
-    c = _case(og8, 0, n, xs, (63, 63) if tuple(xs) != (63, 63) else (0, 0), samples, 0)
+    og8, xs, samples, n = tc.sized(1, 101)
+    c = tc.oracle_case(og8, 0, n, xs, (63, 63) if tuple(xs) != (63, 63) else (0, 0), samples, 0)
     assert c["ro"].j == 1
-    b = tg._batch(gpu_ctx, c, "team")
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    prev = _planned_tree(b, 0, c)
     R, g, res = _reroot(b, 0, og8, prev, False, 0, NONE, c)
     assert res.j == 1 and len(R.ids) == 1
     b.close()
@@ -171,11 +146,11 @@ def test_a_chain_of_1100_vertices_rerooted_at_its_far_end(gpu_ctx):
     og8 = np.zeros((1104, 1104), dtype=np.uint8)
     chain = np.stack([np.arange(1, 1100), np.arange(1, 1100)], axis=1)
     samples = np.concatenate([chain, np.tile(chain[:1], (9, 1))])
-    c = _case(og8, 0, 1108, (0, 0), (1103, 0), samples, 0)
+    c = tc.oracle_case(og8, 0, 1108, (0, 0), (1103, 0), samples, 0)
     ro = c["ro"]
     assert ro.j == 1100 and np.array_equal(ro.parent[1:1100], np.arange(1099))
-    b = tg._batch(gpu_ctx, c, "team")
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    prev = _planned_tree(b, 0, c)
     R, g, res = _reroot(b, 0, og8, prev, False, 1099, NONE, c)
     assert R.d == 1099 and np.array_equal(R.ids, np.arange(1099, -1, -1)) and np.array_equal(res.parent[1:1100], np.arange(1099))
     b.close()
@@ -187,11 +162,11 @@ def test_a_star_with_one_level_of_2000_vertices(gpu_ctx):
     vec = [(dx, dy) for dx in range(-50, 51) for dy in range(-50, 51) if np.gcd(dx, dy) == 1]  # no lattice point between it and the start
     rays = np.array(vec, dtype=np.int64)[np.random.default_rng(7).permutation(len(vec))[:2000]] + 50
     samples = np.concatenate([rays, np.tile(rays[:1], (9, 1))])
-    c = _case(og8, 1, 2009, (50, 50), (100, 100), samples, hostprep.radius_threshold(80))
+    c = tc.oracle_case(og8, 1, 2009, (50, 50), (100, 100), samples, hostprep.radius_threshold(80))
     ro = c["ro"]
     assert ro.j == 2001 and (ro.parent[1:2001] == 0).all()
-    b = tg._batch(gpu_ctx, c, "team", Q=2)
-    prevs = [_run(b, q, c) for q in range(2)]
+    b = tc.shaped_batch(gpu_ctx, c, "team", Q=2)
+    prevs = [_planned_tree(b, q, c) for q in range(2)]
     out = []
     for q, r in enumerate((0, 1000)):
         R, g = _restate(og8, prevs[q], False, r, NONE, c)
@@ -199,18 +174,18 @@ def test_a_star_with_one_level_of_2000_vertices(gpu_ctx):
     b.launch()
     b.sync()
     for q, (R, g, log0) in enumerate(out):
-        tg._same_result(b.get_result(q), g, log0)
+        tc.same_result(b.get_result(q), g, log0)
     assert (out[0][0].depth == 1).sum() == 2000 and (out[1][0].depth == 2).sum() == 1999
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 3. after keep_tree
 def test_a_kept_view_is_rerooted_in_the_callers_numbers(gpu_ctx):
-    c = tg._base()
-    w = tg._wall(c)
+    c = tc.base()
+    w = tc.wall(c)
     og2 = w["og2"]
-    b = tg._batch(gpu_ctx, c, "team")
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    prev = _planned_tree(b, 0, c)
     gpu_ctx.set_grid(og2)
     assert np.array_equal(b.keep_tree(0), w["alive"])
     alive = np.flatnonzero(w["alive"])
@@ -218,29 +193,29 @@ def test_a_kept_view_is_rerooted_in_the_callers_numbers(gpu_ctx):
     r = int(alive[np.argmax(dep[alive])])
     dead = int(np.flatnonzero(~w["alive"])[0])
     assert r != np.flatnonzero(w["ids"] == r)[0]  # its number in the view is another one: the caller's number is what the call takes
-    goals = tg._goals(og2)
+    goals = tc.mixed_goals(og2)
     before = b.connect_goals(0, goals)
-    msg = tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, dead))
+    msg = tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, dead))
     assert f"root={dead} is not alive" in msg
     after = b.connect_goals(0, goals)
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])  # the view stands
     R, g, res = _reroot(b, 0, og2, prev, True, r, NONE, c, "team")
     assert len(R.ids) <= len(alive) and set(R.ids.tolist()) <= set(alive.tolist()) and R.d == dep[r] > 3
-    tg._goals_and_routes(b, 0, og2, res)
+    tc.goals_and_routes(b, 0, og2, res)
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4. m > 0 on every launch shape
-@pytest.mark.parametrize("shape", list(tg.SHAPES))
+@pytest.mark.parametrize("shape", list(tc.SHAPES))
 def test_reroot_then_grow_on_every_launch_shape(gpu_ctx, shape):
-    c = tg._base()
+    c = tc.base()
     ro = c["ro"]
     m = min(c["n"] - ro.j, 150)
     assert ro.j > 1000 and m >= 100
     more = hostprep.draw_free_samples(np.random.default_rng(33), np.argwhere(c["og8"] == 0), m)
     more[3] = ro.pts[0]  # the old start drawn again: its cell is a vertex's now, so it is refused
-    b = tg._batch(gpu_ctx, c, shape)
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, shape)
+    prev = _planned_tree(b, 0, c)
     r = _mid(prev)
     R, g, res = _reroot(b, 0, c["og8"], prev, False, r, more, c, shape)
     assert g.j > g.j0 + 20 and not g.accept_log[3] and R.d >= 3
@@ -249,15 +224,15 @@ def test_reroot_then_grow_on_every_launch_shape(gpu_ctx, shape):
 
 # ------------------------------------------------------------------------------------------------ 5. afterwards
 def test_the_tree_calls_answer_on_the_rerooted_tree(gpu_ctx):
-    c = tg._base()
+    c = tc.base()
     og8 = c["og8"]
-    b = tg._batch(gpu_ctx, c, "team")
-    prev = _run(b, 0, c)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    prev = _planned_tree(b, 0, c)
     r = _mid(prev)
     R, g, res = _reroot(b, 0, og8, prev, False, r, NONE, c)
-    cur = tg._tree_of(res)
-    tg._goals_and_routes(b, 0, og8, res)  # connect_goals, and routes with shortcuts
-    goals = tg._goals(og8)
+    cur = tc.tree_of(res)
+    tc.goals_and_routes(b, 0, og8, res)  # connect_goals, and routes with shortcuts
+    goals = tc.mixed_goals(og8)
     for x, y in zip(b.routes(0, goals), routeref.routes(og8, cur[0], cur[2], cur[1], cur[3], goals, cut=False)):
         assert np.array_equal(x, y)  # raw routes: they begin at the new start
     # rearm + launch plans from the new start
@@ -270,17 +245,17 @@ def test_the_tree_calls_answer_on_the_rerooted_tree(gpu_ctx):
     assert again.j == rn.j and again.found == rn.found and np.array_equal(again.pts[:live], rn.pts[:live]) and np.array_equal(again.parent[:live], rn.parent[:live])
     assert np.array_equal(again.vcost[:live].view(np.int64), rn.vcost[:live].view(np.int64)) and np.array_equal(again.pts[0], prev[0][r])
     # a second reroot, a keep_tree on another map, and a grow behind it
-    cur = tg._tree_of(again)
+    cur = tc.tree_of(again)
     R2, g2, res2 = _reroot(b, 0, og8, cur, False, _deepest(cur), NONE, c)
-    cur = tg._tree_of(res2)
-    w = tg._wall(c)
+    cur = tc.tree_of(res2)
+    w = tc.wall(c)
     gpu_ctx.set_grid(w["og2"])
     alive = b.keep_tree(0)
     assert np.array_equal(alive, keepref.alive(w["og2"], cur[0], cur[1], cur[3]))
     if alive[0]:
         m = min(c["n"] - int(alive.sum()), 120)
-        g3, res3 = tg._grow(b, 0, w["og2"], cur, True, hostprep.draw_free_samples(np.random.default_rng(8), np.argwhere(w["og2"] == 0), m), c, "team")
-        tg._goals_and_routes(b, 0, w["og2"], res3, connected=0)
+        g3, res3 = tc.grow_checked(b, 0, w["og2"], cur, True, hostprep.draw_free_samples(np.random.default_rng(8), np.argwhere(w["og2"] == 0), m), c, "team")
+        tc.goals_and_routes(b, 0, w["og2"], res3, connected=0)
     b.close()
 
 
@@ -291,16 +266,16 @@ def _stands(answer, goals, before):
 
 
 def test_batch_refusals_change_nothing(gpu_ctx):
-    c = tg._base()
-    w = tg._wall(c)
-    b = tg._batch(gpu_ctx, c, "pipe1")
-    tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))  # no query set
-    tg._set_and_run(b, 0, c)
-    assert "has not finished" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))  # not launched
+    c = tc.base()
+    w = tc.wall(c)
+    b = tc.shaped_batch(gpu_ctx, c, "pipe1")
+    tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))  # no query set
+    tc.set_case_query(b, 0, c)
+    assert "has not finished" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))  # not launched
     b.launch()
     b.sync()
     r0 = b.get_result(0)
-    goals = tg._goals(c["og8"])
+    goals = tc.mixed_goals(c["og8"])
     ans0 = b.connect_goals(0, goals)
     j0, log0 = ctypes.c_int32(-1), ctypes.c_int32(-1)
     L = _ffi.lib()
@@ -308,29 +283,29 @@ def test_batch_refusals_change_nothing(gpu_ctx):
     assert (j0.value, log0.value) == (-1, -1) and b"m=-1" in L.rrt_last_error_string(gpu_ctx.handle)
     assert L.rrt_batch_reroot(b._h, 0, 0, None, 0, None, None, ctypes.byref(log0)) == _ffi.RRT_E_ARG  # NULL j0
     room = c["n"] - r0.j
-    assert "q=1 of 1" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(1, 0))
-    assert f"room for {room}" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0, c["samples"][:room + 1]))
+    assert "q=1 of 1" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(1, 0))
+    assert f"room for {room}" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0, c["samples"][:room + 1]))
     for bad in (-1, r0.j, r0.j + 5):
-        assert f"root={bad}, query 0 has the vertices [0, {r0.j})" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, bad))
-    assert "outside the" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0, np.array([(5, 5), (200, 5)])))
+        assert f"root={bad}, query 0 has the vertices [0, {r0.j})" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, bad))
+    assert "outside the" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0, np.array([(5, 5), (200, 5)])))
     _stands(lambda g: b.connect_goals(0, g), goals, ans0)
     # a new grid without keep_tree
     gpu_ctx.set_grid(w["og2"])
-    assert "was not kept on it (rrt_batch_keep_tree)" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))
+    assert "was not kept on it (rrt_batch_keep_tree)" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))
     # the root blocked: an empty view
     og3 = w["og2"].copy()
     og3[c["xs"][0], c["xs"][1]] = 1
     gpu_ctx.set_grid(og3)
     assert not b.keep_tree(0).any()
     v0 = b.connect_goals(0, goals)
-    assert "root is blocked" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))
+    assert "root is blocked" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 0))
     _stands(lambda g: b.connect_goals(0, g), goals, v0)
     # a root that the wall cut
     gpu_ctx.set_grid(w["og2"])
     assert np.array_equal(b.keep_tree(0), w["alive"])
     v1 = b.connect_goals(0, goals)
     dead = int(np.flatnonzero(~w["alive"])[-1])
-    assert f"root={dead} is not alive" in tg._refused(_ffi.RRT_E_ARG, lambda: b.reroot(0, dead))
+    assert f"root={dead} is not alive" in tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, dead))
     _stands(lambda g: b.connect_goals(0, g), goals, v1)
     # after all these refusals the tree is what it was
     gpu_ctx.set_grid(c["og8"])
@@ -344,7 +319,7 @@ def test_batch_refusals_change_nothing(gpu_ctx):
     # what the batch cannot re-root
     for kw, why in ((dict(rewire=True), "RRT_FLAG_REWIRE"), (dict(dubins=True), "a Dubins word is not reversible"), (dict(large_grid=True), "RRT_FLAG_LARGE_GRID")):
         bb = _ffi.Batch(gpu_ctx, 1, 100, **kw)
-        assert why in tg._refused(_ffi.RRT_E_UNSUPPORTED, lambda: bb.reroot(0, 0))
+        assert why in tc.refused_with_code(_ffi.RRT_E_UNSUPPORTED, lambda: bb.reroot(0, 0))
         bb.close()
     # an Informed query
     b = _ffi.Batch(gpu_ctx, 1, 300, logs=True)
@@ -354,14 +329,14 @@ def test_batch_refusals_change_nothing(gpu_ctx):
     b.launch()
     b.sync()
     ansi = b.connect_goals(0, goals)
-    assert "Informed" in tg._refused(_ffi.RRT_E_UNSUPPORTED, lambda: b.reroot(0, 0))
+    assert "Informed" in tc.refused_with_code(_ffi.RRT_E_UNSUPPORTED, lambda: b.reroot(0, 0))
     _stands(lambda g: b.connect_goals(0, g), goals, ansi)
     b.close()
 
 
 def test_plan_refusals_change_nothing():
-    c = tg._base()
-    w = tg._wall(c)
+    c = tc.base()
+    w = tc.wall(c)
     ctx = _ffi.Context(0)
     ctx.set_grid(c["og8"])
     n = c["n"]
@@ -373,7 +348,7 @@ def test_plan_refusals_change_nothing():
         return str(e.value)
 
     assert "no rrt_plan on this context yet" in refused(_ffi.RRT_E_ARG, 0)
-    goals = tg._goals(c["og8"])
+    goals = tc.mixed_goals(c["og8"])
     Cm = hostprep.rotation_to_world_frame(np.asarray(c["xs"], dtype=np.int64), np.asarray(c["xg"], dtype=np.int64))
     qi, keepi = _ffi.make_query(2, 300, c["xs"], c["xg"], c["samples"][:300], r2_rewire=c["r2"], goal_d2=0, Cmat=Cm)
     ctx.plan(qi, 300, logs=True)
@@ -407,22 +382,22 @@ def test_plan_refusals_change_nothing():
     # and the call itself, on the kept view, equals the restatement
     ctx.set_grid(w["og2"])
     ctx.keep_tree()
-    prev = tg._tree_of(res)
+    prev = tc.tree_of(res)
     alive = np.flatnonzero(w["alive"])
     r = int(alive[np.argmax(keepref.depth(prev[1], prev[3])[alive])])
     R, g = _restate(w["og2"], prev, True, r, NONE, c)
     rc, out, j0, old_id = ctx.reroot(r, NONE, n)
     assert j0 == len(R.ids) and np.array_equal(old_id, R.ids) and len(ctx.reroot_ms()) == 8
-    tg._same_result(out, g)
+    tc.same_result(out, g)
     ctx.close()
 
 
 # ------------------------------------------------------------------------------------------------ 7. the class
 def test_rrtstar_reroot_is_the_restatement_fed_with_the_same_draws():
-    c = tg._base()
+    c = tc.base()
     og = c["og8"].astype(np.int64)
-    N = tg.N
-    p = amd.RRTStar(og, N, tg.RR, pbar=False, seed=3)
+    N = tc.N
+    p = amd.RRTStar(og, N, tc.RR, pbar=False, seed=3)
     with pytest.raises(RuntimeError):
         p.reroot(3)
     T, gv = p.plan(c["xs"], c["xg"])
@@ -453,7 +428,7 @@ def test_rrtstar_reroot_is_the_restatement_fed_with_the_same_draws():
     assert gv2 == vg == g.vgoal and len(pts2) == g.rows and len(par2) == live
     assert np.array_equal(pts2[:live], g.pts[:live]) and np.array_equal(par2, g.parent[:live])
     assert np.array_equal(np.asarray(vc2[:live]).view(np.int64), g.vcost[:live].view(np.int64))
-    tg._class_goals_and_routes(p, c["og8"], g, tg._goals(c["og8"]))
+    tc.class_goals_and_routes(p, c["og8"], g, tc.mixed_goals(c["og8"]))
     # a further reroot and a grow on the re-rooted tree
     cur = (g.pts, g.parent, g.vcost, g.j)
     r2 = _deepest(cur)
@@ -465,9 +440,9 @@ def test_rrtstar_reroot_is_the_restatement_fed_with_the_same_draws():
 
 
 def test_the_classes_that_do_not_reroot():
-    c = tg._base()
+    c = tc.base()
     og = c["og8"].astype(np.int64)
-    for p in (amd.RRTStarInformed(og, tg.N, tg.RR, 10, pbar=False), amd.RRTStar(og, tg.N, tg.RR, pbar=False, rewire="correct")):
+    for p in (amd.RRTStarInformed(og, tc.N, tc.RR, 10, pbar=False), amd.RRTStar(og, tc.N, tc.RR, pbar=False, rewire="correct")):
         try:
             p.plan(c["xs"], c["xg"])
         except IndexError:  # (the plan's own goal not reached: the tree is resident all the same)

@@ -8,6 +8,7 @@ import pytest
 
 import oracle
 import orchelp
+from devcheck import check_rewired_tree
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pair
@@ -20,33 +21,6 @@ def _query(grid, n, seed, gseed=1):
     rng = np.random.default_rng(seed)
     samples = hostprep.draw_free_samples(rng, np.argwhere(og8 == 0), n)
     return og, og8, xs, xg, samples, rng
-
-
-def _check_tree(og8, r, xs):
-    """Every property a rewired tree must have: rooted and acyclic, costs exactly parent cost + edge length, every edge free
-    in the direction the rewire / choose-parent tested it (child-side endpoint last), costs non-decreasing along root paths."""
-    live = r.j + (1 if r.found else 0)
-    par = r.parent[:live].astype(np.int64)
-    pts = r.pts[:live].astype(np.int64)
-    assert par[0] == -1 and np.all(par[1:] >= 0) and np.all(par[1:] < r.j) and pts[0].tolist() == [int(xs[0]), int(xs[1])]
-    depth = np.zeros(live, dtype=np.int64)
-    order = np.argsort(r.vcost[:live], kind="stable")
-    hops = np.full(live, -1)
-    hops[0] = 0
-    for _ in range(live):  # relax until every vertex has its hop count: terminates iff the parent map is a tree
-        todo = hops < 0
-        if not todo.any():
-            break
-        ok = todo & (hops[np.where(par >= 0, par, 0)] >= 0)
-        assert ok.any(), "cycle or orphan in the parent map"
-        hops[ok] = hops[par[ok]] + 1
-    d = pts[1:] - pts[par[1:]]
-    dist = np.sqrt((d * d).sum(1).astype(np.float64))
-    assert np.array_equal(r.vcost[1:live], r.vcost[par[1:]] + dist), "a cost is not its parent's cost + the edge length"
-    assert np.all(r.vcost[1:live] >= r.vcost[par[1:]])
-    for c in range(1, live, max(1, live // 400)):
-        assert oracle.collisionfree(og8, pts[par[c]], pts[c])[0] or oracle.collisionfree(og8, pts[c], pts[par[c]])[0]
-    del depth, order
 
 
 @pytest.mark.parametrize("alg,rr,rg,grid,n", [(1, 24, None, 160, 1500), (1, 64, None, 512, 6000), (2, 32, 10, 200, 2500)])
@@ -64,7 +38,7 @@ def test_oracle_rewire_is_a_correct_rewire(alg, rr, rg, grid, n):
         st0, r0 = oracle.plan(og8, n, alg, xs, xg, samples, unitball=ub, ub_offset=r1.i_switch, **kw)
         st1, r1 = oracle.plan(og8, n, alg, xs, xg, samples, unitball=ub, ub_offset=r1.i_switch, rewire=True, **kw)
     assert st0 == 0 and st1 == 0 and r0.n_rewired == 0 and r1.n_rewired > 0 and r1.n_propagated > 0
-    _check_tree(og8, r1, xs)
+    check_rewired_tree(og8, r1, xs)
     if alg == 1:  # same sample stream, same acceptance: the vertex set is the reference's, only parents and costs differ
         assert r1.j == r0.j and np.array_equal(r1.pts[:r1.j], r0.pts[:r0.j])
         assert np.all(r1.vcost[:r1.j] <= r0.vcost[:r0.j] + 1e-9), "a rewire made some vertex more expensive"
@@ -132,7 +106,7 @@ def test_device_rewire_equals_the_oracle(gpu_ctx, alg, rr, rg, grid, n, seed):
     gpu_ctx.set_grid(og8)
     res, ro = _device_vs_oracle_rewire(gpu_ctx, og8, alg, n, rng, xs, xg, samples, rr, rg)
     assert res.n_rewired > 0
-    _check_tree(og8, res, xs)
+    check_rewired_tree(og8, res, xs)
 
 
 @pytest.mark.gpu

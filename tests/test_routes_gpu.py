@@ -14,30 +14,21 @@ import routeref
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.dubins import RRTStarDubins
-from test_connect_goals_gpu import _free_goals, _grow, _refused, _samples, _wall_map
+from treecalls import corridor_map, free_goals, free_samples, march, plan_on_own_batch, refused_with_word, same_routes, wall_map
 
 pytestmark = pytest.mark.gpu
 
 INF = np.inf
-NAMES = ("vertex", "cost", "length", "offsets", "xy", "ids")
-
-
-def _same(got, want):
-    for name, g, w in zip(NAMES, got, want):
-        assert g.dtype == w.dtype and g.shape == w.shape, (name, g.dtype, w.dtype, g.shape, w.shape)
-        assert np.array_equal(g, w), (name, np.flatnonzero(np.asarray(g != w).reshape(len(g), -1).any(axis=1))[:8])
-
-
 def _wall_goals(og):
     """about 200 free goals, one in the closed box, some on obstacle cells"""
-    return np.concatenate([_free_goals(og, 197, 31), [[30, 130]], np.argwhere(og != 0)[::400][:6]])
+    return np.concatenate([free_goals(og, 197, 31), [[30, 130]], np.argwhere(og != 0)[::400][:6]])
 
 
 @functools.lru_cache(maxsize=None)
 def _planned(kind):
     """(planner, T, og8, (points, parent, vcosts, j), goals, reference raw, reference shortcut): one plan() and one pair of
     reference results per planner class, shared by the tests and left unchanged"""
-    og = _wall_map()
+    og = wall_map()
     p = {"std": lambda: amd.RRTStandard(og, 2000, pbar=False, seed=1), "star": lambda: amd.RRTStar(og, 2000, 30, pbar=False, seed=1),
          "informed": lambda: amd.RRTStarInformed(og, 2000, 30, 25, pbar=False, seed=1)}[kind]()
     T, gv = p.plan(np.array((5, 5)), np.array((190, 150)))
@@ -55,7 +46,7 @@ def _planned(kind):
 def test_raw_routes_on_the_planners(kind):
     p, T, og8, (points, parent, vcosts, j), goals, want, _ = _planned(kind)
     got = p.device_context().routes(goals)
-    _same(got, want)
+    same_routes(got, want)
     vertex, cost, length, offsets, xy, ids = got
     cv, cc = p.connect_goals(goals)
     assert np.array_equal(vertex, cv) and np.array_equal(cost, cc)
@@ -89,7 +80,7 @@ def test_shortcut_routes_on_the_planners(kind):
     assert shorter.sum() >= 100 and same.sum() >= 30
     assert np.all(want[2][shorter] < raw[2][shorter]) and np.array_equal(want[2][same], raw[2][same])
     got = p.device_context().routes(goals, shortcut=True)
-    _same(got, want)
+    same_routes(got, want)
     vertex, cost, length, offsets, xy, ids = got
     assert np.array_equal(vertex, raw[0]) and np.array_equal(cost, raw[1])
     assert np.all(length[ok] <= cost[ok] * (1 + 1e-9)) and np.all(length[~ok] == INF)
@@ -111,42 +102,10 @@ def test_shortcut_routes_on_the_planners(kind):
 
 
 # ------------------------------------------------------------------------------------------------ 3. long routes
-def _corridor_map(W=200, H=160):
-    """three corridors along x, joined at alternating ends, each a slalom round pillars that stand alternately on its lower and its
-    upper wall; and the way through them"""
-    og = np.zeros((W, H), dtype=np.int64)
-    og[0:185, 38:42] = 1   # between corridors 1 and 2, open at the right end
-    og[15:200, 78:82] = 1  # between corridors 2 and 3, open at the left end
-    way = [(5, 20)]
-    for c, (y0, xs) in enumerate([(0, range(20, 180, 20)), (42, range(180, 20, -20)), (82, range(20, 180, 20))]):
-        for i, x in enumerate(xs):
-            if i % 2 == 0:
-                og[x, y0:y0 + 24] = 1
-                way.append((x, y0 + 30))
-            else:
-                og[x, y0 + 14:y0 + 38] = 1
-                way.append((x, y0 + 8))
-        way.append((192, y0 + 20) if c % 2 == 0 else (8, y0 + 20))
-        if c < 2:
-            way.append((192, y0 + 60) if c % 2 == 0 else (8, y0 + 60))
-    return og, way
-
-
-def _march(way, step=3):
-    """samples along the polyline `way` in steps of at most `step` cells a coordinate: each one's nearest vertex is (almost always) the
-    one before it, which chains the tree"""
-    out, p = [], np.array(way[0])
-    for w in way[1:]:
-        while np.any(p != np.array(w)):
-            p = p + np.clip(np.array(w) - p, -step, step)
-            out.append(p.tolist())
-    return np.array(out)
-
-
 def test_routes_longer_than_a_workgroup_has_waves_and_a_wave_has_lanes(gpu_ctx):
-    og, way = _corridor_map()
+    og, way = corridor_map()
     og8 = oracle.og_u8(og)
-    samples = _march(way)
+    samples = march(way)
     n = len(samples)
     goals = np.array([(190, 150), (100, 150), (30, 100), (110, 45), (190, 60), (70, 20), (5, 21), (0, 159)])
     st, ro = oracle.plan(og8, n, 0, way[0], (190, 150), samples, logs=False)
@@ -163,11 +122,11 @@ def test_routes_longer_than_a_workgroup_has_waves_and_a_wave_has_lanes(gpu_ctx):
         beyond += sum(1 for b in at[1:] if rows[g] - 1 - b >= 16)
     assert beyond >= 20
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 0, n, way[0], (190, 150), samples)
+    b, res = plan_on_own_batch(gpu_ctx, 0, n, way[0], (190, 150), samples)
     assert res.j == ro.j and np.array_equal(res.parent[:res.j], ro.parent[:ro.j]) and np.array_equal(res.pts[:res.j], ro.pts[:ro.j])
-    _same(b.routes(0, goals), raw)
-    _same(b.routes(0, goals, shortcut=True), want)
-    _same(b.routes(0, goals), raw)  # (the shortcut pass rewrote its rows in place: the next call fills them again)
+    same_routes(b.routes(0, goals), raw)
+    same_routes(b.routes(0, goals, shortcut=True), want)
+    same_routes(b.routes(0, goals), raw)  # (the shortcut pass rewrote its rows in place: the next call fills them again)
     b.close()
 
 
@@ -181,7 +140,7 @@ def test_the_largest_visible_row_wins_not_the_first_run_of_visible_ones(gpu_ctx)
     gpu_ctx.set_grid(og8)
     st, ro = oracle.plan(og8, 4, 0, s, (199, 159), samples, logs=False)
     assert ro.j == 4 and ro.parent[:4].tolist() == [-1, 0, 1, 2]
-    b, res = _grow(gpu_ctx, 0, 4, s, (199, 159), samples)
+    b, res = plan_on_own_batch(gpu_ctx, 0, 4, s, (199, 159), samples)
     assert res.parent[:4].tolist() == [-1, 0, 1, 2] and res.pts[:4].tolist() == [list(s), list(A), list(B), list(C)]
     raw = b.routes(0, [g])
     assert res.j == 4 and raw[0].tolist() == [3]
@@ -190,36 +149,36 @@ def test_the_largest_visible_row_wins_not_the_first_run_of_visible_ones(gpu_ctx)
     assert cut[0].tolist() == [3] and cut[1][0] == raw[1][0]
     assert cut[4].tolist() == [list(s), list(C), list(g)] and cut[5].tolist() == [0, 3, -1] and cut[3].tolist() == [0, 3]
     assert cut[2][0] == float(np.sqrt(np.float64(105 * 105 + 20 * 20)) + np.sqrt(np.float64(2500))) < raw[2][0]
-    _same(cut, routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, [g], cut=True))
+    same_routes(cut, routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, [g], cut=True))
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 5. bookkeeping
 def test_more_goals_than_workgroups(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 1, 600, (5, 5), (190, 150), _samples(og, 600, 4), r2=hostprep.radius_threshold(30))
-    goals = np.concatenate([_free_goals(og, 1480, 5), np.argwhere(og != 0)[::45][:20]])
+    b, res = plan_on_own_batch(gpu_ctx, 1, 600, (5, 5), (190, 150), free_samples(og, 600, 4), r2=hostprep.radius_threshold(30))
+    goals = np.concatenate([free_goals(og, 1480, 5), np.argwhere(og != 0)[::45][:20]])
     assert len(goals) == 1500
     for cut in (False, True):
         want = routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals, cut=cut)
-        _same(b.routes(0, goals, shortcut=cut), want)
+        same_routes(b.routes(0, goals, shortcut=cut), want)
         # the first m goals, m around one pass of the scan of the row counts (1024 values): a goal's route does not depend on the
         # other goals, so the reference is the front of the one above
         vertex, cost, length, offsets, xy, ids = want
         for m in (1023, 1024, 1025):
             rows = offsets[m]
             assert vertex[m - 1] >= 0 and rows > offsets[m - 1]  # (the goal at the edge has rows)
-            _same(b.routes(0, goals[:m], shortcut=cut), (vertex[:m], cost[:m], length[:m], offsets[:m + 1], xy[:rows], ids[:rows]))
+            same_routes(b.routes(0, goals[:m], shortcut=cut), (vertex[:m], cost[:m], length[:m], offsets[:m + 1], xy[:rows], ids[:rows]))
     b.close()
 
 
 def test_no_goals_and_one_goal(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 0, 300, (5, 5), (190, 150), _samples(og, 300, 4))
+    b, res = plan_on_own_batch(gpu_ctx, 0, 300, (5, 5), (190, 150), free_samples(og, 300, 4))
     for cut in (False, True):
         vertex, cost, length, offsets, xy, ids = b.routes(0, np.zeros((0, 2), dtype=np.int64), shortcut=cut)
         assert vertex.shape == cost.shape == length.shape == ids.shape == (0,) and offsets.tolist() == [0] and xy.shape == (0, 2)
@@ -233,49 +192,49 @@ def test_no_goals_and_one_goal(gpu_ctx):
 
 
 def test_a_batch_of_three_queries(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
     ns = [300, 1500, 800]
     b = _ffi.Batch(gpu_ctx, 3, max(ns))
     keeps = []
     for q, n in enumerate(ns):
-        qu, keep = _ffi.make_query(1, n, (5 + q, 5), (190, 150 - q), _samples(og, n, 10 + q), r2_rewire=hostprep.radius_threshold(25))
+        qu, keep = _ffi.make_query(1, n, (5 + q, 5), (190, 150 - q), free_samples(og, n, 10 + q), r2_rewire=hostprep.radius_threshold(25))
         keeps.append(keep)
         b.set_query(q, qu)
     b.launch()
     b.sync()
-    goals = _free_goals(og, 60, 13)
+    goals = free_goals(og, 60, 13)
     res = b.get_result(1)
     assert res.pts[0].tolist() == [6, 5]
     for cut in (False, True):
-        _same(b.routes(1, goals, shortcut=cut), routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals, cut=cut))
+        same_routes(b.routes(1, goals, shortcut=cut), routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals, cut=cut))
     b.close()
 
 
 def test_large_grid_batch_on_a_small_grid():
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     ctx = _ffi.Context(0)
     ctx.set_grid(og8)
-    b, res = _grow(ctx, 1, 1500, (5, 5), (190, 150), _samples(og, 1500, 14), r2=hostprep.radius_threshold(30), large_grid=True)
+    b, res = plan_on_own_batch(ctx, 1, 1500, (5, 5), (190, 150), free_samples(og, 1500, 14), r2=hostprep.radius_threshold(30), large_grid=True)
     assert b.kernel_name() == "rrt_pipe_large_kernel" and res.j > 500
-    goals = np.concatenate([_free_goals(og, 80, 22), [[30, 130]]])
+    goals = np.concatenate([free_goals(og, 80, 22), [[30, 130]]])
     raw, want = [routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals, cut=cut) for cut in (False, True)]
     assert (np.diff(want[3]) < np.diff(raw[3])).sum() >= 20
-    _same(b.routes(0, goals), raw)
-    _same(b.routes(0, goals, shortcut=True), want)
+    same_routes(b.routes(0, goals), raw)
+    same_routes(b.routes(0, goals, shortcut=True), want)
     b.close()
     ctx.close()
 
 
 def test_connect_goals_is_what_it_was_and_rows_go_with_their_call(gpu_ctx):
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
-    b, res = _grow(gpu_ctx, 1, 1000, (5, 5), (190, 150), _samples(og, 1000, 15), r2=hostprep.radius_threshold(25))
-    goals = _free_goals(og, 300, 16)
-    _refused(_ffi.RRT_E_ARG, "no routes", b.routes_rows, 0)
+    b, res = plan_on_own_batch(gpu_ctx, 1, 1000, (5, 5), (190, 150), free_samples(og, 1000, 15), r2=hostprep.radius_threshold(25))
+    goals = free_goals(og, 300, 16)
+    refused_with_word(_ffi.RRT_E_ARG, "no routes", b.routes_rows, 0)
     before = b.connect_goals(0, goals)
     got = b.routes(0, goals, shortcut=True)
     after = b.connect_goals(0, goals[:40])  # (fewer goals: the routes' rows stay those of the 300)
@@ -284,19 +243,19 @@ def test_connect_goals_is_what_it_was_and_rows_go_with_their_call(gpu_ctx):
     rows = int(got[3][-1])
     xy, ids = b.routes_rows(rows)
     assert np.array_equal(xy, got[4]) and np.array_equal(ids, got[5])
-    _refused(_ffi.RRT_E_ARG, "rows=", b.routes_rows, rows - 1)
-    _refused(_ffi.RRT_E_ARG, "rows=", b.routes_rows, rows + 1)
+    refused_with_word(_ffi.RRT_E_ARG, "rows=", b.routes_rows, rows - 1)
+    refused_with_word(_ffi.RRT_E_ARG, "rows=", b.routes_rows, rows + 1)
     b.rearm()
-    _refused(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
-    _refused(_ffi.RRT_E_ARG, "not finished", b.routes, 0, goals)
+    refused_with_word(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.routes, 0, goals)
     b.launch()
-    _refused(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
+    refused_with_word(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
     b.sync()
-    _refused(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
-    _same(b.routes(0, goals, shortcut=True), got)
+    refused_with_word(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
+    same_routes(b.routes(0, goals, shortcut=True), got)
     # a call that is refused leaves no rows behind either
-    _refused(_ffi.RRT_E_ARG, "outside", b.routes, 0, [(200, 5)])
-    _refused(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.routes, 0, [(200, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "no routes", b.routes_rows, rows)
     b.close()
 
 
@@ -304,15 +263,15 @@ def test_connect_goals_is_what_it_was_and_rows_go_with_their_call(gpu_ctx):
 def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx, cut):
     """scratch that was allocated for a large call serves a small one: 257 goals, the goal with the longest route tiled, then that
     goal alone and three different goals, their rows read back through routes_rows"""
-    og = _wall_map()
+    og = wall_map()
     og8 = oracle.og_u8(og)
     gpu_ctx.set_grid(og8)
 
     def run():
-        return _grow(gpu_ctx, 1, 1000, (5, 5), (190, 150), _samples(og, 1000, 15), r2=hostprep.radius_threshold(25))
+        return plan_on_own_batch(gpu_ctx, 1, 1000, (5, 5), (190, 150), free_samples(og, 1000, 15), r2=hostprep.radius_threshold(25))
 
     b, res = run()
-    goals = _free_goals(og, 60, 16)
+    goals = free_goals(og, 60, 16)
     want = routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals, cut=cut)
     by_rows = np.argsort(-np.diff(want[3]), kind="stable")
     g = int(by_rows[0])
@@ -326,34 +285,34 @@ def test_small_calls_after_a_large_one_on_the_same_batch(gpu_ctx, cut):
         xy, ids = b.routes_rows(int(got[3][-1]))
         assert np.array_equal(xy, got[4]) and np.array_equal(ids, got[5])
         got = got[:4] + (xy, ids)
-        _same(got, routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals[sel], cut=cut))
+        same_routes(got, routeref.routes(og8, res.pts, res.vcost, res.parent, res.j, goals[sel], cut=cut))
         f, _ = run()  # a batch that made no call before this one
-        _same(got, f.routes(0, goals[sel], shortcut=cut))
+        same_routes(got, f.routes(0, goals[sel], shortcut=cut))
         f.close()
     b.close()
 
 
 def test_refusals():
     ctx = _ffi.Context(0)
-    og = _wall_map()
+    og = wall_map()
     ctx.set_grid(oracle.og_u8(og))
     L = _ffi.lib()
-    _refused(_ffi.RRT_E_ARG, "no rrt_plan", ctx.routes, [(5, 5)])
-    samples = _samples(og, 500, 17)
+    refused_with_word(_ffi.RRT_E_ARG, "no rrt_plan", ctx.routes, [(5, 5)])
+    samples = free_samples(og, 500, 17)
     b = _ffi.Batch(ctx, 2, 500)
-    _refused(_ffi.RRT_E_ARG, "no query set", b.routes, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.routes, 0, [(5, 5)])
     q, keep = _ffi.make_query(1, 500, (5, 5), (190, 150), samples, r2_rewire=900)
     b.set_query(0, q)
-    _refused(_ffi.RRT_E_ARG, "not launched", b.routes, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "not launched", b.routes, 0, [(5, 5)])
     b.launch()
     b.sync()
     want = b.routes(0, [(150, 150)], shortcut=True)
-    _refused(_ffi.RRT_E_ARG, "q=2", b.routes, 2, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "q=-1", b.routes, -1, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "no query set", b.routes, 1, [(5, 5)])
-    _refused(_ffi.RRT_E_ARG, "outside", b.routes, 0, [(5, 5), (200, 5)])
-    _refused(_ffi.RRT_E_ARG, "outside", b.routes, 0, [(5, -1)])
-    _refused(_ffi.RRT_E_ARG, "at most", b.routes, 0, np.zeros(((1 << 20) + 1, 2), dtype=np.int32))
+    refused_with_word(_ffi.RRT_E_ARG, "q=2", b.routes, 2, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "q=-1", b.routes, -1, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "no query set", b.routes, 1, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.routes, 0, [(5, 5), (200, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "outside", b.routes, 0, [(5, -1)])
+    refused_with_word(_ffi.RRT_E_ARG, "at most", b.routes, 0, np.zeros(((1 << 20) + 1, 2), dtype=np.int32))
     # the C calls themselves: NULL arguments, an unknown flag
     g = np.array([[150, 150]], dtype=np.int32)
     v, c, ln, off = np.zeros(1, np.int32), np.zeros(1), np.zeros(1), np.zeros(2, np.int64)
@@ -367,18 +326,18 @@ def test_refusals():
     assert L.rrt_batch_routes(b._h, 0, *args) == _ffi.RRT_OK and off.tolist() == [0, int(np.diff(b.routes(0, [(150, 150)])[3])[0])]
     assert L.rrt_batch_routes_rows(b._h, None, None, int(off[1])) == _ffi.RRT_E_ARG
     b.rearm()
-    _refused(_ffi.RRT_E_ARG, "not finished", b.routes, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "not finished", b.routes, 0, [(5, 5)])
     b.launch()
     b.sync()
     # the grid replaced between run and call: same shape, another generation
     ctx.set_grid(oracle.og_u8(og))
-    _refused(_ffi.RRT_E_ARG, "replaced", b.routes, 0, [(150, 150)])
+    refused_with_word(_ffi.RRT_E_ARG, "replaced", b.routes, 0, [(150, 150)])
     b.rearm()
     b.launch()
     b.sync()
-    _same(b.routes(0, [(150, 150)], shortcut=True), want)
+    same_routes(b.routes(0, [(150, 150)], shortcut=True), want)
     ctx.set_grid(np.zeros((64, 64), dtype=np.uint8))
-    _refused(_ffi.RRT_E_ARG, "shape", b.routes, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "shape", b.routes, 0, [(5, 5)])
     b.close()
     # an Informed query that reached the goal region waits for its unit ball
     b = _ffi.Batch(ctx, 1, 300)
@@ -389,7 +348,7 @@ def test_refusals():
     b.launch()
     b.sync()
     assert b.get_result(0).status == _ffi.RRT_NEED_UNITBALL
-    _refused(_ffi.RRT_E_ARG, "unit-ball", b.routes, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_ARG, "unit-ball", b.routes, 0, [(5, 5)])
     b.close()
     # a Dubins batch
     hd = np.random.default_rng(19).integers(0, 16, size=300)
@@ -398,7 +357,7 @@ def test_refusals():
     b.set_query(0, q)
     b.launch()
     b.sync()
-    _refused(_ffi.RRT_E_UNSUPPORTED, "Dubins", b.routes, 0, [(5, 5)])
+    refused_with_word(_ffi.RRT_E_UNSUPPORTED, "Dubins", b.routes, 0, [(5, 5)])
     b.close()
     ctx.close()
     with pytest.raises(ValueError, match="Dubins"):
@@ -407,7 +366,7 @@ def test_refusals():
 
 def test_the_planner_keeps_its_state_rules():
     p, T, og8, tree, goals, raw, want = _planned("std")
-    q = amd.RRTStandard(_wall_map(), 500, pbar=False, seed=3)
+    q = amd.RRTStandard(wall_map(), 500, pbar=False, seed=3)
     with pytest.raises(RuntimeError, match="plan"):
         q.routes_to(goals)
     q.plan(np.array((5, 5)), np.array((190, 150)))

@@ -12,16 +12,13 @@ import pytest
 import growref
 import oracle
 import treemodel as tm
+from orchelp import bits
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd import rrt as amd
 from rrtplanner_amd.oggen import DeviceGrids
-from test_grow_gpu import SHAPES
+from treecalls import SHAPES, tree_of
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.int64)
 
 
 def _call(f):
@@ -44,7 +41,7 @@ def _answered(got, want):
 def _same_tree(res, t, logs=True):
     assert (res.status, res.j, res.found, res.vgoal, res.rows) == (t.status, t.j, t.found, t.vgoal, t.rows)
     assert np.array_equal(res.pts[:t.live], t.pts[:t.live]) and np.array_equal(res.parent[:t.live], t.parent[:t.live])
-    assert np.array_equal(_bits(res.vcost[:t.live]), _bits(t.vcost[:t.live]))
+    assert np.array_equal(bits(res.vcost[:t.live]), bits(t.vcost[:t.live]))
     assert res.sum_j == t.sum_j and res.sum_near == t.sum_near  # the statistics of the last run: a grow counts its own iterations alone
     if logs and t.log0 is not None:
         lo, hi = t.log0, t.log0 + len(t.accept_log)
@@ -53,13 +50,13 @@ def _same_tree(res, t, logs=True):
 
 
 def _same_goals(got, want):
-    assert np.array_equal(got[0], want[0]) and np.array_equal(_bits(got[1]), _bits(want[1]))
+    assert np.array_equal(got[0], want[0]) and np.array_equal(bits(got[1]), bits(want[1]))
 
 
 def _same_routes(got, want):
     assert len(got) == len(want) == 6
     for k, (x, y) in enumerate(zip(got, want)):
-        assert np.array_equal(_bits(x), _bits(y)) if k in (1, 2) else np.array_equal(x, y), k
+        assert np.array_equal(bits(x), bits(y)) if k in (1, 2) else np.array_equal(x, y), k
 
 
 class BatchDriver:
@@ -252,7 +249,7 @@ class PlannerDriver:
         vg, pts, par, vc = T.__dict__["_lazy"]
         assert gv == vg == t.vgoal and len(pts) == t.rows and len(par) == t.live
         assert np.array_equal(pts[:t.live], t.pts[:t.live]) and np.array_equal(par, t.parent[:t.live])
-        assert np.array_equal(_bits(np.asarray(vc[:t.live])), _bits(t.vcost[:t.live]))
+        assert np.array_equal(bits(np.asarray(vc[:t.live])), bits(t.vcost[:t.live]))
 
     def _run(self, call, t):
         """plan() and grow() raise IndexError where the reference does (no vertex sees the goal and rows are left); the tree is there all the same"""
@@ -264,7 +261,7 @@ class PlannerDriver:
         st = self.p.last_stats
         assert (st["j"], st["sum_j"], st["sum_near"]) == (t.j, t.sum_j, t.sum_near) and self.p.last_route == "kernel" and self.p._tree_resident == "device"
 
-    def _refused(self, call, want):
+    def _refused_by_class(self, call, want):
         with pytest.raises((ValueError, RuntimeError)) as e:
             call()
         if want.word in ("room for", "nothing to grow from"):
@@ -289,21 +286,21 @@ class PlannerDriver:
             assert got.dtype == bool and np.array_equal(got, want)
         elif kind == "grow1":
             if isinstance(want, tm.Refusal):
-                self._refused(lambda: self.p.grow(len(op[1])), want)
+                self._refused_by_class(lambda: self.p.grow(len(op[1])), want)
             else:
                 self._run(lambda: self.p.grow(len(op[1])), want["tree"])
                 assert np.array_equal(self.p.last_grow_ids, want["old_id"])
         elif kind == "goals1":
             if isinstance(want, tm.Refusal):
-                self._refused(lambda: self.p.connect_goals(op[1]), want)
+                self._refused_by_class(lambda: self.p.connect_goals(op[1]), want)
             else:
                 _same_goals(self.p.connect_goals(op[1]), want)
         elif kind == "routes1":
             if isinstance(want, tm.Refusal):
-                self._refused(lambda: self.p.routes_to(op[1], shortcut=op[2]), want)
+                self._refused_by_class(lambda: self.p.routes_to(op[1], shortcut=op[2]), want)
             else:
                 routes, length = self.p.routes_to(op[1], shortcut=op[2])
-                assert np.array_equal(_bits(length), _bits(want[2])) and len(routes) == len(op[1])
+                assert np.array_equal(bits(length), bits(want[2])) and len(routes) == len(op[1])
                 for k, r in enumerate(routes):
                     lo, hi = want[3][k], want[3][k + 1]
                     assert (r is None and lo == hi) or np.array_equal(r, want[4][lo:hi]), k
@@ -313,7 +310,7 @@ class PlannerDriver:
     def everyone(self, after, probe):
         want = after[0][0][1]
         if isinstance(want, tm.Refusal):
-            self._refused(lambda: self.p.connect_goals(probe), want)
+            self._refused_by_class(lambda: self.p.connect_goals(probe), want)
         else:
             _same_goals(self.p.connect_goals(probe), want)
         assert self.p.rand_gen.bit_generator.state == self.draws_state, "the planner's stream is not where the sequence's draws stand"
@@ -333,15 +330,11 @@ def test_a_sequence_on_the_planner_classes(seed):
 
 
 # ------------------------------------------------------------------------------------------------ 5. armed on one map, launched on another
-def _tree_of(res):
-    return np.array(res.pts, dtype=np.int64), np.array(res.parent, dtype=np.int64), np.array(res.vcost), res.j
-
-
 def _grown(n, g, j0):
     return tm.Tree(n, g.pts, g.parent, g.vcost, g.j, g.found, g.vgoal, g.status, g.sum_j, g.sum_near, j0, g.nearest_log, g.accept_log, g.jlog)
 
 
-def _refused(call, word=""):
+def _refused_arg(call, word=""):
     with pytest.raises(_ffi.RRTError) as e:
         call()
     assert e.value.code == _ffi.RRT_E_ARG and word in str(e.value), e.value
@@ -371,12 +364,12 @@ def test_a_grow_armed_on_one_map_is_not_launched_on_another(gpu_ctx, shape):
     j0, old_id, log0 = b.grow(0, more)
     assert j0 == alive.sum() and np.array_equal(old_id, np.flatnonzero(alive))
     gpu_ctx.set_grid(maps[tm.MAP_B])  # same shape, other obstacles across the seed
-    msg = _refused(b.launch, "seeded")
+    msg = _refused_arg(b.launch, "seeded")
     assert "query 0" in msg and f"generation {gen_seed} then, {gpu_ctx.grid_generation()} now" in msg
     for call in (lambda: b.get_result(0), lambda: b.connect_goals(0, [(5, 5)]), lambda: b.grow(0, more), lambda: b.keep_tree(0)):
-        _refused(call)  # query 0 is armed and not launched, as it was
+        _refused_arg(call)  # query 0 is armed and not launched, as it was
     gpu_ctx.set_grid(maps[tm.MAP_WALL])  # the same cells, a new generation
-    _refused(b.launch, "seeded")
+    _refused_arg(b.launch, "seeded")
     b.rearm()
     b.launch()
     b.sync()
@@ -410,15 +403,15 @@ def test_a_grow_armed_on_a_resident_frame_runs_when_that_frame_is_back(gpu_ctx):
     r0 = b.get_result(0)
     more = hostprep.draw_free_samples(rng, np.argwhere(og[0] == 0), min(50, n - r0.j))
     assert len(more) >= 10
-    ids, sp, sc, spar = growref.seed(*_tree_of(r0))
+    ids, sp, sc, spar = growref.seed(*tree_of(r0))
     want = growref.grow(og[0], 1, n, xg, tm.R2, sp, sc, spar, more)
     goals = free[rng.integers(0, len(free), size=16)]
     assert b.keep_tree(1).all()
     j0, old_id, log0 = b.grow(0, more)
     ans1 = b.routes(1, goals)
     grids.select(1)
-    _refused(b.launch, "seeded")
-    _refused(lambda: b.connect_goals(1, goals), "replaced")
+    _refused_arg(b.launch, "seeded")
+    _refused_arg(lambda: b.connect_goals(1, goals), "replaced")
     grids.select(0)
     _same_goals(b.connect_goals(1, goals), ans1[:2])  # (after a launch query 1 would be refused: it lost its view)
     xy, ids1 = b.routes_rows(len(ans1[5]))
@@ -428,5 +421,5 @@ def test_a_grow_armed_on_a_resident_frame_runs_when_that_frame_is_back(gpu_ctx):
     res = b.get_result(0)
     _same_tree(res, _grown(n, want, j0))
     assert res.j > r0.j and b.team_info()["timeouts"] == 0
-    _refused(lambda: b.connect_goals(1, goals), "replaced")  # the launch that ran dropped the view
+    _refused_arg(lambda: b.connect_goals(1, goals), "replaced")  # the launch that ran dropped the view
     b.close()

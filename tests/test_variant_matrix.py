@@ -56,7 +56,7 @@ def _workload(tag):
 
 def _query(spec):
     """One query and the oracle's run of it (an Informed one through the unit-ball hand-over), once per process: the dict that
-    test_record_slabs._fill and _hand_over take"""
+    slabs.fill_batch and slabs.hand_over_unitballs take"""
     if spec not in _queries:
         tag, alg, n = spec
         w = WORKLOADS[tag]
@@ -244,22 +244,18 @@ def _check_launch(b, row, tag):
 
 
 def _compare_plain(b, qs, tag):
-    from test_record_slabs import _same_as_oracle
-
     for q, d in enumerate(qs):
         if d["alg"] != 2:
-            _same_as_oracle(b.get_result(q), d["st"], d["ro"], tag + (q,))
+            slabs.same_as_oracle(b.get_result(q), d["st"], d["ro"], tag + (q,))
 
 
 def _run_batch(ctx, row, rec, batch):
-    from test_record_slabs import _fill, _hand_over, _same_as_oracle
-
     qs = [_query(spec) for spec in batch]
     for d in qs:
         _check_workload(d)
     ctx.set_grid(qs[0]["og8"])
     b = _ffi.Batch(ctx, len(qs), max(d["n"] for d in qs), logs=True, **rec.batch)
-    keep = _fill(b, qs)
+    keep = slabs.fill_batch(b, qs)
     for rep in range(2):  # the second time on the same buffers, after a rearm
         tag = (variants.kernel_name(row), tuple(batch), rep)
         b.launch()
@@ -267,11 +263,11 @@ def _run_batch(ctx, row, rec, batch):
         _check_launch(b, row, tag)
         _compare_plain(b, qs, tag)
         if rec.informed:
-            assert _hand_over(b, qs, tag) == 1, tag
+            assert slabs.hand_over_unitballs(b, qs, tag) == 1, tag
             _check_launch(b, row, tag + ("resumed",))
             for q, d in enumerate(qs):
                 if d["alg"] == 2:
-                    _same_as_oracle(b.get_result(q), d["st"], d["ro"], tag + (q,))
+                    slabs.same_as_oracle(b.get_result(q), d["st"], d["ro"], tag + (q,))
             _compare_plain(b, qs, tag + ("untouched by the second launch",))
         b.rearm()
     ms = b.elapsed_ms()

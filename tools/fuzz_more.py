@@ -9,7 +9,7 @@ import numpy as np
 import oracle
 from rrtplanner_amd import _ffi
 from rrtplanner_amd.oggen import perlin_occupancygrid
-import test_gpu_parity as T
+from devcheck import oracle_vs_device
 
 seeds = [int(x) for x in sys.argv[1:]] or [1, 2, 3]
 ctx = _ffi.Context(0)
@@ -33,7 +33,7 @@ for seed in seeds:
             xg = free[rng.integers(0, free.shape[0])]
             ctx.set_grid(og8)
             try:
-                T._oracle_vs_device(ctx, og8, alg, n, case, xs, xg, rr if alg else None, None, kernel=kernel)
+                oracle_vs_device(ctx, og8, alg, n, case, xs, xg, rr if alg else None, None, kernel=kernel)
             except AssertionError as e:
                 print(f"MISMATCH seed {seed} kernel {kernel} case {case}: grid {w}x{h} dens {dens} alg {alg} n {n} r {rr} xs {xs} xg {xg}")
                 raise
