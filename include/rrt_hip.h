@@ -36,6 +36,7 @@ extern "C" {
                                       expansion kernels' packed keys; such a planner runs host-driven over rrt_tree_query instead, slower, same results);
                                       RRT_FLAG_LARGE_GRID with a planner or flag it does not take; rrt_set_grid: more than 32767 cells per axis */
 #define RRT_E_COMM (-6)            /* multi-GPU gather: librccl missing, no communicator, RCCL error, unequal slabs */
+#define RRT_E_INTERNAL (-7)        /* rrt_batch_relax: an iteration went past the bound that its own reasoning sets */
 
 #define RRT_ALG_STANDARD 0 /* RRTStandard.plan     rrt.py:386 */
 #define RRT_ALG_STAR 1     /* RRTStar.plan         rrt.py:466 */
@@ -402,6 +403,32 @@ int rrt_batch_reroot(rrt_batch *b, int32_t q, int32_t root, const int32_t *sampl
  * test, ms[2] alive and depth (pointer jumping), ms[3] the order, ms[4] the costs, then ms[5 .. 7] the seed's stages as
  * rrt_batch_grow_ms reports them; the first `count` (1 .. 8) are written.  RRT_E_ARG when there is none, or after a later rrt_batch_grow. */
 int rrt_batch_reroot_ms(rrt_batch *b, float *ms, int32_t count);
+/* Relax the finished tree of query q to the shortest-path tree from its root over the graph of its own vertices, then rrt_batch_grow
+ * from it (rrt_relax.h): the vertices stay and every parent is chosen again -- the limit the rewire of RRT* approaches.  RRTStandard
+ * and RRTStar, the default cost.
+ *   input    the whole tree [0, j), or with a view (rrt_batch_keep_tree) its alive vertices.
+ *   edges    E(v), v != 0: every u != v with d2(u, v) < r2 (integer d2; r2 as rrt_query.r2_rewire is formed) whose line u -> v is free
+ *            on the context's CURRENT grid -- the walk is not symmetric and runs from the parent to the child --, and the old parent
+ *            of v, which is not walked again (it stands tested on this grid) and may be longer than the radius.  No vertex is cut.
+ *   costs    cost[0] = 0, cost[v] = min over u in E(v) of cost[u] + sqrt((double)d2(u, v)) in f64: the unique fixpoint, what Dijkstra
+ *            from the root gives with these sums.
+ *   parents  chosen over the final costs: the u in E(v) with cost[u] + d == cost[v] and (cost[u], u) < (cost[v], v), the smallest
+ *            (cost[u], u) of them.
+ *   then     the numbering of rrt_batch_reroot, by (depth, previous number), old_id as there, the costs summed from the root down
+ *            (they must equal the fixpoint bit for bit: RRT_E_HIP otherwise), and rrt_batch_grow's seed, arming and launch with
+ *            the m samples.  The query's start stays.  m == 0: the plain relaxation, then go2goal.
+ * Refusals: all of rrt_batch_grow's in its order (a batch created with RRT_FLAG_DUBINS: the cost of a word depends on the headings
+ * at its ends), then RRT_E_ARG for r2 <= 0.  A refusal changes nothing; a call that fails later leaves the query without a tree.
+ * RRT_E_INTERNAL: the costs still fell after j rounds, which no shortest path needs. */
+int rrt_batch_relax(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
+/* time in ms on the stream of the stages of the last successful rrt_batch_relax on this batch: ms[0] the buckets, ms[1] the rounds (the
+ * host's read of every round's count of changes included), ms[2] the parents, ms[3] alive and depth, ms[4] the order, ms[5] the costs,
+ * then ms[6 .. 8] the seed's stages as rrt_batch_grow_ms reports them; the first `count` (1 .. 9) are written.  RRT_E_ARG when there is
+ * none, or after a later rrt_batch_grow or rrt_batch_reroot. */
+int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count);
+/* of the same call: out[0] rounds run (the last one changed nothing), out[1] vertices whose cost fell, out[2] lines of sight walked,
+ * out[3] candidate pairs priced (the last two depend on the order in which the rounds' wavefronts ran) */
+int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -479,6 +506,11 @@ int rrt_plan_grow_poses(rrt_ctx *ctx, const int32_t *samples_xyh, int32_t m, int
  * rrt_plan_grow.  rrt_plan_reroot_ms: rrt_batch_reroot_ms of that batch. */
 int rrt_plan_reroot(rrt_ctx *ctx, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
 int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count);
+/* rrt_batch_relax on the tree of the context's last rrt_plan / rrt_plan_resume, launch, sync and result included: returns like
+ * rrt_plan_grow.  rrt_plan_relax_ms, rrt_plan_relax_stats: rrt_batch_relax_ms and rrt_batch_relax_stats of that batch. */
+int rrt_plan_relax(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
+int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count);
+int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

@@ -21,6 +21,7 @@ RRT_E_HIP = -3
 RRT_E_NOGRID = -4
 RRT_E_UNSUPPORTED = -5
 RRT_E_COMM = -6
+RRT_E_INTERNAL = -7
 
 ALG_STANDARD, ALG_STAR, ALG_INFORMED = 0, 1, 2
 ALG_DUBINS, ALG_DUBINS_STAR = 3, 4  # no reference counterpart (README only), see include/rrt_dubins.h
@@ -77,6 +78,7 @@ SYMBOLS = (
     "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
     "rrt_batch_grow_poses", "rrt_plan_grow_poses",
     "rrt_batch_reroot", "rrt_batch_reroot_ms", "rrt_plan_reroot", "rrt_plan_reroot_ms",
+    "rrt_batch_relax", "rrt_batch_relax_ms", "rrt_batch_relax_stats", "rrt_plan_relax", "rrt_plan_relax_ms", "rrt_plan_relax_stats",
     "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
     "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
     "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
@@ -197,6 +199,12 @@ def lib():
             "rrt_batch_reroot_ms": ([vp, C.POINTER(C.c_float * 8), i32], C.c_int),
             "rrt_plan_reroot": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
             "rrt_plan_reroot_ms": ([vp, C.POINTER(C.c_float * 8), i32], C.c_int),
+            "rrt_batch_relax": ([vp, i32, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
+            "rrt_batch_relax_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
+            "rrt_batch_relax_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
+            "rrt_plan_relax": ([vp, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
+            "rrt_plan_relax_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
+            "rrt_plan_relax_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
             "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
             "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
             "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
@@ -332,6 +340,12 @@ def _stage_ms(handle, call, stages, *count):
     ms = (C.c_float * stages)()
     _check(handle, call(C.byref(ms), *count))
     return tuple(ms)
+
+
+def _relax_stats(handle, call):
+    out = (C.c_int64 * 4)()
+    _check(handle, call(C.byref(out)))
+    return dict(zip(("rounds", "fell", "los", "priced"), (int(v) for v in out)))
 
 
 class ResultArrays:
@@ -567,12 +581,14 @@ class Context:
         n of that plan (the result arrays are sized by it).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
         return self._grow(samples, n, logs, False)
 
-    def _grow(self, samples, n, logs, poses, root=None):
+    def _grow(self, samples, n, logs, poses, root=None, r2=None):
         s = _grow_samples(samples, poses)
         res = ResultArrays(int(n), logs, headings=poses)
         j0 = C.c_int32(-1)
         old_id = np.full(int(n) + 1, -1, dtype=np.int32)
-        if root is not None:
+        if r2 is not None:
+            rc = lib().rrt_plan_relax(self._h, int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+        elif root is not None:
             rc = lib().rrt_plan_reroot(self._h, int(root), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
         else:
             call = lib().rrt_plan_grow_poses if poses else lib().rrt_plan_grow
@@ -602,6 +618,21 @@ class Context:
         """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
         seed's three as grow_ms() gives them"""
         return _stage_ms(self._h, lambda *a: lib().rrt_plan_reroot_ms(self._h, *a), 8, 8)
+
+    def relax(self, r2, samples, n, logs=False):
+        """rrt_plan_relax: Batch.relax on the tree of this context's last plan() / plan_resume(), launch and result included.
+        r2: the threshold of the squared distance (hostprep.radius_threshold(r)); n: the n of that plan.  Returns (rc, ResultArrays, j0,
+        old_id int32[j0]) as grow()."""
+        return self._grow(samples, n, logs, False, r2=r2)
+
+    def relax_ms(self):
+        """time in ms of the stages of the last relax(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's three
+        as grow_ms() gives them"""
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_relax_ms(self._h, *a), 9, 9)
+
+    def relax_stats(self):
+        """of the last relax(): dict(rounds, fell, los, priced)"""
+        return _relax_stats(self._h, lambda *a: lib().rrt_plan_relax_stats(self._h, *a))
 
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
@@ -905,6 +936,27 @@ class Batch:
         """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
         seed's three as grow_ms() gives them"""
         return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_reroot_ms(self._h, *a), 8, 8)
+
+    def relax(self, q, r2, samples=()):
+        """rrt_batch_relax: the finished tree of query q (the alive vertices of its keep_tree view, else the whole tree) relaxed to the
+        shortest-path tree from its root over its own vertices and the free edges with d2 < r2 (hostprep.radius_threshold(r)), every
+        old parent edge included; then seeded and armed like grow() for len(samples) more iterations.  Returns (j0, old_id int32[j0],
+        log0): the vertices (all of them), the number each had before, the log row of the first new iteration."""
+        s = _grow_samples(np.zeros((0, 2), dtype=np.int32) if len(samples) == 0 else samples)
+        j0, log0 = C.c_int32(-1), C.c_int32(-1)
+        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_relax(self._h, int(q), int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
+        return j0.value, old_id[:j0.value].copy(), log0.value
+
+    def relax_ms(self):
+        """time in ms of the stages of the last relax(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's three
+        as grow_ms() gives them"""
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_relax_ms(self._h, *a), 9, 9)
+
+    def relax_stats(self):
+        """of the last relax(): dict(rounds, fell, los, priced) -- rounds run, vertices whose cost fell, lines of sight walked,
+        candidate pairs priced"""
+        return _relax_stats(self.ctx.handle, lambda *a: lib().rrt_batch_relax_stats(self._h, *a))
 
     def pose_routes_rows(self, rows):
         """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, with shortcuts or without, which left `rows` rows"""

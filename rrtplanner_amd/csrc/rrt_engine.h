@@ -145,7 +145,7 @@ struct RRT_PRIVATE DevBuf {
 // table says between which two marks each stage lies, so that stages may share a mark or have a pair each.
 constexpr int STAGE_MARKS = 10;
 constexpr int STAGES_IN_A_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}};               // four marks around three stages
-constexpr int STAGES_IN_A_LONG_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}};  // six marks around five stages
+constexpr int STAGES_IN_A_LONG_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}};  // up to seven marks around six stages
 constexpr int STAGES_IN_PAIRS[][2] = {{0, 1}, {2, 3}, {4, 5}, {6, 7}, {8, 9}};  // a pair around each stage
 struct RRT_PRIVATE StageTimer {
     const int (*stages)[2];
@@ -265,6 +265,11 @@ struct rrt_batch {
     // rrt_batch_reroot: the re-root stages in front of that seed (rrt_reroot.h)
     DevBuf reroot_tmp;                             // RerootScratch of n_cap vertices
     StageTimer reroot_time{STAGES_IN_A_LONG_ROW};  // the five stages of the last rrt_batch_reroot; the seed's three are seed_time's
+    // rrt_batch_relax: the buckets, the rounds and the parent pass in front of the later re-root stages and that seed (rrt_relax.h);
+    // it works in reroot_tmp too
+    DevBuf relax_tmp;                             // RelaxScratch of n_cap vertices and RELAX_MAX_CELLS cells
+    StageTimer relax_time{STAGES_IN_A_LONG_ROW};  // the six stages of the last rrt_batch_relax; the seed's three are seed_time's
+    int64_t relax_stats[4] = {0, 0, 0, 0};        // of that call: rounds run, vertices whose cost fell, lines of sight walked, pairs priced
     // the rows and points an earlier routes call left are gone (a launch, a rearm, a keep, a grow: they belong to another tree or view)
     void drop_routes() { route_rows = pose_route_rows = pose_route_points = -1; }
 };

@@ -350,6 +350,34 @@ struct RerootView {
 };
 enum : int { REROOT_D = 0, REROOT_COUNT = 1, REROOT_ERR = 2, REROOT_XY = 3, REROOT_MAXD = 4, REROOT_HEAD = 8 };
 
+// ---- rrt_relax.h ----
+constexpr int RELAX_TPB = 256;           // buckets and check: one vertex per lane; rounds and parents: 4 vertices a workgroup (one per wave)
+constexpr int RELAX_MAX_WG = 2048;       // workgroups of a round and of the parent pass, grid-stride beyond
+constexpr int RELAX_MAX_CELLS = 4096;    // cells of the buckets: the cell edge doubles until they fit
+constexpr int RELAX_LIST = 1024;         // qualifying candidates a wavefront lists in LDS at a time (12 bytes each: 48 KiB a workgroup)
+
+struct RelaxView {
+    const uint8_t *og;       // (W,H) x-major occupancy of the context's grid, != 0 is obstacle
+    int32_t H;
+    const uint32_t *nodes;   // [j] the input tree, dense: the query's tree arrays, or its kept view
+    const int32_t *parent;   // [j] ... its parents in the same numbering; vertex 0 is its root
+    const double *vcost;     // [j] ... and its costs: cost[v] == cost[parent[v]] + d bit for bit
+    int32_t j;
+    int64_t R;               // an edge u -> v is a candidate when d2(u, v) < R (hostprep.radius_threshold)
+    int32_t shift, ncx, ncy; // buckets: cells of edge 2^shift with 2^(2 shift) >= R, ncx * ncy <= RELAX_MAX_CELLS of them
+    int32_t *cell_of;        // [j] the cell of a vertex, -1 for one outside the cells
+    int32_t *cell_start;     // [ncx * ncy + 1] the CSR
+    int32_t *cell_fill;      // [ncx * ncy] counts, then cursors (zeroed by the host)
+    int32_t *items;          // [j] the vertices by cell
+    uint32_t *item_xy;       // [j] ... and the point of each
+    int32_t *pos_of;         // [j] where a vertex stands in items: the rounds flag the vertices whose cost fell in that order
+    double *cost;            // [j] relaxed in place
+    int32_t *new_parent;     // [j] out of the parent pass, input numbering; -1 for the root
+    unsigned long long *stats;  // [4] (zeroed by the host)
+    int32_t *err;            // != 0: an index that cannot be placed, or costs that are no fixpoint
+};
+enum : int { RELAX_CHANGES = 0, RELAX_FELL = 1, RELAX_LOS = 2, RELAX_PRICED = 3, RELAX_STATS = 4 };
+
 // ---- the kernels a host unit launches, by the file that defines them ----
 // rrt_serial.h (units 2 and 3 instantiate it)
 template <bool RW, bool DUB = false>
@@ -414,5 +442,13 @@ __global__ __launch_bounds__(TPB) void rrt_reroot_scan_kernel(RerootView rv);
 __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_place_kernel(RerootView rv);
 __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_parent_kernel(RerootView rv);
 __global__ __launch_bounds__(TPB) void rrt_reroot_cost_kernel(RerootView rv);
+// rrt_relax.h (unit 0, beside the re-root kernels whose later stages it runs)
+__global__ __launch_bounds__(RELAX_TPB) void rrt_relax_cell_kernel(RelaxView xv);
+__global__ __launch_bounds__(TPB) void rrt_relax_scan_kernel(RelaxView xv);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_relax_fill_kernel(RelaxView xv);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_relax_round_kernel(RelaxView xv, const double *cin, double *cout, const uint8_t *dirty_in, uint8_t *dirty_out,
+                                                                    const uint8_t *changed_in, uint8_t *changed_out, int32_t first);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_relax_parent_kernel(RelaxView xv);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_relax_check_kernel(RelaxView xv, const int32_t *src, const double *out_vcost, const int32_t *count);
 
 }  // namespace rrtdev

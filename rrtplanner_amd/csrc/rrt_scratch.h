@@ -128,3 +128,23 @@ struct RerootScratch : Carver {
     int32_t *head = take<int32_t>(8);
     uint8_t *ok[2] = {take<uint8_t>(cap8), take<uint8_t>(cap8)};
 };
+
+// What a relax call works in beside a RerootScratch (rrt_relax.h); cap = n_cap, cells = the most cells of the buckets.  The costs are
+// relaxed in `cost`; the rounds mark the cells that changed in one of the two `dirty` arrays and the vertices whose cost fell, in the
+// order of `items`, in one of the two `changed` arrays, and read the other of each.
+struct RelaxScratch : Carver {
+    RelaxScratch(void *base_, size_t cap_, size_t cells_) : Carver(base_, cap_), cells(cells_) {}
+    size_t cells;
+    size_t cells8 = (cells + 7) & ~(size_t)7;
+    size_t cap8 = (cap + 7) & ~(size_t)7;
+    double *cost = take<double>(cap);
+    unsigned long long *stats = take<unsigned long long>(4);
+    int32_t *cell_of = take<int32_t>(cap);
+    int32_t *items = take<int32_t>(cap);
+    uint32_t *item_xy = take<uint32_t>(cap);
+    int32_t *pos_of = take<int32_t>(cap);
+    int32_t *cell_start = take<int32_t>(cells + 1);
+    int32_t *cell_fill = take<int32_t>(cells);
+    uint8_t *dirty[2] = {take<uint8_t>(cells8), take<uint8_t>(cells8)};
+    uint8_t *changed[2] = {take<uint8_t>(cap8), take<uint8_t>(cap8)};
+};

@@ -1,6 +1,6 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h and rrt_reroot.h.  What the calls share comes first and is written once:
+// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h and rrt_relax.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
@@ -616,11 +616,137 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     HIPCHK(ctx, b->seed_time.create(4));
-    b->reroot_time.ran = 0;  // (the seed's times are this call's from here on: rrt_batch_reroot_ms has nothing to report)
+    b->reroot_time.ran = b->relax_time.ran = 0;  // (the seed's times are this call's from here on: rrt_batch_reroot_ms and rrt_batch_relax_ms have nothing to report)
     return seed_and_arm(who, b, q, seed_from_tree(tree_ref(b, q), j_in), m, j0_out, old_id, log0, poses);
 }
 
-// ---- re-root a finished tree at one of its vertices (rrt_reroot.h), then the seed and the arming of grow ----
+// ---- re-root a finished tree at one of its vertices (rrt_reroot.h) or relax it over its r-disc (rrt_relax.h), then the seed and the
+// arming of grow ----
+// What rrt_batch_reroot and rrt_batch_relax share comes in three parts: the dense input with a kept view (tree_input), the view of the
+// scratch both work in and its reset (reroot_view, reroot_reset), and every stage from the pointer jumping to the armed descriptor
+// (order_price_and_seed).
+
+// The dense input of the call: the query's tree arrays, or, with a kept view, the view with its parents renumbered into stmp.new_parent
+// (one wait: the view's err).  rv: nodes, parent, id, j.  vertex >= 0: a number of the tree as the caller holds it, whose number in
+// the input goes to in_input (-1: not alive in the view).
+static int tree_input(const char *who, rrt_batch *b, int32_t q, const TreeRef &t, const SeedTmpScratch &stmp, int32_t j_in, int32_t vertex, RerootView &rv,
+                      int32_t &in_input) {
+    rrt_ctx *ctx = b->ctx;
+    rv.nodes = t.nodes;
+    rv.parent = t.parent;
+    rv.id = nullptr;
+    rv.j = j_in;
+    in_input = vertex;
+    if (t.kept <= 0) return RRT_OK;
+    SeedView sv{};
+    sv.parent = t.parent;
+    sv.j_old = b->h_desc[(size_t)q].j;
+    sv.j0 = j_in;
+    sv.live_id = t.live_id;
+    sv.rank = stmp.rank;
+    sv.new_parent = stmp.new_parent;
+    sv.err = stmp.err;
+    HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
+    if (const int rc = renumber_view_parents(ctx, sv)) return rc;
+    HIPCHK(ctx, hipGetLastError());
+    int32_t err = 0;
+    in_input = -1;
+    HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    if (vertex >= 0) HIPCHK(ctx, hipMemcpyAsync(&in_input, sv.rank + vertex, sizeof in_input, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err || in_input >= j_in)
+        return fail(ctx, RRT_E_HIP, "%s: the kept view of query %d on the device is not a tree (a parent that is not alive)", who, q);
+    rv.nodes = t.live_nodes;
+    rv.parent = stmp.new_parent;
+    rv.id = t.live_id;
+    return RRT_OK;
+}
+
+static void reroot_view(RerootView &rv, const RerootScratch &tmp) {
+    rv.path = tmp.path;
+    rv.new_parent = tmp.new_parent;
+    rv.ok = tmp.ok[0];
+    rv.anc = tmp.anc[0];
+    rv.dep = tmp.dep[0];
+    rv.level_cnt = tmp.level_cnt;
+    rv.level_start = tmp.level_start;
+    rv.rank = tmp.rank;
+    rv.src = tmp.src;
+    rv.out_nodes = tmp.out_nodes;
+    rv.out_vcost = tmp.out_vcost;
+    rv.out_parent = tmp.out_parent;
+    rv.out_id = tmp.out_id;
+    rv.head = tmp.head;
+}
+
+static int reroot_reset(rrt_ctx *ctx, const RerootView &rv) {
+    const int32_t head0[REROOT_HEAD] = {0, 0, 0, 0, -1, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(rv.head, head0, sizeof head0, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.level_cnt, 0, ((size_t)rv.j + 1) * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.rank, 0xff, (size_t)rv.j * sizeof(int32_t), ctx->stream));
+    return RRT_OK;
+}
+
+// a call that failed past its refusals leaves the query idle without a tree, on the device too
+static int leave_without_tree(rrt_batch *b, int32_t q) {
+    rrt_ctx *ctx = b->ctx;
+    drop_keep_views(b, q);
+    HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &b->h_desc[(size_t)q], sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    return RRT_OK;
+}
+
+// Behind rrt_reroot_link_kernel (rv.new_parent, ok, anc, dep of set 0 stand; the caller recorded mark `mark0` of `time`): alive and
+// depth by pointer jumping, the order by (depth, previous number), the costs from the root down -- marks mark0 + 1 .. mark0 + 3 --,
+// `checks` (what the call queues behind the costs), the one wait, then the seed and the arming.  whole: every input vertex has to be
+// alive.  new_start: the descriptor's xs becomes the root's cell.  what: the failure in the call's words.
+template <typename Checks>
+static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, RerootView &rv, const RerootScratch &tmp, StageTimer &time, int mark0, bool whole,
+                                bool new_start, const char *what, Checks checks, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0) {
+    rrt_ctx *ctx = b->ctx;
+    QDesc &d = b->h_desc[(size_t)q];
+    const int j = rv.j;
+    auto blocks = [](int items) { return dim3(wgs(items, REROOT_TPB)); };
+    const int cur = jump_rounds(j, [&](int from) {
+        hipLaunchKernelGGL(rrt_reroot_jump_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, (const uint8_t *)tmp.ok[from], (const int32_t *)tmp.anc[from],
+                           (const int32_t *)tmp.dep[from], tmp.ok[from ^ 1], tmp.anc[from ^ 1], tmp.dep[from ^ 1], j);
+    });
+    HIPCHK(ctx, time.mark(mark0 + 1, ctx->stream));
+    rv.key = tmp.dep[cur ^ 1];  // (the set the last round read: free from here on)
+    hipLaunchKernelGGL(rrt_reroot_count_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
+                       (const int32_t *)tmp.dep[cur]);
+    hipLaunchKernelGGL(rrt_reroot_level_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_place_kernel, dim3(REROOT_WG), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    hipLaunchKernelGGL(rrt_reroot_parent_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(mark0 + 2, ctx->stream));
+    hipLaunchKernelGGL(rrt_reroot_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(mark0 + 3, ctx->stream));
+    if (const int rc = checks()) return rc;
+    HIPCHK(ctx, hipGetLastError());
+    // the one wait that the sizes force: how many vertices are alive decides the launches of the seed
+    int32_t head[REROOT_HEAD] = {0, 0, 1, 0, -1, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(head, rv.head, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (head[REROOT_ERR] || head[REROOT_COUNT] < 1 || head[REROOT_COUNT] > j || (whole && head[REROOT_COUNT] != j)) {
+        if (const int rc = leave_without_tree(b, q)) return rc;
+        return fail(ctx, RRT_E_HIP, "%s: %s: the query is left without a tree", who, what);
+    }
+    if (new_start) {
+        d.xs[0] = (int32_t)((uint32_t)head[REROOT_XY] & 0xffffu);
+        d.xs[1] = (int32_t)((uint32_t)head[REROOT_XY] >> 16);
+    }
+    SeedFrom from;
+    from.nodes = tmp.out_nodes;
+    from.vcost = tmp.out_vcost;
+    from.id = tmp.out_id;
+    from.parent = tmp.out_parent;
+    from.j0 = head[REROOT_COUNT];
+    if (const int rc = seed_and_arm(who, b, q, from, m, j0_out, old_id, log0, false)) return rc;
+    time.ran = mark0 + 3;
+    return RRT_OK;
+}
+
 // `root` is a vertex number of the tree as the caller holds it: with a kept view an original number, which must be alive.  The stages
 // of rrt_reroot.h leave the re-rooted tree, renumbered by depth and repriced, in scratch; the seed installs it.  The descriptor's xs
 // becomes the new root's cell.  A refusal changes nothing; past the refusals a failure leaves the query idle without a tree.
@@ -641,66 +767,24 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     HIPCHK(ctx, b->seed_time.create(4));
     HIPCHK(ctx, b->reroot_time.create(6));
     const TreeRef t = tree_ref(b, q);
-    const SeedTmpScratch stmp = b->seed_tmp.carve<SeedTmpScratch>();
     const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
     auto blocks = [](int items) { return dim3(wgs(items, REROOT_TPB)); };
     RerootView rv{};
     rv.og = ctx->og;
     rv.H = ctx->H;
-    rv.nodes = t.nodes;
-    rv.parent = t.parent;
-    rv.j = j_in;
-    rv.root = root;
-    if (t.kept > 0) {  // the input is the view: its parents renumbered into scratch, and the root's number in it (-1: not alive)
-        SeedView sv{};
-        sv.parent = t.parent;
-        sv.j_old = d.j;
-        sv.j0 = j_in;
-        sv.live_id = t.live_id;
-        sv.rank = stmp.rank;
-        sv.new_parent = stmp.new_parent;
-        sv.err = stmp.err;
-        HIPCHK(ctx, hipMemsetAsync(sv.err, 0, sizeof(int32_t), ctx->stream));
-        if (const int rc = renumber_view_parents(ctx, sv)) return rc;
-        HIPCHK(ctx, hipGetLastError());
-        int32_t err = 0, in_view = -1;
-        HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(&in_view, sv.rank + root, sizeof in_view, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, wait_stream_spin(ctx->stream));
-        if (err || in_view >= j_in)
-            return fail(ctx, RRT_E_HIP, "%s: the kept view of query %d on the device is not a tree (a parent that is not alive)", who, q);
-        if (in_view < 0)
-            return fail(ctx, RRT_E_ARG, "%s: root=%d is not alive in the kept view of query %d (%d of %d vertices alive)", who, root, q, j_in, d.j);
-        rv.nodes = t.live_nodes;
-        rv.parent = stmp.new_parent;
-        rv.id = t.live_id;
-        rv.root = in_view;
-    }
-    rv.path = tmp.path;
-    rv.new_parent = tmp.new_parent;
-    rv.ok = tmp.ok[0];
-    rv.anc = tmp.anc[0];
-    rv.dep = tmp.dep[0];
-    rv.level_cnt = tmp.level_cnt;
-    rv.level_start = tmp.level_start;
-    rv.rank = tmp.rank;
-    rv.src = tmp.src;
-    rv.out_nodes = tmp.out_nodes;
-    rv.out_vcost = tmp.out_vcost;
-    rv.out_parent = tmp.out_parent;
-    rv.out_id = tmp.out_id;
-    rv.head = tmp.head;
+    // with a view the input is the view: its parents renumbered into scratch, and the root's number in it (-1: not alive)
+    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, root, rv, rv.root)) return rc;
+    if (rv.root < 0)
+        return fail(ctx, RRT_E_ARG, "%s: root=%d is not alive in the kept view of query %d (%d of %d vertices alive)", who, root, q, j_in, d.j);
+    reroot_view(rv, tmp);
     // ---- from here on the query is being replaced ----
     StageTimer &time = b->reroot_time;
-    time.ran = 0;
+    time.ran = b->relax_time.ran = 0;
     b->seed_time.ran = 0;
     b->drop_routes();
     d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
     const int j = j_in;
-    const int32_t head0[REROOT_HEAD] = {0, 0, 0, 0, -1, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(rv.head, head0, sizeof head0, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(rv.level_cnt, 0, ((size_t)j + 1) * sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(rv.rank, 0xff, (size_t)j * sizeof(int32_t), ctx->stream));
+    if (const int rc = reroot_reset(ctx, rv)) return rc;
     HIPCHK(ctx, time.mark(0, ctx->stream));
     hipLaunchKernelGGL(rrt_reroot_path_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, time.mark(1, ctx->stream));
@@ -708,43 +792,149 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     hipLaunchKernelGGL(rrt_reroot_edge_kernel, dim3(std::clamp<unsigned>(wgs(j, REROOT_TPB / 64), 1, REROOT_MAX_WG)), dim3(REROOT_TPB), 0, ctx->stream, rv);
     hipLaunchKernelGGL(rrt_reroot_link_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, time.mark(2, ctx->stream));
-    const int cur = jump_rounds(j, [&](int from) {
-        hipLaunchKernelGGL(rrt_reroot_jump_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, (const uint8_t *)tmp.ok[from], (const int32_t *)tmp.anc[from],
-                           (const int32_t *)tmp.dep[from], tmp.ok[from ^ 1], tmp.anc[from ^ 1], tmp.dep[from ^ 1], j);
-    });
-    HIPCHK(ctx, time.mark(3, ctx->stream));
-    rv.key = tmp.dep[cur ^ 1];  // (the set the last round read: free from here on)
-    hipLaunchKernelGGL(rrt_reroot_count_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
-                       (const int32_t *)tmp.dep[cur]);
-    hipLaunchKernelGGL(rrt_reroot_level_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_reroot_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_reroot_place_kernel, dim3(REROOT_WG), dim3(REROOT_TPB), 0, ctx->stream, rv);
-    hipLaunchKernelGGL(rrt_reroot_parent_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
-    HIPCHK(ctx, time.mark(4, ctx->stream));
-    hipLaunchKernelGGL(rrt_reroot_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
-    HIPCHK(ctx, time.mark(5, ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    // the one wait that the sizes force: how many vertices are alive decides the launches of the seed
-    int32_t head[REROOT_HEAD] = {0, 0, 1, 0, -1, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(head, rv.head, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (head[REROOT_ERR] || head[REROOT_COUNT] < 1 || head[REROOT_COUNT] > j) {
-        drop_keep_views(b, q);
-        HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+    char what[256];
+    snprintf(what, sizeof what, "the parent array of query %d on the device is not a tree (a walk that did not reach vertex 0 within %d steps, or a "
+             "vertex that cannot be placed)", q, j);
+    return order_price_and_seed(who, b, q, rv, tmp, time, 2, false, true, what, [] { return RRT_OK; }, m, j0_out, old_id, log0);
+}
+
+// ---- relax a finished tree to shortest paths over its r-disc (rrt_relax.h) ----
+#ifndef RRT_RELAX_READ_EVERY
+#define RRT_RELAX_READ_EVERY 1  // the host looks at the count of changes behind every round (DESIGN.md 4.2f3 measured 4 against it)
+#endif
+constexpr int RELAX_READ_EVERY = RRT_RELAX_READ_EVERY;
+static_assert(RELAX_READ_EVERY >= 1, "rounds between two looks at the count of changes");
+
+// The cells of the buckets for the threshold R on a W x H grid: the edge 2^shift with 2^(2 shift) >= R, so that d2 < R keeps u within
+// one cell of v on either axis, doubled until the cells fit RELAX_MAX_CELLS.  (Coordinates are below 2^12 on every grid that is not
+// refused, so shift 12 is one cell.)
+static void relax_cells(int64_t R, int W, int H, RelaxView &xv) {
+    int s = 0;
+    while (s < 12 && ((int64_t)1 << (2 * s)) < R) ++s;
+    auto across = [&](int cells_of) { return ((cells_of - 1) >> s) + 1; };
+    while (s < 12 && (int64_t)across(W) * across(H) > RELAX_MAX_CELLS) ++s;
+    xv.shift = s;
+    xv.ncx = across(W);
+    xv.ncy = across(H);
+}
+
+// The vertices stay and every parent is chosen again: the costs relaxed in rounds to their fixpoint, the parents in a pass over the
+// final costs, then the later stages of the re-root (every vertex stays alive: its old parent edge is a candidate), whose repriced
+// costs have to be the fixpoint's, and the seed.  The descriptor's xs stays.  The host reads the count of changes back after every
+// round and stops behind a round that changed nothing; a shortest path has fewer than j edges, so j rounds are the most.
+static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id,
+                       int32_t *log0) {
+    rrt_ctx *ctx = b->ctx;
+    int j_in = 0;
+    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, false,
+                                   "the cost of a Dubins word depends on the headings at its ends: a new parent changes the word", j_in))
+        return rc;
+    if (r2 <= 0) return fail(ctx, RRT_E_ARG, "%s: r2=%lld: the threshold of the squared distance has to be positive", who, (long long)r2);
+    if (b->n_cap > REROOT_WAVES * REROOT_OWN)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
+                    REROOT_WAVES * REROOT_OWN);
+    if (const int rc = stage_cells(who, b, q, "sample", samples, m, 0)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
+    HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
+    HIPCHK(ctx, b->relax_tmp.reserve<RelaxScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
+    HIPCHK(ctx, b->seed_time.create(4));
+    HIPCHK(ctx, b->relax_time.create(7));
+    QDesc &d = b->h_desc[(size_t)q];
+    const TreeRef t = tree_ref(b, q);
+    const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
+    const RelaxScratch rx = b->relax_tmp.carve<RelaxScratch>((size_t)RELAX_MAX_CELLS);
+    RerootView rv{};
+    rv.og = ctx->og;
+    rv.H = ctx->H;
+    int32_t unused = -1;
+    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, -1, rv, unused)) return rc;
+    rv.root = 0;
+    reroot_view(rv, tmp);
+    const int j = j_in;
+    RelaxView xv{};
+    xv.og = ctx->og;
+    xv.H = ctx->H;
+    xv.nodes = rv.nodes;
+    xv.parent = rv.parent;
+    xv.vcost = t.kept > 0 ? t.live_vcost : t.vcost;
+    xv.j = j;
+    xv.R = r2;
+    relax_cells(r2, ctx->W, ctx->H, xv);
+    xv.cell_of = rx.cell_of;
+    xv.cell_start = rx.cell_start;
+    xv.cell_fill = rx.cell_fill;
+    xv.items = rx.items;
+    xv.item_xy = rx.item_xy;
+    xv.pos_of = rx.pos_of;
+    xv.cost = rx.cost;
+    xv.new_parent = tmp.new_parent;
+    xv.stats = rx.stats;
+    xv.err = tmp.head + REROOT_ERR;
+    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
+    // ---- from here on the query is being replaced ----
+    StageTimer &time = b->relax_time;
+    time.ran = b->reroot_time.ran = 0;
+    b->seed_time.ran = 0;
+    b->drop_routes();
+    d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
+    auto blocks = [](int items) { return dim3(wgs(items, RELAX_TPB)); };
+    const dim3 per_wave(std::clamp<unsigned>(wgs(j, RELAX_TPB / 64), 1, RELAX_MAX_WG));
+    if (const int rc = reroot_reset(ctx, rv)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, RELAX_STATS * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.ok, 1, (size_t)j, ctx->stream));  // no edge is cut
+    HIPCHK(ctx, time.mark(0, ctx->stream));
+    hipLaunchKernelGGL(rrt_relax_cell_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
+    hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
+    hipLaunchKernelGGL(rrt_relax_fill_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
+    HIPCHK(ctx, time.mark(1, ctx->stream));
+    int64_t rounds = 0;
+    unsigned long long changes = 0, before = 0;
+    bool settled = false;
+    double *costs[2] = {xv.cost, xv.cost};
+#ifdef RRT_RELAX_TWO_ARRAYS  // (experiment build: a round reads the costs of the round before alone; out_vcost is free until the cost kernel)
+    costs[1] = tmp.out_vcost;
+    HIPCHK(ctx, hipMemcpyAsync(costs[1], costs[0], (size_t)j * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+#endif
+    const int64_t most = (int64_t)j + 2 * (RELAX_READ_EVERY - 1);
+    while (!settled && rounds < most) {
+        const int in = (int)(rounds & 1);
+        HIPCHK(ctx, hipMemsetAsync(rx.dirty[in ^ 1], 0, cells, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(rx.changed[in ^ 1], 0, (size_t)j, ctx->stream));
+        hipLaunchKernelGGL(rrt_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv, (const double *)costs[in], costs[in ^ 1],
+                           (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1], (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], (int32_t)(rounds == 0));
+        HIPCHK(ctx, hipGetLastError());
+        if (++rounds % RELAX_READ_EVERY != 0 && rounds < most) continue;
+        HIPCHK(ctx, hipMemcpyAsync(&changes, xv.stats + RELAX_CHANGES, sizeof changes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, wait_stream_spin(ctx->stream));
-        return fail(ctx, RRT_E_HIP, "%s: the parent array of query %d on the device is not a tree (a walk that did not reach vertex 0 within %d steps, or a "
-                    "vertex that cannot be placed): the query is left without a tree", who, q, j);
+        settled = changes == before;  // (nothing changed since the last look: the last round changed nothing)
+        before = changes;
     }
-    d.xs[0] = (int32_t)((uint32_t)head[REROOT_XY] & 0xffffu);
-    d.xs[1] = (int32_t)((uint32_t)head[REROOT_XY] >> 16);
-    SeedFrom from;
-    from.nodes = tmp.out_nodes;
-    from.vcost = tmp.out_vcost;
-    from.id = tmp.out_id;
-    from.parent = tmp.out_parent;
-    from.j0 = head[REROOT_COUNT];
-    if (const int rc = seed_and_arm(who, b, q, from, m, j0_out, old_id, log0, false)) return rc;
-    time.ran = 5;
+    if (!settled) {
+        if (const int rc = leave_without_tree(b, q)) return rc;
+        return fail(ctx, RRT_E_INTERNAL, "%s: the costs of query %d still fell in round %d of a tree of %d vertices: the query is left without a tree", who, q,
+                    j, j);
+    }
+    HIPCHK(ctx, time.mark(2, ctx->stream));
+    hipLaunchKernelGGL(rrt_relax_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv);
+    hipLaunchKernelGGL(rrt_reroot_link_kernel, dim3(wgs(j, REROOT_TPB)), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(3, ctx->stream));
+    unsigned long long stats[RELAX_STATS] = {0, 0, 0, 0};
+    char what[256];
+    snprintf(what, sizeof what, "the relaxed parents of query %d on the device are not a tree over all %d vertices, or its costs summed from the root "
+             "down are not the fixpoint's", q, j);
+    const int rc = order_price_and_seed(who, b, q, rv, tmp, time, 3, true, false, what, [&] {
+        hipLaunchKernelGGL(rrt_relax_check_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv, (const int32_t *)tmp.src, (const double *)tmp.out_vcost,
+                           (const int32_t *)(tmp.head + REROOT_COUNT));
+        HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)RRT_OK;
+    }, m, j0_out, old_id, log0);
+    if (rc != RRT_OK) return rc;
+    b->relax_stats[0] = rounds;
+    b->relax_stats[1] = (int64_t)stats[RELAX_FELL];
+    b->relax_stats[2] = (int64_t)stats[RELAX_LOS];
+    b->relax_stats[3] = (int64_t)stats[RELAX_PRICED];
     return RRT_OK;
 }
 
@@ -814,6 +1004,49 @@ extern "C" int rrt_batch_reroot_ms(rrt_batch *b, float *ms, int32_t count) {
 extern "C" int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_ms", NO_PLAN);
     return s ? rrt_batch_reroot_ms(s, ms, count) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_relax(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
+    return b ? batch_relax("rrt_batch_relax", b, q, r2, samples_xy, m, j0, old_id, log0) : fail(nullptr, RRT_E_ARG, "rrt_batch_relax: NULL");
+}
+
+extern "C" int rrt_plan_relax(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    const char *who = "rrt_plan_relax";
+    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
+    if (!s) return RRT_E_ARG;
+    int32_t log0 = 0;
+    const int rc = batch_relax(who, s, 0, r2, samples_xy, m, j0, old_id, &log0);
+    return rc != RRT_OK ? rc : run_single(ctx, out);
+}
+
+// ms[0, 6): buckets, rounds, parents, alive and depth, order, costs; ms[6, 9): the seed's stages, as rrt_batch_grow_ms reports them
+extern "C" int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_relax_ms: NULL");
+    if (count < 1 || count > 9) return fail(b->ctx, RRT_E_ARG, "rrt_batch_relax_ms: count=%d, a relax has 6 stages and its seed 3", count);
+    if (!b->relax_time.ran || !b->seed_time.ran)
+        return fail(b->ctx, RRT_E_ARG, "rrt_batch_relax_ms: no rrt_batch_relax on this batch yet, its last one failed, or a grow or a reroot came after it");
+    HIPCHK(b->ctx, b->relax_time.read(ms, std::min(count, 6)));
+    if (count > 6) HIPCHK(b->ctx, b->seed_time.read(ms + 6, count - 6));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_ms", NO_PLAN);
+    return s ? rrt_batch_relax_ms(s, ms, count) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]) {
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_relax_stats: NULL");
+    if (!b->relax_time.ran)
+        return fail(b->ctx, RRT_E_ARG, "rrt_batch_relax_stats: no rrt_batch_relax on this batch yet, its last one failed, or a grow or a reroot came after it");
+    for (int k = 0; k < 4; ++k) out[k] = b->relax_stats[k];
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_stats", NO_PLAN);
+    return s ? rrt_batch_relax_stats(s, out) : RRT_E_ARG;
 }
 
 // ---- the rows of the routes to the goals a decision answered: what rrt_batch_routes and rrt_batch_pose_routes start with ----

@@ -1,4 +1,4 @@
-// rrt_tree_dev.h -- device building blocks of the tree-call kernels (rrt_routes.h, rrt_keep.h, rrt_seed.h, rrt_reroot.h and the pose
+// rrt_tree_dev.h -- device building blocks of the tree-call kernels (rrt_routes.h, rrt_keep.h, rrt_seed.h, rrt_reroot.h, rrt_relax.h and the pose
 // calls of unit 9; kernels_tu.hip units 0, 6, 7, 8, 9).  No expansion kernel includes this file.
 //
 //   wg_scan_step        the cross-wave step of an exclusive scan by ONE workgroup of TPB threads

@@ -318,6 +318,10 @@ class _DubinsBase(RRT):
     def keep_tree_resident(self, grids, k=0):
         return self.keep_tree(None)
 
+    def relax(self, r=None, m=0):
+        raise ValueError("relax: the cost of a Dubins word depends on the headings at its ends, and a new parent changes the word: a "
+                         "Dubins tree is not relaxed (RRTStandard and RRTStar only)")
+
     def keep_pose_tree(self, og_new):
         """The map changed: keep the Dubins tree of the last plan() instead of planning again (rrt_plan_keep_pose_tree).  Like
         set_og(og_new) -- og, free, the upload; a later plan() plans on og_new -- except that the tree stays on the device.  Returns

@@ -500,6 +500,7 @@ class RRT(object):
         self._grid_dirty = True
         self.device_id = 0
         self.last_stats = None
+        self.last_relax = None  # dict(rounds, fell, los, priced) of the last relax()
         self.last_route = None  # which way the last plan() went: "kernel", "kernel-large" (grids up to 4096 x 4096) or "host" (hostloop.py)
         self._tree_resident = None  # connect_goals: "device" while the tree of the last plan() is on the device for this grid and n, "host" after the host route
 
@@ -687,9 +688,35 @@ class RRT(object):
         Raises as grow; ValueError for a vertex outside the tree or one that is not alive."""
         return self._grow_or_reroot("reroot", m, vertex)
 
-    def _grow_or_reroot(self, who: str, m: int, vertex):
-        """grow (vertex is None) and reroot: the refusals of the classes, the draws and the context's call"""
+    def relax(self, r: float = None, m: int = 0) -> Tuple[nx.DiGraph, int]:
+        """Choose every parent of the tree of the last plan() again (rrt_plan_relax): the vertices stay, and the tree becomes the
+        shortest-path tree from its root over the graph of its own vertices with the edges that are shorter than r and free on the
+        current grid, each walked from the parent to the child, and every old parent edge (however long).  That is the limit the
+        rewire of RRT* approaches.  It is what makes the routes over a re-rooted tree short again: reroot reprices the edges that
+        were chosen for the old start, relax chooses them for the new one.
+
+        r defaults to self.r_rewire; RRTStandard has none and must pass it.  cost[v] = min over the candidate parents u of
+        cost[u] + |uv| in the loop's own f64 sum; among the parents that give a vertex its cost the one nearest the root wins
+        (smallest (cost, number)).  The vertices are renumbered by (depth, previous number) as reroot numbers them, then m more samples
+        are spent exactly as grow(m) spends them, and go2goal connects plan()'s xgoal.
+
+        Returns (T, gv) with the row contract of plan() for self.n, as grow.  self.last_grow_ids[k] is the number vertex k had before
+        the call; self.last_relax holds dict(rounds, fell, los, priced): rounds run, vertices whose cost fell, lines of sight
+        walked, candidate pairs priced.  Raises as grow; ValueError for a missing or non-positive r."""
+        if r is None:
+            r = getattr(self, "r_rewire", None)
+        if r is None:
+            raise ValueError("relax: this planner has no r_rewire: pass r, the radius of the candidate edges in cells")
+        if not (float(r) > 0):
+            raise ValueError(f"relax: r={r}")
+        out = self._grow_or_reroot("relax", m, None, r2=hostprep.radius_threshold(r))
+        return out
+
+    def _grow_or_reroot(self, who: str, m: int, vertex, r2=None):
+        """grow (vertex is None), reroot and relax (r2: its threshold): the refusals of the classes, the draws and the context's call"""
         if not self._GROWS:
+            if r2 is not None:
+                raise ValueError(f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, which is not rebuilt)")
             raise ValueError(f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, a Dubins tree headings, which the seed does not rebuild)"
                              if vertex is None else
                              f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, which is not rebuilt; a Dubins word is not reversible)")
@@ -698,7 +725,7 @@ class RRT(object):
         if _rewire_mode(getattr(self, "rewire", "reference")):
             raise ValueError(f'{who}: rewire="correct" keeps child lists on the device, which the seed does not rebuild')
         if self.last_route == "kernel-large" or self._on_the_large_grid_kernel():
-            raise ValueError(f"{who}: the large-grid route (grids beyond 2048 cells a side) is not {'grown' if vertex is None else 're-rooted'}")
+            raise ValueError(f"{who}: the large-grid route (grids beyond 2048 cells a side) is not {'relaxed' if r2 is not None else 'grown' if vertex is None else 're-rooted'}")
         self._keep_guard(who, np.asarray(self.og).shape)
         m = int(m)
         if m < 0:
@@ -721,7 +748,10 @@ class RRT(object):
         try:
             self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
             try:
-                rc, res, j0, old_id = ctx.grow(samples, int(self.n)) if vertex is None else ctx.reroot(vertex, samples, int(self.n))
+                if r2 is not None:
+                    rc, res, j0, old_id = ctx.relax(r2, samples, int(self.n))
+                else:
+                    rc, res, j0, old_id = ctx.grow(samples, int(self.n)) if vertex is None else ctx.reroot(vertex, samples, int(self.n))
             except _ffi.RRTError as e:
                 if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
                     self._tree_resident = "device"
@@ -732,6 +762,8 @@ class RRT(object):
             self._tree_resident = "device"
             self.last_route = "kernel"
             self.last_grow_ids = old_id
+            if r2 is not None:
+                self.last_relax = ctx.relax_stats()
             self._grow_j0 = int(res.j)
             self.last_stats = {k: getattr(res, k) for k in ("j", "i_switch", "sum_j", "sum_cells_nn", "sum_near",
                                                               "sum_cells_cand", "n_los_cand", "n_rewired", "n_propagated")}
