@@ -36,7 +36,7 @@ extern "C" {
                                       expansion kernels' packed keys; such a planner runs host-driven over rrt_tree_query instead, slower, same results);
                                       RRT_FLAG_LARGE_GRID with a planner or flag it does not take; rrt_set_grid: more than 32767 cells per axis */
 #define RRT_E_COMM (-6)            /* multi-GPU gather: librccl missing, no communicator, RCCL error, unequal slabs */
-#define RRT_E_INTERNAL (-7)        /* rrt_batch_relax: an iteration went past the bound that its own reasoning sets */
+#define RRT_E_INTERNAL (-7)        /* rrt_batch_relax, rrt_batch_relax_poses: an iteration went past the bound that its own reasoning sets */
 
 #define RRT_ALG_STANDARD 0 /* RRTStandard.plan     rrt.py:386 */
 #define RRT_ALG_STAR 1     /* RRTStar.plan         rrt.py:466 */
@@ -429,6 +429,27 @@ int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count);
 /* of the same call: out[0] rounds run (the last one changed nothing), out[1] vertices whose cost fell, out[2] lines of sight walked,
  * out[3] candidate pairs priced (the last two depend on the order in which the rounds' wavefronts ran) */
 int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]);
+/* rrt_batch_relax for a batch created with RRT_FLAG_DUBINS (rrt_pose_relax.h): the finished Dubins tree of query q relaxed to the
+ * shortest-path tree from its root over the directed graph of its own poses, then rrt_batch_grow_poses from it.  A vertex's pose
+ * (x, y, h) is fixed and the shortest word u -> v is a function of the two poses alone, so every parent can be chosen again.
+ *   input    the whole tree [0, j), or with a view (rrt_batch_keep_pose_tree) its alive vertices with their heading bytes.
+ *   edges    E(v), v != 0: every u != v with d2(u, v) < r2 whose shortest Dubins word from pose u to pose v is finite and sweeps free
+ *            on the context's current grid -- the sweep of rrt_batch_connect_poses and rrt_batch_keep_pose_tree: every sample inside the
+ *            grid and on a free cell, then v's cell --, and the edge parent[v] -> v, which is not swept again and may be longer than
+ *            the radius: no vertex is ever cut.
+ *   costs    cost[0] = 0, cost[v] = min over u in E(v) of cost[u] + len(u -> v) in f64, the expansion loop's own sum.
+ *   parents, then: as rrt_batch_relax, the costs summed again from the root down as cost[parent] + word (RRT_E_HIP unless they equal
+ *            the fixpoint bit for bit), the headings gathered into the new order, rrt_batch_grow_poses' seed, arming and launch with
+ *            the m pose samples (x, y, heading index).
+ * Refusals: all of rrt_batch_grow_poses' in its order (a straight-line batch: use rrt_batch_relax), then RRT_E_ARG for r2 <= 0.
+ * A refusal changes nothing; a call that fails later leaves the query without a tree.  RRT_E_INTERNAL as rrt_batch_relax. */
+int rrt_batch_relax_poses(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
+/* as rrt_batch_relax_ms, of the last successful rrt_batch_relax_poses: the buckets (with the items' headings and the old parent edges'
+ * lengths), the rounds, the parents, alive and depth, the order, the costs (words, then sums), then the seed's three stages */
+int rrt_batch_relax_poses_ms(rrt_batch *b, float *ms, int32_t count);
+/* of the same call: out[0] rounds run, out[1] vertices whose cost fell, out[2] sweeps run and out[3] words evaluated in the rounds (a
+ * round meets a pair at most once; the parent pass is not counted; both depend on the order in which the rounds' wavefronts ran) */
+int rrt_batch_relax_poses_stats(rrt_batch *b, int64_t out[4]);
 /* diagnostic builds (-DRRT_STAMPS): shader cycles wave 0 of query q spent in scan / barrier / nearest+line of sight /
  * choose parent / insert / go2goal; zeros in the product build */
 int rrt_batch_debug_cycles(rrt_batch *b, int32_t q, uint64_t out[38]); /* [0..5] phases, [6..37] per-wave owner-phase cycles */
@@ -511,6 +532,11 @@ int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count);
 int rrt_plan_relax(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
 int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count);
 int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]);
+/* rrt_batch_relax_poses on the Dubins tree of the context's last rrt_plan, launch, sync and result (headings included) as
+ * rrt_plan_grow_poses; rrt_plan_relax_poses_ms, rrt_plan_relax_poses_stats: those of that batch. */
+int rrt_plan_relax_poses(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out);
+int rrt_plan_relax_poses_ms(rrt_ctx *ctx, float *ms, int32_t count);
+int rrt_plan_relax_poses_stats(rrt_ctx *ctx, int64_t out[4]);
 
 /* ---- host-driven planners: a caller-supplied cost function (rrt.py:55, :70-80 accepts any Python callable) cannot run on the
  * device, so for such a planner the loop of rrt.py:498-548 / :690-748 stays on the host and asks the device, once per

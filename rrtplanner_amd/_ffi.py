@@ -79,6 +79,8 @@ SYMBOLS = (
     "rrt_batch_grow_poses", "rrt_plan_grow_poses",
     "rrt_batch_reroot", "rrt_batch_reroot_ms", "rrt_plan_reroot", "rrt_plan_reroot_ms",
     "rrt_batch_relax", "rrt_batch_relax_ms", "rrt_batch_relax_stats", "rrt_plan_relax", "rrt_plan_relax_ms", "rrt_plan_relax_stats",
+    "rrt_batch_relax_poses", "rrt_batch_relax_poses_ms", "rrt_batch_relax_poses_stats",
+    "rrt_plan_relax_poses", "rrt_plan_relax_poses_ms", "rrt_plan_relax_poses_stats",
     "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
     "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
     "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
@@ -205,6 +207,12 @@ def lib():
             "rrt_plan_relax": ([vp, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
             "rrt_plan_relax_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
             "rrt_plan_relax_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
+            "rrt_batch_relax_poses": ([vp, i32, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
+            "rrt_batch_relax_poses_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
+            "rrt_batch_relax_poses_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
+            "rrt_plan_relax_poses": ([vp, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
+            "rrt_plan_relax_poses_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
+            "rrt_plan_relax_poses_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
             "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
             "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
             "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
@@ -342,10 +350,13 @@ def _stage_ms(handle, call, stages, *count):
     return tuple(ms)
 
 
-def _relax_stats(handle, call):
+def _relax_stats(handle, call, names=("rounds", "fell", "los", "priced")):
     out = (C.c_int64 * 4)()
     _check(handle, call(C.byref(out)))
-    return dict(zip(("rounds", "fell", "los", "priced"), (int(v) for v in out)))
+    return dict(zip(names, (int(v) for v in out)))
+
+
+POSE_RELAX_STATS = ("rounds", "fell", "sweeps", "words")
 
 
 class ResultArrays:
@@ -587,7 +598,8 @@ class Context:
         j0 = C.c_int32(-1)
         old_id = np.full(int(n) + 1, -1, dtype=np.int32)
         if r2 is not None:
-            rc = lib().rrt_plan_relax(self._h, int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
+            call = lib().rrt_plan_relax_poses if poses else lib().rrt_plan_relax
+            rc = call(self._h, int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
         elif root is not None:
             rc = lib().rrt_plan_reroot(self._h, int(root), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
         else:
@@ -633,6 +645,20 @@ class Context:
     def relax_stats(self):
         """of the last relax(): dict(rounds, fell, los, priced)"""
         return _relax_stats(self._h, lambda *a: lib().rrt_plan_relax_stats(self._h, *a))
+
+    def relax_poses(self, r2, samples, n, logs=False):
+        """rrt_plan_relax_poses: Batch.relax_poses on the Dubins tree of this context's last plan(), launch and result (headings
+        included) as grow_poses().  samples: (m, 3) rows (x, y, heading index).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
+        return self._grow(samples, n, logs, True, r2=r2)
+
+    def relax_poses_ms(self):
+        """time in ms of the stages of the last relax_poses(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's
+        three as grow_ms() gives them"""
+        return _stage_ms(self._h, lambda *a: lib().rrt_plan_relax_poses_ms(self._h, *a), 9, 9)
+
+    def relax_poses_stats(self):
+        """of the last relax_poses(): dict(rounds, fell, sweeps, words)"""
+        return _relax_stats(self._h, lambda *a: lib().rrt_plan_relax_poses_stats(self._h, *a), POSE_RELAX_STATS)
 
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
@@ -957,6 +983,28 @@ class Batch:
         """of the last relax(): dict(rounds, fell, los, priced) -- rounds run, vertices whose cost fell, lines of sight walked,
         candidate pairs priced"""
         return _relax_stats(self.ctx.handle, lambda *a: lib().rrt_batch_relax_stats(self._h, *a))
+
+    def relax_poses(self, q, r2, samples=()):
+        """rrt_batch_relax_poses: relax() for a Dubins batch.  The finished tree of query q (the alive vertices of its keep_pose_tree
+        view, else the whole tree) relaxed to the shortest-path tree from its root over its own poses: the edges u -> v with d2 < r2
+        whose shortest Dubins word sweeps free, every old parent edge included; then seeded with its headings and armed like
+        grow_poses() for len(samples) more iterations.  samples: (m, 3) rows (x, y, heading index).  Returns (j0, old_id int32[j0],
+        log0) as relax()."""
+        s = _grow_samples(np.zeros((0, 3), dtype=np.int32) if len(samples) == 0 else samples, True)
+        j0, log0 = C.c_int32(-1), C.c_int32(-1)
+        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
+        _check(self.ctx.handle, lib().rrt_batch_relax_poses(self._h, int(q), int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
+        return j0.value, old_id[:j0.value].copy(), log0.value
+
+    def relax_poses_ms(self):
+        """time in ms of the stages of the last relax_poses(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's
+        three as grow_ms() gives them"""
+        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_relax_poses_ms(self._h, *a), 9, 9)
+
+    def relax_poses_stats(self):
+        """of the last relax_poses(): dict(rounds, fell, sweeps, words) -- rounds run, vertices whose cost fell, sweeps run, words
+        evaluated"""
+        return _relax_stats(self.ctx.handle, lambda *a: lib().rrt_batch_relax_poses_stats(self._h, *a), POSE_RELAX_STATS)
 
     def pose_routes_rows(self, rows):
         """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, with shortcuts or without, which left `rows` rows"""

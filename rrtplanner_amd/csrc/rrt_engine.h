@@ -270,6 +270,9 @@ struct rrt_batch {
     DevBuf relax_tmp;                             // RelaxScratch of n_cap vertices and RELAX_MAX_CELLS cells
     StageTimer relax_time{STAGES_IN_A_LONG_ROW};  // the six stages of the last rrt_batch_relax; the seed's three are seed_time's
     int64_t relax_stats[4] = {0, 0, 0, 0};        // of that call: rounds run, vertices whose cost fell, lines of sight walked, pairs priced
+    // rrt_batch_relax_poses (a Dubins batch): what it needs beside the two (rrt_pose_relax.h); the timer and the counters are those above,
+    // which then count sweeps and words
+    DevBuf pose_relax_tmp;                        // PoseRelaxScratch of n_cap vertices
     // the rows and points an earlier routes call left are gone (a launch, a rearm, a keep, a grow: they belong to another tree or view)
     void drop_routes() { route_rows = pose_route_rows = pose_route_points = -1; }
 };

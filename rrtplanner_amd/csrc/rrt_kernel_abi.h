@@ -378,6 +378,21 @@ struct RelaxView {
 };
 enum : int { RELAX_CHANGES = 0, RELAX_FELL = 1, RELAX_LOS = 2, RELAX_PRICED = 3, RELAX_STATS = 4 };
 
+// ---- rrt_pose_relax.h ----
+constexpr int POSE_RELAX_LIST = 256;     // surviving candidates a wavefront lists in LDS at a time (17 bytes each: 17 KiB a workgroup)
+
+// The buckets, the costs, the flags and the counters are rrt_relax.h's (xv; its RELAX_LOS counts sweeps and its RELAX_PRICED words here);
+// a pose adds a heading byte to every vertex and every item, and an edge is a Dubins word.
+struct PoseRelaxView {
+    RelaxView xv;
+    int32_t W;               // the grid's other side (xv.H is the stride)
+    int32_t nh;              // the query's discrete headings
+    double rho;              // ... and turning radius
+    const uint8_t *heading;  // [j] the heading index of every input vertex
+    uint8_t *item_h;         // [j] ... and of every item of the CSR, beside item_xy
+    double *plen;            // [j] the length of the word parent[v] -> v, the old parent edge, evaluated once
+};
+
 // ---- the kernels a host unit launches, by the file that defines them ----
 // rrt_serial.h (units 2 and 3 instantiate it)
 template <bool RW, bool DUB = false>
@@ -450,5 +465,12 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_relax_round_kernel(RelaxView xv
                                                                     const uint8_t *changed_in, uint8_t *changed_out, int32_t first);
 __global__ __launch_bounds__(RELAX_TPB) void rrt_relax_parent_kernel(RelaxView xv);
 __global__ __launch_bounds__(RELAX_TPB) void rrt_relax_check_kernel(RelaxView xv, const int32_t *src, const double *out_vcost, const int32_t *count);
+// rrt_pose_relax.h (unit 0, beside the relax kernels whose buckets and check it runs)
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_item_kernel(PoseRelaxView pv);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_round_kernel(PoseRelaxView pv, const uint8_t *dirty_in, uint8_t *dirty_out, const uint8_t *changed_in,
+                                                                         uint8_t *changed_out, int32_t first);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_parent_kernel(PoseRelaxView pv);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_word_kernel(PoseRelaxView pv, RerootView rv, uint8_t *out_heading, double *word);
+__global__ __launch_bounds__(TPB) void rrt_pose_relax_cost_kernel(RerootView rv, const double *word);
 
 }  // namespace rrtdev

@@ -235,7 +235,11 @@ __global__ __launch_bounds__(REROOT_TPB) void rrt_reroot_parent_kernel(RerootVie
     rv.out_parent[pos] = np;
 }
 
-__global__ __launch_bounds__(TPB) void rrt_reroot_cost_kernel(RerootView rv) {
+// The costs of the new numbers from the root down, by ONE workgroup of TPB threads: edge(p, pos) is the length of the edge from new
+// number p to its child pos (rrt_reroot_cost_kernel: the straight line; rrt_pose_relax_cost_kernel, rrt_pose_relax.h: a Dubins word
+// evaluated beforehand).
+template <typename Edge>
+__device__ __forceinline__ void reroot_cost_levels(const RerootView &rv, Edge edge) {
     const int t = (int)threadIdx.x;
     const int j = rv.j, count = rv.head[REROOT_COUNT];
     if (count < 1 || count > j || rv.head[REROOT_ERR] != 0) return;  // (uniform)
@@ -249,9 +253,13 @@ __global__ __launch_bounds__(TPB) void rrt_reroot_cost_kernel(RerootView rv) {
         if (lo >= count || hi > count || hi < lo) break;  // (uniform; the levels of alive vertices have no gap)
         for (int pos = lo + t; pos < hi; pos += TPB) {
             const int p = rv.out_parent[pos];
-            if (p >= 0 && p < lo) rv.out_vcost[pos] = rv.out_vcost[p] + sqrt_u32(dist2(rv.out_nodes[p], rv.out_nodes[pos]));
+            if (p >= 0 && p < lo) rv.out_vcost[pos] = rv.out_vcost[p] + edge(p, pos);
         }
     }
+}
+
+__global__ __launch_bounds__(TPB) void rrt_reroot_cost_kernel(RerootView rv) {
+    reroot_cost_levels(rv, [&](int p, int pos) { return sqrt_u32(dist2(rv.out_nodes[p], rv.out_nodes[pos])); });
 }
 
 }  // namespace rrtdev

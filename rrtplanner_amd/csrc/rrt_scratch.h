@@ -148,3 +148,15 @@ struct RelaxScratch : Carver {
     uint8_t *dirty[2] = {take<uint8_t>(cells8), take<uint8_t>(cells8)};
     uint8_t *changed[2] = {take<uint8_t>(cap8), take<uint8_t>(cap8)};
 };
+
+// What a relax_poses call works in beside a RerootScratch and a RelaxScratch (rrt_pose_relax.h); cap = n_cap.  plen: the length of every
+// old parent edge; word: of the edge to every new number's parent, for the cost stage; item_h: the heading byte of every item of the
+// CSR; out_heading: the headings in the new order, which the seed installs.  The byte arrays have cap rounded up to 8 and come last.
+struct PoseRelaxScratch : Carver {
+    using Carver::Carver;
+    size_t cap8 = (cap + 7) & ~(size_t)7;
+    double *plen = take<double>(cap);
+    double *word = take<double>(cap);
+    uint8_t *item_h = take<uint8_t>(cap8);
+    uint8_t *out_heading = take<uint8_t>(cap8);
+};

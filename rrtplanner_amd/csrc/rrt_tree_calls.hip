@@ -1,6 +1,6 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h and rrt_relax.h.  What the calls share comes first and is written once:
+// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax, relax_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h, rrt_relax.h and rrt_pose_relax.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
@@ -457,13 +457,14 @@ extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
 // (seed_and_arm), and what the seed is made from (SeedFrom).
 
 // Every refusal of a grow call up to the room, in its order; `dubins`: why this call takes no Dubins batch.  0: not refused, and
-// j_in is what the call starts from: the vertices of the view, else of the tree.
-static int refuse_grow(const char *who, rrt_batch *b, int32_t q, bool null_arg, int32_t m, bool poses, const char *dubins, int &j_in) {
+// j_in is what the call starts from: the vertices of the view, else of the tree.  use: the call a pose call sends a straight-line batch to.
+static int refuse_grow(const char *who, rrt_batch *b, int32_t q, bool null_arg, int32_t m, bool poses, const char *dubins, int &j_in,
+                       const char *use = "rrt_batch_grow") {
     rrt_ctx *ctx = b->ctx;
     if (null_arg) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     if (!poses && (b->flags & RRT_FLAG_DUBINS)) return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (%s)", who, dubins);
     if (poses && !(b->flags & RRT_FLAG_DUBINS))
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its samples are cells and its edges straight lines: use rrt_batch_grow)", who);
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its samples are cells and its edges straight lines: use %s)", who, use);
     if (b->flags & RRT_FLAG_REWIRE)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch created with RRT_FLAG_REWIRE (its kernel keeps child lists, which the seed does not rebuild)", who);
     if (b->flags & RRT_FLAG_LARGE_GRID)
@@ -628,10 +629,11 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
 
 // The dense input of the call: the query's tree arrays, or, with a kept view, the view with its parents renumbered into stmp.new_parent
 // (one wait: the view's err).  rv: nodes, parent, id, j.  vertex >= 0: a number of the tree as the caller holds it, whose number in
-// the input goes to in_input (-1: not alive in the view).
+// the input goes to in_input (-1: not alive in the view).  heading: nullptr, or where the heading bytes of the input go (a Dubins batch).
 static int tree_input(const char *who, rrt_batch *b, int32_t q, const TreeRef &t, const SeedTmpScratch &stmp, int32_t j_in, int32_t vertex, RerootView &rv,
-                      int32_t &in_input) {
+                      int32_t &in_input, const uint8_t **heading = nullptr) {
     rrt_ctx *ctx = b->ctx;
+    if (heading) *heading = t.kept > 0 ? t.live_heading : t.heading;
     rv.nodes = t.nodes;
     rv.parent = t.parent;
     rv.id = nullptr;
@@ -696,13 +698,19 @@ static int leave_without_tree(rrt_batch *b, int32_t q) {
     return RRT_OK;
 }
 
+// the cost stage of a straight-line call: what batch_reroot and batch_relax hand to order_price_and_seed as `price`
+static void price_lines(rrt_ctx *ctx, const RerootView &rv) { hipLaunchKernelGGL(rrt_reroot_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv); }
+
 // Behind rrt_reroot_link_kernel (rv.new_parent, ok, anc, dep of set 0 stand; the caller recorded mark `mark0` of `time`): alive and
-// depth by pointer jumping, the order by (depth, previous number), the costs from the root down -- marks mark0 + 1 .. mark0 + 3 --,
+// depth by pointer jumping, the order by (depth, previous number), the costs from the root down (`price` queues that stage) --
+// marks mark0 + 1 .. mark0 + 3 --,
 // `checks` (what the call queues behind the costs), the one wait, then the seed and the arming.  whole: every input vertex has to be
-// alive.  new_start: the descriptor's xs becomes the root's cell.  what: the failure in the call's words.
-template <typename Checks>
+// alive.  new_start: the descriptor's xs becomes the root's cell.  what: the failure in the call's words.  out_heading: nullptr, or the
+// heading bytes in the new order, which `price` wrote (a Dubins batch: the seed is a pose seed).
+template <typename Price, typename Checks>
 static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, RerootView &rv, const RerootScratch &tmp, StageTimer &time, int mark0, bool whole,
-                                bool new_start, const char *what, Checks checks, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0) {
+                                bool new_start, const char *what, Price price, Checks checks, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
+                                const uint8_t *out_heading = nullptr) {
     rrt_ctx *ctx = b->ctx;
     QDesc &d = b->h_desc[(size_t)q];
     const int j = rv.j;
@@ -720,7 +728,7 @@ static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, Reroot
     hipLaunchKernelGGL(rrt_reroot_place_kernel, dim3(REROOT_WG), dim3(REROOT_TPB), 0, ctx->stream, rv);
     hipLaunchKernelGGL(rrt_reroot_parent_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, time.mark(mark0 + 2, ctx->stream));
-    hipLaunchKernelGGL(rrt_reroot_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
+    price();
     HIPCHK(ctx, time.mark(mark0 + 3, ctx->stream));
     if (const int rc = checks()) return rc;
     HIPCHK(ctx, hipGetLastError());
@@ -741,8 +749,9 @@ static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, Reroot
     from.vcost = tmp.out_vcost;
     from.id = tmp.out_id;
     from.parent = tmp.out_parent;
+    from.heading = out_heading;
     from.j0 = head[REROOT_COUNT];
-    if (const int rc = seed_and_arm(who, b, q, from, m, j0_out, old_id, log0, false)) return rc;
+    if (const int rc = seed_and_arm(who, b, q, from, m, j0_out, old_id, log0, out_heading != nullptr)) return rc;
     time.ran = mark0 + 3;
     return RRT_OK;
 }
@@ -795,7 +804,7 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     char what[256];
     snprintf(what, sizeof what, "the parent array of query %d on the device is not a tree (a walk that did not reach vertex 0 within %d steps, or a "
              "vertex that cannot be placed)", q, j);
-    return order_price_and_seed(who, b, q, rv, tmp, time, 2, false, true, what, [] { return RRT_OK; }, m, j0_out, old_id, log0);
+    return order_price_and_seed(who, b, q, rv, tmp, time, 2, false, true, what, [&] { price_lines(ctx, rv); }, [] { return RRT_OK; }, m, j0_out, old_id, log0);
 }
 
 // ---- relax a finished tree to shortest paths over its r-disc (rrt_relax.h) ----
@@ -822,22 +831,26 @@ static void relax_cells(int64_t R, int W, int H, RelaxView &xv) {
 // final costs, then the later stages of the re-root (every vertex stays alive: its old parent edge is a candidate), whose repriced
 // costs have to be the fixpoint's, and the seed.  The descriptor's xs stays.  The host reads the count of changes back after every
 // round and stops behind a round that changed nothing; a shortest path has fewer than j edges, so j rounds are the most.
+// rrt_batch_relax (poses == false: straight-line batches, rows (x, y)) and rrt_batch_relax_poses (poses == true: Dubins batches, rows
+// (x, y, h)) are one call with two edges: a Dubins batch relaxes over the words between its poses (rrt_pose_relax.h) on the same
+// buckets, flags and counters, prices the new order with words, and its seed carries the heading bytes.
 static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id,
-                       int32_t *log0) {
+                       int32_t *log0, bool poses) {
     rrt_ctx *ctx = b->ctx;
     int j_in = 0;
-    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, false,
-                                   "the cost of a Dubins word depends on the headings at its ends: a new parent changes the word", j_in))
+    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, poses,
+                                   "the cost of a Dubins word depends on the headings at its ends: a new parent changes the word", j_in, "rrt_batch_relax"))
         return rc;
     if (r2 <= 0) return fail(ctx, RRT_E_ARG, "%s: r2=%lld: the threshold of the squared distance has to be positive", who, (long long)r2);
     if (b->n_cap > REROOT_WAVES * REROOT_OWN)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
                     REROOT_WAVES * REROOT_OWN);
-    if (const int rc = stage_cells(who, b, q, "sample", samples, m, 0)) return rc;
+    if (const int rc = stage_cells(who, b, q, "sample", samples, m, poses ? b->h_desc[(size_t)q].nh : 0)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
     HIPCHK(ctx, b->relax_tmp.reserve<RelaxScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
+    if (poses) HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
     HIPCHK(ctx, b->seed_time.create(4));
     HIPCHK(ctx, b->relax_time.create(7));
     QDesc &d = b->h_desc[(size_t)q];
@@ -848,7 +861,8 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     rv.og = ctx->og;
     rv.H = ctx->H;
     int32_t unused = -1;
-    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, -1, rv, unused)) return rc;
+    PoseRelaxView pv{};
+    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, -1, rv, unused, poses ? &pv.heading : nullptr)) return rc;
     rv.root = 0;
     reroot_view(rv, tmp);
     const int j = j_in;
@@ -872,6 +886,15 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     xv.stats = rx.stats;
     xv.err = tmp.head + REROOT_ERR;
     const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
+    const PoseRelaxScratch px = poses ? b->pose_relax_tmp.carve<PoseRelaxScratch>() : PoseRelaxScratch(nullptr, 0);
+    if (poses) {
+        pv.xv = xv;
+        pv.W = ctx->W;
+        pv.nh = d.nh;
+        pv.rho = d.rho;
+        pv.item_h = px.item_h;
+        pv.plen = px.plen;
+    }
     // ---- from here on the query is being replaced ----
     StageTimer &time = b->relax_time;
     time.ran = b->reroot_time.ran = 0;
@@ -888,6 +911,7 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     hipLaunchKernelGGL(rrt_relax_cell_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
     hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
     hipLaunchKernelGGL(rrt_relax_fill_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
+    if (poses) hipLaunchKernelGGL(rrt_pose_relax_item_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv);
     HIPCHK(ctx, time.mark(1, ctx->stream));
     int64_t rounds = 0;
     unsigned long long changes = 0, before = 0;
@@ -902,8 +926,12 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
         const int in = (int)(rounds & 1);
         HIPCHK(ctx, hipMemsetAsync(rx.dirty[in ^ 1], 0, cells, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(rx.changed[in ^ 1], 0, (size_t)j, ctx->stream));
-        hipLaunchKernelGGL(rrt_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv, (const double *)costs[in], costs[in ^ 1],
-                           (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1], (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], (int32_t)(rounds == 0));
+        if (poses)
+            hipLaunchKernelGGL(rrt_pose_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv, (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1],
+                               (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], (int32_t)(rounds == 0));
+        else
+            hipLaunchKernelGGL(rrt_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv, (const double *)costs[in], costs[in ^ 1],
+                               (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1], (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], (int32_t)(rounds == 0));
         HIPCHK(ctx, hipGetLastError());
         if (++rounds % RELAX_READ_EVERY != 0 && rounds < most) continue;
         HIPCHK(ctx, hipMemcpyAsync(&changes, xv.stats + RELAX_CHANGES, sizeof changes, hipMemcpyDeviceToHost, ctx->stream));
@@ -917,19 +945,26 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
                     j, j);
     }
     HIPCHK(ctx, time.mark(2, ctx->stream));
-    hipLaunchKernelGGL(rrt_relax_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv);
+    if (poses) hipLaunchKernelGGL(rrt_pose_relax_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv);
+    else hipLaunchKernelGGL(rrt_relax_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv);
     hipLaunchKernelGGL(rrt_reroot_link_kernel, dim3(wgs(j, REROOT_TPB)), dim3(REROOT_TPB), 0, ctx->stream, rv);
     HIPCHK(ctx, time.mark(3, ctx->stream));
     unsigned long long stats[RELAX_STATS] = {0, 0, 0, 0};
     char what[256];
     snprintf(what, sizeof what, "the relaxed parents of query %d on the device are not a tree over all %d vertices, or its costs summed from the root "
              "down are not the fixpoint's", q, j);
-    const int rc = order_price_and_seed(who, b, q, rv, tmp, time, 3, true, false, what, [&] {
+    auto price = [&] {
+        if (!poses) return price_lines(ctx, rv);
+        // the j words in parallel (and the headings into the new order), then the sums level by level
+        hipLaunchKernelGGL(rrt_pose_relax_word_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv, rv, px.out_heading, px.word);
+        hipLaunchKernelGGL(rrt_pose_relax_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv, (const double *)px.word);
+    };
+    const int rc = order_price_and_seed(who, b, q, rv, tmp, time, 3, true, false, what, price, [&] {
         hipLaunchKernelGGL(rrt_relax_check_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv, (const int32_t *)tmp.src, (const double *)tmp.out_vcost,
                            (const int32_t *)(tmp.head + REROOT_COUNT));
         HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
         return (int)RRT_OK;
-    }, m, j0_out, old_id, log0);
+    }, m, j0_out, old_id, log0, poses ? px.out_heading : nullptr);
     if (rc != RRT_OK) return rc;
     b->relax_stats[0] = rounds;
     b->relax_stats[1] = (int64_t)stats[RELAX_FELL];
@@ -1007,28 +1042,67 @@ extern "C" int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count) {
 }
 
 extern "C" int rrt_batch_relax(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_relax("rrt_batch_relax", b, q, r2, samples_xy, m, j0, old_id, log0) : fail(nullptr, RRT_E_ARG, "rrt_batch_relax: NULL");
+    return b ? batch_relax("rrt_batch_relax", b, q, r2, samples_xy, m, j0, old_id, log0, false) : fail(nullptr, RRT_E_ARG, "rrt_batch_relax: NULL");
 }
 
-extern "C" int rrt_plan_relax(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    const char *who = "rrt_plan_relax";
+extern "C" int rrt_batch_relax_poses(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
+    return b ? batch_relax("rrt_batch_relax_poses", b, q, r2, samples_xyh, m, j0, old_id, log0, true) : fail(nullptr, RRT_E_ARG, "rrt_batch_relax_poses: NULL");
+}
+
+static int plan_relax(const char *who, rrt_ctx *ctx, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out, bool poses) {
     if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
     if (!s) return RRT_E_ARG;
     int32_t log0 = 0;
-    const int rc = batch_relax(who, s, 0, r2, samples_xy, m, j0, old_id, &log0);
+    const int rc = batch_relax(who, s, 0, r2, samples, m, j0, old_id, &log0, poses);
     return rc != RRT_OK ? rc : run_single(ctx, out);
 }
 
-// ms[0, 6): buckets, rounds, parents, alive and depth, order, costs; ms[6, 9): the seed's stages, as rrt_batch_grow_ms reports them
-extern "C" int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_relax_ms: NULL");
-    if (count < 1 || count > 9) return fail(b->ctx, RRT_E_ARG, "rrt_batch_relax_ms: count=%d, a relax has 6 stages and its seed 3", count);
+extern "C" int rrt_plan_relax(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    return plan_relax("rrt_plan_relax", ctx, r2, samples_xy, m, j0, old_id, out, false);
+}
+
+extern "C" int rrt_plan_relax_poses(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
+    return plan_relax("rrt_plan_relax_poses", ctx, r2, samples_xyh, m, j0, old_id, out, true);
+}
+
+// ms[0, 6): buckets, rounds, parents, alive and depth, order, costs; ms[6, 9): the seed's stages, as rrt_batch_grow_ms reports them.
+// A batch is a Dubins batch or not for life, so the timer and the counters of a batch belong to one of the two calls: `call` names it.
+static int relax_ms(const char *who, const char *call, rrt_batch *b, float *ms, int32_t count) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    if (count < 1 || count > 9) return fail(b->ctx, RRT_E_ARG, "%s: count=%d, a relax has 6 stages and its seed 3", who, count);
     if (!b->relax_time.ran || !b->seed_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "rrt_batch_relax_ms: no rrt_batch_relax on this batch yet, its last one failed, or a grow or a reroot came after it");
+        return fail(b->ctx, RRT_E_ARG, "%s: no %s on this batch yet, its last one failed, or a grow or a reroot came after it", who, call);
     HIPCHK(b->ctx, b->relax_time.read(ms, std::min(count, 6)));
     if (count > 6) HIPCHK(b->ctx, b->seed_time.read(ms + 6, count - 6));
     return RRT_OK;
+}
+
+static int relax_stats(const char *who, const char *call, rrt_batch *b, int64_t out[4]) {
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    if (!b->relax_time.ran) return fail(b->ctx, RRT_E_ARG, "%s: no %s on this batch yet, its last one failed, or a grow or a reroot came after it", who, call);
+    for (int k = 0; k < 4; ++k) out[k] = b->relax_stats[k];
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count) { return relax_ms("rrt_batch_relax_ms", "rrt_batch_relax", b, ms, count); }
+
+extern "C" int rrt_batch_relax_poses_ms(rrt_batch *b, float *ms, int32_t count) {
+    return relax_ms("rrt_batch_relax_poses_ms", "rrt_batch_relax_poses", b, ms, count);
+}
+
+extern "C" int rrt_plan_relax_poses_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_poses_ms", NO_PLAN);
+    return s ? rrt_batch_relax_poses_ms(s, ms, count) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_relax_poses_stats(rrt_batch *b, int64_t out[4]) {
+    return relax_stats("rrt_batch_relax_poses_stats", "rrt_batch_relax_poses", b, out);
+}
+
+extern "C" int rrt_plan_relax_poses_stats(rrt_ctx *ctx, int64_t out[4]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_poses_stats", NO_PLAN);
+    return s ? rrt_batch_relax_poses_stats(s, out) : RRT_E_ARG;
 }
 
 extern "C" int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count) {
@@ -1036,13 +1110,7 @@ extern "C" int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count) {
     return s ? rrt_batch_relax_ms(s, ms, count) : RRT_E_ARG;
 }
 
-extern "C" int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]) {
-    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_relax_stats: NULL");
-    if (!b->relax_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "rrt_batch_relax_stats: no rrt_batch_relax on this batch yet, its last one failed, or a grow or a reroot came after it");
-    for (int k = 0; k < 4; ++k) out[k] = b->relax_stats[k];
-    return RRT_OK;
-}
+extern "C" int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]) { return relax_stats("rrt_batch_relax_stats", "rrt_batch_relax", b, out); }
 
 extern "C" int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_stats", NO_PLAN);

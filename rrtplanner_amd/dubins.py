@@ -357,18 +357,22 @@ class _DubinsBase(RRT):
 
         RuntimeError / ValueError as connect_poses; ValueError when m does not fit (it names the room); IndexError as plan() when
         the goal pose is unreachable and rows are left (the grown tree stays resident)."""
+        return self._grow_poses_call("grow_poses", m, None)
+
+    def _grow_poses_call(self, who: str, m: int, r2):
+        """grow_poses (r2 is None) and relax_poses (r2: its threshold): the refusals of the classes, the draws and the context's call"""
         if self._custom_cost:
-            raise ValueError("grow_poses: the Dubins planners run with the arc-length cost on the device; a Python costfn has no tree there")
-        self._keep_guard("grow_poses", np.asarray(self.og).shape)
+            raise ValueError(f"{who}: the Dubins planners run with the arc-length cost on the device; a Python costfn has no tree there")
+        self._keep_guard(who, np.asarray(self.og).shape)
         m = int(m)
         if m < 0:
-            raise ValueError(f"grow_poses: m={m}")
+            raise ValueError(f"{who}: m={m}")
         ctx = self._device()
-        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow_poses(), or the alive ones of the last keep_pose_tree
+        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow_poses() / relax_poses(), or the alive ones of the last keep_pose_tree
         if j0 == 0:
-            raise ValueError("grow_poses: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
+            raise ValueError(f"{who}: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
         if j0 + m > int(self.n):
-            raise ValueError(f"grow_poses: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
+            raise ValueError(f"{who}: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
         cells = hostprep.draw_free_samples(self.rand_gen, self.free, m)
         headings = self.rand_gen.integers(0, self.n_headings, size=m)
         samples = np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), headings])
@@ -376,13 +380,15 @@ class _DubinsBase(RRT):
         try:
             self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
             try:
-                rc, res, j0, old_id = ctx.grow_poses(samples, int(self.n))
+                rc, res, j0, old_id = ctx.grow_poses(samples, int(self.n)) if r2 is None else ctx.relax_poses(r2, samples, int(self.n))
             except _ffi.RRTError as e:
                 if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
                     self._tree_resident = "device"
                 raise
             self._tree_resident = "device"
             self.last_grow_ids = old_id
+            if r2 is not None:
+                self.last_relax = ctx.relax_poses_stats()
             self._grow_j0 = int(res.j)
             self.last_stats = {k: getattr(res, k) for k in ("j", "sum_j", "sum_cells_nn", "sum_near", "sum_cells_cand", "n_los_cand")}
             if rc == _ffi.RRT_E_GOAL_UNREACHABLE:  # (as plan(): the grown tree is complete and resident all the same)
@@ -395,6 +401,31 @@ class _DubinsBase(RRT):
             if bar is not None:
                 bar.close()
         return out
+
+    def relax_poses(self, r: float = None, m: int = 0) -> Tuple[nx.DiGraph, int]:
+        """Choose every parent of the Dubins tree of the last plan() again (rrt_plan_relax_poses): the vertices and their poses stay,
+        and the tree becomes the shortest-path tree from its root over the directed graph of its own poses.  RRTDubins takes the
+        nearest vertex as parent and RRTStarDubins chooses among earlier vertices only and never rewires, so their trees are far
+        from it.  The word between two poses depends on the two poses alone, so it does not change with the parent's own parent.
+
+        The candidate parents of a vertex are the vertices within r cells (d2 < hostprep.radius_threshold(r)) whose shortest Dubins
+        word to it is free on the current grid, swept as plan(), connect_poses and keep_pose_tree sweep, and its old parent, however
+        far.  cost[v] = min cost[u] + length of the word u -> v in the loop's own f64 sum; among the parents that give a vertex its
+        cost the smallest (cost, number) wins.  The vertices are renumbered by (depth, previous number), then m more pose samples are
+        spent exactly as grow_poses(m) spends them, and the goal decision connects plan()'s xgoal.
+
+        r defaults to self.r_rewire; RRTDubins has none and must pass it.  Returns (T, gv) as grow_poses.  self.last_grow_ids[k] is
+        the number vertex k had before the call; self.last_relax holds dict(rounds, fell, sweeps, words): rounds run, vertices whose
+        cost fell, sweeps run, words evaluated.  connect_poses, paths_to_poses, routes_to_poses, keep_pose_tree, grow_poses and a
+        further relax_poses work on the result in its new numbering.  Raises as grow_poses; ValueError for a missing or
+        non-positive r."""
+        if r is None:
+            r = getattr(self, "r_rewire", None)
+        if r is None:
+            raise ValueError("relax_poses: this planner has no r_rewire: pass r, the radius of the candidate edges in cells")
+        if not (float(r) > 0):
+            raise ValueError(f"relax_poses: r={r}")
+        return self._grow_poses_call("relax_poses", m, hostprep.radius_threshold(r))
 
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""

@@ -500,7 +500,7 @@ class RRT(object):
         self._grid_dirty = True
         self.device_id = 0
         self.last_stats = None
-        self.last_relax = None  # dict(rounds, fell, los, priced) of the last relax()
+        self.last_relax = None  # dict(rounds, fell, los, priced) of the last relax(); dict(rounds, fell, sweeps, words) of the last relax_poses()
         self.last_route = None  # which way the last plan() went: "kernel", "kernel-large" (grids up to 4096 x 4096) or "host" (hostloop.py)
         self._tree_resident = None  # connect_goals: "device" while the tree of the last plan() is on the device for this grid and n, "host" after the host route
 
@@ -781,6 +781,10 @@ class RRT(object):
     def grow_poses(self, m: int):
         raise ValueError("grow_poses: this planner's samples are cells and its edges straight lines: use grow (pose samples belong to "
                          "RRTDubins and RRTStarDubins)")
+
+    def relax_poses(self, r=None, m=0):
+        raise ValueError("relax_poses: this planner's vertices are cells and its edges straight lines: use relax (poses belong to RRTDubins "
+                         "and RRTStarDubins)")
 
     def device_context(self) -> "_ffi.Context":
         """The planner's device context (created on demand, without uploading a grid)."""
