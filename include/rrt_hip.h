@@ -363,7 +363,8 @@ int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]);
 int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0);
 /* kernel time in ms of the seed's stages of the last successful rrt_batch_grow on this batch, from events on the stream: ms[0]
  * renumbering and node slots, ms[1] the `sampled` bitmap, ms[2] the cell records; the first `count` (1 .. 3) are written.
- * RRT_E_ARG when there is none. */
+ * RRT_E_ARG when there is none, or after a later rrt_batch_reroot or rrt_batch_relax (their seed's times are theirs to report): of
+ * the three timing calls only the one of the last seed call that ran answers. */
 int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count);
 /* rrt_batch_grow for a batch created with RRT_FLAG_DUBINS (Dubins-RRT and Dubins-RRT*): samples_xyh holds m rows (x, y, h) of int32, a
  * cell and a heading index in [0, nh) of the query.  The seed is rrt_batch_grow's -- the alive vertices of the view that

@@ -1002,6 +1002,8 @@ extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
     if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
     if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
     if (!b->seed_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
+    if (b->reroot_time.ran || b->relax_time.ran)  // (the seed's times are that call's: rrt_batch_reroot_ms / rrt_batch_relax_ms report them)
+        return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: a reroot or a relax came after the last rrt_batch_grow on this batch");
     HIPCHK(b->ctx, b->seed_time.read(ms, count));
     return RRT_OK;
 }

@@ -259,6 +259,38 @@ def test_the_tree_calls_answer_on_the_rerooted_tree(gpu_ctx):
     b.close()
 
 
+def test_only_the_last_seed_calls_stage_times_answer(gpu_ctx):
+    """grow_ms is the last grow's alone: after a reroot or a relax the seed's times are that call's, which reroot_ms / relax_ms report.
+    (Every reroot and relax sequence of tests/test_tree_sequences_gpu.py meets it at its first reroot or relax that runs: grow_ms
+    answered with that call's seed.)"""
+    og8, xs, samples, n = tc.sized(65, 165)
+    c = tc.oracle_case(og8, 0, n, xs, (63, 63), samples, 0)
+    b = tc.shaped_batch(gpu_ctx, c, "team")
+    _planned_tree(b, 0, c)
+
+    def answers():
+        out = set()
+        for name, call in (("grow", b.grow_ms), ("reroot", b.reroot_ms), ("relax", b.relax_ms), ("stats", b.relax_stats)):
+            try:
+                call()
+                out.add(name)
+            except _ffi.RRTError as e:
+                assert e.code == _ffi.RRT_E_ARG, e
+        return out
+
+    assert answers() == set()
+    for call, want in ((lambda: b.grow(0, NONE), {"grow"}), (lambda: b.reroot(0, 7), {"reroot"}), (lambda: b.relax(0, tc.R2), {"relax", "stats"}),
+                       (lambda: b.reroot(0, 3), {"reroot"}), (lambda: b.grow(0, NONE), {"grow"})):
+        call()
+        assert answers() == want
+        tc.refused_with_code(_ffi.RRT_E_ARG, lambda: b.reroot(0, 65))  # a refusal changes nothing
+        assert answers() == want
+        b.launch()
+        b.sync()
+        assert answers() == want
+    b.close()
+
+
 # ------------------------------------------------------------------------------------------------ 6. refusals
 def _stands(answer, goals, before):
     after = answer(goals)

@@ -3,7 +3,8 @@
 (a) every sequence exercises what it is for -- conditions on the model's own notes, met by the choice of the seeds and of the
     generator's blocks, so that a GPU run of the same seeds cannot pass on sequences that cut, grow or refuse nothing;
 (b) the model agrees with itself: every edge of a tree that answers is free on the active map, a keep directly after a grow keeps
-    everything, keeping for the first map again restores the first answers, and grows with nothing cut are the longer plan."""
+    everything, keeping for the first map again restores the first answers, and grows with nothing cut are the longer plan;
+(c) the same for the sequences with reroot and relax (treemodel.ROOT_SEEDS)."""
 import numpy as np
 import pytest
 
@@ -160,3 +161,116 @@ def test_a_chain_of_grows_with_nothing_cut_is_the_plan_over_all_samples(q):
     assert (t.j, t.found) == (ro.j, ro.found) and t.j > out["j0"] >= s.n - room
     assert np.array_equal(t.pts[:live], ro.pts[:live]) and np.array_equal(t.parent[:live], ro.parent[:live])
     assert np.array_equal(np.ascontiguousarray(t.vcost[:live]).view(np.int64), np.ascontiguousarray(ro.vcost[:live]).view(np.int64))
+
+
+# ------------------------------------------------------------------------------------------------ (c) the sequences with reroot and relax
+WORDS = ("no query set", "not launched", "replaced", "nothing to grow from", "room for", "has the vertices [0,", "is not alive", "r2=")  # the refusals of reroot and relax, in the engine's order
+
+
+def _seed_calls(notes, how):
+    return [n for n in notes if n["kind"] in tm.SEED_OPS and not n["refused"] and n["how"] == how]
+
+
+@pytest.mark.parametrize("seed", tm.ROOT_SEEDS)
+def test_the_reroot_and_relax_sequence_exercises_what_it_is_for(seed):
+    steps, notes = tm.trace(seed)
+    assert len(steps) == len(notes) >= 40
+    assert sum(n["refused"] for n in notes) <= 0.30 * len(notes)
+    assert sum(0.05 <= n["cut"] <= 0.95 for n in notes if n["kind"] == "keep" and not n["refused"]) >= 3
+    reroots, relaxes = _seed_calls(notes, "reroot"), _seed_calls(notes, "relax")
+    assert sum(n["root"] != 0 for n in reroots) >= 2 and sum(n["root"] != 0 and n["view"] and n["m"] > 0 for n in reroots) >= 1
+    assert sum(n["fell"] > 0 for n in relaxes) >= 2 and sum(n["fell"] > 0 and n["j0"] > 1024 for n in relaxes) >= 1
+    assert any("reroot" in n["on"] for n in relaxes) and any("relax" in n["on"] for n in reroots)
+    assert any(n["fell"] == 0 for n in relaxes)  # the second of two relaxes with one radius
+    assert any(n["m"] > 0 and n["j0"] + n["m"] == n["n"] for n in relaxes)  # exactly the room
+    refused = {(s.op[0], s.expect.word) for s in steps if isinstance(s.expect, tm.Refusal)}
+    assert {w for _, w in refused} >= set(WORDS) | {"seeded"}
+    assert ("reroot", "replaced") in refused and ("relax", "room for") in refused and ("relax", "nothing to grow from") in refused
+    # the finished-tree gate: no query set, a query that is set, one that is armed -- each for both calls
+    assert {("reroot", "no query set"), ("relax", "no query set"), ("reroot", "not launched"), ("relax", "not launched"), ("relax_arm", "not launched")} <= refused
+    armed = [k for k, s in enumerate(steps) if s.op[0] == "arm" and not isinstance(s.expect, tm.Refusal)]
+    assert any(steps[k + 1].op[0] == "reroot" and steps[k + 1].op[2] == steps[k].op[2] and isinstance(steps[k + 1].expect, tm.Refusal) for k in armed)
+    # r2 <= 0 together with too many samples: the room wins
+    assert any(s.op[0] == "relax" and s.op[3] <= 0 and isinstance(s.expect, tm.Refusal) and s.expect.word == "room for" for s in steps)
+    # the room is checked with the vertices before the call: refused for one sample more, though the reroot that follows cuts vertices
+    at = [k for k, n in enumerate(notes) if n.get("behind", 0) > 0 and n["refused"]]
+    assert at and all(steps[k].expect.word == "room for" and not notes[k + 1]["refused"] and notes[k + 1]["j0"] < notes[k + 1]["count"] and
+                      notes[k + 1]["j0"] + len(steps[k].op[4]) <= notes[k + 1]["n"] for k in at)
+    # rearm + launch from a moved root
+    assert any(a["kind"] == "rearm" and any(n.get("moved") for n in notes[k + 1:k + 4] if n["kind"] == "launch") for k, a in enumerate(notes))
+    # armed on one map, launched on another: both calls armed, the launch refused
+    at = [k for k, s in enumerate(steps) if s.op[0] == "launch" and isinstance(s.expect, tm.Refusal)]
+    assert at and {s.op[0] for s in steps[:at[0]]} >= {"reroot_arm", "relax_arm"}
+    # the old start's cell blocked: the re-rooted tree keeps vertices, a tree that starts there keeps none
+    root_map = [n for n in notes if n["kind"] == "keep" and not n["refused"] and n["map"] == tm.MAP_ROOT]
+    assert any(n["alive"] > 0 for n in root_map) and any(n["alive"] == 0 for n in root_map)
+    # which timer answers changes hands
+    assert {s.timed[0][0] for s in steps if s.timed[0]} == {"grow", "reroot", "relax"}
+
+
+def test_some_reroot_drops_vertices_behind_a_blocked_reversed_edge():
+    """j0 smaller than the count the room was checked with"""
+    cut = [(seed, n["count"], n["j0"]) for seed in tm.ROOT_SEEDS for n in _seed_calls(tm.trace(seed)[1], "reroot") if n["j0"] < n["count"]]
+    assert len(cut) >= 1, cut
+
+
+def test_the_reroot_and_relax_sequences_in_turns():
+    steps, notes = tm.interleaved(*tm.ROOT_PAIR, tm.ROOT_PAIR_OPS)
+    words = [s.expect.word for s in steps if isinstance(s.expect, tm.Refusal)]
+    assert words.count("replaced") >= 4 and len(words) <= 0.30 * len(steps)
+    assert len([n for n in _seed_calls(notes, "reroot") if n["root"] != 0]) >= 4 and len([n for n in _seed_calls(notes, "relax") if n["fell"] > 0]) >= 4
+    assert {op[1] for op in (s.op for s in steps) if op[0] != "set_grid"} == {0, 1}
+    assert {t[0] for s in steps for t in s.timed if t} == {"grow", "reroot", "relax"}
+
+
+@pytest.mark.parametrize("seed", tm.ROOT_ONE_SEEDS)
+def test_the_single_query_reroot_and_relax_sequence_exercises_what_it_is_for(seed):
+    steps, notes = tm.trace_one(seed)
+    assert sum(n["refused"] for n in notes) <= 0.30 * len(notes)
+    reroots, relaxes = _seed_calls(notes, "reroot"), _seed_calls(notes, "relax")
+    assert sum(n["root"] != 0 and n["view"] for n in reroots) >= 2 and sum(n["root"] != 0 and not n["view"] for n in reroots) >= 2
+    assert sum(n["fell"] > 0 for n in relaxes) >= 3 and any("reroot" in n["on"] for n in relaxes) and any("relax" in n["on"] for n in reroots)
+    assert any(n["m"] > 0 for n in reroots) and any(n["m"] > 0 for n in relaxes)
+    words = {s.expect.word for s in steps if s.op[0] in ("reroot1", "relax1") and isinstance(s.expect, tm.Refusal)}
+    assert words >= {"replaced", "nothing to grow from", "is not alive"}
+    assert sum(0.05 <= n["cut"] <= 0.95 for n in notes if n["kind"] == "keep") >= 3
+    assert {s.op[2]["alg"] for s in steps if s.op[0] == "plan"} == {0, 1}
+    # a refused call draws nothing from the planner's stream
+    for a, b in zip(steps, steps[1:]):
+        if b.op[0] in ("reroot1", "relax1", "grow1") and isinstance(b.expect, tm.Refusal):
+            assert a.draws_state == b.draws_state
+
+
+def test_replay_rebuilds_a_prefix_of_a_reroot_and_relax_sequence():
+    seed = tm.ROOT_SEEDS[1]
+    steps, _ = tm.trace(seed)
+    m, part = tm.replay(seed, 10)
+    assert len(part) == 10 and all(a.op is b.op and type(a.expect) is type(b.expect) and a.timed == b.timed for a, b in zip(part, steps))
+
+
+@pytest.mark.parametrize("seed", tm.ROOT_SEEDS)
+def test_every_edge_of_a_rerooted_or_relaxed_tree_that_answers_is_free_on_the_active_map(seed):
+    """over the states the model recorded while the sequence was drawn (notes[k]["answers"]): no second replay"""
+    _, notes = tm.trace(seed)
+    maps = tm.workload()[0]
+    seen = 0
+    for n in notes:
+        for t, view, k in n["answers"]:
+            assert _edges_free(maps[k], t, view)
+            seen += 1
+    assert seen >= 15
+
+
+@pytest.mark.parametrize("seed", tm.ROOT_SEEDS)
+def test_a_reroot_puts_the_vertex_first_and_prices_it_zero(seed):
+    """after a reroot at r, pts[0] is the old pts[r] and vcost[0] == 0.0; a relax leaves the root where it is"""
+    steps, _ = tm.trace(seed)
+    hits = 0
+    for before, st in zip(steps, steps[1:]):
+        if st.op[0] in ("reroot", "relax") and not isinstance(st.expect, tm.Refusal):
+            old, new = before.after[st.op[1]][st.op[2]][0], st.expect["tree"]
+            r = st.op[3] if st.op[0] == "reroot" else 0
+            assert np.array_equal(new.pts[0], old.pts[r]) and new.vcost[0] == 0.0 and new.parent[0] == -1 and st.expect["old_id"][0] == r
+            assert st.expect["j0"] == len(st.expect["old_id"]) <= new.j
+            hits += 1
+    assert hits >= 10

@@ -1,11 +1,14 @@
-"""GPU: long mixed histories of keep_tree / grow / connect_goals / routes / rearm / set_query / set_grid on one batch, replayed against
+"""GPU: long mixed histories of keep_tree / grow / reroot / relax / connect_goals / routes / rearm / set_query / set_grid on one batch, replayed against
 the host model of tests/treemodel.py -- the orders nobody scripted.
 
 After every operation the answer (or the refusal: code and one word of the message) is compared exactly, and then EVERY query of
 every batch is asked for its result and for a fixed goals call, which have to be what the model says: an operation must not change a
 query it did not name, whether it succeeded or was refused.  The first mismatch ends the sequence; its message names the sequence, the
 driver and the operation, and treemodel.replay(seed, upto) rebuilds that prefix on the CPU.  tests/test_tree_sequences_cpu.py holds the
-same seeds to the conditions that make the sequences worth running."""
+same seeds to the conditions that make the sequences worth running.  After every grow, reroot or relax, refused or not, the batch is
+also asked for the stage times of all three and for the relax counters: only those of the last such call that ran answer."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -57,6 +60,32 @@ def _same_routes(got, want):
     assert len(got) == len(want) == 6
     for k, (x, y) in enumerate(zip(got, want)):
         assert np.array_equal(bits(x), bits(y)) if k in (1, 2) else np.array_equal(x, y), k
+
+
+def _seeded(got, want):
+    """what a grow, a reroot or a relax call answered: (j0, old_id, log0)"""
+    assert got[0] == want["j0"] and got[2] == want["log0"] and np.array_equal(got[1], want["old_id"])
+
+
+def _timers(o, timed):
+    """`o` (a Batch or a Context) is asked for the stage times of all three seed calls and for the relax counters: only those of the
+    last seed call that ran answer -- timed = (call, the relax's fell, its j0), None: no seed call has run --, the others are refused"""
+    how = timed[0] if timed else None
+    for name, stages in (("grow", 3), ("reroot", 8), ("relax", 9)):
+        got = _call(getattr(o, name + "_ms"))
+        if name == how:
+            assert not isinstance(got, _ffi.RRTError) and len(got) == stages and all(t >= 0.0 for t in got), f"{name}_ms after a {how}: {got}"
+        else:
+            assert isinstance(got, _ffi.RRTError) and got.code == _ffi.RRT_E_ARG, f"{name}_ms answers after a {how}: {got}"
+    st = _call(o.relax_stats)
+    if how == "relax":
+        assert not isinstance(st, _ffi.RRTError) and st["fell"] == timed[1] and 1 <= st["rounds"] <= max(timed[2], 1), (st, timed)
+    else:
+        assert isinstance(st, _ffi.RRTError) and st.code == _ffi.RRT_E_ARG, f"relax_stats answers after a {how}: {st}"
+
+
+POSE = np.array([(5, 5, 0)], dtype=np.int32)  # a pose for the Dubins calls that a straight-line batch refuses
+RADIUS = {hostprep.radius_threshold(r): r for r in tm.RELAX_R}  # the planner classes take the radius, the calls its threshold
 
 
 class BatchDriver:
@@ -111,14 +140,18 @@ class BatchDriver:
             got = _call(lambda: b.keep_tree(op[2]))
             if not _answered(got, want):
                 assert got.dtype == bool and np.array_equal(got, want)
-        elif kind in ("arm", "grow"):
-            got = _call(lambda: b.grow(op[2], op[3]))
+        elif kind in tm.SEED_OPS:
+            call = tm.ARMS.get(kind, kind)
+            got = _call(lambda: getattr(b, call)(*op[2:]))  # grow(q, samples), reroot(q, root, samples), relax(q, r2, samples)
             if not _answered(got, want):
-                assert got[0] == want["j0"] and got[2] == want["log0"] and np.array_equal(got[1], want["old_id"])
-                if kind == "grow":
+                _seeded(got, want)
+                if kind not in tm.ARMS:
                     self._launch(b)
                     self._launched(b, True)
                     _same_tree(b.get_result(op[2]), want["tree"])
+        elif kind == "pose_calls":
+            _answered(_call(lambda: b.relax_poses(op[2], tm.R2, POSE)), want)
+            _answered(_call(lambda: b.connect_poses(op[2], POSE)), want)
         elif kind == "goals":
             got = _call(lambda: b.connect_goals(op[2], op[3]))
             if not _answered(got, want):
@@ -129,6 +162,10 @@ class BatchDriver:
                 _same_routes(got, want)
         else:
             raise ValueError(kind)
+
+    def timers(self, op, timed):
+        if op[0] in tm.SEED_OPS:
+            _timers(self.b[op[1]], timed[op[1]])
 
     def everyone(self, after, probe):
         """every query of every batch: its result and the probe goals call, as the model has them after the operation"""
@@ -151,6 +188,7 @@ def _replay(driver, steps, label):
         for k, st in enumerate(steps):
             try:
                 driver.step(st.op, st.expect)
+                driver.timers(st.op, st.timed)
                 driver.everyone(st.after, tm.PROBE)
             except AssertionError as e:
                 raise AssertionError(f"{label}, operation {k} {st.op[:3]!r}: {e}") from None
@@ -191,6 +229,7 @@ class ContextDriver:
             s = op[2]
             ctx.set_grid(self.maps[op[1]])
             qu, keep = _ffi.make_query(s["alg"], s["n"], self.xs, s["xg"], s["samples"], r2_rewire=tm.R2 if s["alg"] else 0)
+            self.n = s["n"]  # (the tree calls of the context take the n of its plan)
             rc, res = ctx.plan(qu, s["n"], logs=True)
             assert rc == want.status
             _same_tree(res, want)
@@ -199,11 +238,20 @@ class ContextDriver:
             got = ctx.keep_tree()
             assert got.dtype == bool and np.array_equal(got, want)
         elif kind == "grow1":
-            got = _call(lambda: ctx.grow(op[1], tm._GenOne.N1, logs=True))
+            got = _call(lambda: ctx.grow(op[1], self.n, logs=True))
             if not _answered(got, want):
                 rc, res, j0, old_id = got
                 assert rc == want["tree"].status and j0 == want["j0"] and np.array_equal(old_id, want["old_id"])
                 _same_tree(res, want["tree"])
+        elif kind in ("reroot1", "relax1"):
+            got = _call(lambda: getattr(ctx, kind[:-1])(op[1], op[2], self.n, logs=True))
+            if not _answered(got, want):
+                rc, res, j0, old_id = got
+                assert rc == want["tree"].status and j0 == want["j0"] and np.array_equal(old_id, want["old_id"])
+                _same_tree(res, want["tree"])
+        elif kind == "pose_calls1":
+            _answered(_call(lambda: ctx.relax_poses(tm.R2, POSE, self.n)), want)
+            _answered(_call(lambda: ctx.connect_poses(POSE)), want)
         elif kind == "goals1":
             got = _call(lambda: ctx.connect_goals(op[1]))
             if not _answered(got, want):
@@ -214,6 +262,11 @@ class ContextDriver:
                 _same_routes(got, want)
         else:
             raise ValueError(kind)
+
+    def timers(self, op, timed):
+        """(the context's own batch outlives a test: what it answers before the sequence's first seed call has run is another test's)"""
+        if op[0] in ("grow1", "reroot1", "relax1") and timed[0]:
+            _timers(self.ctx, timed[0])
 
     def everyone(self, after, probe):
         got = _call(lambda: self.ctx.connect_goals(probe))
@@ -237,6 +290,7 @@ class PlannerDriver:
         self.maps, self.xs, _ = tm.workload()
         self.p = None
         self.draws_state = None
+        self.seeded = False
 
     def close(self):
         self.p = None
@@ -264,7 +318,7 @@ class PlannerDriver:
     def _refused_by_class(self, call, want):
         with pytest.raises((ValueError, RuntimeError)) as e:
             call()
-        if want.word in ("room for", "nothing to grow from"):
+        if want.word in ("room for", "nothing to grow from", "is not alive", "has the vertices [0,"):
             assert want.word in str(e.value), e.value
 
     def step(self, op, want):
@@ -277,6 +331,7 @@ class PlannerDriver:
             if type(self.p) is not cls:
                 self.p = cls(self._og(op[1]), s["n"], tm.RR, pbar=False) if s["alg"] else cls(self._og(op[1]), s["n"], pbar=False)
                 self.p.rand_gen.bit_generator.state = s["draws_state"]
+                self.seeded = False  # (a new planner has a context of its own: no seed call has run on it)
             else:
                 self.p.set_og(self._og(op[1]))
                 self.p.set_n(s["n"])
@@ -290,6 +345,19 @@ class PlannerDriver:
             else:
                 self._run(lambda: self.p.grow(len(op[1])), want["tree"])
                 assert np.array_equal(self.p.last_grow_ids, want["old_id"])
+        elif kind in ("reroot1", "relax1"):
+            call = (lambda: self.p.reroot(op[1], len(op[2]))) if kind == "reroot1" else (lambda: self.p.relax(RADIUS[op[1]], len(op[2])))
+            if isinstance(want, tm.Refusal):
+                self._refused_by_class(call, want)
+            else:
+                self._run(call, want["tree"])
+                assert np.array_equal(self.p.last_grow_ids, want["old_id"])
+                if kind == "relax1":
+                    assert self.p.last_relax["fell"] == want["fell"] and 1 <= self.p.last_relax["rounds"] <= max(want["j0"], 1)
+        elif kind == "pose_calls1":
+            for call in (lambda: self.p.relax_poses(tm.RR, 1), lambda: self.p.connect_poses(POSE)):
+                with pytest.raises(ValueError):
+                    call()
         elif kind == "goals1":
             if isinstance(want, tm.Refusal):
                 self._refused_by_class(lambda: self.p.connect_goals(op[1]), want)
@@ -307,6 +375,11 @@ class PlannerDriver:
         else:
             raise ValueError(kind)
 
+    def timers(self, op, timed, ran):
+        self.seeded = self.seeded or ran
+        if op[0] in ("grow1", "reroot1", "relax1") and self.seeded:
+            _timers(self.p.device_context(), timed[0])
+
     def everyone(self, after, probe):
         want = after[0][0][1]
         if isinstance(want, tm.Refusal):
@@ -316,20 +389,49 @@ class PlannerDriver:
         assert self.p.rand_gen.bit_generator.state == self.draws_state, "the planner's stream is not where the sequence's draws stand"
 
 
-@pytest.mark.parametrize("seed", tm.ONE_SEEDS[2:])
-def test_a_sequence_on_the_planner_classes(seed):
+def _replay_on_the_planner_classes(seed):
     steps, _ = tm.trace_one(seed)
     d = PlannerDriver()
     for k, st in enumerate(steps):
         try:
             d.draws_state = st.draws_state
             d.step(st.op, st.expect)
+            d.timers(st.op, st.timed, st.op[0] in ("grow1", "reroot1", "relax1") and not isinstance(st.expect, tm.Refusal))
             d.everyone(st.after, tm.PROBE)
         except AssertionError as e:
             raise AssertionError(f"single-query sequence {seed} through the planner classes (treemodel.trace_one({seed})), operation {k} {st.op[:2]!r}: {e}") from None
 
 
-# ------------------------------------------------------------------------------------------------ 5. armed on one map, launched on another
+@pytest.mark.parametrize("seed", tm.ONE_SEEDS[2:])
+def test_a_sequence_on_the_planner_classes(seed):
+    _replay_on_the_planner_classes(seed)
+
+
+# ------------------------------------------------------------------------------------------------ 5. the sequences with reroot and relax
+@pytest.mark.parametrize("shape, seed", list(zip(SHAPES, itertools.cycle(tm.ROOT_SEEDS))))
+def test_a_reroot_and_relax_sequence_on_one_batch(gpu_ctx, shape, seed):
+    steps, _ = tm.trace(seed)
+    _replay(BatchDriver(gpu_ctx, 1, shape), steps, f"sequence {seed} on a batch of shape {shape} (treemodel.replay({seed}, k + 1))")
+
+
+def test_two_batches_take_turns_with_reroot_and_relax(gpu_ctx):
+    a, b = tm.ROOT_PAIR
+    steps, _ = tm.interleaved(a, b, tm.ROOT_PAIR_OPS)
+    _replay(BatchDriver(gpu_ctx, 2, "team"), steps, f"sequences {a} and {b} in turns on two batches (treemodel.interleaved({a}, {b}, {tm.ROOT_PAIR_OPS}))")
+
+
+@pytest.mark.parametrize("seed", tm.ROOT_ONE_SEEDS)
+def test_a_reroot_and_relax_sequence_on_the_contexts_own_batch(gpu_ctx, seed):
+    steps, _ = tm.trace_one(seed)
+    _replay(ContextDriver(gpu_ctx), steps, f"single-query sequence {seed} through Context (treemodel.trace_one({seed}))")
+
+
+@pytest.mark.parametrize("seed", tm.ROOT_ONE_SEEDS)
+def test_a_reroot_and_relax_sequence_on_the_planner_classes(seed):
+    _replay_on_the_planner_classes(seed)
+
+
+# ------------------------------------------------------------------------------------------------ 6. armed on one map, launched on another
 def _grown(n, g, j0):
     return tm.Tree(n, g.pts, g.parent, g.vcost, g.j, g.found, g.vgoal, g.status, g.sum_j, g.sum_near, j0, g.nearest_log, g.accept_log, g.jlog)
 
