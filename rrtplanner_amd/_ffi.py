@@ -803,8 +803,8 @@ class Batch:
         return g.value, f.value
 
     def team_info(self):
-        """dict: workers per query at creation / of the last launch, hand-off timeouts, launches that ran a smaller team because
-        other launches held compute units of the device"""
+        """dict: workers per query at creation / of the last launch (128 = two shifts of 64), hand-off timeouts, launches that ran
+        fewer workers than `created` (a smaller team, or one shift of two) because other launches held compute units of the device"""
         out = (C.c_int32 * 4)()
         _check(self.ctx.handle, lib().rrt_batch_team_info(self._h, C.byref(out)))
         return dict(created=out[0], last=out[1], timeouts=out[2], shrunk=out[3])

@@ -346,12 +346,20 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
     const int g = ROLE == ROLE_COMMIT ? 0 : g_;
     if (ROLE == ROLE_WORK) __builtin_assume(g > 0);
     const bool worker = !PIPE || ROLE == ROLE_WORK;  // scans and resolves samples (a pipelined team's member 0 only commits)
-    const int wg = PIPE ? (ROLE == ROLE_COMMIT ? 0 : g - 1) : g;  // which BSM samples of a super-block this workgroup owns (a committer: none)
+    // shifts (a split team of 64 workers on a batch without Informed queries, when the engine says so): SH * G workers, members
+    // 1 .. G take blocks 1, 3, 5, ... and members G + 1 .. 2 G blocks 2, 4, 6, ...  Which tree a block is resolved against does not
+    // change (the one after commit b - 1 - LAG), so a worker has SH periods of the ring for a block instead of one.
+    const int SH = (PIPE && !INF && G == TEAM_MAX && PipeShape<PIPE, INF, BSM>::LAG == 2 && bv.shifts == 2) ? 2 : 1;  // (every other variant: the constant 1)
+    const bool shift1 = ROLE == ROLE_WORK && g > G;  // a worker of the second shift
+    const int wg = PIPE ? (ROLE == ROLE_COMMIT ? 0 : (shift1 ? g - 1 - G : g - 1)) : g;  // which BSM samples of a super-block this workgroup owns (a committer: none)
     QDesc *D = bv.desc + q;
     if (D->status != ST_RUNNING) return;
     unsigned char *tb = (G > 1) ? bv.team + (size_t)q * TEAM_BYTES : nullptr;
     gu32 *const t_arrive = (gu32 *)(tb + TEAM_OFF_ARRIVE), *const t_go = (gu32 *)(tb + TEAM_OFF_GO), *const t_fail = (gu32 *)(tb + TEAM_OFF_FAIL);
     gu64 *const t_state = (gu64 *)(tb + TEAM_OFF_STATE), *const t_rec = (gu64 *)(tb + TEAM_OFF_REC);  // PIPE: NSLOT of each, by block number
+    gu32 *const t_arrive2 = (gu32 *)(tb + TEAM_OFF_ARRIVE2);                  // the second shift's arrival flags: member G + m at index m
+    auto my_arrive = [&]() -> gu32 * { return (gu32 *)(tb + (g > G ? TEAM_OFF_ARRIVE2 + 128 * (g - G) : TEAM_OFF_ARRIVE + 128 * g)); };  // this member's flag
+    auto arrive_of = [&](uint32_t ep) -> gu32 * { return (SH == 2 && (ep & 1u) == 0u) ? t_arrive2 : t_arrive; };  // the flags of the shift that owns block ep
     uint32_t epoch = 0;  // super-blocks of this launch so far
     // pre-scan (team members, RRTStandard / RRTStar): while member 0 commits block s, a member already scans the snapshot of
     // block s for the samples of block s + 1; after the commit only the steps that hold the new nodes are scanned again
@@ -654,6 +662,17 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
         // loads); the stores above bypass it, so drop it like every other member does when it takes the commit
         if (!grid_nn) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     };
+    if (PIPE && SH == 2) {
+        // the second shift starts with block 2: resolved against the initial tree with block 1 in flight, exactly as a single shift
+        // resolves it (block 1 is full when there is a block 2; a run of one block leaves the shift nothing to resolve)
+        if (shift1) {
+            if (wave == 0) xqp_lds[0][lane] = (i + lane < n) ? at32(samples, (uint32_t)(i + lane)) : 0u;
+            i += SB;
+            epoch = 1;
+            nprev = 1;
+        }
+        __syncthreads();
+    }
     while ((pipe_inf && g > 0) || i < n) {
         const int i0 = i, j0 = j;
         int nb = (n - i0) < SB ? (n - i0) : SB;  // samples of this (super-)block; lane s of every wave: sample s
@@ -756,7 +775,8 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
 
     // ---------------- the end of the run: member 0 finishes the query; a team shares go2goal ----------------
     constexpr uint32_t FINAL = 0x40000000u;   // "epoch" of the final hand-offs, above every block's
-    constexpr int NWG = G + (PIPE ? 1 : 0);   // workgroups of the team
+    constexpr int NW1 = G + (PIPE ? 1 : 0) - 1;  // members 1 .. NW1 answer to member 0 (with two shifts: G more)
+    const int NWG = NW1 + 1 + (SH - 1) * G;      // workgroups of the team
     if (team_failed) {
         if (G > 1 && g > 0) return;
         status = ST_TEAM_FAIL;
@@ -797,15 +817,16 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
         go2goal_phase<false, NTG>(og, H, nodes_g, vcost, g, NWG, cnt, xg, reinterpret_cast<uint32_t *>(clist_base), (RRT_LDS uint32_t *)smem, bslots, t, lane,
                                   wave, pc, pi);
         if (G > 1) {
-            gu64 *const t_res = (gu64 *)(tb + TEAM_OFF_RES);
+            gu64 *const t_res = (gu64 *)(tb + TEAM_OFF_RES), *const t_res2 = (gu64 *)(tb + TEAM_OFF_RES2);  // (the second shift's: member G + m at index m)
             if (g > 0) {
                 if (wave == 0) {
                     if (lane == 0) {
-                        __hip_atomic_store(t_res + 2 * g, (u64)__double_as_longlong(pc), RRT_RLX_AGENT);
-                        __hip_atomic_store(t_res + 2 * g + 1, (u64)pi, RRT_RLX_AGENT);
+                        gu64 *const mine = shift1 ? t_res2 + 2 * (g - G) : t_res + 2 * g;
+                        __hip_atomic_store(mine, (u64)__double_as_longlong(pc), RRT_RLX_AGENT);
+                        __hip_atomic_store(mine + 1, (u64)pi, RRT_RLX_AGENT);
                     }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0) __hip_atomic_store(t_arrive + 32 * g, FINAL, RRT_RLX_AGENT);
+                    if (lane == 0) __hip_atomic_store(my_arrive(), FINAL, RRT_RLX_AGENT);
                 }
 #ifdef RRT_STAMPS
                 if (PIPE && t == 0 && g == 1)
@@ -816,18 +837,27 @@ __device__ __forceinline__ void rrt_block_body(BatchView bv, BlockLds<G, BSM, PI
                 return;
             }
             if (wave == 0) {
-                const bool ok = team_wait_all(t_arrive, 1, NWG - 1, FINAL, t_fail, lane);
+                bool ok = team_wait_all(t_arrive, 1, NW1, FINAL, t_fail, lane);
+                if (ok && SH == 2) ok = team_wait_all(t_arrive2, 1, G, FINAL, t_fail, lane);  // (a wave has 64 lanes: one pass per shift)
                 double c = f64_inf();
                 uint32_t ci = NONE;
-                if (ok && lane < NWG - 1) {
+                if (ok && lane < NW1) {
                     c = __longlong_as_double((long long)__hip_atomic_load(t_res + 2 * (lane + 1), RRT_RLX_AGENT));
                     ci = (uint32_t)__hip_atomic_load(t_res + 2 * (lane + 1) + 1, RRT_RLX_AGENT);
                 }
-                if (lane == 63 && key_lt(pc, pi, c, ci)) {  // (NWG - 1 <= 64 members in lanes 0..NWG-2; this workgroup's own answer: lane 63 ...
+                if (ok && SH == 2 && lane < G) {  // lane l: the better of members 1 + l and G + 1 + l
+                    const double c2 = __longlong_as_double((long long)__hip_atomic_load(t_res2 + 2 * (lane + 1), RRT_RLX_AGENT));
+                    const uint32_t ci2 = (uint32_t)__hip_atomic_load(t_res2 + 2 * (lane + 1) + 1, RRT_RLX_AGENT);
+                    if (key_lt(c2, ci2, c, ci)) {
+                        c = c2;
+                        ci = ci2;
+                    }
+                }
+                if (lane == 63 && key_lt(pc, pi, c, ci)) {  // (NW1 <= 64 members in lanes 0..NW1-1; this workgroup's own answer: lane 63 ...
                     c = pc;
                     ci = pi;
                 }
-                if (NWG - 1 == 64) {  // ... unless all 64 lanes are taken: fold it in after the reduction)
+                if (NW1 == 64) {  // ... unless all 64 lanes are taken: fold it in after the reduction)
                     wave_min_f64_idx(c, ci);
                     if (key_lt(pc, pi, c, ci)) {
                         c = pc;
@@ -919,7 +949,7 @@ __global__ __launch_bounds__(TPB) void rrt_expand_block_kernel(BatchView bv) {
 // RRT_FLAG_ONEBODY keeps rrt_expand_block_kernel).  Register allocation is per kernel: the committer, a workgroup of 8 waves, gets
 // 256 vector registers instead of the 128 of a 16-wave workgroup, at which its half of the one-body kernel spills; the workers are
 // compiled without the committer's code.  The committer kernel has one workgroup per team (blockIdx.x = query slot), the workers'
-// kernel team_qpad * G of them, launched with bv.member0 = 1.
+// kernel team_qpad * G of them (team_qpad * 2 G with bv.shifts = 2), launched with bv.member0 = 1.
 template <int G, int BSM, bool INF>
 __global__ __launch_bounds__(512) void rrt_block_commit_kernel(BatchView bv) {
     __shared__ BlockLds<G, BSM, true, INF> L;

@@ -306,7 +306,7 @@
                 if (PIPE && prefetched) {  // wave 1 fetched them during the last commit
                     remote_ok = uni32(pre_state[bsel]) == 1u;
                 } else {
-                    remote_ok = team_wait_all(t_arrive, 1, PIPE ? G : G - 1, epoch, t_fail, lane);
+                    remote_ok = team_wait_all(PIPE ? arrive_of(epoch) : t_arrive, 1, PIPE ? G : G - 1, epoch, t_fail, lane);  // (the shift that owns the block)
                     if (PIPE) {
                         if (remote_ok) fetch_records(epoch, bsel);
                     } else if (remote_ok && lane >= BSM && lane < nb) {
@@ -513,7 +513,7 @@
                 const u64 t0w = wall_clock64();
                 u64 lastmiss = 0;
                 for (;;) {
-                    const bool mine = lane < G ? __hip_atomic_load(t_arrive + 32 * (1 + lane), RRT_RLX_AGENT) >= epoch + 1 : true;
+                    const bool mine = lane < G ? __hip_atomic_load(arrive_of(epoch + 1) + 32 * (1 + lane), RRT_RLX_AGENT) >= epoch + 1 : true;
                     const u64 miss = __ballot(!mine);
                     if (miss == 0) break;
                     if (!mine) D->dbg2[lane] += 1;
@@ -527,7 +527,7 @@
                 if (lastmiss != 0 && (lastmiss & (lastmiss - 1)) == 0 && ((lastmiss >> lane) & 1ull)) D->dbg2[64 + lane] += 1;
             }
 #else
-            const bool ok = team_wait_all(t_arrive, 1, G, epoch + 1, t_fail, lane);
+            const bool ok = team_wait_all(arrive_of(epoch + 1), 1, G, epoch + 1, t_fail, lane);
 #endif
 #ifdef RRT_STAMPS
             const unsigned long long pf1 = __builtin_amdgcn_s_memtime();

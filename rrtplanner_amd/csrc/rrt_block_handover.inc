@@ -14,8 +14,11 @@
             }
 #endif
             DBGT(0);
-            const bool more = i0 + nb < n;
-            const bool take = (int)epoch > LAG && (more || pipe_inf);  // there is a commit to take (an Informed worker always looks)
+            // this worker's next block: the one behind this one, or (two shifts) the one behind the other shift's, which is full if ours exists
+            const int i_next = i0 + nb + (SH - 1) * SB;
+            const bool more = i_next < n;
+            const uint32_t ep_take = epoch + (uint32_t)(SH - 1) - (uint32_t)LAG;  // the commit the next block is resolved against
+            const bool take = (int)epoch + SH - 1 > LAG && (more || pipe_inf);  // there is a commit to take (an Informed worker always looks)
             if (wave == 0) {
                 if (!void_blk) {
                     const RRT_LDS u64 *src = (const RRT_LDS u64 *)&brec[0][wg * BSM];
@@ -23,7 +26,7 @@
                     for (int w = lane; w < BSM * BREC_WORDS; w += 64) __hip_atomic_store(dst + w, src[w], RRT_RLX_AGENT);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the storing wave drains, then signals
                 }
-                if (lane == 0) __hip_atomic_store(t_arrive + 32 * g, epoch, RRT_RLX_AGENT);
+                if (lane == 0) __hip_atomic_store(my_arrive(), epoch, RRT_RLX_AGENT);
                 if (g == 1) TSMARK(epoch, 5);
                 if (g == 8) TSMARK(epoch, 8);
             }
@@ -32,7 +35,7 @@
             // nodes are left.
             pre_i = -1;
             if (!informed && more && !grid_nn) {
-                pre_i = i0 + nb;
+                pre_i = i_next;
                 pre_j = j0;
                 const int nbn = (n - pre_i) < SB ? (n - pre_i) : SB;
                 pre_xv = lane < nbn ? at32(samples, (uint32_t)(pre_i + lane)) : 0u;
@@ -49,9 +52,21 @@
             }
             if (wave == 0) {
                 bool ok = true;
+                // the next block's "previous" samples (a block that has a successor is full).  Written in front of the wait for go, not
+                // behind it as before, for every pipelined team: the last reads of xqp_lds are the owner phase's, in front of the barrier
+                // that precedes this hand-over, and the next ones are behind the barrier below, so the interval is the same and the
+                // stores no longer stand between go and the take
+                if (SH == 2) {  // this block, and in front of it the other shift's, which comes from the sample stream
+                    xqp_lds[NP - 1][lane] = xv;
+                    xqp_lds[0][lane] = more ? at32(samples, (uint32_t)(i0 + nb + lane)) : 0u;
+                } else {
+#pragma unroll
+                    for (int p2 = NP - 1; p2 > 0; --p2) xqp_lds[p2][lane] = xqp_lds[p2 - 1][lane];
+                    xqp_lds[0][lane] = xv;
+                }
                 DBGT(1);
                 if (take) {
-                    ok = team_wait(t_go, epoch - LAG, t_fail);
+                    ok = team_wait(t_go, ep_take, t_fail);
                     if (g == 1) TSMARK(epoch, 6);
                     if (g == 8) TSMARK(epoch, 9);
                     DBGT(2);
@@ -61,24 +76,23 @@
                     }
                 }
                 if (lane == 0) blk.pad0 = ok ? 0 : 1;
-#pragma unroll
-                for (int p2 = NP - 1; p2 > 0; --p2) xqp_lds[p2][lane] = xqp_lds[p2 - 1][lane];
-                xqp_lds[0][lane] = xv;  // the next block's "previous" samples (a block that has a successor is full)
             }
             __syncthreads();
             if (blk.pad0 != 0) {
                 team_failed = true;
                 break;
             }
-            i = i0 + nb;
-            nprev = void_blk ? 0 : (nprev < NP ? nprev + 1 : NP);
+            i = i_next;
+            nprev = void_blk ? 0 : (nprev + SH < NP ? nprev + SH : NP);  // (follows the block number, not the worker's own count)
             if (take) {
                 BlkWords u;
 #pragma unroll
-                for (int w = 0; w < 5; ++w) u.w[w] = __hip_atomic_load(t_state + (size_t)((epoch - LAG) % NSLOT) * 8 + w, RRT_RLX_AGENT);
+                // (two shifts: the state of epoch b - 1 only.  The slot of epoch b - 2 may hold epoch b + 1 by now, which needs only the other
+                //  shift's records; this one is rewritten by epoch b + 2, which needs this worker's own.  Up to 2 SB new nodes.)
+                for (int w = 0; w < 5; ++w) u.w[w] = __hip_atomic_load(t_state + (size_t)(ep_take % NSLOT) * 8 + w, RRT_RLX_AGENT);
                 if (pipe_inf && ((u.b.pad1 & ST_FLAG_STOP) != 0 || u.b.i >= n)) break;  // the run is over (or waits for the host)
                 const int jn = unis32(u.b.j);
-                if (t < jn - j0) {  // at most SB new nodes: append them to this CU's node cache and cell fill counts
+                if (t < jn - j0) {  // at most SH * SB new nodes (one pass of the 1 024 threads): append them to this CU's node cache and cell fill counts
                     const uint32_t Xn = ld_u32<COH>(&at32(nodes_g, (uint32_t)(j0 + t)));
                     if (j0 + t < lds_nodes) nodes_lds[j0 + t] = Xn;
                     if (cells_on) __hip_atomic_fetch_add(&cellcnt[cell_of(Xn)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -115,6 +129,7 @@
             if (wave == 0 && g == 1) TSMARK(epoch, 7);
             if (wave == 0 && g == 8) TSMARK(epoch, 10);
             DBGT(3);
+            epoch += (uint32_t)(SH - 1);  // (the other shift's block)
             continue;
         }
 

@@ -23,7 +23,8 @@
     constexpr bool GLIST = false;
     constexpr bool LDSLIST = BSM >= 16 || GLIST;
     constexpr uint32_t LCAP = BSM >= 16 ? (uint32_t)BLOCK_LIST_CAP : (uint32_t)(SB * BREC_WORDS * 8 / 16 / NWAVE);
-    const uint32_t clist_cap = (uint32_t)(bv.spill_stride / (2 * NWAVE * (G + (PIPE ? 1 : 0))));  // the engine sizes the spill area per team member
+    const uint32_t clist_cap = SH == 2 ? (uint32_t)(bv.spill_stride / (2 * NWAVE * (2 * G + 1)))  // the engine sizes the spill area per team member
+                                       : (uint32_t)(bv.spill_stride / (2 * NWAVE * (G + (PIPE ? 1 : 0))));
     u32x4 *const clist_base = reinterpret_cast<u32x4 *>(spill) + (size_t)(g * NWAVE) * (size_t)clist_cap;  // this member's 16 lists (and go2goal's scratch)
     u32x4 *const clist = clist_base + (size_t)wave * (size_t)clist_cap;
     RRT_LDS u32x4 *const clist_l =

@@ -87,6 +87,7 @@ struct BlockVariant;  // a row of the engine's table of team kernels (rrt_engine
 struct LaunchPlan {
     int team = 0;               // workers per query (1 after a hand-off timed out; 0: nothing launched yet)
     int qpad = 0;               // block = member * qpad + query
+    int shifts = 1;             // worker shifts of the split team of 64: 2 = 128 workers, each shift takes every other block
     bool pipe = false;          // the pipelined team kernel: one more workgroup per query, which only commits
     bool inf = false;           // the Informed instantiation
     bool wide = false;          // a team variant with more than 16 samples per member
@@ -180,6 +181,7 @@ struct RRT_PRIVATE StageTimer {
 struct rrt_batch {
     rrt_ctx *ctx = nullptr;
     int32_t Q = 0, n_cap = 0, node_stride = 0, bitmap_words = 0, lds_chunks = 1, spill_stride = 0;
+    int32_t spill_stride2 = 0;  // the stride a launch on two shifts carves the spill area by (129 members; 0: the batch has no room for two shifts)
     int32_t gridW = 0, gridH = 0;
     uint32_t flags = 0;
     bool use_block = false;     // block-parallel kernel (rrt_block.h) instead of the one-sample-per-iteration kernel
@@ -188,12 +190,14 @@ struct rrt_batch {
     int32_t blk_lds_chunks16 = 1; // ... and the kernels that also keep their parked-entry lists there
     int32_t team = 1;           // workgroups (CUs) per query of the block kernel that scan and resolve (rrt_block.h, teams)
     bool pipe_team = false;     // the team is pipelined: one more workgroup per query, which only commits
+    int32_t shifts_room = 1;    // fixed at rrt_batch_create: 2 = two shifts of `team` workers fit (no cap from the caller, a team of 64 + 1, 129 CUs per query)
+    int32_t shifts = 1;         // what a launch asks for and rrt_batch_team reports: shifts_room, or 1 while an Informed query is set (rrt_batch_set_query recomputes it)
     LaunchPlan last;            // the plan of the last launch
     int32_t team_fallbacks = 0; // launches repeated with one CU per query after a team hand-off timed out
     int32_t team_qpad = 0;      // Q rounded up to a multiple of 8: block = member * team_qpad + query
     int32_t team_want = TEAM_MAX;  // the caller's cap on the team size
     int32_t claimed_cus = 0;    // compute units this batch's launch in flight holds in the device's registry (0: nothing in flight)
-    int32_t shrunk = 0;         // launches that ran a smaller team than the batch was created with because other launches held CUs
+    int32_t shrunk = 0;         // launches that ran fewer workers than the batch was created with (a smaller team, or one shift of two) because other launches held CUs
     unsigned char *d_team = nullptr;  // [Q][TEAM_BYTES] sync words, state, exchanged records; zeroed before every launch
     QDesc *d_desc = nullptr;
     PinnedDescs h_desc;  // page-locked

@@ -399,8 +399,19 @@ extern "C" int rrt_batch_destroy(rrt_batch *b) {
 struct TeamShape {
     int team = 1, qpad = 0;
     bool pipe = false;
-    int cus() const { return team > 1 ? qpad * (team + (pipe ? 1 : 0)) : 0; }  // workgroups that must be resident together
+    int shifts = 1;  // worker shifts: 2 = twice the workers, each shift takes every other block (two_shifts_fit)
+    int cus() const { return team > 1 ? qpad * (team * shifts + (pipe ? 1 : 0)) : 0; }  // workgroups that must be resident together
 };
+// Two shifts of 64 workers and a committer per query, block = member * Q + query (stride Q: a single query's 128 workers are dealt
+// 16 to each of the 8 XCDs, and no workgroup of the launch is padding -- with the one-shift stride of 2 the launch would be 258
+// workgroups for 129 that stay).  Taken by a batch whose caller set no cap, when every such team is resident at once.
+#ifndef RRT_TWO_SHIFT_STRIDE
+#define RRT_TWO_SHIFT_STRIDE 1  // block = member * stride * Q + query.  2 (the one-shift team's placement: 32 workers on each of 4 XCDs, every other
+                                // workgroup of the launch padding) measured 7.32 ms against 7.26 for config 2: profiles/worker_shifts.md
+#endif
+static bool two_shifts_fit(int Q, bool capped, const TeamShape &one, int cus) {
+    return one.pipe && one.team == TEAM_MAX && !capped && Q * (2 * TEAM_MAX + 1) <= cus;
+}
 static TeamShape pick_team(int Q, int want, bool allow_pipe, int cus) {
     TeamShape t;
     t.qpad = (Q + 7) & ~7;
@@ -487,7 +498,12 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
         b->team = ts.team;
         b->team_qpad = ts.qpad;
         b->pipe_team = ts.pipe;
+        // (an explicit cap, team = 64 included, keeps one shift; so do RRT_FLAG_ONEBODY and, at the launch, Informed queries)
+        const bool capped = ((flags >> 8) & 0x7fu) != 0 || want < TEAM_MAX;
+        if (!(flags & RRT_FLAG_ONEBODY) && two_shifts_fit(Q, capped, ts, ctx->num_cu)) b->shifts = b->shifts_room = 2;
     }
+    // (a launch on two shifts carves the same area for 129 members: spill_stride2, which sizes it; every other launch sees the one-shift stride)
+    b->spill_stride2 = b->shifts_room == 2 ? chunks * CHUNK * (2 * b->team + 1) : 0;
     b->spill_stride = chunks * CHUNK * (b->team + 1);  // per member (and a pipelined team's committer): 256 parked entries per wave and node chunk; also go2goal's cost array
     {   // block kernel LDS: [node cache | cell fill counts 16 KiB | the waves' parked-entry lists 64 KiB (teams of up to 4 workers and
         // single CUs, where one wave resolves a sample: rrt_block.h LDSLIST)]
@@ -534,7 +550,7 @@ extern "C" int rrt_batch_create(rrt_ctx *ctx, int32_t Q, int32_t n_cap, uint32_t
     b->d_nodes = reinterpret_cast<uint32_t *>(b->d_slab + q * b->node_stride * sizeof(double));
     b->d_parent = reinterpret_cast<int32_t *>(b->d_slab + q * b->node_stride * (sizeof(double) + sizeof(uint32_t)));
     ALLOC(b->d_bitmap, q * b->bitmap_words * sizeof(uint32_t));
-    ALLOC(b->d_spill, q * b->spill_stride * sizeof(uint2));
+    ALLOC(b->d_spill, q * (size_t)std::max(b->spill_stride, b->spill_stride2) * sizeof(uint2));
     if (b->use_block || b->dub_block) {
         ALLOC(b->d_cellrec, q * (size_t)b->rec_stride * sizeof(uint4));
         ALLOC(b->d_cellcnt, q * (size_t)MAX_CELLS * sizeof(uint32_t));
@@ -661,6 +677,11 @@ extern "C" int rrt_batch_set_query(rrt_batch *b, int32_t q, const rrt_query *qu)
     const bool pipe1 = b->use_block && (b->team == 1 || two_cus_run_the_pipeline(b)) && !(b->flags & RRT_FLAG_NOPIPE1) && qu->alg != RRT_ALG_INFORMED;
     cell_geometry(W, H, (int64_t)d.r2_rewire, b->n_cap, pipe1 ? RRT_CELL_DIV_PIPE : RRT_CELL_DIV, d.cell_shift, d.ncx, d.ncy, d.cell_cap);
     arm_desc(d);
+    if (b->shifts_room == 2) {  // two shifts unless the batch holds an Informed query (those run the one-body kernel): what rrt_batch_team reports
+        bool inf = false;
+        for (const QDesc &o : b->h_desc) inf = inf || (o.status != ST_IDLE && o.alg == RRT_ALG_INFORMED);
+        b->shifts = inf ? 1 : 2;
+    }
     HIPCHK(ctx, hipMemcpyAsync(b->d_samples + (size_t)q * b->n_cap, b->stage.data(), (size_t)qu->n * sizeof(uint32_t),
                                hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
@@ -734,6 +755,7 @@ static BatchView make_view(rrt_batch *b) {
     v.team_qpad = b->team_qpad;
     v.team_fault = (b->flags & RRT_FLAG_TEAM_FAULT) ? 1 : 0;
     v.member0 = 0;
+    v.shifts = 1;
     if (b->d_kids) {
         const size_t qs = (size_t)b->Q * b->node_stride;
         v.kid_first = b->d_kids;
@@ -763,7 +785,7 @@ static size_t expand_lds_bytes(int lds_chunks) {
 // must be resident at once: a team takes the largest shape that fits next to the launches in flight on this device (other
 // batches, other contexts, other host threads of this process).  One CU per query needs no co-residency, but its workgroups occupy
 // CUs all the same.
-static TeamShape claim_cus(rrt_batch *b, int team) {
+static TeamShape claim_cus(rrt_batch *b, int team, int shifts = 1) {
     rrt_ctx *ctx = b->ctx;
     cu_release(ctx->device, b->claimed_cus);  // (a launch that was never synchronised)
     b->claimed_cus = 0;
@@ -771,6 +793,16 @@ static TeamShape claim_cus(rrt_batch *b, int team) {
     ts.team = team;
     ts.qpad = b->team_qpad;
     ts.pipe = b->pipe_team;
+    if (team > 1 && shifts == 2) {  // two shifts if they fit next to what is in flight; else one shift, then smaller teams as below
+        TeamShape two = ts;
+        two.shifts = 2;
+        two.qpad = b->Q * RRT_TWO_SHIFT_STRIDE;
+        const int stay = b->Q * (2 * team + 1);  // the workgroups that stay resident (a stride above 1 launches padding ones, which leave at once)
+        if (cu_claim(ctx->device, ctx->num_cu, stay, 0) < 0) {
+            b->claimed_cus = stay;
+            return two;
+        }
+    }
     if (team > 1) {
         for (;;) {
             const int free_cus = cu_claim(ctx->device, ctx->num_cu, ts.cus(), 0);
@@ -780,7 +812,7 @@ static TeamShape claim_cus(rrt_batch *b, int team) {
             ts = smaller;
             if (ts.team <= 1) break;
         }
-        if (ts.team != team) b->shrunk += 1;
+        if (ts.team != team || shifts == 2) b->shrunk += 1;  // (two shifts asked for and not granted counts too)
         b->claimed_cus = ts.team > 1 ? ts.cus() : 0;
     }
     if (ts.team <= 1) {
@@ -834,9 +866,12 @@ static int plan_launch(rrt_batch *b, LaunchPlan &p) {
     // two is slower than the barrier-free pipeline on ONE of them (config 4's query x 128: 12.7 ms against 11.0; config 2's:
     // 45.6 against 37.4, profiles/r04_experiments.md §11) -- unless the batch holds Informed queries, which that kernel does not run.
     if (two_cus_run_the_pipeline(b) && !p.continuation && !inf) team = 1;
-    const TeamShape ts = claim_cus(b, team);
+    // two worker shifts: only the split pair of 64 workers runs them (RRTStandard / RRTStar; Informed batches keep the one-body kernel)
+    const int shifts = (b->shifts == 2 && team == TEAM_MAX && split_team(team, b->pipe_team, inf, false, b->flags)) ? 2 : 1;
+    const TeamShape ts = claim_cus(b, team, shifts);
     p.team = ts.team;
     p.qpad = ts.qpad;
+    p.shifts = ts.shifts;
     p.inf = inf;
     // a two-deep pipeline of super-blocks (one more workgroup per team, which only commits)
     p.pipe = ts.team > 1 && ts.pipe;
@@ -862,12 +897,14 @@ static int plan_launch(rrt_batch *b, LaunchPlan &p) {
     p.wide = p.pipe && !inf && p.team == 2 && !narrow;
 #endif
     p.split = split_team(p.team, p.pipe, inf, p.wide, b->flags);
+    if (p.shifts == 2 && !p.split)  // (never: the shifts were only asked for where the pair runs)
+        return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_launch: two worker shifts need the split team kernels");
     p.row = find_variant(p.team, p.pipe, inf, p.wide, p.split);
     if (!p.row)
         return fail(ctx, RRT_E_UNSUPPORTED, "rrt_batch_launch: no team kernel for %d workers per query (pipelined %d, Informed %d, wide %d, as two kernels %d): "
                     "rrt_block_variants.def lists the variants", p.team, p.pipe, inf, p.wide, p.split);
     p.kern = p.row->one;
-    if (p.team > 1) p.grid = (unsigned)(p.qpad * (p.team + (p.pipe ? 1 : 0)));
+    if (p.team > 1) p.grid = (unsigned)(p.qpad * (p.team * p.shifts + (p.pipe ? 1 : 0)));
     return RRT_OK;
 }
 
@@ -897,6 +934,8 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
         }
     BatchView v = make_view(b);
     v.team_qpad = p.qpad;
+    v.shifts = p.shifts;
+    if (p.shifts == 2) v.spill_stride = b->spill_stride2;
     v.lds_chunks = p.lds_chunks;
     if (p.split) {
         if (!ctx->stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
@@ -918,7 +957,7 @@ extern "C" int rrt_batch_launch(rrt_batch *b) {
         hipLaunchKernelGGL(p.row->commit, dim3((unsigned)p.qpad), dim3(512), p.lds_bytes, ctx->stream2, v);
         BatchView vw = v;
         vw.member0 = 1;
-        hipLaunchKernelGGL(p.row->work, dim3((unsigned)(p.qpad * p.team)), dim3(TPB), p.lds_bytes, ctx->stream, vw);
+        hipLaunchKernelGGL(p.row->work, dim3((unsigned)(p.qpad * p.team * p.shifts)), dim3(TPB), p.lds_bytes, ctx->stream, vw);
         HIPCHK(ctx, hipEventRecord(b->ev_join, ctx->stream2));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_join, 0));
     } else {
@@ -1014,15 +1053,15 @@ extern "C" int rrt_batch_sync(rrt_batch *b) {
 
 extern "C" int rrt_batch_team(rrt_batch *b, int32_t *cus_per_query, int32_t *fallbacks) {
     if (!b || !cus_per_query) return fail(nullptr, RRT_E_ARG, "rrt_batch_team: NULL");
-    *cus_per_query = b->use_block ? b->team : 1;
+    *cus_per_query = b->use_block ? b->team * b->shifts : 1;  // (workers: both shifts)
     if (fallbacks) *fallbacks = b->team_fallbacks;
     return RRT_OK;
 }
 
 extern "C" int rrt_batch_team_info(rrt_batch *b, int32_t out[4]) {
     if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_team_info: NULL");
-    out[0] = b->use_block ? b->team : 1;
-    out[1] = b->use_block ? (b->last.team > 0 ? b->last.team : b->team) : 1;
+    out[0] = b->use_block ? b->team * b->shifts : 1;
+    out[1] = b->use_block ? (b->last.team > 0 ? b->last.team * b->last.shifts : b->team * b->shifts) : 1;
     out[2] = b->team_fallbacks;
     out[3] = b->shrunk;
     return RRT_OK;
@@ -1052,6 +1091,10 @@ extern "C" int rrt_batch_kernel_name(rrt_batch *b, char *buf, int32_t len) {
         snprintf(tmp, sizeof tmp, "rrt_dubins_block_kernel");
     } else {
         snprintf(tmp, sizeof tmp, "rrt_expand_kernel<%s, %s>", (b->flags & RRT_FLAG_REWIRE) ? "true" : "false", (b->flags & RRT_FLAG_DUBINS) ? "true" : "false");
+    }
+    if (b->use_block && b->last.team > 0 && b->last.shifts == 2) {  // (one shift keeps the name it always had)
+        const size_t at = strlen(tmp);
+        snprintf(tmp + at, sizeof tmp - at, " in 2 shifts");
     }
     snprintf(buf, (size_t)len, "%s", tmp);
     return RRT_OK;

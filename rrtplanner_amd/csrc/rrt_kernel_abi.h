@@ -73,6 +73,7 @@ struct BatchView {
     int32_t Q, team_qpad;     // queries of the batch; block stride between the members of a team (block = member * team_qpad + query)
     int32_t team_fault;       // testing: member 1 of every team leaves at once (the others' hand-offs time out)
     int32_t member0;          // added to the member number a team kernel derives from its block index (1: a launch of the workers only)
+    int32_t shifts;           // worker shifts of a split team of 64 (rrt_block.h, "shifts"): 2 = members 1..64 take the odd blocks, 65..128 the even ones
     // opt-in true rewire (RRT_FLAG_REWIRE; serial kernel only), null otherwise
     int32_t *kid_first, *kid_next, *kid_prev;  // [Q][node_stride] child lists: first child, next / previous sibling (-1 = none)
     uint32_t *frontier;                        // [Q][2 * node_stride] two propagation frontiers
@@ -103,11 +104,14 @@ constexpr int NPMAX = RRT_NPMAX;
 #endif
 constexpr int PL_MAX = RRT_PL_MAX, PL_WORDS = (RRT_PL_MAX + 3) / 4;
 constexpr int BREC_WORDS = 10 + 3 * NPMAX + PL_WORDS;  // 8-byte words of an owner's record (BRec, rrt_block.h): 152 bytes for two blocks in flight
-// per query: [go | fail | state (NPMAX + 1 slots of 64 bytes) | records (NPMAX + 1 slots of 64) | arrival flags (65 x 128) | go2goal answers (65 x 16)]
+// per query: [go | fail | state (NPMAX + 1 slots of 64 bytes) | records (NPMAX + 1 slots of 64) | arrival flags (65 x 128) | go2goal answers (65 x 16)
+//             | the second shift's arrival flags (65 x 128: member 64 + m at index m) | its go2goal answers (65 x 16)]
 constexpr int TEAM_OFF_GO = 128, TEAM_OFF_FAIL = 256, TEAM_OFF_STATE = 384, TEAM_OFF_REC = 1024;
 constexpr int TEAM_OFF_ARRIVE = (TEAM_OFF_REC + (NPMAX + 1) * 64 * BREC_WORDS * 8 + 127) / 128 * 128;
 constexpr int TEAM_OFF_RES = TEAM_OFF_ARRIVE + 65 * 128;
-constexpr int TEAM_BYTES = (TEAM_OFF_RES + 65 * 16 + 1023) / 1024 * 1024;
+constexpr int TEAM_OFF_ARRIVE2 = (TEAM_OFF_RES + 65 * 16 + 1023) / 1024 * 1024;  // (behind everything a one-shift team uses: those offsets stay)
+constexpr int TEAM_OFF_RES2 = TEAM_OFF_ARRIVE2 + 65 * 128;
+constexpr int TEAM_BYTES = (TEAM_OFF_RES2 + 65 * 16 + 1023) / 1024 * 1024;
 static_assert(TEAM_OFF_STATE + (NPMAX + 1) * 64 <= TEAM_OFF_REC, "state slots");
 
 // ---- rrt_goals.h ----

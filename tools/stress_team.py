@@ -47,5 +47,20 @@ for team, pipe in ((None, True), (None, False), (32, True), (32, False), (16, Tr
                 print(f"MISMATCH team={team} pipe={pipe} rep={rep} query={q}: status/j/vgoal {out[q][:3]} vs {ref[q][:3]}")
     print(f"team cap {team} pipe {pipe}: cus/query {b.team()[0]}, fallbacks {b.team()[1]}, {a.reps} repetitions, last kernel {b.elapsed_ms():.2f} ms")
     b.close()
+# two shifts of 64 workers: the shape a single query without a cap runs (a batch of one; each of the queries in turn)
+for q, (qu, keep) in enumerate(qs):
+    b = _ffi.Batch(ctx, 1, a.n)
+    b.set_query(0, qu)
+    for rep in range(a.reps):
+        b.rearm(); b.launch(); b.sync()
+        r = b.get_result(0)
+        live = r.j + (1 if r.found else 0)
+        out = (r.status, r.j, r.vgoal, r.pts[:live].copy(), r.parent[:live].copy(), r.vcost[:live].copy())
+        same = out[:3] == ref[q][:3] and all(np.array_equal(x, y) for x, y in zip(out[3:], ref[q][3:]))
+        if not same:
+            bad += 1
+            print(f"MISMATCH single query {q} ({b.kernel_name()}) rep={rep}: status/j/vgoal {out[:3]} vs {ref[q][:3]}")
+    print(f"single query {q}: {b.kernel_name()}, workers {b.team()[0]}, fallbacks {b.team()[1]}, {a.reps} repetitions, last kernel {b.elapsed_ms():.2f} ms")
+    b.close()
 print("mismatches:", bad)
 sys.exit(1 if bad else 0)
