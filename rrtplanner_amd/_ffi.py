@@ -60,34 +60,6 @@ def kernel_flags(logs=False, serial=False, team=None, team_fault=False, pipe=Tru
         f |= int(team) << 8
     return f
 
-# every symbol include/rrt_hip.h declares (tests/test_capi_symbols.py checks the library exports them)
-SYMBOLS = (
-    "rrt_ctx_create", "rrt_ctx_destroy", "rrt_last_error_string", "rrt_set_grid", "rrt_noise_grids", "rrt_select_frame",
-    "rrt_grid_generation", "rrt_ctx_sync",
-    "rrt_comm_use_library", "rrt_comm_unique_id", "rrt_comm_init", "rrt_comm_destroy", "rrt_comm_allreduce_f64", "rrt_gather", "rrt_gather_fetch",
-    "rrt_batch_create", "rrt_batch_destroy", "rrt_batch_set_query", "rrt_batch_set_unitball",
-    "rrt_batch_rearm", "rrt_batch_launch", "rrt_batch_sync", "rrt_batch_team", "rrt_batch_team_info", "rrt_batch_pipelined", "rrt_batch_kernel_name", "rrt_batch_elapsed_ms",
-    "rrt_batch_get_result", "rrt_batch_result_block", "rrt_batch_debug_cycles",
-    "rrt_plan", "rrt_plan_resume", "rrt_plan_batch",
-    "rrt_tree_create", "rrt_tree_destroy", "rrt_tree_reset", "rrt_tree_append", "rrt_tree_query",
-    "rrt_prim_collisionfree", "rrt_prim_nearest_within", "rrt_prim_sqrt_u32", "rrt_prim_sqrt_u24", "rrt_prim_sqrt_f64",
-    "rrt_prim_collisionfree_walk", "rrt_prim_sqrt_u25",
-    "rrt_batch_connect_goals", "rrt_plan_connect_goals",
-    "rrt_batch_routes", "rrt_batch_routes_rows", "rrt_plan_routes", "rrt_plan_routes_rows",
-    "rrt_batch_keep_tree", "rrt_batch_keep_tree_ms", "rrt_plan_keep_tree", "rrt_plan_keep_tree_ms", "rrt_plan_tree_size",
-    "rrt_batch_grow", "rrt_batch_grow_ms", "rrt_plan_grow", "rrt_plan_grow_ms",
-    "rrt_batch_grow_poses", "rrt_plan_grow_poses",
-    "rrt_batch_reroot", "rrt_batch_reroot_ms", "rrt_plan_reroot", "rrt_plan_reroot_ms",
-    "rrt_batch_relax", "rrt_batch_relax_ms", "rrt_batch_relax_stats", "rrt_plan_relax", "rrt_plan_relax_ms", "rrt_plan_relax_stats",
-    "rrt_batch_relax_poses", "rrt_batch_relax_poses_ms", "rrt_batch_relax_poses_stats",
-    "rrt_plan_relax_poses", "rrt_plan_relax_poses_ms", "rrt_plan_relax_poses_stats",
-    "rrt_batch_connect_poses", "rrt_plan_connect_poses", "rrt_batch_connect_poses_counts",
-    "rrt_batch_keep_pose_tree", "rrt_plan_keep_pose_tree",
-    "rrt_batch_pose_routes", "rrt_batch_pose_routes_rows", "rrt_batch_pose_routes_points", "rrt_batch_pose_routes_ms",
-    "rrt_plan_pose_routes", "rrt_plan_pose_routes_rows", "rrt_plan_pose_routes_points", "rrt_plan_pose_routes_ms",
-    "rrt_batch_pose_shortcuts", "rrt_batch_pose_shortcuts_ms", "rrt_plan_pose_shortcuts", "rrt_plan_pose_shortcuts_ms",
-)
-
 
 class RRTError(RuntimeError):
     def __init__(self, code, msg):
@@ -120,6 +92,105 @@ class Result(C.Structure):
     ]
 
 
+_vp, _i32, _u32, _i64, _P = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.POINTER
+
+
+def _ms(stages, *count):
+    return [_P(C.c_float * stages), *count]
+
+
+# The argument types of every symbol include/rrt_hip.h declares, the handle included (tests/test_capi_symbols.py checks the names
+# against the header and that the library exports them).  All return int but _RESTYPE's.
+_SIG = {
+    "rrt_ctx_create": [_i32, _P(_vp)],
+    "rrt_ctx_destroy": [_vp],
+    "rrt_last_error_string": [_vp],
+    "rrt_set_grid": [_vp, _vp, _i32, _i32],
+    "rrt_noise_grids": [_vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp],
+    "rrt_select_frame": [_vp, _i32],
+    "rrt_grid_generation": [_vp, _P(C.c_uint64)],
+    "rrt_ctx_sync": [_vp],
+    "rrt_comm_use_library": [C.c_char_p],
+    "rrt_comm_unique_id": [_vp],
+    "rrt_comm_init": [_vp, _i32, _i32, _vp],
+    "rrt_comm_destroy": [_vp],
+    "rrt_comm_allreduce_f64": [_vp, _vp, _i32, _i32],
+    "rrt_gather": [_vp, _P(_vp), _P(_i64)],
+    "rrt_gather_fetch": [_vp, _i32, _i32, _P(Result)],
+    "rrt_batch_create": [_vp, _i32, _i32, _u32, _P(_vp)],
+    "rrt_batch_destroy": [_vp],
+    "rrt_batch_set_query": [_vp, _i32, _P(Query)],
+    "rrt_batch_set_unitball": [_vp, _i32, _vp, _i32, _i32],
+    "rrt_batch_rearm": [_vp],
+    "rrt_batch_launch": [_vp],
+    "rrt_batch_sync": [_vp],
+    "rrt_batch_team": [_vp, _P(_i32), _P(_i32)],
+    "rrt_batch_team_info": [_vp, _P(_i32 * 4)],
+    "rrt_batch_pipelined": [_vp, _P(_i32)],
+    "rrt_batch_kernel_name": [_vp, C.c_char_p, _i32],
+    "rrt_batch_elapsed_ms": [_vp, _P(C.c_float)],
+    "rrt_batch_get_result": [_vp, _i32, _P(Result)],
+    "rrt_batch_result_block": [_vp, _P(_vp), _P(_i64)],
+    "rrt_batch_debug_cycles": [_vp, _i32, _P(C.c_uint64 * 38)],
+    "rrt_plan": [_vp, _P(Query), _u32, _P(Result)],
+    "rrt_plan_resume": [_vp, _vp, _i32, _P(Result)],
+    "rrt_plan_batch": [_vp, _i32, _P(Query), _P(Result)],
+    "rrt_tree_create": [_vp, _i32, _P(_vp)],
+    "rrt_tree_destroy": [_vp],
+    "rrt_tree_reset": [_vp],
+    "rrt_tree_append": [_vp, _i32, _i32, _P(_i32)],
+    "rrt_tree_query": [_vp, _i32, _i32, _i64, _P(_i32), _P(_i32), _vp, _vp, _i32],
+    "rrt_prim_collisionfree": [_vp, _vp, _i32, _vp, _vp],
+    "rrt_prim_nearest_within": [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp],
+    "rrt_prim_sqrt_u32": [_vp, _u32, _u32, _vp],
+    "rrt_prim_sqrt_u24": [_vp, _u32, _u32, _vp],
+    "rrt_prim_sqrt_f64": [_vp, _vp, _u32, _vp],
+    "rrt_prim_collisionfree_walk": [_vp, _vp, _i32, _i32, _vp, _vp],
+    "rrt_prim_sqrt_u25": [_vp, _u32, _u32, _vp],
+    "rrt_plan_tree_size": [_vp, _P(_i32)],  # the two tree calls without a twin
+    "rrt_batch_connect_poses_counts": [_vp, _P(_i64 * 2)],
+}
+_RESTYPE = {"rrt_last_error_string": C.c_char_p}
+
+# The tree calls come as rrt_batch_X / rrt_plan_X, one row each; the arguments behind the handle (and q).
+# ... on the tree of a query: (b, q, args...) / (ctx, args...)
+_TREE_CALLS = {
+    "connect_goals": [_vp, _i32, _vp, _vp],
+    "connect_poses": [_vp, _i32, _vp, _vp],
+    "routes": [_vp, _i32, _u32, _vp, _vp, _vp, _vp],
+    "pose_routes": [_vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp],
+    "pose_shortcuts": [_vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp],
+    "keep_tree": [_P(_i32), _vp],
+    "keep_pose_tree": [_P(_i32), _vp],
+}
+# ... reports on the last such call: (handle, args...) in both forms
+_REPORT_CALLS = {
+    "routes_rows": [_vp, _vp, _i64],
+    "pose_routes_rows": [_vp, _vp, _i64],
+    "pose_routes_points": [_vp, _i64],
+    "pose_routes_ms": _ms(4),
+    "pose_shortcuts_ms": _ms(5),
+    "keep_tree_ms": _ms(3),
+    "grow_ms": _ms(3, _i32),
+    "reroot_ms": _ms(8, _i32),
+    "relax_ms": _ms(9, _i32),
+    "relax_poses_ms": _ms(9, _i32),
+    "relax_stats": [_P(_i64 * 4)],
+    "relax_poses_stats": [_P(_i64 * 4)],
+}
+# ... the seed family: (b, q, lead..., samples, m, j0, old_id, int32 *log0) / (ctx, lead..., samples, m, j0, old_id, rrt_result *out)
+_SEED_CALLS = {"grow": [], "grow_poses": [], "reroot": [_i32], "relax": [_i64], "relax_poses": [_i64]}
+for _name, _args in _TREE_CALLS.items():
+    _SIG["rrt_batch_" + _name], _SIG["rrt_plan_" + _name] = [_vp, _i32] + _args, [_vp] + _args
+for _name, _args in _REPORT_CALLS.items():
+    _SIG["rrt_batch_" + _name] = _SIG["rrt_plan_" + _name] = [_vp] + _args
+for _name, _args in _SEED_CALLS.items():
+    _SIG["rrt_batch_" + _name] = [_vp, _i32] + _args + [_vp, _i32, _P(_i32), _vp, _P(_i32)]
+    _SIG["rrt_plan_" + _name] = [_vp] + _args + [_vp, _i32, _P(_i32), _vp, _P(Result)]
+del _name, _args
+
+SYMBOLS = tuple(_SIG)
+
 _lib = None
 
 
@@ -133,108 +204,10 @@ def lib():
                 "(hipcc --offload-arch=gfx950).  rrtplanner_amd has no CPU fallback."
             )
         L = C.CDLL(LIB_PATH)
-        vp, i32, u32, i64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64
-        sig = {
-            "rrt_ctx_create": ([i32, C.POINTER(vp)], C.c_int),
-            "rrt_ctx_destroy": ([vp], C.c_int),
-            "rrt_last_error_string": ([vp], C.c_char_p),
-            "rrt_set_grid": ([vp, vp, i32, i32], C.c_int),
-            "rrt_noise_grids": ([vp, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp, vp], C.c_int),
-            "rrt_select_frame": ([vp, i32], C.c_int),
-            "rrt_grid_generation": ([vp, C.POINTER(C.c_uint64)], C.c_int),
-            "rrt_ctx_sync": ([vp], C.c_int),
-            "rrt_comm_use_library": ([C.c_char_p], C.c_int),
-            "rrt_comm_unique_id": ([vp], C.c_int),
-            "rrt_comm_init": ([vp, i32, i32, vp], C.c_int),
-            "rrt_comm_destroy": ([vp], C.c_int),
-            "rrt_comm_allreduce_f64": ([vp, vp, i32, i32], C.c_int),
-            "rrt_gather": ([vp, C.POINTER(vp), C.POINTER(i64)], C.c_int),
-            "rrt_gather_fetch": ([vp, i32, i32, C.POINTER(Result)], C.c_int),
-            "rrt_batch_create": ([vp, i32, i32, u32, C.POINTER(vp)], C.c_int),
-            "rrt_batch_destroy": ([vp], C.c_int),
-            "rrt_batch_set_query": ([vp, i32, C.POINTER(Query)], C.c_int),
-            "rrt_batch_set_unitball": ([vp, i32, vp, i32, i32], C.c_int),
-            "rrt_batch_rearm": ([vp], C.c_int),
-            "rrt_batch_launch": ([vp], C.c_int),
-            "rrt_batch_sync": ([vp], C.c_int),
-            "rrt_batch_team": ([vp, C.POINTER(i32), C.POINTER(i32)], C.c_int),
-            "rrt_batch_team_info": ([vp, C.POINTER(i32 * 4)], C.c_int),
-            "rrt_batch_pipelined": ([vp, C.POINTER(i32)], C.c_int),
-            "rrt_batch_kernel_name": ([vp, C.c_char_p, i32], C.c_int),
-            "rrt_batch_elapsed_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
-            "rrt_batch_get_result": ([vp, i32, C.POINTER(Result)], C.c_int),
-            "rrt_batch_result_block": ([vp, C.POINTER(vp), C.POINTER(i64)], C.c_int),
-            "rrt_batch_debug_cycles": ([vp, i32, C.POINTER(C.c_uint64 * 38)], C.c_int),
-            "rrt_plan": ([vp, C.POINTER(Query), u32, C.POINTER(Result)], C.c_int),
-            "rrt_plan_resume": ([vp, vp, i32, C.POINTER(Result)], C.c_int),
-            "rrt_plan_batch": ([vp, i32, C.POINTER(Query), C.POINTER(Result)], C.c_int),
-            "rrt_tree_create": ([vp, i32, C.POINTER(vp)], C.c_int),
-            "rrt_tree_destroy": ([vp], C.c_int),
-            "rrt_tree_reset": ([vp], C.c_int),
-            "rrt_tree_append": ([vp, i32, i32, C.POINTER(i32)], C.c_int),
-            "rrt_tree_query": ([vp, i32, i32, i64, C.POINTER(i32), C.POINTER(i32), vp, vp, i32], C.c_int),
-            "rrt_prim_collisionfree": ([vp, vp, i32, vp, vp], C.c_int),
-            "rrt_prim_nearest_within": ([vp, vp, i32, vp, i32, i64, vp, vp, vp], C.c_int),
-            "rrt_prim_sqrt_u32": ([vp, u32, u32, vp], C.c_int),
-            "rrt_prim_sqrt_u24": ([vp, u32, u32, vp], C.c_int),
-            "rrt_prim_sqrt_f64": ([vp, vp, u32, vp], C.c_int),
-            "rrt_prim_collisionfree_walk": ([vp, vp, i32, i32, vp, vp], C.c_int),
-            "rrt_prim_sqrt_u25": ([vp, u32, u32, vp], C.c_int),
-            "rrt_batch_connect_goals": ([vp, i32, vp, i32, vp, vp], C.c_int),
-            "rrt_plan_connect_goals": ([vp, vp, i32, vp, vp], C.c_int),
-            "rrt_batch_routes": ([vp, i32, vp, i32, u32, vp, vp, vp, vp], C.c_int),
-            "rrt_batch_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
-            "rrt_plan_routes": ([vp, vp, i32, u32, vp, vp, vp, vp], C.c_int),
-            "rrt_plan_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
-            "rrt_batch_keep_tree": ([vp, i32, C.POINTER(i32), vp], C.c_int),
-            "rrt_batch_keep_tree_ms": ([vp, C.POINTER(C.c_float * 3)], C.c_int),
-            "rrt_plan_keep_tree": ([vp, C.POINTER(i32), vp], C.c_int),
-            "rrt_plan_keep_tree_ms": ([vp, C.POINTER(C.c_float * 3)], C.c_int),
-            "rrt_plan_tree_size": ([vp, C.POINTER(i32)], C.c_int),
-            "rrt_batch_grow": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
-            "rrt_batch_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
-            "rrt_plan_grow": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
-            "rrt_plan_grow_ms": ([vp, C.POINTER(C.c_float * 3), i32], C.c_int),
-            "rrt_batch_grow_poses": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
-            "rrt_plan_grow_poses": ([vp, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
-            "rrt_batch_reroot": ([vp, i32, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
-            "rrt_batch_reroot_ms": ([vp, C.POINTER(C.c_float * 8), i32], C.c_int),
-            "rrt_plan_reroot": ([vp, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
-            "rrt_plan_reroot_ms": ([vp, C.POINTER(C.c_float * 8), i32], C.c_int),
-            "rrt_batch_relax": ([vp, i32, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
-            "rrt_batch_relax_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
-            "rrt_batch_relax_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
-            "rrt_plan_relax": ([vp, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
-            "rrt_plan_relax_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
-            "rrt_plan_relax_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
-            "rrt_batch_relax_poses": ([vp, i32, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)], C.c_int),
-            "rrt_batch_relax_poses_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
-            "rrt_batch_relax_poses_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
-            "rrt_plan_relax_poses": ([vp, i64, vp, i32, C.POINTER(i32), vp, C.POINTER(Result)], C.c_int),
-            "rrt_plan_relax_poses_ms": ([vp, C.POINTER(C.c_float * 9), i32], C.c_int),
-            "rrt_plan_relax_poses_stats": ([vp, C.POINTER(i64 * 4)], C.c_int),
-            "rrt_batch_connect_poses": ([vp, i32, vp, i32, vp, vp], C.c_int),
-            "rrt_plan_connect_poses": ([vp, vp, i32, vp, vp], C.c_int),
-            "rrt_batch_connect_poses_counts": ([vp, C.POINTER(C.c_int64 * 2)], C.c_int),
-            "rrt_batch_keep_pose_tree": ([vp, i32, C.POINTER(i32), vp], C.c_int),
-            "rrt_plan_keep_pose_tree": ([vp, C.POINTER(i32), vp], C.c_int),
-            "rrt_batch_pose_routes": ([vp, i32, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
-            "rrt_batch_pose_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
-            "rrt_batch_pose_routes_points": ([vp, vp, C.c_int64], C.c_int),
-            "rrt_batch_pose_routes_ms": ([vp, C.POINTER(C.c_float * 4)], C.c_int),
-            "rrt_plan_pose_routes": ([vp, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
-            "rrt_plan_pose_routes_rows": ([vp, vp, vp, C.c_int64], C.c_int),
-            "rrt_plan_pose_routes_points": ([vp, vp, C.c_int64], C.c_int),
-            "rrt_plan_pose_routes_ms": ([vp, C.POINTER(C.c_float * 4)], C.c_int),
-            "rrt_batch_pose_shortcuts": ([vp, i32, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
-            "rrt_batch_pose_shortcuts_ms": ([vp, C.POINTER(C.c_float * 5)], C.c_int),
-            "rrt_plan_pose_shortcuts": ([vp, vp, i32, u32, vp, vp, vp, vp, vp], C.c_int),
-            "rrt_plan_pose_shortcuts_ms": ([vp, C.POINTER(C.c_float * 5)], C.c_int),
-        }
-        for name, (argtypes, restype) in sig.items():
+        for name, argtypes in _SIG.items():
             fn = getattr(L, name)
             fn.argtypes = argtypes
-            fn.restype = restype
+            fn.restype = _RESTYPE.get(name, C.c_int)
         _lib = L
     return _lib
 
@@ -278,56 +251,6 @@ def _pose_arrays(poses):
     return _goal_arrays(poses, 3)
 
 
-def _routes(handle, call, rows_call, goals, shortcut):
-    """the two steps of a routes call: `call` decides and builds the routes on the device and gives the CSR offsets, `rows_call`
-    copies the rows out.  (vertex, cost, length, offsets int64[M + 1], xy int32[(rows, 2)], ids int32[rows])"""
-    g, vertex, cost = _goal_arrays(goals)
-    m = g.shape[0]
-    length = np.full(m, np.inf, dtype=np.float64)
-    offsets = np.zeros(m + 1, dtype=np.int64)
-    _check(handle, call(g.ctypes.data, m, RRT_ROUTES_SHORTCUT if shortcut else 0, vertex.ctypes.data, cost.ctypes.data, length.ctypes.data, offsets.ctypes.data))
-    rows = int(offsets[m])
-    xy = np.empty((rows, 2), dtype=np.int32)
-    ids = np.empty(rows, dtype=np.int32)
-    _check(handle, rows_call(xy.ctypes.data, ids.ctypes.data, rows))
-    return vertex, cost, length, offsets, xy, ids
-
-
-def _pose_routes(handle, call, rows_call, points_call, poses, points):
-    """the steps of a pose routes call: `call` decides and builds the routes on the device and gives the CSR offsets, `rows_call` and,
-    with points, `points_call` copy the rows and the points out.  (vertex, cost, length, offsets int64[M + 1], xyh int32[(rows, 3)],
-    ids int32[rows]) and with points (point_offsets int64[M + 1], pts float64[(P, 2)]) behind them"""
-    g, vertex, cost = _pose_arrays(poses)
-    m = g.shape[0]
-    length = np.full(m, np.inf, dtype=np.float64)
-    offsets = np.zeros(m + 1, dtype=np.int64)
-    point_offsets = np.zeros(m + 1, dtype=np.int64) if points else None
-    _check(handle, call(g.ctypes.data, m, RRT_POSE_ROUTES_POINTS if points else 0, vertex.ctypes.data, cost.ctypes.data, length.ctypes.data,
-                        offsets.ctypes.data, point_offsets.ctypes.data if points else None))
-    rows = int(offsets[m])
-    xyh = np.empty((rows, 3), dtype=np.int32)
-    ids = np.empty(rows, dtype=np.int32)
-    _check(handle, rows_call(xyh.ctypes.data, ids.ctypes.data, rows))
-    if not points:
-        return vertex, cost, length, offsets, xyh, ids
-    pts = np.empty((int(point_offsets[m]), 2), dtype=np.float64)
-    _check(handle, points_call(pts.ctypes.data, pts.shape[0]))
-    return vertex, cost, length, offsets, xyh, ids, point_offsets, pts
-
-
-def _keep_tree(handle, call, size, j):
-    """a keep_tree call: `call` takes (n_alive, alive) and fills one flag per vertex of the tree.  `size` bounds them and comes from
-    the library: the capacity the batch was created with, or the tree size the library reports for the query.  j() is asked for the
-    vertices of the tree after the call has accepted the query.  bool[j]"""
-    alive = np.zeros(max(int(size), 1), dtype=np.uint8)
-    n_alive = C.c_int32(-1)
-    _check(handle, call(C.byref(n_alive), alive.ctypes.data))
-    alive = alive[:int(j())].astype(bool)
-    if int(alive.sum()) != n_alive.value:
-        raise RRTError(RRT_E_HIP, f"keep_tree: {n_alive.value} vertices alive, {int(alive.sum())} flags set")
-    return alive
-
-
 def _grow_samples(samples, poses=False):
     """the samples of a grow call as contiguous int32 (m, 2), packed uint32 samples (x | y << 16) unpacked; of a grow_poses call
     (poses) as contiguous int32 (m, 3): rows (x, y, heading index)"""
@@ -343,20 +266,90 @@ def _grow_pose_samples(samples):
     return _grow_samples(samples, True)
 
 
-def _stage_ms(handle, call, stages, *count):
-    """a *_ms call: the kernel time in ms of the `stages` stages of the last call it reports on, as a tuple"""
-    ms = (C.c_float * stages)()
-    _check(handle, call(C.byref(ms), *count))
-    return tuple(ms)
-
-
-def _relax_stats(handle, call, names=("rounds", "fell", "los", "priced")):
-    out = (C.c_int64 * 4)()
-    _check(handle, call(C.byref(out)))
-    return dict(zip(names, (int(v) for v in out)))
-
-
 POSE_RELAX_STATS = ("rounds", "fell", "sweeps", "words")
+
+
+class _Tree:
+    """How the C ABI addresses one finished tree, and the marshalling of every tree call written against it: `err` the handle the
+    error string is read from, `h` the native handle, `prefix` "rrt_plan_" (the tree of a context's last plan) or "rrt_batch_"
+    (then q = (query,))."""
+
+    def __init__(self, err, h, prefix, q=()):
+        self.err, self.h, self.prefix, self.q = err, h, prefix, q
+
+    def call(self, name, *args, ok=(RRT_OK,)):
+        """a call on the tree: rrt_batch_<name>(b, q, args...) / rrt_plan_<name>(ctx, args...)"""
+        return _check(self.err, getattr(lib(), self.prefix + name)(self.h, *self.q, *args), ok)
+
+    def report(self, name, *args):
+        """a call that reports on the last call: (handle, args...) in both forms"""
+        return _check(self.err, getattr(lib(), self.prefix + name)(self.h, *args))
+
+    def connect(self, name, goals, cols):
+        """connect_goals (cols = 2) / connect_poses (cols = 3): (vertex int32[M], cost float64[M])"""
+        g, vertex, cost = _goal_arrays(goals, cols)
+        self.call(name, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data)
+        return vertex, cost
+
+    def rows(self, name, cols, rows):
+        """<name>_rows: the rows the last routes call left, (xy int32[(rows, cols)], ids int32[rows])"""
+        xy = np.empty((int(rows), cols), dtype=np.int32)
+        ids = np.empty(int(rows), dtype=np.int32)
+        self.report(name + "_rows", xy.ctypes.data, ids.ctypes.data, int(rows))
+        return xy, ids
+
+    def points(self, points):
+        """pose_routes_points: the points the last pose routes call left, float64[(points, 2)]"""
+        pts = np.empty((int(points), 2), dtype=np.float64)
+        self.report("pose_routes_points", pts.ctypes.data, int(points))
+        return pts
+
+    def routes(self, name, goals, cols, flags, points=False):
+        """the steps of a routes call (cols = 2: name "routes") or a pose routes call (cols = 3: "pose_routes" / "pose_shortcuts"):
+        `name` decides and builds the routes on the device and gives the CSR offsets, then the rows and, with points, the points are
+        copied out.  (vertex, cost, length, offsets int64[M + 1], xy or xyh int32[(rows, cols)], ids int32[rows]) and with points
+        (point_offsets int64[M + 1], pts float64[(P, 2)]) behind them"""
+        g, vertex, cost = _goal_arrays(goals, cols)
+        m = g.shape[0]
+        length = np.full(m, np.inf, dtype=np.float64)
+        offsets = np.zeros(m + 1, dtype=np.int64)
+        point_offsets = np.zeros(m + 1, dtype=np.int64) if points else None
+        pose_args = () if cols == 2 else (point_offsets.ctypes.data if points else None,)
+        self.call(name, g.ctypes.data, m, flags, vertex.ctypes.data, cost.ctypes.data, length.ctypes.data, offsets.ctypes.data, *pose_args)
+        out = (vertex, cost, length, offsets) + self.rows("routes" if cols == 2 else "pose_routes", cols, offsets[m])
+        return out + (point_offsets, self.points(point_offsets[m])) if points else out
+
+    def keep(self, name, size, j):
+        """keep_tree / keep_pose_tree: the call fills one flag per vertex of the tree.  `size` bounds them and comes from the library:
+        the capacity the batch was created with, or the tree size the library reports for the query.  j() is asked for the vertices
+        of the tree after the call has accepted the query.  bool[j]"""
+        alive = np.zeros(max(int(size), 1), dtype=np.uint8)
+        n_alive = C.c_int32(-1)
+        self.call(name, C.byref(n_alive), alive.ctypes.data)
+        alive = alive[:int(j())].astype(bool)
+        if int(alive.sum()) != n_alive.value:
+            raise RRTError(RRT_E_HIP, f"keep_tree: {n_alive.value} vertices alive, {int(alive.sum())} flags set")
+        return alive
+
+    def seed(self, name, lead, samples, poses, rows, j0, tail, ok=(RRT_OK,)):
+        """the seed family (grow, grow_poses, reroot, relax, relax_poses): `lead` its arguments ahead of the samples, `rows` the rows
+        old_id may need, j0 the caller's c_int32 (it stays below 0 when the call refuses before the seed), `tail` the last argument
+        (the batch's log0, the context's result).  (rc, old_id int32[j0])"""
+        s = _grow_samples(samples, poses)
+        old_id = np.full(int(rows) + 1, -1, dtype=np.int32)
+        rc = self.call(name, *lead, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, tail, ok=ok)
+        return rc, old_id[:j0.value].copy()
+
+    def stage_ms(self, name, stages, *count):
+        """<name>_ms: the kernel time in ms of the `stages` stages of the last call it reports on, as a tuple"""
+        ms = (C.c_float * stages)()
+        self.report(name + "_ms", C.byref(ms), *count)
+        return tuple(ms)
+
+    def relax_stats(self, name, names=("rounds", "fell", "los", "priced")):
+        out = (C.c_int64 * 4)()
+        self.report(name + "_stats", C.byref(out))
+        return dict(zip(names, (int(v) for v in out)))
 
 
 class ResultArrays:
@@ -435,7 +428,53 @@ def _disown(child, destroy):
         child._h = C.c_void_p()
 
 
-class Context:
+class _TreeReports:
+    """What Context and Batch report about their last tree call: the same methods on self._tree()."""
+
+    def pose_shortcuts_ms(self):
+        """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
+        lengths, points)"""
+        return self._tree().stage_ms("pose_shortcuts", 5)
+
+    def pose_routes_ms(self):
+        """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
+        return self._tree().stage_ms("pose_routes", 4)
+
+    def keep_tree_ms(self):
+        """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
+        return self._tree().stage_ms("keep_tree", 3)
+
+    def grow_ms(self):
+        """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
+        return self._tree().stage_ms("grow", 3, 3)
+
+    def reroot_ms(self):
+        """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
+        seed's three as grow_ms() gives them"""
+        return self._tree().stage_ms("reroot", 8, 8)
+
+    def relax_ms(self):
+        """time in ms of the stages of the last relax(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's three
+        as grow_ms() gives them"""
+        return self._tree().stage_ms("relax", 9, 9)
+
+    def relax_stats(self):
+        """of the last relax(): dict(rounds, fell, los, priced) -- rounds run, vertices whose cost fell, lines of sight walked,
+        candidate pairs priced"""
+        return self._tree().relax_stats("relax")
+
+    def relax_poses_ms(self):
+        """time in ms of the stages of the last relax_poses(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's
+        three as grow_ms() gives them"""
+        return self._tree().stage_ms("relax_poses", 9, 9)
+
+    def relax_poses_stats(self):
+        """of the last relax_poses(): dict(rounds, fell, sweeps, words) -- rounds run, vertices whose cost fell, sweeps run, words
+        evaluated"""
+        return self._tree().relax_stats("relax_poses", POSE_RELAX_STATS)
+
+
+class Context(_TreeReports):
     """One device context: a HIP stream + the device-resident occupancy grid."""
 
     def __init__(self, device_id=0):
@@ -535,130 +574,75 @@ class Context:
         _check(self._h, rc, ok=(RRT_OK, RRT_NEED_UNITBALL, RRT_E_GOAL_UNREACHABLE))
         return rc
 
+    def _tree(self):
+        return _Tree(self._h, self._h, "rrt_plan_")
+
     def connect_goals(self, goals):
         """rrt_plan_connect_goals: Batch.connect_goals on the tree of this context's last plan() / plan_resume()"""
-        g, vertex, cost = _goal_arrays(goals)
-        _check(self._h, lib().rrt_plan_connect_goals(self._h, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
-        return vertex, cost
+        return self._tree().connect("connect_goals", goals, 2)
 
     def connect_poses(self, poses):
         """rrt_plan_connect_poses: Batch.connect_poses on the Dubins tree of this context's last plan()"""
-        g, vertex, cost = _pose_arrays(poses)
-        _check(self._h, lib().rrt_plan_connect_poses(self._h, g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
-        return vertex, cost
+        return self._tree().connect("connect_poses", poses, 3)
 
     def routes(self, goals, shortcut=False):
         """rrt_plan_routes + rrt_plan_routes_rows: Batch.routes on the tree of this context's last plan() / plan_resume()"""
-        L = lib()
-        return _routes(self._h, lambda *a: L.rrt_plan_routes(self._h, *a), lambda *a: L.rrt_plan_routes_rows(self._h, *a), goals, shortcut)
+        return self._tree().routes("routes", goals, 2, RRT_ROUTES_SHORTCUT if shortcut else 0)
 
     def pose_routes(self, poses, points=False, shortcut=False):
         """rrt_plan_pose_routes (shortcut=True: rrt_plan_pose_shortcuts) + rrt_plan_pose_routes_rows (+ rrt_plan_pose_routes_points):
         Batch.pose_routes on the Dubins tree of this context's last plan()"""
-        L = lib()
-        call = L.rrt_plan_pose_shortcuts if shortcut else L.rrt_plan_pose_routes
-        return _pose_routes(self._h, lambda *a: call(self._h, *a), lambda *a: L.rrt_plan_pose_routes_rows(self._h, *a),
-                            lambda *a: L.rrt_plan_pose_routes_points(self._h, *a), poses, points)
+        return self._tree().routes("pose_shortcuts" if shortcut else "pose_routes", poses, 3, RRT_POSE_ROUTES_POINTS if points else 0, points)
 
-    def pose_shortcuts_ms(self):
-        """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
-        lengths, points)"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_pose_shortcuts_ms(self._h, *a), 5)
-
-    def pose_routes_ms(self):
-        """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_pose_routes_ms(self._h, *a), 4)
+    def _keep(self, name):
+        j = C.c_int32(0)
+        _check(self._h, lib().rrt_plan_tree_size(self._h, C.byref(j)))
+        return self._tree().keep(name, j.value, lambda: j.value)
 
     def keep_tree(self):
         """rrt_plan_keep_tree: Batch.keep_tree on the tree of this context's last plan() / plan_resume()"""
-        L = lib()
-        j = C.c_int32(0)
-        _check(self._h, L.rrt_plan_tree_size(self._h, C.byref(j)))
-        return _keep_tree(self._h, lambda *a: L.rrt_plan_keep_tree(self._h, *a), j.value, lambda: j.value)
+        return self._keep("keep_tree")
 
     def keep_pose_tree(self):
         """rrt_plan_keep_pose_tree: Batch.keep_pose_tree on the Dubins tree of this context's last plan()"""
-        L = lib()
-        j = C.c_int32(0)
-        _check(self._h, L.rrt_plan_tree_size(self._h, C.byref(j)))
-        return _keep_tree(self._h, lambda *a: L.rrt_plan_keep_pose_tree(self._h, *a), j.value, lambda: j.value)
+        return self._keep("keep_pose_tree")
 
-    def keep_tree_ms(self):
-        """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_keep_tree_ms(self._h, *a), 3)
+    def _seed(self, name, lead, samples, n, logs, poses=False):
+        """the seed family on the tree of the last plan, launch and result included: (rc, ResultArrays, j0, old_id int32[j0])"""
+        res = ResultArrays(int(n), logs, headings=poses)
+        j0 = C.c_int32(-1)
+        try:
+            rc, old_id = self._tree().seed(name, lead, samples, poses, n, j0, C.byref(res.c), ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
+        except RRTError as e:
+            e.seeded = j0.value >= 0  # False: the call refused before the seed and changed nothing
+            raise
+        return rc, res, j0.value, old_id
 
     def grow(self, samples, n, logs=False):
         """rrt_plan_grow: Batch.grow on the tree of this context's last plan() / plan_resume(), launch and result included.  n: the
         n of that plan (the result arrays are sized by it).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
-        return self._grow(samples, n, logs, False)
-
-    def _grow(self, samples, n, logs, poses, root=None, r2=None):
-        s = _grow_samples(samples, poses)
-        res = ResultArrays(int(n), logs, headings=poses)
-        j0 = C.c_int32(-1)
-        old_id = np.full(int(n) + 1, -1, dtype=np.int32)
-        if r2 is not None:
-            call = lib().rrt_plan_relax_poses if poses else lib().rrt_plan_relax
-            rc = call(self._h, int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
-        elif root is not None:
-            rc = lib().rrt_plan_reroot(self._h, int(root), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
-        else:
-            call = lib().rrt_plan_grow_poses if poses else lib().rrt_plan_grow
-            rc = call(self._h, s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(res.c))
-        try:
-            _check(self._h, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
-        except RRTError as e:
-            e.seeded = j0.value >= 0  # False: the call refused before the seed and changed nothing
-            raise
-        return rc, res, j0.value, old_id[:j0.value].copy()
+        return self._seed("grow", (), samples, n, logs)
 
     def grow_poses(self, samples, n, logs=False):
         """rrt_plan_grow_poses: Batch.grow_poses on the Dubins tree of this context's last plan(), launch and result (headings
         included) as grow().  samples: (m, 3) rows (x, y, heading index).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
-        return self._grow(samples, n, logs, True)
-
-    def grow_ms(self):
-        """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_grow_ms(self._h, *a), 3, 3)
+        return self._seed("grow_poses", (), samples, n, logs, True)
 
     def reroot(self, root, samples, n, logs=False):
         """rrt_plan_reroot: Batch.reroot on the tree of this context's last plan() / plan_resume(), launch and result included.
         root: a vertex number of that tree; n: the n of that plan.  Returns (rc, ResultArrays, j0, old_id int32[j0]) as grow()."""
-        return self._grow(samples, n, logs, False, root=root)
-
-    def reroot_ms(self):
-        """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
-        seed's three as grow_ms() gives them"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_reroot_ms(self._h, *a), 8, 8)
+        return self._seed("reroot", (int(root),), samples, n, logs)
 
     def relax(self, r2, samples, n, logs=False):
         """rrt_plan_relax: Batch.relax on the tree of this context's last plan() / plan_resume(), launch and result included.
         r2: the threshold of the squared distance (hostprep.radius_threshold(r)); n: the n of that plan.  Returns (rc, ResultArrays, j0,
         old_id int32[j0]) as grow()."""
-        return self._grow(samples, n, logs, False, r2=r2)
-
-    def relax_ms(self):
-        """time in ms of the stages of the last relax(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's three
-        as grow_ms() gives them"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_relax_ms(self._h, *a), 9, 9)
-
-    def relax_stats(self):
-        """of the last relax(): dict(rounds, fell, los, priced)"""
-        return _relax_stats(self._h, lambda *a: lib().rrt_plan_relax_stats(self._h, *a))
+        return self._seed("relax", (int(r2),), samples, n, logs)
 
     def relax_poses(self, r2, samples, n, logs=False):
         """rrt_plan_relax_poses: Batch.relax_poses on the Dubins tree of this context's last plan(), launch and result (headings
         included) as grow_poses().  samples: (m, 3) rows (x, y, heading index).  Returns (rc, ResultArrays, j0, old_id int32[j0])."""
-        return self._grow(samples, n, logs, True, r2=r2)
-
-    def relax_poses_ms(self):
-        """time in ms of the stages of the last relax_poses(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's
-        three as grow_ms() gives them"""
-        return _stage_ms(self._h, lambda *a: lib().rrt_plan_relax_poses_ms(self._h, *a), 9, 9)
-
-    def relax_poses_stats(self):
-        """of the last relax_poses(): dict(rounds, fell, sweeps, words)"""
-        return _relax_stats(self._h, lambda *a: lib().rrt_plan_relax_poses_stats(self._h, *a), POSE_RELAX_STATS)
+        return self._seed("relax_poses", (int(r2),), samples, n, logs, True)
 
     def plan_batch(self, queries, ns):
         """rrt_plan_batch: Q independent queries on this context's grid in one call (RRTStandard / RRTStar; an Informed
@@ -758,7 +742,7 @@ class DeviceTree:
         return nn.value, self._idx[:m].copy(), bool(self._los[0]), self._los[1:1 + m].astype(bool)
 
 
-class Batch:
+class Batch(_TreeReports):
     """Q independent queries resident on the device (rrt_batch_*)."""
 
     def __init__(self, ctx: Context, Q: int, n_cap: int, logs: bool = False, serial: bool = False, team=None, team_fault: bool = False,
@@ -836,22 +820,21 @@ class Batch:
         _check(self.ctx.handle, rc, ok=(RRT_OK, RRT_E_GOAL_UNREACHABLE))
         return res
 
+    def _tree(self, q=None):
+        return _Tree(self.ctx.handle, self._h, "rrt_batch_", () if q is None else (int(q),))
+
     def connect_goals(self, q, goals):
         """rrt_batch_connect_goals: connect the goals (M, 2) to the finished tree of query q in one launch.  Returns
         (vertex int32[M], cost float64[M]): per goal the first vertex of [0, j), in stable (cost, index) order of
         cost = vcost[k] + dist(k, goal), with a free line of sight to it, and that cost; (-1, inf) where no vertex connects."""
-        g, vertex, cost = _goal_arrays(goals)
-        _check(self.ctx.handle, lib().rrt_batch_connect_goals(self._h, int(q), g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
-        return vertex, cost
+        return self._tree(q).connect("connect_goals", goals, 2)
 
     def connect_poses(self, q, poses):
         """rrt_batch_connect_poses: connect the goal poses (M, 3) = (x, y, heading index) to the finished Dubins tree of query q in one
         launch.  Returns (vertex int32[M], cost float64[M]): per pose the first vertex of [0, j), in stable (cost, index) order of
         cost = vcost[k] + length of the Dubins word from vertex k's pose to it, whose sweep is free, and that cost; (-1, inf) where
         no vertex connects."""
-        g, vertex, cost = _pose_arrays(poses)
-        _check(self.ctx.handle, lib().rrt_batch_connect_poses(self._h, int(q), g.ctypes.data, g.shape[0], vertex.ctypes.data, cost.ctypes.data))
-        return vertex, cost
+        return self._tree(q).connect("connect_poses", poses, 3)
 
     def connect_poses_counts(self):
         """rrt_batch_connect_poses_counts: (words evaluated, sweeps run) summed over the goals of the last connect_poses"""
@@ -865,8 +848,7 @@ class Batch:
         and cost as connect_goals gives them; the route of goal g is xy[offsets[g]:offsets[g + 1]], the points root .. vertex[g] along
         the tree and then the goal, ids the tree vertices and -1 for the goal row; no rows and length inf where vertex is -1.
         shortcut=True: from each emitted row the route jumps to the farthest later row it has a free line of sight to."""
-        L = lib()
-        return _routes(self.ctx.handle, lambda *a: L.rrt_batch_routes(self._h, int(q), *a), lambda *a: L.rrt_batch_routes_rows(self._h, *a), goals, shortcut)
+        return self._tree(q).routes("routes", goals, 2, RRT_ROUTES_SHORTCUT if shortcut else 0)
 
     def pose_routes(self, q, poses, points=False, shortcut=False):
         """rrt_batch_pose_routes + rrt_batch_pose_routes_rows (+ rrt_batch_pose_routes_points): finished routes from the start pose to
@@ -880,19 +862,10 @@ class Batch:
         which the shortest Dubins word from the kept row's pose sweeps free on the active grid (the next row is never tested); the
         poses stay, the words between them change.  The rows are a subsequence of the raw rows with their ids, length the sum of the
         kept legs' words (<= cost up to rounding), the points those of the kept legs."""
-        L = lib()
-        call = L.rrt_batch_pose_shortcuts if shortcut else L.rrt_batch_pose_routes
-        return _pose_routes(self.ctx.handle, lambda *a: call(self._h, int(q), *a), lambda *a: L.rrt_batch_pose_routes_rows(self._h, *a),
-                            lambda *a: L.rrt_batch_pose_routes_points(self._h, *a), poses, points)
+        return self._tree(q).routes("pose_shortcuts" if shortcut else "pose_routes", poses, 3, RRT_POSE_ROUTES_POINTS if points else 0, points)
 
-    def pose_shortcuts_ms(self):
-        """kernel time in ms of the last pose_routes(shortcut=True): (decision, depth and scan, rows + shortcuts + scan + pack, legs +
-        lengths, points)"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_pose_shortcuts_ms(self._h, *a), 5)
-
-    def pose_routes_ms(self):
-        """kernel time in ms of the last pose_routes(): (decision, depth and scan, rows + legs + lengths, points)"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_pose_routes_ms(self._h, *a), 4)
+    def _keep(self, q, name):
+        return self._tree(q).keep(name, self.n_cap, lambda: self.get_result(q, arrays=False).j)
 
     def keep_tree(self, q):
         """rrt_batch_keep_tree: keep the finished tree of query q on the context's CURRENT grid (set_grid / select_frame since the
@@ -900,16 +873,14 @@ class Batch:
         from the parent to the child.  Afterwards connect_goals / routes of query q run on the new grid over the alive vertices only
         and answer in the original vertex numbers; the tree arrays (get_result) are untouched.  Not cumulative: every call starts
         from the whole tree.  rearm, launch and set_query drop the view."""
-        L = lib()
-        return _keep_tree(self.ctx.handle, lambda *a: L.rrt_batch_keep_tree(self._h, int(q), *a), self.n_cap, lambda: self.get_result(q, arrays=False).j)
+        return self._keep(q, "keep_tree")
 
     def keep_pose_tree(self, q):
         """rrt_batch_keep_pose_tree: keep_tree for a Dubins batch.  An edge is the shortest Dubins word from the parent's pose to the
         child's, free if its sweep is (include/rrt_dubins.h) -- the test plan() accepted it by, so an unchanged grid keeps every
         vertex.  Returns alive bool[j].  Afterwards connect_poses of query q runs on the new grid over the alive vertices only and
         answers in the original vertex numbers; everything else as keep_tree."""
-        L = lib()
-        return _keep_tree(self.ctx.handle, lambda *a: L.rrt_batch_keep_pose_tree(self._h, int(q), *a), self.n_cap, lambda: self.get_result(q, arrays=False).j)
+        return self._keep(q, "keep_pose_tree")
 
     def keep_pose_tree_resident(self, grids, k, q=0):
         """keep_pose_tree(q) on frame k of grids generated on this batch's context (oggen.DeviceGrids): the frame becomes the
@@ -919,70 +890,37 @@ class Batch:
         grids.select(k)
         return self.keep_pose_tree(q)
 
-    def keep_tree_ms(self):
-        """kernel time in ms of the last keep_tree() or keep_pose_tree(): (edge test, pointer jumping, compaction)"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_keep_tree_ms(self._h, *a), 3)
+    def _seed(self, q, name, lead, samples, poses=False):
+        """the seed family on the tree of query q: (j0, old_id int32[j0], log0)"""
+        j0, log0 = C.c_int32(-1), C.c_int32(-1)
+        old_id = self._tree(q).seed(name, lead, samples, poses, self.n_cap, j0, C.byref(log0))[1]
+        return j0.value, old_id, log0.value
 
     def grow(self, q, samples):
         """rrt_batch_grow: seed query q from its finished tree (the alive vertices of its keep_tree view, else the whole tree) and arm
         it for len(samples) more iterations on the context's current grid; then launch() / sync() / get_result(q) as after set_query.
         Returns (j0, old_id int32[j0], log0): the seed's vertices, the original number of each, the log row of the first new
         iteration."""
-        return self._grow(q, samples, False)
-
-    def _grow(self, q, samples, poses):
-        s = _grow_samples(samples, poses)
-        j0, log0 = C.c_int32(-1), C.c_int32(-1)
-        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
-        call = lib().rrt_batch_grow_poses if poses else lib().rrt_batch_grow
-        _check(self.ctx.handle, call(self._h, int(q), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
-        return j0.value, old_id[:j0.value].copy(), log0.value
+        return self._seed(q, "grow", (), samples)
 
     def grow_poses(self, q, samples):
         """rrt_batch_grow_poses: grow() for a Dubins batch.  samples: (m, 3) rows (x, y, heading index); the seed keeps every vertex's
         heading (the view of keep_pose_tree, else the whole tree).  Returns (j0, old_id int32[j0], log0) as grow()."""
-        return self._grow(q, samples, True)
-
-    def grow_ms(self):
-        """kernel time in ms of the seed stages of the last grow(): (renumbering and node slots, bitmap, cell records)"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_grow_ms(self._h, *a), 3, 3)
+        return self._seed(q, "grow_poses", (), samples, True)
 
     def reroot(self, q, root, samples=()):
         """rrt_batch_reroot: re-root the finished tree of query q at its vertex `root` (a number of the tree as get_result gave it;
         alive, if the query has a keep_tree view), then seed and arm it like grow() for len(samples) more iterations.  The reversed
         edges are tested on the context's current grid; what hangs behind a blocked one is cut.  Returns (j0, old_id int32[j0],
         log0): the vertices of the re-rooted tree, the number each had before, the log row of the first new iteration."""
-        s = _grow_samples(np.zeros((0, 2), dtype=np.int32) if len(samples) == 0 else samples)
-        j0, log0 = C.c_int32(-1), C.c_int32(-1)
-        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_reroot(self._h, int(q), int(root), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
-        return j0.value, old_id[:j0.value].copy(), log0.value
-
-    def reroot_ms(self):
-        """kernel time in ms of the stages of the last reroot(): (path, reversed edges, alive and depth, order, costs) and the
-        seed's three as grow_ms() gives them"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_reroot_ms(self._h, *a), 8, 8)
+        return self._seed(q, "reroot", (int(root),), samples)
 
     def relax(self, q, r2, samples=()):
         """rrt_batch_relax: the finished tree of query q (the alive vertices of its keep_tree view, else the whole tree) relaxed to the
         shortest-path tree from its root over its own vertices and the free edges with d2 < r2 (hostprep.radius_threshold(r)), every
         old parent edge included; then seeded and armed like grow() for len(samples) more iterations.  Returns (j0, old_id int32[j0],
         log0): the vertices (all of them), the number each had before, the log row of the first new iteration."""
-        s = _grow_samples(np.zeros((0, 2), dtype=np.int32) if len(samples) == 0 else samples)
-        j0, log0 = C.c_int32(-1), C.c_int32(-1)
-        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_relax(self._h, int(q), int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
-        return j0.value, old_id[:j0.value].copy(), log0.value
-
-    def relax_ms(self):
-        """time in ms of the stages of the last relax(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's three
-        as grow_ms() gives them"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_relax_ms(self._h, *a), 9, 9)
-
-    def relax_stats(self):
-        """of the last relax(): dict(rounds, fell, los, priced) -- rounds run, vertices whose cost fell, lines of sight walked,
-        candidate pairs priced"""
-        return _relax_stats(self.ctx.handle, lambda *a: lib().rrt_batch_relax_stats(self._h, *a))
+        return self._seed(q, "relax", (int(r2),), samples)
 
     def relax_poses(self, q, r2, samples=()):
         """rrt_batch_relax_poses: relax() for a Dubins batch.  The finished tree of query q (the alive vertices of its keep_pose_tree
@@ -990,41 +928,19 @@ class Batch:
         whose shortest Dubins word sweeps free, every old parent edge included; then seeded with its headings and armed like
         grow_poses() for len(samples) more iterations.  samples: (m, 3) rows (x, y, heading index).  Returns (j0, old_id int32[j0],
         log0) as relax()."""
-        s = _grow_samples(np.zeros((0, 3), dtype=np.int32) if len(samples) == 0 else samples, True)
-        j0, log0 = C.c_int32(-1), C.c_int32(-1)
-        old_id = np.full(self.n_cap + 1, -1, dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_relax_poses(self._h, int(q), int(r2), s.ctypes.data, s.shape[0], C.byref(j0), old_id.ctypes.data, C.byref(log0)))
-        return j0.value, old_id[:j0.value].copy(), log0.value
-
-    def relax_poses_ms(self):
-        """time in ms of the stages of the last relax_poses(): (buckets, rounds, parents, alive and depth, order, costs) and the seed's
-        three as grow_ms() gives them"""
-        return _stage_ms(self.ctx.handle, lambda *a: lib().rrt_batch_relax_poses_ms(self._h, *a), 9, 9)
-
-    def relax_poses_stats(self):
-        """of the last relax_poses(): dict(rounds, fell, sweeps, words) -- rounds run, vertices whose cost fell, sweeps run, words
-        evaluated"""
-        return _relax_stats(self.ctx.handle, lambda *a: lib().rrt_batch_relax_poses_stats(self._h, *a), POSE_RELAX_STATS)
+        return self._seed(q, "relax_poses", (int(r2),), samples, True)
 
     def pose_routes_rows(self, rows):
         """rrt_batch_pose_routes_rows alone: (xyh, ids) of the last pose_routes() call, with shortcuts or without, which left `rows` rows"""
-        xyh = np.empty((int(rows), 3), dtype=np.int32)
-        ids = np.empty(int(rows), dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_pose_routes_rows(self._h, xyh.ctypes.data, ids.ctypes.data, int(rows)))
-        return xyh, ids
+        return self._tree().rows("pose_routes", 3, rows)
 
     def pose_routes_points(self, points):
         """rrt_batch_pose_routes_points alone: the points of the last pose_routes(points=True) call, which left `points` points"""
-        pts = np.empty((int(points), 2), dtype=np.float64)
-        _check(self.ctx.handle, lib().rrt_batch_pose_routes_points(self._h, pts.ctypes.data, int(points)))
-        return pts
+        return self._tree().points(points)
 
     def routes_rows(self, rows):
         """rrt_batch_routes_rows alone: (xy, ids) of the last routes() call, which left `rows` rows"""
-        xy = np.empty((int(rows), 2), dtype=np.int32)
-        ids = np.empty(int(rows), dtype=np.int32)
-        _check(self.ctx.handle, lib().rrt_batch_routes_rows(self._h, xy.ctypes.data, ids.ctypes.data, int(rows)))
-        return xy, ids
+        return self._tree().rows("routes", 2, rows)
 
     def debug_cycles(self, q):
         out = (C.c_uint64 * 38)()

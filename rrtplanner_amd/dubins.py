@@ -105,8 +105,33 @@ def dubins_polyline(pose0, pose1, rho, n_headings, ds=0.5):
     return np.asarray(pose0[:2], dtype=np.float64) + out * rho
 
 
+class DubinsTree(TreeDiGraph):
+    """TreeDiGraph whose nodes also carry `heading` and whose edge `dist` is the Dubins arc length."""
+
+    def _materialise(self):
+        dub = self.__dict__.get("_dub")
+        lazy = self.__dict__.get("_lazy")
+        super()._materialise()
+        if lazy is None or dub is None:
+            return
+        heads, rho, nh = dub
+        _, points, parent, _ = lazy
+        node, succ = self.__dict__["_td_node"], self.__dict__["_td_adj"]
+        for v, a in node.items():
+            a["heading"] = int(heads[v])
+        ch = np.arange(1, len(parent))
+        if ch.size:
+            pa = parent[1:]
+            L = dubins_shortest(points[pa, 0], points[pa, 1], _TWOPI * heads[pa] / nh, points[ch, 0], points[ch, 1], _TWOPI * heads[ch] / nh, rho)[3]
+            for p, c, d in zip(pa.tolist(), ch.tolist(), L.tolist()):
+                succ[p][c]["dist"] = d
+
+
 class _DubinsBase(RRT):
     _STAR = False
+    _STATS = ("j", "sum_j", "sum_cells_nn", "sum_near", "sum_cells_cand", "n_los_cand")  # last_stats
+    _TREE_ROUTE = None
+    _TREE = DubinsTree
 
     def __init__(self, og: np.ndarray, n: int, rho: float, n_headings: int = 64, costfn: callable = None, pbar: bool = True, seed: int = 0):
         super().__init__(og, n, costfn=costfn, pbar=pbar, seed=seed)
@@ -151,30 +176,25 @@ class _DubinsBase(RRT):
         if rc == _ffi.RRT_E_GOAL_UNREACHABLE:
             raise IndexError(f"index {hostprep.INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")  # as rrt.py:317-318
         res.xs, res.xg = xs, xg
-        self.last_stats = {k: getattr(res, k) for k in ("j", "sum_j", "sum_cells_nn", "sum_near", "sum_cells_cand", "n_los_cand")}
+        self.last_stats = {k: getattr(res, k) for k in self._STATS}
         return res
 
-    def _materialise_dubins(self, res) -> Tuple[nx.DiGraph, int]:
+    def _materialise(self, res) -> Tuple[nx.DiGraph, int]:
         """The reference's graph contract (rrt.py:334-369) with poses: node attributes `pt` (int64 (2,)) and `heading` (int),
         edge attributes `dist` (arc length of the Dubins word, float) and `cost` (np.float64)."""
-        n, j, found = res.n, res.j, bool(res.found)
-        rows = n + 1 if found else n
-        live = j + 1 if found else j
-        points = np.full((rows, 2), hostprep.INT64_MIN, dtype=np.int64)
-        vcosts = np.full((rows,), np.inf)
-        heads = np.zeros(rows, dtype=np.int64)
-        points[:live], vcosts[:live], heads[:live] = res.pts[:live], res.vcost[:live], res.head[:live]
-        vgoal = int(res.vgoal)
+        T, vgoal = super()._materialise(res)
+        found = bool(res.found)
+        heads = np.zeros(res.n + found, dtype=np.int64)
+        heads[:res.j + found] = res.head[:res.j + found]
         if found:
-            points[n], vcosts[n], heads[n] = res.xg[:2], vcosts[vgoal], res.xg[2]
-        T = DubinsTree.from_arrays(vgoal, points, np.array(res.parent[:live], dtype=np.int64), vcosts)
+            heads[res.n] = res.xg[2]
         T.__dict__["_dub"] = (heads, self.rho, self.n_headings)
         return T, vgoal
 
     def _plan_dubins(self, xstart, xgoal, **kw):
         bar = tqdm(total=self.n) if self.pbar else None
         try:
-            out = self._materialise_dubins(self._run_dubins(xstart, xgoal, **kw))
+            out = self._materialise(self._run_dubins(xstart, xgoal, **kw))
             if bar is not None:
                 bar.update(self.n)
         finally:
@@ -226,8 +246,7 @@ class _DubinsBase(RRT):
         RuntimeError before any plan() and after set_og / set_og_resident / set_n until the next plan(); ValueError for a pose
         outside the grid or a heading outside [0, n_headings) other than -1."""
         g = self._pose_array(poses)
-        if self._tree_resident is None:
-            raise RuntimeError("connect_poses: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        self._keep_guard("connect_poses")
         nh = self.n_headings
         anyh = g[:, 2] < 0
         rows = np.where(anyh, nh, 1)
@@ -296,8 +315,7 @@ class _DubinsBase(RRT):
         Heading -1 (any arrival heading) is resolved first, by one connect_poses call for those poses.  It takes no T: the tree is the
         one resident on the device.  RuntimeError / ValueError as connect_poses."""
         g = self._pose_array(poses)
-        if self._tree_resident is None:
-            raise RuntimeError("routes_to_poses: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
+        self._keep_guard("routes_to_poses")
         anyh = np.flatnonzero(g[:, 2] < 0)
         if anyh.size:
             g = g.copy()
@@ -357,50 +375,19 @@ class _DubinsBase(RRT):
 
         RuntimeError / ValueError as connect_poses; ValueError when m does not fit (it names the room); IndexError as plan() when
         the goal pose is unreachable and rows are left (the grown tree stays resident)."""
-        return self._grow_poses_call("grow_poses", m, None)
+        return self._tree_call("grow_poses", m)
 
-    def _grow_poses_call(self, who: str, m: int, r2):
-        """grow_poses (r2 is None) and relax_poses (r2: its threshold): the refusals of the classes, the draws and the context's call"""
+    def _tree_call_refusals(self, who: str):
+        if not who.endswith("_poses"):
+            super()._tree_call_refusals(who)  # (grow and reroot take straight-line trees only: refused there)
         if self._custom_cost:
             raise ValueError(f"{who}: the Dubins planners run with the arc-length cost on the device; a Python costfn has no tree there")
-        self._keep_guard(who, np.asarray(self.og).shape)
-        m = int(m)
-        if m < 0:
-            raise ValueError(f"{who}: m={m}")
-        ctx = self._device()
-        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow_poses() / relax_poses(), or the alive ones of the last keep_pose_tree
-        if j0 == 0:
-            raise ValueError(f"{who}: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
-        if j0 + m > int(self.n):
-            raise ValueError(f"{who}: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
+
+    def _draw_samples(self, m: int):
+        """m pose samples (x, y, heading index) drawn as plan() draws its n: m free cells (like rrt.py:240, one block), then m heading indices"""
         cells = hostprep.draw_free_samples(self.rand_gen, self.free, m)
         headings = self.rand_gen.integers(0, self.n_headings, size=m)
-        samples = np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), headings])
-        bar = tqdm(total=m) if self.pbar else None
-        try:
-            self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
-            try:
-                rc, res, j0, old_id = ctx.grow_poses(samples, int(self.n)) if r2 is None else ctx.relax_poses(r2, samples, int(self.n))
-            except _ffi.RRTError as e:
-                if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
-                    self._tree_resident = "device"
-                raise
-            self._tree_resident = "device"
-            self.last_grow_ids = old_id
-            if r2 is not None:
-                self.last_relax = ctx.relax_poses_stats()
-            self._grow_j0 = int(res.j)
-            self.last_stats = {k: getattr(res, k) for k in ("j", "sum_j", "sum_cells_nn", "sum_near", "sum_cells_cand", "n_los_cand")}
-            if rc == _ffi.RRT_E_GOAL_UNREACHABLE:  # (as plan(): the grown tree is complete and resident all the same)
-                raise IndexError(f"index {hostprep.INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")
-            res.xs, res.xg = None, self._grow_xg
-            out = self._materialise_dubins(res)
-            if bar is not None:
-                bar.update(m)
-        finally:
-            if bar is not None:
-                bar.close()
-        return out
+        return np.column_stack([np.asarray(cells, dtype=np.int64).reshape(m, 2), headings])
 
     def relax_poses(self, r: float = None, m: int = 0) -> Tuple[nx.DiGraph, int]:
         """Choose every parent of the Dubins tree of the last plan() again (rrt_plan_relax_poses): the vertices and their poses stay,
@@ -425,7 +412,7 @@ class _DubinsBase(RRT):
             raise ValueError("relax_poses: this planner has no r_rewire: pass r, the radius of the candidate edges in cells")
         if not (float(r) > 0):
             raise ValueError(f"relax_poses: r={r}")
-        return self._grow_poses_call("relax_poses", m, hostprep.radius_threshold(r))
+        return self._tree_call("relax_poses", m, hostprep.radius_threshold(r))
 
     def path_points(self, T: nx.DiGraph, path: list, ds: float = 0.5) -> np.ndarray:
         """(M, 2) float polyline of the vehicle's path along the vertices of `path` (from route2gv)."""
@@ -434,28 +421,6 @@ class _DubinsBase(RRT):
             a, b = T.nodes[u], T.nodes[v]
             legs.append(dubins_polyline((*a["pt"], a["heading"]), (*b["pt"], b["heading"]), self.rho, self.n_headings, ds))
         return np.concatenate(legs) if legs else np.zeros((0, 2))
-
-
-class DubinsTree(TreeDiGraph):
-    """TreeDiGraph whose nodes also carry `heading` and whose edge `dist` is the Dubins arc length."""
-
-    def _materialise(self):
-        dub = self.__dict__.get("_dub")
-        lazy = self.__dict__.get("_lazy")
-        super()._materialise()
-        if lazy is None or dub is None:
-            return
-        heads, rho, nh = dub
-        _, points, parent, _ = lazy
-        node, succ = self.__dict__["_td_node"], self.__dict__["_td_adj"]
-        for v, a in node.items():
-            a["heading"] = int(heads[v])
-        ch = np.arange(1, len(parent))
-        if ch.size:
-            pa = parent[1:]
-            L = dubins_shortest(points[pa, 0], points[pa, 1], _TWOPI * heads[pa] / nh, points[ch, 0], points[ch, 1], _TWOPI * heads[ch] / nh, rho)[3]
-            for p, c, d in zip(pa.tolist(), ch.tolist(), L.tolist()):
-                succ[p][c]["dist"] = d
 
 
 class RRTDubins(_DubinsBase):

@@ -479,6 +479,9 @@ class RRT(object):
 
     _ALG = None
     _GROWS = False  # does grow() take this class's trees?  (RRTStandard and RRTStar)
+    _STATS = ("j", "i_switch", "sum_j", "sum_cells_nn", "sum_near", "sum_cells_cand", "n_los_cand", "n_rewired", "n_propagated")  # last_stats
+    _TREE_ROUTE = "kernel"  # last_route after a tree call (the Dubins planners keep none)
+    _TREE = TreeDiGraph  # what _materialise returns
 
     def __init__(self, og: np.ndarray, n: int, costfn: callable = None, pbar: bool = True, seed: int = 0):
         self.pbar = pbar
@@ -593,13 +596,14 @@ class RRT(object):
         self._grid_dirty = False
         self._tree_resident = None
 
-    def _keep_guard(self, who: str, shape):
+    def _keep_guard(self, who: str, shape=None):
+        """`who` needs the tree of the last plan() on the device (and, with a shape, a grid of the shape it was planned on)"""
         if self._tree_resident is None:
             raise RuntimeError(f"{who}: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
         if self._tree_resident == "host":
             raise ValueError(f"{who}: the last plan() ran on the host route (a custom cost function has no device cost; a grid or n beyond "
                              "the kernels' range is not planned on the device), so its tree is not resident on the device")
-        if tuple(shape) != tuple(np.asarray(self.og).shape):
+        if shape is not None and tuple(shape) != tuple(np.asarray(self.og).shape):
             raise ValueError(f"{who}: the new grid is {tuple(shape)}, the tree was planned on {tuple(np.asarray(self.og).shape)}")
 
     def keep_tree(self, og_new: np.ndarray) -> np.ndarray:
@@ -621,11 +625,15 @@ class RRT(object):
         """the host steps of keep_tree and of the Dubins planners' keep_pose_tree; `who` is also the context's call"""
         og_new = np.asarray(og_new)
         self._keep_guard(who, og_new.shape)
+        return self._keep_call(who, og_new, True)
+
+    def _keep_call(self, who: str, og_new, upload: bool) -> np.ndarray:
+        """og_new becomes the planner's grid (upload=False: it is the context's active grid already) and the context keeps the tree on it"""
         self._tree_resident = None  # (until the call below has succeeded: a failure leaves no tree for this grid)
         self.og = og_new
         self.free = np.argwhere(og_new == 0)
-        self._grid_dirty = True
-        alive = getattr(self._device(), who)()
+        self._grid_dirty = upload
+        alive = getattr(self._device() if upload else self._ctx, who)()
         self._tree_resident = "device"
         self._grow_j0 = int(alive.sum())
         return alive
@@ -641,14 +649,7 @@ class RRT(object):
             raise ValueError("grids were generated on a different device context: use oggen.DeviceGrids(planner.device_context(), ...)")
         self._keep_guard(who + "_resident", grids.host[k].shape)
         grids.select(k)  # checks the context's grid generation; when it raises nothing has changed and the tree stays
-        self._tree_resident = None  # (until the call below has succeeded: a failure leaves no tree for this grid)
-        self.og = grids.host[k]
-        self.free = np.argwhere(self.og == 0)
-        self._grid_dirty = False
-        alive = getattr(self._ctx, who)()
-        self._tree_resident = "device"
-        self._grow_j0 = int(alive.sum())
-        return alive
+        return self._keep_call(who, grids.host[k], False)
 
     def grow(self, m: int) -> Tuple[nx.DiGraph, int]:
         """Spend m more samples on the tree of the last plan() (rrt_plan_grow): after keep_tree the region behind a new obstacle has
@@ -666,7 +667,7 @@ class RRT(object):
 
         RuntimeError / ValueError as connect_goals; ValueError when m does not fit (it names the room), for RRTStarInformed, the
         Dubins planners, rewire="correct", the large-grid route and a custom cost function."""
-        return self._grow_or_reroot("grow", m, None)
+        return self._tree_call("grow", m)
 
     def reroot(self, vertex: int, m: int = 0) -> Tuple[nx.DiGraph, int]:
         """The start moved: re-root the tree of the last plan() at one of its vertices instead of planning again (rrt_plan_reroot).
@@ -686,7 +687,7 @@ class RRT(object):
         new numbering; a later plan() takes its own xstart as ever.
 
         Raises as grow; ValueError for a vertex outside the tree or one that is not alive."""
-        return self._grow_or_reroot("reroot", m, vertex)
+        return self._tree_call("reroot", m, vertex)
 
     def relax(self, r: float = None, m: int = 0) -> Tuple[nx.DiGraph, int]:
         """Choose every parent of the tree of the last plan() again (rrt_plan_relax): the vertices stay, and the tree becomes the
@@ -709,64 +710,69 @@ class RRT(object):
             raise ValueError("relax: this planner has no r_rewire: pass r, the radius of the candidate edges in cells")
         if not (float(r) > 0):
             raise ValueError(f"relax: r={r}")
-        out = self._grow_or_reroot("relax", m, None, r2=hostprep.radius_threshold(r))
-        return out
+        return self._tree_call("relax", m, hostprep.radius_threshold(r))
 
-    def _grow_or_reroot(self, who: str, m: int, vertex, r2=None):
-        """grow (vertex is None), reroot and relax (r2: its threshold): the refusals of the classes, the draws and the context's call"""
+    def _tree_call_refusals(self, who: str):
+        """the trees of this class that the tree call `who` does not take"""
         if not self._GROWS:
-            if r2 is not None:
+            if who == "relax":
                 raise ValueError(f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, which is not rebuilt)")
             raise ValueError(f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, a Dubins tree headings, which the seed does not rebuild)"
-                             if vertex is None else
+                             if who == "grow" else
                              f"{who}: RRTStandard and RRTStar only (an Informed tree carries ellipse state, which is not rebuilt; a Dubins word is not reversible)")
         if self._custom_cost:
             raise ValueError(f"{who}: a custom cost function runs on the host route: its tree is not resident on the device")
         if _rewire_mode(getattr(self, "rewire", "reference")):
             raise ValueError(f'{who}: rewire="correct" keeps child lists on the device, which the seed does not rebuild')
         if self.last_route == "kernel-large" or self._on_the_large_grid_kernel():
-            raise ValueError(f"{who}: the large-grid route (grids beyond 2048 cells a side) is not {'relaxed' if r2 is not None else 'grown' if vertex is None else 're-rooted'}")
-        self._keep_guard(who, np.asarray(self.og).shape)
+            raise ValueError(f"{who}: the large-grid route (grids beyond 2048 cells a side) is not {'relaxed' if who == 'relax' else 'grown' if who == 'grow' else 're-rooted'}")
+
+    def _draw_samples(self, m: int):
+        """m samples drawn from self.free as plan() draws its n: packed cells"""
+        if getattr(self, "_free_packed_of", None) is not self.free:  # (free is replaced, never edited in place: set_og / set_og_resident)
+            self._free_packed, self._free_packed_of = hostprep.pack_cells(self.free), self.free
+        return hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, m)
+
+    def _tree_call(self, who: str, m: int, *lead):
+        """The calls that replace the tree of the last plan() by one seeded from it -- grow, reroot (lead: the vertex), relax (lead: the
+        threshold r2) and the Dubins planners' grow_poses and relax_poses: the refusals of the classes, the draws and the context's
+        call of that name"""
+        self._tree_call_refusals(who)
+        self._keep_guard(who)
         m = int(m)
         if m < 0:
             raise ValueError(f"{who}: m={m}")
-        j0 = int(self._grow_j0)  # the vertices of the last plan() / grow() / reroot(), or the alive ones of the last keep_tree
+        j0 = int(self._grow_j0)  # the vertices of the last plan() or tree call, or the alive ones of the last keep_tree / keep_pose_tree
         if j0 == 0:
             raise ValueError(f"{who}: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
         if j0 + m > int(self.n):
             raise ValueError(f"{who}: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
-        if vertex is not None:
-            vertex = int(vertex)
-            if vertex < 0:
-                raise ValueError(f"reroot: vertex={vertex}")
+        if who == "reroot":
+            lead = (int(lead[0]),)
+            if lead[0] < 0:
+                raise ValueError(f"reroot: vertex={lead[0]}")
         ctx = self._device()
-        if getattr(self, "_free_packed_of", None) is not self.free:
-            self._free_packed, self._free_packed_of = hostprep.pack_cells(self.free), self.free
         state0 = self.rand_gen.bit_generator.state
-        samples = hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, m)
+        samples = self._draw_samples(m)
         bar = tqdm(total=m) if self.pbar else None
         try:
             self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
             try:
-                if r2 is not None:
-                    rc, res, j0, old_id = ctx.relax(r2, samples, int(self.n))
-                else:
-                    rc, res, j0, old_id = ctx.grow(samples, int(self.n)) if vertex is None else ctx.reroot(vertex, samples, int(self.n))
+                rc, res, j0, old_id = getattr(ctx, who)(*lead, samples, int(self.n))
             except _ffi.RRTError as e:
                 if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
                     self._tree_resident = "device"
-                    if vertex is not None and e.code == _ffi.RRT_E_ARG and "root=" in str(e):
+                    if who == "reroot" and e.code == _ffi.RRT_E_ARG and "root=" in str(e):
                         self.rand_gen.bit_generator.state = state0  # (a refused vertex spends no draws)
                         raise ValueError(f"reroot: {str(e).split(': ', 2)[-1]}") from e
                 raise
             self._tree_resident = "device"
-            self.last_route = "kernel"
+            self.last_route = self._TREE_ROUTE or self.last_route
             self.last_grow_ids = old_id
-            if r2 is not None:
-                self.last_relax = ctx.relax_stats()
+            if who.startswith("relax"):
+                self.last_relax = getattr(ctx, who + "_stats")()
             self._grow_j0 = int(res.j)
-            self.last_stats = {k: getattr(res, k) for k in ("j", "i_switch", "sum_j", "sum_cells_nn", "sum_near",
-                                                              "sum_cells_cand", "n_los_cand", "n_rewired", "n_propagated")}
+            self.last_stats = {k: getattr(res, k) for k in self._STATS}
             if rc == _ffi.RRT_E_GOAL_UNREACHABLE:  # (as plan(): the grown tree is complete and resident all the same)
                 raise IndexError(f"index {INT64_MIN} is out of bounds for axis 0 with size {np.asarray(self.og).shape[0]}")
             res.xg = self._grow_xg
@@ -795,13 +801,11 @@ class RRT(object):
 
     # ------------------------------------------------------------------ device plumbing
     def _device(self) -> "_ffi.Context":
-        if self._ctx is None:
-            self._ctx = _ffi.Context(self.device_id)
-            self._grid_dirty = True
+        ctx = self.device_context()
         if self._grid_dirty:
-            self._ctx.set_grid(hostprep.og_nonzero(self.og))
+            ctx.set_grid(hostprep.og_nonzero(self.og))
             self._grid_dirty = False
-        return self._ctx
+        return ctx
 
     def _run(self, alg: int, xstart, xgoal, r_rewire=None, r_goal=None, logs=False, rewire=False, large_grid=False):
         """Drive one query through the C ABI.  Returns the ResultArrays (+ ellipse log inputs)."""
@@ -816,9 +820,7 @@ class RRT(object):
         self._tree_resident = None
         bitgen = self.rand_gen.bit_generator
         state0 = bitgen.state
-        if getattr(self, "_free_packed_of", None) is not self.free:  # (free is replaced, never edited in place: set_og / set_og_resident)
-            self._free_packed, self._free_packed_of = hostprep.pack_cells(self.free), self.free
-        samples = hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, n)  # n draws, as rrt.py:421/502/696
+        samples = self._draw_samples(n)  # n draws, as rrt.py:421/502/696
         Cm = None
         if alg == _ffi.ALG_INFORMED:
             try:
@@ -845,7 +847,7 @@ class RRT(object):
             # unit-ball stream for the remaining iterations and resume on the device.
             i_sw = res.i_switch
             bitgen.state = state0
-            hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, i_sw)
+            self._draw_samples(i_sw)
             if Cm is None:
                 hostprep.rotation_to_world_frame(xs, xg)  # raises like rrt.py:609-612 would
                 raise np.linalg.LinAlgError("rotation_to_world_frame is not finite (xstart == xgoal?)")
@@ -857,8 +859,7 @@ class RRT(object):
             # rrt.py:317-318: the next argsort entry is an unfilled row -> og[INT64_MIN, ...]
             raise IndexError(f"index {INT64_MIN} is out of bounds for axis 0 with size {W}")
         res.xs, res.xg, res.Cm = xs, xg, Cm
-        self.last_stats = {k: getattr(res, k) for k in ("j", "i_switch", "sum_j", "sum_cells_nn", "sum_near",
-                                                          "sum_cells_cand", "n_los_cand", "n_rewired", "n_propagated")}
+        self.last_stats = {k: getattr(res, k) for k in self._STATS}
         return res
 
     def _materialise(self, res) -> Tuple[nx.DiGraph, int]:
@@ -873,9 +874,9 @@ class RRT(object):
         vcosts[:live] = res.vcost[:live]
         vgoal = int(res.vgoal)
         if found:
-            points[n] = res.xg
+            points[n] = res.xg[:2]
             vcosts[n] = vcosts[vgoal]
-        return TreeDiGraph.from_arrays(vgoal, points, np.array(res.parent[:live], dtype=np.int64), vcosts), vgoal
+        return self._TREE.from_arrays(vgoal, points, np.array(res.parent[:live], dtype=np.int64), vcosts), vgoal
 
     def build_graph(self, vgoal, points, parents, vcosts) -> nx.DiGraph:
         """DiGraph with every row of `points` as a node (`pt`) and one edge per tree link with
@@ -991,11 +992,7 @@ class RRT(object):
         RuntimeError before any plan() and after set_og / set_og_resident / set_n until the next plan(); ValueError for a goal
         outside the grid and when the last plan() ran on the host (a custom cost function, or a problem beyond the kernels)."""
         g = self._goal_array(goals)
-        if self._tree_resident is None:
-            raise RuntimeError("connect_goals: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
-        if self._tree_resident == "host":
-            raise ValueError("connect_goals: the last plan() ran on the host route (a custom cost function has no device cost; a grid or n beyond "
-                             "the kernels' range is not planned on the device), so its tree is not resident on the device")
+        self._keep_guard("connect_goals")
         return self._device().connect_goals(g)
 
     def connect_poses(self, poses):
@@ -1040,11 +1037,7 @@ class RRT(object):
         sight (collisionfree, walked towards the goal) from where it stands; every leg stays free and the route never gets longer.
         It takes no T: the tree is the one resident on the device.  RuntimeError / ValueError as connect_goals."""
         g = self._goal_array(goals)
-        if self._tree_resident is None:
-            raise RuntimeError("routes_to: no tree on the device: call plan() first (and again after set_og, set_og_resident or set_n)")
-        if self._tree_resident == "host":
-            raise ValueError("routes_to: the last plan() ran on the host route (a custom cost function has no device cost; a grid or n beyond "
-                             "the kernels' range is not planned on the device), so its tree is not resident on the device")
+        self._keep_guard("routes_to")
         vertex, _, length, offsets, xy, _ = self._device().routes(g, shortcut=shortcut)
         if len(vertex) == 0:
             return [], length
