@@ -582,6 +582,10 @@ int rrt_prim_sqrt_u25(rrt_ctx *ctx, uint32_t lo, uint32_t count, double *out);
 /* sqrt of arbitrary doubles as the kernels compute it (ellipse minor axis, rrt.py:622) */
 int rrt_prim_sqrt_f64(rrt_ctx *ctx, const double *in, uint32_t count, double *out);
 
+/* The moving start of a Dubins vehicle: the pose re-root calls.  They are part of this ABI and declared in a file of their own, which
+ * rrtplanner_amd/moving.py binds: the signature table of rrtplanner_amd/_ffi.py lists what THIS file declares, name by name. */
+#include "rrt_hip_moving.h"
+
 #ifdef __cplusplus
 }
 #endif

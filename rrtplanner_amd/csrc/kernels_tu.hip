@@ -54,10 +54,12 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
                     // its r-disc (rrt_relax_*_kernel), which runs the same later stages: not team kernels.  (Units 0 to 9 are taken and
                     // the numbers from 10 on are the team kernels' by tests/test_variant_matrix.py, so the relax kernels live here.)
                     // And a finished Dubins tree relaxed the same way (rrt_pose_relax_*_kernel): it launches the relax kernels' buckets
-                    // and check and shares their device functions, so it lives beside them.
+                    // and check and shares their device functions, so it lives beside them.  And a finished Dubins tree re-rooted at
+                    // one of its poses (rrt_pose_reroot_*_kernel): the round and the parent pass of rrt_pose_relax.h from another root.
 #include "rrt_reroot.h"
 #include "rrt_relax.h"
 #include "rrt_pose_relax.h"
+#include "rrt_pose_reroot.h"
 
 #else  // teams of compute units: the variants that rrt_block_variants.def (included by rrt_block.h) deals to this unit
 #include "rrt_block.h"

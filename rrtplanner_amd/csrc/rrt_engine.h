@@ -146,7 +146,7 @@ struct RRT_PRIVATE DevBuf {
 // table says between which two marks each stage lies, so that stages may share a mark or have a pair each.
 constexpr int STAGE_MARKS = 10;
 constexpr int STAGES_IN_A_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}};               // four marks around three stages
-constexpr int STAGES_IN_A_LONG_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}};  // up to seven marks around six stages
+constexpr int STAGES_IN_A_LONG_ROW[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}, {6, 7}};  // up to eight marks around seven stages
 constexpr int STAGES_IN_PAIRS[][2] = {{0, 1}, {2, 3}, {4, 5}, {6, 7}, {8, 9}};  // a pair around each stage
 struct RRT_PRIVATE StageTimer {
     const int (*stages)[2];
@@ -277,6 +277,10 @@ struct rrt_batch {
     // rrt_batch_relax_poses (a Dubins batch): what it needs beside the two (rrt_pose_relax.h); the timer and the counters are those above,
     // which then count sweeps and words
     DevBuf pose_relax_tmp;                        // PoseRelaxScratch of n_cap vertices
+    // rrt_batch_reroot_poses (a Dubins batch): the root-first input beside the three above (rrt_pose_reroot.h), and its own timer and counters
+    DevBuf pose_reroot_tmp;                             // PoseRerootScratch of n_cap vertices
+    StageTimer pose_reroot_time{STAGES_IN_A_LONG_ROW};  // the seven stages of the last rrt_batch_reroot_poses; the seed's three are seed_time's
+    int64_t pose_reroot_stats[4] = {0, 0, 0, 0};        // of that call: rounds run, vertices reached, sweeps run, words evaluated
     // the rows and points an earlier routes call left are gone (a launch, a rearm, a keep, a grow: they belong to another tree or view)
     void drop_routes() { route_rows = pose_route_rows = pose_route_points = -1; }
 };

@@ -397,6 +397,21 @@ struct PoseRelaxView {
     double *plen;            // [j] the length of the word parent[v] -> v, the old parent edge, evaluated once
 };
 
+// ---- rrt_pose_reroot.h ----
+// The dense input of a pose re-root (the tree arrays or the kept view, as RerootView takes them, with the heading bytes) and where it
+// goes with `root` moved to the front as number 0 and the others in their order: what the relax kernels then take as their input.
+struct PoseRerootView {
+    const uint32_t *nodes;   // [j] the input, dense
+    const int32_t *parent;   // [j] ... its parents in the same numbering; vertex 0 is its root, whatever parent[0] holds
+    const uint8_t *heading;  // [j] ... its heading indices
+    const int32_t *id;       // [j] the number each input vertex has for the caller; null: its own
+    int32_t j, root;         // input vertices [0, j); the new root, one of them
+    uint32_t *f_nodes;       // [j] root first
+    int32_t *f_parent;       // [j] ... the old parents in the new numbers; -1 for the new root and for the old one
+    uint8_t *f_heading;      // [j]
+    int32_t *f_id;           // [j] ... the caller's number of each
+};
+
 // ---- the kernels a host unit launches, by the file that defines them ----
 // rrt_serial.h (units 2 and 3 instantiate it)
 template <bool RW, bool DUB = false>
@@ -476,5 +491,12 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_round_kernel(PoseRel
 __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_parent_kernel(PoseRelaxView pv);
 __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_word_kernel(PoseRelaxView pv, RerootView rv, uint8_t *out_heading, double *word);
 __global__ __launch_bounds__(TPB) void rrt_pose_relax_cost_kernel(RerootView rv, const double *word);
+// rrt_pose_reroot.h (unit 0, beside the pose relax kernels whose round and parent pass it runs from another root)
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_front_kernel(PoseRerootView fv, RelaxView xv);
+__global__ __launch_bounds__(TPB) void rrt_pose_reroot_start_kernel(RerootView rv, const double *plen, double *cost);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_round_kernel(PoseRelaxView pv, const uint8_t *dirty_in, uint8_t *dirty_out, const uint8_t *changed_in,
+                                                                          uint8_t *changed_out, int32_t first);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_parent_kernel(PoseRelaxView pv);
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_check_kernel(RelaxView xv, const int32_t *src, const double *out_vcost, const int32_t *count);
 
 }  // namespace rrtdev

@@ -179,9 +179,13 @@ __device__ __forceinline__ int pose_relax_walk(const PoseRelaxView &pv, const Du
     const DubCfg dc = dub_cfg_fill<RELAX_TPB>((RRT_LDS double *)htab_s, pv.rho, pv.nh, pv.W, pv.xv.H);                              \
     __syncthreads()
 
-__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_round_kernel(PoseRelaxView pv, const uint8_t *dirty_in, uint8_t *dirty_out, const uint8_t *changed_in,
-                                                                         uint8_t *changed_out, int32_t first) {
-    RRT_POSE_RELAX_LDS(ls, dc);
+// One round over the vertices of this workgroup's wavefronts.  OPEN (rrt_pose_reroot.h: the shortest-path tree from a root that the old
+// tree does not hang on): a vertex other than the root may have no old parent (parent outside [0, j): its only edges are the swept
+// ones), and a cost may be +inf -- chord_lower_bound(inf, d2) is inf, so an unreached u never survives a screen, and a bound of inf
+// lets every finite candidate through.  With OPEN false the code is rrt_pose_relax_round_kernel's as it always was.
+template <bool OPEN>
+__device__ __forceinline__ void pose_relax_round(const PoseRelaxView &pv, const DubCfg &dc, const PoseRelaxList &ls, const uint8_t *dirty_in, uint8_t *dirty_out,
+                                                 const uint8_t *changed_in, uint8_t *changed_out, int32_t first) {
     const RelaxView &xv = pv.xv;
     const int lane = (int)threadIdx.x & 63;
     const int waves = (int)(blockDim.x >> 6);
@@ -191,16 +195,17 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_round_kernel(PoseRel
         if (v == 0) continue;
         const uint32_t xy = xv.nodes[v];
         const int p = xv.parent[v], cell = xv.cell_of[v];
-        if (p < 0 || p >= j || cell < 0 || cell >= cells) continue;  // (the cell kernel raised err)
+        const bool has_p = p >= 0 && p < j;
+        if ((!OPEN && !has_p) || cell < 0 || cell >= cells) continue;  // (the cell kernel raised err)
         if (!first) {  // lanes 0 .. 8: the cells of the box; lane 9: the old parent's cell
             const int cx = cell / xv.ncy + lane / 3 - 1, cy = cell % xv.ncy + lane % 3 - 1;
             int look = lane < 9 && cx >= 0 && cx < xv.ncx && cy >= 0 && cy < xv.ncy ? cx * xv.ncy + cy : -1;
-            if (lane == 9) look = xv.cell_of[p];
+            if (lane == 9) look = has_p ? xv.cell_of[p] : -1;
             if (__ballot(look >= 0 && look < cells && dirty_in[look] != 0) == 0) continue;
         }
         const RelaxBox box = relax_box(xv, xy);
         const double cv = relax_load(&xv.cost[v]);
-        const double pc = relax_load(&xv.cost[p]) + pv.plen[v];
+        const double pc = has_p ? relax_load(&xv.cost[p]) + pv.plen[v] : f64_inf();
         double bound = pc < cv ? pc : cv;
         uint32_t bu = 0;  // (strictly below the bound)
         pose_relax_walk<false>(pv, dc, first ? nullptr : changed_in, box, v, xy, (int)pv.heading[v], cv, bound, bu, lane, ls, n_sweeps, n_words);
@@ -223,8 +228,16 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_round_kernel(PoseRel
     }
 }
 
-__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_parent_kernel(PoseRelaxView pv) {
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_round_kernel(PoseRelaxView pv, const uint8_t *dirty_in, uint8_t *dirty_out, const uint8_t *changed_in,
+                                                                         uint8_t *changed_out, int32_t first) {
     RRT_POSE_RELAX_LDS(ls, dc);
+    pose_relax_round<false>(pv, dc, ls, dirty_in, dirty_out, changed_in, changed_out, first);
+}
+
+// The parent rule over the final costs.  OPEN: a vertex whose cost is +inf was not reached: it gets no parent and raises no err (the
+// link kernel cuts it), and RELAX_FELL counts the vertices that were reached, the root among them, instead of those whose cost fell.
+template <bool OPEN>
+__device__ __forceinline__ void pose_relax_parents(const PoseRelaxView &pv, const DubCfg &dc, const PoseRelaxList &ls) {
     const RelaxView &xv = pv.xv;
     const int lane = (int)threadIdx.x & 63;
     const int waves = (int)(blockDim.x >> 6);
@@ -233,18 +246,24 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_parent_kernel(PoseRe
     for (int v = (int)blockIdx.x * waves + ((int)threadIdx.x >> 6); v < j; v += (int)gridDim.x * waves) {  // (v is wave-uniform)
         if (v == 0) {
             if (lane == 0) xv.new_parent[0] = -1;
+            if (OPEN) ++n_fell;
             continue;
         }
         const uint32_t xy = xv.nodes[v];
         const int p = xv.parent[v], cell = xv.cell_of[v];
-        if (p < 0 || p >= j || cell < 0 || cell >= cells) {  // (the cell kernel raised err)
+        const bool has_p = p >= 0 && p < j;
+        if ((!OPEN && !has_p) || cell < 0 || cell >= cells) {  // (the cell kernel raised err)
+            if (lane == 0) xv.new_parent[v] = -1;
+            continue;
+        }
+        const double cv = xv.cost[v], pc = has_p ? xv.cost[p] : f64_inf();
+        if (OPEN && !(cv < f64_inf())) {  // (uniform) not reached
             if (lane == 0) xv.new_parent[v] = -1;
             continue;
         }
         const RelaxBox box = relax_box(xv, xy);
-        const double cv = xv.cost[v], pc = xv.cost[p];
         // the old parent qualifies without a sweep; then only a smaller (c[u], u) can take its place
-        const bool keeps = pc + pv.plen[v] == cv && key_lt(pc, (uint32_t)p, cv, (uint32_t)v);
+        const bool keeps = has_p && pc + pv.plen[v] == cv && key_lt(pc, (uint32_t)p, cv, (uint32_t)v);
         double bk = keeps ? pc : cv;
         uint32_t bu = keeps ? (uint32_t)p : (uint32_t)v;
         const int u = pose_relax_walk<true>(pv, dc, nullptr, box, v, xy, (int)pv.heading[v], cv, bk, bu, lane, ls, n_sweeps, n_words);
@@ -253,10 +272,16 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_parent_kernel(PoseRe
             xv.new_parent[v] = np;
             if (np < 0) atomicOr(xv.err, 1);  // (no edge gives the vertex its cost: the costs are no fixpoint)
         }
-        if (cv < xv.vcost[v]) ++n_fell;
+        if (OPEN) ++n_fell;
+        else if (cv < xv.vcost[v]) ++n_fell;
     }
     // (the sweeps and words of this pass are not counted: the counters are the rounds', each of which meets a pair at most once)
     if (lane == 0 && n_fell) atomicAdd(&xv.stats[RELAX_FELL], (unsigned long long)n_fell);
+}
+
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_relax_parent_kernel(PoseRelaxView pv) {
+    RRT_POSE_RELAX_LDS(ls, dc);
+    pose_relax_parents<false>(pv, dc, ls);
 }
 #undef RRT_POSE_RELAX_LDS
 

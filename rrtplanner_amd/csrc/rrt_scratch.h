@@ -160,3 +160,14 @@ struct PoseRelaxScratch : Carver {
     uint8_t *item_h = take<uint8_t>(cap8);
     uint8_t *out_heading = take<uint8_t>(cap8);
 };
+
+// What a reroot_poses call works in beside the three of relax_poses (rrt_pose_reroot.h); cap = n_cap.  The dense input with the new root
+// moved to the front: points, old parents in the new numbers, the caller's number of each, heading bytes (cap rounded up to 8, last).
+struct PoseRerootScratch : Carver {
+    using Carver::Carver;
+    size_t cap8 = (cap + 7) & ~(size_t)7;
+    uint32_t *f_nodes = take<uint32_t>(cap);
+    int32_t *f_parent = take<int32_t>(cap);
+    int32_t *f_id = take<int32_t>(cap);
+    uint8_t *f_heading = take<uint8_t>(cap8);
+};

@@ -1,6 +1,6 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax, relax_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h, rrt_relax.h and rrt_pose_relax.h.  What the calls share comes first and is written once:
+// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax, relax_poses, reroot_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h, rrt_relax.h, rrt_pose_relax.h and rrt_pose_reroot.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
@@ -617,7 +617,7 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     HIPCHK(ctx, b->seed_time.create(4));
-    b->reroot_time.ran = b->relax_time.ran = 0;  // (the seed's times are this call's from here on: rrt_batch_reroot_ms and rrt_batch_relax_ms have nothing to report)
+    b->reroot_time.ran = b->relax_time.ran = b->pose_reroot_time.ran = 0;  // (the seed's times are this call's from here on: rrt_batch_reroot_ms and rrt_batch_relax_ms have nothing to report)
     return seed_and_arm(who, b, q, seed_from_tree(tree_ref(b, q), j_in), m, j0_out, old_id, log0, poses);
 }
 
@@ -681,9 +681,13 @@ static void reroot_view(RerootView &rv, const RerootScratch &tmp) {
     rv.head = tmp.head;
 }
 
-static int reroot_reset(rrt_ctx *ctx, const RerootView &rv) {
-    const int32_t head0[REROOT_HEAD] = {0, 0, 0, 0, -1, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(rv.head, head0, sizeof head0, hipMemcpyHostToDevice, ctx->stream));
+// keep_err: the order is run a second time in one call (batch_reroot_poses), and what the first run raised stays raised
+static int reroot_reset(rrt_ctx *ctx, const RerootView &rv, bool keep_err = false) {
+    static const int32_t head0[REROOT_HEAD] = {0, 0, 0, 0, -1, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(rv.head, head0, keep_err ? REROOT_ERR * sizeof(int32_t) : sizeof head0, hipMemcpyHostToDevice, ctx->stream));
+    if (keep_err)
+        HIPCHK(ctx, hipMemcpyAsync(rv.head + REROOT_ERR + 1, head0 + REROOT_ERR + 1, (REROOT_HEAD - REROOT_ERR - 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(rv.level_cnt, 0, ((size_t)rv.j + 1) * sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(rv.rank, 0xff, (size_t)rv.j * sizeof(int32_t), ctx->stream));
     return RRT_OK;
@@ -701,25 +705,16 @@ static int leave_without_tree(rrt_batch *b, int32_t q) {
 // the cost stage of a straight-line call: what batch_reroot and batch_relax hand to order_price_and_seed as `price`
 static void price_lines(rrt_ctx *ctx, const RerootView &rv) { hipLaunchKernelGGL(rrt_reroot_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv); }
 
-// Behind rrt_reroot_link_kernel (rv.new_parent, ok, anc, dep of set 0 stand; the caller recorded mark `mark0` of `time`): alive and
-// depth by pointer jumping, the order by (depth, previous number), the costs from the root down (`price` queues that stage) --
-// marks mark0 + 1 .. mark0 + 3 --,
-// `checks` (what the call queues behind the costs), the one wait, then the seed and the arming.  whole: every input vertex has to be
-// alive.  new_start: the descriptor's xs becomes the root's cell.  what: the failure in the call's words.  out_heading: nullptr, or the
-// heading bytes in the new order, which `price` wrote (a Dubins batch: the seed is a pose seed).
-template <typename Price, typename Checks>
-static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, RerootView &rv, const RerootScratch &tmp, StageTimer &time, int mark0, bool whole,
-                                bool new_start, const char *what, Price price, Checks checks, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
-                                const uint8_t *out_heading = nullptr) {
-    rrt_ctx *ctx = b->ctx;
-    QDesc &d = b->h_desc[(size_t)q];
+// Behind rrt_reroot_link_kernel (ok, anc, dep of set 0 stand): alive and depth by pointer jumping, then the order by (depth, previous
+// number) down to rrt_reroot_parent_kernel.  time: nullptr, or the timer whose mark `mark` goes between the two.
+static int order_by_depth(rrt_ctx *ctx, RerootView &rv, const RerootScratch &tmp, StageTimer *time, int mark) {
     const int j = rv.j;
     auto blocks = [](int items) { return dim3(wgs(items, REROOT_TPB)); };
     const int cur = jump_rounds(j, [&](int from) {
         hipLaunchKernelGGL(rrt_reroot_jump_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, (const uint8_t *)tmp.ok[from], (const int32_t *)tmp.anc[from],
                            (const int32_t *)tmp.dep[from], tmp.ok[from ^ 1], tmp.anc[from ^ 1], tmp.dep[from ^ 1], j);
     });
-    HIPCHK(ctx, time.mark(mark0 + 1, ctx->stream));
+    if (time) HIPCHK(ctx, time->mark(mark, ctx->stream));
     rv.key = tmp.dep[cur ^ 1];  // (the set the last round read: free from here on)
     hipLaunchKernelGGL(rrt_reroot_count_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv, (const uint8_t *)tmp.ok[cur], (const int32_t *)tmp.anc[cur],
                        (const int32_t *)tmp.dep[cur]);
@@ -727,6 +722,25 @@ static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, Reroot
     hipLaunchKernelGGL(rrt_reroot_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv);
     hipLaunchKernelGGL(rrt_reroot_place_kernel, dim3(REROOT_WG), dim3(REROOT_TPB), 0, ctx->stream, rv);
     hipLaunchKernelGGL(rrt_reroot_parent_kernel, blocks(j), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    return RRT_OK;
+}
+
+// Behind rrt_reroot_link_kernel (rv.new_parent, ok, anc, dep of set 0 stand; the caller recorded mark `mark0` of `time`): alive and
+// depth by pointer jumping, the order by (depth, previous number) (order_by_depth), the costs from the root down (`price` queues that
+// stage) -- marks mark0 + 1 .. mark0 + 3 --,
+// `checks` (what the call queues behind the costs), the one wait, then the seed and the arming.  whole: every input vertex has to be
+// alive.  new_start: the descriptor's xs becomes the root's cell.  what: the failure in the call's words.  out_heading: nullptr, or the
+// heading bytes in the new order, which `price` wrote (a Dubins batch: the seed is a pose seed).
+// start_heading: nullptr, or with new_start the host byte that `checks` has queued the new root's heading index into (a Dubins batch: the
+// descriptor's hs becomes it).
+template <typename Price, typename Checks>
+static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, RerootView &rv, const RerootScratch &tmp, StageTimer &time, int mark0, bool whole,
+                                bool new_start, const char *what, Price price, Checks checks, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
+                                const uint8_t *out_heading = nullptr, const uint8_t *start_heading = nullptr) {
+    rrt_ctx *ctx = b->ctx;
+    QDesc &d = b->h_desc[(size_t)q];
+    const int j = rv.j;
+    if (const int rc = order_by_depth(ctx, rv, tmp, &time, mark0 + 1)) return rc;
     HIPCHK(ctx, time.mark(mark0 + 2, ctx->stream));
     price();
     HIPCHK(ctx, time.mark(mark0 + 3, ctx->stream));
@@ -743,6 +757,7 @@ static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, Reroot
     if (new_start) {
         d.xs[0] = (int32_t)((uint32_t)head[REROOT_XY] & 0xffffu);
         d.xs[1] = (int32_t)((uint32_t)head[REROOT_XY] >> 16);
+        if (start_heading) d.hs = (int32_t)*start_heading;
     }
     SeedFrom from;
     from.nodes = tmp.out_nodes;
@@ -788,7 +803,7 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     reroot_view(rv, tmp);
     // ---- from here on the query is being replaced ----
     StageTimer &time = b->reroot_time;
-    time.ran = b->relax_time.ran = 0;
+    time.ran = b->relax_time.ran = b->pose_reroot_time.ran = 0;
     b->seed_time.ran = 0;
     b->drop_routes();
     d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
@@ -825,6 +840,65 @@ static void relax_cells(int64_t R, int W, int H, RelaxView &xv) {
     xv.shift = s;
     xv.ncx = across(W);
     xv.ncy = across(H);
+}
+
+// What batch_relax and batch_reroot_poses share of a RelaxView: the grid, the threshold R with its buckets (cells for max(R, 1): R = 0
+// has no near pair, and one cell edge serves), and the arrays of the two scratch buffers.  nodes, parent, vcost and j are the call's.
+static void relax_view(rrt_ctx *ctx, RelaxView &xv, int64_t R, const RelaxScratch &rx, const RerootScratch &tmp) {
+    xv.og = ctx->og;
+    xv.H = ctx->H;
+    xv.R = R;
+    relax_cells(std::max<int64_t>(R, 1), ctx->W, ctx->H, xv);
+    xv.cell_of = rx.cell_of;
+    xv.cell_start = rx.cell_start;
+    xv.cell_fill = rx.cell_fill;
+    xv.items = rx.items;
+    xv.item_xy = rx.item_xy;
+    xv.pos_of = rx.pos_of;
+    xv.cost = rx.cost;
+    xv.new_parent = tmp.new_parent;
+    xv.stats = rx.stats;
+    xv.err = tmp.head + REROOT_ERR;
+}
+
+// ... and of a PoseRelaxView around it (heading is the call's)
+static void pose_relax_view(rrt_ctx *ctx, PoseRelaxView &pv, const RelaxView &xv, const QDesc &d, const PoseRelaxScratch &px) {
+    pv.xv = xv;
+    pv.W = ctx->W;
+    pv.nh = d.nh;
+    pv.rho = d.rho;
+    pv.item_h = px.item_h;
+    pv.plen = px.plen;
+}
+
+// The rounds of both calls: round(in, first) queues one round that reads the flags of set `in` and writes those of the other.  The host
+// reads the count of changes back behind every RELAX_READ_EVERY-th round and stops behind a look that saw none; a shortest path has
+// fewer than j edges, so j rounds are the most.  rounds: how many ran.  Not settled by then: the query is left without a tree.
+template <typename Round>
+static int relax_rounds(const char *who, rrt_batch *b, int32_t q, const RelaxView &xv, const RelaxScratch &rx, Round round, int64_t &rounds) {
+    rrt_ctx *ctx = b->ctx;
+    const int j = xv.j;
+    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
+    unsigned long long changes = 0, before = 0;
+    bool settled = false;
+    const int64_t most = (int64_t)j + 2 * (RELAX_READ_EVERY - 1);
+    rounds = 0;
+    while (!settled && rounds < most) {
+        const int in = (int)(rounds & 1);
+        HIPCHK(ctx, hipMemsetAsync(rx.dirty[in ^ 1], 0, cells, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(rx.changed[in ^ 1], 0, (size_t)j, ctx->stream));
+        round(in, (int32_t)(rounds == 0));
+        HIPCHK(ctx, hipGetLastError());
+        if (++rounds % RELAX_READ_EVERY != 0 && rounds < most) continue;
+        HIPCHK(ctx, hipMemcpyAsync(&changes, xv.stats + RELAX_CHANGES, sizeof changes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream_spin(ctx->stream));
+        settled = changes == before;  // (nothing changed since the last look: the last round changed nothing)
+        before = changes;
+    }
+    if (settled) return RRT_OK;
+    if (const int rc = leave_without_tree(b, q)) return rc;
+    return fail(ctx, RRT_E_INTERNAL, "%s: the costs of query %d still fell in round %lld of a tree of %d vertices: the query is left without a tree", who, q,
+                (long long)rounds, j);
 }
 
 // The vertices stay and every parent is chosen again: the costs relaxed in rounds to their fixpoint, the parents in a pass over the
@@ -867,37 +941,17 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     reroot_view(rv, tmp);
     const int j = j_in;
     RelaxView xv{};
-    xv.og = ctx->og;
-    xv.H = ctx->H;
     xv.nodes = rv.nodes;
     xv.parent = rv.parent;
     xv.vcost = t.kept > 0 ? t.live_vcost : t.vcost;
     xv.j = j;
-    xv.R = r2;
-    relax_cells(r2, ctx->W, ctx->H, xv);
-    xv.cell_of = rx.cell_of;
-    xv.cell_start = rx.cell_start;
-    xv.cell_fill = rx.cell_fill;
-    xv.items = rx.items;
-    xv.item_xy = rx.item_xy;
-    xv.pos_of = rx.pos_of;
-    xv.cost = rx.cost;
-    xv.new_parent = tmp.new_parent;
-    xv.stats = rx.stats;
-    xv.err = tmp.head + REROOT_ERR;
+    relax_view(ctx, xv, r2, rx, tmp);
     const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
     const PoseRelaxScratch px = poses ? b->pose_relax_tmp.carve<PoseRelaxScratch>() : PoseRelaxScratch(nullptr, 0);
-    if (poses) {
-        pv.xv = xv;
-        pv.W = ctx->W;
-        pv.nh = d.nh;
-        pv.rho = d.rho;
-        pv.item_h = px.item_h;
-        pv.plen = px.plen;
-    }
+    if (poses) pose_relax_view(ctx, pv, xv, d, px);
     // ---- from here on the query is being replaced ----
     StageTimer &time = b->relax_time;
-    time.ran = b->reroot_time.ran = 0;
+    time.ran = b->reroot_time.ran = b->pose_reroot_time.ran = 0;
     b->seed_time.ran = 0;
     b->drop_routes();
     d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
@@ -914,36 +968,20 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     if (poses) hipLaunchKernelGGL(rrt_pose_relax_item_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv);
     HIPCHK(ctx, time.mark(1, ctx->stream));
     int64_t rounds = 0;
-    unsigned long long changes = 0, before = 0;
-    bool settled = false;
     double *costs[2] = {xv.cost, xv.cost};
 #ifdef RRT_RELAX_TWO_ARRAYS  // (experiment build: a round reads the costs of the round before alone; out_vcost is free until the cost kernel)
     costs[1] = tmp.out_vcost;
     HIPCHK(ctx, hipMemcpyAsync(costs[1], costs[0], (size_t)j * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
 #endif
-    const int64_t most = (int64_t)j + 2 * (RELAX_READ_EVERY - 1);
-    while (!settled && rounds < most) {
-        const int in = (int)(rounds & 1);
-        HIPCHK(ctx, hipMemsetAsync(rx.dirty[in ^ 1], 0, cells, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(rx.changed[in ^ 1], 0, (size_t)j, ctx->stream));
-        if (poses)
-            hipLaunchKernelGGL(rrt_pose_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv, (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1],
-                               (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], (int32_t)(rounds == 0));
-        else
-            hipLaunchKernelGGL(rrt_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv, (const double *)costs[in], costs[in ^ 1],
-                               (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1], (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], (int32_t)(rounds == 0));
-        HIPCHK(ctx, hipGetLastError());
-        if (++rounds % RELAX_READ_EVERY != 0 && rounds < most) continue;
-        HIPCHK(ctx, hipMemcpyAsync(&changes, xv.stats + RELAX_CHANGES, sizeof changes, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, wait_stream_spin(ctx->stream));
-        settled = changes == before;  // (nothing changed since the last look: the last round changed nothing)
-        before = changes;
-    }
-    if (!settled) {
-        if (const int rc = leave_without_tree(b, q)) return rc;
-        return fail(ctx, RRT_E_INTERNAL, "%s: the costs of query %d still fell in round %d of a tree of %d vertices: the query is left without a tree", who, q,
-                    j, j);
-    }
+    if (const int rc = relax_rounds(who, b, q, xv, rx, [&](int in, int32_t first) {
+            if (poses)
+                hipLaunchKernelGGL(rrt_pose_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv, (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1],
+                                   (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], first);
+            else
+                hipLaunchKernelGGL(rrt_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv, (const double *)costs[in], costs[in ^ 1],
+                                   (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1], (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], first);
+        }, rounds))
+        return rc;
     HIPCHK(ctx, time.mark(2, ctx->stream));
     if (poses) hipLaunchKernelGGL(rrt_pose_relax_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv);
     else hipLaunchKernelGGL(rrt_relax_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, xv);
@@ -970,6 +1008,135 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     b->relax_stats[1] = (int64_t)stats[RELAX_FELL];
     b->relax_stats[2] = (int64_t)stats[RELAX_LOS];
     b->relax_stats[3] = (int64_t)stats[RELAX_PRICED];
+    return RRT_OK;
+}
+
+// ---- re-root a finished Dubins tree at one of its poses (rrt_pose_reroot.h) ----
+// batch_relax for a Dubins batch from another root.  The dense input (tree_input) goes root-first into scratch, and that is what the
+// buckets, the item kernel, the rounds and the parent pass of the pose relax see.  The costs start at 0 for the root, at the sums of
+// the old edges' words for what hangs below it in the old tree (the link kernel, the pointer jumping and the order by depth over the
+// OLD parents, then rrt_pose_reroot_start_kernel), and at +inf elsewhere.  What is +inf at the fixpoint is cut; the later stages are
+// order_price_and_seed's with whole = false and new_start = true, and the descriptor's hs becomes the root's heading too.
+static int batch_reroot_poses(const char *who, rrt_batch *b, int32_t q, int32_t root, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0_out,
+                              int32_t *old_id, int32_t *log0) {
+    rrt_ctx *ctx = b->ctx;
+    int j_in = 0;
+    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, true, "", j_in, "rrt_batch_reroot")) return rc;
+    if (b->n_cap > REROOT_WAVES * REROOT_OWN)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
+                    REROOT_WAVES * REROOT_OWN);
+    QDesc &d = b->h_desc[(size_t)q];
+    if (root < 0 || root >= d.j) return fail(ctx, RRT_E_ARG, "%s: root=%d, query %d has the vertices [0, %d)", who, root, q, d.j);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
+    const TreeRef t = tree_ref(b, q);
+    RerootView rv{};
+    rv.og = ctx->og;
+    rv.H = ctx->H;
+    PoseRerootView fv{};
+    // with a view the input is the view: its parents renumbered into scratch, and the root's number in it (-1: not alive)
+    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, root, rv, fv.root, &fv.heading)) return rc;
+    if (fv.root < 0)
+        return fail(ctx, RRT_E_ARG, "%s: root=%d is not alive in the kept view of query %d (%d of %d vertices alive)", who, root, q, j_in, d.j);
+    if (r2 < 0) return fail(ctx, RRT_E_ARG, "%s: r2=%lld: the threshold of the squared distance cannot be negative", who, (long long)r2);
+    if (const int rc = stage_cells(who, b, q, "sample", samples, m, d.nh)) return rc;
+    HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
+    HIPCHK(ctx, b->relax_tmp.reserve<RelaxScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
+    HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
+    HIPCHK(ctx, b->pose_reroot_tmp.reserve<PoseRerootScratch>(b->n_cap));
+    HIPCHK(ctx, b->seed_time.create(4));
+    HIPCHK(ctx, b->pose_reroot_time.create(8));
+    const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
+    const RelaxScratch rx = b->relax_tmp.carve<RelaxScratch>((size_t)RELAX_MAX_CELLS);
+    const PoseRelaxScratch px = b->pose_relax_tmp.carve<PoseRelaxScratch>();
+    const PoseRerootScratch fx = b->pose_reroot_tmp.carve<PoseRerootScratch>();
+    const int j = j_in;
+    fv.nodes = rv.nodes;
+    fv.parent = rv.parent;
+    fv.id = rv.id;
+    fv.j = j;
+    fv.f_nodes = fx.f_nodes;
+    fv.f_parent = fx.f_parent;
+    fv.f_heading = fx.f_heading;
+    fv.f_id = fx.f_id;
+    // from here on the input is the root-first one
+    rv.nodes = fx.f_nodes;
+    rv.parent = fx.f_parent;
+    rv.id = fx.f_id;
+    rv.root = 0;
+    reroot_view(rv, tmp);
+    RelaxView xv{};
+    xv.nodes = fx.f_nodes;
+    xv.parent = fx.f_parent;
+    xv.vcost = nullptr;  // (the costs start from the sums below the new root: no kernel of this call reads the old ones)
+    xv.j = j;
+    relax_view(ctx, xv, r2, rx, tmp);
+    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
+    PoseRelaxView pv{};
+    pv.heading = fx.f_heading;
+    pose_relax_view(ctx, pv, xv, d, px);
+    // ---- from here on the query is being replaced ----
+    StageTimer &time = b->pose_reroot_time;
+    time.ran = b->relax_time.ran = b->reroot_time.ran = 0;
+    b->seed_time.ran = 0;
+    b->drop_routes();
+    d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
+    auto blocks = [](int items) { return dim3(wgs(items, RELAX_TPB)); };
+    const dim3 per_wave(std::clamp<unsigned>(wgs(j, RELAX_TPB / 64), 1, RELAX_MAX_WG));
+    if (const int rc = reroot_reset(ctx, rv)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, RELAX_STATS * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.ok, 1, (size_t)j, ctx->stream));
+    HIPCHK(ctx, time.mark(0, ctx->stream));
+    hipLaunchKernelGGL(rrt_pose_reroot_front_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, fv, xv);
+    hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
+    hipLaunchKernelGGL(rrt_relax_fill_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
+    hipLaunchKernelGGL(rrt_pose_relax_item_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv);
+    HIPCHK(ctx, time.mark(1, ctx->stream));
+    {  // the start: what hangs below the new root in the OLD tree, placed by depth, and its costs along the old edges
+        RerootView sv = rv;
+        sv.new_parent = fx.f_parent;  // (the link kernel and rrt_reroot_parent_kernel only read it)
+        hipLaunchKernelGGL(rrt_reroot_link_kernel, dim3(wgs(j, REROOT_TPB)), dim3(REROOT_TPB), 0, ctx->stream, sv);
+        if (const int rc = order_by_depth(ctx, sv, tmp, nullptr, 0)) return rc;
+        hipLaunchKernelGGL(rrt_pose_reroot_start_kernel, dim3(1), dim3(TPB), 0, ctx->stream, sv, (const double *)px.plen, xv.cost);
+        HIPCHK(ctx, hipGetLastError());
+        if (const int rc = reroot_reset(ctx, rv, true)) return rc;  // (the order runs again behind the parents; an err of this run stays)
+        HIPCHK(ctx, hipMemsetAsync(rv.ok, 1, (size_t)j, ctx->stream));
+    }
+    HIPCHK(ctx, time.mark(2, ctx->stream));
+    int64_t rounds = 0;
+    if (const int rc = relax_rounds(who, b, q, xv, rx, [&](int in, int32_t first) {
+            hipLaunchKernelGGL(rrt_pose_reroot_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv, (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1],
+                               (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], first);
+        }, rounds))
+        return rc;
+    HIPCHK(ctx, time.mark(3, ctx->stream));
+    hipLaunchKernelGGL(rrt_pose_reroot_parent_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv);
+    hipLaunchKernelGGL(rrt_reroot_link_kernel, dim3(wgs(j, REROOT_TPB)), dim3(REROOT_TPB), 0, ctx->stream, rv);
+    HIPCHK(ctx, time.mark(4, ctx->stream));
+    unsigned long long stats[RELAX_STATS] = {0, 0, 0, 0};
+    uint8_t root_heading = 0;
+    char what[256];
+    snprintf(what, sizeof what, "the parents of query %d on the device chosen from its new root are not a tree over the vertices that were reached, or "
+             "its costs summed from the root down are not the fixpoint's", q);
+    auto price = [&] {
+        hipLaunchKernelGGL(rrt_pose_relax_word_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv, rv, px.out_heading, px.word);
+        hipLaunchKernelGGL(rrt_pose_relax_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv, (const double *)px.word);
+    };
+    const int rc = order_price_and_seed(who, b, q, rv, tmp, time, 4, false, true, what, price, [&] {
+        hipLaunchKernelGGL(rrt_pose_reroot_check_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv, (const int32_t *)tmp.src, (const double *)tmp.out_vcost,
+                           (const int32_t *)(tmp.head + REROOT_COUNT));
+        // the new start: the root's cell to the head, where order_price_and_seed reads it, and its heading index
+        HIPCHK(ctx, hipMemcpyAsync(tmp.head + REROOT_XY, tmp.out_nodes, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&root_heading, px.out_heading, 1, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)RRT_OK;
+    }, m, j0_out, old_id, log0, px.out_heading, &root_heading);
+    if (rc != RRT_OK) return rc;
+    b->pose_reroot_stats[0] = rounds;
+    b->pose_reroot_stats[1] = (int64_t)stats[RELAX_FELL];
+    b->pose_reroot_stats[2] = (int64_t)stats[RELAX_LOS];
+    b->pose_reroot_stats[3] = (int64_t)stats[RELAX_PRICED];
     return RRT_OK;
 }
 
@@ -1002,7 +1169,7 @@ extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
     if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
     if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
     if (!b->seed_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
-    if (b->reroot_time.ran || b->relax_time.ran)  // (the seed's times are that call's: rrt_batch_reroot_ms / rrt_batch_relax_ms report them)
+    if (b->reroot_time.ran || b->relax_time.ran || b->pose_reroot_time.ran)  // (the seed's times are that call's: rrt_batch_reroot_ms / rrt_batch_relax_ms report them)
         return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: a reroot or a relax came after the last rrt_batch_grow on this batch");
     HIPCHK(b->ctx, b->seed_time.read(ms, count));
     return RRT_OK;
@@ -1117,6 +1284,54 @@ extern "C" int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]) { return rela
 extern "C" int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_stats", NO_PLAN);
     return s ? rrt_batch_relax_stats(s, out) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_reroot_poses(rrt_batch *b, int32_t q, int32_t root, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id,
+                                      int32_t *log0) {
+    return b ? batch_reroot_poses("rrt_batch_reroot_poses", b, q, root, r2, samples_xyh, m, j0, old_id, log0)
+             : fail(nullptr, RRT_E_ARG, "rrt_batch_reroot_poses: NULL");
+}
+
+extern "C" int rrt_plan_reroot_poses(rrt_ctx *ctx, int32_t root, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id,
+                                     rrt_result *out) {
+    const char *who = "rrt_plan_reroot_poses";
+    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
+    if (!s) return RRT_E_ARG;
+    int32_t log0 = 0;
+    const int rc = batch_reroot_poses(who, s, 0, root, r2, samples_xyh, m, j0, old_id, &log0);
+    return rc != RRT_OK ? rc : run_single(ctx, out);
+}
+
+// ms[0, 7): buckets, start, rounds, parents, alive and depth, order, costs; ms[7, 10): the seed's stages, as rrt_batch_grow_ms reports them
+extern "C" int rrt_batch_reroot_poses_ms(rrt_batch *b, float *ms, int32_t count) {
+    const char *who = "rrt_batch_reroot_poses_ms";
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    if (count < 1 || count > 10) return fail(b->ctx, RRT_E_ARG, "%s: count=%d, a pose re-root has 7 stages and its seed 3", who, count);
+    if (!b->pose_reroot_time.ran || !b->seed_time.ran)
+        return fail(b->ctx, RRT_E_ARG, "%s: no rrt_batch_reroot_poses on this batch yet, its last one failed, or another seed call came after it", who);
+    HIPCHK(b->ctx, b->pose_reroot_time.read(ms, std::min(count, 7)));
+    if (count > 7) HIPCHK(b->ctx, b->seed_time.read(ms + 7, count - 7));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_reroot_poses_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_poses_ms", NO_PLAN);
+    return s ? rrt_batch_reroot_poses_ms(s, ms, count) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_reroot_poses_stats(rrt_batch *b, int64_t out[4]) {
+    const char *who = "rrt_batch_reroot_poses_stats";
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    if (!b->pose_reroot_time.ran)
+        return fail(b->ctx, RRT_E_ARG, "%s: no rrt_batch_reroot_poses on this batch yet, its last one failed, or another seed call came after it", who);
+    for (int k = 0; k < 4; ++k) out[k] = b->pose_reroot_stats[k];
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_reroot_poses_stats(rrt_ctx *ctx, int64_t out[4]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_poses_stats", NO_PLAN);
+    return s ? rrt_batch_reroot_poses_stats(s, out) : RRT_E_ARG;
 }
 
 // ---- the rows of the routes to the goals a decision answered: what rrt_batch_routes and rrt_batch_pose_routes start with ----

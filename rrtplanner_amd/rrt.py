@@ -733,10 +733,11 @@ class RRT(object):
             self._free_packed, self._free_packed_of = hostprep.pack_cells(self.free), self.free
         return hostprep.draw_free_samples_packed(self.rand_gen, self._free_packed, m)
 
-    def _tree_call(self, who: str, m: int, *lead):
+    def _tree_call(self, who: str, m: int, *lead, call=None, stats=None):
         """The calls that replace the tree of the last plan() by one seeded from it -- grow, reroot (lead: the vertex), relax (lead: the
-        threshold r2) and the Dubins planners' grow_poses and relax_poses: the refusals of the classes, the draws and the context's
-        call of that name"""
+        threshold r2), the Dubins planners' grow_poses and relax_poses, and moving.reroot_poses (lead: the vertex, the threshold r2):
+        the refusals of the classes, the draws and the context's call of that name, or `call(ctx, *lead, samples, n)` for a call that is
+        no method of the context; stats(ctx): what such a call leaves in last_relax"""
         self._tree_call_refusals(who)
         self._keep_guard(who)
         m = int(m)
@@ -747,10 +748,10 @@ class RRT(object):
             raise ValueError(f"{who}: no vertex of the tree is alive on this grid (xstart is blocked): there is nothing to grow from")
         if j0 + m > int(self.n):
             raise ValueError(f"{who}: the tree holds {j0} vertices and n={int(self.n)}: room for {int(self.n) - j0} more samples, not {m}")
-        if who == "reroot":
-            lead = (int(lead[0]),)
+        if who.startswith("reroot"):
+            lead = (int(lead[0]),) + lead[1:]
             if lead[0] < 0:
-                raise ValueError(f"reroot: vertex={lead[0]}")
+                raise ValueError(f"{who}: vertex={lead[0]}")
         ctx = self._device()
         state0 = self.rand_gen.bit_generator.state
         samples = self._draw_samples(m)
@@ -758,19 +759,21 @@ class RRT(object):
         try:
             self._tree_resident = None  # (until the call below has succeeded, or has refused and so changed nothing)
             try:
-                rc, res, j0, old_id = getattr(ctx, who)(*lead, samples, int(self.n))
+                rc, res, j0, old_id = (call(ctx, *lead, samples, int(self.n)) if call else getattr(ctx, who)(*lead, samples, int(self.n)))
             except _ffi.RRTError as e:
                 if e.code in (_ffi.RRT_E_ARG, _ffi.RRT_E_UNSUPPORTED) and not getattr(e, "seeded", True):
                     self._tree_resident = "device"
-                    if who == "reroot" and e.code == _ffi.RRT_E_ARG and "root=" in str(e):
+                    if who.startswith("reroot") and e.code == _ffi.RRT_E_ARG and "root=" in str(e):
                         self.rand_gen.bit_generator.state = state0  # (a refused vertex spends no draws)
-                        raise ValueError(f"reroot: {str(e).split(': ', 2)[-1]}") from e
+                        raise ValueError(f"{who}: {str(e).split(': ', 2)[-1]}") from e
                 raise
             self._tree_resident = "device"
             self.last_route = self._TREE_ROUTE or self.last_route
             self.last_grow_ids = old_id
             if who.startswith("relax"):
                 self.last_relax = getattr(ctx, who + "_stats")()
+            elif stats:
+                self.last_relax = stats(ctx)
             self._grow_j0 = int(res.j)
             self.last_stats = {k: getattr(res, k) for k in self._STATS}
             if rc == _ffi.RRT_E_GOAL_UNREACHABLE:  # (as plan(): the grown tree is complete and resident all the same)
