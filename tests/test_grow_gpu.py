@@ -182,7 +182,7 @@ def test_one_query_of_three_grown_the_others_unchanged(gpu_ctx):
     gpu_ctx.set_grid(w["og2"])
     b.keep_tree(0)
     b.keep_tree(2)
-    g, res = grow_checked(b, 0, w["og2"], tree_of(before[0]), True, w["samples"], c, "team")
+    g, res = grow_checked(b, 0, w["og2"], tree_of(before[0]), True, w["samples"], c, "team", Q=3)
     for q in (1, 2):
         r = b.get_result(q)
         assert (r.status, r.j, r.found, r.vgoal) == (before[q].status, before[q].j, before[q].found, before[q].vgoal)

@@ -19,6 +19,7 @@ from posecalls import assert_audit_clean, check_dubins_tree, device_vs_oracle_du
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.oggen import random_connected_pair
 from slabs import fill_batch, hand_over_unitballs, query_of, same_as_oracle
+from treecalls import ONE_SHIFT, TWO_SHIFTS
 
 
 def _id(c):
@@ -128,9 +129,12 @@ def _run_slab_case(ctx, c, kernel):
 def test_slab_radii_on_every_kernel(gpu_ctx, c, kernel):
     name, info = _run_slab_case(gpu_ctx, c, kernel)
     inf = "true" if c["alg"] == 2 else "false"
-    if kernel == "team":  # committer and workers as two kernels (Informed batches keep the one-body kernel)
-        assert ("rrt_block_commit_kernel + rrt_block_work_kernel" in name) == (c["alg"] != 2), name
-        assert name.startswith("rrt_expand_block_kernel<64, 1, true, "), name
+    if kernel == "team":  # one query without a cap: committer and workers as two kernels in two shifts (an Informed one keeps the one-body kernel)
+        assert name == (TWO_SHIFTS if c["alg"] != 2 else "rrt_expand_block_kernel<64, 1, true, true>"), name
+        assert info["created"] == info["last"] == (128 if c["alg"] != 2 else 64), info
+    elif kernel == "team64":  # the cap of 64: the same pair in one shift
+        assert name == (ONE_SHIFT if c["alg"] != 2 else "rrt_expand_block_kernel<64, 1, true, true>"), name
+        assert info["created"] == 64 and info["last"] == 64, info
     elif kernel == "onebody":
         assert name == f"rrt_expand_block_kernel<64, 1, true, {inf}>", name
     elif kernel == "onebody8":

@@ -66,7 +66,7 @@ def _relax(b, q, og8, prev, view, r, samples, c, shape=None, X=None):
     info = b.team_info()
     assert info["timeouts"] == 0 and b.team()[1] == 0, info
     if shape:
-        assert tc.SHAPES[shape][1](b.kernel_name()), b.kernel_name()
+        tc.shape_ran(b, shape)  # (every caller that names its shape has a batch of one query)
     if len(samples) == 0:  # the device's own arrays, by rules of their own
         j0 = len(X.ids)
         assert relaxref.certify(og8, res.pts[:j0], res.parent[:j0], res.vcost[:j0], rc.R_of(r), relaxref.old_edges_of(X.in_parent, X.order)) == []

@@ -8,6 +8,7 @@ import pytest
 import oracle
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pairs
+from treecalls import TWO_SHIFTS
 
 pytestmark = pytest.mark.gpu
 
@@ -65,13 +66,14 @@ def _check_oracle(og8, alg, n, qs, out):
 
 
 def test_config2_full_size_split_team_equals_the_oracle_twice(gpu_ctx):
-    """BASELINE config 2 (RRT*, 1024^2, n = 50 000) on the default team of 64 + 1 as two kernels, two launches on the same buffers."""
+    """BASELINE config 2 (RRT*, 1024^2, n = 50 000) on the default of one query, the committer + worker pair of 64 in two shifts, two
+    launches on the same buffers."""
     og, og8 = _grid()
     gpu_ctx.set_grid(og8)
     n = 50000
     qs = _queries(og, og8, 1, n)
     runs, name, fallbacks = _run(gpu_ctx, qs, n, launches=2)
-    assert name.startswith("rrt_expand_block_kernel<64, 1, true, false> as rrt_block_commit_kernel"), name
+    assert name == TWO_SHIFTS, name
     assert fallbacks == 0
     _check_oracle(og8, 1, n, qs, runs[0])
     assert _equal(runs[1][0], runs[0][0])

@@ -10,11 +10,10 @@ import pytest
 import oracle
 from rrtplanner_amd import _ffi, hostprep
 from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pairs
+from treecalls import ONE_SHIFT, TWO_SHIFTS
 
 pytestmark = pytest.mark.gpu
 
-ONE_SHIFT = "rrt_expand_block_kernel<64, 1, true, false> as rrt_block_commit_kernel + rrt_block_work_kernel<64, 1, false>"
-TWO_SHIFTS = ONE_SHIFT + " in 2 shifts"
 N_MAX = 12000
 
 _cache = {}

@@ -17,13 +17,69 @@ from rrtplanner_amd.oggen import perlin_occupancygrid, random_connected_pair
 
 N, RR = 2000, 24
 R2 = hostprep.radius_threshold(RR)
-SHAPES = {  # launch shape -> (Batch keywords, what the kernel's name has to say)
-    "team": (dict(), lambda s: s.startswith("rrt_expand_block_kernel<") and not s.startswith("rrt_expand_block_kernel<1,")),
-    "team8": (dict(team=8), lambda s: s.startswith("rrt_expand_block_kernel<8,")),
-    "team2": (dict(team=2), lambda s: s.startswith("rrt_expand_block_kernel<2,")),
-    "pipe1": (dict(team=1), lambda s: s == "rrt_pipe_kernel"),
-    "block1": (dict(team=1, pipe1=False), lambda s: s == "rrt_expand_block_kernel<1, 16, false, false>"),
-    "serial": (dict(serial=True), lambda s: s == "rrt_expand_kernel<false, false>"),
+# the committer + worker pair of 64: what a batch of one or two RRTStandard / RRT* queries runs when it is capped at 64 (one query) or
+# cannot have 129 compute units per query (two), and the same pair on 2 x 64 workers, the default of a single query without a cap
+ONE_SHIFT = "rrt_expand_block_kernel<64, 1, true, false> as rrt_block_commit_kernel + rrt_block_work_kernel<64, 1, false>"
+TWO_SHIFTS = ONE_SHIFT + " in 2 shifts"
+
+
+MI355X_CUS = 256  # the compute units of the device the GPU tests run on: the fixed names below hold for it, as TWO_SHIFTS needs 129 of them
+
+
+def planned_name(Q, want=64, cus=MI355X_CUS, narrow=False):
+    """The name of the kernel a batch of Q RRTStandard / RRT* queries with a team cap of `want` runs on an otherwise idle device of
+    `cus` compute units, one shift: pick_team of rrt_engine.hip restated, then the row of rrt_block_variants.def that plan_launch
+    takes (tests/variants.py, test_variant_matrix.py).  narrow: the RRT* queries have r2_rewire < variants.NARROW_R2 (only a
+    pipelined team of two asks)."""
+    import variants
+
+    def stride_of(g):
+        step = 8 if g <= 16 else (4 if g == 32 else 2)
+        stride = (Q + step - 1) // step * step
+        if g == 32 and stride % 8 == 0:
+            stride += 4
+        if g == 64 and stride % 4 == 0:
+            stride += 2
+        return stride
+    team, pipe, pipe_g = 1, False, 0
+    for g in (2, 4, 8, 16, 32, 64):
+        if g <= want and stride_of(g) * g <= cus:
+            team = g
+    for g in (2, 3, 4, 8, 16, 32, 64):
+        if g <= want and stride_of(g) * (g + 1) <= cus:
+            pipe_g = g
+    if pipe_g != 0 and team <= 2 * pipe_g:
+        team, pipe = pipe_g, True
+    if team == 1:
+        return "rrt_pipe_kernel"
+    wide = pipe and team == variants.WIDE_TEAM and not narrow
+    split = pipe and not wide and team >= variants.SPLIT_FROM
+    for r in variants.rows():
+        if r.G == team and r.pipe == pipe and not r.inf and (r.BSM > 16) == wide and (r.kind == "S") == split:
+            return variants.kernel_name(r)
+    raise LookupError(f"no team kernel for Q={Q}, want={want}, cus={cus}")
+
+
+def team_name_ok(name, Q):
+    """the "team" shape (no cap) held to its name: one query runs two shifts, two run the pair of 64 in one shift, and a larger
+    batch what the launch plan gives it (three queries on 256 compute units: the pair of 32, because the stride of a team of 64 is
+    6 slots for them)"""
+    return name == (TWO_SHIFTS if Q == 1 else ONE_SHIFT if Q == 2 else planned_name(Q))
+
+
+def team64_name_ok(name, Q):
+    """the cap of 64: as team_name_ok, but a single query keeps one shift"""
+    return name == (ONE_SHIFT if Q <= 2 else planned_name(Q, 64))
+
+
+SHAPES = {  # launch shape -> (Batch keywords, what the kernel's name has to say: check(name, Q) with Q the queries of the batch)
+    "team": (dict(), team_name_ok),
+    "team8": (dict(team=8), lambda s, Q=1: s.startswith("rrt_expand_block_kernel<8,")),
+    "team2": (dict(team=2), lambda s, Q=1: s.startswith("rrt_expand_block_kernel<2,")),
+    "pipe1": (dict(team=1), lambda s, Q=1: s == "rrt_pipe_kernel"),
+    "block1": (dict(team=1, pipe1=False), lambda s, Q=1: s == "rrt_expand_block_kernel<1, 16, false, false>"),
+    "serial": (dict(serial=True), lambda s, Q=1: s == "rrt_expand_kernel<false, false>"),
+    "team64": (dict(team=64), team64_name_ok),  # (last: test_tree_sequences_gpu.py pairs shapes with seeds by position)
 }
 _cache = {}
 
@@ -251,9 +307,18 @@ def class_goals_and_routes(p, og8, g, goals):
         assert (r is None and lo == hi) or np.array_equal(r, want[4][lo:hi]), k
 
 
-def grow_checked(b, q, og8, prev, view, samples, c, shape):
-    """one grow of query q on map og8 from the tree `prev` = (pts, parent, vcost, j); view: the tree was kept on og8.  Checked
-    against growref.  Returns (restatement, result)."""
+def shape_ran(b, shape, Q=1):
+    """the last launch of batch b (Q queries, none Informed) ran the kernel of this launch shape, by its exact name where the shape
+    is "team" or "team64"; a single query on 128 workers (two shifts) or 64, and no launch fell back to one CU per query"""
+    name = b.kernel_name()
+    assert SHAPES[shape][1](name, Q), (shape, Q, name)
+    if Q == 1 and shape in ("team", "team64"):
+        assert b.team() == ((128, 0) if shape == "team" else (64, 0)), (shape, b.team())
+
+
+def grow_checked(b, q, og8, prev, view, samples, c, shape, Q=1):
+    """one grow of query q of a batch of Q on map og8 from the tree `prev` = (pts, parent, vcost, j); view: the tree was kept on og8.
+    Checked against growref.  Returns (restatement, result)."""
     ids, sp, sc, spar = growref.seed(*prev, og8_view=og8 if view else None)
     g = growref.grow(og8, c["alg"], c["n"], c["xg"], c["r2"], sp, sc, spar, samples)
     j0, old_id, log0 = b.grow(q, samples)
@@ -264,7 +329,7 @@ def grow_checked(b, q, og8, prev, view, samples, c, shape):
     same_result(res, g, log0)
     info = b.team_info()
     assert info["timeouts"] == 0 and b.team()[1] == 0, info
-    assert SHAPES[shape][1](b.kernel_name()), b.kernel_name()
+    shape_ran(b, shape, Q)
     ms = b.grow_ms()
     assert len(ms) == 3 and all(t >= 0.0 for t in ms)
     return g, res

@@ -61,7 +61,7 @@ PROBE = np.array([(10, 10), (30, 70), (47, 50), (60, 20), (80, 90), (95, 99), (0
 ARMS = {"arm": "grow", "reroot_arm": "reroot", "relax_arm": "relax"}  # the seed calls alone; "grow", "reroot", "relax" include the launch and the sync
 SEED_OPS = ("grow", "reroot", "relax") + tuple(ARMS)
 RELAX_R = (4, 6)  # the radii of the sequences' relaxes, in cells: below the rewire radius, so the host's candidate edges stay few
-ROOT_SEEDS = (109, 115, 107)  # the sequences with reroot and relax (_GenRoot), each on two of the six launch shapes; test_tree_sequences_cpu.py holds them to their conditions
+ROOT_SEEDS = (109, 115, 107)  # the sequences with reroot and relax (_GenRoot), each on two of the launch shapes of treecalls.SHAPES, the first on a third (team64); test_tree_sequences_cpu.py holds them to their conditions
 # Known gap: a launched grow / reroot / relax of one query while ANOTHER query of its batch is armed on an older grid.  There the call
 # answers and the launch behind it is refused ("seeded"), which one expected answer per operation cannot say (Model._apply asserts).
 # No single sequence gets there; of two in turns only some pairs do, and the pairs are chosen among those that do not.
