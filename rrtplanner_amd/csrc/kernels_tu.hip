@@ -28,8 +28,10 @@ template __global__ void rrt_expand_kernel<false, false>(BatchView);
 template __global__ void rrt_expand_kernel<true, false>(BatchView);
 }
 
-#elif RRT_TU == 5  // many goals against a finished tree (rrt_goals_kernel, rrt_goals_large_kernel): not a team kernel
+#elif RRT_TU == 5  // many goals against a finished tree (rrt_goals_kernel, rrt_goals_large_kernel), and every cell of a window of the map
+                   // against it (rrt_field_kernel, rrt_field_large_kernel): not team kernels
 #include "rrt_goals.h"
+#include "rrt_field.h"
 
 #elif RRT_TU == 6  // finished routes to many goals, with line-of-sight shortcuts (rrt_route_*_kernel): not a team kernel
 #include "rrt_routes.h"

@@ -281,6 +281,10 @@ struct rrt_batch {
     DevBuf pose_reroot_tmp;                             // PoseRerootScratch of n_cap vertices
     StageTimer pose_reroot_time{STAGES_IN_A_LONG_ROW};  // the seven stages of the last rrt_batch_reroot_poses; the seed's three are seed_time's
     int64_t pose_reroot_stats[4] = {0, 0, 0, 0};        // of that call: rounds run, vertices reached, sweeps run, words evaluated
+    // rrt_batch_cost_field: the buckets of the call (rrt_field.h); the answers of the window go through goal_vertex / goal_cost
+    DevBuf field_tmp;                             // FieldScratch of n_cap vertices and RELAX_MAX_CELLS cells
+    StageTimer field_time{STAGES_IN_A_LONG_ROW};  // the four stages of the last rrt_batch_cost_field: buckets, decide, remap, read-back
+    int64_t field_stats[4] = {0, 0, 0, 0};        // of that call: free cells decided, buckets visited, vertices priced, lines walked
     // the rows and points an earlier routes call left are gone (a launch, a rearm, a keep, a grow: they belong to another tree or view)
     void drop_routes() { route_rows = pose_route_rows = pose_route_points = -1; }
 };

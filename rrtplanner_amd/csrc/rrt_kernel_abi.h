@@ -379,6 +379,10 @@ struct RelaxView {
     int32_t *new_parent;     // [j] out of the parent pass, input numbering; -1 for the root
     unsigned long long *stats;  // [4] (zeroed by the host)
     int32_t *err;            // != 0: an index that cannot be placed, or costs that are no fixpoint
+    // The buckets alone serve rrt_field.h too, which has no parents and relaxes nothing: parent, pos_of and cost may be null (then the cell
+    // kernel checks no parent and the two kernels leave those arrays out), and these two, null for the relax calls, are filled if given.
+    double *item_cost;       // [j] vcost of every item of the CSR, beside item_xy
+    unsigned long long *cell_min;  // [ncx * ncy] the smallest vcost of a cell's vertices, as the bits of a non-negative f64 (filled with ~0 by the host: an empty cell keeps it)
 };
 enum : int { RELAX_CHANGES = 0, RELAX_FELL = 1, RELAX_LOS = 2, RELAX_PRICED = 3, RELAX_STATS = 4 };
 
@@ -396,6 +400,25 @@ struct PoseRelaxView {
     uint8_t *item_h;         // [j] ... and of every item of the CSR, beside item_xy
     double *plen;            // [j] the length of the word parent[v] -> v, the old parent edge, evaluated once
 };
+
+// ---- rrt_field.h ----
+constexpr int FIELD_TPB = 256;           // 4 cells a workgroup at a time (one per wave)
+constexpr int FIELD_MAX_WG = 8192;       // workgroups of the decision, grid-stride beyond
+constexpr int FIELD_RUN = 16;            // consecutive cells of one column that a wavefront decides one after the other, each starting from the winner before it
+constexpr int FIELD_MIN_SHIFT = 3;       // buckets of edge 2^shift, shift at least this, doubled until they fit RELAX_MAX_CELLS
+constexpr int FIELD_BUCKETS = 128;       // qualifying buckets a wavefront lists in LDS at a time (12 bytes each)
+constexpr int FIELD_LIST = 256;          // candidates a wavefront lists in LDS (16 bytes each) before it walks them, one line per lane; both lists: 22 KiB a workgroup
+
+// The cost-to-come field of a window of the grid: for every cell the smallest (vcost[k] + sqrt(d2(k, cell)), k) over the vertices that see it.
+// xv holds the buckets (rrt_relax.h's CSR with item_cost and cell_min) over the dense input: the tree arrays, or the kept view.
+struct FieldView {
+    RelaxView xv;
+    int32_t W;               // the grid's other side (xv.H is the stride)
+    int32_t x0, y0, w, h;    // the window, inside the grid
+    int32_t *vertex;         // [w * h] out, cell (x, y) at (x - x0) * h + (y - y0): the vertex in the numbers of the input, or -1
+    double *cost;            // [w * h] out: the cost through it, or +inf
+};
+enum : int { FIELD_CELLS = 0, FIELD_BUCKETS_SEEN = 1, FIELD_PRICED = 2, FIELD_LOS = 3, FIELD_STATS = 4 };
 
 // ---- rrt_pose_reroot.h ----
 // The dense input of a pose re-root (the tree arrays or the kept view, as RerootView takes them, with the heading bytes) and where it
@@ -431,6 +454,9 @@ __global__ __launch_bounds__(TPB) void rrt_block_work_kernel(BatchView bv);
 __global__ __launch_bounds__(TPB) void rrt_goals_kernel(GoalsView gv);
 __global__ __launch_bounds__(TPB) void rrt_goals_large_kernel(GoalsView gv);
 __global__ __launch_bounds__(TPB) void rrt_pose_goals_kernel(PoseGoalsView pv);
+// rrt_field.h (unit 5, beside the goals kernels; its buckets are rrt_relax.h's kernels of unit 0)
+__global__ __launch_bounds__(FIELD_TPB) void rrt_field_kernel(FieldView fv);
+__global__ __launch_bounds__(FIELD_TPB) void rrt_field_large_kernel(FieldView fv);
 // rrt_routes.h (unit 6)
 __global__ __launch_bounds__(ROUTE_TPB) void rrt_route_depth_kernel(RoutesView rv);
 __global__ __launch_bounds__(TPB) void rrt_route_scan_kernel(const int32_t *in, int64_t *out, int32_t m);

@@ -15,6 +15,8 @@
 //      rrt_relax_scan_kernel     one workgroup: cell_start = exclusive scan of the counts; the counts become the cells' cursors.
 //      rrt_relax_fill_kernel     items[cursor++] = k, with k's point beside it.  The order inside a cell is that of the atomics: no result depends on it, since
 //                                every choice below is a minimum over the whole box in an order of its own.
+//      (rrt_field.h runs the same three kernels for its buckets: without parents, cost and pos_of, which may be null, and with the two
+//      arrays only it asks for, item_cost and cell_min.)
 //   2. rrt_relax_round_kernel    one round, one wavefront per vertex v, grid-stride.  A vertex scans only if a cell of its box or its
 //      old parent's cell changed in the round before (dirty_in; the first round scans all), and then only the candidates whose own
 //      cost fell in that round (changed_in, a flag per item of the CSR): the others it has priced, against a c[v] no lower.  The bound is min(c[v], c[p] + d(p, v)): the
@@ -48,11 +50,15 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_relax_cell_kernel(RelaxView xv)
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= xv.j) return;
     const int cell = relax_cell(xv, xv.nodes[k]);
-    const int p = k == 0 ? 0 : xv.parent[k];
+    const int p = k == 0 || !xv.parent ? 0 : xv.parent[k];  // (the buckets of rrt_field.h have no parents)
     if (cell < 0 || p < 0 || p >= xv.j) atomicOr(xv.err, 1);
     xv.cell_of[k] = cell;
-    xv.cost[k] = k == 0 ? 0.0 : xv.vcost[k];
+    if (xv.cost) xv.cost[k] = k == 0 ? 0.0 : xv.vcost[k];
     if (cell >= 0) atomicAdd(&xv.cell_fill[cell], 1);
+    if (xv.cell_min && cell >= 0) {  // the smallest cost of the cell: the bits of non-negative doubles order like unsigned integers
+        const double c = xv.vcost[k];
+        atomicMin(&xv.cell_min[cell], (unsigned long long)__double_as_longlong(c > 0.0 ? c : 0.0));  // (-0, a negative cost or a NaN: 0, which bounds them too)
+    }
 }
 
 // cell_start[0, cells] = exclusive scan of cell_fill[0, cells), and cell_fill[c] = cell_start[c]: the cursor of the fill
@@ -82,10 +88,11 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_relax_fill_kernel(RelaxView xv)
     const int cell = xv.cell_of[k];
     if (cell < 0 || cell >= xv.ncx * xv.ncy) return;  // (the cell kernel raised err)
     const int pos = atomicAdd(&xv.cell_fill[cell], 1);
-    xv.pos_of[k] = pos;
+    if (xv.pos_of) xv.pos_of[k] = pos;
     if (pos >= 0 && pos < xv.j) {
         xv.items[pos] = k;
         xv.item_xy[pos] = xv.nodes[k];
+        if (xv.item_cost) xv.item_cost[pos] = xv.vcost[k];
     } else {
         atomicOr(xv.err, 1);
     }

@@ -171,3 +171,20 @@ struct PoseRerootScratch : Carver {
     int32_t *f_id = take<int32_t>(cap);
     uint8_t *f_heading = take<uint8_t>(cap8);
 };
+
+// What a cost_field call works in (rrt_field.h); cap = n_cap, cells = the most cells of the buckets.  The CSR of rrt_relax.h without what
+// only a relaxation needs, with the cost of every item and the smallest cost of every bucket.  stats: the four counters of the call;
+// two words are reserved for err.
+struct FieldScratch : Carver {
+    FieldScratch(void *base_, size_t cap_, size_t cells_) : Carver(base_, cap_), cells(cells_) {}
+    size_t cells;
+    double *item_cost = take<double>(cap);
+    unsigned long long *cell_min = take<unsigned long long>(cells);
+    unsigned long long *stats = take<unsigned long long>(4);
+    int32_t *cell_of = take<int32_t>(cap);
+    int32_t *items = take<int32_t>(cap);
+    uint32_t *item_xy = take<uint32_t>(cap);
+    int32_t *cell_start = take<int32_t>(cells + 1);
+    int32_t *cell_fill = take<int32_t>(cells);
+    int32_t *err = take<int32_t>(2);
+};

@@ -1,9 +1,10 @@
 // rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax, relax_poses, reroot_poses and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h, rrt_relax.h, rrt_pose_relax.h and rrt_pose_reroot.h.  What the calls share comes first and is written once:
+// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax, relax_poses, reroot_poses, cost_field and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
+// rrt_field.h, rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h, rrt_relax.h, rrt_pose_relax.h and rrt_pose_reroot.h.  What the calls share comes first and is written once:
 // the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
 // batch behind rrt_plan.
 #include "rrt_engine.h"
+#include "rrt_hip_field.h"  // rrt_batch_cost_field and its forms: declared beside rrt_hip.h, not in it
 
 // ---- the gate: a finished tree on the grid it belongs to ----
 // Every call makes these in this order, after the refusals that are its own (NULL, the batch's flags).  0: not refused.
@@ -1724,4 +1725,124 @@ extern "C" int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]) {
 extern "C" int rrt_plan_pose_shortcuts_ms(rrt_ctx *ctx, float ms[5]) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_shortcuts_ms", NO_PLAN);
     return s ? rrt_batch_pose_shortcuts_ms(s, ms) : RRT_E_ARG;
+}
+
+// ---- the cost-to-come field: every cell of a window of the map against a finished tree (rrt_field.h) ----
+// connect_goals for every cell of the window, without the cells as goals: the vertices of the dense input (decide_over: the tree, or its
+// kept view) are bucketed once by the relax calls' bucket kernels (relax_cells gives the edge: FIELD_MIN_SHIFT, doubled until the cells
+// fit), and rrt_field_kernel decides every cell from the buckets whose lower bound can still beat what the cell has.  The answers go
+// through goal_vertex / goal_cost, which the goals calls share, and are copied out in the window's own (w, h) order.
+static int cost_field(const char *who, rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its goal is a pose, and there is no field of poses here; these kernels price straight lines to cells)", who);
+    if (const int rc = refuse_goals_call(who, b, q, 0, "goals")) return rc;
+    if (w < 1 || h < 1) return fail(ctx, RRT_E_ARG, "%s: a window of %d x %d cells", who, w, h);
+    if (x0 < 0 || y0 < 0 || x0 > ctx->W - w || y0 > ctx->H - h)
+        return fail(ctx, RRT_E_ARG, "%s: the window (%d, %d) + %d x %d is not inside the %dx%d grid", who, x0, y0, w, h, ctx->W, ctx->H);
+    if (!vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    const QDesc &d = b->h_desc[(size_t)q];
+    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    const int64_t m = (int64_t)w * h;  // (inside a grid of at most 4096 x 4096: 2^24 cells)
+    StageTimer &time = b->field_time;
+    time.ran = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, b->goal_vertex.reserve(m, (size_t)m * sizeof(int32_t)));
+    HIPCHK(ctx, b->goal_cost.reserve(m, (size_t)m * sizeof(double)));
+    HIPCHK(ctx, b->field_tmp.reserve<FieldScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
+    HIPCHK(ctx, time.create(5));
+    const FieldScratch fx = b->field_tmp.carve<FieldScratch>((size_t)RELAX_MAX_CELLS);
+    FieldView fv{};
+    RelaxView &xv = fv.xv;
+    xv.og = ctx->og;
+    xv.H = ctx->H;
+    relax_cells((int64_t)1 << (2 * FIELD_MIN_SHIFT), ctx->W, ctx->H, xv);
+    xv.cell_of = fx.cell_of;
+    xv.cell_start = fx.cell_start;
+    xv.cell_fill = fx.cell_fill;
+    xv.items = fx.items;
+    xv.item_xy = fx.item_xy;
+    xv.item_cost = fx.item_cost;
+    xv.cell_min = fx.cell_min;
+    xv.stats = fx.stats;
+    xv.err = fx.err;
+    fv.W = ctx->W;
+    fv.x0 = x0;
+    fv.y0 = y0;
+    fv.w = w;
+    fv.h = h;
+    fv.vertex = b->goal_vertex.as<int32_t>();
+    fv.cost = b->goal_cost.as<double>();
+    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
+    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, FIELD_STATS * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.err, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_start, 0, (cells + 1) * sizeof(int32_t), ctx->stream));  // (a tree without a vertex launches no bucket kernel)
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_min, 0xff, cells * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, time.mark(0, ctx->stream));
+    hipError_t marked = hipSuccess;
+    decide_over(b, q, fv.vertex, (int32_t)m, [&](const uint32_t *nodes, const double *vcost, const uint8_t *, int32_t j) {
+        xv.nodes = nodes;
+        xv.vcost = vcost;
+        xv.j = j;
+        if (j > 0) {
+            hipLaunchKernelGGL(rrt_relax_cell_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, xv);
+            hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
+            hipLaunchKernelGGL(rrt_relax_fill_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, xv);
+        }
+        marked = time.mark(1, ctx->stream);
+        const int64_t runs = (int64_t)w * ((h + FIELD_RUN - 1) / FIELD_RUN);
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_field_large_kernel : rrt_field_kernel,
+                           dim3(std::clamp<unsigned>(wgs(runs, FIELD_TPB / 64), 1, FIELD_MAX_WG)), dim3(FIELD_TPB), 0, ctx->stream, fv);
+        if (marked == hipSuccess) marked = time.mark(2, ctx->stream);
+    });
+    HIPCHK(ctx, marked);
+    HIPCHK(ctx, time.mark(3, ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    unsigned long long stats[FIELD_STATS] = {0, 0, 0, 0};
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(vertex, fv.vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cost, fv.cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, xv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, time.mark(4, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err) return fail(ctx, RRT_E_HIP, "%s: a vertex of query %d on the device lies outside the buckets of the %dx%d grid", who, q, ctx->W, ctx->H);
+    for (int k = 0; k < FIELD_STATS; ++k) b->field_stats[k] = (int64_t)stats[k];
+    time.ran = 4;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_cost_field(rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
+    return b ? cost_field("rrt_batch_cost_field", b, q, x0, y0, w, h, vertex, cost) : fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field: NULL");
+}
+
+extern "C" int rrt_plan_cost_field(rrt_ctx *ctx, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_cost_field", NO_PLAN_NO_TREE);
+    return s ? cost_field("rrt_plan_cost_field", s, 0, x0, y0, w, h, vertex, cost) : RRT_E_ARG;
+}
+
+// ms[0, 4): buckets, decide, remap, read-back
+extern "C" int rrt_batch_cost_field_ms(rrt_batch *b, float ms[4]) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field_ms: NULL");
+    if (!b->field_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_cost_field_ms: no rrt_batch_cost_field on this batch yet, or its last one failed");
+    HIPCHK(b->ctx, b->field_time.read(ms, 4));
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_cost_field_ms(rrt_ctx *ctx, float ms[4]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_cost_field_ms", NO_PLAN);
+    return s ? rrt_batch_cost_field_ms(s, ms) : RRT_E_ARG;
+}
+
+extern "C" int rrt_batch_cost_field_stats(rrt_batch *b, int64_t out[4]) {
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field_stats: NULL");
+    if (!b->field_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_cost_field_stats: no rrt_batch_cost_field on this batch yet, or its last one failed");
+    for (int k = 0; k < 4; ++k) out[k] = b->field_stats[k];
+    return RRT_OK;
+}
+
+extern "C" int rrt_plan_cost_field_stats(rrt_ctx *ctx, int64_t out[4]) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_cost_field_stats", NO_PLAN);
+    return s ? rrt_batch_cost_field_stats(s, out) : RRT_E_ARG;
 }
