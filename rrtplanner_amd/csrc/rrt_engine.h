@@ -178,6 +178,10 @@ struct RRT_PRIVATE StageTimer {
     }
 };
 
+// the seed calls of a batch, as its last_seed names the one that succeeded last (relax: rrt_batch_relax and rrt_batch_relax_poses, of
+// which a batch only ever takes one: it is a Dubins batch or not for life)
+enum class SeedKind { none, grow, reroot, relax, reroot_poses };
+
 struct rrt_batch {
     rrt_ctx *ctx = nullptr;
     int32_t Q = 0, n_cap = 0, node_stride = 0, bitmap_words = 0, lds_chunks = 1, spill_stride = 0;
@@ -265,22 +269,18 @@ struct rrt_batch {
     std::vector<uint64_t> grow_gen;         // [Q] while it is armed so: the grid generation the seed was built on (rrt_batch_launch asks for it)
     std::vector<const uint8_t *> grow_og;   // [Q] ... and that grid
     DevBuf seed_tmp;                        // SeedTmpScratch of n_cap vertices
-    StageTimer seed_time{STAGES_IN_A_ROW};  // the three stages of the last rrt_batch_grow
-    // rrt_batch_reroot: the re-root stages in front of that seed (rrt_reroot.h)
-    DevBuf reroot_tmp;                             // RerootScratch of n_cap vertices
-    StageTimer reroot_time{STAGES_IN_A_LONG_ROW};  // the five stages of the last rrt_batch_reroot; the seed's three are seed_time's
-    // rrt_batch_relax: the buckets, the rounds and the parent pass in front of the later re-root stages and that seed (rrt_relax.h);
-    // it works in reroot_tmp too
-    DevBuf relax_tmp;                             // RelaxScratch of n_cap vertices and RELAX_MAX_CELLS cells
-    StageTimer relax_time{STAGES_IN_A_LONG_ROW};  // the six stages of the last rrt_batch_relax; the seed's three are seed_time's
-    int64_t relax_stats[4] = {0, 0, 0, 0};        // of that call: rounds run, vertices whose cost fell, lines of sight walked, pairs priced
-    // rrt_batch_relax_poses (a Dubins batch): what it needs beside the two (rrt_pose_relax.h); the timer and the counters are those above,
-    // which then count sweeps and words
-    DevBuf pose_relax_tmp;                        // PoseRelaxScratch of n_cap vertices
-    // rrt_batch_reroot_poses (a Dubins batch): the root-first input beside the three above (rrt_pose_reroot.h), and its own timer and counters
-    DevBuf pose_reroot_tmp;                             // PoseRerootScratch of n_cap vertices
-    StageTimer pose_reroot_time{STAGES_IN_A_LONG_ROW};  // the seven stages of the last rrt_batch_reroot_poses; the seed's three are seed_time's
-    int64_t pose_reroot_stats[4] = {0, 0, 0, 0};        // of that call: rounds run, vertices reached, sweeps run, words evaluated
+    // The seed calls all end in that seed, so the batch keeps once what the last successful one left: which it was (none from where a
+    // seed call starts replacing the query until it has armed it; the report calls answer for that kind alone), and the times of ...
+    SeedKind last_seed = SeedKind::none;
+    StageTimer seed_time{STAGES_IN_A_ROW};        // ... the three stages of its seed
+    StageTimer front_time{STAGES_IN_A_LONG_ROW};  // ... its stages in front of the seed: the five of reroot, the six of relax / relax_poses, the seven of reroot_poses
+    // ... and its counters: of a relax rounds run, vertices whose cost fell, lines of sight walked, pairs priced (a Dubins batch: sweeps
+    // run, words evaluated); of a pose re-root rounds run, vertices reached, sweeps run, words evaluated
+    int64_t front_stats[4] = {0, 0, 0, 0};
+    DevBuf reroot_tmp;       // rrt_batch_reroot (rrt_reroot.h): RerootScratch of n_cap vertices
+    DevBuf relax_tmp;        // rrt_batch_relax (rrt_relax.h; it works in reroot_tmp too): RelaxScratch of n_cap vertices and RELAX_MAX_CELLS cells
+    DevBuf pose_relax_tmp;   // rrt_batch_relax_poses (a Dubins batch, rrt_pose_relax.h): PoseRelaxScratch of n_cap vertices beside the two
+    DevBuf pose_reroot_tmp;  // rrt_batch_reroot_poses (a Dubins batch, rrt_pose_reroot.h): the root-first input beside the three, PoseRerootScratch of n_cap vertices
     // rrt_batch_cost_field: the buckets of the call (rrt_field.h); the answers of the window go through goal_vertex / goal_cost
     DevBuf field_tmp;                             // FieldScratch of n_cap vertices and RELAX_MAX_CELLS cells
     StageTimer field_time{STAGES_IN_A_LONG_ROW};  // the four stages of the last rrt_batch_cost_field: buckets, decide, remap, read-back

@@ -1,8 +1,14 @@
-// rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device: connect_goals, connect_poses,
-// routes, pose_routes, pose_shortcuts, keep_tree, keep_pose_tree, grow, grow_poses, reroot, relax, relax_poses, reroot_poses, cost_field and their rrt_plan_* forms.  Host code only; the kernels are those of rrt_goals.h,
-// rrt_field.h, rrt_pose_goals.h, rrt_routes.h, rrt_pose_routes.h, rrt_keep.h, rrt_pose_keep.h, rrt_seed.h, rrt_pose_seed.h, rrt_reroot.h, rrt_relax.h, rrt_pose_relax.h and rrt_pose_reroot.h.  What the calls share comes first and is written once:
-// the refusals (refuse_*), the pointers of a query's tree and kept view (tree_ref), the scratch of the goals calls (goal_scratch), the
-// batch behind rrt_plan.
+// rrt_tree_calls.hip -- the calls of the C ABI that work on the tree a finished query left on the device, each as rrt_batch_X and
+// rrt_plan_X.  Host code only: the kernels are launched through rrt_kernel_abi.h.  In this order:
+//   what the calls share  the refusals (refuse_*), a query's tree and kept view (tree_ref), launches that several calls queue, the scratch
+//                         of the goals calls (goal_scratch), the batch behind rrt_plan (plan_batch)
+//   reading a tree        connect_goals (rrt_goals.h), connect_poses (rrt_pose_goals.h), keep_tree, keep_pose_tree (rrt_keep.h, rrt_pose_keep.h)
+//   the seed calls        grow, grow_poses (rrt_seed.h, rrt_pose_seed.h), reroot (rrt_reroot.h), relax, relax_poses (rrt_relax.h, rrt_pose_relax.h),
+//                         reroot_poses (rrt_pose_reroot.h).  Each replaces a query's tree and re-arms it: one record says which call it is
+//                         (SeedCall), one place starts replacing the query (start_replacing), one arms it and makes the call the batch's last
+//                         (seed_and_arm)
+//   routes and the field  routes (rrt_routes.h), pose_routes, pose_shortcuts (rrt_pose_routes.h), cost_field (rrt_field.h)
+//   the reports           every _ms and _stats call: one table row per family (Report), one reader for the times and one for the counters
 #include "rrt_engine.h"
 #include "rrt_hip_field.h"  // rrt_batch_cost_field and its forms: declared beside rrt_hip.h, not in it
 
@@ -423,18 +429,6 @@ extern "C" int rrt_plan_keep_pose_tree(rrt_ctx *ctx, int32_t *n_alive, uint8_t *
     return s ? keep_tree("rrt_plan_keep_pose_tree", s, 0, n_alive, alive, true) : RRT_E_ARG;
 }
 
-extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_keep_tree_ms: NULL");
-    if (!b->keep_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_keep_tree_ms: no rrt_batch_keep_tree on this batch yet, or its last one failed");
-    HIPCHK(b->ctx, b->keep_time.read(ms, 3));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_keep_tree_ms", NO_PLAN);
-    return s ? rrt_batch_keep_tree_ms(s, ms) : RRT_E_ARG;
-}
-
 extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
     if (!ctx || !j) return fail(ctx, RRT_E_ARG, "rrt_plan_tree_size: NULL");
     rrt_batch *s = ctx->single;
@@ -454,15 +448,32 @@ extern "C" int rrt_plan_tree_size(rrt_ctx *ctx, int32_t *j) {
 // rrt_batch_grow (poses == false: straight-line batches, rows (x, y)) and rrt_batch_grow_poses (poses == true: Dubins batches, rows
 // (x, y, h)) are one call: the Dubins seed carries one more array, the heading bytes (rrt_pose_seed.h), and the m sample headings go
 // to rows [j0, j0 + m) of the sample heading buffer, which both Dubins kernels read by absolute row like the samples.
-// What rrt_batch_grow and rrt_batch_reroot share comes in three parts: the refusals (refuse_grow), the seed stages and the arming
-// (seed_and_arm), and what the seed is made from (SeedFrom).
+// What the seed calls share: the record of the call (SeedCall), the refusals (refuse_grow), where the query starts being replaced
+// (start_replacing), what the seed is made from (SeedFrom), and the seed stages and the arming (seed_and_arm).
+
+// One seed call, as its entry point fills it in once: every stage the seed calls share takes it.
+struct SeedCall {
+    const char *who;         // the entry point, as its messages name it
+    SeedKind kind;           // what the batch's last_seed says once the call has succeeded
+    rrt_batch *b;
+    int32_t q;
+    const int32_t *samples;  // m rows (x, y), of a pose call (x, y, heading index)
+    int32_t m;
+    int32_t *j0_out, *old_id, *log0;
+    bool poses;              // a pose call: it takes a Dubins batch, and its seed carries the heading bytes
+    rrt_ctx *ctx() const { return b->ctx; }
+    QDesc &desc() const { return b->h_desc[(size_t)q]; }  // (once refuse_q has passed)
+};
 
 // Every refusal of a grow call up to the room, in its order; `dubins`: why this call takes no Dubins batch.  0: not refused, and
 // j_in is what the call starts from: the vertices of the view, else of the tree.  use: the call a pose call sends a straight-line batch to.
-static int refuse_grow(const char *who, rrt_batch *b, int32_t q, bool null_arg, int32_t m, bool poses, const char *dubins, int &j_in,
-                       const char *use = "rrt_batch_grow") {
+static int refuse_grow(const SeedCall &c, const char *dubins, int &j_in, const char *use = "rrt_batch_grow") {
+    const char *who = c.who;
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
-    if (null_arg) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    const int32_t q = c.q, m = c.m;
+    const bool poses = c.poses;
+    if (!c.j0_out || !c.log0 || (m > 0 && !c.samples)) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
     if (!poses && (b->flags & RRT_FLAG_DUBINS)) return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (%s)", who, dubins);
     if (poses && !(b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its samples are cells and its edges straight lines: use %s)", who, use);
@@ -515,20 +526,38 @@ static SeedFrom seed_from_tree(const TreeRef &t, int32_t j_in) {
     return from;
 }
 
+// the refusal of reroot, relax and reroot_poses that the placement by depth forces (rrt_reroot.h)
+static int refuse_capacity(const SeedCall &c) {
+    if (c.b->n_cap <= REROOT_WAVES * REROOT_OWN) return RRT_OK;
+    return fail(c.ctx(), RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", c.who, c.b->n_cap,
+                REROOT_WAVES * REROOT_OWN);
+}
+
+// the samples of the call checked and staged (stage_cells): the last refusal that touches nothing of the batch
+static int stage_samples(const SeedCall &c) { return stage_cells(c.who, c.b, c.q, "sample", c.samples, c.m, c.poses ? c.desc().nh : 0); }
+
+// From here on the query is being replaced.  No seed call is the batch's last until this one has armed the query (seed_and_arm), so
+// every report of a seed call is refused meanwhile and after a failure; the rows of an earlier routes call belong to the old tree;
+// and the query is idle: a failure on the way leaves it without a tree.
+static void start_replacing(const SeedCall &c) {
+    c.b->last_seed = SeedKind::none;
+    c.b->seed_time.ran = c.b->front_time.ran = 0;
+    c.b->drop_routes();
+    c.desc().status = ST_IDLE;
+}
+
 // The seed of query q from `from`, the m staged samples uploaded, and the descriptor armed at (j0, j0) of j0 + m.  The caller has
-// made every refusal, staged the samples (stage_cells) and reserved seed_tmp and the marks of seed_time.  From here on the query is
-// being replaced: a failure leaves it idle without a tree.
-static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom &from, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
-                        bool poses) {
+// made every refusal, staged the samples (stage_samples), reserved seed_tmp and the marks of seed_time, and started replacing the
+// query (start_replacing): a failure leaves it idle without a tree.  A success makes the call the batch's last seed call.
+static int seed_and_arm(const SeedCall &c, const SeedFrom &from) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
-    QDesc &d = b->h_desc[(size_t)q];
+    const int32_t q = c.q, m = c.m;
+    QDesc &d = c.desc();
     const int j_old = d.j, own_n = d.n, j0 = from.j0;
     const TreeRef t = tree_ref(b, q);
     const SeedTmpScratch tmp = b->seed_tmp.carve<SeedTmpScratch>();
     StageTimer &time = b->seed_time;
-    time.ran = 0;
-    b->drop_routes();
-    d.status = ST_IDLE;  // (until the descriptor is armed below: a failure on the way leaves a query without a tree)
     SeedView sv{};
     sv.nodes = t.nodes;
     sv.vcost = t.vcost;
@@ -551,7 +580,7 @@ static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom
     if (sv.live_id && !from.parent)
         if (const int rc = renumber_view_parents(ctx, sv)) return rc;
     hipLaunchKernelGGL(rrt_seed_install_kernel, blocks(b->node_stride), dim3(SEED_TPB), 0, ctx->stream, sv);
-    if (poses && sv.live_id)  // (without a view heading[0, j0) already stands; rrt_pose_seed.h says why the slots behind j0 are left)
+    if (c.poses && sv.live_id)  // (without a view heading[0, j0) already stands; rrt_pose_seed.h says why the slots behind j0 are left)
         hipLaunchKernelGGL(rrt_pose_seed_heading_kernel, blocks(j0), dim3(SEED_TPB), 0, ctx->stream, t.heading, from.heading, j0, b->node_stride);
     HIPCHK(ctx, time.mark(1, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(sv.bitmap, 0, (size_t)b->bitmap_words * sizeof(uint32_t), ctx->stream));
@@ -576,14 +605,14 @@ static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom
     HIPCHK(ctx, hipGetLastError());
     int32_t err = 0;
     HIPCHK(ctx, hipMemcpyAsync(&err, sv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    if (old_id) {
-        if (sv.live_id) HIPCHK(ctx, hipMemcpyAsync(old_id, sv.live_id, (size_t)j0 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (c.old_id) {
+        if (sv.live_id) HIPCHK(ctx, hipMemcpyAsync(c.old_id, sv.live_id, (size_t)j0 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         else
-            for (int k = 0; k < j0; ++k) old_id[k] = k;
+            for (int k = 0; k < j0; ++k) c.old_id[k] = k;
     }
     if (m > 0)
         HIPCHK(ctx, hipMemcpyAsync(b->d_samples + (size_t)q * b->n_cap + j0, b->stage.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (poses && m > 0)
+    if (c.poses && m > 0)
         HIPCHK(ctx, hipMemcpyAsync(b->d_shead + (size_t)q * b->n_cap + j0, b->stage8.data(), (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     drop_keep_views(b, q);  // the view is used up: the tree arrays hold its vertices now
@@ -591,7 +620,7 @@ static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom
         HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, wait_stream_spin(ctx->stream));
         return fail(ctx, RRT_E_HIP, "%s: the tree of query %d on the device is not one the seed can place (a parent that is not alive, a vertex outside the "
-                    "record grid or a cell past its capacity): the query is left without a tree", who, q);
+                    "record grid or a cell past its capacity): the query is left without a tree", c.who, q);
     }
     arm_desc(d);
     d.n = j0 + m;
@@ -603,23 +632,24 @@ static int seed_and_arm(const char *who, rrt_batch *b, int32_t q, const SeedFrom
     HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &d, sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     time.ran = 3;
-    *j0_out = j0;
-    *log0 = j0;
+    b->last_seed = c.kind;
+    *c.j0_out = j0;
+    *c.log0 = j0;
     return RRT_OK;
 }
 
-static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
-                      bool poses) {
+static int batch_grow(const SeedCall &c) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
     int j_in = 0;
-    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, poses, "the seed kernels carry no headings", j_in)) return rc;
+    if (const int rc = refuse_grow(c, "the seed kernels carry no headings", j_in)) return rc;
     // (the last refusal: the staging buffers, written once every sample has passed, are the first thing of the batch this call touches)
-    if (const int rc = stage_cells(who, b, q, "sample", samples, m, poses ? b->h_desc[(size_t)q].nh : 0)) return rc;
+    if (const int rc = stage_samples(c)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     HIPCHK(ctx, b->seed_time.create(4));
-    b->reroot_time.ran = b->relax_time.ran = b->pose_reroot_time.ran = 0;  // (the seed's times are this call's from here on: rrt_batch_reroot_ms and rrt_batch_relax_ms have nothing to report)
-    return seed_and_arm(who, b, q, seed_from_tree(tree_ref(b, q), j_in), m, j0_out, old_id, log0, poses);
+    start_replacing(c);
+    return seed_and_arm(c, seed_from_tree(tree_ref(b, c.q), j_in));
 }
 
 // ---- re-root a finished tree at one of its vertices (rrt_reroot.h) or relax it over its r-disc (rrt_relax.h), then the seed and the
@@ -628,13 +658,19 @@ static int batch_grow(const char *who, rrt_batch *b, int32_t q, const int32_t *s
 // scratch both work in and its reset (reroot_view, reroot_reset), and every stage from the pointer jumping to the armed descriptor
 // (order_price_and_seed).
 
-// The dense input of the call: the query's tree arrays, or, with a kept view, the view with its parents renumbered into stmp.new_parent
-// (one wait: the view's err).  rv: nodes, parent, id, j.  vertex >= 0: a number of the tree as the caller holds it, whose number in
-// the input goes to in_input (-1: not alive in the view).  heading: nullptr, or where the heading bytes of the input go (a Dubins batch).
-static int tree_input(const char *who, rrt_batch *b, int32_t q, const TreeRef &t, const SeedTmpScratch &stmp, int32_t j_in, int32_t vertex, RerootView &rv,
-                      int32_t &in_input, const uint8_t **heading = nullptr) {
+// The dense input of the call: the query's tree arrays, or, with a kept view, the view with its parents renumbered into the new_parent
+// of seed_tmp (one wait: the view's err).  rv: og, H, nodes, parent, id, j.  vertex >= 0: a number of the tree as the caller holds it,
+// whose number in the input goes to in_input (-1: not alive in the view).  heading: nullptr, or where the heading bytes of the input go
+// (a Dubins batch).
+static int tree_input(const SeedCall &c, const TreeRef &t, int32_t j_in, int32_t vertex, RerootView &rv, int32_t &in_input, const uint8_t **heading = nullptr) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
+    const int32_t q = c.q;
+    const char *who = c.who;
+    const SeedTmpScratch stmp = b->seed_tmp.carve<SeedTmpScratch>();
     if (heading) *heading = t.kept > 0 ? t.live_heading : t.heading;
+    rv.og = ctx->og;
+    rv.H = ctx->H;
     rv.nodes = t.nodes;
     rv.parent = t.parent;
     rv.id = nullptr;
@@ -695,10 +731,11 @@ static int reroot_reset(rrt_ctx *ctx, const RerootView &rv, bool keep_err = fals
 }
 
 // a call that failed past its refusals leaves the query idle without a tree, on the device too
-static int leave_without_tree(rrt_batch *b, int32_t q) {
+static int leave_without_tree(const SeedCall &c) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
-    drop_keep_views(b, q);
-    HIPCHK(ctx, hipMemcpyAsync(b->d_desc + q, &b->h_desc[(size_t)q], sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
+    drop_keep_views(b, c.q);
+    HIPCHK(ctx, hipMemcpyAsync(b->d_desc + c.q, &c.desc(), sizeof(QDesc), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
     return RRT_OK;
 }
@@ -726,88 +763,93 @@ static int order_by_depth(rrt_ctx *ctx, RerootView &rv, const RerootScratch &tmp
     return RRT_OK;
 }
 
-// Behind rrt_reroot_link_kernel (rv.new_parent, ok, anc, dep of set 0 stand; the caller recorded mark `mark0` of `time`): alive and
-// depth by pointer jumping, the order by (depth, previous number) (order_by_depth), the costs from the root down (`price` queues that
-// stage) -- marks mark0 + 1 .. mark0 + 3 --,
-// `checks` (what the call queues behind the costs), the one wait, then the seed and the arming.  whole: every input vertex has to be
-// alive.  new_start: the descriptor's xs becomes the root's cell.  what: the failure in the call's words.  out_heading: nullptr, or the
-// heading bytes in the new order, which `price` wrote (a Dubins batch: the seed is a pose seed).
-// start_heading: nullptr, or with new_start the host byte that `checks` has queued the new root's heading index into (a Dubins batch: the
-// descriptor's hs becomes it).
+// ... and of a pose call: the j words in parallel (and the headings into the new order, px.out_heading), then the sums level by level
+static void price_words(rrt_ctx *ctx, const PoseRelaxView &pv, const RerootView &rv, const PoseRelaxScratch &px) {
+    hipLaunchKernelGGL(rrt_pose_relax_word_kernel, dim3(wgs(rv.j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, pv, rv, px.out_heading, px.word);
+    hipLaunchKernelGGL(rrt_pose_relax_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv, (const double *)px.word);
+}
+
+// What order_price_and_seed is told beside the call.  The caller recorded mark `mark0` of front_time, and the call has mark0 + 3 stages
+// in front of its seed.
+struct OrderAndSeed {
+    int mark0 = 0;
+    bool whole = false;       // every input vertex has to be alive
+    bool new_start = false;   // the descriptor's xs becomes the root's cell
+    const char *what = "";    // the failure in the call's words
+    const uint8_t *out_heading = nullptr;    // a pose call: the heading bytes in the new order, which `price` wrote
+    const uint8_t *start_heading = nullptr;  // with new_start, a pose call: the host byte that `checks` has queued the new root's heading index into (the descriptor's hs becomes it)
+};
+
+// Behind rrt_reroot_link_kernel (rv.new_parent, ok, anc, dep of set 0 stand): alive and depth by pointer jumping, the order by (depth,
+// previous number) (order_by_depth), the costs from the root down (`price` queues that stage) -- marks o.mark0 + 1 .. o.mark0 + 3 --,
+// `checks` (what the call queues behind the costs), the one wait, then the seed and the arming.
 template <typename Price, typename Checks>
-static int order_price_and_seed(const char *who, rrt_batch *b, int32_t q, RerootView &rv, const RerootScratch &tmp, StageTimer &time, int mark0, bool whole,
-                                bool new_start, const char *what, Price price, Checks checks, int32_t m, int32_t *j0_out, int32_t *old_id, int32_t *log0,
-                                const uint8_t *out_heading = nullptr, const uint8_t *start_heading = nullptr) {
-    rrt_ctx *ctx = b->ctx;
-    QDesc &d = b->h_desc[(size_t)q];
+static int order_price_and_seed(const SeedCall &c, RerootView &rv, const RerootScratch &tmp, const OrderAndSeed &o, Price price, Checks checks) {
+    rrt_ctx *ctx = c.ctx();
+    StageTimer &time = c.b->front_time;
+    QDesc &d = c.desc();
     const int j = rv.j;
-    if (const int rc = order_by_depth(ctx, rv, tmp, &time, mark0 + 1)) return rc;
-    HIPCHK(ctx, time.mark(mark0 + 2, ctx->stream));
+    if (const int rc = order_by_depth(ctx, rv, tmp, &time, o.mark0 + 1)) return rc;
+    HIPCHK(ctx, time.mark(o.mark0 + 2, ctx->stream));
     price();
-    HIPCHK(ctx, time.mark(mark0 + 3, ctx->stream));
+    HIPCHK(ctx, time.mark(o.mark0 + 3, ctx->stream));
     if (const int rc = checks()) return rc;
     HIPCHK(ctx, hipGetLastError());
     // the one wait that the sizes force: how many vertices are alive decides the launches of the seed
     int32_t head[REROOT_HEAD] = {0, 0, 1, 0, -1, 0, 0, 0};
     HIPCHK(ctx, hipMemcpyAsync(head, rv.head, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (head[REROOT_ERR] || head[REROOT_COUNT] < 1 || head[REROOT_COUNT] > j || (whole && head[REROOT_COUNT] != j)) {
-        if (const int rc = leave_without_tree(b, q)) return rc;
-        return fail(ctx, RRT_E_HIP, "%s: %s: the query is left without a tree", who, what);
+    if (head[REROOT_ERR] || head[REROOT_COUNT] < 1 || head[REROOT_COUNT] > j || (o.whole && head[REROOT_COUNT] != j)) {
+        if (const int rc = leave_without_tree(c)) return rc;
+        return fail(ctx, RRT_E_HIP, "%s: %s: the query is left without a tree", c.who, o.what);
     }
-    if (new_start) {
+    if (o.new_start) {
         d.xs[0] = (int32_t)((uint32_t)head[REROOT_XY] & 0xffffu);
         d.xs[1] = (int32_t)((uint32_t)head[REROOT_XY] >> 16);
-        if (start_heading) d.hs = (int32_t)*start_heading;
+        if (o.start_heading) d.hs = (int32_t)*o.start_heading;
     }
     SeedFrom from;
     from.nodes = tmp.out_nodes;
     from.vcost = tmp.out_vcost;
     from.id = tmp.out_id;
     from.parent = tmp.out_parent;
-    from.heading = out_heading;
+    from.heading = o.out_heading;
     from.j0 = head[REROOT_COUNT];
-    if (const int rc = seed_and_arm(who, b, q, from, m, j0_out, old_id, log0, out_heading != nullptr)) return rc;
-    time.ran = mark0 + 3;
+    if (const int rc = seed_and_arm(c, from)) return rc;
+    time.ran = o.mark0 + 3;
     return RRT_OK;
 }
 
 // `root` is a vertex number of the tree as the caller holds it: with a kept view an original number, which must be alive.  The stages
 // of rrt_reroot.h leave the re-rooted tree, renumbered by depth and repriced, in scratch; the seed installs it.  The descriptor's xs
 // becomes the new root's cell.  A refusal changes nothing; past the refusals a failure leaves the query idle without a tree.
-static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id,
-                        int32_t *log0) {
+static int batch_reroot(const SeedCall &c, int32_t root) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
+    const char *who = c.who;
+    const int32_t q = c.q;
     int j_in = 0;
-    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, false, "a Dubins word is not reversible", j_in)) return rc;
-    QDesc &d = b->h_desc[(size_t)q];
+    if (const int rc = refuse_grow(c, "a Dubins word is not reversible", j_in)) return rc;
+    QDesc &d = c.desc();
     if (root < 0 || root >= d.j) return fail(ctx, RRT_E_ARG, "%s: root=%d, query %d has the vertices [0, %d)", who, root, q, d.j);
-    if (b->n_cap > REROOT_WAVES * REROOT_OWN)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
-                    REROOT_WAVES * REROOT_OWN);
-    if (const int rc = stage_cells(who, b, q, "sample", samples, m, 0)) return rc;
+    if (const int rc = refuse_capacity(c)) return rc;
+    if (const int rc = stage_samples(c)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
     HIPCHK(ctx, b->seed_time.create(4));
-    HIPCHK(ctx, b->reroot_time.create(6));
+    HIPCHK(ctx, b->front_time.create(6));
     const TreeRef t = tree_ref(b, q);
     const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
     auto blocks = [](int items) { return dim3(wgs(items, REROOT_TPB)); };
     RerootView rv{};
-    rv.og = ctx->og;
-    rv.H = ctx->H;
     // with a view the input is the view: its parents renumbered into scratch, and the root's number in it (-1: not alive)
-    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, root, rv, rv.root)) return rc;
+    if (const int rc = tree_input(c, t, j_in, root, rv, rv.root)) return rc;
     if (rv.root < 0)
         return fail(ctx, RRT_E_ARG, "%s: root=%d is not alive in the kept view of query %d (%d of %d vertices alive)", who, root, q, j_in, d.j);
     reroot_view(rv, tmp);
-    // ---- from here on the query is being replaced ----
-    StageTimer &time = b->reroot_time;
-    time.ran = b->relax_time.ran = b->pose_reroot_time.ran = 0;
-    b->seed_time.ran = 0;
-    b->drop_routes();
-    d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
+    start_replacing(c);
+    StageTimer &time = b->front_time;
     const int j = j_in;
     if (const int rc = reroot_reset(ctx, rv)) return rc;
     HIPCHK(ctx, time.mark(0, ctx->stream));
@@ -820,7 +862,11 @@ static int batch_reroot(const char *who, rrt_batch *b, int32_t q, int32_t root, 
     char what[256];
     snprintf(what, sizeof what, "the parent array of query %d on the device is not a tree (a walk that did not reach vertex 0 within %d steps, or a "
              "vertex that cannot be placed)", q, j);
-    return order_price_and_seed(who, b, q, rv, tmp, time, 2, false, true, what, [&] { price_lines(ctx, rv); }, [] { return RRT_OK; }, m, j0_out, old_id, log0);
+    OrderAndSeed o;
+    o.mark0 = 2;
+    o.new_start = true;
+    o.what = what;
+    return order_price_and_seed(c, rv, tmp, o, [&] { price_lines(ctx, rv); }, [] { return (int)RRT_OK; });
 }
 
 // ---- relax a finished tree to shortest paths over its r-disc (rrt_relax.h) ----
@@ -876,8 +922,8 @@ static void pose_relax_view(rrt_ctx *ctx, PoseRelaxView &pv, const RelaxView &xv
 // reads the count of changes back behind every RELAX_READ_EVERY-th round and stops behind a look that saw none; a shortest path has
 // fewer than j edges, so j rounds are the most.  rounds: how many ran.  Not settled by then: the query is left without a tree.
 template <typename Round>
-static int relax_rounds(const char *who, rrt_batch *b, int32_t q, const RelaxView &xv, const RelaxScratch &rx, Round round, int64_t &rounds) {
-    rrt_ctx *ctx = b->ctx;
+static int relax_rounds(const SeedCall &c, const RelaxView &xv, const RelaxScratch &rx, Round round, int64_t &rounds) {
+    rrt_ctx *ctx = c.ctx();
     const int j = xv.j;
     const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
     unsigned long long changes = 0, before = 0;
@@ -897,9 +943,56 @@ static int relax_rounds(const char *who, rrt_batch *b, int32_t q, const RelaxVie
         before = changes;
     }
     if (settled) return RRT_OK;
-    if (const int rc = leave_without_tree(b, q)) return rc;
-    return fail(ctx, RRT_E_INTERNAL, "%s: the costs of query %d still fell in round %lld of a tree of %d vertices: the query is left without a tree", who, q,
+    if (const int rc = leave_without_tree(c)) return rc;
+    return fail(ctx, RRT_E_INTERNAL, "%s: the costs of query %d still fell in round %lld of a tree of %d vertices: the query is left without a tree", c.who, c.q,
                 (long long)rounds, j);
+}
+
+// ---- what rrt_batch_relax and rrt_batch_reroot_poses both do around their own stages ----
+// The scratch both calls work in beside seed_tmp: reserved, then carved (px: of a pose call).
+static int reserve_relax_set(const SeedCall &c) {
+    rrt_batch *b = c.b;
+    HIPCHK(b->ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
+    HIPCHK(b->ctx, b->relax_tmp.reserve<RelaxScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
+    if (c.poses) HIPCHK(b->ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
+    return RRT_OK;
+}
+
+struct RelaxSet {
+    const RerootScratch tmp;
+    const RelaxScratch rx;
+    const PoseRelaxScratch px;
+    explicit RelaxSet(const SeedCall &c)
+        : tmp(c.b->reroot_tmp.carve<RerootScratch>()), rx(c.b->relax_tmp.carve<RelaxScratch>((size_t)RELAX_MAX_CELLS)),
+          px(c.poses ? c.b->pose_relax_tmp.carve<PoseRelaxScratch>() : PoseRelaxScratch(nullptr, 0)) {}
+};
+
+// In front of the buckets: the re-root scratch reset, the counters and the cells' fill counts zeroed, every vertex alive (no edge is cut)
+static int reset_for_buckets(rrt_ctx *ctx, const RerootView &rv, const RelaxView &xv) {
+    if (const int rc = reroot_reset(ctx, rv)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, RELAX_STATS * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, (size_t)xv.ncx * (size_t)xv.ncy * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(rv.ok, 1, (size_t)rv.j, ctx->stream));
+    return RRT_OK;
+}
+
+// The buckets of xv filled (rrt_batch_cost_field fills its own with these too): `first`, the kernel that says which cell each vertex
+// lies in and counts the cells (rrt_relax_cell_kernel, or rrt_pose_reroot_front_kernel, which writes the root-first input on the way),
+// then the scan of the counts and the fill.
+template <typename... Args>
+static void fill_buckets(rrt_ctx *ctx, const RelaxView &xv, void (*first)(Args...), Args... args) {
+    const dim3 per_vertex(wgs(xv.j, RELAX_TPB));
+    hipLaunchKernelGGL(first, per_vertex, dim3(RELAX_TPB), 0, ctx->stream, args...);
+    hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
+    hipLaunchKernelGGL(rrt_relax_fill_kernel, per_vertex, dim3(RELAX_TPB), 0, ctx->stream, xv);
+}
+
+// the counters of the call that has just succeeded, for its _stats report: the rounds, then what the device counted
+static void store_front_stats(rrt_batch *b, int64_t rounds, const unsigned long long (&stats)[RELAX_STATS]) {
+    b->front_stats[0] = rounds;
+    b->front_stats[1] = (int64_t)stats[RELAX_FELL];
+    b->front_stats[2] = (int64_t)stats[RELAX_LOS];
+    b->front_stats[3] = (int64_t)stats[RELAX_PRICED];
 }
 
 // The vertices stay and every parent is chosen again: the costs relaxed in rounds to their fixpoint, the parents in a pass over the
@@ -909,35 +1002,30 @@ static int relax_rounds(const char *who, rrt_batch *b, int32_t q, const RelaxVie
 // rrt_batch_relax (poses == false: straight-line batches, rows (x, y)) and rrt_batch_relax_poses (poses == true: Dubins batches, rows
 // (x, y, h)) are one call with two edges: a Dubins batch relaxes over the words between its poses (rrt_pose_relax.h) on the same
 // buckets, flags and counters, prices the new order with words, and its seed carries the heading bytes.
-static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0_out, int32_t *old_id,
-                       int32_t *log0, bool poses) {
+static int batch_relax(const SeedCall &c, int64_t r2) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
+    const bool poses = c.poses;
     int j_in = 0;
-    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, poses,
-                                   "the cost of a Dubins word depends on the headings at its ends: a new parent changes the word", j_in, "rrt_batch_relax"))
+    if (const int rc = refuse_grow(c, "the cost of a Dubins word depends on the headings at its ends: a new parent changes the word", j_in, "rrt_batch_relax"))
         return rc;
-    if (r2 <= 0) return fail(ctx, RRT_E_ARG, "%s: r2=%lld: the threshold of the squared distance has to be positive", who, (long long)r2);
-    if (b->n_cap > REROOT_WAVES * REROOT_OWN)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
-                    REROOT_WAVES * REROOT_OWN);
-    if (const int rc = stage_cells(who, b, q, "sample", samples, m, poses ? b->h_desc[(size_t)q].nh : 0)) return rc;
+    if (r2 <= 0) return fail(ctx, RRT_E_ARG, "%s: r2=%lld: the threshold of the squared distance has to be positive", c.who, (long long)r2);
+    if (const int rc = refuse_capacity(c)) return rc;
+    if (const int rc = stage_samples(c)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
-    HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
-    HIPCHK(ctx, b->relax_tmp.reserve<RelaxScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
-    if (poses) HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
+    if (const int rc = reserve_relax_set(c)) return rc;
     HIPCHK(ctx, b->seed_time.create(4));
-    HIPCHK(ctx, b->relax_time.create(7));
-    QDesc &d = b->h_desc[(size_t)q];
-    const TreeRef t = tree_ref(b, q);
-    const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
-    const RelaxScratch rx = b->relax_tmp.carve<RelaxScratch>((size_t)RELAX_MAX_CELLS);
+    HIPCHK(ctx, b->front_time.create(7));
+    const TreeRef t = tree_ref(b, c.q);
+    const RelaxSet set(c);
+    const RerootScratch &tmp = set.tmp;
+    const RelaxScratch &rx = set.rx;
+    const PoseRelaxScratch &px = set.px;
     RerootView rv{};
-    rv.og = ctx->og;
-    rv.H = ctx->H;
     int32_t unused = -1;
     PoseRelaxView pv{};
-    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, -1, rv, unused, poses ? &pv.heading : nullptr)) return rc;
+    if (const int rc = tree_input(c, t, j_in, -1, rv, unused, poses ? &pv.heading : nullptr)) return rc;
     rv.root = 0;
     reroot_view(rv, tmp);
     const int j = j_in;
@@ -947,25 +1035,14 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     xv.vcost = t.kept > 0 ? t.live_vcost : t.vcost;
     xv.j = j;
     relax_view(ctx, xv, r2, rx, tmp);
-    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
-    const PoseRelaxScratch px = poses ? b->pose_relax_tmp.carve<PoseRelaxScratch>() : PoseRelaxScratch(nullptr, 0);
-    if (poses) pose_relax_view(ctx, pv, xv, d, px);
-    // ---- from here on the query is being replaced ----
-    StageTimer &time = b->relax_time;
-    time.ran = b->reroot_time.ran = b->pose_reroot_time.ran = 0;
-    b->seed_time.ran = 0;
-    b->drop_routes();
-    d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
+    if (poses) pose_relax_view(ctx, pv, xv, c.desc(), px);
+    start_replacing(c);
+    StageTimer &time = b->front_time;
     auto blocks = [](int items) { return dim3(wgs(items, RELAX_TPB)); };
     const dim3 per_wave(std::clamp<unsigned>(wgs(j, RELAX_TPB / 64), 1, RELAX_MAX_WG));
-    if (const int rc = reroot_reset(ctx, rv)) return rc;
-    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, RELAX_STATS * sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(rv.ok, 1, (size_t)j, ctx->stream));  // no edge is cut
+    if (const int rc = reset_for_buckets(ctx, rv, xv)) return rc;
     HIPCHK(ctx, time.mark(0, ctx->stream));
-    hipLaunchKernelGGL(rrt_relax_cell_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
-    hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
-    hipLaunchKernelGGL(rrt_relax_fill_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
+    fill_buckets(ctx, xv, rrt_relax_cell_kernel, xv);
     if (poses) hipLaunchKernelGGL(rrt_pose_relax_item_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv);
     HIPCHK(ctx, time.mark(1, ctx->stream));
     int64_t rounds = 0;
@@ -974,7 +1051,7 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     costs[1] = tmp.out_vcost;
     HIPCHK(ctx, hipMemcpyAsync(costs[1], costs[0], (size_t)j * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
 #endif
-    if (const int rc = relax_rounds(who, b, q, xv, rx, [&](int in, int32_t first) {
+    if (const int rc = relax_rounds(c, xv, rx, [&](int in, int32_t first) {
             if (poses)
                 hipLaunchKernelGGL(rrt_pose_relax_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv, (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1],
                                    (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], first);
@@ -991,24 +1068,20 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
     unsigned long long stats[RELAX_STATS] = {0, 0, 0, 0};
     char what[256];
     snprintf(what, sizeof what, "the relaxed parents of query %d on the device are not a tree over all %d vertices, or its costs summed from the root "
-             "down are not the fixpoint's", q, j);
-    auto price = [&] {
-        if (!poses) return price_lines(ctx, rv);
-        // the j words in parallel (and the headings into the new order), then the sums level by level
-        hipLaunchKernelGGL(rrt_pose_relax_word_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv, rv, px.out_heading, px.word);
-        hipLaunchKernelGGL(rrt_pose_relax_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv, (const double *)px.word);
-    };
-    const int rc = order_price_and_seed(who, b, q, rv, tmp, time, 3, true, false, what, price, [&] {
+             "down are not the fixpoint's", c.q, j);
+    OrderAndSeed o;
+    o.mark0 = 3;
+    o.whole = true;
+    o.what = what;
+    o.out_heading = poses ? px.out_heading : nullptr;
+    const int rc = order_price_and_seed(c, rv, tmp, o, [&] { poses ? price_words(ctx, pv, rv, px) : price_lines(ctx, rv); }, [&] {
         hipLaunchKernelGGL(rrt_relax_check_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv, (const int32_t *)tmp.src, (const double *)tmp.out_vcost,
                            (const int32_t *)(tmp.head + REROOT_COUNT));
         HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
         return (int)RRT_OK;
-    }, m, j0_out, old_id, log0, poses ? px.out_heading : nullptr);
+    });
     if (rc != RRT_OK) return rc;
-    b->relax_stats[0] = rounds;
-    b->relax_stats[1] = (int64_t)stats[RELAX_FELL];
-    b->relax_stats[2] = (int64_t)stats[RELAX_LOS];
-    b->relax_stats[3] = (int64_t)stats[RELAX_PRICED];
+    store_front_stats(b, rounds, stats);
     return RRT_OK;
 }
 
@@ -1018,38 +1091,35 @@ static int batch_relax(const char *who, rrt_batch *b, int32_t q, int64_t r2, con
 // the old edges' words for what hangs below it in the old tree (the link kernel, the pointer jumping and the order by depth over the
 // OLD parents, then rrt_pose_reroot_start_kernel), and at +inf elsewhere.  What is +inf at the fixpoint is cut; the later stages are
 // order_price_and_seed's with whole = false and new_start = true, and the descriptor's hs becomes the root's heading too.
-static int batch_reroot_poses(const char *who, rrt_batch *b, int32_t q, int32_t root, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0_out,
-                              int32_t *old_id, int32_t *log0) {
+static int batch_reroot_poses(const SeedCall &c, int32_t root, int64_t r2) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
+    const char *who = c.who;
+    const int32_t q = c.q;
     int j_in = 0;
-    if (const int rc = refuse_grow(who, b, q, !j0_out || !log0 || (m > 0 && !samples), m, true, "", j_in, "rrt_batch_reroot")) return rc;
-    if (b->n_cap > REROOT_WAVES * REROOT_OWN)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a batch of capacity %d; the placement by depth takes trees of up to %d vertices", who, b->n_cap,
-                    REROOT_WAVES * REROOT_OWN);
-    QDesc &d = b->h_desc[(size_t)q];
+    if (const int rc = refuse_grow(c, "", j_in, "rrt_batch_reroot")) return rc;
+    if (const int rc = refuse_capacity(c)) return rc;
+    QDesc &d = c.desc();
     if (root < 0 || root >= d.j) return fail(ctx, RRT_E_ARG, "%s: root=%d, query %d has the vertices [0, %d)", who, root, q, d.j);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, b->seed_tmp.reserve<SeedTmpScratch>(b->n_cap));
     const TreeRef t = tree_ref(b, q);
     RerootView rv{};
-    rv.og = ctx->og;
-    rv.H = ctx->H;
     PoseRerootView fv{};
     // with a view the input is the view: its parents renumbered into scratch, and the root's number in it (-1: not alive)
-    if (const int rc = tree_input(who, b, q, t, b->seed_tmp.carve<SeedTmpScratch>(), j_in, root, rv, fv.root, &fv.heading)) return rc;
+    if (const int rc = tree_input(c, t, j_in, root, rv, fv.root, &fv.heading)) return rc;
     if (fv.root < 0)
         return fail(ctx, RRT_E_ARG, "%s: root=%d is not alive in the kept view of query %d (%d of %d vertices alive)", who, root, q, j_in, d.j);
     if (r2 < 0) return fail(ctx, RRT_E_ARG, "%s: r2=%lld: the threshold of the squared distance cannot be negative", who, (long long)r2);
-    if (const int rc = stage_cells(who, b, q, "sample", samples, m, d.nh)) return rc;
-    HIPCHK(ctx, b->reroot_tmp.reserve<RerootScratch>(b->n_cap));
-    HIPCHK(ctx, b->relax_tmp.reserve<RelaxScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
-    HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
+    if (const int rc = stage_samples(c)) return rc;
+    if (const int rc = reserve_relax_set(c)) return rc;
     HIPCHK(ctx, b->pose_reroot_tmp.reserve<PoseRerootScratch>(b->n_cap));
     HIPCHK(ctx, b->seed_time.create(4));
-    HIPCHK(ctx, b->pose_reroot_time.create(8));
-    const RerootScratch tmp = b->reroot_tmp.carve<RerootScratch>();
-    const RelaxScratch rx = b->relax_tmp.carve<RelaxScratch>((size_t)RELAX_MAX_CELLS);
-    const PoseRelaxScratch px = b->pose_relax_tmp.carve<PoseRelaxScratch>();
+    HIPCHK(ctx, b->front_time.create(8));
+    const RelaxSet set(c);
+    const RerootScratch &tmp = set.tmp;
+    const RelaxScratch &rx = set.rx;
+    const PoseRelaxScratch &px = set.px;
     const PoseRerootScratch fx = b->pose_reroot_tmp.carve<PoseRerootScratch>();
     const int j = j_in;
     fv.nodes = rv.nodes;
@@ -1072,26 +1142,16 @@ static int batch_reroot_poses(const char *who, rrt_batch *b, int32_t q, int32_t 
     xv.vcost = nullptr;  // (the costs start from the sums below the new root: no kernel of this call reads the old ones)
     xv.j = j;
     relax_view(ctx, xv, r2, rx, tmp);
-    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
     PoseRelaxView pv{};
     pv.heading = fx.f_heading;
     pose_relax_view(ctx, pv, xv, d, px);
-    // ---- from here on the query is being replaced ----
-    StageTimer &time = b->pose_reroot_time;
-    time.ran = b->relax_time.ran = b->reroot_time.ran = 0;
-    b->seed_time.ran = 0;
-    b->drop_routes();
-    d.status = ST_IDLE;  // (until seed_and_arm has armed the descriptor: a failure on the way leaves a query without a tree)
+    start_replacing(c);
+    StageTimer &time = b->front_time;
     auto blocks = [](int items) { return dim3(wgs(items, RELAX_TPB)); };
     const dim3 per_wave(std::clamp<unsigned>(wgs(j, RELAX_TPB / 64), 1, RELAX_MAX_WG));
-    if (const int rc = reroot_reset(ctx, rv)) return rc;
-    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, RELAX_STATS * sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(rv.ok, 1, (size_t)j, ctx->stream));
+    if (const int rc = reset_for_buckets(ctx, rv, xv)) return rc;
     HIPCHK(ctx, time.mark(0, ctx->stream));
-    hipLaunchKernelGGL(rrt_pose_reroot_front_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, fv, xv);
-    hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
-    hipLaunchKernelGGL(rrt_relax_fill_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv);
+    fill_buckets(ctx, xv, rrt_pose_reroot_front_kernel, fv, xv);
     hipLaunchKernelGGL(rrt_pose_relax_item_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv);
     HIPCHK(ctx, time.mark(1, ctx->stream));
     {  // the start: what hangs below the new root in the OLD tree, placed by depth, and its costs along the old edges
@@ -1106,7 +1166,7 @@ static int batch_reroot_poses(const char *who, rrt_batch *b, int32_t q, int32_t 
     }
     HIPCHK(ctx, time.mark(2, ctx->stream));
     int64_t rounds = 0;
-    if (const int rc = relax_rounds(who, b, q, xv, rx, [&](int in, int32_t first) {
+    if (const int rc = relax_rounds(c, xv, rx, [&](int in, int32_t first) {
             hipLaunchKernelGGL(rrt_pose_reroot_round_kernel, per_wave, dim3(RELAX_TPB), 0, ctx->stream, pv, (const uint8_t *)rx.dirty[in], rx.dirty[in ^ 1],
                                (const uint8_t *)rx.changed[in], rx.changed[in ^ 1], first);
         }, rounds))
@@ -1120,11 +1180,13 @@ static int batch_reroot_poses(const char *who, rrt_batch *b, int32_t q, int32_t 
     char what[256];
     snprintf(what, sizeof what, "the parents of query %d on the device chosen from its new root are not a tree over the vertices that were reached, or "
              "its costs summed from the root down are not the fixpoint's", q);
-    auto price = [&] {
-        hipLaunchKernelGGL(rrt_pose_relax_word_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, pv, rv, px.out_heading, px.word);
-        hipLaunchKernelGGL(rrt_pose_relax_cost_kernel, dim3(1), dim3(TPB), 0, ctx->stream, rv, (const double *)px.word);
-    };
-    const int rc = order_price_and_seed(who, b, q, rv, tmp, time, 4, false, true, what, price, [&] {
+    OrderAndSeed o;
+    o.mark0 = 4;
+    o.new_start = true;
+    o.what = what;
+    o.out_heading = px.out_heading;
+    o.start_heading = &root_heading;
+    const int rc = order_price_and_seed(c, rv, tmp, o, [&] { price_words(ctx, pv, rv, px); }, [&] {
         hipLaunchKernelGGL(rrt_pose_reroot_check_kernel, blocks(j), dim3(RELAX_TPB), 0, ctx->stream, xv, (const int32_t *)tmp.src, (const double *)tmp.out_vcost,
                            (const int32_t *)(tmp.head + REROOT_COUNT));
         // the new start: the root's cell to the head, where order_price_and_seed reads it, and its heading index
@@ -1132,207 +1194,79 @@ static int batch_reroot_poses(const char *who, rrt_batch *b, int32_t q, int32_t 
         HIPCHK(ctx, hipMemcpyAsync(&root_heading, px.out_heading, 1, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
         return (int)RRT_OK;
-    }, m, j0_out, old_id, log0, px.out_heading, &root_heading);
+    });
     if (rc != RRT_OK) return rc;
-    b->pose_reroot_stats[0] = rounds;
-    b->pose_reroot_stats[1] = (int64_t)stats[RELAX_FELL];
-    b->pose_reroot_stats[2] = (int64_t)stats[RELAX_LOS];
-    b->pose_reroot_stats[3] = (int64_t)stats[RELAX_PRICED];
+    store_front_stats(b, rounds, stats);
     return RRT_OK;
+}
+
+// ---- the entry points of the seed calls ----
+// The rrt_batch_ form of a seed call hands its record to `call`, the batch-level call, with what that takes beside the record (`lead`).
+// The rrt_plan_ form does the same with a record that lacks batch and log0, which become the batch behind rrt_plan and a local, and
+// adds the launch and the result of rrt_plan.
+template <typename Call, typename... Lead>
+static int batch_seed(const SeedCall &c, Call call, Lead... lead) {
+    return c.b ? call(c, lead...) : fail(nullptr, RRT_E_ARG, "%s: NULL", c.who);
+}
+
+template <typename Call, typename... Lead>
+static int plan_seed(SeedCall c, rrt_ctx *ctx, rrt_result *out, Call call, Lead... lead) {
+    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", c.who);
+    int32_t log0 = 0;
+    c.b = plan_batch(ctx, c.who, NO_PLAN_NO_TREE);
+    c.log0 = &log0;
+    const int rc = c.b ? call(c, lead...) : RRT_E_ARG;
+    return rc != RRT_OK ? rc : run_single(ctx, out);
 }
 
 extern "C" int rrt_batch_grow(rrt_batch *b, int32_t q, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_grow("rrt_batch_grow", b, q, samples_xy, m, j0, old_id, log0, false) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow: NULL");
+    return batch_seed({"rrt_batch_grow", SeedKind::grow, b, q, samples_xy, m, j0, old_id, log0, false}, batch_grow);
 }
 
 extern "C" int rrt_batch_grow_poses(rrt_batch *b, int32_t q, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_grow("rrt_batch_grow_poses", b, q, samples_xyh, m, j0, old_id, log0, true) : fail(nullptr, RRT_E_ARG, "rrt_batch_grow_poses: NULL");
-}
-
-static int plan_grow(const char *who, rrt_ctx *ctx, const int32_t *samples, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out, bool poses) {
-    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
-    if (!s) return RRT_E_ARG;
-    int32_t log0 = 0;
-    const int rc = batch_grow(who, s, 0, samples, m, j0, old_id, &log0, poses);
-    return rc != RRT_OK ? rc : run_single(ctx, out);
+    return batch_seed({"rrt_batch_grow_poses", SeedKind::grow, b, q, samples_xyh, m, j0, old_id, log0, true}, batch_grow);
 }
 
 extern "C" int rrt_plan_grow(rrt_ctx *ctx, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    return plan_grow("rrt_plan_grow", ctx, samples_xy, m, j0, old_id, out, false);
+    return plan_seed({"rrt_plan_grow", SeedKind::grow, nullptr, 0, samples_xy, m, j0, old_id, nullptr, false}, ctx, out, batch_grow);
 }
 
 extern "C" int rrt_plan_grow_poses(rrt_ctx *ctx, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    return plan_grow("rrt_plan_grow_poses", ctx, samples_xyh, m, j0, old_id, out, true);
-}
-
-extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_grow_ms: NULL");
-    if (count < 1 || count > 3) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: count=%d, the seed has 3 stages", count);
-    if (!b->seed_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: no rrt_batch_grow on this batch yet, or its last one failed");
-    if (b->reroot_time.ran || b->relax_time.ran || b->pose_reroot_time.ran)  // (the seed's times are that call's: rrt_batch_reroot_ms / rrt_batch_relax_ms report them)
-        return fail(b->ctx, RRT_E_ARG, "rrt_batch_grow_ms: a reroot or a relax came after the last rrt_batch_grow on this batch");
-    HIPCHK(b->ctx, b->seed_time.read(ms, count));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_grow_ms", NO_PLAN);
-    return s ? rrt_batch_grow_ms(s, ms, count) : RRT_E_ARG;
+    return plan_seed({"rrt_plan_grow_poses", SeedKind::grow, nullptr, 0, samples_xyh, m, j0, old_id, nullptr, true}, ctx, out, batch_grow);
 }
 
 extern "C" int rrt_batch_reroot(rrt_batch *b, int32_t q, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_reroot("rrt_batch_reroot", b, q, root, samples_xy, m, j0, old_id, log0) : fail(nullptr, RRT_E_ARG, "rrt_batch_reroot: NULL");
+    return batch_seed({"rrt_batch_reroot", SeedKind::reroot, b, q, samples_xy, m, j0, old_id, log0, false}, batch_reroot, root);
 }
 
 extern "C" int rrt_plan_reroot(rrt_ctx *ctx, int32_t root, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    const char *who = "rrt_plan_reroot";
-    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
-    if (!s) return RRT_E_ARG;
-    int32_t log0 = 0;
-    const int rc = batch_reroot(who, s, 0, root, samples_xy, m, j0, old_id, &log0);
-    return rc != RRT_OK ? rc : run_single(ctx, out);
-}
-
-// ms[0, 5): path, edge test, alive and depth, order, costs; ms[5, 8): the seed's stages, as rrt_batch_grow_ms reports them
-extern "C" int rrt_batch_reroot_ms(rrt_batch *b, float *ms, int32_t count) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_reroot_ms: NULL");
-    if (count < 1 || count > 8) return fail(b->ctx, RRT_E_ARG, "rrt_batch_reroot_ms: count=%d, a re-root has 5 stages and its seed 3", count);
-    if (!b->reroot_time.ran || !b->seed_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "rrt_batch_reroot_ms: no rrt_batch_reroot on this batch yet, its last one failed, or a grow came after it");
-    HIPCHK(b->ctx, b->reroot_time.read(ms, std::min(count, 5)));
-    if (count > 5) HIPCHK(b->ctx, b->seed_time.read(ms + 5, count - 5));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_ms", NO_PLAN);
-    return s ? rrt_batch_reroot_ms(s, ms, count) : RRT_E_ARG;
+    return plan_seed({"rrt_plan_reroot", SeedKind::reroot, nullptr, 0, samples_xy, m, j0, old_id, nullptr, false}, ctx, out, batch_reroot, root);
 }
 
 extern "C" int rrt_batch_relax(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_relax("rrt_batch_relax", b, q, r2, samples_xy, m, j0, old_id, log0, false) : fail(nullptr, RRT_E_ARG, "rrt_batch_relax: NULL");
+    return batch_seed({"rrt_batch_relax", SeedKind::relax, b, q, samples_xy, m, j0, old_id, log0, false}, batch_relax, r2);
 }
 
 extern "C" int rrt_batch_relax_poses(rrt_batch *b, int32_t q, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, int32_t *log0) {
-    return b ? batch_relax("rrt_batch_relax_poses", b, q, r2, samples_xyh, m, j0, old_id, log0, true) : fail(nullptr, RRT_E_ARG, "rrt_batch_relax_poses: NULL");
-}
-
-static int plan_relax(const char *who, rrt_ctx *ctx, int64_t r2, const int32_t *samples, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out, bool poses) {
-    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
-    if (!s) return RRT_E_ARG;
-    int32_t log0 = 0;
-    const int rc = batch_relax(who, s, 0, r2, samples, m, j0, old_id, &log0, poses);
-    return rc != RRT_OK ? rc : run_single(ctx, out);
+    return batch_seed({"rrt_batch_relax_poses", SeedKind::relax, b, q, samples_xyh, m, j0, old_id, log0, true}, batch_relax, r2);
 }
 
 extern "C" int rrt_plan_relax(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xy, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    return plan_relax("rrt_plan_relax", ctx, r2, samples_xy, m, j0, old_id, out, false);
+    return plan_seed({"rrt_plan_relax", SeedKind::relax, nullptr, 0, samples_xy, m, j0, old_id, nullptr, false}, ctx, out, batch_relax, r2);
 }
 
 extern "C" int rrt_plan_relax_poses(rrt_ctx *ctx, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id, rrt_result *out) {
-    return plan_relax("rrt_plan_relax_poses", ctx, r2, samples_xyh, m, j0, old_id, out, true);
-}
-
-// ms[0, 6): buckets, rounds, parents, alive and depth, order, costs; ms[6, 9): the seed's stages, as rrt_batch_grow_ms reports them.
-// A batch is a Dubins batch or not for life, so the timer and the counters of a batch belong to one of the two calls: `call` names it.
-static int relax_ms(const char *who, const char *call, rrt_batch *b, float *ms, int32_t count) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
-    if (count < 1 || count > 9) return fail(b->ctx, RRT_E_ARG, "%s: count=%d, a relax has 6 stages and its seed 3", who, count);
-    if (!b->relax_time.ran || !b->seed_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "%s: no %s on this batch yet, its last one failed, or a grow or a reroot came after it", who, call);
-    HIPCHK(b->ctx, b->relax_time.read(ms, std::min(count, 6)));
-    if (count > 6) HIPCHK(b->ctx, b->seed_time.read(ms + 6, count - 6));
-    return RRT_OK;
-}
-
-static int relax_stats(const char *who, const char *call, rrt_batch *b, int64_t out[4]) {
-    if (!b || !out) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
-    if (!b->relax_time.ran) return fail(b->ctx, RRT_E_ARG, "%s: no %s on this batch yet, its last one failed, or a grow or a reroot came after it", who, call);
-    for (int k = 0; k < 4; ++k) out[k] = b->relax_stats[k];
-    return RRT_OK;
-}
-
-extern "C" int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count) { return relax_ms("rrt_batch_relax_ms", "rrt_batch_relax", b, ms, count); }
-
-extern "C" int rrt_batch_relax_poses_ms(rrt_batch *b, float *ms, int32_t count) {
-    return relax_ms("rrt_batch_relax_poses_ms", "rrt_batch_relax_poses", b, ms, count);
-}
-
-extern "C" int rrt_plan_relax_poses_ms(rrt_ctx *ctx, float *ms, int32_t count) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_poses_ms", NO_PLAN);
-    return s ? rrt_batch_relax_poses_ms(s, ms, count) : RRT_E_ARG;
-}
-
-extern "C" int rrt_batch_relax_poses_stats(rrt_batch *b, int64_t out[4]) {
-    return relax_stats("rrt_batch_relax_poses_stats", "rrt_batch_relax_poses", b, out);
-}
-
-extern "C" int rrt_plan_relax_poses_stats(rrt_ctx *ctx, int64_t out[4]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_poses_stats", NO_PLAN);
-    return s ? rrt_batch_relax_poses_stats(s, out) : RRT_E_ARG;
-}
-
-extern "C" int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_ms", NO_PLAN);
-    return s ? rrt_batch_relax_ms(s, ms, count) : RRT_E_ARG;
-}
-
-extern "C" int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]) { return relax_stats("rrt_batch_relax_stats", "rrt_batch_relax", b, out); }
-
-extern "C" int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_relax_stats", NO_PLAN);
-    return s ? rrt_batch_relax_stats(s, out) : RRT_E_ARG;
+    return plan_seed({"rrt_plan_relax_poses", SeedKind::relax, nullptr, 0, samples_xyh, m, j0, old_id, nullptr, true}, ctx, out, batch_relax, r2);
 }
 
 extern "C" int rrt_batch_reroot_poses(rrt_batch *b, int32_t q, int32_t root, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id,
                                       int32_t *log0) {
-    return b ? batch_reroot_poses("rrt_batch_reroot_poses", b, q, root, r2, samples_xyh, m, j0, old_id, log0)
-             : fail(nullptr, RRT_E_ARG, "rrt_batch_reroot_poses: NULL");
+    return batch_seed({"rrt_batch_reroot_poses", SeedKind::reroot_poses, b, q, samples_xyh, m, j0, old_id, log0, true}, batch_reroot_poses, root, r2);
 }
 
 extern "C" int rrt_plan_reroot_poses(rrt_ctx *ctx, int32_t root, int64_t r2, const int32_t *samples_xyh, int32_t m, int32_t *j0, int32_t *old_id,
                                      rrt_result *out) {
-    const char *who = "rrt_plan_reroot_poses";
-    if (ctx && !out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    rrt_batch *s = plan_batch(ctx, who, NO_PLAN_NO_TREE);
-    if (!s) return RRT_E_ARG;
-    int32_t log0 = 0;
-    const int rc = batch_reroot_poses(who, s, 0, root, r2, samples_xyh, m, j0, old_id, &log0);
-    return rc != RRT_OK ? rc : run_single(ctx, out);
-}
-
-// ms[0, 7): buckets, start, rounds, parents, alive and depth, order, costs; ms[7, 10): the seed's stages, as rrt_batch_grow_ms reports them
-extern "C" int rrt_batch_reroot_poses_ms(rrt_batch *b, float *ms, int32_t count) {
-    const char *who = "rrt_batch_reroot_poses_ms";
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
-    if (count < 1 || count > 10) return fail(b->ctx, RRT_E_ARG, "%s: count=%d, a pose re-root has 7 stages and its seed 3", who, count);
-    if (!b->pose_reroot_time.ran || !b->seed_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "%s: no rrt_batch_reroot_poses on this batch yet, its last one failed, or another seed call came after it", who);
-    HIPCHK(b->ctx, b->pose_reroot_time.read(ms, std::min(count, 7)));
-    if (count > 7) HIPCHK(b->ctx, b->seed_time.read(ms + 7, count - 7));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_reroot_poses_ms(rrt_ctx *ctx, float *ms, int32_t count) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_poses_ms", NO_PLAN);
-    return s ? rrt_batch_reroot_poses_ms(s, ms, count) : RRT_E_ARG;
-}
-
-extern "C" int rrt_batch_reroot_poses_stats(rrt_batch *b, int64_t out[4]) {
-    const char *who = "rrt_batch_reroot_poses_stats";
-    if (!b || !out) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
-    if (!b->pose_reroot_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "%s: no rrt_batch_reroot_poses on this batch yet, its last one failed, or another seed call came after it", who);
-    for (int k = 0; k < 4; ++k) out[k] = b->pose_reroot_stats[k];
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_reroot_poses_stats(rrt_ctx *ctx, int64_t out[4]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_reroot_poses_stats", NO_PLAN);
-    return s ? rrt_batch_reroot_poses_stats(s, out) : RRT_E_ARG;
+    return plan_seed({"rrt_plan_reroot_poses", SeedKind::reroot_poses, nullptr, 0, samples_xyh, m, j0, old_id, nullptr, true}, ctx, out, batch_reroot_poses, root, r2);
 }
 
 // ---- the rows of the routes to the goals a decision answered: what rrt_batch_routes and rrt_batch_pose_routes start with ----
@@ -1361,9 +1295,16 @@ static int count_route_rows(const char *who, rrt_batch *b, int32_t q, const Rout
 }
 
 // ---- finished routes to many goals (rrt_routes.h) ----
-static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
-                        double *length, int64_t *offsets) {
+// where a routes call puts its answers: an entry per goal, one more in offsets and in point_offsets (the pose calls' alone)
+struct RoutesOut {
+    int32_t *vertex;
+    double *cost, *length;
+    int64_t *offsets, *point_offsets;
+};
+
+static int batch_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, const RoutesOut &out) {
     rrt_ctx *ctx = b->ctx;
+    const auto [vertex, cost, length, offsets, point_offsets] = out;
     b->route_rows = -1;  // whatever happens below, the rows of an earlier call are gone
     if (flags & ~(uint32_t)RRT_ROUTES_SHORTCUT) return fail(ctx, RRT_E_ARG, "%s: flags=0x%x, only RRT_ROUTES_SHORTCUT is defined", who, flags);
     if (const int rc = goals_decide(who, b, q, goals_xy, m, !vertex || !cost || !length || !offsets); rc != RRT_OK) return rc;
@@ -1432,7 +1373,7 @@ static int batch_routes_rows(const char *who, rrt_batch *b, int32_t *xy, int32_t
 
 extern "C" int rrt_batch_routes(rrt_batch *b, int32_t q, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                                 int64_t *offsets) {
-    return b ? batch_routes("rrt_batch_routes", b, q, goals_xy, m, flags, vertex, cost, length, offsets) : fail(nullptr, RRT_E_ARG, "rrt_batch_routes: NULL");
+    return b ? batch_routes("rrt_batch_routes", b, q, goals_xy, m, flags, {vertex, cost, length, offsets, nullptr}) : fail(nullptr, RRT_E_ARG, "rrt_batch_routes: NULL");
 }
 
 extern "C" int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int64_t rows) {
@@ -1441,7 +1382,7 @@ extern "C" int rrt_batch_routes_rows(rrt_batch *b, int32_t *xy, int32_t *id, int
 
 extern "C" int rrt_plan_routes(rrt_ctx *ctx, const int32_t *goals_xy, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length, int64_t *offsets) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_routes", NO_PLAN_NO_TREE);
-    return s ? batch_routes("rrt_plan_routes", s, 0, goals_xy, m, flags, vertex, cost, length, offsets) : RRT_E_ARG;
+    return s ? batch_routes("rrt_plan_routes", s, 0, goals_xy, m, flags, {vertex, cost, length, offsets, nullptr}) : RRT_E_ARG;
 }
 
 extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int64_t rows) {
@@ -1454,9 +1395,9 @@ extern "C" int rrt_plan_routes_rows(rrt_ctx *ctx, int32_t *xy, int32_t *id, int6
 // scratch of their own, the shortcut kernel keeps some of them, and the dense rows that the leg, length and points kernels read are
 // the kept ones under their own offsets.  The rows and points either call leaves are what the _rows / _points calls serve; the stage
 // times are kept apart (pose_route_time / pose_cut_time), so that rrt_batch_pose_routes_ms goes on reporting the last plain call.
-static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
-                             double *length, int64_t *offsets, int64_t *point_offsets, bool cut) {
+static int batch_pose_routes(const char *who, rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, const RoutesOut &out, bool cut) {
     rrt_ctx *ctx = b->ctx;
+    const auto [vertex, cost, length, offsets, point_offsets] = out;
     b->pose_route_rows = b->pose_route_points = -1;  // whatever happens below, the rows and points of an earlier call are gone
     StageTimer &time = cut ? b->pose_cut_time : b->pose_route_time;
     time.ran = 0;
@@ -1657,7 +1598,7 @@ static int batch_pose_routes_points(const char *who, rrt_batch *b, double *xy, i
 
 extern "C" int rrt_batch_pose_routes(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                                      int64_t *offsets, int64_t *point_offsets) {
-    return b ? batch_pose_routes("rrt_batch_pose_routes", b, q, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, false)
+    return b ? batch_pose_routes("rrt_batch_pose_routes", b, q, poses_xyh, m, flags, {vertex, cost, length, offsets, point_offsets}, false)
              : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes: NULL");
 }
 
@@ -1672,20 +1613,20 @@ extern "C" int rrt_batch_pose_routes_points(rrt_batch *b, double *xy, int64_t po
 extern "C" int rrt_plan_pose_routes(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                                     int64_t *offsets, int64_t *point_offsets) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes", NO_PLAN_NO_TREE);
-    return s ? batch_pose_routes("rrt_plan_pose_routes", s, 0, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, false) : RRT_E_ARG;
+    return s ? batch_pose_routes("rrt_plan_pose_routes", s, 0, poses_xyh, m, flags, {vertex, cost, length, offsets, point_offsets}, false) : RRT_E_ARG;
 }
 
 // the same call with the shortcut pass (rrt_pose_route_cut_kernel) between the walks and the legs
 extern "C" int rrt_batch_pose_shortcuts(rrt_batch *b, int32_t q, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost,
                                         double *length, int64_t *offsets, int64_t *point_offsets) {
-    return b ? batch_pose_routes("rrt_batch_pose_shortcuts", b, q, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, true)
+    return b ? batch_pose_routes("rrt_batch_pose_shortcuts", b, q, poses_xyh, m, flags, {vertex, cost, length, offsets, point_offsets}, true)
              : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_shortcuts: NULL");
 }
 
 extern "C" int rrt_plan_pose_shortcuts(rrt_ctx *ctx, const int32_t *poses_xyh, int32_t m, uint32_t flags, int32_t *vertex, double *cost, double *length,
                                        int64_t *offsets, int64_t *point_offsets) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_shortcuts", NO_PLAN_NO_TREE);
-    return s ? batch_pose_routes("rrt_plan_pose_shortcuts", s, 0, poses_xyh, m, flags, vertex, cost, length, offsets, point_offsets, true) : RRT_E_ARG;
+    return s ? batch_pose_routes("rrt_plan_pose_shortcuts", s, 0, poses_xyh, m, flags, {vertex, cost, length, offsets, point_offsets}, true) : RRT_E_ARG;
 }
 
 extern "C" int rrt_plan_pose_routes_rows(rrt_ctx *ctx, int32_t *xyh, int32_t *id, int64_t rows) {
@@ -1698,42 +1639,18 @@ extern "C" int rrt_plan_pose_routes_points(rrt_ctx *ctx, double *xy, int64_t poi
     return s ? batch_pose_routes_points("rrt_plan_pose_routes_points", s, xy, points) : RRT_E_ARG;
 }
 
-// kernel time in ms of the stages of the last successful rrt_batch_pose_routes: the decision (the pose goals kernel), depth and scan,
-// rows + legs + lengths (+ the scan of the point counts), the points (0 for a call without points, or without a point)
-extern "C" int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_pose_routes_ms: NULL");
-    if (!b->pose_route_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_routes_ms: no rrt_batch_pose_routes with a pose on this batch yet, or its last one failed");
-    HIPCHK(b->ctx, b->pose_route_time.read(ms, 4));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_routes_ms", NO_PLAN);
-    return s ? rrt_batch_pose_routes_ms(s, ms) : RRT_E_ARG;
-}
-
-// kernel time in ms of the stages of the last successful rrt_batch_pose_shortcuts: the decision, depth and scan, rows + shortcuts + scan
-// + pack, legs + lengths (+ the scan of the point counts), the points (0 for a call without points, or without a point)
-extern "C" int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_pose_shortcuts_ms: NULL");
-    if (!b->pose_cut_time.ran)
-        return fail(b->ctx, RRT_E_ARG, "rrt_batch_pose_shortcuts_ms: no rrt_batch_pose_shortcuts with a pose on this batch yet, or its last one failed");
-    HIPCHK(b->ctx, b->pose_cut_time.read(ms, 5));
-    return RRT_OK;
-}
-
-extern "C" int rrt_plan_pose_shortcuts_ms(rrt_ctx *ctx, float ms[5]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_shortcuts_ms", NO_PLAN);
-    return s ? rrt_batch_pose_shortcuts_ms(s, ms) : RRT_E_ARG;
-}
-
 // ---- the cost-to-come field: every cell of a window of the map against a finished tree (rrt_field.h) ----
 // connect_goals for every cell of the window, without the cells as goals: the vertices of the dense input (decide_over: the tree, or its
 // kept view) are bucketed once by the relax calls' bucket kernels (relax_cells gives the edge: FIELD_MIN_SHIFT, doubled until the cells
 // fit), and rrt_field_kernel decides every cell from the buckets whose lower bound can still beat what the cell has.  The answers go
 // through goal_vertex / goal_cost, which the goals calls share, and are copied out in the window's own (w, h) order.
-static int cost_field(const char *who, rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
+struct FieldWindow {
+    int32_t x0, y0, w, h;
+};
+
+static int cost_field(const char *who, rrt_batch *b, int32_t q, const FieldWindow &win, int32_t *vertex, double *cost) {
     rrt_ctx *ctx = b->ctx;
+    const int32_t x0 = win.x0, y0 = win.y0, w = win.w, h = win.h;
     if (b->flags & RRT_FLAG_DUBINS)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its goal is a pose, and there is no field of poses here; these kernels price straight lines to cells)", who);
     if (const int rc = refuse_goals_call(who, b, q, 0, "goals")) return rc;
@@ -1785,11 +1702,7 @@ static int cost_field(const char *who, rrt_batch *b, int32_t q, int32_t x0, int3
         xv.nodes = nodes;
         xv.vcost = vcost;
         xv.j = j;
-        if (j > 0) {
-            hipLaunchKernelGGL(rrt_relax_cell_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, xv);
-            hipLaunchKernelGGL(rrt_relax_scan_kernel, dim3(1), dim3(TPB), 0, ctx->stream, xv);
-            hipLaunchKernelGGL(rrt_relax_fill_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, xv);
-        }
+        if (j > 0) fill_buckets(ctx, xv, rrt_relax_cell_kernel, xv);
         marked = time.mark(1, ctx->stream);
         const int64_t runs = (int64_t)w * ((h + FIELD_RUN - 1) / FIELD_RUN);
         hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_field_large_kernel : rrt_field_kernel,
@@ -1814,35 +1727,116 @@ static int cost_field(const char *who, rrt_batch *b, int32_t q, int32_t x0, int3
 }
 
 extern "C" int rrt_batch_cost_field(rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
-    return b ? cost_field("rrt_batch_cost_field", b, q, x0, y0, w, h, vertex, cost) : fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field: NULL");
+    return b ? cost_field("rrt_batch_cost_field", b, q, {x0, y0, w, h}, vertex, cost) : fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field: NULL");
 }
 
 extern "C" int rrt_plan_cost_field(rrt_ctx *ctx, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
     rrt_batch *s = plan_batch(ctx, "rrt_plan_cost_field", NO_PLAN_NO_TREE);
-    return s ? cost_field("rrt_plan_cost_field", s, 0, x0, y0, w, h, vertex, cost) : RRT_E_ARG;
+    return s ? cost_field("rrt_plan_cost_field", s, 0, {x0, y0, w, h}, vertex, cost) : RRT_E_ARG;
 }
 
+// ---- the reports: the kernel times in ms of the stages (_ms) and the counters (_stats) of the last successful call of a family ----
+// One row per family.  A family that is a seed call answers while it is the batch's last seed call (last_seed); the others answer
+// while their timer says that stages ran.  A stage that did not run reads 0.
+struct Report {
+    StageTimer rrt_batch::*time;     // the timer of the family's own stages
+    int own;                         // how many those are
+    bool seed;                       // the three stages of the seed follow them (seed_time)
+    int64_t (rrt_batch::*stats)[4];  // the family's counters, or nullptr
+    SeedKind kind;                   // the seed call it reports on; none: no seed call, the timer's `ran` says whether there is a call to report on
+    const char *stages;              // what a count out of range is told; nullptr: the form has a fixed size
+    const char *refusal;             // what the call is told when there is nothing to report
+    const char *after_other;         // rrt_batch_grow_ms alone: ... when another seed call came last
+};
+// ms[0, 3): edge test, pointer jumping, compaction
+static const Report KEEP_TREE{&rrt_batch::keep_time, 3, false, nullptr, SeedKind::none, nullptr,
+                              "no rrt_batch_keep_tree on this batch yet, or its last one failed", nullptr};
+// ms[0, 3): renumbering and node slots, bitmap, cell records
+static const Report GROW{&rrt_batch::seed_time, 0, true, nullptr, SeedKind::grow, "the seed has 3 stages",
+                         "no rrt_batch_grow on this batch yet, or its last one failed", "a reroot or a relax came after the last rrt_batch_grow on this batch"};
+// ms[0, 5): path, edge test, alive and depth, order, costs; ms[5, 8): the seed's stages, as rrt_batch_grow_ms reports them
+static const Report REROOT{&rrt_batch::front_time, 5, true, nullptr, SeedKind::reroot, "a re-root has 5 stages and its seed 3",
+                           "no rrt_batch_reroot on this batch yet, its last one failed, or a grow came after it", nullptr};
+// ms[0, 6): buckets, rounds, parents, alive and depth, order, costs; ms[6, 9): the seed's stages.  A batch is a Dubins batch or not for
+// life, so the kind, the timer and the counters of a batch belong to one of the two calls: each row names its own.
+static const Report RELAX{&rrt_batch::front_time, 6, true, &rrt_batch::front_stats, SeedKind::relax, "a relax has 6 stages and its seed 3",
+                          "no rrt_batch_relax on this batch yet, its last one failed, or a grow or a reroot came after it", nullptr};
+static const Report RELAX_POSES{&rrt_batch::front_time, 6, true, &rrt_batch::front_stats, SeedKind::relax, "a relax has 6 stages and its seed 3",
+                                "no rrt_batch_relax_poses on this batch yet, its last one failed, or a grow or a reroot came after it", nullptr};
+// ms[0, 7): buckets, start, rounds, parents, alive and depth, order, costs; ms[7, 10): the seed's stages
+static const Report REROOT_POSES{&rrt_batch::front_time, 7, true, &rrt_batch::front_stats, SeedKind::reroot_poses, "a pose re-root has 7 stages and its seed 3",
+                                 "no rrt_batch_reroot_poses on this batch yet, its last one failed, or another seed call came after it", nullptr};
+// ms[0, 4): the decision (the pose goals kernel), depth and scan, rows + legs + lengths (+ the scan of the point counts), the points (0 for
+// a call without points, or without a point)
+static const Report POSE_ROUTES{&rrt_batch::pose_route_time, 4, false, nullptr, SeedKind::none, nullptr,
+                                "no rrt_batch_pose_routes with a pose on this batch yet, or its last one failed", nullptr};
+// ms[0, 5): the decision, depth and scan, rows + shortcuts + scan + pack, legs + lengths (+ the scan of the point counts), the points
+static const Report POSE_SHORTCUTS{&rrt_batch::pose_cut_time, 5, false, nullptr, SeedKind::none, nullptr,
+                                   "no rrt_batch_pose_shortcuts with a pose on this batch yet, or its last one failed", nullptr};
 // ms[0, 4): buckets, decide, remap, read-back
-extern "C" int rrt_batch_cost_field_ms(rrt_batch *b, float ms[4]) {
-    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field_ms: NULL");
-    if (!b->field_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_cost_field_ms: no rrt_batch_cost_field on this batch yet, or its last one failed");
-    HIPCHK(b->ctx, b->field_time.read(ms, 4));
+static const Report COST_FIELD{&rrt_batch::field_time, 4, false, &rrt_batch::field_stats, SeedKind::none, nullptr,
+                               "no rrt_batch_cost_field on this batch yet, or its last one failed", nullptr};
+
+static int refuse_report(const char *who, const Report &r, rrt_batch *b) {
+    if (r.kind == SeedKind::none ? (b->*r.time).ran != 0 : b->last_seed == r.kind) return RRT_OK;
+    return fail(b->ctx, RRT_E_ARG, "%s: %s", who, r.after_other && b->last_seed != SeedKind::none ? r.after_other : r.refusal);
+}
+
+// ms[0, count): the family's own stages, then the seed's; a form of fixed size passes its size
+static int report_ms(const char *who, const Report &r, rrt_batch *b, float *ms, int32_t count) {
+    if (!b || !ms) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    if (r.stages && (count < 1 || count > r.own + (r.seed ? 3 : 0))) return fail(b->ctx, RRT_E_ARG, "%s: count=%d, %s", who, count, r.stages);
+    if (const int rc = refuse_report(who, r, b)) return rc;
+    if (r.own) HIPCHK(b->ctx, (b->*r.time).read(ms, std::min(count, r.own)));
+    if (count > r.own) HIPCHK(b->ctx, b->seed_time.read(ms + r.own, count - r.own));
     return RRT_OK;
 }
 
-extern "C" int rrt_plan_cost_field_ms(rrt_ctx *ctx, float ms[4]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_cost_field_ms", NO_PLAN);
-    return s ? rrt_batch_cost_field_ms(s, ms) : RRT_E_ARG;
-}
-
-extern "C" int rrt_batch_cost_field_stats(rrt_batch *b, int64_t out[4]) {
-    if (!b || !out) return fail(nullptr, RRT_E_ARG, "rrt_batch_cost_field_stats: NULL");
-    if (!b->field_time.ran) return fail(b->ctx, RRT_E_ARG, "rrt_batch_cost_field_stats: no rrt_batch_cost_field on this batch yet, or its last one failed");
-    for (int k = 0; k < 4; ++k) out[k] = b->field_stats[k];
+static int report_stats(const char *who, const Report &r, rrt_batch *b, int64_t out[4]) {
+    if (!b || !out) return fail(nullptr, RRT_E_ARG, "%s: NULL", who);
+    if (const int rc = refuse_report(who, r, b)) return rc;
+    for (int k = 0; k < 4; ++k) out[k] = (b->*r.stats)[k];
     return RRT_OK;
 }
 
-extern "C" int rrt_plan_cost_field_stats(rrt_ctx *ctx, int64_t out[4]) {
-    rrt_batch *s = plan_batch(ctx, "rrt_plan_cost_field_stats", NO_PLAN);
-    return s ? rrt_batch_cost_field_stats(s, out) : RRT_E_ARG;
+// the rrt_plan_ form of a report: the rrt_batch_ form on the batch behind rrt_plan, in that form's words
+template <typename... Args>
+static int plan_report(const char *who, rrt_ctx *ctx, int (*batch_form)(rrt_batch *, Args...), Args... args) {
+    rrt_batch *s = plan_batch(ctx, who, NO_PLAN);
+    return s ? batch_form(s, args...) : RRT_E_ARG;
 }
+
+extern "C" int rrt_batch_keep_tree_ms(rrt_batch *b, float ms[3]) { return report_ms("rrt_batch_keep_tree_ms", KEEP_TREE, b, ms, 3); }
+extern "C" int rrt_plan_keep_tree_ms(rrt_ctx *ctx, float ms[3]) { return plan_report("rrt_plan_keep_tree_ms", ctx, rrt_batch_keep_tree_ms, ms); }
+extern "C" int rrt_batch_grow_ms(rrt_batch *b, float *ms, int32_t count) { return report_ms("rrt_batch_grow_ms", GROW, b, ms, count); }
+extern "C" int rrt_plan_grow_ms(rrt_ctx *ctx, float *ms, int32_t count) { return plan_report("rrt_plan_grow_ms", ctx, rrt_batch_grow_ms, ms, count); }
+extern "C" int rrt_batch_reroot_ms(rrt_batch *b, float *ms, int32_t count) { return report_ms("rrt_batch_reroot_ms", REROOT, b, ms, count); }
+extern "C" int rrt_plan_reroot_ms(rrt_ctx *ctx, float *ms, int32_t count) { return plan_report("rrt_plan_reroot_ms", ctx, rrt_batch_reroot_ms, ms, count); }
+extern "C" int rrt_batch_relax_ms(rrt_batch *b, float *ms, int32_t count) { return report_ms("rrt_batch_relax_ms", RELAX, b, ms, count); }
+extern "C" int rrt_plan_relax_ms(rrt_ctx *ctx, float *ms, int32_t count) { return plan_report("rrt_plan_relax_ms", ctx, rrt_batch_relax_ms, ms, count); }
+extern "C" int rrt_batch_relax_stats(rrt_batch *b, int64_t out[4]) { return report_stats("rrt_batch_relax_stats", RELAX, b, out); }
+extern "C" int rrt_plan_relax_stats(rrt_ctx *ctx, int64_t out[4]) { return plan_report("rrt_plan_relax_stats", ctx, rrt_batch_relax_stats, out); }
+extern "C" int rrt_batch_relax_poses_ms(rrt_batch *b, float *ms, int32_t count) { return report_ms("rrt_batch_relax_poses_ms", RELAX_POSES, b, ms, count); }
+extern "C" int rrt_plan_relax_poses_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    return plan_report("rrt_plan_relax_poses_ms", ctx, rrt_batch_relax_poses_ms, ms, count);
+}
+extern "C" int rrt_batch_relax_poses_stats(rrt_batch *b, int64_t out[4]) { return report_stats("rrt_batch_relax_poses_stats", RELAX_POSES, b, out); }
+extern "C" int rrt_plan_relax_poses_stats(rrt_ctx *ctx, int64_t out[4]) {
+    return plan_report("rrt_plan_relax_poses_stats", ctx, rrt_batch_relax_poses_stats, out);
+}
+extern "C" int rrt_batch_reroot_poses_ms(rrt_batch *b, float *ms, int32_t count) { return report_ms("rrt_batch_reroot_poses_ms", REROOT_POSES, b, ms, count); }
+extern "C" int rrt_plan_reroot_poses_ms(rrt_ctx *ctx, float *ms, int32_t count) {
+    return plan_report("rrt_plan_reroot_poses_ms", ctx, rrt_batch_reroot_poses_ms, ms, count);
+}
+extern "C" int rrt_batch_reroot_poses_stats(rrt_batch *b, int64_t out[4]) { return report_stats("rrt_batch_reroot_poses_stats", REROOT_POSES, b, out); }
+extern "C" int rrt_plan_reroot_poses_stats(rrt_ctx *ctx, int64_t out[4]) {
+    return plan_report("rrt_plan_reroot_poses_stats", ctx, rrt_batch_reroot_poses_stats, out);
+}
+extern "C" int rrt_batch_pose_routes_ms(rrt_batch *b, float ms[4]) { return report_ms("rrt_batch_pose_routes_ms", POSE_ROUTES, b, ms, 4); }
+extern "C" int rrt_plan_pose_routes_ms(rrt_ctx *ctx, float ms[4]) { return plan_report("rrt_plan_pose_routes_ms", ctx, rrt_batch_pose_routes_ms, ms); }
+extern "C" int rrt_batch_pose_shortcuts_ms(rrt_batch *b, float ms[5]) { return report_ms("rrt_batch_pose_shortcuts_ms", POSE_SHORTCUTS, b, ms, 5); }
+extern "C" int rrt_plan_pose_shortcuts_ms(rrt_ctx *ctx, float ms[5]) { return plan_report("rrt_plan_pose_shortcuts_ms", ctx, rrt_batch_pose_shortcuts_ms, ms); }
+extern "C" int rrt_batch_cost_field_ms(rrt_batch *b, float ms[4]) { return report_ms("rrt_batch_cost_field_ms", COST_FIELD, b, ms, 4); }
+extern "C" int rrt_plan_cost_field_ms(rrt_ctx *ctx, float ms[4]) { return plan_report("rrt_plan_cost_field_ms", ctx, rrt_batch_cost_field_ms, ms); }
+extern "C" int rrt_batch_cost_field_stats(rrt_batch *b, int64_t out[4]) { return report_stats("rrt_batch_cost_field_stats", COST_FIELD, b, out); }
+extern "C" int rrt_plan_cost_field_stats(rrt_ctx *ctx, int64_t out[4]) { return plan_report("rrt_plan_cost_field_stats", ctx, rrt_batch_cost_field_stats, out); }
