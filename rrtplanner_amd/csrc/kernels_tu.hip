@@ -63,6 +63,11 @@ template __global__ void rrt_expand_kernel<true, false>(BatchView);
 #include "rrt_pose_relax.h"
 #include "rrt_pose_reroot.h"
 
+#elif RRT_TU == -1  // the pose cost field of a finished Dubins tree: every cell of a window of the map against it (rrt_pose_field_kernel
+                    // and the gather kernel in front of it), a unit of its own: not a team kernel.  (The numbers 0 to 9 are taken and those from
+                    // 10 on are the team kernels', so this one counts down.)
+#include "rrt_pose_field.h"
+
 #else  // teams of compute units: the variants that rrt_block_variants.def (included by rrt_block.h) deals to this unit
 #include "rrt_block.h"
 namespace rrtdev {

@@ -285,6 +285,12 @@ struct rrt_batch {
     DevBuf field_tmp;                             // FieldScratch of n_cap vertices and RELAX_MAX_CELLS cells
     StageTimer field_time{STAGES_IN_A_LONG_ROW};  // the four stages of the last rrt_batch_cost_field: buckets, decide, remap, read-back
     int64_t field_stats[4] = {0, 0, 0, 0};        // of that call: free cells decided, buckets visited, vertices priced, lines walked
+    // rrt_batch_pose_field (a Dubins batch, rrt_pose_field.h): its buckets are a FieldScratch in field_tmp, which no other call of a Dubins
+    // batch uses, and the heading byte of every item is PoseRelaxScratch's item_h in pose_relax_tmp, which relax_poses and reroot_poses
+    // fill anew in every call of theirs; the vertex and the cost of the window go through goal_vertex / goal_cost
+    DevBuf pose_field_heading;                         // i32 [cells of the window] the arrival heading of every answer
+    StageTimer pose_field_time{STAGES_IN_A_LONG_ROW};  // the four stages of the last rrt_batch_pose_field: buckets, decide, remap, read-back
+    int64_t pose_field_stats[4] = {0, 0, 0, 0};        // of that call: free cells decided, buckets visited, words evaluated, sweeps run
     // the rows and points an earlier routes call left are gone (a launch, a rearm, a keep, a grow: they belong to another tree or view)
     void drop_routes() { route_rows = pose_route_rows = pose_route_points = -1; }
 };

@@ -420,6 +420,35 @@ struct FieldView {
 };
 enum : int { FIELD_CELLS = 0, FIELD_BUCKETS_SEEN = 1, FIELD_PRICED = 2, FIELD_LOS = 3, FIELD_STATS = 4 };
 
+// ---- rrt_pose_field.h ----
+constexpr int POSE_FIELD_TPB = 256;      // 4 cells a workgroup at a time (one per wave)
+constexpr int POSE_FIELD_MAX_WG = 8192;  // workgroups of the decision, grid-stride beyond
+constexpr int POSE_FIELD_RUN = 16;       // most consecutive cells of one column that a wavefront decides one after the other, each starting from the winner before it
+constexpr int POSE_FIELD_WAVES = 4096;   // wavefronts a window should give work to before its runs grow: 16 on each of 256 CUs
+constexpr int POSE_FIELD_BUCKETS = 128;  // qualifying buckets a wavefront lists in LDS at a time (8 bytes each)
+constexpr int POSE_FIELD_LIST = 256;     // surviving vertices a wavefront lists in LDS (17 bytes each) before it expands them to pairs; with the
+                                         // heading table 27 KiB a workgroup: five of them fit the 160 KiB of a CU
+constexpr int POSE_FIELD_MAX_J = 1 << 18;  // vertices of the dense input: a pair's key is heading << 18 | vertex in 32 bits
+
+// The pose cost field of a window of the grid: for every cell the smallest (vcost[k] + word(pose_k -> (cell, a)).len, a, k) over the pairs
+// (heading a in [heading_lo, heading_hi), vertex k) whose sweep is free.  xv holds the buckets (rrt_relax.h's CSR with item_cost and
+// cell_min) over the dense input: the tree arrays, or the kept view.
+struct PoseFieldView {
+    RelaxView xv;
+    int32_t W;               // the grid's other side (xv.H is the stride)
+    int32_t nh;              // the query's discrete headings
+    double rho;              // ... and turning radius
+    const uint8_t *heading;  // [j] the heading index of every input vertex
+    uint8_t *item_h;         // [j] ... and of every item of the CSR, beside item_xy
+    int32_t x0, y0, w, h;    // the window, inside the grid
+    int32_t heading_lo, heading_hi;  // the arrival headings asked: one, [H, H + 1), or all, [0, nh)
+    int32_t run;             // consecutive cells of a column that one wavefront decides: 1 to POSE_FIELD_RUN
+    int32_t *vertex;         // [w * h] out, cell (x, y) at (x - x0) * h + (y - y0): the vertex in the numbers of the input, or -1
+    double *cost;            // [w * h] out: the cost through it, or +inf
+    int32_t *heading_out;    // [w * h] out: the arrival heading of the answer, or -1
+};
+enum : int { POSE_FIELD_CELLS = 0, POSE_FIELD_BUCKETS_SEEN = 1, POSE_FIELD_WORDS = 2, POSE_FIELD_SWEEPS = 3, POSE_FIELD_STATS = 4 };
+
 // ---- rrt_pose_reroot.h ----
 // The dense input of a pose re-root (the tree arrays or the kept view, as RerootView takes them, with the heading bytes) and where it
 // goes with `root` moved to the front as number 0 and the others in their order: what the relax kernels then take as their input.
@@ -524,5 +553,8 @@ __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_round_kernel(PoseRe
                                                                           uint8_t *changed_out, int32_t first);
 __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_parent_kernel(PoseRelaxView pv);
 __global__ __launch_bounds__(RELAX_TPB) void rrt_pose_reroot_check_kernel(RelaxView xv, const int32_t *src, const double *out_vcost, const int32_t *count);
+// rrt_pose_field.h (unit -1: the numbers 0 to 9 are taken and those from 10 on are the team kernels'; its buckets are rrt_relax.h's kernels of unit 0)
+__global__ __launch_bounds__(RELAX_TPB) void rrt_pose_field_item_kernel(PoseFieldView pv);
+__global__ __launch_bounds__(POSE_FIELD_TPB) void rrt_pose_field_kernel(PoseFieldView pv);
 
 }  // namespace rrtdev

@@ -7,10 +7,11 @@
 //                         reroot_poses (rrt_pose_reroot.h).  Each replaces a query's tree and re-arms it: one record says which call it is
 //                         (SeedCall), one place starts replacing the query (start_replacing), one arms it and makes the call the batch's last
 //                         (seed_and_arm)
-//   routes and the field  routes (rrt_routes.h), pose_routes, pose_shortcuts (rrt_pose_routes.h), cost_field (rrt_field.h)
+//   routes and the fields routes (rrt_routes.h), pose_routes, pose_shortcuts (rrt_pose_routes.h), cost_field (rrt_field.h), pose_field (rrt_pose_field.h)
 //   the reports           every _ms and _stats call: one table row per family (Report), one reader for the times and one for the counters
 #include "rrt_engine.h"
 #include "rrt_hip_field.h"  // rrt_batch_cost_field and its forms: declared beside rrt_hip.h, not in it
+#include "rrt_hip_pose_field.h"  // rrt_batch_pose_field and its forms: the same
 
 // ---- the gate: a finished tree on the grid it belongs to ----
 // Every call makes these in this order, after the refusals that are its own (NULL, the batch's flags).  0: not refused.
@@ -1735,6 +1736,121 @@ extern "C" int rrt_plan_cost_field(rrt_ctx *ctx, int32_t x0, int32_t y0, int32_t
     return s ? cost_field("rrt_plan_cost_field", s, 0, {x0, y0, w, h}, vertex, cost) : RRT_E_ARG;
 }
 
+// ---- the pose cost field: every cell of a window of the map against a finished Dubins tree (rrt_pose_field.h) ----
+// connect_poses for every cell of the window, at one arrival heading or at the best of all of them (heading -1), without the cells as
+// goal poses: cost_field's buckets (a FieldScratch in field_tmp, which no other call of a Dubins batch uses), the heading byte of every
+// item beside them (PoseRelaxScratch's item_h: the relax calls fill it anew each time), and rrt_pose_field_kernel.  Vertex and cost go through goal_vertex / goal_cost, the arrival
+// heading through pose_field_heading; all three are copied out in the window's own (w, h) order.
+static int pose_field(const char *who, rrt_batch *b, int32_t q, const FieldWindow &win, int32_t heading, int32_t *vertex, double *cost, int32_t *heading_out) {
+    rrt_ctx *ctx = b->ctx;
+    const int32_t x0 = win.x0, y0 = win.y0, w = win.w, h = win.h;
+    if (!(b->flags & RRT_FLAG_DUBINS))
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use rrt_batch_cost_field)", who);
+    if (const int rc = refuse_goals_call(who, b, q, 0, "poses")) return rc;
+    if (w < 1 || h < 1) return fail(ctx, RRT_E_ARG, "%s: a window of %d x %d cells", who, w, h);
+    if (x0 < 0 || y0 < 0 || x0 > ctx->W - w || y0 > ctx->H - h)
+        return fail(ctx, RRT_E_ARG, "%s: the window (%d, %d) + %d x %d is not inside the %dx%d grid", who, x0, y0, w, h, ctx->W, ctx->H);
+    if (!vertex || !cost || !heading_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    const QDesc &d = b->h_desc[(size_t)q];
+    if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
+    if (heading < -1 || heading >= d.nh)
+        return fail(ctx, RRT_E_ARG, "%s: heading %d, query %d has headings [0, %d) (-1: any heading)", who, heading, q, d.nh);
+    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    if (d.j > POSE_FIELD_MAX_J)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d has %d vertices, at most %d (a pair of heading and vertex is one 32-bit key)", who, q, d.j, POSE_FIELD_MAX_J);
+    const int64_t m = (int64_t)w * h;  // (inside a grid of at most 4096 x 4096: 2^24 cells)
+    StageTimer &time = b->pose_field_time;
+    time.ran = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, b->goal_vertex.reserve(m, (size_t)m * sizeof(int32_t)));
+    HIPCHK(ctx, b->goal_cost.reserve(m, (size_t)m * sizeof(double)));
+    HIPCHK(ctx, b->pose_field_heading.reserve(m, (size_t)m * sizeof(int32_t)));
+    HIPCHK(ctx, b->field_tmp.reserve<FieldScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
+    HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
+    HIPCHK(ctx, time.create(5));
+    const FieldScratch fx = b->field_tmp.carve<FieldScratch>((size_t)RELAX_MAX_CELLS);
+    const PoseRelaxScratch px = b->pose_relax_tmp.carve<PoseRelaxScratch>();  // (its item_h alone)
+    PoseFieldView pv{};
+    RelaxView &xv = pv.xv;
+    xv.og = ctx->og;
+    xv.H = ctx->H;
+    relax_cells((int64_t)1 << (2 * FIELD_MIN_SHIFT), ctx->W, ctx->H, xv);
+    xv.cell_of = fx.cell_of;
+    xv.cell_start = fx.cell_start;
+    xv.cell_fill = fx.cell_fill;
+    xv.items = fx.items;
+    xv.item_xy = fx.item_xy;
+    xv.item_cost = fx.item_cost;
+    xv.cell_min = fx.cell_min;
+    xv.stats = fx.stats;
+    xv.err = fx.err;
+    pv.W = ctx->W;
+    pv.nh = d.nh;
+    pv.rho = d.rho;
+    pv.item_h = px.item_h;
+    pv.x0 = x0;
+    pv.y0 = y0;
+    pv.w = w;
+    pv.h = h;
+    pv.heading_lo = heading < 0 ? 0 : heading;
+    pv.heading_hi = heading < 0 ? d.nh : heading + 1;
+    pv.run = (int32_t)std::clamp<int64_t>(m / POSE_FIELD_WAVES, 1, POSE_FIELD_RUN);  // (a small window: short runs, so that every CU has cells)
+    pv.vertex = b->goal_vertex.as<int32_t>();
+    pv.cost = b->goal_cost.as<double>();
+    pv.heading_out = b->pose_field_heading.as<int32_t>();
+    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
+    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, POSE_FIELD_STATS * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.err, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_start, 0, (cells + 1) * sizeof(int32_t), ctx->stream));  // (a tree without a vertex launches no bucket kernel)
+    HIPCHK(ctx, hipMemsetAsync(xv.cell_min, 0xff, cells * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, time.mark(0, ctx->stream));
+    hipError_t marked = hipSuccess;
+    decide_over(b, q, pv.vertex, (int32_t)m, [&](const uint32_t *nodes, const double *vcost, const uint8_t *headings, int32_t j) {
+        xv.nodes = nodes;
+        xv.vcost = vcost;
+        xv.j = j;
+        pv.heading = headings;
+        if (j > 0) {
+            fill_buckets(ctx, xv, rrt_relax_cell_kernel, xv);
+            hipLaunchKernelGGL(rrt_pose_field_item_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, pv);
+        }
+        marked = time.mark(1, ctx->stream);
+        const int64_t runs = (int64_t)w * ((h + pv.run - 1) / pv.run);
+        hipLaunchKernelGGL(rrt_pose_field_kernel, dim3(std::clamp<unsigned>(wgs(runs, POSE_FIELD_TPB / 64), 1, POSE_FIELD_MAX_WG)), dim3(POSE_FIELD_TPB), 0,
+                           ctx->stream, pv);
+        if (marked == hipSuccess) marked = time.mark(2, ctx->stream);
+    });
+    HIPCHK(ctx, marked);
+    HIPCHK(ctx, time.mark(3, ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    unsigned long long stats[POSE_FIELD_STATS] = {0, 0, 0, 0};
+    int32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(vertex, pv.vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cost, pv.cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(heading_out, pv.heading_out, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&err, xv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, time.mark(4, ctx->stream));
+    HIPCHK(ctx, wait_stream_spin(ctx->stream));
+    if (err)
+        return fail(ctx, RRT_E_HIP, "%s: a vertex of query %d on the device lies outside the buckets of the %dx%d grid, or its heading outside [0, %d)", who, q, ctx->W,
+                    ctx->H, d.nh);
+    for (int k = 0; k < POSE_FIELD_STATS; ++k) b->pose_field_stats[k] = (int64_t)stats[k];
+    time.ran = 4;
+    return RRT_OK;
+}
+
+extern "C" int rrt_batch_pose_field(rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t heading, int32_t *vertex, double *cost,
+                                    int32_t *heading_out) {
+    return b ? pose_field("rrt_batch_pose_field", b, q, {x0, y0, w, h}, heading, vertex, cost, heading_out) : fail(nullptr, RRT_E_ARG, "rrt_batch_pose_field: NULL");
+}
+
+extern "C" int rrt_plan_pose_field(rrt_ctx *ctx, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t heading, int32_t *vertex, double *cost, int32_t *heading_out) {
+    rrt_batch *s = plan_batch(ctx, "rrt_plan_pose_field", NO_PLAN_NO_TREE);
+    return s ? pose_field("rrt_plan_pose_field", s, 0, {x0, y0, w, h}, heading, vertex, cost, heading_out) : RRT_E_ARG;
+}
+
 // ---- the reports: the kernel times in ms of the stages (_ms) and the counters (_stats) of the last successful call of a family ----
 // One row per family.  A family that is a seed call answers while it is the batch's last seed call (last_seed); the others answer
 // while their timer says that stages ran.  A stage that did not run reads 0.
@@ -1773,9 +1889,12 @@ static const Report POSE_ROUTES{&rrt_batch::pose_route_time, 4, false, nullptr, 
 // ms[0, 5): the decision, depth and scan, rows + shortcuts + scan + pack, legs + lengths (+ the scan of the point counts), the points
 static const Report POSE_SHORTCUTS{&rrt_batch::pose_cut_time, 5, false, nullptr, SeedKind::none, nullptr,
                                    "no rrt_batch_pose_shortcuts with a pose on this batch yet, or its last one failed", nullptr};
-// ms[0, 4): buckets, decide, remap, read-back
+// ms[0, 4): buckets, decide, remap, read-back (both fields)
 static const Report COST_FIELD{&rrt_batch::field_time, 4, false, &rrt_batch::field_stats, SeedKind::none, nullptr,
                                "no rrt_batch_cost_field on this batch yet, or its last one failed", nullptr};
+
+static const Report POSE_FIELD{&rrt_batch::pose_field_time, 4, false, &rrt_batch::pose_field_stats, SeedKind::none, nullptr,
+                               "no rrt_batch_pose_field on this batch yet, or its last one failed", nullptr};
 
 static int refuse_report(const char *who, const Report &r, rrt_batch *b) {
     if (r.kind == SeedKind::none ? (b->*r.time).ran != 0 : b->last_seed == r.kind) return RRT_OK;
@@ -1840,3 +1959,7 @@ extern "C" int rrt_batch_cost_field_ms(rrt_batch *b, float ms[4]) { return repor
 extern "C" int rrt_plan_cost_field_ms(rrt_ctx *ctx, float ms[4]) { return plan_report("rrt_plan_cost_field_ms", ctx, rrt_batch_cost_field_ms, ms); }
 extern "C" int rrt_batch_cost_field_stats(rrt_batch *b, int64_t out[4]) { return report_stats("rrt_batch_cost_field_stats", COST_FIELD, b, out); }
 extern "C" int rrt_plan_cost_field_stats(rrt_ctx *ctx, int64_t out[4]) { return plan_report("rrt_plan_cost_field_stats", ctx, rrt_batch_cost_field_stats, out); }
+extern "C" int rrt_batch_pose_field_ms(rrt_batch *b, float ms[4]) { return report_ms("rrt_batch_pose_field_ms", POSE_FIELD, b, ms, 4); }
+extern "C" int rrt_plan_pose_field_ms(rrt_ctx *ctx, float ms[4]) { return plan_report("rrt_plan_pose_field_ms", ctx, rrt_batch_pose_field_ms, ms); }
+extern "C" int rrt_batch_pose_field_stats(rrt_batch *b, int64_t out[4]) { return report_stats("rrt_batch_pose_field_stats", POSE_FIELD, b, out); }
+extern "C" int rrt_plan_pose_field_stats(rrt_ctx *ctx, int64_t out[4]) { return plan_report("rrt_plan_pose_field_stats", ctx, rrt_batch_pose_field_stats, out); }
