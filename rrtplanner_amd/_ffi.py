@@ -212,6 +212,29 @@ def lib():
     return _lib
 
 
+def _side_binding(prototypes):
+    """For a module whose symbols stay outside SYMBOLS (moving, field, posefield): its (_lib, _tree_of).  _lib() is lib() with
+    `prototypes` declared on it, once per library; a library without them is an error.  _tree_of(handle, *q) is the _Tree of a Batch
+    (with its query, or without one for the reports) or a Context, with the prototypes declared."""
+    bound = None
+
+    def _lib():
+        nonlocal bound
+        L = lib()
+        if bound is not L:
+            for name, argtypes in prototypes.items():
+                fn = getattr(L, name)
+                fn.argtypes, fn.restype = argtypes, C.c_int
+            bound = L
+        return L
+
+    def _tree_of(handle, *q):
+        _lib()
+        return handle._tree(*q)
+
+    return _lib, _tree_of
+
+
 def _check(ctx_handle, rc, ok=(RRT_OK,)):
     if rc in ok:
         return rc

@@ -7,7 +7,7 @@
 //                         reroot_poses (rrt_pose_reroot.h).  Each replaces a query's tree and re-arms it: one record says which call it is
 //                         (SeedCall), one place starts replacing the query (start_replacing), one arms it and makes the call the batch's last
 //                         (seed_and_arm)
-//   routes and the fields routes (rrt_routes.h), pose_routes, pose_shortcuts (rrt_pose_routes.h), cost_field (rrt_field.h), pose_field (rrt_pose_field.h)
+//   routes and the fields routes (rrt_routes.h), pose_routes, pose_shortcuts (rrt_pose_routes.h), cost_field (rrt_field.h), pose_field (rrt_pose_field.h; FieldCall)
 //   the reports           every _ms and _stats call: one table row per family (Report), one reader for the times and one for the counters
 #include "rrt_engine.h"
 #include "rrt_hip_field.h"  // rrt_batch_cost_field and its forms: declared beside rrt_hip.h, not in it
@@ -39,6 +39,30 @@ static int refuse_grid(const char *who, rrt_batch *b, int32_t q, const char *how
     if (so && (b->ran_gen[(size_t)q] != ctx->grid_gen || b->ran_og[(size_t)q] != ctx->og))
         return fail(ctx, RRT_E_ARG, "%s: the context's grid was replaced since query %d ran (grid generation %llu then, %llu now)%s", who, q,
                     (unsigned long long)b->ran_gen[(size_t)q], (unsigned long long)ctx->grid_gen, so);
+    return RRT_OK;
+}
+
+// What the descriptor of a finished query reports, held against what the batch can hold before anything is sized by it: the vertices,
+// and of a Dubins query (the caller says which) the turning radius and the headings.
+static int refuse_vertex_count(const char *who, rrt_batch *b, int32_t q) {
+    const int32_t j = b->h_desc[(size_t)q].j;
+    return j < 0 || j > b->n_cap ? fail(b->ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, j, b->n_cap) : RRT_OK;
+}
+
+static int refuse_pose_desc(const char *who, rrt_batch *b, int32_t q) {
+    const QDesc &d = b->h_desc[(size_t)q];
+    return d.nh < 1 || d.nh > 256 || !(d.rho > 0.0) ? fail(b->ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh) : RRT_OK;
+}
+
+// The window of a field call: its size, then its place inside the context's grid
+struct FieldWindow {
+    int32_t x0, y0, w, h;
+};
+
+static int refuse_window(const char *who, rrt_ctx *ctx, const FieldWindow &win) {
+    if (win.w < 1 || win.h < 1) return fail(ctx, RRT_E_ARG, "%s: a window of %d x %d cells", who, win.w, win.h);
+    if (win.x0 < 0 || win.y0 < 0 || win.x0 > ctx->W - win.w || win.y0 > ctx->H - win.h)
+        return fail(ctx, RRT_E_ARG, "%s: the window (%d, %d) + %d x %d is not inside the %dx%d grid", who, win.x0, win.y0, win.w, win.h, ctx->W, ctx->H);
     return RRT_OK;
 }
 
@@ -183,12 +207,11 @@ static int goals_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
     if (b->flags & RRT_FLAG_DUBINS)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (an edge to a goal is a Dubins word to a goal pose; these kernels price straight lines)", who);
     if (const int rc = refuse_goals_call(who, b, q, m, "goals")) return rc;
-    const QDesc &d = b->h_desc[(size_t)q];
     if (const int rc = stage_cells(who, b, q, "goal", goals_xy, m, 0)) return rc;
     if (m == 0) return RRT_OK;
     int slabs = 0;
     HIPCHK(ctx, goal_scratch(b, m, slabs));
-    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    if (const int rc = refuse_vertex_count(who, b, q)) return rc;
     GoalsView gv{};
     gv.og = ctx->og;
     gv.H = ctx->H;
@@ -238,9 +261,9 @@ static int poses_decide(const char *who, rrt_batch *b, int32_t q, const int32_t 
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use %s)", who, use);
     if (const int rc = refuse_goals_call(who, b, q, m, "goal poses")) return rc;
     const QDesc &d = b->h_desc[(size_t)q];
-    if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
+    if (const int rc = refuse_pose_desc(who, b, q)) return rc;
     if (const int rc = stage_cells(who, b, q, "goal", poses_xyh, m, d.nh)) return rc;
-    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    if (const int rc = refuse_vertex_count(who, b, q)) return rc;
     b->pose_last_m = m == 0 ? 0 : -1;  // (-1 until this call has succeeded: the counters are being rewritten)
     if (m == 0) return RRT_OK;
     int slabs = 0;
@@ -330,8 +353,8 @@ static int keep_tree(const char *who, rrt_batch *b, int32_t q, int32_t *n_alive,
     if (const int rc = refuse_grid(who, b, q, "has another shape than the batch was created for", nullptr)) return rc;
     const QDesc &d = b->h_desc[(size_t)q];
     const int j = d.j;
-    if (j < 0 || j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, j, b->n_cap);
-    if (poses && (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0))) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
+    if (const int rc = refuse_vertex_count(who, b, q)) return rc;
+    if (const int rc = poses ? refuse_pose_desc(who, b, q) : RRT_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     drop_keep_views(b, q);
     StageTimer &time = b->keep_time;
@@ -491,7 +514,7 @@ static int refuse_grow(const SeedCall &c, const char *dubins, int &j_in, const c
                                    poses ? " and the tree was not kept on it (rrt_batch_keep_pose_tree)" : " and the tree was not kept on it (rrt_batch_keep_tree)"))
         return rc;
     if (m < 0) return fail(ctx, RRT_E_ARG, "%s: m=%d", who, m);
-    if (poses && (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0))) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
+    if (const int rc = poses ? refuse_pose_desc(who, b, q) : RRT_OK) return rc;
     const int j_old = d.j, own_n = d.n;
     if (j_old < 1 || j_old > b->n_cap || own_n < 1 || own_n > b->n_cap)
         return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices of %d, capacity %d", who, q, j_old, own_n, b->n_cap);
@@ -890,22 +913,29 @@ static void relax_cells(int64_t R, int W, int H, RelaxView &xv) {
     xv.ncy = across(H);
 }
 
+// The grid of a RelaxView with the buckets for the threshold R, and what the bucket kernels and the counters work in: the arrays that
+// a RelaxScratch (the relax calls) and a FieldScratch (the field calls) both have.
+template <typename Scratch>
+static void bucket_view(rrt_ctx *ctx, RelaxView &xv, int64_t R, const Scratch &s) {
+    xv.og = ctx->og;
+    xv.H = ctx->H;
+    relax_cells(R, ctx->W, ctx->H, xv);
+    xv.cell_of = s.cell_of;
+    xv.cell_start = s.cell_start;
+    xv.cell_fill = s.cell_fill;
+    xv.items = s.items;
+    xv.item_xy = s.item_xy;
+    xv.stats = s.stats;
+}
+
 // What batch_relax and batch_reroot_poses share of a RelaxView: the grid, the threshold R with its buckets (cells for max(R, 1): R = 0
 // has no near pair, and one cell edge serves), and the arrays of the two scratch buffers.  nodes, parent, vcost and j are the call's.
 static void relax_view(rrt_ctx *ctx, RelaxView &xv, int64_t R, const RelaxScratch &rx, const RerootScratch &tmp) {
-    xv.og = ctx->og;
-    xv.H = ctx->H;
+    bucket_view(ctx, xv, std::max<int64_t>(R, 1), rx);
     xv.R = R;
-    relax_cells(std::max<int64_t>(R, 1), ctx->W, ctx->H, xv);
-    xv.cell_of = rx.cell_of;
-    xv.cell_start = rx.cell_start;
-    xv.cell_fill = rx.cell_fill;
-    xv.items = rx.items;
-    xv.item_xy = rx.item_xy;
     xv.pos_of = rx.pos_of;
     xv.cost = rx.cost;
     xv.new_parent = tmp.new_parent;
-    xv.stats = rx.stats;
     xv.err = tmp.head + REROOT_ERR;
 }
 
@@ -1640,74 +1670,85 @@ extern "C" int rrt_plan_pose_routes_points(rrt_ctx *ctx, double *xy, int64_t poi
     return s ? batch_pose_routes_points("rrt_plan_pose_routes_points", s, xy, points) : RRT_E_ARG;
 }
 
-// ---- the cost-to-come field: every cell of a window of the map against a finished tree (rrt_field.h) ----
-// connect_goals for every cell of the window, without the cells as goals: the vertices of the dense input (decide_over: the tree, or its
-// kept view) are bucketed once by the relax calls' bucket kernels (relax_cells gives the edge: FIELD_MIN_SHIFT, doubled until the cells
-// fit), and rrt_field_kernel decides every cell from the buckets whose lower bound can still beat what the cell has.  The answers go
-// through goal_vertex / goal_cost, which the goals calls share, and are copied out in the window's own (w, h) order.
-struct FieldWindow {
-    int32_t x0, y0, w, h;
+// ---- the field calls: every cell of a window of the map against a finished tree (rrt_field.h, rrt_pose_field.h) ----
+// connect_goals / connect_poses for every cell of the window, without the cells as goals: the vertices of the dense input (decide_over:
+// the tree, or its kept view) are bucketed once by the relax calls' bucket kernels (relax_cells gives the edge: FIELD_MIN_SHIFT, doubled
+// until the cells fit), and the call's kernel decides every cell from the buckets whose lower bound can still beat what the cell has.
+// The answers go through goal_vertex / goal_cost, which the goals calls share, and are copied out in the window's own (w, h) order.
+static_assert(FIELD_STATS == 4 && POSE_FIELD_STATS == 4, "the field calls clear, read back and report four counters, whichever kernel counted them");
+
+// One field call, as its entry point fills it in once its refusals have passed: field_buckets and run_field take it.
+struct FieldCall {
+    rrt_batch *b;
+    int32_t q;
+    FieldWindow win;
+    StageTimer *time;  // the call's own timer ...
+    int64_t *stats;    // ... and where its four counters go
+    struct {
+        void *host;  // (nullptr: no such output)
+        DevBuf *dev;
+        size_t each;
+    } out[3];  // what is read back, an entry per cell of the window each: vertex, cost, and of a pose call the arrival heading
+    int64_t cells() const { return (int64_t)win.w * win.h; }  // (inside a grid of at most 4096 x 4096: 2^24 cells)
 };
 
-static int cost_field(const char *who, rrt_batch *b, int32_t q, const FieldWindow &win, int32_t *vertex, double *cost) {
+// From here on the last reports of the call's family are gone.  Room for the outputs and for the buckets (a FieldScratch in field_tmp), and
+// what both kernel views have filled in: the RelaxView from the scratch, the window and the answers.
+template <typename View>
+static int field_buckets(const FieldCall &c, View &v) {
+    rrt_batch *b = c.b;
     rrt_ctx *ctx = b->ctx;
-    const int32_t x0 = win.x0, y0 = win.y0, w = win.w, h = win.h;
-    if (b->flags & RRT_FLAG_DUBINS)
-        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its goal is a pose, and there is no field of poses here; these kernels price straight lines to cells)", who);
-    if (const int rc = refuse_goals_call(who, b, q, 0, "goals")) return rc;
-    if (w < 1 || h < 1) return fail(ctx, RRT_E_ARG, "%s: a window of %d x %d cells", who, w, h);
-    if (x0 < 0 || y0 < 0 || x0 > ctx->W - w || y0 > ctx->H - h)
-        return fail(ctx, RRT_E_ARG, "%s: the window (%d, %d) + %d x %d is not inside the %dx%d grid", who, x0, y0, w, h, ctx->W, ctx->H);
-    if (!vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
-    const QDesc &d = b->h_desc[(size_t)q];
-    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
-    const int64_t m = (int64_t)w * h;  // (inside a grid of at most 4096 x 4096: 2^24 cells)
-    StageTimer &time = b->field_time;
-    time.ran = 0;
+    c.time->ran = 0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, b->goal_vertex.reserve(m, (size_t)m * sizeof(int32_t)));
-    HIPCHK(ctx, b->goal_cost.reserve(m, (size_t)m * sizeof(double)));
+    for (const auto &o : c.out)
+        if (o.host) HIPCHK(ctx, o.dev->reserve(c.cells(), (size_t)c.cells() * o.each));
     HIPCHK(ctx, b->field_tmp.reserve<FieldScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
-    HIPCHK(ctx, time.create(5));
     const FieldScratch fx = b->field_tmp.carve<FieldScratch>((size_t)RELAX_MAX_CELLS);
-    FieldView fv{};
-    RelaxView &xv = fv.xv;
-    xv.og = ctx->og;
-    xv.H = ctx->H;
-    relax_cells((int64_t)1 << (2 * FIELD_MIN_SHIFT), ctx->W, ctx->H, xv);
-    xv.cell_of = fx.cell_of;
-    xv.cell_start = fx.cell_start;
-    xv.cell_fill = fx.cell_fill;
-    xv.items = fx.items;
-    xv.item_xy = fx.item_xy;
-    xv.item_cost = fx.item_cost;
-    xv.cell_min = fx.cell_min;
-    xv.stats = fx.stats;
-    xv.err = fx.err;
-    fv.W = ctx->W;
-    fv.x0 = x0;
-    fv.y0 = y0;
-    fv.w = w;
-    fv.h = h;
-    fv.vertex = b->goal_vertex.as<int32_t>();
-    fv.cost = b->goal_cost.as<double>();
+    bucket_view(ctx, v.xv, (int64_t)1 << (2 * FIELD_MIN_SHIFT), fx);
+    v.xv.item_cost = fx.item_cost;
+    v.xv.cell_min = fx.cell_min;
+    v.xv.err = fx.err;
+    v.W = ctx->W;
+    v.x0 = c.win.x0;
+    v.y0 = c.win.y0;
+    v.w = c.win.w;
+    v.h = c.win.h;
+    v.vertex = b->goal_vertex.as<int32_t>();
+    v.cost = b->goal_cost.as<double>();
+    return RRT_OK;
+}
+
+static int clear_field_buckets(rrt_ctx *ctx, const RelaxView &xv) {
     const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
     HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, FIELD_STATS * sizeof(unsigned long long), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(xv.err, 0, sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(xv.cell_start, 0, (cells + 1) * sizeof(int32_t), ctx->stream));  // (a tree without a vertex launches no bucket kernel)
     HIPCHK(ctx, hipMemsetAsync(xv.cell_min, 0xff, cells * sizeof(unsigned long long), ctx->stream));
+    return RRT_OK;
+}
+
+// The four stages of a field call, every reserve behind it: buckets, decide, remap, read-back.  v: the view the call's kernels take; the
+// tree goes into it here.  items(heading, j): behind the buckets, what else the call keeps per item; decide(): its kernel over the window.
+// FIELD_VERTEX_LOST: the device raised err; the caller says what that means for its kernels, and no reports are left, as after any failure.
+constexpr int FIELD_VERTEX_LOST = 1 << 30;  // (no RRT_ code, and never returned to a caller of the library)
+template <typename View, typename Items, typename Decide>
+static int run_field(const FieldCall &c, View &v, Items items, Decide decide) {
+    rrt_ctx *ctx = c.b->ctx;
+    StageTimer &time = *c.time;
+    RelaxView &xv = v.xv;
+    HIPCHK(ctx, time.create(5));
+    if (const int rc = clear_field_buckets(ctx, xv)) return rc;
     HIPCHK(ctx, time.mark(0, ctx->stream));
     hipError_t marked = hipSuccess;
-    decide_over(b, q, fv.vertex, (int32_t)m, [&](const uint32_t *nodes, const double *vcost, const uint8_t *, int32_t j) {
+    decide_over(c.b, c.q, v.vertex, (int32_t)c.cells(), [&](const uint32_t *nodes, const double *vcost, const uint8_t *heading, int32_t j) {
         xv.nodes = nodes;
         xv.vcost = vcost;
         xv.j = j;
         if (j > 0) fill_buckets(ctx, xv, rrt_relax_cell_kernel, xv);
+        items(heading, j);
         marked = time.mark(1, ctx->stream);
-        const int64_t runs = (int64_t)w * ((h + FIELD_RUN - 1) / FIELD_RUN);
-        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_field_large_kernel : rrt_field_kernel,
-                           dim3(std::clamp<unsigned>(wgs(runs, FIELD_TPB / 64), 1, FIELD_MAX_WG)), dim3(FIELD_TPB), 0, ctx->stream, fv);
+        decide();
         if (marked == hipSuccess) marked = time.mark(2, ctx->stream);
     });
     HIPCHK(ctx, marked);
@@ -1715,16 +1756,37 @@ static int cost_field(const char *who, rrt_batch *b, int32_t q, const FieldWindo
     HIPCHK(ctx, hipGetLastError());
     unsigned long long stats[FIELD_STATS] = {0, 0, 0, 0};
     int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(vertex, fv.vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cost, fv.cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    for (const auto &o : c.out)
+        if (o.host) HIPCHK(ctx, hipMemcpyAsync(o.host, o.dev->p, (size_t)c.cells() * o.each, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&err, xv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, time.mark(4, ctx->stream));
     HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (err) return fail(ctx, RRT_E_HIP, "%s: a vertex of query %d on the device lies outside the buckets of the %dx%d grid", who, q, ctx->W, ctx->H);
-    for (int k = 0; k < FIELD_STATS; ++k) b->field_stats[k] = (int64_t)stats[k];
+    if (err) return FIELD_VERTEX_LOST;
+    for (int k = 0; k < FIELD_STATS; ++k) c.stats[k] = (int64_t)stats[k];
     time.ran = 4;
     return RRT_OK;
+}
+
+// the cost-to-come field (rrt_field.h): rrt_field_kernel, on a large grid rrt_field_large_kernel, prices straight lines to cells
+static int cost_field(const char *who, rrt_batch *b, int32_t q, const FieldWindow &win, int32_t *vertex, double *cost) {
+    rrt_ctx *ctx = b->ctx;
+    if (b->flags & RRT_FLAG_DUBINS)
+        return fail(ctx, RRT_E_UNSUPPORTED, "%s: a Dubins batch (its goal is a pose, and there is no field of poses here; these kernels price straight lines to cells)", who);
+    if (const int rc = refuse_goals_call(who, b, q, 0, "goals")) return rc;
+    if (const int rc = refuse_window(who, ctx, win)) return rc;
+    if (!vertex || !cost) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (const int rc = refuse_vertex_count(who, b, q)) return rc;
+    const FieldCall c{b, q, win, &b->field_time, b->field_stats, {{vertex, &b->goal_vertex, sizeof(int32_t)}, {cost, &b->goal_cost, sizeof(double)}, {}}};
+    FieldView fv{};
+    if (const int rc = field_buckets(c, fv)) return rc;
+    const int rc = run_field(c, fv, [](const uint8_t *, int32_t) {}, [&] {
+        const int64_t runs = (int64_t)win.w * ((win.h + FIELD_RUN - 1) / FIELD_RUN);
+        hipLaunchKernelGGL((b->flags & RRT_FLAG_LARGE_GRID) ? rrt_field_large_kernel : rrt_field_kernel,
+                           dim3(std::clamp<unsigned>(wgs(runs, FIELD_TPB / 64), 1, FIELD_MAX_WG)), dim3(FIELD_TPB), 0, ctx->stream, fv);
+    });
+    if (rc != FIELD_VERTEX_LOST) return rc;
+    return fail(ctx, RRT_E_HIP, "%s: a vertex of query %d on the device lies outside the buckets of the %dx%d grid", who, q, ctx->W, ctx->H);
 }
 
 extern "C" int rrt_batch_cost_field(rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t *vertex, double *cost) {
@@ -1736,109 +1798,47 @@ extern "C" int rrt_plan_cost_field(rrt_ctx *ctx, int32_t x0, int32_t y0, int32_t
     return s ? cost_field("rrt_plan_cost_field", s, 0, {x0, y0, w, h}, vertex, cost) : RRT_E_ARG;
 }
 
-// ---- the pose cost field: every cell of a window of the map against a finished Dubins tree (rrt_pose_field.h) ----
-// connect_poses for every cell of the window, at one arrival heading or at the best of all of them (heading -1), without the cells as
-// goal poses: cost_field's buckets (a FieldScratch in field_tmp, which no other call of a Dubins batch uses), the heading byte of every
-// item beside them (PoseRelaxScratch's item_h: the relax calls fill it anew each time), and rrt_pose_field_kernel.  Vertex and cost go through goal_vertex / goal_cost, the arrival
-// heading through pose_field_heading; all three are copied out in the window's own (w, h) order.
+// The pose cost field (rrt_pose_field.h), at one arrival heading or at the best of all (heading -1): cost_field's buckets (field_tmp serves no
+// other call of a Dubins batch), the heading byte of every item beside them (PoseRelaxScratch's item_h: the relax calls fill it anew each time).
 static int pose_field(const char *who, rrt_batch *b, int32_t q, const FieldWindow &win, int32_t heading, int32_t *vertex, double *cost, int32_t *heading_out) {
     rrt_ctx *ctx = b->ctx;
-    const int32_t x0 = win.x0, y0 = win.y0, w = win.w, h = win.h;
     if (!(b->flags & RRT_FLAG_DUBINS))
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: not a Dubins batch (its goals are cells and its edges straight lines: use rrt_batch_cost_field)", who);
     if (const int rc = refuse_goals_call(who, b, q, 0, "poses")) return rc;
-    if (w < 1 || h < 1) return fail(ctx, RRT_E_ARG, "%s: a window of %d x %d cells", who, w, h);
-    if (x0 < 0 || y0 < 0 || x0 > ctx->W - w || y0 > ctx->H - h)
-        return fail(ctx, RRT_E_ARG, "%s: the window (%d, %d) + %d x %d is not inside the %dx%d grid", who, x0, y0, w, h, ctx->W, ctx->H);
+    if (const int rc = refuse_window(who, ctx, win)) return rc;
     if (!vertex || !cost || !heading_out) return fail(ctx, RRT_E_ARG, "%s: NULL", who);
+    if (const int rc = refuse_pose_desc(who, b, q)) return rc;
     const QDesc &d = b->h_desc[(size_t)q];
-    if (d.nh < 1 || d.nh > 256 || !(d.rho > 0.0)) return fail(ctx, RRT_E_HIP, "%s: query %d reports rho=%g, nh=%d", who, q, d.rho, d.nh);
     if (heading < -1 || heading >= d.nh)
         return fail(ctx, RRT_E_ARG, "%s: heading %d, query %d has headings [0, %d) (-1: any heading)", who, heading, q, d.nh);
-    if (d.j < 0 || d.j > b->n_cap) return fail(ctx, RRT_E_HIP, "%s: query %d reports %d vertices, capacity %d", who, q, d.j, b->n_cap);
+    if (const int rc = refuse_vertex_count(who, b, q)) return rc;
     if (d.j > POSE_FIELD_MAX_J)
         return fail(ctx, RRT_E_UNSUPPORTED, "%s: query %d has %d vertices, at most %d (a pair of heading and vertex is one 32-bit key)", who, q, d.j, POSE_FIELD_MAX_J);
-    const int64_t m = (int64_t)w * h;  // (inside a grid of at most 4096 x 4096: 2^24 cells)
-    StageTimer &time = b->pose_field_time;
-    time.ran = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, b->goal_vertex.reserve(m, (size_t)m * sizeof(int32_t)));
-    HIPCHK(ctx, b->goal_cost.reserve(m, (size_t)m * sizeof(double)));
-    HIPCHK(ctx, b->pose_field_heading.reserve(m, (size_t)m * sizeof(int32_t)));
-    HIPCHK(ctx, b->field_tmp.reserve<FieldScratch>(b->n_cap, (size_t)RELAX_MAX_CELLS));
-    HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
-    HIPCHK(ctx, time.create(5));
-    const FieldScratch fx = b->field_tmp.carve<FieldScratch>((size_t)RELAX_MAX_CELLS);
-    const PoseRelaxScratch px = b->pose_relax_tmp.carve<PoseRelaxScratch>();  // (its item_h alone)
+    const FieldCall c{b, q, win, &b->pose_field_time, b->pose_field_stats,
+                      {{vertex, &b->goal_vertex, sizeof(int32_t)}, {cost, &b->goal_cost, sizeof(double)}, {heading_out, &b->pose_field_heading, sizeof(int32_t)}}};
     PoseFieldView pv{};
-    RelaxView &xv = pv.xv;
-    xv.og = ctx->og;
-    xv.H = ctx->H;
-    relax_cells((int64_t)1 << (2 * FIELD_MIN_SHIFT), ctx->W, ctx->H, xv);
-    xv.cell_of = fx.cell_of;
-    xv.cell_start = fx.cell_start;
-    xv.cell_fill = fx.cell_fill;
-    xv.items = fx.items;
-    xv.item_xy = fx.item_xy;
-    xv.item_cost = fx.item_cost;
-    xv.cell_min = fx.cell_min;
-    xv.stats = fx.stats;
-    xv.err = fx.err;
-    pv.W = ctx->W;
+    if (const int rc = field_buckets(c, pv)) return rc;
+    HIPCHK(ctx, b->pose_relax_tmp.reserve<PoseRelaxScratch>(b->n_cap));
     pv.nh = d.nh;
     pv.rho = d.rho;
-    pv.item_h = px.item_h;
-    pv.x0 = x0;
-    pv.y0 = y0;
-    pv.w = w;
-    pv.h = h;
+    pv.item_h = b->pose_relax_tmp.carve<PoseRelaxScratch>().item_h;  // (of that scratch, item_h alone)
     pv.heading_lo = heading < 0 ? 0 : heading;
     pv.heading_hi = heading < 0 ? d.nh : heading + 1;
+    const int64_t m = c.cells();
     pv.run = (int32_t)std::clamp<int64_t>(m / POSE_FIELD_WAVES, 1, POSE_FIELD_RUN);  // (a small window: short runs, so that every CU has cells)
-    pv.vertex = b->goal_vertex.as<int32_t>();
-    pv.cost = b->goal_cost.as<double>();
     pv.heading_out = b->pose_field_heading.as<int32_t>();
-    const size_t cells = (size_t)xv.ncx * (size_t)xv.ncy;
-    HIPCHK(ctx, hipMemsetAsync(xv.stats, 0, POSE_FIELD_STATS * sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(xv.err, 0, sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(xv.cell_fill, 0, cells * sizeof(int32_t), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(xv.cell_start, 0, (cells + 1) * sizeof(int32_t), ctx->stream));  // (a tree without a vertex launches no bucket kernel)
-    HIPCHK(ctx, hipMemsetAsync(xv.cell_min, 0xff, cells * sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, time.mark(0, ctx->stream));
-    hipError_t marked = hipSuccess;
-    decide_over(b, q, pv.vertex, (int32_t)m, [&](const uint32_t *nodes, const double *vcost, const uint8_t *headings, int32_t j) {
-        xv.nodes = nodes;
-        xv.vcost = vcost;
-        xv.j = j;
+    auto items = [&](const uint8_t *headings, int32_t j) {
         pv.heading = headings;
-        if (j > 0) {
-            fill_buckets(ctx, xv, rrt_relax_cell_kernel, xv);
-            hipLaunchKernelGGL(rrt_pose_field_item_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, pv);
-        }
-        marked = time.mark(1, ctx->stream);
-        const int64_t runs = (int64_t)w * ((h + pv.run - 1) / pv.run);
+        if (j > 0) hipLaunchKernelGGL(rrt_pose_field_item_kernel, dim3(wgs(j, RELAX_TPB)), dim3(RELAX_TPB), 0, ctx->stream, pv);
+    };
+    const int rc = run_field(c, pv, items, [&] {
+        const int64_t runs = (int64_t)win.w * ((win.h + pv.run - 1) / pv.run);
         hipLaunchKernelGGL(rrt_pose_field_kernel, dim3(std::clamp<unsigned>(wgs(runs, POSE_FIELD_TPB / 64), 1, POSE_FIELD_MAX_WG)), dim3(POSE_FIELD_TPB), 0,
                            ctx->stream, pv);
-        if (marked == hipSuccess) marked = time.mark(2, ctx->stream);
     });
-    HIPCHK(ctx, marked);
-    HIPCHK(ctx, time.mark(3, ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    unsigned long long stats[POSE_FIELD_STATS] = {0, 0, 0, 0};
-    int32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(vertex, pv.vertex, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cost, pv.cost, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(heading_out, pv.heading_out, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(stats, xv.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&err, xv.err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, time.mark(4, ctx->stream));
-    HIPCHK(ctx, wait_stream_spin(ctx->stream));
-    if (err)
-        return fail(ctx, RRT_E_HIP, "%s: a vertex of query %d on the device lies outside the buckets of the %dx%d grid, or its heading outside [0, %d)", who, q, ctx->W,
-                    ctx->H, d.nh);
-    for (int k = 0; k < POSE_FIELD_STATS; ++k) b->pose_field_stats[k] = (int64_t)stats[k];
-    time.ran = 4;
-    return RRT_OK;
+    if (rc != FIELD_VERTEX_LOST) return rc;
+    return fail(ctx, RRT_E_HIP, "%s: a vertex of query %d on the device lies outside the buckets of the %dx%d grid, or its heading outside [0, %d)", who, q, ctx->W,
+                ctx->H, d.nh);
 }
 
 extern "C" int rrt_batch_pose_field(rrt_batch *b, int32_t q, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t heading, int32_t *vertex, double *cost,
@@ -1892,7 +1892,6 @@ static const Report POSE_SHORTCUTS{&rrt_batch::pose_cut_time, 5, false, nullptr,
 // ms[0, 4): buckets, decide, remap, read-back (both fields)
 static const Report COST_FIELD{&rrt_batch::field_time, 4, false, &rrt_batch::field_stats, SeedKind::none, nullptr,
                                "no rrt_batch_cost_field on this batch yet, or its last one failed", nullptr};
-
 static const Report POSE_FIELD{&rrt_batch::pose_field_time, 4, false, &rrt_batch::pose_field_stats, SeedKind::none, nullptr,
                                "no rrt_batch_pose_field on this batch yet, or its last one failed", nullptr};
 

@@ -6,8 +6,8 @@ the tree planned from the goal it is a feedback policy for a robot that may be a
 goal is "any cell of this region".  The vertices are bucketed once per call and a cell looks only at the buckets that can still beat what
 it has found, so a field costs a small fraction of the same cells sent through connect_goals.
 
-The module binds its six symbols itself, on the handle _ffi.lib() returns, as moving.py does: the signature table of _ffi and the
-methods of Context, Batch and the planner classes are a recorded surface.
+The module binds its six symbols itself, on the handle _ffi.lib() returns, through the binder moving.py and posefield.py use too
+(_ffi._side_binding): the signature table of _ffi and the methods of Context, Batch and the planner classes are a recorded surface.
 
   cost_field(planner, window=None)               the field of the tree of planner's last plan(); window (x0, y0, w, h), None: the grid
   batch_cost_field(batch, q, window)             rrt_batch_cost_field
@@ -30,25 +30,7 @@ _PROTOTYPES = {
     "rrt_batch_cost_field_stats": [_vp, _P(_i64 * 4)],
     "rrt_plan_cost_field_stats": [_vp, _P(_i64 * 4)],
 }
-_bound = None
-
-
-def _lib():
-    """_ffi.lib() with the prototypes of this module's symbols declared on it; a library without them is an error"""
-    global _bound
-    L = _ffi.lib()
-    if _bound is not L:
-        for name, argtypes in _PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.argtypes, fn.restype = argtypes, C.c_int
-        _bound = L
-    return L
-
-
-def _tree_of(handle, *q):
-    """the _ffi._Tree of a Batch (with its query, or without one for the reports) or a Context"""
-    _lib()
-    return handle._tree(*q)
+_lib, _tree_of = _ffi._side_binding(_PROTOTYPES)
 
 
 def _window(window):
@@ -60,14 +42,26 @@ def _window(window):
     return x0, y0, w, h
 
 
-def _field(tree, window):
-    """the call on a _Tree: (vertex int32 (w, h), cost float64 (w, h)); the arrays are sized by the window asked for, which the library
-    checks against its grid before it writes any"""
+def _planner_window(who, planner, window):
+    """the window of a planner-level field call, `who`, as four ints: None is the whole grid, anything else has to lie inside it"""
+    W, H = np.asarray(planner.og).shape
+    x0, y0, w, h = (0, 0, W, H) if window is None else _window(window)
+    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError(f"{who}: the window ({x0}, {y0}) + {w} x {h} does not lie inside the {W}x{H} occupancy grid")
+    return x0, y0, w, h
+
+
+def _answers(window, kinds):
+    """(window as four ints, one (w, h) array per (dtype, fill) of kinds); the arrays are sized by the window asked for, which the
+    library checks against its grid before it writes any"""
     x0, y0, w, h = _window(window)
-    shape = (max(w, 0), max(h, 0))
-    vertex = np.full(shape, -1, dtype=np.int32)
-    cost = np.full(shape, np.inf, dtype=np.float64)
-    tree.call("cost_field", x0, y0, w, h, vertex.ctypes.data, cost.ctypes.data)
+    return (x0, y0, w, h), [np.full((max(w, 0), max(h, 0)), fill, dtype=dtype) for dtype, fill in kinds]
+
+
+def _field(tree, window):
+    """the call on a _Tree: (vertex int32 (w, h), cost float64 (w, h))"""
+    win, (vertex, cost) = _answers(window, ((np.int32, -1), (np.float64, np.inf)))
+    tree.call("cost_field", *win, vertex.ctypes.data, cost.ctypes.data)
     return vertex, cost
 
 
@@ -107,9 +101,6 @@ def cost_field(planner, window=None):
     if hasattr(planner, "n_headings"):
         raise ValueError("cost_field: a Dubins planner's goal is a pose and its edge a Dubins word; there is no field of poses, and the "
                          "field kernel prices straight lines to cells (RRTStandard, RRTStar, RRTStarInformed only)")
-    W, H = np.asarray(planner.og).shape
-    x0, y0, w, h = (0, 0, W, H) if window is None else _window(window)
-    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
-        raise ValueError(f"cost_field: the window ({x0}, {y0}) + {w} x {h} does not lie inside the {W}x{H} occupancy grid")
+    window = _planner_window("cost_field", planner, window)
     planner._keep_guard("cost_field")
-    return context_cost_field(planner._device(), (x0, y0, w, h))
+    return context_cost_field(planner._device(), window)

@@ -6,8 +6,8 @@ shortest-path tree from the new root's pose over the directed graph of the tree'
 what hangs below the new root keeps its old edges, everything else is re-attached by words between poses swept on the current map,
 what cannot be reached is cut, and m new pose samples grow it back.
 
-The module binds its six symbols itself, on the handle _ffi.lib() returns: the signature table of _ffi and the methods of Context,
-Batch and the planner classes are a recorded surface, which a later change moves these calls onto.
+The module binds its six symbols itself, on the handle _ffi.lib() returns, through the binder field.py and posefield.py use too
+(_ffi._side_binding): the signature table of _ffi and the methods of Context, Batch and the planner classes are a recorded surface.
 
   reroot_poses(planner, vertex, r=None, m=0)             the call of RRTDubins / RRTStarDubins
   batch_reroot_poses(batch, q, root, r2, samples=())     rrt_batch_reroot_poses
@@ -28,25 +28,7 @@ _PROTOTYPES = {
     "rrt_batch_reroot_poses_stats": [_vp, _P(_i64 * 4)],
     "rrt_plan_reroot_poses_stats": [_vp, _P(_i64 * 4)],
 }
-_bound = None
-
-
-def _lib():
-    """_ffi.lib() with the prototypes of this module's symbols declared on it; a library without them is an error"""
-    global _bound
-    L = _ffi.lib()
-    if _bound is not L:
-        for name, argtypes in _PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.argtypes, fn.restype = argtypes, C.c_int
-        _bound = L
-    return L
-
-
-def _tree_of(handle):
-    """the _ffi._Tree of a Batch or a Context (without a query)"""
-    _lib()
-    return handle._tree()
+_lib, _tree_of = _ffi._side_binding(_PROTOTYPES)
 
 
 def batch_reroot_poses(batch, q, root, r2, samples=()):

@@ -11,8 +11,8 @@ the field wins at any heading where the cells are reached cheaply, by one to thr
 through connect_poses; for a fixed heading on windows with unreached or deeply hidden cells connect_poses remains the faster call,
 by up to 4.5 times: there the work is sweeps that no bound removes, and the field gives a cell one wavefront.
 
-The module binds its six symbols itself, on the handle _ffi.lib() returns, as field.py and moving.py do: the signature table of _ffi
-and the methods of Context, Batch and the planner classes are a recorded surface.
+The module binds its six symbols itself, on the handle _ffi.lib() returns, through the binder field.py and moving.py use too
+(_ffi._side_binding): the signature table of _ffi and the methods of Context, Batch and the planner classes are a recorded surface.
 
   pose_field(planner, window=None, heading=None)   the field of the tree of planner's last plan(); window (x0, y0, w, h), None: the grid;
                                                    heading None: any arrival heading
@@ -24,7 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .field import _window
+from .field import _answers, _planner_window
 
 POSE_FIELD_STATS = ("cells", "buckets", "words", "sweeps")
 
@@ -37,37 +37,14 @@ _PROTOTYPES = {
     "rrt_batch_pose_field_stats": [_vp, _P(_i64 * 4)],
     "rrt_plan_pose_field_stats": [_vp, _P(_i64 * 4)],
 }
-_bound = None
-
-
-def _lib():
-    """_ffi.lib() with the prototypes of this module's symbols declared on it; a library without them is an error"""
-    global _bound
-    L = _ffi.lib()
-    if _bound is not L:
-        for name, argtypes in _PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.argtypes, fn.restype = argtypes, C.c_int
-        _bound = L
-    return L
-
-
-def _tree_of(handle, *q):
-    """the _ffi._Tree of a Batch (with its query, or without one for the reports) or a Context"""
-    _lib()
-    return handle._tree(*q)
+_lib, _tree_of = _ffi._side_binding(_PROTOTYPES)
 
 
 def _field(tree, window, heading):
-    """the call on a _Tree: (vertex int32 (w, h), cost float64 (w, h), heading int32 (w, h)); the arrays are sized by the window asked
-    for, which the library checks against its grid before it writes any"""
-    x0, y0, w, h = _window(window)
-    shape = (max(w, 0), max(h, 0))
-    vertex = np.full(shape, -1, dtype=np.int32)
-    cost = np.full(shape, np.inf, dtype=np.float64)
-    arrive = np.full(shape, -1, dtype=np.int32)
-    tree.call("pose_field", x0, y0, w, h, int(heading), vertex.ctypes.data, cost.ctypes.data, arrive.ctypes.data)
-    return vertex, cost, arrive
+    """the call on a _Tree: (vertex int32 (w, h), cost float64 (w, h), heading int32 (w, h))"""
+    win, out = _answers(window, ((np.int32, -1), (np.float64, np.inf), (np.int32, -1)))
+    tree.call("pose_field", *win, int(heading), *(a.ctypes.data for a in out))
+    return tuple(out)
 
 
 def batch_pose_field(batch, q, window, heading=-1):
@@ -112,10 +89,7 @@ def pose_field(planner, window=None, heading=None):
     if not hasattr(planner, "n_headings"):
         raise ValueError("pose_field: a straight-line planner's goal is a cell and its edge a line; its field is field.cost_field "
                          "(RRTDubins, RRTStarDubins only)")
-    W, H = np.asarray(planner.og).shape
-    x0, y0, w, h = (0, 0, W, H) if window is None else _window(window)
-    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
-        raise ValueError(f"pose_field: the window ({x0}, {y0}) + {w} x {h} does not lie inside the {W}x{H} occupancy grid")
+    window = _planner_window("pose_field", planner, window)
     nh = int(planner.n_headings)
     try:
         hd = -1 if heading is None else int(heading)
@@ -125,4 +99,4 @@ def pose_field(planner, window=None, heading=None):
     if not ok or hd < -1 or hd >= nh:
         raise ValueError(f"pose_field: heading must be an integer in [0, {nh}), or None (-1) for any heading, got {heading!r}")
     planner._keep_guard("pose_field")
-    return context_pose_field(planner._device(), (x0, y0, w, h), hd)
+    return context_pose_field(planner._device(), window, hd)
